@@ -19,11 +19,18 @@ queries over the ranks).  --config pq / join time BASELINE configs[1] / configs[
 sharded step -- double-buffered asynchronous gather included -- on CPU tensors with a stand-in search, which
 is how the CPU test suite covers this file's N > 1 path.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) builds the index, warms up, times exactly K steps and prints ONE JSON
+line on rank 0: metric, value (queries/s), unit, higher_is_better, dtype, ms_per_step (milliseconds per timed step) and the
+workload; "roofline" and "cpu_baseline" are null.  `--full` adds everything else, as one run: serial and instrumented passes,
+recall@5, the CPU oracle's timing and its bit-for-bit check of the timed region's lists, the host-buffer ABI, the K = 256 / pq /
+join / exact configurations and the one-rank collective child; the line then carries
   "roofline":     the dominant kernel against the HBM roofline + the ceilings that actually bind (LDS gather)
-  "cpu_baseline": the CPU oracle (oracle/, a port of the reference loops) on a bounded sample.
+  "cpu_baseline": the CPU oracle (oracle/, a port of the reference loops) on a bounded sample,
+and the whole record goes to bench_details.json.  `--dump-outputs DIR` writes the lists of the last timed step as DIR/ids.npy
+(float64) and DIR/dist.npy (float32); the corpus, tables and queries are the same in every run with the same arguments.
 """
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -99,7 +106,55 @@ def parse(argv=None):
     ap.add_argument("--reserve-cus", type=int, default=2, help="option reserve_cus of the collective path (CUs every persistent scan leaves free)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only with --dry-run)")
     ap.add_argument("--dry-run", action="store_true", help="CPU tensors + stand-in search: exercises the sharded step / gather only")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: serial and instrumented passes, roofline, recall, CPU oracle baseline and "
+                         "parity, host-buffer ABI child, the other configurations, the one-rank collective child, bench_details.json; "
+                         "without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the lists a caller receives) as DIR/<name>.npy, float32 / float64")
     return ap.parse_args(argv)
+
+
+# Steps of the timed path run between the warm-up and the timed region of a plain run: after the idle period of pinning the index
+# the chip's first ~10 ms of bursts run up to 12 % slower (profiles/r04_burst_ramp.txt).  A --full run reaches the timed region
+# after ~500 steps of side measurements (60-100 ms); a plain run runs 1000 of the timed steps themselves (~0.1 s).
+RAMP_STEPS = 1000
+DUMP_MAX_BYTES = 64 << 20
+
+
+@contextlib.contextmanager
+def same_inputs():
+    """Index building on the GPU with torch's deterministic algorithms: index_add_ (k-means sums) and index_put_ with repeated
+    indices (the corpus' duplicate rows) otherwise use atomics, and the tables' bits could differ from run to run.  With the same
+    arguments every run then searches the same corpus, tables and queries."""
+    prev, prev_warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        yield
+    finally:
+        torch.use_deterministic_algorithms(prev, warn_only=prev_warn)
+
+
+def result_arrays(ids, dist):
+    """The lists of one step as --dump-outputs writes them: ids as float64 (exact for int32), distances as float32."""
+    ids = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+    dist = dist.cpu().numpy() if isinstance(dist, torch.Tensor) else np.asarray(dist)
+    if dist.dtype != np.float32:
+        dist = dist.view(np.float32)   # (the [2][q][k] int32 buffers hold the distances' bits)
+    return {"ids": ids.astype(np.float64), "dist": dist.astype(np.float32)}
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy for every array; over DUMP_MAX_BYTES in all, a fixed seeded sample of the rows (queries), listed in rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        n = next(iter(arrays.values())).shape[0]
+        keep = max(1, int(n * (DUMP_MAX_BYTES // 2) / total))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = dict({k: v[rows] for k, v in arrays.items()}, rows=rows.astype(np.float64))
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(v))
 
 
 def _free_port():
@@ -216,6 +271,9 @@ def run_dry(a, rank, world):
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if a.dump_outputs:
+            last = pg.res[(pg.steps - 1) % pg.depth]
+            dump_outputs(a.dump_outputs, result_arrays(last[0], last[1]))
         print(json.dumps(headline(out)), flush=True)
     return 0 if ok else 1
 
@@ -390,12 +448,23 @@ def digest(out):
     return d if len(json.dumps(d)) <= DIGEST_MAX_BYTES else None
 
 
-def emit(out, details_name="bench_details.json"):
-    """Details into bench_details.json (once), a digest line, then the headline as the LAST stdout line."""
+def emit(out, details_name="bench_details.json", full=True):
+    """Details into bench_details.json (once), a digest line, then the headline as the LAST stdout line.  full=False (a plain
+    run): the headline alone."""
     if not isinstance(out, dict):
         print(json.dumps(out), flush=True)
         return
     out.pop("_exact", None)
+    if not full:
+        line = headline(out)
+        line.pop("details", None)
+        try:   # (RCCL's version banner, still in stdio's buffer, must leave before the result line)
+            import ctypes
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        print(json.dumps(line), flush=True)
+        return
     blob = json.dumps(out, indent=1)
     for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
         if os.path.isdir(d):
@@ -419,8 +488,9 @@ def emit(out, details_name="bench_details.json"):
 # exact brute-force kNN (k_nearest_neighbour / knn_in_exact, core_functions.c:67-81): the bench's recall
 # ground truth AND a measured path of its own (other_configs.exact)
 # ---------------------------------------------------------------------------------------------------
-def exact_truth(x, d_qs, k, dev_index, cpu_queries=4, steps=5):
-    """Pins the raw vectors (freddy_gpu_pin_vectors) and returns ([ids [Q][k] per query set], measurement dict)."""
+def exact_truth(x, d_qs, k, dev_index, cpu_queries=4, steps=5, full=True, outputs=None):
+    """Pins the raw vectors (freddy_gpu_pin_vectors) and returns ([ids [Q][k] per query set], measurement dict).  full=False: no
+    CPU oracle leg; outputs (a dict): receives the lists of the last timed call of every batch size under "Q<n>"."""
     from freddy_amd import gpu
     N, d = x.shape
     hx = x.cpu().numpy()
@@ -442,6 +512,8 @@ def exact_truth(x, d_qs, k, dev_index, cpu_queries=4, steps=5):
         for _ in range(reps):
             got_i, got_s = vi.search(hq, k)
         dt = (time.perf_counter() - t0) / reps
+        if outputs is not None:
+            outputs[f"Q{Q}"] = result_arrays(got_i, got_s)
         vi.profile_enable(True)
         for _ in range(3):
             vi.search(hq, k)
@@ -461,6 +533,10 @@ def exact_truth(x, d_qs, k, dev_index, cpu_queries=4, steps=5):
                                         "flops": {"per_call": flops, "achieved_tflops": round(flops / avg_s / 1e12, 3),
                                                   "note": "2*N*d*Q multiply-adds of the similarity chain (separately rounded mul + add on the VALU for "
                                                           "the exact chain; the matrix cores when the filter + refine path is taken)"}})}
+    if not full:
+        info["cpu_baseline"] = None
+        vi.close()
+        return truth, info
     # CPU oracle (port of cosine_similarity_bytea + ORDER BY ... FETCH FIRST k) on a bounded sample, and parity on it
     from oracle.oracle import Oracle
     o = Oracle()
@@ -512,8 +588,9 @@ def run_ivfadc(a, rank, world, dev, dev_index):
     else:
         q_local = Q
     t0 = time.time()
-    x = ib.make_corpus(N, d=300, seed=20260101, device=dev)
-    tab = ib.build_ivf_index(x, C=a.C, m=a.m, K=a.K, train_size=100000, iters=10, seed=2)
+    with same_inputs():
+        x = ib.make_corpus(N, d=300, seed=20260101, device=dev)
+        tab = ib.build_ivf_index(x, C=a.C, m=a.m, K=a.K, train_size=100000, iters=10, seed=2)
     log(rank, f"corpus+index built in {time.time() - t0:.1f}s")
     t0 = time.time()
     index = gpu.IVFIndex(tab["coarse"], tab["codebook"], tab["list_off"], tab["ids"], tab["codes"], device=dev_index)
@@ -537,8 +614,6 @@ def run_ivfadc(a, rank, world, dev, dev_index):
     # inside the library, its own workspace): a batch is a chain of dependent kernels, and the latency-bound ends of
     # the batches overlap with the scans of the others.  --in-flight 1 is the strict sequence.
     a.warmup = max(a.warmup, n_fl)   # (every stream's workspace is allocated by its first search: never inside the timed region)
-    if a.steps < n_fl:
-        raise SystemExit(f"--steps must be at least --in-flight ({n_fl}): every stream's buffer is verified after the timed region")
     # (the streams are created ONCE per process: the K = 256 side configuration runs this function a second time, and four MORE
     #  streams landed on hardware queues the first four already used -- 6.1 instead of 10.4 M queries/s for that side figure)
     streams = bench_streams(a, dev)
@@ -600,33 +675,41 @@ def run_ivfadc(a, rank, world, dev, dev_index):
             # an RCCL kernel must never queue behind 4 x 64 persistent scan workgroups that hold every CU: each scan leaves
             # CUs free (measured with a one-rank group on one GPU: other_configs.collective_1rank, profiles/r06_collective_1rank.txt)
             index.set_option("reserve_cus", a.reserve_cus)
-        # ---- the side measurements FIRST: the same steps strictly one after the other, and the per-kernel durations (HIP
+        # ---- --full: the side measurements FIRST: the same steps strictly one after the other, and the per-kernel durations (HIP
         # events on the launch stream; instrumented re-runs).  They are this very workload, so the timed region below starts
         # on a chip in its steady state: after an idle period (pinning the index is host work) the first ~10 ms of bursts
         # run up to 12 % slower (clocks / power state: tools/burst_trace.py RAMP=1, profiles/r04_burst_ramp.txt), which is
         # longer than the driver's whole 20-step region.
         step = step_on(n_fl)
-        index.set_option("scan_share", 1)
-        step1 = step_on(1)
-        dt1, barrier = sharded_steps(step1, pg, a.steps, max(2, a.warmup), sync, world)
-        # (at least 240 launches per kernel: averages that do not depend on --steps, and ~60 ms of this very workload before the
-        # timed region -- the driver's 20-step command used to time the chip's ramp: 0.105 ms per step against 0.099 over 300 steps)
-        n_prof = max(a.steps, 240)
-        index.profile_enable(True)
-        for _ in range(n_prof):
-            step1()
-        barrier()
-        prof = index.profile_read()
-        index.profile_enable(False)
-        prof_ov = {}
-        index.set_option("scan_share", a.scan_share or n_fl)   # the *_dev contract: the caller states how many batches it keeps in flight
-        if n_fl > 1:   # ... and with the batches in flight as in the timed region: durations under overlap
+        if a.full:
+            index.set_option("scan_share", 1)
+            step1 = step_on(1)
+            dt1, barrier = sharded_steps(step1, pg, a.steps, max(2, a.warmup), sync, world)
+            # (at least 240 launches per kernel: averages that do not depend on --steps, and ~60 ms of this very workload before the
+            # timed region -- the driver's 20-step command used to time the chip's ramp: 0.105 ms per step against 0.099 over 300 steps)
+            n_prof = max(a.steps, 240)
             index.profile_enable(True)
-            for _ in range(max(n_prof, 4 * n_fl)):
-                step()
+            for _ in range(n_prof):
+                step1()
             barrier()
-            prof_ov = index.profile_read()
+            prof = index.profile_read()
             index.profile_enable(False)
+            prof_ov = {}
+            index.set_option("scan_share", a.scan_share or n_fl)   # the *_dev contract: the caller states how many batches it keeps in flight
+            if n_fl > 1:   # ... and with the batches in flight as in the timed region: durations under overlap
+                index.profile_enable(True)
+                for _ in range(max(n_prof, 4 * n_fl)):
+                    step()
+                barrier()
+                prof_ov = index.profile_read()
+                index.profile_enable(False)
+        else:
+            # a plain run: no side measurements, RAMP_STEPS of the timed steps bring the chip to its steady state instead
+            index.set_option("scan_share", a.scan_share or n_fl)
+            for _ in range(RAMP_STEPS):
+                step()
+            pg.drain()
+            sync()
         # ---- the timed region: W warmup steps, barrier, exactly K steps, barrier ----
         counter[0] = 0
         pg.steps = 0   # (drained by the barrier above: step c again writes buffer c % depth)
@@ -638,14 +721,14 @@ def run_ivfadc(a, rank, world, dev, dev_index):
         # compared bit for bit with the oracle below -- verify what is timed.
         total_steps = counter[0]
         timed_results = []
-        for back in range(min(n_fl, a.steps)):
+        for back in range(min(n_fl, a.steps) if a.full else 1):   # (timed_results[0]: the last timed step)
             sidx = total_steps - 1 - back
             timed_results.append((sidx % n_fl, pg.res[sidx % depth].clone()))   # (depth is a multiple of n_fl or equal to it)
-        straggler = int(d_status[0].item())
+        straggler = int(d_status[0].item()) if a.full else None
         # ---- --force-collective on one rank: the SAME process, streams and steps without the collective, alternating with the
         # collective path (what the gather, its stream and the reserved CUs cost rank 0 of an N-GPU run)
         coll_ab = None
-        if a.force_collective and world == 1:
+        if a.full and a.force_collective and world == 1:
             with torch.cuda.stream(streams[0]):
                 pg0 = shard.PipelinedGather(q_local, a.k, dev, depth=max(2, n_fl))
             plain = step_on(n_fl, pg0, False)
@@ -681,6 +764,24 @@ def run_ivfadc(a, rank, world, dev, dev_index):
             torch.cuda.synchronize(dev)
             for cm in (comm.values() if isinstance(comm, dict) else [comm]):
                 cm.close()
+    dtype = "f32 (results: the reference's binary32 sub/mul/add chains; filter stage: int16 fixed-point table x f32 scale, f32 sums)"
+    cfg = {"workload": "IVFADC batch (ivfadc_batch_search generalised to nprobe), "
+                       f"{N}x300d, C={a.C}, m={a.m}, K={a.K}, nprobe={a.nprobe}, k={a.k}, "
+                       f"batch={q_local} queries per GPU, replicated index, queries sharded by rank",
+           "N": N, "d": 300, "C": a.C, "m": a.m, "K": a.K, "nprobe": a.nprobe, "k": a.k,
+           "batch_per_gpu": q_local, "parallelism": f"dp{world}",
+           "batches_in_flight": n_fl, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+           "world_size": (dist.get_world_size() if dist.is_initialized() else 1),
+           "backend": (("rccl (torch.distributed nccl)" if a.backend == "nccl" else a.backend) if collective else "none (single GPU)"),
+           "gather_every": (G if collective else None), "gather_path": gather_path,
+           "communicators": (len(comm) if isinstance(comm, dict) else (1 if comm is not None else None))}
+    if not a.full:
+        if rank != 0:
+            return None
+        return {"metric": METRIC, "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+                "ms_per_step": round(1e3 * dt / a.steps, 4), "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None,
+                "dtype": dtype, "data": "synthetic", "config": cfg, "gather_verified": gather_ok, "roofline": None, "cpu_baseline": None,
+                "_dump": result_arrays(timed_results[0][1][0], timed_results[0][1][1])}
     scanned_rows = index.last_scanned_rows()
     n_cells, cell_rows = index.last_probed_cells()
     bound_violations = index.bound_violations()   # self-check of the filter + refine scan (must be 0)
@@ -877,27 +978,18 @@ def run_ivfadc(a, rank, world, dev, dev_index):
             "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(1e3 * dt / a.steps, 4), "higher_is_better": True, "scaling": a.scaling,
             "vs_baseline": None,
-            "dtype": "f32 (results: the reference's binary32 sub/mul/add chains; filter stage: int16 fixed-point table x f32 scale, f32 sums)",
+            "dtype": dtype,
             "data": "synthetic",
-            "config": {"workload": "IVFADC batch (ivfadc_batch_search generalised to nprobe), "
-                                   f"{N}x300d, C={a.C}, m={a.m}, K={a.K}, nprobe={a.nprobe}, k={a.k}, "
-                                   f"batch={q_local} queries per GPU, replicated index, queries sharded by rank",
-                       "N": N, "d": 300, "C": a.C, "m": a.m, "K": a.K, "nprobe": a.nprobe, "k": a.k,
-                       "batch_per_gpu": q_local, "parallelism": f"dp{world}",
-                       "batches_in_flight": n_fl, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-                       "world_size": (dist.get_world_size() if dist.is_initialized() else 1),
-                       "backend": (("rccl (torch.distributed nccl)" if a.backend == "nccl" else a.backend) if collective else "none (single GPU)"),
-                       "gather_every": (G if collective else None), "gather_path": gather_path,
-                       "communicators": (len(comm) if isinstance(comm, dict) else (1 if comm is not None else None)),
-                       "recall_at_5": None if recall is None else round(recall, 4),
-                       "recall_at_5_without_self": None if recall_info is None else recall_info["recall_at_5_without_self"],
-                       "host_abi_q1024_qps": (abi_brief.get("Q1024") or {}).get("queries_per_s"),
-                       "host_abi_q4096_qps": (abi_brief.get("Q4096") or {}).get("queries_per_s"),
-                       "recall": recall_info,
-                       "queries_needing_extra_round": straggler,
-                       "measurement_order": "serial and instrumented passes of the same steps first, then W warmup steps, barrier, the K timed steps, "
-                                            "barrier (a chip that idled while the index was pinned runs its first ~10 ms of bursts up to 12 % "
-                                            "slower: profiles/r04_burst_ramp.txt)"},
+            "config": dict(cfg, **{
+                "recall_at_5": None if recall is None else round(recall, 4),
+                "recall_at_5_without_self": None if recall_info is None else recall_info["recall_at_5_without_self"],
+                "host_abi_q1024_qps": (abi_brief.get("Q1024") or {}).get("queries_per_s"),
+                "host_abi_q4096_qps": (abi_brief.get("Q4096") or {}).get("queries_per_s"),
+                "recall": recall_info,
+                "queries_needing_extra_round": straggler,
+                "measurement_order": "serial and instrumented passes of the same steps first, then W warmup steps, barrier, the K timed steps, "
+                                     "barrier (a chip that idled while the index was pinned runs its first ~10 ms of bursts up to 12 % "
+                                     "slower: profiles/r04_burst_ramp.txt)"}),
             "recall_at_5": None if recall is None else round(recall, 4),
             "queries_needing_extra_round": straggler,
             "filter_bound_violations": bound_violations,
@@ -919,6 +1011,7 @@ def run_ivfadc(a, rank, world, dev, dev_index):
             "roofline": roof, "kernels": kern,
             "kernels_overlapped": {n: {"launches": l, "avg_us": round(1e3 * ms / max(l, 1), 2)} for n, (l, ms) in prof_ov.items()},
             "cpu_baseline": cpu,
+            "_dump": result_arrays(timed_results[0][1][0], timed_results[0][1][1]),
         }
         if other_exact is not None:
             out["_exact"] = other_exact
@@ -932,8 +1025,9 @@ def run_pq(a, rank, world, dev, dev_index):
     from freddy_amd import gpu, index_build as ib
     N = a.N or 1_000_000
     Q = a.Q or 64
-    x = ib.make_corpus(N, d=300, seed=11, device=dev)
-    tab = ib.build_pq_index(x, m=a.m, K=a.K, train_size=100000, iters=6, seed=1)
+    with same_inputs():
+        x = ib.make_corpus(N, d=300, seed=11, device=dev)
+        tab = ib.build_pq_index(x, m=a.m, K=a.K, train_size=100000, iters=6, seed=1)
     index = gpu.PQIndex(tab["codebook"], tab["ids"], tab["codes"], device=dev_index)
     rng = np.random.default_rng(7 + rank)
     qids = np.sort(rng.choice(np.arange(1, N + 1), size=Q, replace=False)).astype(np.int64)
@@ -954,6 +1048,14 @@ def run_pq(a, rank, world, dev, dev_index):
         step()
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
+    dump = result_arrays(d_ids, d_dist)
+    line = {"metric": "PQ search queries/sec (pq_search, k=5), 1Mx300d", "value": round(Q * a.steps / dt, 1), "unit": "queries/s",
+            "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"PQ search (pq_search / knn_in_pq), {N}x300d, m={a.m}, K={a.K}, k={a.k}, batch={Q} queries",
+                       "N": N, "m": a.m, "K": a.K, "k": a.k, "batch": Q}}
+    if not a.full:
+        return dict(line, roofline=None, cpu_baseline=None, _dump=dump)
     index.profile_enable(True)
     for _ in range(a.steps):
         step()
@@ -1008,18 +1110,14 @@ def run_pq(a, rank, world, dev, dev_index):
         t1 = prof1["adc_scan"][1] / max(prof1["adc_scan"][0], 1) / 1e3
         single["roofline"] = roofline("adc_scan_kernel", t1, N * row_bytes + a.m * a.K * 4, "the code table once (28 B per row) + the query's 48 KiB LUT",
                                       None, {"note": "the table is Infinity-Cache resident; the call is a chain of latency-bound launches around this kernel"})
-    return {
-        "metric": "PQ search queries/sec (pq_search, k=5), 1Mx300d", "value": round(Q * a.steps / dt, 1), "unit": "queries/s",
-        "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"PQ search (pq_search / knn_in_pq), {N}x300d, m={a.m}, K={a.K}, k={a.k}, batch={Q} queries",
-                   "N": N, "m": a.m, "K": a.K, "k": a.k, "batch": Q},
+    return dict(line, **{
         "single_query_host_abi_ms": round(one_ms, 4), "single_query": single,
         "roofline": roof, "kernels": kern,
         "cpu_baseline": {"value": round(ns / cdt, 2), "unit": "queries/s", "cores": 1, "kind": "port",
                          "sample": f"first {ns} bench queries, same table",
                          "loop": "oracle/fo_pq_search (freddy.c:28-152: LUT, ADC over all rows, updateTopK), one thread; SPI excluded",
-                         "parity_with_gpu_on_sample": parity}}
+                         "parity_with_gpu_on_sample": parity},
+        "_dump": dump})
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1030,8 +1128,9 @@ def run_join(a, rank, world, dev, dev_index):
     N = a.N or 1_000_000
     Q = a.Q or 5000
     T = 100_000
-    x = ib.make_corpus(N, d=300, seed=5, device=dev)
-    t = ib.build_ivpq_index(x, m=30, K=32, k_coarse=32, train_size=100000, iters=6, seed=3)
+    with same_inputs():
+        x = ib.make_corpus(N, d=300, seed=5, device=dev)
+        t = ib.build_ivpq_index(x, m=30, K=32, k_coarse=32, train_size=100000, iters=6, seed=3)
     index = gpu.IVPQIndex(t["codebook"], t["coarse"], t["ids"], t["coarse_id"], t["codes"], t["vectors"], t["stats"], device=dev_index)
     rng = np.random.default_rng(4)
     qid = rng.choice(np.arange(1, N + 1), Q, replace=False)
@@ -1063,6 +1162,17 @@ def run_join(a, rank, world, dev, dev_index):
     dt = time.perf_counter() - t0
     med = float(np.median(step_s))   # (a host hiccup -- one 66 ms step among twenty of 0.9 ms was seen in the combined run -- must not set the median)
     mean = dt / a.steps
+    dump = result_arrays(gi, gd)
+    line = {"metric": "kNN-join queries/sec (ivpq_search_in, 5000 x 100000, k=5, alpha=100, pvf=20, method 2)",
+            "value": round(Q / mean, 1), "unit": "queries/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(1e3 * mean, 4), "median_ms_per_step": round(1e3 * med, 4), "slowest_step_ms": round(1e3 * max(step_s), 3)}
+    tail = {"higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"knn_join (ivpq_search_in): {Q} queries x {T} targets of {N} rows, k={a.k}, alpha={alpha}, "
+                                   f"pvf={pvf}, method=2, host-buffer ABI (one synchronous call per step)",
+                       "N": N, "Q": Q, "targets": T, "m": 30, "K": 32, "coarse": "2 x 32"}}
+    if not a.full:
+        return dict(line, **tail, roofline=None, cpu_baseline=None, _dump=dump)
     call(cached=True)
     call(cached=True)
     cached_s = []
@@ -1109,10 +1219,7 @@ def run_join(a, rank, world, dev, dev_index):
     cdt = time.perf_counter() - t0
     parity = bool(np.array_equal(exp["id"].reshape(gi.shape), gi) and
                   np.array_equal(exp["dist"].reshape(gd.shape).view(np.uint32), gd.view(np.uint32)) and eit == it)
-    return {
-        "metric": "kNN-join queries/sec (ivpq_search_in, 5000 x 100000, k=5, alpha=100, pvf=20, method 2)",
-        "value": round(Q / mean, 1), "unit": "queries/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(1e3 * mean, 4), "median_ms_per_step": round(1e3 * med, 4), "slowest_step_ms": round(1e3 * max(step_s), 3),
+    return dict(line, **{
         "cached_targets": {"mean_ms_per_step": round(1e3 * float(np.mean(cached_s)), 4), "median_ms_per_step": round(1e3 * float(np.median(cached_s)), 4),
                            "note": "every call repeats ONE target array: the library finds the array's buckets in place (not what the reference does per call)"},
         "pinned_queries": {"mean_ms_per_step": round(1e3 * float(np.mean(pinned_s)), 4), "median_ms_per_step": round(1e3 * float(np.median(pinned_s)), 4),
@@ -1120,18 +1227,15 @@ def run_join(a, rank, world, dev, dev_index):
                            "note": "the query batch in a freddy_gpu_host_alloc buffer (as pg/freddy_gpu_glue.c passes it): no staging copy; cold target arrays"},
         "timing": "value / ms_per_step = total time of the timed region / steps (mean), one synchronous call per step, no step with the target "
                   "array of its predecessor (three arrays in turn: the resolution of fq.id IN (targets) is inside every step); median beside it",
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"knn_join (ivpq_search_in): {Q} queries x {T} targets of {N} rows, k={a.k}, alpha={alpha}, "
-                               f"pvf={pvf}, method=2, host-buffer ABI (one synchronous call per step)",
-                   "N": N, "Q": Q, "targets": T, "m": 30, "K": 32, "coarse": "2 x 32"},
+        **tail,
         "track": {n: (round(v, 6) if isinstance(v, float) else v) for n, v in track.items()},
         "roofline": roof,
         "cpu_baseline": {"value": round(Q / cdt, 2), "unit": "queries/s", "cores": 1, "kind": "port",
                          "sample": f"the same call ({Q} queries, {T} targets), once",
                          "loop": "oracle/fo_ivpq_search_in (ivpq_search_in.c:61-699), one thread; SPI / SQL string building excluded "
                                  "(README: 2.7-20 s for this join end to end)",
-                         "parity_with_gpu_on_sample": parity}}
+                         "parity_with_gpu_on_sample": parity},
+        "_dump": dump})
 
 
 def run_exact(a, rank, world, dev, dev_index):
@@ -1139,16 +1243,18 @@ def run_exact(a, rank, world, dev, dev_index):
     from freddy_amd import index_build as ib
     N = a.N or 3_000_000
     Q = a.Q or 64
-    x = ib.make_corpus(N, d=300, seed=20260101, device=dev)
+    with same_inputs():
+        x = ib.make_corpus(N, d=300, seed=20260101, device=dev)
     rng = np.random.default_rng(7)
     qids = np.sort(rng.choice(np.arange(1, N + 1), size=max(Q, 64), replace=False)).astype(np.int64)
     d_q = x[torch.from_numpy(qids - 1).to(dev)].contiguous()
-    _, info = exact_truth(x, [d_q], a.k, dev_index, steps=a.steps)
+    last = {}
+    _, info = exact_truth(x, [d_q], a.k, dev_index, steps=a.steps, full=a.full, outputs=last)
     key = f"Q{Q}" if f"Q{Q}" in info else "Q64"
     out = {"metric": info["metric"], "value": info[key]["value"], "unit": "queries/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
            "ms_per_step": info[key]["ms_per_call"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
            "data": "synthetic", "config": info["config"], "roofline": info[key]["roofline"], "cpu_baseline": info["cpu_baseline"],
-           "kernels": info[key]["kernels_us"], "Q1": info["Q1"], "Q64": info["Q64"]}
+           "kernels": info[key]["kernels_us"], "Q1": info["Q1"], "Q64": info["Q64"], "_dump": last[key]}
     return out
 
 
@@ -1223,6 +1329,8 @@ def main():
     a = parse()
     if a.host_abi_child:
         sys.exit(run_host_abi_child(a))
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a))
     rank = int(os.environ.get("RANK", "0"))
@@ -1256,7 +1364,7 @@ def main():
             dist.init_process_group(a.backend, rank=rank, world_size=world)
     if a.config == "ivfadc":
         out = run_ivfadc(a, rank, world, dev, dev_index)
-        if world == 1 and not a.no_other_configs and a.N is None and a.Q is None:
+        if a.full and world == 1 and not a.no_other_configs and a.N is None and a.Q is None:
             # BASELINE configs[1] and configs[3] beside the metric's configuration: bounded passes (a few seconds each)
             import copy
             other = {}
@@ -1290,7 +1398,7 @@ def main():
             if not a.force_collective and not a.no_collective_child and a.in_flight > 1:
                 try:
                     torch.cuda.empty_cache()
-                    cmd = [sys.executable, os.path.abspath(__file__), "--force-collective", "--no-other-configs", "--no-host-abi", "--no-recall",
+                    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--force-collective", "--no-other-configs", "--no-host-abi", "--no-recall",
                            "--cpu-sample", "0", "--steps", str(max(a.steps, 100)), "--warmup", str(a.warmup), "--in-flight", str(a.in_flight),
                            "--backend", a.backend]
                     side = os.path.join(ROOT, "bench_details_collective.json")
@@ -1315,7 +1423,10 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        emit(out, "bench_details_collective.json" if (a.force_collective and world == 1) else "bench_details.json")
+        dump = out.pop("_dump", None)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, dump)
+        emit(out, "bench_details_collective.json" if (a.force_collective and world == 1) else "bench_details.json", full=a.full)
 
 
 if __name__ == "__main__":

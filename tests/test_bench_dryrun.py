@@ -67,6 +67,22 @@ def test_bench_single_rank_dry_run():
     assert out["n_gpus"] == 1 and out["gather_verified"] is True
 
 
+def test_bench_dry_run_dumps_the_last_step(tmp_path):
+    """--dump-outputs DIR: the lists of the last timed step as DIR/ids.npy (float64) and DIR/dist.npy (float32)."""
+    import numpy as np
+    out = _run("--dry-run", "--steps", "3", "--warmup", "1", "--Q", "16", "--dump-outputs", str(tmp_path))
+    assert out["steps"] == 3
+    ids, dist = np.load(tmp_path / "ids.npy"), np.load(tmp_path / "dist.npy")
+    assert ids.dtype == np.float64 and dist.dtype == np.float32 and ids.shape == dist.shape == (16, 5)
+    assert ids[0, 0] == 3 * 7919   # fill_pattern of rank 0, step index 3 (one warm-up step + three timed ones)
+
+
+def test_bench_refuses_zero_steps():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "0"], capture_output=True, text=True,
+                       timeout=600)
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
 def test_pipelined_gather_detects_a_wrong_slot():
     """verify_gather must fail when a gathered slot does not hold its rank's result (world 1: trivially true)."""
     sys.path[:0] = [ROOT, os.path.join(ROOT, "postgres-word2vec_amd")]

@@ -21,7 +21,7 @@ def _bench(*args):
 
 @pytest.mark.parametrize("path,every", [("rccl", 1), ("rccl", 4), ("c10d", 1), ("c10d-async", 4)])
 def test_one_rank_rccl_gather_equals_the_local_buffer(path, every):
-    line = _bench("--force-collective", "--gather-path", path, "--gather-every", str(every), "--N", "200000", "--C", "100", "--steps", "22",
+    line = _bench("--full", "--force-collective", "--gather-path", path, "--gather-every", str(every), "--N", "200000", "--C", "100", "--steps", "22",
                   "--warmup", "5", "--cpu-sample", "1024", "--no-other-configs", "--no-host-abi", "--no-recall", "--ab-rounds", "1")
     assert line["n_gpus"] == 1 and line["gather_verified"] is True
     assert line["config"]["backend"].startswith("rccl") and line["config"]["world_size"] == 1

@@ -6,7 +6,7 @@ N=${1:-2}; shift
 for r in $(seq $N); do
   for v in new base; do
     if [ $v = base ]; then export FREDDY_GPU_SO=$PWD/postgres-word2vec_amd/libfreddy_gpu_base.so; else unset FREDDY_GPU_SO; fi
-    python bench.py --no-other-configs --no-host-abi --no-recall --cpu-sample 0 "$@" > /tmp/ab.out 2>/dev/null
+    python bench.py --full --no-other-configs --no-host-abi --no-recall --cpu-sample 0 "$@" > /tmp/ab.out 2>/dev/null
     python - "$v" <<'P'
 import json, sys
 o = json.load(open("bench_details.json"))

@@ -4,7 +4,7 @@
 NAME=$1; A=$2; B=$3; N=${4:-2}; shift 4
 for r in $(seq $N); do
   for v in $A $B; do
-    env $NAME=$v python bench.py --no-other-configs --no-host-abi --no-recall --cpu-sample 0 "$@" > /tmp/ab.out 2>/dev/null
+    env $NAME=$v python bench.py --full --no-other-configs --no-host-abi --no-recall --cpu-sample 0 "$@" > /tmp/ab.out 2>/dev/null
     python - "$NAME=$v" <<'P'
 import json, sys
 o = json.load(open("bench_details.json"))

@@ -5,7 +5,7 @@ N=${1:-2}; SOS=$2; shift 2
 for r in $(seq $N); do
   for so in $SOS; do
     export FREDDY_GPU_SO=$PWD/$so
-    python bench.py --no-other-configs --no-host-abi --no-recall --cpu-sample 0 --no-collective-child "$@" > /tmp/ab.out 2>/dev/null
+    python bench.py --full --no-other-configs --no-host-abi --no-recall --cpu-sample 0 --no-collective-child "$@" > /tmp/ab.out 2>/dev/null
     python - "$so" <<'P'
 import json, sys
 o = json.load(open("bench_details.json"))
