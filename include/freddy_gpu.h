@@ -177,6 +177,27 @@ int freddy_gpu_pin_vectors(const freddy_vec_desc* desc, int device, freddy_gpu_i
 int freddy_gpu_exact_search(freddy_gpu_index_t* vecs, const float* queries, int32_t Q, int32_t k,
                             const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_sim);
 
+/* ---- exact word analogies on the same handle (analogy.h) ------------------------------------------------------------
+ * The bodies of analogy_3cosadd, analogy_3cosadd_in (freddy--0.0.1.sql:1270-1315) and analogy_3cosmul (:1231-1249), batched:
+ * for every triple (w1, w2, w3) of row ids the k rows v4 with the largest score, v4 not one of the three input rows
+ * ("v4.word NOT IN (...)"; another row with an identical vector is not excluded), ordered by score DESC, id ASC.
+ *   3CosAdd: cosine_similarity_bytea(vec_plus_bytea(vec_minus_bytea(v3, v1), v2), v4) -- binary32, reported widened to double
+ *   3CosMul: ((c3 + 1)/2) * ((c2 + 1.0)/2.0) / (((c1 + 1.0)/2.0) + 0.001), c_i = cosine_similarity_bytea(v4, v_i), all in
+ *            float8 (PostgreSQL's float48pl: the binary32 c_i widened, constants the doubles nearest 1, 2, 0.001)
+ * subset_ids == NULL: all rows; else "id = ANY(subset_ids)" (the _in form: duplicates / unknown ids ignored; the inputs may lie
+ * outside the set).  An unknown input id (the SQL's empty INNER JOIN, NULL) and slots beyond the rows hold (-1, -inf).
+ * Any Q (processed in passes); k <= 32 (FREDDY_E_LIMIT above).  Argument errors are reported before any device work. */
+#define FREDDY_ANALOGY_3COSADD 0
+#define FREDDY_ANALOGY_3COSMUL 1
+int freddy_gpu_exact_analogy(freddy_gpu_index_t* vecs, int32_t method, const int32_t* triples /*[Q][3] ids w1,w2,w3*/,
+                             int32_t Q, int32_t k, const int32_t* subset_ids, int64_t n_subset,
+                             int32_t* out_ids /*[Q][k]*/, double* out_score /*[Q][k]; 3CosAdd: the float widened*/);
+/* What the last freddy_gpu_exact_analogy call on this handle did: passes of (up to 32) analogies the filter + refine path ran
+ * over the whole table (0: the all-exact path answered everything -- subsets, small or non-finite tables, exact_filter = 0,
+ * 3CosMul with d > 416), the candidates those passes refined (summed over their analogies), and how many of them were redone on
+ * the all-exact path (a candidate buffer overflowed or the pass's vectors were not finite).  NULL pointers are skipped. */
+int freddy_gpu_last_analogy_stats(const freddy_gpu_index_t* vecs, int64_t* filter_passes, int64_t* candidates, int64_t* redone_passes);
+
 /* ---- next row: grouping_pq ---------------------------------------------------------
  * Body of grouping_pq (freddy.c:1176-1401): for every row of the PQ table (subset_ids == NULL) or of
  * "id IN (subset_ids)" the nearest of G group vectors by ADC distance -- one LUT per group from the PQ
@@ -332,7 +353,8 @@ int freddy_gpu_abi_version(void);
  *                1 always)
  *   self-checks (tests):  "check_brackets" (bit 0: the scan keeps and the merge refines EVERY probed row, bit 1: the cell
  *                selection refines every cell, bit 2: exact kNN refines every row -- each with its proven bracket compared with
- *                the reference's value: freddy_gpu_filter_bound_violations / _checked), "join_host_traversal",
+ *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines
+ *                every row for every analogy, counted the same way), "join_host_traversal",
  *                "join_libm_margin_ppm" */
 int freddy_gpu_set_option(freddy_gpu_index_t* index, const char* name, int64_t value);
 

@@ -176,6 +176,27 @@ int cluster_exact(freddy_session_t* s, const int32_t* token_ids, int32_t n, int3
 int cluster_pq(freddy_session_t* s, const int32_t* token_ids, int32_t n, int32_t k, const double* draws, int32_t n_draws, int32_t* cluster_out);
 int cluster_ivpq(freddy_session_t* s, const int32_t* token_ids, int32_t n, int32_t k, const double* draws, int32_t n_draws, int32_t* cluster_out);
 
+/* Exact analogies and the analogy dispatchers, by row id (analogy.h; the device entry point freddy_gpu_exact_analogy).
+ * analogy_3cosadd / analogy_3cosadd_in                      freddy--0.0.1.sql:1270-1315
+ * analogy_3cosmul                                           freddy--0.0.1.sql:1231-1249
+ *   the row v4 (v4 not w1, w2, w3; _in: id = ANY(input_ids)) with the largest score, ties by lowest id; *result = -1 where the
+ *   SQL returns NULL (an unknown input id, no row left).
+ * analogy(a, b, c) / analogy_in(w1, w2, w3, input_set)      freddy--0.0.1.sql:269-297
+ *   call the function set_analogy_function / set_analogy_in_function named (defaults analogy_3cosadd / analogy_3cosadd_in,
+ *   :198-199).  The setters accept any name, as the SQL ones do; a name this library does not implement fails at call time
+ *   with PostgreSQL's wording: "function <name>(unknown, unknown, unknown) does not exist" (analogy_in: "..., character
+ *   varying[])").  analogy(): analogy_3cosadd, analogy_3cosmul, analogy_3cosadd_pq, analogy_3cosadd_ivfadc; analogy_in():
+ *   analogy_3cosadd_in, analogy_3cosadd_in_pq, analogy_3cosadd_in_ivpq. */
+int analogy_3cosadd(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, int32_t* result);
+int analogy_3cosmul(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, int32_t* result);
+int analogy_3cosadd_in(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids, int32_t n_ids, int32_t* result);
+int freddy_set_analogy_function(freddy_session_t* s, const char* name);
+const char* freddy_get_analogy_function(const freddy_session_t* s);
+int freddy_set_analogy_in_function(freddy_session_t* s, const char* name);
+const char* freddy_get_analogy_in_function(const freddy_session_t* s);
+int analogy(freddy_session_t* s, int32_t a, int32_t b, int32_t c, int32_t* result);
+int analogy_in(freddy_session_t* s, int32_t w1, int32_t w2, int32_t w3, const int32_t* input_ids, int32_t n_ids, int32_t* result);
+
 /* Next row: insert_batch(varchar[]) -> int4                  freddy.c:1403-1658
  * The tokenisation sub-query (:1503-1519: tokenize(term) for the terms NOT yet in the vocabulary) stays with SQL;
  * the caller passes its result, the normalised vectors of the new terms.  Per vector: PQ code, coarse cell +

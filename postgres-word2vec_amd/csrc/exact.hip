@@ -1,9 +1,11 @@
-// exact.hip -- pin_vectors and exact brute-force kNN (core_functions.c:67-81, freddy--0.0.1.sql:426-454).
+// exact.hip -- pin_vectors, exact brute-force kNN (core_functions.c:67-81, freddy--0.0.1.sql:426-454) and the
+// exact analogies on the same handle (freddy--0.0.1.sql:1231-1315; analogy.h).
 #include "internal.h"
 
 #include "kernels.h"
 #include "exact.h"
 #include "exact2.h"
+#include "analogy.h"
 
 // ---------------------------------------------------------------------------------------
 // exact brute-force kNN
@@ -333,6 +335,236 @@ extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* quer
   return FREDDY_OK;
 }
 
+// ---- exact analogies (analogy.h) ----------------------------------------------------------------------------------------
+// The all-exact path for the na analogies at d_in_rows (device [na][3] table rows): scores of every eligible row, per-wave lists,
+// one merge per analogy into d_ids / d_score ([na][k]).  Enqueued only.
+static int analogy_scan(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, int M, const int32_t* d_in_rows, int na, int k, const float* xb,
+                        const int32_t* pos, int64_t n_rows, int64_t n_blocks, int32_t* d_ids, double* d_score) {
+  const int d = ix->d;
+  const int AT = M == 1 ? 8 : 4;
+  const int groups = (na + AT - 1) / AT;
+  int chunk_blocks = 8;
+  while ((n_blocks + chunk_blocks - 1) / chunk_blocks * (int64_t)groups > 8192 && chunk_blocks < 1024) chunk_blocks *= 2;
+  const int nchunk = (int)std::max<int64_t>(1, (n_blocks + chunk_blocks - 1) / chunk_blocks);
+  if (ws->w_qc.ensure(sizeof(float) * (size_t)na * M * d) || ws->w_part.ensure(sizeof(AnEnt) * (size_t)na * nchunk * AN_WAVES * k))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  float* cols = ws->w_qc.as<float>();
+  timed_launch(ix, s, "analogy_gather", [&] { hipLaunchKernelGGL(an_gather_kernel, dim3((unsigned)(na * M)), dim3(256), 0, s, ix->coarse, d, d_in_rows, na, M, 0, cols); });
+  HIP_TRY(hipGetLastError());
+  AnScanArgs sa;
+  sa.xb = xb; sa.pos = pos; sa.n_rows = n_rows; sa.n_blocks = (int)n_blocks; sa.chunk_blocks = chunk_blocks; sa.nchunk = nchunk;
+  sa.cols = cols; sa.in_rows = d_in_rows; sa.na = na; sa.d = d; sa.k = k; sa.part = ws->w_part.as<AnEnt>();
+  const dim3 grid((unsigned)nchunk, (unsigned)groups);
+  timed_launch(ix, s, "analogy_scan", [&] {
+    if (M == 1) hipLaunchKernelGGL((an_scan_kernel<1, 8>), grid, dim3(AN_WG), (an_scan_lds<1, 8>(d)), s, sa);
+    else hipLaunchKernelGGL((an_scan_kernel<3, 4>), grid, dim3(AN_WG), (an_scan_lds<3, 4>(d)), s, sa);
+  });
+  HIP_TRY(hipGetLastError());
+  timed_launch(ix, s, "analogy_merge", [&] {
+    hipLaunchKernelGGL(an_merge_kernel, dim3((unsigned)na), dim3(AN_WG), 0, s, (const AnEnt*)sa.part, nchunk * AN_WAVES, k, ix->ids, d_ids, d_score);
+  });
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The filter + refine path over the whole table, passes of AN_PASS analogies.  flags[p] (device, zeroed here) != 0: pass p's
+// results are not valid (its columns were not finite, or a candidate buffer overflowed) -- the caller redoes it; flags[passes + p]
+// receives the number of candidates pass p refined.  Enqueued only.
+static int analogy_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, int M, const int32_t* d_in_rows, int na, int k,
+                          int32_t* d_ids, double* d_score, int32_t* flags) {
+  const int d = ix->d, T = (d + 15) / 16;
+  const int64_t N = ix->N;
+  const bool all = (ix->tune.check_brackets & 8) != 0;
+  const int cap = (int)(all ? N : std::min<int64_t>(N, 8192));
+  const int64_t full_strips = N / 32;
+  const int n_sample = (int)(std::min<int64_t>(full_strips, EXF_SAMPLE / 32) * 32);
+  const int64_t sample_stride = n_sample > 0 ? std::max<int64_t>(1, full_strips / (n_sample / 32)) : 1;
+  const int passes = (na + AN_PASS - 1) / AN_PASS;
+  // per-pass state: [0, 256) tau (double [32]), [256, 640) eps, [640, 1024) unscale (float [96]), [1024, 1152) candidate counts
+  if (ws->w_found.ensure(2048) || ix->exf_qfrag.ensure((size_t)M * T * 2 * 64 * 16) || ws->w_qc.ensure(sizeof(float) * (size_t)M * AN_PASS * d) ||
+      ix->exf_sample.ensure(sizeof(double) * (size_t)AN_PASS * std::max(n_sample, 1)) || ix->exf_cand.ensure(sizeof(uint4) * (size_t)AN_PASS * cap))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  if (!ix->viol) {
+    HIP_TRY(hipMalloc((void**)&ix->viol, 4 * sizeof(int32_t)));
+    HIP_TRY(hipMemset(ix->viol, 0, 4 * sizeof(int32_t)));
+  }
+  char* sm = ws->w_found.as<char>();
+  double* thr = reinterpret_cast<double*>(sm);
+  float* qeps = reinterpret_cast<float*>(sm + 256);
+  float* qunscale = reinterpret_cast<float*>(sm + 640);
+  int32_t* cand_cnt = reinterpret_cast<int32_t*>(sm + 1024);
+  float* cols = ws->w_qc.as<float>();
+  HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int32_t) * 2 * passes, s));
+  auto grid_for = [&](int64_t rows) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, (int64_t)ix->n_cus * 2)); };
+  const size_t flds = an_filter_lds(M, d);
+  for (int p = 0; p < passes; ++p) {
+    const int a0 = p * AN_PASS, np = std::min(AN_PASS, na - a0);
+    const int32_t* in_rows = d_in_rows + (size_t)a0 * 3;
+    timed_launch(ix, s, "analogy_gather", [&] {
+      hipLaunchKernelGGL(an_gather_kernel, dim3((unsigned)(M * AN_PASS)), dim3(256), 0, s, ix->coarse, d, in_rows, np, M, 1, cols);
+    });
+    HIP_TRY(hipGetLastError());
+    ExfPrepArgs pa;
+    pa.queries = cols; pa.nq = M * AN_PASS; pa.d = d; pa.T = T; pa.xmax_norm = ix->exf_xnorm; pa.ex = ix->exf_ex;
+    pa.eps_factor = exf_eps_factor(d); pa.qfrag = ix->exf_qfrag.as<h8v>(); pa.qeps = qeps; pa.qunscale = qunscale; pa.qbad = flags + p;
+    pa.copy_out = nullptr;
+    timed_launch(ix, s, "analogy_prep", [&] { hipLaunchKernelGGL(exf_prep_kernel, dim3((unsigned)(M * AN_PASS)), dim3(256), 0, s, pa); });
+    HIP_TRY(hipGetLastError());
+    AnFilterArgs fa;
+    fa.xf = ix->exf_xf.as<h8v>(); fa.n_rows = n_sample; fa.strip_stride = sample_stride; fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>();
+    fa.qunscale = qunscale; fa.qeps = qeps; fa.in_rows = in_rows; fa.na = np; fa.sample_out = ix->exf_sample.as<double>();
+    fa.thr = thr; fa.cand_cnt = cand_cnt; fa.cand = ix->exf_cand.as<uint4>(); fa.cap = cap; fa.refine_all = all ? 1 : 0;
+    if (n_sample > 0) {
+      timed_launch(ix, s, "analogy_sample", [&] {
+        if (M == 1) hipLaunchKernelGGL((an_filter_kernel<1, true>), dim3(grid_for(n_sample)), dim3(EXF_WG), flds, s, fa);
+        else hipLaunchKernelGGL((an_filter_kernel<3, true>), dim3(grid_for(n_sample)), dim3(EXF_WG), flds, s, fa);
+      });
+      HIP_TRY(hipGetLastError());
+    }
+    timed_launch(ix, s, "analogy_threshold", [&] {
+      hipLaunchKernelGGL(an_threshold_kernel, dim3(AN_PASS), dim3(AN_WG), 0, s, (const double*)fa.sample_out, n_sample, np, k, all ? 1 : 0, thr, cand_cnt);
+    });
+    HIP_TRY(hipGetLastError());
+    fa.n_rows = N; fa.strip_stride = 1; fa.sample_out = nullptr;
+    timed_launch(ix, s, "analogy_filter", [&] {
+      if (M == 1) hipLaunchKernelGGL((an_filter_kernel<1, false>), dim3(grid_for(N)), dim3(EXF_WG), flds, s, fa);
+      else hipLaunchKernelGGL((an_filter_kernel<3, false>), dim3(grid_for(N)), dim3(EXF_WG), flds, s, fa);
+    });
+    HIP_TRY(hipGetLastError());
+    AnRefineArgs ra;
+    ra.rows = ix->coarse; ra.cols = cols; ra.cand = fa.cand; ra.cand_cnt = cand_cnt; ra.qeps = qeps; ra.in_rows = in_rows; ra.viol = ix->viol;
+    ra.flag = flags + p; ra.cand_total = flags + passes + p; ra.cap = cap; ra.d = d; ra.k = k; ra.count_checked = all ? 1 : 0; ra.ids = ix->ids;
+    ra.out_ids = d_ids + (size_t)a0 * k; ra.out_score = d_score + (size_t)a0 * k;
+    timed_launch(ix, s, "analogy_refine", [&] {
+      if (M == 1) hipLaunchKernelGGL((an_refine_kernel<1>), dim3((unsigned)np), dim3(64 * AN_RW), an_refine_lds(1, d), s, ra);
+      else hipLaunchKernelGGL((an_refine_kernel<3>), dim3((unsigned)np), dim3(64 * AN_RW), an_refine_lds(3, d), s, ra);
+    });
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
+extern "C" int freddy_gpu_exact_analogy(freddy_gpu_index_t* ix, int32_t method, const int32_t* triples, int32_t Q, int32_t k,
+                                        const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, double* out_score) {
+  // (the scalar arguments first: they are checked before the handle is looked at, so no device is needed to see these errors)
+  if (method != FREDDY_ANALOGY_3COSADD && method != FREDDY_ANALOGY_3COSMUL) return fail(FREDDY_E_ARG, "unknown analogy method %d", method);
+  if (Q < 0 || k <= 0 || n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad sizes");
+  if (Q > 0 && (!triples || !out_ids || !out_score)) return fail(FREDDY_E_ARG, "NULL buffer");
+  if (k > AN_MAXK) return fail(FREDDY_E_LIMIT, "k=%d exceeds the exact analogy's limit of %d", k, AN_MAXK);
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  const int M = method == FREDDY_ANALOGY_3COSMUL ? 3 : 1;
+  const int d = ix->d;
+  ix->an_stats[0] = ix->an_stats[1] = ix->an_stats[2] = 0;
+  if (std::max(an_scan_lds<1, 8>(d), an_scan_lds<3, 4>(d)) > AN_MAX_LDS) return fail(FREDDY_E_LIMIT, "d=%d too large for the exact analogy", d);
+  for (size_t i = 0; i < (size_t)Q * k; ++i) { out_ids[i] = -1; out_score[i] = -HUGE_VAL; }
+  if (Q == 0) return FREDDY_OK;
+  // the INNER JOINs: an analogy with an unknown id has no rows at all; the others, compacted
+  std::vector<int32_t> live, rows3;
+  for (int32_t q = 0; q < Q; ++q) {
+    int32_t r[3];
+    bool ok = true;
+    for (int m = 0; m < 3 && ok; ++m) {
+      auto it = std::lower_bound(ix->h_ids.begin(), ix->h_ids.end(), triples[(size_t)q * 3 + m]);
+      ok = it != ix->h_ids.end() && *it == triples[(size_t)q * 3 + m];
+      if (ok) r[m] = (int32_t)(it - ix->h_ids.begin());
+    }
+    if (!ok) continue;
+    live.push_back(q);
+    rows3.insert(rows3.end(), r, r + 3);
+  }
+  const int na = (int)live.size();
+  if (na == 0) return FREDDY_OK;
+  HIP_TRY(hipSetDevice(ix->device));
+  Workspace* ws = workspace_for(ix, ix->stream);
+  hipStream_t s = ix->stream;
+  const float* xb = ix->xb;
+  const int32_t* pos = nullptr;
+  int64_t n_rows = ix->N, n_blocks = ix->n_blocks;
+  if (subset_ids) {
+    std::vector<int32_t> rows;
+    rows.reserve((size_t)n_subset);
+    for (int64_t i = 0; i < n_subset; ++i) {
+      auto it = std::lower_bound(ix->h_ids.begin(), ix->h_ids.end(), subset_ids[i]);
+      if (it != ix->h_ids.end() && *it == subset_ids[i]) rows.push_back((int32_t)(it - ix->h_ids.begin()));
+    }
+    std::sort(rows.begin(), rows.end());
+    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+    n_rows = (int64_t)rows.size();
+    n_blocks = (n_rows + 63) / 64;
+    if (n_rows == 0) return FREDDY_OK;
+    if (ws->w_sub_rows.ensure(sizeof(int32_t) * rows.size()) || ws->w_sub_pos.ensure(sizeof(int32_t) * (size_t)n_blocks * 64) ||
+        ws->w_resid.ensure(sizeof(float) * (size_t)n_blocks * d * 64))
+      return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+    HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(block_rows_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, ix->coarse, ws->w_sub_rows.as<int32_t>(), n_rows,
+                       ws->w_resid.as<float>(), ws->w_sub_pos.as<int32_t>(), d);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));   // `rows` is a host temporary
+    xb = ws->w_resid.as<float>();
+    pos = ws->w_sub_pos.as<int32_t>();
+  }
+  const int passes = (na + AN_PASS - 1) / AN_PASS;
+  if (ws->w_rows.ensure(sizeof(int32_t) * rows3.size()) || ws->w_out_ids.ensure(sizeof(int32_t) * (size_t)na * k) ||
+      ws->w_out_dist.ensure(sizeof(double) * (size_t)na * k) || ws->w_cnt.ensure(sizeof(int32_t) * 2 * (size_t)passes))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  int32_t* d_rows = ws->w_rows.as<int32_t>();
+  int32_t* d_ids = ws->w_out_ids.as<int32_t>();
+  double* d_score = ws->w_out_dist.as<double>();
+  HIP_TRY(hipMemcpyAsync(d_rows, rows3.data(), sizeof(int32_t) * rows3.size(), hipMemcpyHostToDevice, s));
+  // filter + refine: the whole table, k <= 32, finite rows of a supported shape (exact kNN's eligibility)
+  // and the pass's query fragments must fit the LDS of a CU (an_filter_kernel holds all M tiles: 3CosMul with d > 416 does not)
+  const bool want_filter = !subset_ids && ix->exf_ok && ix->tune.exact_filter != 0 && (ix->tune.exact_filter == 1 || n_rows >= 8192) &&
+                           an_filter_lds(M, d) <= AN_MAX_LDS;
+  std::vector<int32_t> redo;   // passes the all-exact path computes
+  if (want_filter) {
+    if (int rc = analogy_filter(ix, ws, s, M, d_rows, na, k, d_ids, d_score, ws->w_cnt.as<int32_t>())) return rc;
+    std::vector<int32_t> flags(2 * (size_t)passes);
+    HIP_TRY(hipMemcpyAsync(flags.data(), ws->w_cnt.p, sizeof(int32_t) * 2 * passes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int p = 0; p < passes; ++p) {
+      if (flags[p]) redo.push_back(p);
+      else ix->an_stats[1] += flags[passes + p];
+    }
+    ix->an_stats[0] = passes;
+    ix->an_stats[2] = (int64_t)redo.size();
+  }
+  // the all-exact path: everything, or the passes the filter could not vouch for (in chunks that bound the partial lists)
+  const int chunk = 1024;
+  auto scan_range = [&](int a0, int n) -> int {
+    for (int c0 = a0; c0 < a0 + n; c0 += chunk) {
+      const int nc = std::min(chunk, a0 + n - c0);
+      if (int rc = analogy_scan(ix, ws, s, M, d_rows + (size_t)c0 * 3, nc, k, xb, pos, n_rows, n_blocks, d_ids + (size_t)c0 * k, d_score + (size_t)c0 * k))
+        return rc;
+    }
+    return 0;
+  };
+  if (!want_filter) {
+    if (int rc = scan_range(0, na)) return rc;
+  } else {
+    for (int p : redo) if (int rc = scan_range(p * AN_PASS, std::min(AN_PASS, na - p * AN_PASS))) return rc;
+  }
+  std::vector<int32_t> h_ids((size_t)na * k);
+  std::vector<double> h_score((size_t)na * k);
+  HIP_TRY(hipMemcpyAsync(h_ids.data(), d_ids, sizeof(int32_t) * h_ids.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(h_score.data(), d_score, sizeof(double) * h_score.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int a = 0; a < na; ++a) {
+    memcpy(out_ids + (size_t)live[a] * k, h_ids.data() + (size_t)a * k, sizeof(int32_t) * k);
+    memcpy(out_score + (size_t)live[a] * k, h_score.data() + (size_t)a * k, sizeof(double) * k);
+  }
+  return FREDDY_OK;
+}
+
+extern "C" int freddy_gpu_last_analogy_stats(const freddy_gpu_index_t* ix, int64_t* filter_passes, int64_t* candidates, int64_t* redone_passes) {
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (filter_passes) *filter_passes = ix->an_stats[0];
+  if (candidates) *candidates = ix->an_stats[1];
+  if (redone_passes) *redone_passes = ix->an_stats[2];
+  return FREDDY_OK;
+}
+
 // The kernels of this unit that want more than the default 64 KiB of dynamic LDS (a per-device function attribute).
 int raise_lds_limits_exact(int device) {
   static std::mutex mu;
@@ -341,9 +573,11 @@ int raise_lds_limits_exact(int device) {
   if ((size_t)device < done.size() && done[(size_t)device]) return 0;
   const void* kernels[] = {
       (const void*)&exf_filter_kernel<1, false>, (const void*)&exf_filter_kernel<2, false>, (const void*)&exf_filter_kernel<1, true>,
-      (const void*)&exf_filter_kernel<2, true>};
+      (const void*)&exf_filter_kernel<2, true>, (const void*)&an_filter_kernel<1, false>, (const void*)&an_filter_kernel<3, false>,
+      (const void*)&an_filter_kernel<1, true>, (const void*)&an_filter_kernel<3, true>, (const void*)&an_scan_kernel<1, 8>,
+      (const void*)&an_scan_kernel<3, 4>};
   for (const void* k : kernels)
-    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, AN_MAX_LDS));
   if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
   done[(size_t)device] = 1;
   return 0;

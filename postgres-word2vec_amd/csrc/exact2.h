@@ -208,6 +208,44 @@ struct ExfArgs {
   int cap;
 };
 
+// One strip of 32 rows against NT 32-column query tiles: acc[n] = the strip's rows . the tile's columns (hi.hi + hi.lo + lo.hi),
+// EXF_PF k-steps of row operands in flight.  xs = the strip's fragments + lane, qf = the tiles' fragments in LDS.
+// The analogy filter (analogy.h) runs this; exf_filter_kernel keeps its own copy of the same loop because routing it through
+// this helper moved that tuned kernel's register allocation (a different instruction stream for the same arithmetic).
+template <int NT>
+__device__ __forceinline__ void exf_strip_mfma(const h8v* __restrict__ xs, const h8v* qf, int T, int lane, f16acc (&acc)[NT]) {
+#pragma unroll
+  for (int n = 0; n < NT; ++n)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[n][v] = 0.0f;
+  // the strip's operands: [t][hi / lo][64 lanes], EXF_PF k-steps in flight
+  h8v ring[EXF_PF][2];
+  auto issue = [&](int slot, int t) {
+    ring[slot][0] = xs[(size_t)(2 * t) * 64];
+    ring[slot][1] = xs[(size_t)(2 * t + 1) * 64];
+  };
+#pragma unroll
+  for (int p = 0; p < EXF_PF; ++p) if (p < T) issue(p, p);
+  for (int t0 = 0; t0 < T; t0 += EXF_PF) {
+#pragma unroll
+    for (int p = 0; p < EXF_PF; ++p) {
+      const int t = t0 + p;
+      if (t < T) {
+        const h8v hi = ring[p][0], lo = ring[p][1];
+        if (t + EXF_PF < T) issue(p, t + EXF_PF);
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+          const h8v bh = qf[((size_t)(n * T + t) * 2 + 0) * 64 + lane];
+          const h8v bl = qf[((size_t)(n * T + t) * 2 + 1) * 64 + lane];
+          acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hi, bh, acc[n], 0, 0, 0);
+          acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hi, bl, acc[n], 0, 0, 0);
+          acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(lo, bh, acc[n], 0, 0, 0);
+        }
+      }
+    }
+  }
+}
+
 template <int NT, bool SAMPLE>
 __global__ __launch_bounds__(EXF_WG, 2) void exf_filter_kernel(ExfArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

@@ -263,6 +263,8 @@ struct freddy_gpu_index {
   // profiling
   bool profiling = false;
   std::map<std::string, ProfRec> prof;
+  // the last exact analogy call (freddy_gpu_last_analogy_stats): filter passes, candidates they refined, passes redone all-exact
+  int64_t an_stats[3] = {0, 0, 0};
 };
 
 template <class F>

@@ -16,6 +16,7 @@ FOUND_ROWS = 0
 FOUND_ACCEPTED = 1
 FOUND_BATCH_UDF = 2   # ivfadc_batch_search itself (W == 1): accepted-rows rule + its argmin cell limit of 1000
 METHOD_PQ, METHOD_EXACT, METHOD_PQ_PV = 0, 1, 2
+ANALOGY_METHODS = {"3cosadd": 0, "3cosmul": 1}   # include/freddy_gpu.h FREDDY_ANALOGY_*
 
 EXPORTS = [
     "freddy_gpu_pin_pq", "freddy_gpu_pin_ivf", "freddy_gpu_pin_ivpq", "freddy_gpu_unpin",
@@ -26,7 +27,8 @@ EXPORTS = [
     "freddy_gpu_encode", "freddy_gpu_set_option", "freddy_gpu_last_track", "freddy_gpu_last_probed_cells", "freddy_gpu_coarse_bound_checked",
     "freddy_gpu_insert_quantize", "freddy_gpu_append_rows", "freddy_gpu_update_codebook", "freddy_gpu_kmeans",
     "freddy_gpu_host_alloc", "freddy_gpu_host_free", "freddy_gpu_pin_ivf_multi", "freddy_gpu_replica_count",
-    "freddy_gpu_last_track_sized", "freddy_gpu_abi_version",
+    "freddy_gpu_last_track_sized", "freddy_gpu_abi_version", "freddy_gpu_exact_analogy",
+    "freddy_gpu_last_analogy_stats",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 
@@ -104,6 +106,9 @@ def load():
     lib.freddy_gpu_pin_vectors.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.freddy_gpu_exact_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                             C.c_void_p, C.c_void_p]
+    lib.freddy_gpu_exact_analogy.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                             C.c_void_p, C.c_void_p]
+    lib.freddy_gpu_last_analogy_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.freddy_gpu_pq_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.freddy_gpu_ivfadc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -285,6 +290,31 @@ class VectorIndex(_Index):
         _check(self.lib.freddy_gpu_exact_search(self.h, _p(qs), Q, k, _p(sub), 0 if sub is None else sub.size,
                                                 _p(out_i), _p(out_s)))
         return out_i, out_s
+
+    def analogy(self, triples, k=1, method="3cosmul", subset_ids=None):
+        """Exact analogies (freddy_gpu_exact_analogy): triples [Q][3] of row ids (w1, w2, w3) -> (ids[Q,k], scores[Q,k] float64),
+        ORDER BY score DESC, id ASC, the three inputs excluded; (-1, -inf) where there is no row (or an input id is unknown).
+        method: "3cosadd" (the binary32 score widened) or "3cosmul" (float8)."""
+        if method not in ANALOGY_METHODS:
+            raise ValueError(f"method must be one of {sorted(ANALOGY_METHODS)}")
+        t = _i32(triples).reshape(-1, 3)
+        Q = t.shape[0]
+        out_i = np.empty((Q, k), np.int32)
+        out_s = np.empty((Q, k), np.float64)
+        sub = None if subset_ids is None else _i32(subset_ids)
+        _check(self.lib.freddy_gpu_exact_analogy(self.h, ANALOGY_METHODS[method], _p(t), Q, k, _p(sub), 0 if sub is None else sub.size,
+                                                 _p(out_i), _p(out_s)))
+        return out_i, out_s
+
+    def last_analogy_stats(self):
+        """The last analogy() call (freddy_gpu_last_analogy_stats): filter passes, candidates they refined, passes redone all-exact."""
+        v = [C.c_int64(0) for _ in range(3)]
+        _check(self.lib.freddy_gpu_last_analogy_stats(self.h, *(C.byref(x) for x in v)))
+        return {"filter_passes": v[0].value, "candidates": v[1].value, "redone_passes": v[2].value}
+
+    def bound_checked(self):
+        """Rows the self-check has compared with their bracket (option check_brackets bits 2 / 3 refine every row)."""
+        return int(self.lib.freddy_gpu_filter_bound_checked(self.h))
 
 
 class IVFIndex(_Index):

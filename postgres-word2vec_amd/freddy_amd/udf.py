@@ -38,6 +38,8 @@ def load():
         _lib.freddy_udf_last_error.restype = C.c_char_p
         _lib.freddy_get_confidence_value.restype = C.c_float
         _lib.freddy_set_confidence_value.argtypes = [C.c_void_p, C.c_float]
+        _lib.freddy_get_analogy_function.restype = C.c_char_p
+        _lib.freddy_get_analogy_in_function.restype = C.c_char_p
     return _lib
 
 
@@ -224,6 +226,27 @@ class Session:
         r, ids = C.c_int32(-1), _i32(input_ids)
         self._check(self.lib.analogy_3cosadd_in_ivpq(self.h, int(id1), int(id2), int(id3), _p(ids), ids.size, C.byref(r)))
         return r.value
+
+    # exact analogies and the dispatchers (freddy--0.0.1.sql:1231-1315, 269-297); -1 where the SQL returns NULL
+    def _analogy3(self, fn, id1, id2, id3):
+        r = C.c_int32(-1)
+        self._check(fn(self.h, int(id1), int(id2), int(id3), C.byref(r)))
+        return r.value
+
+    def _analogy4(self, fn, id1, id2, id3, input_ids):
+        r, ids = C.c_int32(-1), _i32(input_ids)
+        self._check(fn(self.h, int(id1), int(id2), int(id3), _p(ids), ids.size, C.byref(r)))
+        return r.value
+
+    def analogy_3cosadd(self, id1, id2, id3): return self._analogy3(self.lib.analogy_3cosadd, id1, id2, id3)
+    def analogy_3cosmul(self, id1, id2, id3): return self._analogy3(self.lib.analogy_3cosmul, id1, id2, id3)
+    def analogy_3cosadd_in(self, id1, id2, id3, input_ids): return self._analogy4(self.lib.analogy_3cosadd_in, id1, id2, id3, input_ids)
+    def analogy(self, a, b, c): return self._analogy3(self.lib.analogy, a, b, c)
+    def analogy_in(self, w1, w2, w3, input_ids): return self._analogy4(self.lib.analogy_in, w1, w2, w3, input_ids)
+    def set_analogy_function(self, name): self._check(self.lib.freddy_set_analogy_function(self.h, str(name).encode()))
+    def set_analogy_in_function(self, name): self._check(self.lib.freddy_set_analogy_in_function(self.h, str(name).encode()))
+    def get_analogy_function_name(self): return self.lib.freddy_get_analogy_function(self.h).decode()
+    def get_analogy_in_function_name(self): return self.lib.freddy_get_analogy_in_function(self.h).decode()
 
     def _cluster(self, fn, token_ids, k, draws):
         ids = _i32(token_ids)

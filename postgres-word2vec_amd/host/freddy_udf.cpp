@@ -86,6 +86,8 @@ struct freddy_session {
   std::vector<float> coarse;                                 // [C][d]
   int C = 0;
   int32_t pq_max_id = 0, fine_max_id = 0, ivpq_max_id = 0;
+  // set_analogy_function / set_analogy_in_function (freddy--0.0.1.sql:198-199)
+  std::string analogy_fn = "analogy_3cosadd", analogy_in_fn = "analogy_3cosadd_in";
 };
 
 extern "C" {
@@ -905,6 +907,64 @@ int analogy_3cosadd_in_pq(freddy_session_t* s, int32_t id1, int32_t id2, int32_t
 }
 int analogy_3cosadd_in_ivpq(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids, int32_t n_ids, int32_t* result) {
   return analogy_in_common(s, true, id1, id2, id3, input_ids, n_ids, result);
+}
+
+// ---- exact analogies and the dispatchers      freddy--0.0.1.sql:1231-1315, 269-297 --------------------------------
+static int exact_analogy(freddy_session_t* s, int32_t method, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids,
+                         int32_t n_ids, bool subset, int32_t* result) {
+  if (!s || !result || n_ids < 0 || (n_ids > 0 && !input_ids)) return fail(-1, "bad argument");
+  if (s->norm_ids.empty()) return fail(-1, "google_vecs_norm is not loaded");
+  *result = -1;
+  if (int rc = ensure_vecs(s)) return rc;
+  // an empty set is a non-NULL pointer with a count of 0 (NULL would mean the whole table)
+  const int32_t triple[3] = {id1, id2, id3}, unused = 0;
+  const int32_t* sub = subset ? (n_ids ? input_ids : &unused) : nullptr;
+  double score = 0;
+  if (int rc = freddy_gpu_exact_analogy(s->vecs, method, triple, 1, 1, sub, subset ? n_ids : 0, result, &score))
+    return gpu_fail(rc);
+  return 0;
+}
+int analogy_3cosadd(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, int32_t* result) {
+  return exact_analogy(s, FREDDY_ANALOGY_3COSADD, id1, id2, id3, nullptr, 0, false, result);
+}
+int analogy_3cosmul(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, int32_t* result) {
+  return exact_analogy(s, FREDDY_ANALOGY_3COSMUL, id1, id2, id3, nullptr, 0, false, result);
+}
+int analogy_3cosadd_in(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids, int32_t n_ids, int32_t* result) {
+  return exact_analogy(s, FREDDY_ANALOGY_3COSADD, id1, id2, id3, input_ids, n_ids, true, result);
+}
+
+int freddy_set_analogy_function(freddy_session_t* s, const char* name) {
+  if (!s || !name) return fail(-1, "bad argument");
+  s->analogy_fn = name;
+  return 0;
+}
+const char* freddy_get_analogy_function(const freddy_session_t* s) { return s ? s->analogy_fn.c_str() : ""; }
+int freddy_set_analogy_in_function(freddy_session_t* s, const char* name) {
+  if (!s || !name) return fail(-1, "bad argument");
+  s->analogy_in_fn = name;
+  return 0;
+}
+const char* freddy_get_analogy_in_function(const freddy_session_t* s) { return s ? s->analogy_in_fn.c_str() : ""; }
+
+// EXECUTE format('SELECT * FROM %s(''%s'', ''%s'',''%s'')', get_analogy_function_name(), ...)
+int analogy(freddy_session_t* s, int32_t a, int32_t b, int32_t c, int32_t* result) {
+  if (!s || !result) return fail(-1, "bad argument");
+  const std::string& f = s->analogy_fn;
+  if (f == "analogy_3cosadd") return analogy_3cosadd(s, a, b, c, result);
+  if (f == "analogy_3cosmul") return analogy_3cosmul(s, a, b, c, result);
+  if (f == "analogy_3cosadd_pq") return analogy_3cosadd_pq(s, a, b, c, result);
+  if (f == "analogy_3cosadd_ivfadc") return analogy_3cosadd_ivfadc(s, a, b, c, result);
+  return fail(-1, "function %s(unknown, unknown, unknown) does not exist", f.c_str());
+}
+// EXECUTE format('SELECT * FROM %s(''%s'', ''%s'',''%s'', ''%s''::varchar(100)[])', get_analogy_in_function_name(), ...)
+int analogy_in(freddy_session_t* s, int32_t w1, int32_t w2, int32_t w3, const int32_t* input_ids, int32_t n_ids, int32_t* result) {
+  if (!s || !result) return fail(-1, "bad argument");
+  const std::string& f = s->analogy_in_fn;
+  if (f == "analogy_3cosadd_in") return analogy_3cosadd_in(s, w1, w2, w3, input_ids, n_ids, result);
+  if (f == "analogy_3cosadd_in_pq") return analogy_3cosadd_in_pq(s, w1, w2, w3, input_ids, n_ids, result);
+  if (f == "analogy_3cosadd_in_ivpq") return analogy_3cosadd_in_ivpq(s, w1, w2, w3, input_ids, n_ids, result);
+  return fail(-1, "function %s(unknown, unknown, unknown, character varying[]) does not exist", f.c_str());
 }
 
 // ---- cluster_exact / cluster_pq / cluster_ivpq = generic_cluster      freddy--0.0.1.sql:1086-1209 --------------
