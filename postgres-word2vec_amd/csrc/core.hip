@@ -94,14 +94,12 @@ void free_index(freddy_gpu_index* ix) {
   (void)hipDeviceSynchronize();   // (every stream that searched on this handle, without touching a caller's stream handle)
   for (Workspace& w : ix->ws) w.release();
   for (DevBuf* b : {&ix->exf_qfrag, &ix->exf_small, &ix->exf_sample, &ix->exf_cand, &ix->exf_xf}) b->release();
-  if (ix->hio_in) { (void)hipHostFree(ix->hio_in); ix->hio_in = nullptr; ix->hio_in_cap = 0; }
-  if (ix->hio_out) { (void)hipHostFree(ix->hio_out); ix->hio_out = nullptr; ix->hio_out_cap = 0; }
+  ix->hio_in.release(); ix->hio_out.release();
   for (Lane& l : ix->lanes) {
     if (l.stream && l.stream != ix->stream) (void)hipStreamDestroy(l.stream);
     for (LaneSlot& c : l.slot) {
       if (c.done) (void)hipEventDestroy(c.done);
-      if (c.h_in) (void)hipHostFree(c.h_in);
-      if (c.h_out) (void)hipHostFree(c.h_out);
+      c.h_in.release(); c.h_out.release();
       c.d_q.release(); c.d_ids.release(); c.d_dist.release();
       c = LaneSlot();
     }

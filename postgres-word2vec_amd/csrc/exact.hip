@@ -60,6 +60,31 @@ int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n) {
   return 0;
 }
 
+// What the filter passes over the whole table (exact kNN, analogies) share.  The threshold's sample: whole 32-row strips of
+// REAL rows (a zero-padded row would be a similarity of 0 that no row has), spread evenly over the table; the candidate
+// buffer: 8192 rows per query (every row under the self-check that refines every row).
+struct FilterPlan {
+  int n_sample;
+  int64_t sample_stride;
+  int cap;
+};
+static FilterPlan filter_plan(int64_t N, bool refine_all) {
+  const int64_t full_strips = N / 32;
+  const int n_sample = (int)(std::min<int64_t>(full_strips, EXF_SAMPLE / 32) * 32);
+  return {n_sample, n_sample > 0 ? std::max<int64_t>(1, full_strips / (n_sample / 32)) : 1, (int)(refine_all ? N : std::min<int64_t>(N, 8192))};
+}
+// workgroups of a filter kernel over `rows` rows: one per 256 rows, at most two per CU
+static unsigned filter_grid(const freddy_gpu_index* ix, int64_t rows) {
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, (int64_t)ix->n_cus * 2));
+}
+// the self-check counters the refine kernels write (allocated by the handle's first filter + refine call)
+static int ensure_viol(freddy_gpu_index* ix) {
+  if (ix->viol) return 0;
+  HIP_TRY(hipMalloc((void**)&ix->viol, 4 * sizeof(int32_t)));
+  HIP_TRY(hipMemset(ix->viol, 0, 4 * sizeof(int32_t)));
+  return 0;
+}
+
 // The filter + refine path for all rows of the table.  *fell_back = 1: a candidate buffer overflowed or a query was not
 // finite -- nothing was written, the caller runs the all-exact kernels.
 // q_copy: NULL, or device memory for the queries when d_queries is mapped host memory (exf_prep_kernel copies them).
@@ -71,22 +96,13 @@ static int exact_filter_search(freddy_gpu_index* ix, Workspace* ws, hipStream_t 
   const int d = ix->d, T = (d + 15) / 16, L = k, V = pick_V(L);
   const int64_t N = ix->N;
   const bool all = (ix->tune.check_brackets & 4) != 0;
-  const int64_t cap64 = all ? N : std::min<int64_t>(N, 8192);
-  const int cap = (int)cap64;
-  // the threshold's sample: whole 32-row strips of REAL rows (a zero-padded row would be a similarity of 0 that no row has),
-  // spread evenly over the table
-  const int64_t full_strips = N / 32;
-  const int n_sample = (int)(std::min<int64_t>(full_strips, EXF_SAMPLE / 32) * 32);
-  const int64_t sample_stride = n_sample > 0 ? std::max<int64_t>(1, full_strips / (n_sample / 32)) : 1;
+  const FilterPlan fp = filter_plan(N, all);
+  const int n_sample = fp.n_sample, cap = fp.cap;
   // small per-call state: [0..63] thr, [64..127] qeps, [128..191] qunscale, [192..255] cand_cnt, [256] qbad
   if (ix->exf_small.ensure(4096) || ix->exf_qfrag.ensure((size_t)2 * T * 2 * 64 * 16) ||
-      ix->exf_sample.ensure(sizeof(float) * (size_t)EXF_QT * n_sample) || ix->exf_cand.ensure(sizeof(uint2) * (size_t)EXF_QT * cap) ||
-      false)
+      ix->exf_sample.ensure(sizeof(float) * (size_t)EXF_QT * n_sample) || ix->exf_cand.ensure(sizeof(uint2) * (size_t)EXF_QT * cap))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  if (!ix->viol) {
-    HIP_TRY(hipMalloc((void**)&ix->viol, 4 * sizeof(int32_t)));
-    HIP_TRY(hipMemset(ix->viol, 0, 4 * sizeof(int32_t)));
-  }
+  if (int rc = ensure_viol(ix)) return rc;
   if (ix->exf_dirty) {   // (the handle's first call, or the one after a call that failed part-way: the verdict words and the arrival counter may be anything; a call's last workgroup leaves them at zero)
     HIP_TRY(hipMemsetAsync(ix->exf_small.as<float>() + 256, 0, 8, s));
     HIP_TRY(hipMemsetAsync(ix->viol + 3, 0, 4, s));
@@ -113,12 +129,11 @@ static int exact_filter_search(freddy_gpu_index* ix, Workspace* ws, hipStream_t 
     timed_launch(ix, s, "exact_prep", [&] { hipLaunchKernelGGL(exf_prep_kernel, dim3(EXF_QT), dim3(256), 0, s, pa); });
     HIP_TRY(hipGetLastError());
     ExfArgs fa;
-    fa.xf = ix->exf_xf.as<h8v>(); fa.n_rows = n_sample; fa.strip_stride = sample_stride; fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>();
+    fa.xf = ix->exf_xf.as<h8v>(); fa.n_rows = n_sample; fa.strip_stride = fp.sample_stride; fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>();
     fa.qunscale = qunscale; fa.sample_out = ix->exf_sample.as<float>(); fa.thr = thr; fa.cand_cnt = cand_cnt; fa.cand = ix->exf_cand.as<uint2>(); fa.cap = cap;
-    auto grid_for = [&](int64_t rows) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, (int64_t)ix->n_cus * 2)); };
     timed_launch(ix, s, "exact_sample", [&] {
-      if (NT == 1) hipLaunchKernelGGL((exf_filter_kernel<1, true>), dim3(grid_for(n_sample)), dim3(EXF_WG), lds1, s, fa);
-      else hipLaunchKernelGGL((exf_filter_kernel<2, true>), dim3(grid_for(n_sample)), dim3(EXF_WG), lds2, s, fa);
+      if (NT == 1) hipLaunchKernelGGL((exf_filter_kernel<1, true>), dim3(filter_grid(ix, n_sample)), dim3(EXF_WG), lds1, s, fa);
+      else hipLaunchKernelGGL((exf_filter_kernel<2, true>), dim3(filter_grid(ix, n_sample)), dim3(EXF_WG), lds2, s, fa);
     });
     HIP_TRY(hipGetLastError());
     ExfThrArgs ta;
@@ -127,8 +142,8 @@ static int exact_filter_search(freddy_gpu_index* ix, Workspace* ws, hipStream_t 
     HIP_TRY(hipGetLastError());
     fa.n_rows = N; fa.strip_stride = 1; fa.sample_out = nullptr;
     timed_launch(ix, s, "exact_filter", [&] {
-      if (NT == 1) hipLaunchKernelGGL((exf_filter_kernel<1, false>), dim3(grid_for(N)), dim3(EXF_WG), lds1, s, fa);
-      else hipLaunchKernelGGL((exf_filter_kernel<2, false>), dim3(grid_for(N)), dim3(EXF_WG), lds2, s, fa);
+      if (NT == 1) hipLaunchKernelGGL((exf_filter_kernel<1, false>), dim3(filter_grid(ix, N)), dim3(EXF_WG), lds1, s, fa);
+      else hipLaunchKernelGGL((exf_filter_kernel<2, false>), dim3(filter_grid(ix, N)), dim3(EXF_WG), lds2, s, fa);
     });
     HIP_TRY(hipGetLastError());
     ExfRefineArgs ra;
@@ -193,6 +208,28 @@ extern "C" int freddy_gpu_pin_vectors(const freddy_vec_desc* t, int device, fred
   return FREDDY_OK;
 }
 
+// "id = ANY(subset)" on a vector handle: the subset's rows (rows_of_ids) re-blocked into w_resid, their positions in w_sub_pos,
+// for the all-exact kernels.  An empty subset launches nothing (its buffers still exist).  Synchronises the stream.
+static int vec_subset(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const std::vector<int32_t>& rows, const float** xb,
+                      const int32_t** pos, int64_t* n_rows, int64_t* n_blocks) {
+  *n_rows = (int64_t)rows.size();
+  *n_blocks = (*n_rows + 63) / 64;
+  if (ws->w_sub_rows.ensure(sizeof(int32_t) * std::max<size_t>(rows.size(), 1)) ||
+      ws->w_sub_pos.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(*n_blocks, 1) * 64) ||
+      ws->w_resid.ensure(sizeof(float) * (size_t)std::max<int64_t>(*n_blocks, 1) * ix->d * 64))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  if (*n_rows) {
+    HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(block_rows_kernel, dim3((unsigned)*n_blocks), dim3(256), 0, s, ix->coarse, ws->w_sub_rows.as<int32_t>(), *n_rows,
+                       ws->w_resid.as<float>(), ws->w_sub_pos.as<int32_t>(), ix->d);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));   // `rows` is the caller's host memory
+  }
+  *xb = ws->w_resid.as<float>();
+  *pos = ws->w_sub_pos.as<int32_t>();
+  return 0;
+}
+
 extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k,
                                        const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_sim) {
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
@@ -208,31 +245,8 @@ extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* quer
   const float* xb = ix->xb;
   const int32_t* pos = nullptr;
   int64_t n_rows = ix->N, n_blocks = ix->n_blocks;
-  if (subset_ids) {
-    std::vector<int32_t> rows;
-    rows.reserve((size_t)n_subset);
-    for (int64_t i = 0; i < n_subset; ++i) {
-      auto it = std::lower_bound(ix->h_ids.begin(), ix->h_ids.end(), subset_ids[i]);
-      if (it != ix->h_ids.end() && *it == subset_ids[i]) rows.push_back((int32_t)(it - ix->h_ids.begin()));
-    }
-    std::sort(rows.begin(), rows.end());
-    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
-    n_rows = (int64_t)rows.size();
-    n_blocks = (n_rows + 63) / 64;
-    if (ws->w_sub_rows.ensure(sizeof(int32_t) * std::max<size_t>(rows.size(), 1)) ||
-        ws->w_sub_pos.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(n_blocks, 1) * 64) ||
-        ws->w_resid.ensure(sizeof(float) * (size_t)std::max<int64_t>(n_blocks, 1) * d * 64))
-      return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-    if (n_rows) {
-      HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(block_rows_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, ix->coarse, ws->w_sub_rows.as<int32_t>(), n_rows,
-                         ws->w_resid.as<float>(), ws->w_sub_pos.as<int32_t>(), d);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipStreamSynchronize(s));   // `rows` is a host temporary
-    }
-    xb = ws->w_resid.as<float>();
-    pos = ws->w_sub_pos.as<int32_t>();
-  }
+  if (subset_ids)   // (an empty subset: the scan below finds nothing)
+    if (int rc = vec_subset(ix, ws, s, rows_of_ids(ix->h_ids, subset_ids, n_subset), &xb, &pos, &n_rows, &n_blocks)) return rc;
   // Filter + refine (exact2.h): the whole table, k <= 32, finite rows of a supported shape; identical lists.
   const bool want_filter = !subset_ids && ix->exf_ok && k <= 32 && ix->tune.exact_filter != 0 &&
                            (ix->tune.exact_filter == 1 || n_rows >= 8192) && n_rows >= 1;
@@ -242,19 +256,14 @@ extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* quer
     const size_t n_out = (size_t)Q * k, q_bytes = sizeof(float) * (size_t)Q * d;
     const bool q_pinned = q_bytes <= (256u << 10);
     const size_t out_bytes = (n_out * 8 + 8 + 255) & ~(size_t)255, need = out_bytes + (q_pinned ? q_bytes : 0);
-    if (need > ix->hio_out_cap) {
-      if (ix->hio_out) (void)hipHostFree(ix->hio_out);
-      ix->hio_out = nullptr; ix->hio_out_cap = 0;
-      if (hipHostMalloc(&ix->hio_out, need + need / 4 + 256, hipHostMallocDefault) != hipSuccess) { ix->hio_out = nullptr; return fail(FREDDY_E_NOMEM, "pinned staging allocation failed"); }
-      ix->hio_out_cap = need + need / 4 + 256;
-    }
+    if (ix->hio_out.ensure(need)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
     void* dp = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&dp, ix->hio_out, 0));
-    int32_t* const h_out = static_cast<int32_t*>(ix->hio_out);
+    HIP_TRY(hipHostGetDevicePointer(&dp, ix->hio_out.p, 0));
+    int32_t* const h_out = ix->hio_out.as<int32_t>();
     const float* d_q = nullptr;
     if (ws->w_q.ensure(q_bytes)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
     if (q_pinned) {
-      memcpy(static_cast<char*>(ix->hio_out) + out_bytes, queries, q_bytes);
+      memcpy(ix->hio_out.as<char>() + out_bytes, queries, q_bytes);
       d_q = reinterpret_cast<const float*>(static_cast<char*>(dp) + out_bytes);
     } else {
       HIP_TRY(hipMemcpyAsync(ws->w_q.p, queries, q_bytes, hipMemcpyHostToDevice, s));
@@ -303,29 +312,21 @@ extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* quer
     }
   } else {
     timed_launch(ix, s, "exact_scan", [&] {
-      switch (V) {
-        case 1: if (EX_QT == 16) hipLaunchKernelGGL((exact_scan_kernel<1, 16>), grid, dim3(EX_WG), lds, s, ea);
-                else hipLaunchKernelGGL((exact_scan_kernel<1, 8>), grid, dim3(EX_WG), lds, s, ea);
-                break;
-        case 2: if (EX_QT == 16) hipLaunchKernelGGL((exact_scan_kernel<2, 16>), grid, dim3(EX_WG), lds, s, ea);
-                else hipLaunchKernelGGL((exact_scan_kernel<2, 8>), grid, dim3(EX_WG), lds, s, ea);
-                break;
-        case 4: if (EX_QT == 16) hipLaunchKernelGGL((exact_scan_kernel<4, 16>), grid, dim3(EX_WG), lds, s, ea);
-                else hipLaunchKernelGGL((exact_scan_kernel<4, 8>), grid, dim3(EX_WG), lds, s, ea);
-                break;
-        case 8: hipLaunchKernelGGL((exact_scan_kernel<8, 8>), grid, dim3(EX_WG), lds, s, ea); break;
-        default: hipLaunchKernelGGL((exact_scan_kernel<16, 8>), grid, dim3(EX_WG), lds, s, ea); break;
-      }
+      with_V(V, [&](auto v) {   // (query tiles of 16 only for V <= 4: ex_qt)
+        constexpr int VV = decltype(v)::value;
+        if constexpr (VV <= 4) {
+          if (EX_QT == 16) { hipLaunchKernelGGL((exact_scan_kernel<VV, 16>), grid, dim3(EX_WG), lds, s, ea); return; }
+        }
+        hipLaunchKernelGGL((exact_scan_kernel<VV, 8>), grid, dim3(EX_WG), lds, s, ea);
+      });
     });
     HIP_TRY(hipGetLastError());
     timed_launch(ix, s, "exact_merge", [&] {
-      switch (V) {
-        case 1: hipLaunchKernelGGL((exact_merge_kernel<1>), dim3(Q), dim3(16 * 64), (size_t)16 * 64 * (1 + 1) * sizeof(u64), s, ea.part, ppq, L, k, ix->ids, ws->w_out_ids.as<int32_t>(), ws->w_out_dist.as<float>()); break;
-        case 2: hipLaunchKernelGGL((exact_merge_kernel<2>), dim3(Q), dim3(16 * 64), (size_t)16 * 64 * (2 + 1) * sizeof(u64), s, ea.part, ppq, L, k, ix->ids, ws->w_out_ids.as<int32_t>(), ws->w_out_dist.as<float>()); break;
-        case 4: hipLaunchKernelGGL((exact_merge_kernel<4>), dim3(Q), dim3(16 * 64), (size_t)16 * 64 * (4 + 1) * sizeof(u64), s, ea.part, ppq, L, k, ix->ids, ws->w_out_ids.as<int32_t>(), ws->w_out_dist.as<float>()); break;
-        case 8: hipLaunchKernelGGL((exact_merge_kernel<8>), dim3(Q), dim3(8 * 64), (size_t)8 * 64 * (8 + 1) * sizeof(u64), s, ea.part, ppq, L, k, ix->ids, ws->w_out_ids.as<int32_t>(), ws->w_out_dist.as<float>()); break;
-        default: hipLaunchKernelGGL((exact_merge_kernel<16>), dim3(Q), dim3(4 * 64), (size_t)4 * 64 * (16 + 1) * sizeof(u64), s, ea.part, ppq, L, k, ix->ids, ws->w_out_ids.as<int32_t>(), ws->w_out_dist.as<float>()); break;
-      }
+      with_V(V, [&](auto v) {   // (16 waves per query up to V = 4, then 64 / V)
+        constexpr int VV = decltype(v)::value, NW = VV <= 4 ? 16 : 64 / VV;
+        hipLaunchKernelGGL((exact_merge_kernel<VV>), dim3(Q), dim3(NW * 64), (size_t)NW * 64 * (VV + 1) * sizeof(u64), s, ea.part, ppq, L, k, ix->ids,
+                           ws->w_out_ids.as<int32_t>(), ws->w_out_dist.as<float>());
+      });
     });
     HIP_TRY(hipGetLastError());
   }
@@ -375,19 +376,14 @@ static int analogy_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, in
   const int d = ix->d, T = (d + 15) / 16;
   const int64_t N = ix->N;
   const bool all = (ix->tune.check_brackets & 8) != 0;
-  const int cap = (int)(all ? N : std::min<int64_t>(N, 8192));
-  const int64_t full_strips = N / 32;
-  const int n_sample = (int)(std::min<int64_t>(full_strips, EXF_SAMPLE / 32) * 32);
-  const int64_t sample_stride = n_sample > 0 ? std::max<int64_t>(1, full_strips / (n_sample / 32)) : 1;
+  const FilterPlan fp = filter_plan(N, all);
+  const int n_sample = fp.n_sample, cap = fp.cap;
   const int passes = (na + AN_PASS - 1) / AN_PASS;
   // per-pass state: [0, 256) tau (double [32]), [256, 640) eps, [640, 1024) unscale (float [96]), [1024, 1152) candidate counts
   if (ws->w_found.ensure(2048) || ix->exf_qfrag.ensure((size_t)M * T * 2 * 64 * 16) || ws->w_qc.ensure(sizeof(float) * (size_t)M * AN_PASS * d) ||
       ix->exf_sample.ensure(sizeof(double) * (size_t)AN_PASS * std::max(n_sample, 1)) || ix->exf_cand.ensure(sizeof(uint4) * (size_t)AN_PASS * cap))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  if (!ix->viol) {
-    HIP_TRY(hipMalloc((void**)&ix->viol, 4 * sizeof(int32_t)));
-    HIP_TRY(hipMemset(ix->viol, 0, 4 * sizeof(int32_t)));
-  }
+  if (int rc = ensure_viol(ix)) return rc;
   char* sm = ws->w_found.as<char>();
   double* thr = reinterpret_cast<double*>(sm);
   float* qeps = reinterpret_cast<float*>(sm + 256);
@@ -395,7 +391,6 @@ static int analogy_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, in
   int32_t* cand_cnt = reinterpret_cast<int32_t*>(sm + 1024);
   float* cols = ws->w_qc.as<float>();
   HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int32_t) * 2 * passes, s));
-  auto grid_for = [&](int64_t rows) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, (int64_t)ix->n_cus * 2)); };
   const size_t flds = an_filter_lds(M, d);
   for (int p = 0; p < passes; ++p) {
     const int a0 = p * AN_PASS, np = std::min(AN_PASS, na - a0);
@@ -411,13 +406,13 @@ static int analogy_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, in
     timed_launch(ix, s, "analogy_prep", [&] { hipLaunchKernelGGL(exf_prep_kernel, dim3((unsigned)(M * AN_PASS)), dim3(256), 0, s, pa); });
     HIP_TRY(hipGetLastError());
     AnFilterArgs fa;
-    fa.xf = ix->exf_xf.as<h8v>(); fa.n_rows = n_sample; fa.strip_stride = sample_stride; fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>();
+    fa.xf = ix->exf_xf.as<h8v>(); fa.n_rows = n_sample; fa.strip_stride = fp.sample_stride; fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>();
     fa.qunscale = qunscale; fa.qeps = qeps; fa.in_rows = in_rows; fa.na = np; fa.sample_out = ix->exf_sample.as<double>();
     fa.thr = thr; fa.cand_cnt = cand_cnt; fa.cand = ix->exf_cand.as<uint4>(); fa.cap = cap; fa.refine_all = all ? 1 : 0;
     if (n_sample > 0) {
       timed_launch(ix, s, "analogy_sample", [&] {
-        if (M == 1) hipLaunchKernelGGL((an_filter_kernel<1, true>), dim3(grid_for(n_sample)), dim3(EXF_WG), flds, s, fa);
-        else hipLaunchKernelGGL((an_filter_kernel<3, true>), dim3(grid_for(n_sample)), dim3(EXF_WG), flds, s, fa);
+        if (M == 1) hipLaunchKernelGGL((an_filter_kernel<1, true>), dim3(filter_grid(ix, n_sample)), dim3(EXF_WG), flds, s, fa);
+        else hipLaunchKernelGGL((an_filter_kernel<3, true>), dim3(filter_grid(ix, n_sample)), dim3(EXF_WG), flds, s, fa);
       });
       HIP_TRY(hipGetLastError());
     }
@@ -427,8 +422,8 @@ static int analogy_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, in
     HIP_TRY(hipGetLastError());
     fa.n_rows = N; fa.strip_stride = 1; fa.sample_out = nullptr;
     timed_launch(ix, s, "analogy_filter", [&] {
-      if (M == 1) hipLaunchKernelGGL((an_filter_kernel<1, false>), dim3(grid_for(N)), dim3(EXF_WG), flds, s, fa);
-      else hipLaunchKernelGGL((an_filter_kernel<3, false>), dim3(grid_for(N)), dim3(EXF_WG), flds, s, fa);
+      if (M == 1) hipLaunchKernelGGL((an_filter_kernel<1, false>), dim3(filter_grid(ix, N)), dim3(EXF_WG), flds, s, fa);
+      else hipLaunchKernelGGL((an_filter_kernel<3, false>), dim3(filter_grid(ix, N)), dim3(EXF_WG), flds, s, fa);
     });
     HIP_TRY(hipGetLastError());
     AnRefineArgs ra;
@@ -464,11 +459,7 @@ extern "C" int freddy_gpu_exact_analogy(freddy_gpu_index_t* ix, int32_t method, 
   for (int32_t q = 0; q < Q; ++q) {
     int32_t r[3];
     bool ok = true;
-    for (int m = 0; m < 3 && ok; ++m) {
-      auto it = std::lower_bound(ix->h_ids.begin(), ix->h_ids.end(), triples[(size_t)q * 3 + m]);
-      ok = it != ix->h_ids.end() && *it == triples[(size_t)q * 3 + m];
-      if (ok) r[m] = (int32_t)(it - ix->h_ids.begin());
-    }
+    for (int m = 0; m < 3 && ok; ++m) ok = (r[m] = row_of(ix->h_ids, triples[(size_t)q * 3 + m])) >= 0;
     if (!ok) continue;
     live.push_back(q);
     rows3.insert(rows3.end(), r, r + 3);
@@ -482,27 +473,9 @@ extern "C" int freddy_gpu_exact_analogy(freddy_gpu_index_t* ix, int32_t method, 
   const int32_t* pos = nullptr;
   int64_t n_rows = ix->N, n_blocks = ix->n_blocks;
   if (subset_ids) {
-    std::vector<int32_t> rows;
-    rows.reserve((size_t)n_subset);
-    for (int64_t i = 0; i < n_subset; ++i) {
-      auto it = std::lower_bound(ix->h_ids.begin(), ix->h_ids.end(), subset_ids[i]);
-      if (it != ix->h_ids.end() && *it == subset_ids[i]) rows.push_back((int32_t)(it - ix->h_ids.begin()));
-    }
-    std::sort(rows.begin(), rows.end());
-    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
-    n_rows = (int64_t)rows.size();
-    n_blocks = (n_rows + 63) / 64;
-    if (n_rows == 0) return FREDDY_OK;
-    if (ws->w_sub_rows.ensure(sizeof(int32_t) * rows.size()) || ws->w_sub_pos.ensure(sizeof(int32_t) * (size_t)n_blocks * 64) ||
-        ws->w_resid.ensure(sizeof(float) * (size_t)n_blocks * d * 64))
-      return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-    HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(block_rows_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, ix->coarse, ws->w_sub_rows.as<int32_t>(), n_rows,
-                       ws->w_resid.as<float>(), ws->w_sub_pos.as<int32_t>(), d);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));   // `rows` is a host temporary
-    xb = ws->w_resid.as<float>();
-    pos = ws->w_sub_pos.as<int32_t>();
+    const std::vector<int32_t> rows = rows_of_ids(ix->h_ids, subset_ids, n_subset);
+    if (rows.empty()) return FREDDY_OK;   // (before any launch: the lists stay empty)
+    if (int rc = vec_subset(ix, ws, s, rows, &xb, &pos, &n_rows, &n_blocks)) return rc;
   }
   const int passes = (na + AN_PASS - 1) / AN_PASS;
   if (ws->w_rows.ensure(sizeof(int32_t) * rows3.size()) || ws->w_out_ids.ensure(sizeof(int32_t) * (size_t)na * k) ||
@@ -565,20 +538,10 @@ extern "C" int freddy_gpu_last_analogy_stats(const freddy_gpu_index_t* ix, int64
   return FREDDY_OK;
 }
 
-// The kernels of this unit that want more than the default 64 KiB of dynamic LDS (a per-device function attribute).
-int raise_lds_limits_exact(int device) {
-  static std::mutex mu;
-  static std::vector<char> done;
-  std::lock_guard<std::mutex> g(mu);
-  if ((size_t)device < done.size() && done[(size_t)device]) return 0;
-  const void* kernels[] = {
-      (const void*)&exf_filter_kernel<1, false>, (const void*)&exf_filter_kernel<2, false>, (const void*)&exf_filter_kernel<1, true>,
-      (const void*)&exf_filter_kernel<2, true>, (const void*)&an_filter_kernel<1, false>, (const void*)&an_filter_kernel<3, false>,
-      (const void*)&an_filter_kernel<1, true>, (const void*)&an_filter_kernel<3, true>, (const void*)&an_scan_kernel<1, 8>,
-      (const void*)&an_scan_kernel<3, 4>};
-  for (const void* k : kernels)
-    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, AN_MAX_LDS));
-  if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
-  done[(size_t)device] = 1;
-  return 0;
+// The kernels of this unit that want more than the default 64 KiB of dynamic LDS.
+std::vector<LdsLimit> lds_limits_exact() {
+  const int b = (int)AN_MAX_LDS;
+  return {{&exf_filter_kernel<1, false>, b}, {&exf_filter_kernel<2, false>, b}, {&exf_filter_kernel<1, true>, b}, {&exf_filter_kernel<2, true>, b},
+          {&an_filter_kernel<1, false>, b},  {&an_filter_kernel<3, false>, b},  {&an_filter_kernel<1, true>, b},  {&an_filter_kernel<3, true>, b},
+          {&an_scan_kernel<1, 8>, b},        {&an_scan_kernel<3, 4>, b}};
 }

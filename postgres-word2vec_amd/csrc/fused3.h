@@ -1,6 +1,6 @@
 // fused3.h -- IVFADC LUT build + ADC scan + selection, role-specialised with TWO builder waves per SIMD.
 //
-// Same scheme as fused2.h (ivf_spec2_kernel: builders write slab(p+1) while gatherers read slab(p), one
+// Same scheme as the kernel's first generation (builders write slab(p+1) while gatherers read slab(p), one
 // LDS-only barrier per position, next entry's descriptor / residuals / slab 0 prepared in the shadow of
 // the current one; same slab arithmetic, selection and outputs).  What changes is the wave budget.  A
 // SIMD issues packed fp32 ~27 % faster from two waves than from one (2.31 vs 3.15 ns per
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_spec2_kernel(FusedArgs a) {
   float* slab = reinterpret_cast<float*>(smem);                                   // [2][K][G]
   uint32_t* colmin = reinterpret_cast<uint32_t*>(smem + a.desc_offset);           // [16][64]
   uint32_t* tau_s = colmin + 16 * 64;                                             // [16]
-  int32_t* dsc = reinterpret_cast<int32_t*>(smem + a.desc_offset + 4096 + 64);    // see fused.h / fused2.h
+  int32_t* dsc = reinterpret_cast<int32_t*>(smem + a.desc_offset + 4096 + 64);    // the entry's descriptor
   float* res = reinterpret_cast<float*>(smem + a.desc_offset + 4096 + 64 + 512);  // [G][M][SP]
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_spec2_kernel(FusedArgs a) {
       int32_t pid[RMAX];
 #pragma unroll
       for (int r = 0; r < RMAX; ++r) pid[r] = a.pos[row_block(r) * 64u + (uint32_t)lane];
-      // Selection on the distance bits (>= +0, so they order like the floats); see fused.h.  Column
+      // Selection on the distance bits (>= +0, so they order like the floats).  Column
       // minima (column = lane index over the 8 gatherer waves x 8 row slots) via LDS atomics.
       {
         bool dead[RMAX];

@@ -1,7 +1,7 @@
-// fused5.h -- the filter + refine scan of fused4.h with INTEGER slabs: one LDS access serves eight items, six
+// fused5.h -- the filter + refine scan (refine.h) with INTEGER slabs: one LDS access serves eight items, six
 // phases instead of twelve.  (DESIGN.md 5.3c has the measurements.)
 //
-// What bounds ivf_filter_kernel (fused4.h) in its main loop is the LDS pipe: per position 48 KB of fp32 slab are
+// What bounded the fp32-slab filter scan this one replaced in its main loop was the LDS pipe: per position 48 KB of fp32 slab are
 // written (48 wave-level ds_write_b128) and gathered (8 waves x 8 rows x <= 3 ds_read_b128, a third of the read
 // cycles being bank conflicts), 87 % of the phase (rocprofv3 SQ_LDS_IDX_ACTIVE / SQ_LDS_BANK_CONFLICT) -- and the
 // cost of a gather is per ACCESS, not per byte (tools/lab/ubench6.hip).  Here a slab entry is the table's own 16-bit
@@ -22,7 +22,7 @@
 //     needs it -- WITHOUT the item's constant OFF: the selection compares floats (a constant shift changes neither
 //     the order nor tau' + E); OFF is added for the survivors only (s = s' + OFF > 0, the bits the merge expects).
 //
-// The bound (u = 2^-24, B and the reference's error as in fused4.h; D exact, d the reference's binary32 value):
+// The bound (u = 2^-24, B and the reference's error as for the fp32 slabs; D exact, d the reference's binary32 value):
 //   reference                                   |d - D|        <= 39 u B
 //   rterm (fp64, rounded once)                                  <=  1 u B
 //   per position: dot product (25 terms; since round 4 on the matrix cores, seven v_mfma_f32_16x16x4_f32 steps -- any
@@ -32,11 +32,11 @@
 //       summed over 12 positions                                <= 58 u B + 6 scale
 //   the sum V itself: exact (integers below 2^15)
 //   s' = fma(scale, V, rterm), s = s' + OFF: two roundings of values <= 3 B + E      <=  7 u B
-//   residual's own rounding (as fused4.h)                                    <=  2 u B
+//   residual's own rounding (as for the fp32 slabs)                         <=  2 u B
 //   =>  |(s - OFF + |r|^2) - d| <= e = 107 u B + 6 scale;  the construction needs e <= E / 4.2 = 121.9 u B + 6.67 scale:
-//   E = 512 u B + 28 scale   (typical: 2.0e-3 against 1.2e-3 of fused4.h -- 13.7 instead of 11.8 survivors per item).
+//   E = 512 u B + 28 scale   (typical: 2.0e-3 against 1.2e-3 of the fp32 slabs -- 13.7 instead of 11.8 survivors per item).
 // Everything downstream (survivor regions, merge_refine_kernel with the same E, the self-check of the bracket on
-// every refined row) is fused4.h's.
+// every refined row) is refine.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,7 +46,7 @@
 
 namespace freddy {
 
-// (FILT5_VMAX, filter_width5: fused4.h, next to the merge that shares them)
+// (FILT5_VMAX, filter_width5: refine.h, next to the merge that shares them)
 static constexpr int SCAN5_G = 16;   // items per work entry
 
 // order-preserving 32-bit key of a float (NaNs sort above +inf or below -inf: only met with non-finite inputs)

@@ -26,9 +26,11 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "join_index.h"
+#include "pinned.h"
 
 using namespace freddy;
 
@@ -145,12 +147,12 @@ struct IvfRun {
   float sentinel, cell_limit;
   int32_t *d_out_ids, *d_status;
   float* d_out_dist;
-  bool fused;          // cell-grouped scans (fused3.h / fused4.h) instead of lut_build + adc_scan
+  bool fused;          // cell-grouped scans (fused3.h / fused5.h / fused8.h) instead of lut_build + adc_scan
   int scan_kernel;     // 5: filter + refine, 3: exact fused scan
   bool tiled;          // batch coarse kernels (tiles of queries)
   bool zeroed;         // the coarse kernel has cleared the round-one scratch (ZeroArgs): no memsets in round one
   bool approx;         // cell selection as filter + refine: MFMA distances with a proven bracket, exact ones for the candidates
-  bool records_ready;  // a batch over the flat PQ table: the entry records were written by pq_records_kernel (no work-table / record kernels)
+  bool records_ready;  // a batch over the flat PQ table: the entry records were written by pq_front_kernel (no work-table / record kernels)
   int merge_slices;    // > 0: the merge of such a batch as `merge_slices` partial merges per query + merge_replay_kernel
   // per round
   int n_active, round;
@@ -161,8 +163,8 @@ struct IvfRun {
 
 struct LaneSlot {
   hipEvent_t done = nullptr;
-  void* h_in = nullptr;  size_t h_in_cap = 0;    // pinned: queries of the sub-batch
-  void* h_out = nullptr; size_t h_out_cap = 0;   // pinned: [ids n*k][dist n*k][n_next][unfinished queries n]
+  PinnedBuf h_in;          // queries of the sub-batch
+  PinnedBuf h_out;         // [ids n*k][dist n*k][n_next][unfinished queries n][completion word]
   DevBuf d_q, d_ids, d_dist;
   bool busy = false;
   int q0 = 0, n = 0;
@@ -203,7 +205,7 @@ struct freddy_gpu_index {
   int Cpad = 0;
   float* cbT = nullptr;         // [m][S][K]
   float* cbP = nullptr;         // fused kernel layout [m][SP/4][512 slots][4 dims][2 codes] (NULL unless K <= 1024)
-  // filter + refine path (fused4.h); NULL unless the shape is the fused one and the table fits the budget
+  // filter + refine path (refine.h); NULL unless the shape is the fused one and the table fits the budget
   float* cbR = nullptr;         // [m][K][S] row-major codebook for the exact stage
   float* rterm = nullptr;       // [blocks*64] sum_p (|c|^2 + 2 co_p . c) of every row
   float* pmax = nullptr;        // [m]        max |co_p| + max |c_p|, rounded up
@@ -250,8 +252,7 @@ struct freddy_gpu_index {
   Lane lanes[FREDDY_LANES];
   // pinned staging of the other synchronous host-buffer calls (pq_search): queries in, lists out -- read / written by
   // kernels, no SDMA copies in the stream
-  void* hio_in = nullptr;  size_t hio_in_cap = 0;
-  void* hio_out = nullptr; size_t hio_out_cap = 0;
+  PinnedBuf hio_in, hio_out;
   // replicas of this index on further devices (freddy_gpu_pin_ivf_multi): a host batch is split contiguously over
   // this handle and its replicas; every replica is a complete pinned index of its own
   std::vector<freddy_gpu_index*> replicas;
@@ -299,13 +300,35 @@ static int upload(T** dst, const T* src, size_t n, int64_t* bytes) {
 void free_index(freddy_gpu_index* ix);
 int check_search_args(const freddy_gpu_index* ix, int kind, const void* q, int Q, int k, const void* oi, const void* od);
 
+// ids -> rows of a table with ascending ids (h_ids): the row of one id (-1: absent), and the rows of "id IN (...)" -- unknown
+// ids vanish, duplicates collapse, order = table order
+static inline int32_t row_of(const std::vector<int32_t>& h_ids, int32_t id) {
+  auto it = std::lower_bound(h_ids.begin(), h_ids.end(), id);
+  return it != h_ids.end() && *it == id ? (int32_t)(it - h_ids.begin()) : -1;
+}
+static inline std::vector<int32_t> rows_of_ids(const std::vector<int32_t>& h_ids, const int32_t* ids, int64_t n) {
+  std::vector<int32_t> rows;
+  rows.reserve((size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    if (const int32_t r = row_of(h_ids, ids[i]); r >= 0) rows.push_back(r);
+  std::sort(rows.begin(), rows.end());
+  rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+  return rows;
+}
+
 // ---- pin.hip ----
 int open_device(freddy_gpu_index* ix, int device);
-// (every unit raises the dynamic-LDS limit of its own kernels; open_device calls them all)
-int raise_lds_limits_ivfadc(int device);
-int raise_lds_limits_pq(int device);
-int raise_lds_limits_join(int device);
-int raise_lds_limits_exact(int device);
+// Every unit lists its kernels that want more than the default 64 KiB of dynamic LDS; open_device raises the limits (a
+// per-device function attribute) once per device.
+struct LdsLimit {
+  const void* kernel;
+  int bytes;
+  template <class K> LdsLimit(K* k, int b = 160 * 1024) : kernel(reinterpret_cast<const void*>(k)), bytes(b) {}
+};
+std::vector<LdsLimit> lds_limits_ivfadc();
+std::vector<LdsLimit> lds_limits_pq();
+std::vector<LdsLimit> lds_limits_join();
+std::vector<LdsLimit> lds_limits_exact();
 
 // ---- ivfadc.hip ----
 namespace freddy { struct PlanArgs; struct ScanArgs; struct MergeArgs; }
@@ -320,6 +343,18 @@ struct WorkTable {
   bool sp_pairs = false;   // units of up to two items (sparse5.h NI = 2)
 };
 int pick_V(int L);
+// f(std::integral_constant<int, V>()) for a selection width of pick_V (1, 2, 4, 8, 16); false for any other V
+template <class F>
+static inline bool with_V(int V, F&& f) {
+  switch (V) {
+    case 1: f(std::integral_constant<int, 1>()); return true;
+    case 2: f(std::integral_constant<int, 2>()); return true;
+    case 4: f(std::integral_constant<int, 4>()); return true;
+    case 8: f(std::integral_constant<int, 8>()); return true;
+    case 16: f(std::integral_constant<int, 16>()); return true;
+  }
+  return false;
+}
 int launch_scan(freddy_gpu_index* ix, hipStream_t s, const ScanArgs& a, int n_items);
 int launch_merge(freddy_gpu_index* ix, hipStream_t s, const MergeArgs& a);
 int bigk_select_replay(freddy_gpu_index* ix, hipStream_t s, Workspace* ws, ScanArgs sa, int n_items, const MergeArgs& ma, int Q);
@@ -329,7 +364,9 @@ int ivf_work_table(IvfRun& r, WorkTable& wt);
 int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt);
 int max_queries_per_chunk(const freddy_gpu_index* ix, int W, int k);
 int one_buffer(Workspace* ws, hipStream_t s, uint64_t shape, size_t bytes, uint32_t* epoch);
-const void* pinned_device_pointer(const void* p);
+bool one_prof();   // FREDDY_GPU_ONE_PROF (read once per process): the one-launch kernels' stamps on stderr
+int one_finish(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, volatile const int32_t* err,
+               void (*print_stamps)(const unsigned long long* st), int* verdict);
 
 // ---- pq.hip ----
 int pq_shadow_build(freddy_gpu_index* ix);

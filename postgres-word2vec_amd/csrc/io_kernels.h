@@ -13,18 +13,9 @@
 static __global__ __launch_bounds__(256) void lane_copy_in_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = src[i];
 }
-static __global__ __launch_bounds__(256) void lane_copy_out_kernel(const int32_t* __restrict__ ids, const float* __restrict__ dist,
-                                                           const int32_t* __restrict__ n_next, const int32_t* __restrict__ unfinished,
-                                                           int32_t* __restrict__ h_out, int n_out, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n_out) { h_out[i] = ids[i]; h_out[n_out + i] = __float_as_int(dist[i]); }
-  const int nn = n_next[0];
-  if (i == 0) h_out[2 * n_out] = nn;
-  if (i < nn && i < n) h_out[2 * n_out + 1 + i] = unfinished[i];
-}
 
-// The same by ONE workgroup, followed by a completion word the host polls (lane_retire): the lists are in (mapped host)
-// memory before the word.  n_out * 2 + n + 1 words: a few tens of KB.
+// The lists, the straggler count and the stragglers' numbers out by ONE workgroup, followed by a completion word the host
+// polls (lane_retire): the lists are in (mapped host) memory before the word.  n_out * 2 + n + 1 words: a few tens of KB.
 static __global__ __launch_bounds__(1024) void lane_copy_out_flag_kernel(const int32_t* __restrict__ ids, const float* __restrict__ dist,
                                                                  const int32_t* __restrict__ n_next, const int32_t* __restrict__ unfinished,
                                                                  int32_t* __restrict__ h_out, int n_out, int n, int32_t* __restrict__ flag) {

@@ -30,32 +30,12 @@ int pick_V(int L) {
   return 0;
 }
 
-template <int M, int V>
-static int launch_scan_mv(freddy_gpu_index* ix, hipStream_t s, const ScanArgs& a, dim3 grid, size_t lds) {
-  timed_launch(ix, s, "adc_scan", [&] { hipLaunchKernelGGL((adc_scan_kernel<M, V>), grid, dim3(SCAN_WG), lds, s, a); });
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-template <int M>
-static int launch_scan_m(freddy_gpu_index* ix, hipStream_t s, const ScanArgs& a, dim3 grid, size_t lds, int V) {
-  switch (V) {
-    case 1: return launch_scan_mv<M, 1>(ix, s, a, grid, lds);
-    case 2: return launch_scan_mv<M, 2>(ix, s, a, grid, lds);
-    case 4: return launch_scan_mv<M, 4>(ix, s, a, grid, lds);
-    case 8: return launch_scan_mv<M, 8>(ix, s, a, grid, lds);
-    case 16: return launch_scan_mv<M, 16>(ix, s, a, grid, lds);
-  }
-  return fail(FREDDY_E_LIMIT, "unsupported selection width");
-}
-
 int launch_scan(freddy_gpu_index* ix, hipStream_t s, const ScanArgs& a, int n_items) {
   if (n_items <= 0 || a.nchunk <= 0) return 0;
-  const int Vl = pick_V(a.L);
-  const size_t lds = std::max((((size_t)a.m * a.K * 4 + 15) & ~(size_t)15) + (size_t)SCAN_WAVES * 64 * sizeof(u64),
-                              (size_t)SCAN_WAVES * 64 * Vl * sizeof(u64));
-  dim3 grid((unsigned)a.nchunk, (unsigned)n_items);
   const int V = pick_V(a.L);
+  const size_t lds = std::max((((size_t)a.m * a.K * 4 + 15) & ~(size_t)15) + (size_t)SCAN_WAVES * 64 * sizeof(u64),
+                              (size_t)SCAN_WAVES * 64 * V * sizeof(u64));
+  dim3 grid((unsigned)a.nchunk, (unsigned)n_items);
   if (a.floor) {   // a later selection pass of a list of more than 512 entries (bigk.h)
     if (V != 16) return fail(FREDDY_E_ARG, "selection passes are 1024 keys wide");
     timed_launch(ix, s, "adc_scan", [&] {
@@ -65,8 +45,15 @@ int launch_scan(freddy_gpu_index* ix, hipStream_t s, const ScanArgs& a, int n_it
     HIP_TRY(hipGetLastError());
     return 0;
   }
-  if (a.m == 12) return launch_scan_m<12>(ix, s, a, grid, lds, V);
-  return launch_scan_m<0>(ix, s, a, grid, lds, V);
+  const bool known = with_V(V, [&](auto v) {
+    timed_launch(ix, s, "adc_scan", [&] {
+      if (a.m == 12) hipLaunchKernelGGL((adc_scan_kernel<12, decltype(v)::value>), grid, dim3(SCAN_WG), lds, s, a);
+      else hipLaunchKernelGGL((adc_scan_kernel<0, decltype(v)::value>), grid, dim3(SCAN_WG), lds, s, a);
+    });
+  });
+  if (!known) return fail(FREDDY_E_LIMIT, "unsupported selection width");
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 int launch_merge(freddy_gpu_index* ix, hipStream_t s, const MergeArgs& a) {
@@ -74,13 +61,7 @@ int launch_merge(freddy_gpu_index* ix, hipStream_t s, const MergeArgs& a) {
   const int V = pick_V(a.L);
   dim3 grid((unsigned)a.n_active), block(64);
   timed_launch(ix, s, "merge_replay", [&] {
-    switch (V) {
-      case 1: hipLaunchKernelGGL((merge_replay_kernel<1>), grid, block, 0, s, a); break;
-      case 2: hipLaunchKernelGGL((merge_replay_kernel<2>), grid, block, 0, s, a); break;
-      case 4: hipLaunchKernelGGL((merge_replay_kernel<4>), grid, block, 0, s, a); break;
-      case 8: hipLaunchKernelGGL((merge_replay_kernel<8>), grid, block, 0, s, a); break;
-      case 16: hipLaunchKernelGGL((merge_replay_kernel<16>), grid, block, 0, s, a); break;
-    }
+    with_V(V, [&](auto v) { hipLaunchKernelGGL((merge_replay_kernel<decltype(v)::value>), grid, block, 0, s, a); });
   });
   HIP_TRY(hipGetLastError());
   return 0;
@@ -273,14 +254,8 @@ static int ivf_plan(IvfRun& r, PlanArgs& pa) {
       else hipLaunchKernelGGL((probe_plan2_kernel<0, true>), dim3(r.n_active), dim3(64 * PLAN2_NW), 0, s, g);   // (more than 1024 cells: streamed)
     });
   } else
-  timed_launch(ix, s, "probe_plan", [&] {
-    switch (PV) {
-      case 1: hipLaunchKernelGGL((probe_plan_kernel<1>), dim3(r.n_active), dim3(64), plan_lds, s, pa); break;
-      case 2: hipLaunchKernelGGL((probe_plan_kernel<2>), dim3(r.n_active), dim3(64), plan_lds, s, pa); break;
-      case 4: hipLaunchKernelGGL((probe_plan_kernel<4>), dim3(r.n_active), dim3(64), plan_lds, s, pa); break;
-      case 8: hipLaunchKernelGGL((probe_plan_kernel<8>), dim3(r.n_active), dim3(64), plan_lds, s, pa); break;
-      default: hipLaunchKernelGGL((probe_plan_kernel<16>), dim3(r.n_active), dim3(64), plan_lds, s, pa); break;
-    }
+  timed_launch(ix, s, "probe_plan", [&] {   // (2W <= 1024: ivfadc_begin)
+    with_V(PV, [&](auto v) { hipLaunchKernelGGL((probe_plan_kernel<decltype(v)::value>), dim3(r.n_active), dim3(64), plan_lds, s, pa); });
   });
   HIP_TRY(hipGetLastError());
   if (!(r.zeroed && r.first())) HIP_TRY(hipMemsetAsync(ws->w_cand.p, 0, sizeof(int32_t) * 2 * r.Q, s));   // (every round starts without bounds)
@@ -802,21 +777,8 @@ static int lane_open(freddy_gpu_index* ix, Lane& l, LaneSlot& c, size_t in_bytes
   if (!l.stream && &l == &ix->lanes[0] && !ix->tune.lane0_own) l.stream = ix->stream;
   if (!l.stream) HIP_TRY(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
   if (!c.done) HIP_TRY(hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
-  if (in_bytes > c.h_in_cap) {
-    if (c.h_in) (void)hipHostFree(c.h_in);
-    c.h_in = nullptr; c.h_in_cap = 0;
-    const size_t want = in_bytes + in_bytes / 8 + 256;
-    if (hipHostMalloc(&c.h_in, want, hipHostMallocDefault) != hipSuccess) { c.h_in = nullptr; return fail(FREDDY_E_NOMEM, "pinned staging allocation failed"); }
-    c.h_in_cap = want;
-  }
   const size_t out_bytes = (n_out * 2 + 1 + n + 1) * 4;   // (+ the completion word)
-  if (out_bytes > c.h_out_cap) {
-    if (c.h_out) (void)hipHostFree(c.h_out);
-    c.h_out = nullptr; c.h_out_cap = 0;
-    const size_t want = out_bytes + out_bytes / 8 + 256;
-    if (hipHostMalloc(&c.h_out, want, hipHostMallocDefault) != hipSuccess) { c.h_out = nullptr; return fail(FREDDY_E_NOMEM, "pinned staging allocation failed"); }
-    c.h_out_cap = want;
-  }
+  if (c.h_in.ensure(in_bytes) || c.h_out.ensure(out_bytes)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
   if (c.d_q.ensure(in_bytes + 16) || c.d_ids.ensure(n_out * 4) || c.d_dist.ensure(n_out * 4))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   return 0;
@@ -865,23 +827,12 @@ static int lane_retire(LaneSlot& c, const PipeCall& pc) {
   c.busy = false;
   const int k = pc.k;
   const size_t n_out = (size_t)c.n * k;
-  const int32_t* ho = static_cast<const int32_t*>(c.h_out);
-  {
-    // the copy-out kernel's last store is a completion word behind the lists: polled for up to a millisecond (a few
-    // microseconds sooner than the event), then the event is waited for the usual way -- which is also where a fault in one
-    // of the lane's kernels surfaces, before its output is trusted
-    volatile const int32_t* flag = ho + 2 * n_out + 1 + (size_t)c.n;
-    const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(1000);
-    int spins = 0;
-    while (*flag == 0) {
-      __builtin_ia32_pause();
-      if ((++spins & 255) == 0 && std::chrono::steady_clock::now() > t_end) break;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (*flag == 0) {
-      HIP_TRY(hipEventSynchronize(c.done));
-      HIP_TRY(hipGetLastError());
-    }
+  const int32_t* ho = c.h_out.as<const int32_t>();
+  // the copy-out kernel's last store is a completion word behind the lists: polled for up to a millisecond, then the event is
+  // waited for the usual way -- which is also where a fault in one of the lane's kernels surfaces, before its output is trusted
+  if (wait_word(ho + 2 * n_out + 1 + (size_t)c.n, 1000) == 0) {
+    HIP_TRY(hipEventSynchronize(c.done));
+    HIP_TRY(hipGetLastError());
   }
   memcpy(pc.out_ids + (size_t)c.q0 * k, ho, n_out * 4);
   memcpy(pc.out_dist + (size_t)c.q0 * k, ho + n_out, n_out * 4);
@@ -905,14 +856,6 @@ static int lane_retire(LaneSlot& c, const PipeCall& pc) {
   return 0;
 }
 
-// the device-side address of a pinned (hipHostMalloc / freddy_gpu_host_alloc) host buffer, or NULL for ordinary memory
-const void* pinned_device_pointer(const void* p) {
-  hipPointerAttribute_t attr;
-  memset(&attr, 0, sizeof(attr));
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  return attr.type == hipMemoryTypeHost ? attr.devicePointer : nullptr;
-}
-
 // The one-launch kernels' hand-off buffer: every published word carries the call's epoch in its top bit (one.h).  Calls of
 // one shape write exactly the same words, so the epoch just flips; a different shape (or a new allocation) clears the
 // buffer to epoch 0 and starts with epoch 1.
@@ -930,6 +873,32 @@ int one_buffer(Workspace* ws, hipStream_t s, uint64_t shape, size_t bytes, uint3
   }
   *epoch = ws->one_epoch;
   ws->one_pending = true;   // until the caller has seen its kernel launched (one_buffer_launched)
+  return 0;
+}
+
+bool one_prof() {
+  static const bool on = getenv("FREDDY_GPU_ONE_PROF") != nullptr;
+  return on;
+}
+
+// The end of a one-launch call (one.h): the kernel's last store is the verdict word `err` in mapped host memory (2 = list
+// written; ivf_one_kernel: 3 = list written, the reference would probe a second time; 1 = a bounded poll ran out), polled for
+// up to a millisecond, then the stream is waited for the usual way.  A poll that ran out (the grid was not co-resident): the
+// counters are re-armed and this handle keeps to the multi-launch paths.
+int one_finish(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, volatile const int32_t* err,
+               void (*print_stamps)(const unsigned long long* st), int* verdict) {
+  if (wait_word(err, 1000) != 2) HIP_TRY(hipStreamSynchronize(s));
+  if (one_prof()) {
+    HIP_TRY(hipStreamSynchronize(s));
+    unsigned long long st[16];
+    (void)hipMemcpy(st, ws->w_one.as<unsigned long long>() + 8, sizeof(st), hipMemcpyDeviceToHost);
+    print_stamps(st);
+  }
+  *verdict = *err;
+  if (*verdict != 2 && *verdict != 3) {
+    ix->one_launch_failed = true;
+    ws->one_shape = 0;
+  }
   return 0;
 }
 
@@ -951,12 +920,7 @@ static int ivf_one(freddy_gpu_index* ix, const float* queries, int k, int W, flo
   const int G = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)ix->n_cus, (int64_t)256, (int64_t)(56 * 1024) / (8 * L)}));
   if (G < W) return 0;   // (an item per workgroup at least)
   const size_t need_out = n_out * 8 + 16;
-  if (need_out > ix->hio_out_cap) {
-    if (ix->hio_out) (void)hipHostFree(ix->hio_out);
-    ix->hio_out = nullptr; ix->hio_out_cap = 0;
-    if (hipHostMalloc(&ix->hio_out, need_out + 256, hipHostMallocDefault) != hipSuccess) { ix->hio_out = nullptr; return fail(FREDDY_E_NOMEM, "pinned staging allocation failed"); }
-    ix->hio_out_cap = need_out + 256;
-  }
+  if (ix->hio_out.ensure(need_out)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
   // the hand-off buffer: coarse distances | the W tables | the workgroups' lists | their accepted-row counts
   const size_t lut_off = (sizeof(float) * ((size_t)C + 8) + 255) & ~(size_t)255;
   const size_t part_off = (lut_off + sizeof(float) * (size_t)W * lutN + 255) & ~(size_t)255;
@@ -964,11 +928,10 @@ static int ivf_one(freddy_gpu_index* ix, const float* queries, int k, int W, flo
   uint32_t epoch = 0;
   if (int rc = one_buffer(ws, s, (2ull << 60) | ((uint64_t)C << 44) | ((uint64_t)K << 32) | ((uint64_t)W << 24) | ((uint64_t)G << 12) | (uint64_t)L,
                           cnt_off + sizeof(uint32_t) * (size_t)G, &epoch)) return rc;
-  static const bool one_prof = getenv("FREDDY_GPU_ONE_PROF") != nullptr;
-  if (one_prof && ws->w_one.ensure(256)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  int32_t* h_ids = static_cast<int32_t*>(ix->hio_out);
+  if (one_prof() && ws->w_one.ensure(256)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  int32_t* h_ids = ix->hio_out.as<int32_t>();
   float* h_dist = reinterpret_cast<float*>(h_ids + n_out);
-  int32_t* err = reinterpret_cast<int32_t*>(static_cast<char*>(ix->hio_out) + n_out * 8);
+  int32_t* err = reinterpret_cast<int32_t*>(ix->hio_out.as<char>() + n_out * 8);
   *err = 0;
   IvfOneArgs a;
   memcpy(a.qv, queries, sizeof(a.qv));
@@ -979,7 +942,7 @@ static int ivf_one(freddy_gpu_index* ix, const float* queries, int k, int W, flo
   a.out_ids = h_ids; a.out_dist = h_dist; a.epoch = epoch; a.err = err;
   a.C = C; a.K = K; a.W = W; a.L = L; a.k = k; a.found_rule = found_rule == FREDDY_FOUND_ROWS ? 0 : 1;
   a.cell_limit = 100.0f; a.sentinel = sentinel;
-  a.prof = one_prof ? ws->w_one.as<unsigned long long>() + 8 : nullptr;
+  a.prof = one_prof() ? ws->w_one.as<unsigned long long>() + 8 : nullptr;
   memcpy(&a.sentinel_bits, &sentinel, 4);
   const size_t n_mine = ((size_t)C + G - 1) / G;
   const size_t lds = std::max({(n_mine + 1) * 300 * sizeof(float), (size_t)C * 4 + 64 + 64 * sizeof(u64) + 64,
@@ -989,35 +952,15 @@ static int ivf_one(freddy_gpu_index* ix, const float* queries, int k, int W, flo
   timed_launch(ix, s, "ivf_one", [&] { hipLaunchKernelGGL((ivf_one_kernel<25>), dim3((unsigned)G), dim3(ONE_WG), lds, s, a); });
   HIP_TRY(hipGetLastError());
   ws->one_pending = false;
-  {   // (the kernel's last store is this word: polled for up to a millisecond, then the stream is waited for the usual way)
-    volatile int32_t* flag = err;
-    const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(1000);
-    int spins = 0;
-    while (*flag == 0) {
-      __builtin_ia32_pause();
-      if ((++spins & 255) == 0 && std::chrono::steady_clock::now() > t_end) break;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (*flag != 2) HIP_TRY(hipStreamSynchronize(s));
-  }
-  if (one_prof) {
-    HIP_TRY(hipStreamSynchronize(s));
-    unsigned long long st[16];
-    (void)hipMemcpy(st, ws->w_one.as<unsigned long long>() + 8, sizeof(st), hipMemcpyDeviceToHost);
-    fprintf(stderr, "[ivf_one] wg0: coarse %.2f barrier %.2f plan %.2f tables %.2f barrier %.2f stage %.2f scan %.2f publish %.2f | last: since wg0 start %.2f load %.2f merge+list %.2f us\n",
-            (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01, (st[3] - st[2]) * 0.01, (st[4] - st[3]) * 0.01, (st[5] - st[4]) * 0.01, (st[6] - st[5]) * 0.01,
-            (st[7] - st[6]) * 0.01, (st[8] - st[7]) * 0.01, (st[10] - st[0]) * 0.01, (st[11] - st[10]) * 0.01, (st[12] - st[11]) * 0.01);
-  }
-  if (*err == 2) {
+  if (int rc = one_finish(ix, ws, s, err, [](const unsigned long long* st) {
+        fprintf(stderr, "[ivf_one] wg0: coarse %.2f barrier %.2f plan %.2f tables %.2f barrier %.2f stage %.2f scan %.2f publish %.2f | last: since wg0 start %.2f load %.2f merge+list %.2f us\n",
+                (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01, (st[3] - st[2]) * 0.01, (st[4] - st[3]) * 0.01, (st[5] - st[4]) * 0.01, (st[6] - st[5]) * 0.01,
+                (st[7] - st[6]) * 0.01, (st[8] - st[7]) * 0.01, (st[10] - st[0]) * 0.01, (st[11] - st[10]) * 0.01, (st[12] - st[11]) * 0.01);
+      }, verdict))
+    return rc;
+  if (*verdict == 2) {
     memcpy(out_ids, h_ids, n_out * 4);
     memcpy(out_dist, h_dist, n_out * 4);
-    *verdict = 2;
-    return 0;
-  }
-  if (*err != 3) {   // a poll ran out: counters re-armed, this handle keeps to the multi-launch paths
-    ix->one_launch_failed = true;
-    ws->one_shape = 0;
-    HIP_TRY(hipStreamSynchronize(s));
   }
   return 0;
 }
@@ -1063,7 +1006,7 @@ static int ivfadc_host_search(freddy_gpu_index* ix, const float* queries, int Q,
     const float* d_queries = c.d_q.as<float>();
     if (n <= 8) {
       // a handful of queries: the kernels read them where they are staged (pinned, mapped) -- one launch less
-      if (stage) { memcpy(c.h_in, queries + (size_t)q0 * ix->d, row * n); src = static_cast<const float*>(c.h_in); }
+      if (stage) { memcpy(c.h_in.p, queries + (size_t)q0 * ix->d, row * n); src = c.h_in.as<const float>(); }
       d_queries = src;
     }
     // pageable queries cross in pieces: the copy kernel of a piece reads it over PCIe while the host stages the next one (1.2 MB per
@@ -1075,8 +1018,8 @@ static int ivfadc_host_search(freddy_gpu_index* ix, const float* queries, int Q,
       // (a range of whole queries; whole 16-byte words except at the end of the sub-batch, whose buffers are padded)
       const size_t w0 = b_lo / 16, w1 = (b_hi + 15) / 16;
       if (b_lo % 16) return fail(FREDDY_E_ARG, "internal: a staged piece must start at a 16-byte word");
-      if (stage) memcpy(static_cast<char*>(c.h_in) + b_lo, reinterpret_cast<const char*>(queries + (size_t)q0 * ix->d) + b_lo, b_hi - b_lo);
-      const char* from = stage ? static_cast<const char*>(c.h_in) : reinterpret_cast<const char*>(src);
+      if (stage) memcpy(c.h_in.as<char>() + b_lo, reinterpret_cast<const char*>(queries + (size_t)q0 * ix->d) + b_lo, b_hi - b_lo);
+      const char* from = stage ? c.h_in.as<const char>() : reinterpret_cast<const char*>(src);
       // without per-piece coarse launches (every other path) the whole range still crosses as four copy launches
       const int cuts = (q_lo == 0 && q_hi == n && stage && b_hi >= (size_t)512 * 1024) ? 4 : 1;
       const size_t per16 = (w1 - w0 + cuts - 1) / cuts;
@@ -1092,7 +1035,7 @@ static int ivfadc_host_search(freddy_gpu_index* ix, const float* queries, int Q,
     if (trace) t2 = now_us();
     IvfRun r;
     const int n_out = n * k;
-    int32_t* h_flag = static_cast<int32_t*>(c.h_out) + 2 * (size_t)n_out + 1 + (size_t)n;
+    int32_t* h_flag = c.h_out.as<int32_t>() + 2 * (size_t)n_out + 1 + (size_t)n;
     *h_flag = 0;
     // (a call of ONE sub-batch launches its cell selection piece by piece behind the staged pieces: 0.398 -> 0.374 ms at 2048 queries;
     // with several lanes the extra launches only get in the way of the other lanes' chains: 0.613 -> 0.666 ms at 4096)
@@ -1101,7 +1044,7 @@ static int ivfadc_host_search(freddy_gpu_index* ix, const float* queries, int Q,
       break;
     if (trace) t3 = now_us();
     hipLaunchKernelGGL(lane_copy_out_flag_kernel, dim3(1), dim3(1024), 0, l.stream, c.d_ids.as<int32_t>(),
-                       c.d_dist.as<float>(), r.ws->w_cnt.as<int32_t>(), r.next, static_cast<int32_t*>(c.h_out), n_out, n, h_flag);
+                       c.d_dist.as<float>(), r.ws->w_cnt.as<int32_t>(), r.next, c.h_out.as<int32_t>(), n_out, n, h_flag);
     if (hipGetLastError() != hipSuccess || hipEventRecord(c.done, l.stream) != hipSuccess) { rc = fail(FREDDY_E_HIP, "launch of the result copy failed"); break; }
     c.busy = true;
     if (trace)
@@ -1139,32 +1082,20 @@ extern "C" int freddy_gpu_ivfadc_search(freddy_gpu_index_t* ix, const float* que
   });
 }
 
-// The kernels of this unit that want more than the default 64 KiB of dynamic LDS (a per-device function attribute).
-int raise_lds_limits_ivfadc(int device) {
-  static std::mutex mu;
-  static std::vector<char> done;
-  std::lock_guard<std::mutex> g(mu);
-  if ((size_t)device < done.size() && done[(size_t)device]) return 0;
-  const void* kernels[] = {
-      (const void*)&adc_scan_kernel<12, 1>, (const void*)&adc_scan_kernel<12, 2>, (const void*)&adc_scan_kernel<12, 4>,
-      (const void*)&adc_scan_kernel<12, 8>, (const void*)&adc_scan_kernel<12, 16>, (const void*)&adc_scan_kernel<0, 1>,
-      (const void*)&adc_scan_kernel<0, 2>, (const void*)&adc_scan_kernel<0, 4>, (const void*)&adc_scan_kernel<0, 8>,
-      (const void*)&adc_scan_kernel<0, 16>, (const void*)&adc_scan_kernel<12, 16, true>, (const void*)&adc_scan_kernel<0, 16, true>,
-      (const void*)&ivf_spec2_kernel<25, 12, true>,
-      (const void*)&ivf_spec2_kernel<25, 12, false>,
-      (const void*)&ivf_filter5_kernel<12, true, false>, (const void*)&ivf_filter5_kernel<12, false, false>,
-      (const void*)&ivf_filter5_kernel<12, true, true>, (const void*)&ivf_filter5_kernel<12, false, true>,
-      (const void*)&ivf_filter5_kernel<12, false, false, false, true>, (const void*)&ivf_filter5_kernel<12, false, true, false, true>,
-      (const void*)&ivf_filter8_kernel<12, false>, (const void*)&ivf_filter8_kernel<12, true>,
+// The kernels of this unit that want more than the default 64 KiB of dynamic LDS.
+std::vector<LdsLimit> lds_limits_ivfadc() {
+  return {&adc_scan_kernel<12, 1>, &adc_scan_kernel<12, 2>, &adc_scan_kernel<12, 4>, &adc_scan_kernel<12, 8>, &adc_scan_kernel<12, 16>,
+          &adc_scan_kernel<0, 1>, &adc_scan_kernel<0, 2>, &adc_scan_kernel<0, 4>, &adc_scan_kernel<0, 8>, &adc_scan_kernel<0, 16>,
+          &adc_scan_kernel<12, 16, true>, &adc_scan_kernel<0, 16, true>,
+          &ivf_spec2_kernel<25, 12, true>, &ivf_spec2_kernel<25, 12, false>,
+          &ivf_filter5_kernel<12, true, false>, &ivf_filter5_kernel<12, false, false>,
+          &ivf_filter5_kernel<12, true, true>, &ivf_filter5_kernel<12, false, true>,
+          &ivf_filter5_kernel<12, false, false, false, true>, &ivf_filter5_kernel<12, false, true, false, true>,
+          &ivf_filter8_kernel<12, false>, &ivf_filter8_kernel<12, true>,
 #ifdef FREDDY_LAB
-      (const void*)&ivf_filter5_kernel<12, true, false, true>, (const void*)&ivf_filter8_kernel<12, false, true>,
+          &ivf_filter5_kernel<12, true, false, true>, &ivf_filter8_kernel<12, false, true>,
 #endif
-      (const void*)&coarse_approx_kernel, (const void*)&coarse_approx16_kernel, (const void*)&ivf_multi_kernel};
-  for (const void* k : kernels)
-    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  // (static LDS beside the dynamic: 16384 keys + 4096 carried ids = 144 KB)
-  HIP_TRY(hipFuncSetAttribute((const void*)&bigk_replay_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bigk_lds_bytes(16384, BIGK_KMAX)));
-  if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
-  done[(size_t)device] = 1;
-  return 0;
+          &coarse_approx_kernel, &coarse_approx16_kernel, &ivf_multi_kernel,
+          // (static LDS beside the dynamic: 16384 keys + 4096 carried ids = 144 KB)
+          {&bigk_replay_kernel, (int)bigk_lds_bytes(16384, BIGK_KMAX)}};
 }

@@ -970,15 +970,11 @@ static inline int join_run(JoinIndex* j, hipStream_t s, const float* queries, in
     return FREDDY_E_NOMEM;
   {
     const size_t tl_bytes = sizeof(int32_t) * ((size_t)cells + 1 + (size_t)std::max<int64_t>(n_targets, 1));
-    if (tl_bytes > j->h_tl_cap) {
-      if (j->h_tl) (void)hipHostFree(j->h_tl);
-      j->h_tl = nullptr; j->h_tl_cap = 0; j->tl_valid = false;
-      if (hipHostMalloc(&j->h_tl, tl_bytes + tl_bytes / 4 + 256, hipHostMallocDefault) != hipSuccess) { j->h_tl = nullptr; return join_fail(FREDDY_E_NOMEM, "pinned staging allocation failed"); }
-      j->h_tl_cap = tl_bytes + tl_bytes / 4 + 256;
-    }
+    if (tl_bytes > j->h_tl.cap) j->tl_valid = false;   // (a new block: the previous target array is gone)
+    if (j->h_tl.ensure(tl_bytes)) return join_fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
   }
-  const int32_t* tcell_off = static_cast<const int32_t*>(j->h_tl);          // [cells + 1]; complete on the host after the first synchronisation
-  int32_t* h_tids = static_cast<int32_t*>(j->h_tl) + (size_t)cells + 1;     // the target array as the mark kernel reads it
+  const int32_t* tcell_off = j->h_tl.as<const int32_t>();          // [cells + 1]; complete on the host after the first synchronisation
+  int32_t* h_tids = j->h_tl.as<int32_t>() + (size_t)cells + 1;     // the target array as the mark kernel reads it
   const bool tl_hit = j->tl_valid && j->tl_n == n_targets && j->tl_cells == cells &&
                       (n_targets == 0 || memcmp(h_tids, target_ids, sizeof(int32_t) * (size_t)n_targets) == 0);
   if (!tl_hit) {   // (a hit: d_tcell / d_trow and the pinned offsets still hold this target array's buckets)
@@ -988,7 +984,7 @@ static inline int join_run(JoinIndex* j, hipStream_t s, const float* queries, in
     JOIN_HIP(hipMemsetAsync(j->markbits, 0, sizeof(uint32_t) * (size_t)((j->N + 31) / 32 + 1), s));
     JOIN_HIP(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (size_t)cells * 2, s));
     void* p_tl = nullptr;
-    JOIN_HIP(hipHostGetDevicePointer(&p_tl, j->h_tl, 0));
+    JOIN_HIP(hipHostGetDevicePointer(&p_tl, j->h_tl.p, 0));
     if (n_targets > 0) {
       memcpy(h_tids, target_ids, sizeof(int32_t) * (size_t)n_targets);
       hipLaunchKernelGGL(join_mark_kernel, dim3((unsigned)((n_targets + 255) / 256)), dim3(256), 0, s, static_cast<const int32_t*>(p_tl) + (size_t)cells + 1,
@@ -1006,40 +1002,29 @@ static inline int join_run(JoinIndex* j, hipStream_t s, const float* queries, in
   track(&freddy_track::data_retrieval_time);   // "fq.id IN (targets)" (enqueue only: the device work overlaps what follows)
   // a query buffer that is pinned already (freddy_gpu_host_alloc: what pg/freddy_gpu_glue.c's query_buffer() hands over) is read
   // where it is -- the 6 MB staging copy of 5 000 queries is the longest host step of a call
-  const float* p_queries = nullptr;
-  {
-    hipPointerAttribute_t attr;
-    memset(&attr, 0, sizeof(attr));
-    if (hipPointerGetAttributes(&attr, queries) == hipSuccess && attr.type == hipMemoryTypeHost) p_queries = static_cast<const float*>(attr.devicePointer);
-    else (void)hipGetLastError();
-    // sub_dist_kernel reads with 16-byte loads: a VIEW into a pinned buffer at an odd offset goes through the staging copy (whose
-    // base hipHostMalloc aligns), and so does a buffer another device's context pinned (no device address here)
-    if (p_queries && (reinterpret_cast<uintptr_t>(p_queries) & 15u)) p_queries = nullptr;
-  }
+  const float* p_queries = static_cast<const float*>(pinned_device_pointer(queries));
+  // sub_dist_kernel reads with 16-byte loads: a VIEW into a pinned buffer at an odd offset goes through the staging copy (whose
+  // base is aligned), and so does a buffer another device's context pinned (no device address here)
+  if (p_queries && (reinterpret_cast<uintptr_t>(p_queries) & 15u)) p_queries = nullptr;
   const bool fused_front_p = (d & 1) == 0 && d / 2 <= 512;
   if (p_queries && fused_front_p) {
     hipLaunchKernelGGL(sub_dist_kernel, dim3((unsigned)Q, 2), dim3(64), 0, s, p_queries, j->coarseT, (float*)d_sub, d, Kc, (float*)d_q, 0);
     JOIN_HIP(hipGetLastError());
   } else {   // queries: host copy into pinned staging, read by a copy kernel (1.2 KB per query over PCIe)
     const size_t qbytes = sizeof(float) * (size_t)Q * d;
-    if (qbytes > j->h_q_cap) {
-      if (j->h_q) (void)hipHostFree(j->h_q);
-      j->h_q = nullptr; j->h_q_cap = 0;
-      if (hipHostMalloc(&j->h_q, qbytes + qbytes / 4 + 256, hipHostMallocDefault) != hipSuccess) { j->h_q = nullptr; return join_fail(FREDDY_E_NOMEM, "pinned staging allocation failed"); }
-      j->h_q_cap = qbytes + qbytes / 4 + 256;
-    }
+    if (j->h_q.ensure(qbytes)) return join_fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
     // (in pieces of whole queries: the host copies piece i + 1 while sub_dist_kernel pulls piece i over PCIe, writes the device
     // copy and computes the piece's sub-distances)
     const int piece_q = std::max((Q + 3) / 4, 64);
     const bool fused_front = (d & 1) == 0 && d / 2 <= 512;   // (the kernel's staging buffer; odd d: the halves do not cover the vector)
     for (int qa = 0; qa < Q; qa += piece_q) {
       const int nq = std::min(piece_q, Q - qa);
-      memcpy(static_cast<float*>(j->h_q) + (size_t)qa * d, queries + (size_t)qa * d, sizeof(float) * (size_t)nq * d);
+      memcpy(j->h_q.as<float>() + (size_t)qa * d, queries + (size_t)qa * d, sizeof(float) * (size_t)nq * d);
       if (fused_front)
-        hipLaunchKernelGGL(sub_dist_kernel, dim3((unsigned)nq, 2), dim3(64), 0, s, (const float*)j->h_q, j->coarseT, (float*)d_sub, d, Kc, (float*)d_q, qa);
+        hipLaunchKernelGGL(sub_dist_kernel, dim3((unsigned)nq, 2), dim3(64), 0, s, j->h_q.as<const float>(), j->coarseT, (float*)d_sub, d, Kc, (float*)d_q, qa);
       else
         hipLaunchKernelGGL(join_copy_kernel, dim3((unsigned)std::min<size_t>(((size_t)nq * d + 255) / 256, 1024)), dim3(256), 0, s,
-                           (const uint32_t*)j->h_q + (size_t)qa * d, (uint32_t*)d_q + (size_t)qa * d, (size_t)nq * d);
+                           j->h_q.as<const uint32_t>() + (size_t)qa * d, (uint32_t*)d_q + (size_t)qa * d, (size_t)nq * d);
     }
     if (!fused_front)
       hipLaunchKernelGGL(sub_dist_kernel, dim3((unsigned)Q, 2), dim3(64), 0, s, (const float*)d_q, j->coarseT, (float*)d_sub, d, Kc, (float*)nullptr, 0);
@@ -1116,13 +1101,8 @@ static inline int join_run(JoinIndex* j, hipStream_t s, const float* queries, in
   float* h_fbsub = nullptr; float* p_fbsub = nullptr;   // [Q][2 * Kc]: sub-distances of the queries the device traversal hands back
   {
     const size_t need = sizeof(int32_t) * (size_t)Q * (TRAV_SUM_DW + 2 * (size_t)k + 2 + 2 * (size_t)Kc) + 64;   // + the active list, the scan list, the handed-back queries' sub-distances
-    if (need > j->h_sum_cap) {
-      if (j->h_sum) (void)hipHostFree(j->h_sum);
-      j->h_sum = nullptr; j->h_sum_cap = 0;
-      if (hipHostMalloc(&j->h_sum, need + need / 4, hipHostMallocDefault) != hipSuccess) { j->h_sum = nullptr; return join_fail(FREDDY_E_NOMEM, "pinned staging allocation failed"); }
-      j->h_sum_cap = need + need / 4;
-    }
-    h_summary = static_cast<int32_t*>(j->h_sum);
+    if (j->h_sum.ensure(need)) return join_fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+    h_summary = j->h_sum.as<int32_t>();
     h_oi_p = h_summary + (size_t)Q * TRAV_SUM_DW;
     h_od_p = reinterpret_cast<float*>(h_oi_p + (size_t)Q * k);
     h_active = reinterpret_cast<int32_t*>(h_od_p + (size_t)Q * k);
@@ -1132,7 +1112,7 @@ static inline int join_run(JoinIndex* j, hipStream_t s, const float* queries, in
     // address space): every hipMemcpyAsync between two kernels of a stream is an SDMA copy ordered against them by signals,
     // ~12 us per hop, and a round had five of them.
     void* dp = nullptr;
-    JOIN_HIP(hipHostGetDevicePointer(&dp, j->h_sum, 0));
+    JOIN_HIP(hipHostGetDevicePointer(&dp, j->h_sum.p, 0));
     p_summary = static_cast<int32_t*>(dp);
     p_oi = p_summary + (size_t)Q * TRAV_SUM_DW;
     p_od = reinterpret_cast<float*>(p_oi + (size_t)Q * k);
@@ -1318,16 +1298,16 @@ static inline int join_run(JoinIndex* j, hipStream_t s, const float* queries, in
       JOIN_HIP(hipEventRecord(j->ev0, s));
       // (a separate launch for the host-traversed queries ran behind the main one -- a lone workgroup's 45 us -- and its two
       // list uploads were SDMA hops: a query with a tie cost the call 0.1 ms)
-      const bool fb_rows = dev_trav && n_fb > 0 && j->h_q && (size_t)n_fb * (size_t)(cells + 1) * sizeof(int32_t) <= j->h_q_cap;
+      const bool fb_rows = dev_trav && n_fb > 0 && j->h_q.p && (size_t)n_fb * (size_t)(cells + 1) * sizeof(int32_t) <= j->h_q.cap;
       if (fb_rows) {
-        int32_t* hf = static_cast<int32_t*>(j->h_q);   // (the query staging block: its copy kernels finished before the first synchronisation)
+        int32_t* hf = j->h_q.as<int32_t>();   // (the query staging block: its copy kernels finished before the first synchronisation)
         for (int x = 0; x < n_fb; ++x) {
           int32_t* row = hf + (size_t)x * (cells + 1);
           const int cnt = qoff[(size_t)x + 1] - qoff[(size_t)x];
           row[0] = cnt;
           memcpy(row + 1, flat.data() + qoff[(size_t)x], sizeof(int32_t) * (size_t)cnt);
         }
-        hipLaunchKernelGGL(join_fb_rows_kernel, dim3((unsigned)n_fb), dim3(256), 0, s, (const int32_t*)j->h_q, (const int32_t*)d_scan + n_dev,
+        hipLaunchKernelGGL(join_fb_rows_kernel, dim3((unsigned)n_fb), dim3(256), 0, s, j->h_q.as<const int32_t>(), (const int32_t*)d_scan + n_dev,
                            (int32_t*)d_qstrided, (int32_t*)d_qcnt, cells);
         JOIN_HIP(hipGetLastError());
       }

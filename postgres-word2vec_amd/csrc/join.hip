@@ -57,18 +57,8 @@ extern "C" int freddy_gpu_last_track_sized(const freddy_gpu_index_t* ix, void* o
   return (int)n;
 }
 
-// The kernels of this unit that want more than the default 64 KiB of dynamic LDS (a per-device function attribute).
-int raise_lds_limits_join(int device) {
-  static std::mutex mu;
-  static std::vector<char> done;
-  std::lock_guard<std::mutex> g(mu);
-  if ((size_t)device < done.size() && done[(size_t)device]) return 0;
-  const void* kernels[] = {
-      (const void*)&join_query_kernel<1>, (const void*)&join_query_kernel<2>,
-      (const void*)&join_query_kernel<4>, (const void*)&join_query_kernel<8>, (const void*)&join_query_kernel<16>, (const void*)&join_query_kernel<16, true>};
-  for (const void* k : kernels)
-    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
-  done[(size_t)device] = 1;
-  return 0;
+// The kernels of this unit that want more than the default 64 KiB of dynamic LDS.
+std::vector<LdsLimit> lds_limits_join() {
+  return {&join_query_kernel<1>, &join_query_kernel<2>, &join_query_kernel<4>, &join_query_kernel<8>, &join_query_kernel<16>,
+          &join_query_kernel<16, true>};
 }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/freddy_gpu.h"
+#include "pinned.h"
 #include "wave_topk.h"
 
 namespace freddy {
@@ -58,10 +59,8 @@ struct JoinIndex {
   int32_t* cell = nullptr;    // [N] coarse cell of each row
   uint32_t* markbits = nullptr;  // [ceil(N/32)] scratch bitmap of the "id IN (targets)" resolution
   float* d_stats = nullptr;      // [cells+1] the statistics row (device traversal)
-  void* h_q = nullptr;           // pinned staging of the query batch (read by a copy kernel: no SDMA ordering hops)
-  size_t h_q_cap = 0;
-  void* h_sum = nullptr;         // pinned: per-round traversal summaries and result lists come back here
-  size_t h_sum_cap = 0;
+  PinnedBuf h_q;                 // staging of the query batch (read by a copy kernel: no SDMA ordering hops)
+  PinnedBuf h_sum;               // per-round traversal summaries and result lists come back here
   // host
   std::vector<int32_t> h_ids, h_cell;
   std::vector<float> h_stats;
@@ -70,8 +69,7 @@ struct JoinIndex {
   // de-duplicated and bucketed by cell already (workspaces 2 and 3 stay as they are); invalidated when rows are appended
   // (kept in ONE pinned block: [cells + 1] bucket offsets, written by the offsets kernel, then the target array, which the mark
   // kernel reads over PCIe -- no SDMA copy in either direction, and the copy the next call is compared with is the staging copy)
-  void* h_tl = nullptr;
-  size_t h_tl_cap = 0;
+  PinnedBuf h_tl;
   int64_t tl_n = -1;
   int tl_cells = -1;
   bool tl_valid = false;
@@ -101,9 +99,7 @@ static inline int join_buf(JoinIndex* j, int slot, size_t bytes, void** out) {
 static inline void join_free(JoinIndex* j) {
   void* ptrs[] = {j->cbT, j->coarseT, j->ids, j->codes, j->vectors, j->cell, j->markbits, j->d_stats};
   for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (j->h_q) (void)hipHostFree(j->h_q);
-  if (j->h_sum) (void)hipHostFree(j->h_sum);
-  if (j->h_tl) (void)hipHostFree(j->h_tl);
+  for (PinnedBuf* b : {&j->h_q, &j->h_sum, &j->h_tl}) b->release();
   for (int i = 0; i < 18; ++i) if (j->w[i]) (void)hipFree(j->w[i]);
   if (j->ev0) (void)hipEventDestroy(j->ev0);
   if (j->ev1) (void)hipEventDestroy(j->ev1);

@@ -254,7 +254,7 @@ static int derive_codebook_tables_into(freddy_gpu_index* ix, const float* codebo
             }
     if (upload(&ix->cbP, cbP.data(), cbP.size(), &ix->bytes)) return fail(FREDDY_E_NOMEM, "device allocation failed");
   }
-  // filter + refine tables (fused4.h)
+  // filter + refine tables (refine.h)
   if (ix->cbP && ix->m == 12 && ix->S == 25) {
     std::vector<float> pmax((size_t)ix->m), cmaxp((size_t)ix->m);
     for (int p = 0; p < ix->m; ++p) {
@@ -296,6 +296,18 @@ static int refresh_row_terms(freddy_gpu_index* ix) {
   return 0;
 }
 
+static int raise_lds_limits(int device) {
+  static std::mutex mu;
+  static std::vector<char> done;
+  std::lock_guard<std::mutex> g(mu);
+  if ((size_t)device < done.size() && done[(size_t)device]) return 0;
+  for (const std::vector<LdsLimit>& unit : {lds_limits_ivfadc(), lds_limits_pq(), lds_limits_join(), lds_limits_exact()})
+    for (const LdsLimit& l : unit) HIP_TRY(hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l.bytes));
+  if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
+  done[(size_t)device] = 1;
+  return 0;
+}
+
 int open_device(freddy_gpu_index* ix, int device) {
   // The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), read once when the
   // runtime starts: the pipeline's four lanes want a queue each beside the library's own stream (6 queues measured
@@ -311,10 +323,7 @@ int open_device(freddy_gpu_index* ix, int device) {
   HIP_TRY(hipSetDevice(device));
   ix->device = device;
   ix->tune = read_tuning();
-  if (int rc = raise_lds_limits_ivfadc(device)) return rc;
-  if (int rc = raise_lds_limits_pq(device)) return rc;
-  if (int rc = raise_lds_limits_join(device)) return rc;
-  if (int rc = raise_lds_limits_exact(device)) return rc;
+  if (int rc = raise_lds_limits(device)) return rc;
   HIP_TRY(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ix->n_cus = prop.multiProcessorCount;

@@ -37,30 +37,6 @@ __global__ __launch_bounds__(256) void pq_shadow_meta_kernel(const int32_t* __re
   if (i < n_blocks * 64) { const int32_t r = pos[i]; pos_ids[i] = r >= 0 ? ids[r] : -1; }
 }
 
-// One workgroup per query: A = squareDistance(q, 0) (sequential binary32, index_utils.c:500-508), the query's items --
-// one per pseudo-list -- and its slot in every list's bucket.
-__global__ __launch_bounds__(256) void pq_items_kernel(const float* __restrict__ queries, int Q, int d, int lists, int64_t n_rows,
-                                                      int32_t* __restrict__ item_cell, int32_t* __restrict__ item_query,
-                                                      float* __restrict__ item_dist, int32_t* __restrict__ cell_items,
-                                                      int32_t* __restrict__ cell_count, int32_t* __restrict__ round_rows) {
-  __shared__ float A_s;
-  const int q = blockIdx.x;
-  if (threadIdx.x == 0) {
-    float acc = 0.0f;
-    for (int i = 0; i < d; ++i) { const float t = queries[(size_t)q * d + i] - 0.0f; acc = acc + t * t; }
-    A_s = acc;
-    round_rows[q] = (int32_t)n_rows;
-  }
-  __syncthreads();
-  const float A = A_s;
-  for (int c = threadIdx.x; c < lists; c += 256) {
-    const int it = q * lists + c;
-    item_cell[it] = c; item_query[it] = q; item_dist[it] = A;
-    cell_items[(size_t)c * Q + q] = it;
-    if (q == 0) cell_count[c] = Q;
-  }
-}
-
 static bool pq_fused_shape(const freddy_gpu_index* ix) {
   return ix->kind == KIND_PQ && ix->cbR && ix->m == 12 && ix->S == 25 && ix->K <= FUSED_T * FUSED_E && ix->n_blocks > 0 && ix->N > 0;
 }
@@ -313,14 +289,13 @@ static int pq_one(freddy_gpu_index* ix, hipStream_t s, const float* h_q, int k, 
   const size_t part_off = (lutN * sizeof(float) + 255) & ~(size_t)255;
   uint32_t epoch = 0;
   if (int rc = one_buffer(ws, s, (1ull << 60) | ((uint64_t)K << 32) | ((uint64_t)G << 16) | (uint64_t)L, part_off + sizeof(u64) * (size_t)G * L, &epoch)) return rc;
-  static const bool one_prof = getenv("FREDDY_GPU_ONE_PROF") != nullptr;
-  if (one_prof && ws->w_one.ensure(256)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  if (one_prof() && ws->w_one.ensure(256)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   OneArgs a;
   memcpy(a.qv, h_q, sizeof(a.qv)); a.cbT = ix->cbT; a.lut_g = ws->w_oneb.as<float>(); a.blk_off = blk_off; a.packed = packed; a.pos = pos;
   a.pos_to_id = nullptr;   // (positions out: the caller maps them through its host copy of the ids -- no dependent gather at the kernel's end)
   a.part = reinterpret_cast<u64*>(ws->w_oneb.as<char>() + part_off); a.out_ids = d_out_ids; a.out_dist = d_out_dist;
   a.epoch = epoch; a.err = err;
-  a.prof = one_prof ? ws->w_one.as<unsigned long long>() + 8 : nullptr;
+  a.prof = one_prof() ? ws->w_one.as<unsigned long long>() + 8 : nullptr;
   a.K = K; a.L = L; a.k = k; a.chunk_blocks = chunk_blocks; a.sentinel = sentinel;
   memcpy(&a.sentinel_bits, &sentinel, 4);
   const size_t lds = std::max(((lutN * 4 + 15) & ~(size_t)15) + (size_t)ONE_WAVES * 64 * sizeof(u64),
@@ -405,14 +380,7 @@ extern "C" int freddy_gpu_pq_search_dev(freddy_gpu_index_t* ix, const float* d_q
 static int pq_subset(freddy_gpu_index* ix, hipStream_t s, const int32_t* subset_ids, int64_t n_subset, const int32_t** blk_off,
                      const uint32_t** packed, const int32_t** pos, int64_t* n_blocks, int64_t* n_rows_out = nullptr) {
   Workspace* ws = workspace_for(ix, s);
-  std::vector<int32_t> rows;
-  rows.reserve((size_t)n_subset);
-  for (int64_t i = 0; i < n_subset; ++i) {
-    auto it = std::lower_bound(ix->h_ids.begin(), ix->h_ids.end(), subset_ids[i]);
-    if (it != ix->h_ids.end() && *it == subset_ids[i]) rows.push_back((int32_t)(it - ix->h_ids.begin()));
-  }
-  std::sort(rows.begin(), rows.end());
-  rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+  const std::vector<int32_t> rows = rows_of_ids(ix->h_ids, subset_ids, n_subset);
   const int n_rows = (int)rows.size();
   const int nb = (n_rows + 63) / 64;
   const int n_pad = nb * 64;
@@ -451,27 +419,18 @@ extern "C" int freddy_gpu_pq_search(freddy_gpu_index_t* ix, const float* queries
   // handful of queries are read where they are staged and their lists written straight back; larger batches cross PCIe
   // once, by a copy kernel each way.  No hipMemcpyAsync in the stream (each one is an SDMA hop with its own latency).
   const size_t q_bytes = sizeof(float) * (size_t)Q * ix->d, n_out = (size_t)Q * k;
-  auto pinned_fit = [](void** p, size_t* cap, size_t need) -> int {
-    if (need <= *cap) return 0;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr; *cap = 0;
-    if (hipHostMalloc(p, need + need / 4 + 256, hipHostMallocDefault) != hipSuccess) { *p = nullptr; return -1; }
-    *cap = need + need / 4 + 256;
-    return 0;
-  };
-  if (pinned_fit(&ix->hio_in, &ix->hio_in_cap, q_bytes + 16) || pinned_fit(&ix->hio_out, &ix->hio_out_cap, n_out * 8 + 16))
-    return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
-  memcpy(ix->hio_in, queries, q_bytes);
+  if (ix->hio_in.ensure(q_bytes + 16) || ix->hio_out.ensure(n_out * 8 + 16)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+  memcpy(ix->hio_in.p, queries, q_bytes);
   const bool direct = Q <= 8;
   if (!direct && (ws->w_q.ensure(q_bytes + 16) || ws->w_out_ids.ensure(sizeof(int32_t) * n_out) || ws->w_out_dist.ensure(sizeof(float) * n_out)))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  const float* d_q = static_cast<const float*>(ix->hio_in);
-  int32_t* d_oi = static_cast<int32_t*>(ix->hio_out);
+  const float* d_q = ix->hio_in.as<const float>();
+  int32_t* d_oi = ix->hio_out.as<int32_t>();
   float* d_od = reinterpret_cast<float*>(d_oi + n_out);
   if (!direct) {
     const size_t n16 = (q_bytes + 15) / 16;
     hipLaunchKernelGGL(lane_copy_in_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, s,
-                       reinterpret_cast<const uint4*>(ix->hio_in), ws->w_q.as<uint4>(), n16);
+                       ix->hio_in.as<const uint4>(), ws->w_q.as<uint4>(), n16);
     HIP_TRY(hipGetLastError());
     d_q = ws->w_q.as<float>(); d_oi = ws->w_out_ids.as<int32_t>(); d_od = ws->w_out_dist.as<float>();
   }
@@ -492,39 +451,22 @@ extern "C" int freddy_gpu_pq_search(freddy_gpu_index_t* ix, const float* queries
   }
   const int qc = fused_path ? pq_fused_queries_per_chunk(ix, n_blocks) : pq_queries_per_chunk(ix, n_blocks, k);
   if (!fused_path && direct && pq_one_shape(ix, Q, k, n_blocks)) {
-    int32_t* err = reinterpret_cast<int32_t*>(static_cast<char*>(ix->hio_out) + n_out * 8);   // (the staging block's spare 16 bytes)
+    int32_t* err = reinterpret_cast<int32_t*>(ix->hio_out.as<char>() + n_out * 8);   // (the staging block's spare 16 bytes)
     *err = 0;
     if (int rc = pq_one(ix, s, queries, k, sentinel, blk_off, packed, pos, n_blocks, d_oi, d_od, err)) return rc;
-    // the kernel's last store is this word (2 = list written, 1 = a bounded poll ran out): polled here for up to a millisecond
-    // -- a few microseconds sooner than the runtime's completion signal -- then the stream is waited for the usual way
-    {
-      volatile int32_t* flag = err;
-      const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(1000);
-      int spins = 0;
-      while (*flag == 0) {
-        __builtin_ia32_pause();
-        if ((++spins & 255) == 0 && std::chrono::steady_clock::now() > t_end) break;
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      if (*flag != 2) HIP_TRY(hipStreamSynchronize(s));
-    }
-    if (getenv("FREDDY_GPU_ONE_PROF")) {
-      HIP_TRY(hipStreamSynchronize(s));
-      unsigned long long st[16];
-      (void)hipMemcpy(st, ws->w_one.as<unsigned long long>() + 8, sizeof(st), hipMemcpyDeviceToHost);
-      fprintf(stderr, "[pq_one] wg0: slice %.2f barrier %.2f stage %.2f scan %.2f publish %.2f | last: since wg0 start %.2f merge %.2f replay %.2f us\n",
-              (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01, (st[3] - st[2]) * 0.01, (st[4] - st[3]) * 0.01, (st[5] - st[4]) * 0.01,
-              (st[8] - st[0]) * 0.01, (st[9] - st[8]) * 0.01, (st[10] - st[9]) * 0.01);
-    }
-    if (*err == 2) {
-      const int32_t* h_pos = static_cast<const int32_t*>(ix->hio_out);
+    int verdict = 0;
+    if (int rc = one_finish(ix, ws, s, err, [](const unsigned long long* st) {
+          fprintf(stderr, "[pq_one] wg0: slice %.2f barrier %.2f stage %.2f scan %.2f publish %.2f | last: since wg0 start %.2f merge %.2f replay %.2f us\n",
+                  (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01, (st[3] - st[2]) * 0.01, (st[4] - st[3]) * 0.01, (st[5] - st[4]) * 0.01,
+                  (st[8] - st[0]) * 0.01, (st[9] - st[8]) * 0.01, (st[10] - st[9]) * 0.01);
+        }, &verdict))
+      return rc;
+    if (verdict == 2) {
+      const int32_t* h_pos = ix->hio_out.as<const int32_t>();
       for (size_t i = 0; i < n_out; ++i) out_ids[i] = h_pos[i] >= 0 ? ix->h_ids[(size_t)h_pos[i]] : -1;
       memcpy(out_dist, h_pos + n_out, n_out * 4);
       return FREDDY_OK;
     }
-    // the grid never met at its barrier (not co-resident): counters re-armed, this handle keeps to the three-launch path
-    ix->one_launch_failed = true;
-    ws->one_shape = 0;
   }
   for (int q0 = 0; q0 < Q; q0 += qc) {
     const int n = std::min(qc, Q - q0);
@@ -538,12 +480,12 @@ extern "C" int freddy_gpu_pq_search(freddy_gpu_index_t* ix, const float* queries
       return rc;
   }
   if (!direct) {
-    hipLaunchKernelGGL(host_io_out_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, d_oi, d_od, static_cast<int32_t*>(ix->hio_out), (int)n_out);
+    hipLaunchKernelGGL(host_io_out_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, d_oi, d_od, ix->hio_out.as<int32_t>(), (int)n_out);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipStreamSynchronize(s));
-  memcpy(out_ids, ix->hio_out, n_out * 4);
-  memcpy(out_dist, static_cast<const int32_t*>(ix->hio_out) + n_out, n_out * 4);
+  memcpy(out_ids, ix->hio_out.p, n_out * 4);
+  memcpy(out_dist, ix->hio_out.as<const int32_t>() + n_out, n_out * 4);
   return FREDDY_OK;
 }
 
@@ -597,17 +539,5 @@ extern "C" int freddy_gpu_grouping_pq(freddy_gpu_index_t* ix, const float* group
   return FREDDY_OK;
 }
 
-// The kernels of this unit that want more than the default 64 KiB of dynamic LDS (a per-device function attribute).
-int raise_lds_limits_pq(int device) {
-  static std::mutex mu;
-  static std::vector<char> done;
-  std::lock_guard<std::mutex> g(mu);
-  if ((size_t)device < done.size() && done[(size_t)device]) return 0;
-  const void* kernels[] = {
-      (const void*)&grouping_kernel<6>, (const void*)&grouping_kernel<15>, (const void*)&grouping_kernel<0>};
-  for (const void* k : kernels)
-    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
-  done[(size_t)device] = 1;
-  return 0;
-}
+// The kernels of this unit that want more than the default 64 KiB of dynamic LDS.
+std::vector<LdsLimit> lds_limits_pq() { return {&grouping_kernel<6>, &grouping_kernel<15>, &grouping_kernel<0>}; }

@@ -6,7 +6,7 @@
 // every gatherer wave appends the rows that pass the item's threshold to its own survivor region, and a
 // merge kernel picks the query's 2k smallest keys and replays the reference's insertion.
 // (The first two generations of the exact scan -- symmetric 8-wave kernel, one builder wave per SIMD --
-// are in the history of this repository: fused.h / fused2.h up to round 1.)
+// are in the history of this repository, up to round 1.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
