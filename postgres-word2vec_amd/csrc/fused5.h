@@ -37,31 +37,20 @@
 //   E = 512 u B + 28 scale   (typical: 2.0e-3 against 1.2e-3 of the fp32 slabs -- 13.7 instead of 11.8 survivors per item).
 // Everything downstream (survivor regions, merge_refine_kernel with the same E, the self-check of the bracket on
 // every refined row) is refine.h's.
+// The gatherer waves' selection tail (column minima, survivor pass) is scan_tail5.inc, ONE text that this kernel and fused8.h's
+// include in their bodies; the keys, the running bound, the thresholds and the main loop's dispatch are functions in scan_tail5.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "refine.h"
 #include "coarse.h"
+#include "scan_tail5.h"
 
 namespace freddy {
 
 // (FILT5_VMAX, filter_width5: refine.h, next to the merge that shares them)
 static constexpr int SCAN5_G = 16;   // items per work entry
-
-// order-preserving 32-bit key of a float (NaNs sort above +inf or below -inf: only met with non-finite inputs)
-__device__ __forceinline__ uint32_t float_key(float x) {
-  const uint32_t b = __float_as_uint(x);
-  return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-// selection threshold of the integer scan from the KEY of tau': tau' + E rounded up, as a float; +inf = keep every row
-__device__ __forceinline__ uint32_t widen_threshold5(uint32_t tau_key, float E) {
-  const uint32_t b = (tau_key & 0x80000000u) ? (tau_key ^ 0x80000000u) : ~tau_key;
-  const float tau = __uint_as_float(b);
-  if (!(tau < 3e38f) || !(tau > -3e38f) || !(E < 1e30f)) return 0x7f800000u;
-  const float t = tau + E;
-  return __float_as_uint(t + __builtin_fabsf(t) * 2.4e-7f + 1e-37f);
-}
 
 // The table stores v + bias(p) >= 0 with sum_p bias(p) = 2^15 (m = 12: 2731 for the first eight positions, 2730 for the
 // others): a (row, item) sum is then an UNSIGNED 16-bit field in [8, 65528] at every step, so two fields per register are
@@ -227,24 +216,6 @@ __global__ __launch_bounds__(256) void coarse_table5_kernel(CoarseTableArgs a) {
     const int t = b - n_coarse;
     query_codebook5_body<S, QT>(a.queries, a.cbT, a.cmax, a.qn, a.qscale, a.qc, a.Q, a.d, a.m, a.K, t % a.m, t / a.m, smem, a.qc8);
   }
-}
-
-// The query's running bound (FilterArgs::tau_run), one (item, chunk)'s part: t = key of its own tau', [a_lo, a_up] its coarse
-// distance, inv = the bound as read earlier (0: none).  Reports tau' + a_up if that improves on what was read (one atomic at
-// most), returns the key the item cuts at: min(tau', bound - a_lo).  (Derivation: ivf_filter5_kernel, S1.)
-__device__ __forceinline__ uint32_t running_bound5(uint32_t* __restrict__ tau_run, uint32_t q, uint32_t t, float a_up, float a_lo, uint32_t inv) {
-  const uint32_t tb = (t & 0x80000000u) ? (t ^ 0x80000000u) : ~t;   // key -> bits
-  const float tau = __uint_as_float(tb);
-  if (tau < 3e38f && tau > -3e38f && a_up < 3e38f) {
-    const uint32_t mine = ~float_key(tau + a_up);
-    if (mine > inv) atomicMax(tau_run + q, mine);
-    if (inv != 0u) {
-      const uint32_t bk = ~inv;
-      const float alt = __uint_as_float((bk & 0x80000000u) ? (bk ^ 0x80000000u) : ~bk) - a_lo;
-      if (alt < tau) return float_key(alt);
-    }
-  }
-  return t;
 }
 
 // Entry records as entry_record_kernel; [128 + g] = the table scale of item g's query.
@@ -620,190 +591,22 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_filter5_kernel(FilterArgs a) {
           if (j + 1 < NP) lds_barrier();
         }
       };
-      {
-        int rl = rl_wave;
-        rl = rl < 1 ? 1 : rl;
-        const int rc = (rl + 1) >> 1;
-        using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-        using I4 = std::integral_constant<int, 4>;
-        using I6 = std::integral_constant<int, 6>; using I8 = std::integral_constant<int, 8>;
-        switch ((nq < 1 ? 1 : nq) * 4 + rc) {
-          case 1 * 4 + 1: main_loop(I1{}, I2{}); break;
-          case 1 * 4 + 2: main_loop(I1{}, I4{}); break;
-          case 1 * 4 + 3: main_loop(I1{}, I6{}); break;
-          case 1 * 4 + 4: main_loop(I1{}, I8{}); break;
-          case 2 * 4 + 1: main_loop(I2{}, I2{}); break;
-          case 2 * 4 + 2: main_loop(I2{}, I4{}); break;
-          case 2 * 4 + 3: main_loop(I2{}, I6{}); break;
-          default: main_loop(I2{}, I8{}); break;
-        }
-      }
-      // ---- tail.  The selection works on s' = fma(scale[item], V, rterm[row]) -- the stored sum WITHOUT the item's
-      // constant OFF -- compared as floats: a constant shift changes neither the order nor tau' + E.  OFF (which keeps
-      // the stored bits positive for the merge) is added for the survivors only: s = s' + OFF.
-      // base[r] = the row's own term (staged by the builders in the previous entry's tail, replaced in this one's after the S1 barrier); +inf for the slots of this wave beyond its last block and for the lanes
-      // past the end of the list (s = +inf: above every finite threshold; S2 skips the former and masks the latter)
-      float base[RMAX];
-      const int last_blk = nrows > 0 ? (nrows - 1) >> 6 : -1;     // chunk-relative block holding the last row
-      const int rs2 = (last_blk >= 0 && (last_blk % NG) == gw && (nrows & 63)) ? last_blk / NG : -1;
-      const bool live_lane = lane < (nrows & 63);
-      {
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) {
-          base[r] = rt_s[(r * NG + gw) * 64 + lane];
-          if (r >= rl_wave || (r == rs2 && !live_lane)) base[r] = __uint_as_float(0x7f800000u);
-        }
-      }
-#pragma unroll
-      for (int h = 0; h < G / 2; ++h)
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) acc[h][r] ^= 0x80008000u;   // biased unsigned fields -> signed sums
+      dispatch_nq_rl(nq, rl_wave, main_loop);
+      // ---- tail (scan_tail5.inc)
+#define SCAN_TAIL5_FENCE a.fence
+#define SCAN_TAIL5_PART 1
+#include "scan_tail5.inc"
       gtick(0);
-      auto sval = [&](int g, int r, float sc) -> float {
-        const uint32_t w = acc[g >> 1][r];
-        const int v = (g & 1) ? ((int32_t)w >> 16) : ((int32_t)(w << 16) >> 16);
-        return __builtin_fmaf(sc, (float)v, base[r]);
-      };
-      // Per-item parameters: lane g holds item g's (one LDS read each, fetched with v_readlane below -- a chain of
-      // dependent LDS round trips per item was a quarter of the entry's time).
-      const int gi = lane & 15;
-      const float p_sc = __int_as_float(rec[128 + gi]);
-      // rows this lane really holds: bit r of live8
-      uint32_t live8 = 0u;
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r)
-        if (r < rl_wave && !(r == rs2 && !live_lane)) live8 |= 1u << r;
-      float best[G];
-      uint32_t sec16[G / 2];           // second smallest, rounded DOWN to 16 bits (sign, exponent, 7 bits): two items per register
-      uint32_t apack[2] = {0u, 0u};
-#pragma unroll
-      for (int g = 0; g < G; ++g) best[g] = __uint_as_float(0x7f800000u);
-#pragma unroll
-      for (int i = 0; i < G / 2; ++i) sec16[i] = 0x7f807f80u;
-      if (!(a.fence & 4)) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          if (g < cnt) {
-            // the lane's smallest and second smallest s' of this item and the row of the smallest: a lane hardly ever
-            // holds two survivors, so S2 can emit (best, its row) without looking at the sums again
-            const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_sc), g));
-            float b1 = __uint_as_float(0x7f800000u), b2 = __uint_as_float(0x7f800000u);
-            uint32_t ar = 0u;
-#pragma unroll
-            for (int r = 0; r < RMAX; ++r) {
-              const float sv = sval(g, r, sc);
-              b2 = __builtin_amdgcn_fmed3f(b1, b2, sv);   // (b1 <= b2: the median is the new second smallest)
-              ar = sv < b1 ? (uint32_t)r : ar;
-              b1 = fminf(b1, sv);
-            }
-            best[g] = b1;
-            {
-              const uint32_t bb = __float_as_uint(b2);
-              const uint32_t dn = ((bb >> 31) ? bb + 0xffffu : bb) >> 16;   // toward -inf: the test below errs to the slow path
-              sec16[g >> 1] = (g & 1) ? ((sec16[g >> 1] & 0x0000ffffu) | (dn << 16)) : ((sec16[g >> 1] & 0xffff0000u) | dn);
-            }
-            // (opaque: the compiler otherwise folds the shift into the eight selects above, whose constants 128, 192, ... are no inline
-            // operands -- a v_mov per row and item)
-            asm volatile("" : "+v"(ar));
-            apack[g >> 3] |= ar << (3 * (g & 7));
-            if (rl_wave > 0) atomicMin(colmin + g * 64 + lane, float_key(b1));
-          }
-        }
-      }
+#define SCAN_TAIL5_PART 2
+#include "scan_tail5.inc"
       gtick(1);
       lds_barrier();
       // (S1, the thresholds tau' + E, is computed by the builder waves between these two barriers)
       lds_barrier();
       gtick(-1);
-      // S2: survivors -> this wave's region of each item's buffer.  Normally every lane has at most one (its smallest
-      // sum, kept from the pass above); otherwise the pass bits of the lane's 8 rows, branch free, then per-row ballots.
-      if (!(a.fence & 4)) {
-        const float p_thr = __uint_as_float(thr_s[gi]);
-        const int p_it = rec[8 + gi];
-        const float p_shift = __int_as_float(rec[72 + gi]);
-        const float p_off = __int_as_float(rec[40 + gi]);
-        const uint32_t p_lo = (uint32_t)rec[88 + gi], p_hi = (uint32_t)rec[104 + gi];
-        const int p_q = rec[24 + gi];
-        // lane g: item g's survivor region of this wave, and (collected below) its count -- ONE store of the counts per entry
-        const int p_reg = (p_it * a.upi + chunk) * NG + gw;
-        int cntv = 0;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          if (g < cnt) {
-            const float thr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_thr), g));
-            const float off = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_off), g));
-            const float shift = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_shift), g));
-            const uint32_t region = (uint32_t)__builtin_amdgcn_readlane(p_reg, g);
-            u64* dst = a.surv + (size_t)region * (size_t)(RMAX * 64);
-            int run = 0;
-            if constexpr (!CAND) {   // the common case (freddy.c:366 counts retrieved rows): nothing but the threshold test
-             const float second = __uint_as_float((g & 1) ? (sec16[g >> 1] & 0xffff0000u) : (sec16[g >> 1] << 16));
-             const u64 multi = __ballot(!(second > thr));   // lanes with two survivors (or: keep every row, NaNs)
-             if (__builtin_expect(multi == 0ull, 1)) {
-              // (no uniform branch around the emission: nearly every (item, wave) has a survivor, the exec mask does the rest)
-              const bool pass = !(best[g] > thr);
-              const u64 mask = __ballot(pass);
-              if (pass) {
-                const uint32_t r = (apack[g >> 3] >> (3 * (g & 7))) & 7u;
-                const float dlo = fmaxf(0.0f, (best[g] + off) - shift);
-                const uint32_t loc = ((uint32_t)(blk0 + gw) + r * (uint32_t)NG) * 64u + (uint32_t)lane;
-                dst[lanes_below(mask)] = ((u64)__float_as_uint(dlo) << 32) | (u64)loc;
-              }
-              run = __popcll(mask);
-             } else {
-              const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_sc), g));   // (this path only)
-              uint32_t m8 = 0u;
-#pragma unroll
-              for (int r = RMAX - 1; r >= 0; --r) m8 = m8 + m8 + (!(sval(g, r, sc) > thr) ? 1u : 0u);   // (a NaN passes: exact stage)
-              m8 &= live8;
-              if ((a.fence & 128) == 0 && __ballot(m8 != 0u) != 0ull) {
-#pragma unroll
-                for (int r = 0; r < RMAX; ++r) {
-                  const bool pass = (m8 >> r) & 1u;
-                  const u64 mask = __ballot(pass);
-                  if (mask != 0ull) {
-                    if (pass) {
-                      const float dlo = fmaxf(0.0f, (sval(g, r, sc) + off) - shift);
-                      const uint32_t loc = (uint32_t)(blk0 + r * NG + gw) * 64u + (uint32_t)lane;
-                      dst[run + lanes_below(mask)] = ((u64)__float_as_uint(dlo) << 32) | (u64)loc;
-                    }
-                    run += __popcll(mask);
-                  }
-                }
-              }
-             }
-            } else {   // rows below the sentinel are counted (freddy.c:971): bounds on the bits of s = s' + OFF > 0
-              const uint32_t lo_b = (uint32_t)__builtin_amdgcn_readlane((int)p_lo, g);
-              const uint32_t hi_b = (uint32_t)__builtin_amdgcn_readlane((int)p_hi, g);
-              const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_sc), g));
-              int accepted = 0;
-#pragma unroll
-              for (int r = 0; r < RMAX; ++r) {
-                if (r >= rl_wave) break;
-                const float sv = sval(g, r, sc);
-                const uint32_t sb = __float_as_uint(sv + off);
-                const bool live = (live8 >> r) & 1u;
-                accepted += __popcll(__ballot(live && sb < lo_b));
-                const bool amb = sb >= lo_b && sb < hi_b;
-                const bool pass = live && (!(sv > thr) || amb);
-                const u64 mask = __ballot(pass);
-                if (mask != 0ull) {
-                  if (pass) {
-                    const float dlo = fmaxf(0.0f, __uint_as_float(sb) - shift);
-                    const uint32_t loc = ((uint32_t)(blk0 + r * NG + gw) * 64u + (uint32_t)lane) | (amb ? 0x80000000u : 0u);
-                    dst[run + lanes_below(mask)] = ((u64)__float_as_uint(dlo) << 32) | (u64)loc;
-                  }
-                  run += __popcll(mask);
-                }
-              }
-              if (lane == 0 && accepted) atomicAdd(a.cand_count + __builtin_amdgcn_readlane(p_q, g), accepted);
-            }
-            // (v_writelane: the compiler's own select read its sixteen lane masks back from spilled scalar registers, five instructions per item)
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(cntv) : "s"(run), "i"(g));
-          }
-        }
-        if (lane < cnt) a.surv_count[(uint32_t)p_reg] = cntv;
-      }
+#define SCAN_TAIL5_PART 3
+#include "scan_tail5.inc"
+#undef SCAN_TAIL5_FENCE
       gtick(2);
       const int next_ok = __builtin_amdgcn_readfirstlane(dsc[nb * REC_DW + 6]);
       if (next_ok > 0) prefetch_first_codes(dsc + nb * REC_DW);

@@ -15,7 +15,9 @@
 //     code s | code s + 128 << 16): a builder wave's load is 256 consecutive bytes, an entry's table words are 96 KB -- the
 //     general layout's 2 KB rows, of which K = 256 uses a quarter, cost the builders as much as K = 1024 (measured: no gain).
 //
-// Everything else is fused5.h's: entry queue and records, row terms, the (row, item) sums as unsigned 16-bit fields with the
+// The gatherers' tail is the SAME text as ivf_filter5_kernel's (scan_tail5.inc, without that kernel's fence conditions), the
+// thresholds scan_tail5.h's filter_threshold5.  Everything else is fused5.h's too: entry queue and records, row terms, the
+// (row, item) sums as unsigned 16-bit fields with the
 // biased table, s' = fma(scale, V, rterm) in the tail, thresholds tau' + E with the query's running bound, survivor regions,
 // merge_refine_kernel.  The sums are the same integers, so the survivors and the lists are the same (tests: every K <= 256 index
 // of the GPU suite takes this kernel by default; option codes_u8 = 2 selects fused5.h's one-byte instantiation, 0 the int16 layout).
@@ -35,10 +37,7 @@ __device__ __forceinline__ void scan8_threshold(const FilterArgs& a, const int32
   uint32_t c = colmin[i * 64 + lane];
   c = wave_sort32(c);   // (order-preserving keys of the float column minima)
   uint32_t t = __shfl(c, a.L - 1, 64);
-  if (lane == 0) {
-    if (a.tau_run) t = running_bound5(a.tau_run, (uint32_t)rec[24 + i], t, __int_as_float(rec[144 + i]), __int_as_float(rec[160 + i]), run);
-    thr_s[i] = a.keep_all ? 0x7f800000u : widen_threshold5(t, __int_as_float(rec[56 + i]));
-  }
+  if (lane == 0) thr_s[i] = filter_threshold5(a, rec, i, t, run);
   colmin[i * 64 + lane] = 0xffffffffu;
 }
 
@@ -274,88 +273,19 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_filter8_kernel(FilterArgs a) {
           if (i + 1 < NS) __builtin_amdgcn_sched_barrier(0);
         }
       };
-      {
-        int rl = rl_wave;
-        rl = rl < 1 ? 1 : rl;
-        const int rc = (rl + 1) >> 1;
-        using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-        using I4 = std::integral_constant<int, 4>;
-        using I6 = std::integral_constant<int, 6>; using I8 = std::integral_constant<int, 8>;
-        switch ((nq < 1 ? 1 : nq) * 4 + rc) {
-          case 1 * 4 + 1: main_loop(I1{}, I2{}); break;
-          case 1 * 4 + 2: main_loop(I1{}, I4{}); break;
-          case 1 * 4 + 3: main_loop(I1{}, I6{}); break;
-          case 1 * 4 + 4: main_loop(I1{}, I8{}); break;
-          case 2 * 4 + 1: main_loop(I2{}, I2{}); break;
-          case 2 * 4 + 2: main_loop(I2{}, I4{}); break;
-          case 2 * 4 + 3: main_loop(I2{}, I6{}); break;
-          default: main_loop(I2{}, I8{}); break;
-        }
-      }
+      dispatch_nq_rl(nq, rl_wave, main_loop);
       // the running bound of this wave's item (S1 below: gatherer wave gw takes item gw + 8): on its way during the column minima
       uint32_t run1 = 0u;
       if (a.tau_run) run1 = gw + NG < cnt ? a.tau_run[(uint32_t)rec[24 + gw + NG]] : 0u;
       gtick(0);
       lds_barrier();   // B1: the slab is free for the next entry
       gtick(1);
-      // ---- tail (fused5.h): s' = fma(scale[item], V, rterm[row]) compared as floats; OFF is added for the survivors only
-      float base[RMAX];
-      const int last_blk = nrows > 0 ? (nrows - 1) >> 6 : -1;
-      const int rs2 = (last_blk >= 0 && (last_blk % NG) == gw && (nrows & 63)) ? last_blk / NG : -1;
-      const bool live_lane = lane < (nrows & 63);
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r) {
-        base[r] = rt_s[(r * NG + gw) * 64 + lane];
-        if (r >= rl_wave || (r == rs2 && !live_lane)) base[r] = __uint_as_float(0x7f800000u);
-      }
-#pragma unroll
-      for (int h = 0; h < G / 2; ++h)
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) acc[h][r] ^= 0x80008000u;   // biased unsigned fields -> signed sums
-      auto sval = [&](int g, int r, float sc) -> float {
-        const uint32_t w = acc[g >> 1][r];
-        const int v = (g & 1) ? ((int32_t)w >> 16) : ((int32_t)(w << 16) >> 16);
-        return __builtin_fmaf(sc, (float)v, base[r]);
-      };
-      const int gi = lane & 15;
-      const float p_sc = __int_as_float(rec[128 + gi]);
-      uint32_t live8 = 0u;
-#pragma unroll
-      for (int r = 0; r < RMAX; ++r)
-        if (r < rl_wave && !(r == rs2 && !live_lane)) live8 |= 1u << r;
-      float best[G];
-      uint32_t sec16[G / 2];
-      uint32_t apack[2] = {0u, 0u};
-#pragma unroll
-      for (int g = 0; g < G; ++g) best[g] = __uint_as_float(0x7f800000u);
-#pragma unroll
-      for (int i = 0; i < G / 2; ++i) sec16[i] = 0x7f807f80u;
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        if (g < cnt) {
-          const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_sc), g));
-          float b1 = __uint_as_float(0x7f800000u), b2 = __uint_as_float(0x7f800000u);
-          uint32_t ar = 0u;
-#pragma unroll
-          for (int r = 0; r < RMAX; ++r) {
-            const float sv = sval(g, r, sc);
-            b2 = __builtin_amdgcn_fmed3f(b1, b2, sv);
-            ar = sv < b1 ? (uint32_t)r : ar;
-            b1 = fminf(b1, sv);
-          }
-          best[g] = b1;
-          {
-            const uint32_t bb = __float_as_uint(b2);
-            const uint32_t dn = ((bb >> 31) ? bb + 0xffffu : bb) >> 16;
-            sec16[g >> 1] = (g & 1) ? ((sec16[g >> 1] & 0x0000ffffu) | (dn << 16)) : ((sec16[g >> 1] & 0xffff0000u) | dn);
-          }
-          // (opaque: the compiler otherwise folds the shift into the eight selects above, whose constants 128, 192, ... are no inline
-          // operands -- a v_mov per row and item)
-          asm volatile("" : "+v"(ar));
-          apack[g >> 3] |= ar << (3 * (g & 7));
-          if (rl_wave > 0) atomicMin(colmin + g * 64 + lane, float_key(b1));
-        }
-      }
+      // ---- tail (scan_tail5.inc): s' = fma(scale[item], V, rterm[row]) compared as floats; OFF is added for the survivors only
+#define SCAN_TAIL5_FENCE 0u
+#define SCAN_TAIL5_PART 1
+#include "scan_tail5.inc"
+#define SCAN_TAIL5_PART 2
+#include "scan_tail5.inc"
       gtick(2);
       lds_barrier();   // B2: every wave's column minima are in
       gtick(3);
@@ -364,94 +294,9 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_filter8_kernel(FilterArgs a) {
       gtick(4);
       lds_barrier();   // B3: thresholds
       gtick(5);
-      // S2: survivors -> this wave's region of each item's buffer (fused5.h)
-      {
-        const float p_thr = __uint_as_float(thr_s[gi]);
-        const int p_it = rec[8 + gi];
-        const float p_shift = __int_as_float(rec[72 + gi]);
-        const float p_off = __int_as_float(rec[40 + gi]);
-        const uint32_t p_lo = (uint32_t)rec[88 + gi], p_hi = (uint32_t)rec[104 + gi];
-        const int p_q = rec[24 + gi];
-        // lane g: item g's survivor region of this wave, and (collected below) its count -- ONE store of the counts per entry
-        const int p_reg = (p_it * a.upi + chunk) * NG + gw;
-        int cntv = 0;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          if (g < cnt) {
-            const float thr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_thr), g));
-            const float off = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_off), g));
-            const float shift = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_shift), g));
-            const uint32_t region = (uint32_t)__builtin_amdgcn_readlane(p_reg, g);
-            u64* dst = a.surv + (size_t)region * (size_t)(RMAX * 64);
-            int run = 0;
-            if constexpr (!CAND) {
-              const float second = __uint_as_float((g & 1) ? (sec16[g >> 1] & 0xffff0000u) : (sec16[g >> 1] << 16));
-              const u64 multi = __ballot(!(second > thr));
-              if (__builtin_expect(multi == 0ull, 1)) {
-                // (no uniform branch around the emission: nearly every (item, wave) has a survivor, the exec mask does the rest)
-                const bool pass = !(best[g] > thr);
-                const u64 mask = __ballot(pass);
-                if (pass) {
-                  const uint32_t r = (apack[g >> 3] >> (3 * (g & 7))) & 7u;
-                  const float dlo = fmaxf(0.0f, (best[g] + off) - shift);
-                  const uint32_t loc = ((uint32_t)(blk0 + gw) + r * (uint32_t)NG) * 64u + (uint32_t)lane;
-                  dst[lanes_below(mask)] = ((u64)__float_as_uint(dlo) << 32) | (u64)loc;
-                }
-                run = __popcll(mask);
-              } else {
-                const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_sc), g));   // (this path only)
-              uint32_t m8 = 0u;
-#pragma unroll
-                for (int r = RMAX - 1; r >= 0; --r) m8 = m8 + m8 + (!(sval(g, r, sc) > thr) ? 1u : 0u);
-                m8 &= live8;
-                if (__ballot(m8 != 0u) != 0ull) {
-#pragma unroll
-                  for (int r = 0; r < RMAX; ++r) {
-                    const bool pass = (m8 >> r) & 1u;
-                    const u64 mask = __ballot(pass);
-                    if (mask != 0ull) {
-                      if (pass) {
-                        const float dlo = fmaxf(0.0f, (sval(g, r, sc) + off) - shift);
-                        const uint32_t loc = (uint32_t)(blk0 + r * NG + gw) * 64u + (uint32_t)lane;
-                        dst[run + lanes_below(mask)] = ((u64)__float_as_uint(dlo) << 32) | (u64)loc;
-                      }
-                      run += __popcll(mask);
-                    }
-                  }
-                }
-              }
-            } else {
-              const uint32_t lo_b = (uint32_t)__builtin_amdgcn_readlane((int)p_lo, g);
-              const uint32_t hi_b = (uint32_t)__builtin_amdgcn_readlane((int)p_hi, g);
-              const float sc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_sc), g));
-              int accepted = 0;
-#pragma unroll
-              for (int r = 0; r < RMAX; ++r) {
-                if (r >= rl_wave) break;
-                const float sv = sval(g, r, sc);
-                const uint32_t sb = __float_as_uint(sv + off);
-                const bool live = (live8 >> r) & 1u;
-                accepted += __popcll(__ballot(live && sb < lo_b));
-                const bool amb = sb >= lo_b && sb < hi_b;
-                const bool pass = live && (!(sv > thr) || amb);
-                const u64 mask = __ballot(pass);
-                if (mask != 0ull) {
-                  if (pass) {
-                    const float dlo = fmaxf(0.0f, __uint_as_float(sb) - shift);
-                    const uint32_t loc = ((uint32_t)(blk0 + r * NG + gw) * 64u + (uint32_t)lane) | (amb ? 0x80000000u : 0u);
-                    dst[run + lanes_below(mask)] = ((u64)__float_as_uint(dlo) << 32) | (u64)loc;
-                  }
-                  run += __popcll(mask);
-                }
-              }
-              if (lane == 0 && accepted) atomicAdd(a.cand_count + __builtin_amdgcn_readlane(p_q, g), accepted);
-            }
-            // (v_writelane: the compiler's own select read its sixteen lane masks back from spilled scalar registers, five instructions per item)
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(cntv) : "s"(run), "i"(g));
-          }
-        }
-        if (lane < cnt) a.surv_count[(uint32_t)p_reg] = cntv;
-      }
+#define SCAN_TAIL5_PART 3
+#include "scan_tail5.inc"
+#undef SCAN_TAIL5_FENCE
       const int next_ok = __builtin_amdgcn_readfirstlane(dsc[nb * REC_DW + 6]);
       if (next_ok > 0) prefetch_codes(dsc + nb * REC_DW);
       gtick(5);
@@ -461,10 +306,10 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_filter8_kernel(FilterArgs a) {
       cur = nb;
     }
     if (PROF && a.prof && gw == 0 && lane == 0) {
+      // slots 0-5, per entry summed: gather, B1, column minima, B2, S1, B3 + S2 + B4; 6: the prologue; 7: the workgroup's whole life
       for (int i = 0; i < 6; ++i) a.prof[(size_t)blockIdx.x * 8 + i] = gt[i];
-      a.prof[(size_t)blockIdx.x * 8 + 6] = gt[6] + (clock64() - gc) * 0;                                   // S2 (the wait at B4 is in the life, not here)
-      a.prof[(size_t)blockIdx.x * 8 + 6] = gt[7];                                                          // slot 6: the prologue
-      a.prof[(size_t)blockIdx.x * 8 + 7] = clock64() - t_kernel;                                           // the workgroup's whole life
+      a.prof[(size_t)blockIdx.x * 8 + 6] = gt[7];
+      a.prof[(size_t)blockIdx.x * 8 + 7] = clock64() - t_kernel;
     }
   }
 }

@@ -358,7 +358,7 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   // 96 -> 128 us -- and its merge gains nothing; an IVFADC batch: +2.6 % queries/s with four batches in flight)
   fl.tau_run = (ix->tune.running_bound && !r.records_ready) ? ws->w_cand.as<uint32_t>() + Q : nullptr;
   if (int rc = scan_prof_buffer(ix, ws, &fl.prof)) return rc;
-  // K <= 256: one byte per code (packed8); the profiling instantiation stays with the int16 layout
+  // K <= 256: one byte per code (packed8) unless option codes_u8 = 0 asks for the int16 layout
   const bool u8 = ix->packed8 && ix->tune.codes_u8 != 0 && K <= 256;
   // ... and by default the kernel that keeps the WHOLE entry's slab in LDS (fused8.h; option codes_u8 = 2: fused5.h's one-byte instantiation)
   const bool whole = u8 && scan_whole_slab(ix);
@@ -436,7 +436,7 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
     int32_t ng = 0;
     HIP_TRY(hipMemcpy(&ng, wt.n_groups, 4, hipMemcpyDeviceToHost));
     const double e = std::max(1, ng);
-    fprintf(stderr, "[scan8 prof] wgs=%u entries=%d  gatherer wave 0 cycles/entry: gather=%.0f B1=%.0f colmin=%.0f B2=%.0f S1=%.0f B3+S2+B4=%.0f | per workgroup: prologue %.0f, stages %.0f, life mean %.0f min %.0f max %.0f\n",
+    fprintf(stderr, "[scan8 prof] wgs=%u entries=%d  gatherer wave 0 cycles/entry (slots 0-5): gather=%.0f B1=%.0f colmin=%.0f B2=%.0f S1=%.0f B3+S2+B4=%.0f | per workgroup: prologue (slot 6) %.0f, stages (0-5) %.0f, life (slot 7) mean %.0f min %.0f max %.0f\n",
             n_persist, ng, sum[0] / e, sum[1] / e, sum[2] / e, sum[3] / e, sum[4] / e, sum[5] / e, sum[6] / n_persist,
             (sum[0] + sum[1] + sum[2] + sum[3] + sum[4] + sum[5]) / n_persist, sum[7] / n_persist, life_min, life_max);
   }
@@ -486,6 +486,18 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   return 0;
 }
 
+// merge_surv_kernel's arguments for a round whose scan (exact or multi) left its survivors in (surv, surv_count)
+static MergeSurvArgs merge_surv_args(const IvfRun& r, const PlanArgs& pa, const u64* surv, const int32_t* surv_count, const int32_t* cand_count) {
+  MergeSurvArgs ms;
+  ms.surv = surv; ms.surv_count = surv_count; ms.active = r.active; ms.round_rows = pa.round_rows;
+  ms.cand_count = cand_count; ms.out_ids = r.d_out_ids; ms.out_dist = r.d_out_dist;
+  ms.found = r.ws->w_found.as<int32_t>(); ms.next_active = r.next; ms.n_next = r.ws->w_cnt.as<int32_t>();
+  ms.status = r.d_status;
+  ms.n_active = r.n_active; ms.W = r.W; ms.upi = r.upi; ms.L = r.L; ms.k = r.k; ms.found_rule = r.found_rule;
+  ms.first_round = r.first() ? 1 : 0; ms.sentinel = r.sentinel;
+  return ms;
+}
+
 // The yardstick: the reference's arithmetic for every probed row (fused3.h).  ivf_spec2_kernel -> merge_surv_kernel.
 static int ivf_scan_exact(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   Workspace* ws = r.ws;
@@ -514,13 +526,7 @@ static int ivf_scan_exact(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
 #ifdef FREDDY_LAB
   if (fa.prof) if (int rc = scan_prof_print(ix, s, fa.prof, n_persist)) return rc;
 #endif
-  MergeSurvArgs ms;
-  ms.surv = fa.surv; ms.surv_count = fa.surv_count; ms.active = r.active; ms.round_rows = pa.round_rows;
-  ms.cand_count = fa.cand_count; ms.out_ids = r.d_out_ids; ms.out_dist = r.d_out_dist;
-  ms.found = ws->w_found.as<int32_t>(); ms.next_active = r.next; ms.n_next = ws->w_cnt.as<int32_t>();
-  ms.status = r.d_status;
-  ms.n_active = r.n_active; ms.W = r.W; ms.upi = r.upi; ms.L = r.L; ms.k = r.k; ms.found_rule = r.found_rule;
-  ms.first_round = r.first() ? 1 : 0; ms.sentinel = r.sentinel;
+  const MergeSurvArgs ms = merge_surv_args(r, pa, fa.surv, fa.surv_count, fa.cand_count);
   timed_launch(ix, s, "merge_surv", [&] { hipLaunchKernelGGL(merge_surv_kernel, dim3(r.n_active), dim3(64), 0, s, ms); });
   HIP_TRY(hipGetLastError());
   return 0;
@@ -547,13 +553,7 @@ static int ivf_scan_multi(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   const unsigned grid = (unsigned)std::min<size_t>(wt.max_groups, (size_t)ix->n_cus * per_cu);
   timed_launch(ix, s, "ivf_multi_scan", [&] { hipLaunchKernelGGL(ivf_multi_kernel, dim3(grid), dim3(MULTI_T), lds, s, ma); });
   HIP_TRY(hipGetLastError());
-  MergeSurvArgs ms;
-  ms.surv = ma.surv; ms.surv_count = ma.surv_count; ms.active = r.active; ms.round_rows = pa.round_rows;
-  ms.cand_count = ma.cand_count; ms.out_ids = r.d_out_ids; ms.out_dist = r.d_out_dist;
-  ms.found = ws->w_found.as<int32_t>(); ms.next_active = r.next; ms.n_next = ws->w_cnt.as<int32_t>();
-  ms.status = r.d_status;
-  ms.n_active = r.n_active; ms.W = r.W; ms.upi = r.upi; ms.L = r.L; ms.k = r.k; ms.found_rule = r.found_rule;
-  ms.first_round = r.first() ? 1 : 0; ms.sentinel = r.sentinel;
+  const MergeSurvArgs ms = merge_surv_args(r, pa, ma.surv, ma.surv_count, ma.cand_count);
   timed_launch(ix, s, "merge_surv", [&] { hipLaunchKernelGGL(merge_surv_kernel, dim3(r.n_active), dim3(64), 0, s, ms); });
   HIP_TRY(hipGetLastError());
   return 0;

@@ -9,7 +9,8 @@
 //   * a lane holds 16 rows: per row six code dwords, twelve ds_read_u16 lookups, the sum (unsigned, see filt5_bias),
 //     s' = fma(scale, V, rterm[row]) -- the SAME value, bit for bit, as the cell-grouped scan forms, kept in registers;
 //   * threshold and survivors exactly as there: tau' = the L-th smallest of the 64 column minima, rows with
-//     s' <= tau' + E (and the sentinel rule's ambiguous rows) -> the item's survivor regions, (bits(d_lo) << 32) | location.
+//     s' <= tau' + E (and the sentinel rule's ambiguous rows) -> the item's survivor regions, surv_key5(d_lo, location) (the
+//     contract with the merge: scan_tail5.inc).
 //     Wave w's row slots r = 0 .. 15 are the blocks 4 r + w of the chunk, i.e. the cell-grouped scan's gatherer waves
 //     w (even r) and w + 4 (odd r): the regions, their capacity and merge_refine_kernel are unchanged.
 // Which cells go here: work_table_kernel (sparse_max items or fewer); the units are pulled from a queue like the scan's.
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(256, 6) void sparse_item5_kernel(SparseArgs a) {
         if (pass) {
           const float dlo = CAND ? fmaxf(0.0f, __uint_as_float(sb) - ib.shift) : fmaxf(0.0f, (sv[r] + ib.off) - ib.shift);
           const uint32_t loc = ((uint32_t)(b0 + bl) * 64u + (uint32_t)lane) | ((CAND && amb) ? 0x80000000u : 0u);
-          dst[h][run[h] + lanes_below(mask)] = ((u64)__float_as_uint(dlo) << 32) | (u64)loc;
+          dst[h][run[h] + lanes_below(mask)] = surv_key5(dlo, loc);
         }
         run[h] += __popcll(mask);
       }
@@ -381,7 +382,7 @@ __global__ __launch_bounds__(256, 3) void sparse_pair5_kernel(SparseArgs a) {
             if (pass) {
               const float dlo = CAND ? fmaxf(0.0f, __uint_as_float(sb) - ib[i].shift) : fmaxf(0.0f, (sv[i][r] + ib[i].off) - ib[i].shift);
               const uint32_t loc = ((uint32_t)(b0 + bl) * 64u + (uint32_t)lane) | ((CAND && amb) ? 0x80000000u : 0u);
-              dst[h][run[h] + lanes_below(mask)] = ((u64)__float_as_uint(dlo) << 32) | (u64)loc;
+              dst[h][run[h] + lanes_below(mask)] = surv_key5(dlo, loc);
             }
             run[h] += __popcll(mask);
           }
