@@ -4,7 +4,8 @@
 //   pin.hip     pin_pq / pin_ivf(_multi): table layouts; append_rows / update_codebook (HBM index mutation)
 //   ivfadc.hip  the IVFADC search: cell selection, work table, scans, merge; *_dev entry, host-buffer pipeline, one-query launch
 //   pq.hip      pq_search (+ subsets, pseudo-list batches, one-query launch), grouping_pq
-//   join.hip    pin_ivpq, knn_join
+//   join.hip    pin_ivpq, knn_join (join.h: overview; join_kernels.h and join_traverse.h the kernels, join_host.h the host heap, join_run.h the run
+//               record of a call and its stages)
 //   exact.hip   pin_vectors, exact kNN
 //   build.hip   encode, insert_quantize, k-means
 // Kernel headers are included by the unit that launches them (kernels shared by two units are static or templates).

@@ -1,7 +1,48 @@
-// join.hip -- pin_ivpq and knn_join (ivpq_search_in.c:61-699); the kernels and the host loop are in join.h.
+// join.hip -- pin_ivpq and knn_join (ivpq_search_in.c:61-699): the entry points.  join.h says which header holds what; the
+// call itself is join_run() in join_run.h.
 #include "internal.h"
 
 #include "join.h"
+#include "join_run.h"
+
+// the ivpq tables in the layouts the kernels read (checked first: ascending ids, cells and codes in range)
+static int join_pin(JoinIndex* j, const freddy_ivpq_desc* t, int64_t* bytes) {
+  j->d = t->d; j->m = t->m; j->K = t->K; j->S = t->d / t->m; j->Kc = t->coarse_codes;
+  j->cells = t->coarse_codes * t->coarse_codes;
+  j->MP = (t->m + 7) & ~7;
+  j->N = t->N;
+  j->has_vectors = t->vectors != nullptr;
+  if (t->K > 32767) return join_fail(FREDDY_E_LIMIT, "K=%d does not fit an int16 code", t->K);
+  for (int64_t r = 0; r < t->N; ++r) {
+    if (r && t->ids[r] <= t->ids[r - 1]) return join_fail(FREDDY_E_ARG, "ids must be strictly ascending (row %lld)", (long long)r);
+    if (t->coarse_id[r] < 0 || t->coarse_id[r] >= j->cells) return join_fail(FREDDY_E_ARG, "coarse_id %d out of range at row %lld", t->coarse_id[r], (long long)r);
+    for (int l = 0; l < t->m; ++l) {
+      const int c = t->codes[(size_t)r * t->m + l];
+      if (c < 0 || c >= t->K) return join_fail(FREDDY_E_ARG, "code %d out of range at row %lld", c, (long long)r);
+    }
+  }
+  const int m = j->m, K = j->K, S = j->S, half = j->d / 2, Kc = j->Kc;
+  std::vector<float> cbT((size_t)m * S * K);
+  for (int p = 0; p < m; ++p)
+    for (int c = 0; c < K; ++c)
+      for (int i = 0; i < S; ++i) cbT[((size_t)p * S + i) * K + c] = t->codebook[((size_t)p * K + c) * S + i];
+  std::vector<float> cqT((size_t)2 * half * Kc);
+  for (int p = 0; p < 2; ++p)
+    for (int c = 0; c < Kc; ++c)
+      for (int i = 0; i < half; ++i) cqT[((size_t)p * half + i) * Kc + c] = t->coarse[((size_t)p * Kc + c) * half + i];
+  if (upload(&j->cbT, cbT.data(), cbT.size(), bytes) || upload(&j->coarseT, cqT.data(), cqT.size(), bytes) ||
+      upload(&j->ids, t->ids, (size_t)t->N, bytes) || upload(&j->codes, join_pad_codes(t->codes, t->N, m, j->MP).data(), (size_t)t->N * j->MP, bytes) ||
+      upload(&j->cell, t->coarse_id, (size_t)t->N, bytes) || upload(&j->d_stats, t->stats, (size_t)j->cells + 1, bytes) ||
+      (t->vectors && upload(&j->vectors, t->vectors, (size_t)t->N * t->d, bytes)))
+    return join_fail(FREDDY_E_NOMEM, "device allocation failed while pinning the ivpq tables");
+  j->h_ids.assign(t->ids, t->ids + t->N);
+  j->h_cell.assign(t->coarse_id, t->coarse_id + t->N);
+  j->h_stats.assign(t->stats, t->stats + j->cells + 1);
+  if (hipMalloc((void**)&j->markbits, sizeof(uint32_t) * (size_t)((t->N + 31) / 32 + 1)) != hipSuccess)
+    return join_fail(FREDDY_E_NOMEM, "device allocation failed while pinning the ivpq tables");
+  j->ids_affine = t->N > 0 && (int64_t)t->ids[t->N - 1] - t->ids[0] == t->N - 1;   // strictly ascending => consecutive
+  return 0;
+}
 
 extern "C" int freddy_gpu_pin_ivpq(const freddy_ivpq_desc* t, int device, freddy_gpu_index_t** out) {
   if (!t || !out || !t->codebook || !t->coarse || !t->stats || (t->N && (!t->ids || !t->codes || !t->coarse_id)))
@@ -24,7 +65,7 @@ extern "C" int freddy_gpu_pin_ivpq(const freddy_ivpq_desc* t, int device, freddy
 }
 
 // ---------------------------------------------------------------------------------------
-// kNN-join (ivpq_search_in): host loop in join.h
+// kNN-join (ivpq_search_in): host loop in join_run.h
 // ---------------------------------------------------------------------------------------
 extern "C" int freddy_gpu_knn_join(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k,
                                    const int32_t* target_ids, int64_t n_targets, int32_t alpha, int32_t pvf,

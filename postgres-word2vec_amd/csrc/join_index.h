@@ -1,5 +1,5 @@
-// join_index.h -- the pinned ivpq index (JoinIndex), its workspaces and error buffer: what the handle holds; the kernels and
-// the host loop of the kNN-join are in join.h.
+// join_index.h -- the pinned ivpq index (JoinIndex), its workspaces and error buffer: what the handle holds.  The kNN-join
+// itself: join.h (overview), join_kernels.h, join_traverse.h, join_host.h, join_run.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -42,8 +42,29 @@ static inline int join_fail(int code, const char* fmt, ...) {
   do {                                                                                          \
     hipError_t e_ = (expr);                                                                     \
     if (e_ != hipSuccess)                                                                       \
-      return join_fail(FREDDY_E_HIP, "%s failed: %s (join.h:%d)", #expr, hipGetErrorString(e_), __LINE__); \
+      return join_fail(FREDDY_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
+
+// The device workspaces of a call (JoinIndex::w), grown on demand and kept between calls.  Every one is a buffer of its own:
+// JW_SCAN and JW_ACTIVE, JW_QCELLS and JW_QCELLS_FLAT are live at the same time in stream order.
+enum JoinSlot {
+  JW_QUERIES,      // float [Q][d]        the queries
+  JW_SUB,          // float [Q][2][Kc]    their sub-distances to the multi-index centroids
+  JW_TCELL_OFF,    // int32 [cells + 1]   target buckets by cell   } kept for the next call with the same target array
+  JW_TROW,         // int32 [n_targets]   target rows by bucket    } (JoinIndex::tl_valid)
+  JW_SCAN,         // int32 [Q]           the round's scan list (before it: the `only` list of a partial side sort)
+  JW_QCELL_OFF,    // int32 [Q + 1]       host-traversed queries: offsets into JW_QCELLS_FLAT
+  JW_QCELLS_FLAT,  // int32               host-traversed queries: their cells, back to back
+  JW_WIN,          // int32 [n_targets]   mark kernel: the row a target id won (-1: unknown or duplicate)
+  JW_CELL_CNT,     // int32 [2][cells]    targets per cell, fill cursors of the place kernel
+  JW_SORTED,       // JoinSide [Q][2][Kc] the sides in stable ascending order (host heap)
+  JW_ACTIVE,       // int32 [Q]           the round's active list
+  JW_QCELLS,       // int32 [Q][cells]    device traversal: row q = the cells query q takes
+  JW_QCELL_CNT,    // int32 [Q]           device traversal: how many
+  JW_BIG_KEYS,     // u64   [n_scan][L]   BIG: post verification's candidates ...
+  JW_BIG_EXACT,    // float [n_scan][L]   ... and their exact distances
+  JW_SLOTS
+};
 
 struct JoinIndex {
   int d = 0, m = 0, K = 0, S = 0, Kc = 0, cells = 0;
@@ -66,7 +87,7 @@ struct JoinIndex {
   std::vector<float> h_stats;
   bool ids_affine = false;       // ids[r] == ids[0] + r: O(1) id -> row
   // "fq.id IN (targets)" of the previous call: the same target array (compared word for word) finds its rows resolved,
-  // de-duplicated and bucketed by cell already (workspaces 2 and 3 stay as they are); invalidated when rows are appended
+  // de-duplicated and bucketed by cell already (JW_TCELL_OFF and JW_TROW stay as they are); invalidated when rows are appended
   // (kept in ONE pinned block: [cells + 1] bucket offsets, written by the offsets kernel, then the target array, which the mark
   // kernel reads over PCIe -- no SDMA copy in either direction, and the copy the next call is compared with is the staging copy)
   PinnedBuf h_tl;
@@ -74,8 +95,8 @@ struct JoinIndex {
   int tl_cells = -1;
   bool tl_valid = false;
   // workspaces
-  void* w[18] = {nullptr};
-  size_t wcap[18] = {0};
+  void* w[JW_SLOTS] = {nullptr};
+  size_t wcap[JW_SLOTS] = {0};
   float libm_margin = 1e-5f;     // option join_libm_margin_ppm: device confidences this close to the threshold are re-evaluated by the host's libm
   bool host_traversal = false;   // option join_host_traversal / FREDDY_GPU_JOIN_HOST_TRAVERSAL: every traversal on the host heap
   // stage timers of the last call under the reference's TRACK names (ivpq_search_in.c:234-697)
@@ -83,7 +104,9 @@ struct JoinIndex {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
-static inline int join_buf(JoinIndex* j, int slot, size_t bytes, void** out) {
+template <class T>
+static inline int join_buf(JoinIndex* j, JoinSlot slot, size_t count, T** out) {
+  const size_t bytes = sizeof(T) * count;
   if (bytes > j->wcap[slot]) {
     if (j->w[slot]) (void)hipFree(j->w[slot]);
     j->w[slot] = nullptr;
@@ -92,7 +115,7 @@ static inline int join_buf(JoinIndex* j, int slot, size_t bytes, void** out) {
     if (hipMalloc(&j->w[slot], want) != hipSuccess) return join_fail(FREDDY_E_NOMEM, "workspace allocation of %zu bytes failed", want);
     j->wcap[slot] = want;
   }
-  *out = j->w[slot];
+  *out = static_cast<T*>(j->w[slot]);
   return 0;
 }
 
@@ -100,7 +123,7 @@ static inline void join_free(JoinIndex* j) {
   void* ptrs[] = {j->cbT, j->coarseT, j->ids, j->codes, j->vectors, j->cell, j->markbits, j->d_stats};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (PinnedBuf* b : {&j->h_q, &j->h_sum, &j->h_tl}) b->release();
-  for (int i = 0; i < 18; ++i) if (j->w[i]) (void)hipFree(j->w[i]);
+  for (int i = 0; i < JW_SLOTS; ++i) if (j->w[i]) (void)hipFree(j->w[i]);
   if (j->ev0) (void)hipEventDestroy(j->ev0);
   if (j->ev1) (void)hipEventDestroy(j->ev1);
   *j = JoinIndex();
@@ -111,6 +134,5 @@ static inline std::vector<int16_t> join_pad_codes(const int16_t* codes, int64_t 
   for (int64_t r = 0; r < n; ++r) memcpy(&out[(size_t)r * MP], codes + (size_t)r * m, sizeof(int16_t) * m);
   return out;
 }
-
 
 }  // namespace freddy
