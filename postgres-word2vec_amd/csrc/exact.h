@@ -28,6 +28,11 @@ static constexpr int EX_WAVES = EX_WG / 64;
 // queries per workgroup (every tile of queries streams the whole table once): 16 for batches while the
 // selection state fits the registers (k <= 256), else 8
 __host__ __device__ constexpr int ex_qt(int V, int Q) { return (V <= 4 && Q > 8) ? 16 : 8; }
+// dynamic LDS of exact_scan_kernel: the tile's queries [d][QT] and one staging row per (wave, query).  A CU has 160 KiB: tiles
+// of 16 queries fit up to d = 2048 (wider tables take tiles of 8), tiles of 8 up to EX_MAX_D, the widest table a handle accepts.
+static constexpr size_t EX_MAX_LDS = 160 * 1024;
+static inline size_t exact_scan_lds(int d, int QT) { return (((size_t)d * QT * 4 + 15) & ~(size_t)15) + (size_t)EX_WAVES * QT * 64 * sizeof(unsigned long long); }
+static constexpr int EX_MAX_D = (int)((EX_MAX_LDS - (size_t)EX_WAVES * 8 * 64 * sizeof(unsigned long long)) / (8 * 4));   // 4608
 
 __device__ __forceinline__ u64 sim_key(float sim, uint32_t row) {
   const uint32_t b = __float_as_uint(sim);

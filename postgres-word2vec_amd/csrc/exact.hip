@@ -170,6 +170,7 @@ static int exact_filter_search(freddy_gpu_index* ix, Workspace* ws, hipStream_t 
 extern "C" int freddy_gpu_pin_vectors(const freddy_vec_desc* t, int device, freddy_gpu_index_t** out) {
   if (!t || !out || t->d <= 0 || t->N < 0 || (t->N && (!t->ids || !t->vectors))) return fail(FREDDY_E_ARG, "bad argument");
   if (t->N > (int64_t)INT32_MAX - 64) return fail(FREDDY_E_LIMIT, "N too large for 32-bit row positions");
+  if (t->d > EX_MAX_D) return fail(FREDDY_E_LIMIT, "d=%d exceeds the exact search's limit of %d dimensions (a query tile must fit the LDS)", t->d, EX_MAX_D);
   for (int64_t r = 1; r < t->N; ++r)
     if (t->ids[r] <= t->ids[r - 1]) return fail(FREDDY_E_ARG, "ids must be strictly ascending (row %lld)", (long long)r);
   freddy_gpu_index* ix = new freddy_gpu_index();
@@ -278,7 +279,8 @@ extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* quer
     }
   }
   int chunk_blocks = 8;   // 512 rows per workgroup-chunk; longer chunks once the grid is large enough
-  const int EX_QT = ex_qt(V, Q);
+  int EX_QT = ex_qt(V, Q);
+  if (EX_QT == 16 && exact_scan_lds(d, 16) > EX_MAX_LDS) EX_QT = 8;   // (d > 2048: sixteen queries do not fit the LDS; d <= EX_MAX_D: eight do)
   const int qgroups = (Q + EX_QT - 1) / EX_QT;
   while ((n_blocks + chunk_blocks - 1) / chunk_blocks * (int64_t)qgroups > 8192 && chunk_blocks < 1024) chunk_blocks *= 2;
   const int nchunk = (int)std::max<int64_t>(1, (n_blocks + chunk_blocks - 1) / chunk_blocks);
@@ -290,7 +292,7 @@ extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* quer
   ExactArgs ea;
   ea.xb = xb; ea.pos = pos; ea.queries = ws->w_q.as<float>(); ea.part = ws->w_part.as<u64>();
   ea.n_rows = n_rows; ea.n_blocks = (int)n_blocks; ea.chunk_blocks = chunk_blocks; ea.nchunk = nchunk; ea.Q = Q; ea.d = d; ea.L = L; ea.floor = nullptr;
-  const size_t lds = (((size_t)d * EX_QT * 4 + 15) & ~(size_t)15) + (size_t)EX_WAVES * EX_QT * 64 * sizeof(u64);
+  const size_t lds = exact_scan_lds(d, EX_QT);
   dim3 grid((unsigned)nchunk, (unsigned)qgroups);
   const int ppq = nchunk * EX_WAVES;
   if (k > 1024) {
@@ -543,5 +545,9 @@ std::vector<LdsLimit> lds_limits_exact() {
   const int b = (int)AN_MAX_LDS;
   return {{&exf_filter_kernel<1, false>, b}, {&exf_filter_kernel<2, false>, b}, {&exf_filter_kernel<1, true>, b}, {&exf_filter_kernel<2, true>, b},
           {&an_filter_kernel<1, false>, b},  {&an_filter_kernel<3, false>, b},  {&an_filter_kernel<1, true>, b},  {&an_filter_kernel<3, true>, b},
-          {&an_scan_kernel<1, 8>, b},        {&an_scan_kernel<3, 4>, b}};
+          {&an_scan_kernel<1, 8>, b},        {&an_scan_kernel<3, 4>, b},
+          // (the all-exact scan: more than 64 KiB from d = 513 on with tiles of 16 queries, from d = 1537 on with tiles of 8)
+          &exact_scan_kernel<1, 16>, &exact_scan_kernel<2, 16>, &exact_scan_kernel<4, 16>,
+          &exact_scan_kernel<1, 8>, &exact_scan_kernel<2, 8>, &exact_scan_kernel<4, 8>, &exact_scan_kernel<8, 8>, &exact_scan_kernel<16, 8>,
+          &exact_scan_kernel<16, 8, true>};
 }

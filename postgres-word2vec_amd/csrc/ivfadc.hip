@@ -1096,6 +1096,7 @@ std::vector<LdsLimit> lds_limits_ivfadc() {
           &ivf_filter5_kernel<12, true, false, true>, &ivf_filter8_kernel<12, false, true>,
 #endif
           &coarse_approx_kernel, &coarse_approx16_kernel, &ivf_multi_kernel,
+          &coarse_dist_kernel<16>,   // (small batches over vectors of more than 1024 dimensions: 64 bytes per dimension)
           // (static LDS beside the dynamic: 16384 keys + 4096 carried ids = 144 KB)
           {&bigk_replay_kernel, (int)bigk_lds_bytes(16384, BIGK_KMAX)}};
 }

@@ -1001,6 +1001,7 @@ __global__ __launch_bounds__(64) void merge_replay_kernel(MergeArgs a) {
 // ---------------------------------------------------------------------------------------
 static constexpr int GROUP_BLOCKS = 16;
 template <int M2>   // dwords of codes per row; 0: read the codes from memory for every group (any m)
+// (an odd m: the upper half of a row's last dword is padding, not a code -- position m does not exist)
 __global__ __launch_bounds__(WG) void grouping_kernel(const float* __restrict__ lut, int G, int m, int K,
                                                      const uint32_t* __restrict__ packed, int n_blocks,
                                                      int32_t* __restrict__ out_group) {
@@ -1008,7 +1009,7 @@ __global__ __launch_bounds__(WG) void grouping_kernel(const float* __restrict__ 
   float* sl = reinterpret_cast<float*>(smem);   // [m][K]
   constexpr int RPT = GROUP_BLOCKS * 64 / WG;   // rows per thread
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int m2 = M2 ? M2 : m / 2;
+  const int m2 = M2 ? M2 : (m + 1) / 2;
   uint32_t cw[RPT][M2 ? M2 : 1];
   float best[RPT];
   int bi[RPT];
@@ -1036,13 +1037,13 @@ __global__ __launch_bounds__(WG) void grouping_kernel(const float* __restrict__ 
         for (int j = 0; j < (M2 ? M2 : 1); ++j) {
           const uint32_t w = cw[r][j];
           dist = dist + sl[(2 * j) * K + (int)(w & 0xffffu)];
-          dist = dist + sl[(2 * j + 1) * K + (int)(w >> 16)];
+          if (2 * j + 1 < m) dist = dist + sl[(2 * j + 1) * K + (int)(w >> 16)];
         }
       } else {
         for (int j = 0; j < m2; ++j) {
           const uint32_t w = packed[((size_t)blk[r] * m2 + j) * 64 + lane];
           dist = dist + sl[(2 * j) * K + (int)(w & 0xffffu)];
-          dist = dist + sl[(2 * j + 1) * K + (int)(w >> 16)];
+          if (2 * j + 1 < m) dist = dist + sl[(2 * j + 1) * K + (int)(w >> 16)];
         }
       }
       if (dist < best[r]) { best[r] = dist; bi[r] = g; }

@@ -368,6 +368,8 @@ extern "C" int freddy_gpu_pin_ivf(const freddy_ivf_desc* t, int device, freddy_g
     return fail(FREDDY_E_ARG, "NULL argument");
   if (int rc = check_pq_shape(t->d, t->m, t->K, t->N)) return rc;
   if (t->C <= 0) return fail(FREDDY_E_ARG, "C must be positive");
+  // (coarse_dist_kernel, batches below 32 queries over vectors of more than 1024 dimensions: 16 queries of d floats in LDS)
+  if ((size_t)t->d * 16 * sizeof(float) > 160 * 1024) return fail(FREDDY_E_LIMIT, "d=%d exceeds the IVFADC search's limit of 2560 dimensions", t->d);
   if (t->list_off[0] != 0 || t->list_off[t->C] != t->N) return fail(FREDDY_E_ARG, "list_off must span [0, N]");
   for (int c = 0; c < t->C; ++c)   // every offset is checked BEFORE any row is touched through it
     if (t->list_off[c] < 0 || t->list_off[c] > t->list_off[c + 1] || (int64_t)t->list_off[c + 1] > t->N)

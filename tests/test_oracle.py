@@ -336,24 +336,25 @@ def test_multi_index_emits_cells_in_ascending_distance(oracle):
 # drivers
 # ---------------------------------------------------------------------------------------------
 def test_pq_search_drivers_against_python_model(oracle):
+    """m = 12 (300-d) and an odd shape, d = 35 / m = 7 / K = 16: what tests/test_gpu_shapes.py holds the kernels to."""
     N = 3000
-    t = util.pq_tables(N=N, K=64)
-    ot = oracle.pq_table(t["codebook"], t["ids"], t["codes"])
-    _, qs = util.queries_from_corpus(N, 3)
-    K = 64
-    for q in qs:
-        lut = oracle.lut(q, t["codebook"])
-        d = np.array([oracle.adc(lut, c, K) for c in t["codes"]], f32)
-        assert as_list(oracle.pq_search(ot, q, 5)) == py_stream(d, t["ids"], 5, 100.0)
-        sub = np.array([5, 17, 17, 900, 2999, 3000, 4000, -1], np.int32)
-        rows = np.unique(sub[(sub >= 1) & (sub <= N)]) - 1
-        assert as_list(oracle.pq_search_in(ot, q, 4, sub)) == py_stream(d[rows], t["ids"][rows], 4, 1000.0)
-    sub = np.arange(1, N + 1, 7).astype(np.int32)
-    a = oracle.pq_search_in_batch(ot, qs, 5, sub, use_target_lists=True)
-    b = oracle.pq_search_in_batch(ot, qs, 5, sub, use_target_lists=False)
-    assert np.array_equal(a, b)
-    for i, q in enumerate(qs):
-        assert np.array_equal(a[i], oracle.pq_search_in(ot, q, 5, sub))
+    for t, qs in ((util.pq_tables(N=N, K=64), util.queries_from_corpus(N, 3)[1]),
+                  (util.shape_pq_tables(35, 7, 16, N), util.shape_queries(N, 35, 3))):
+        ot = oracle.pq_table(t["codebook"], t["ids"], t["codes"])
+        K = t["codebook"].shape[1]
+        for q in qs:
+            lut = oracle.lut(q, t["codebook"])
+            d = np.array([oracle.adc(lut, c, K) for c in t["codes"]], f32)
+            assert as_list(oracle.pq_search(ot, q, 5)) == py_stream(d, t["ids"], 5, 100.0)
+            sub = np.array([5, 17, 17, 900, 2999, 3000, 4000, -1], np.int32)
+            rows = np.unique(sub[(sub >= 1) & (sub <= N)]) - 1
+            assert as_list(oracle.pq_search_in(ot, q, 4, sub)) == py_stream(d[rows], t["ids"][rows], 4, 1000.0)
+        sub = np.arange(1, N + 1, 7).astype(np.int32)
+        a = oracle.pq_search_in_batch(ot, qs, 5, sub, use_target_lists=True)
+        b = oracle.pq_search_in_batch(ot, qs, 5, sub, use_target_lists=False)
+        assert np.array_equal(a, b)
+        for i, q in enumerate(qs):
+            assert np.array_equal(a[i], oracle.pq_search_in(ot, q, 5, sub))
 
 
 def test_ivfadc_single_vs_python_model(oracle):
@@ -456,32 +457,32 @@ def test_emit_text_roundtrip(oracle):
 
 
 def test_exact_knn_oracle(oracle):
-    """cosine_similarity_bytea (core_functions.c:67-81) and ORDER BY ... DESC FETCH FIRST k."""
-    x = util.corpus(3000).numpy()
-    ids = np.arange(1, 3001, dtype=np.int32)
-    q = x[10]
-    sims = np.empty(3000, f32)
-    for r in range(3000):
-        acc = f32(0)
-        for a_, b_ in zip(q, x[r]):
-            acc = f32(acc + f32(a_ * b_))
-        sims[r] = acc
-        if r < 50:
-            assert oracle.cosine_similarity_bytea(q, x[r]).view(np.uint32) == acc.view(np.uint32)
-    for k in (1, 5, 64):
-        order = np.lexsort((ids, -sims.astype(np.float64)))[:k]
-        got = oracle.exact_knn(x, ids, q, k)
-        assert got["id"].tolist() == ids[order].tolist()
-        assert np.array_equal(got["dist"].view(np.uint32), sims[order].view(np.uint32))
-    sub = np.array([5, 11, 12, 9000, 11, -3], np.int32)
-    got = oracle.exact_knn(x, ids, q, 5, sub)
-    assert got["id"].tolist() == [11, 12, 5] or set(got["id"].tolist()) == {11, 12, 5}
-    assert len(got) == 3
-    # duplicated rows tie exactly: ascending id decides
-    x2 = np.concatenate([x[:20], x[5:6], x[5:6]])
-    ids2 = np.arange(1, 23, dtype=np.int32)
-    got = oracle.exact_knn(x2, ids2, x[5], 3)
-    assert got["id"].tolist() == [6, 21, 22]
+    """cosine_similarity_bytea (core_functions.c:67-81) and ORDER BY ... DESC FETCH FIRST k; 300-d and an odd width (35)."""
+    for x in (util.corpus(3000).numpy(), util.shape_corpus(3000, 35).numpy()):
+        ids = np.arange(1, 3001, dtype=np.int32)
+        q = x[10]
+        sims = np.empty(3000, f32)
+        for r in range(3000):
+            acc = f32(0)
+            for a_, b_ in zip(q, x[r]):
+                acc = f32(acc + f32(a_ * b_))
+            sims[r] = acc
+            if r < 50:
+                assert oracle.cosine_similarity_bytea(q, x[r]).view(np.uint32) == acc.view(np.uint32)
+        for k in (1, 5, 64):
+            order = np.lexsort((ids, -sims.astype(np.float64)))[:k]
+            got = oracle.exact_knn(x, ids, q, k)
+            assert got["id"].tolist() == ids[order].tolist()
+            assert np.array_equal(got["dist"].view(np.uint32), sims[order].view(np.uint32))
+        sub = np.array([5, 11, 12, 9000, 11, -3], np.int32)
+        got = oracle.exact_knn(x, ids, q, 5, sub)
+        assert got["id"].tolist() == [11, 12, 5] or set(got["id"].tolist()) == {11, 12, 5}
+        assert len(got) == 3
+        # duplicated rows tie exactly: ascending id decides
+        x2 = np.concatenate([x[:20], x[5:6], x[5:6]])
+        ids2 = np.arange(1, 23, dtype=np.int32)
+        got = oracle.exact_knn(x2, ids2, x[5], 3)
+        assert got["id"].tolist() == [6, 21, 22]
 
 
 def test_vec_ops_and_grouping_pq_oracle(oracle):
@@ -498,26 +499,27 @@ def test_vec_ops_and_grouping_pq_oracle(oracle):
     unit = np.array([f32(v / length) for v in raw], f32)
     assert np.array_equal(oracle.vec_normalize(raw).view(np.uint32), unit.view(np.uint32))
 
-    t = util.pq_tables(N=3000, K=64)
-    ot = oracle.pq_table(t["codebook"], t["ids"], t["codes"])
-    gvec = x[[10, 500, 2222]]
-    asked = [7, 7, 2999, 1, 5000, -2, 1500]
-    ids, grp = oracle.grouping_pq(ot, gvec, asked)
-    assert ids.tolist() == [1, 7, 1500, 2999]                      # table order, de-duplicated, unknown ids dropped
-    luts = [oracle.lut(g, t["codebook"]) for g in gvec]
-    K = t["codebook"].shape[1]
-    for i, g in zip(ids, grp):
-        best, md = -1, f32(100)
-        for gi, L in enumerate(luts):
-            acc = f32(0)
-            for j, code in enumerate(t["codes"][i - 1]):
-                acc = f32(acc + L[j * K + code])
-            if acc < md:
-                md, best = acc, gi
-        assert best == g
-    # a duplicated group vector: the FIRST of the equally near groups wins (strict <)
-    ids2, grp2 = oracle.grouping_pq(ot, np.stack([gvec[1], gvec[1], gvec[0]]), [501])
-    assert grp2.tolist() in ([0], [2]) and 1 not in grp2.tolist()
+    # m = 12 (300-d) and an odd m (d = 35, m = 7, K = 16: the last code dword of a packed row is half filled)
+    for t, x in ((util.pq_tables(N=3000, K=64), x), (util.shape_pq_tables(35, 7, 16, 3000), util.shape_corpus(3000, 35).numpy())):
+        ot = oracle.pq_table(t["codebook"], t["ids"], t["codes"])
+        gvec = x[[10, 500, 2222]]
+        asked = [7, 7, 2999, 1, 5000, -2, 1500]
+        ids, grp = oracle.grouping_pq(ot, gvec, asked)
+        assert ids.tolist() == [1, 7, 1500, 2999]                      # table order, de-duplicated, unknown ids dropped
+        luts = [oracle.lut(g, t["codebook"]) for g in gvec]
+        K = t["codebook"].shape[1]
+        for i, g in zip(ids, grp):
+            best, md = -1, f32(100)
+            for gi, L in enumerate(luts):
+                acc = f32(0)
+                for j, code in enumerate(t["codes"][i - 1]):
+                    acc = f32(acc + L[j * K + code])
+                if acc < md:
+                    md, best = acc, gi
+            assert best == g
+        # a duplicated group vector: the FIRST of the equally near groups wins (strict <)
+        ids2, grp2 = oracle.grouping_pq(ot, np.stack([gvec[1], gvec[1], gvec[0]]), [501])
+        assert grp2.tolist() in ([0], [2]) and 1 not in grp2.tolist()
 
 
 def test_encode_oracle(oracle):

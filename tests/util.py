@@ -32,6 +32,36 @@ def ivpq_tables(N=20000, m=30, K=32, k_coarse=8, seed=7):
     return ib.build_ivpq_index(x, m=m, K=K, k_coarse=k_coarse, train_size=min(N, 5000), iters=4, seed=seed)
 
 
+# ---- tables of other shapes (tests/test_gpu_shapes.py, the odd-shape cases of tests/test_oracle.py) ----
+@functools.lru_cache(maxsize=None)
+def shape_corpus(N, d, seed=0):
+    """N x d rows like corpus() in a latent space of min(10, d) dimensions, 1 % of them copies of other rows (ties)."""
+    torch.manual_seed(0)
+    return ib.make_corpus(N, d=d, seed=1000 + 7 * d + seed, n_clusters=120, latent=min(10, d), dup_frac=0.01, device="cpu")
+
+
+@functools.lru_cache(maxsize=None)
+def shape_pq_tables(d, m, K, N, seed=6):
+    return ib.build_pq_index(shape_corpus(N, d), m=m, K=K, train_size=min(N, 5000), iters=3, seed=seed)
+
+
+@functools.lru_cache(maxsize=None)
+def shape_ivf_tables(d, m, K, C, N, seed=5):
+    return ib.build_ivf_index(shape_corpus(N, d), C=C, m=m, K=K, train_size=min(N, 5000), iters=3, seed=seed)
+
+
+@functools.lru_cache(maxsize=None)
+def shape_ivpq_tables(d, m, K, k_coarse, N, seed=7):
+    return ib.build_ivpq_index(shape_corpus(N, d), m=m, K=K, k_coarse=k_coarse, train_size=min(N, 5000), iters=3, seed=seed)
+
+
+def shape_queries(N, d, Q, seed=7):
+    """Q rows of shape_corpus(N, d) as queries (float32 copies)."""
+    rng = np.random.default_rng(seed)
+    rows = np.sort(rng.choice(N, size=Q, replace=False))
+    return shape_corpus(N, d)[torch.from_numpy(rows)].numpy().astype(np.float32)
+
+
 def queries_from_corpus(N, Q, seed=7):
     rng = np.random.default_rng(seed)
     ids = np.sort(rng.choice(np.arange(1, N + 1), size=Q, replace=False)).astype(np.int32)
