@@ -209,6 +209,7 @@ struct freddy_gpu_index {
   // filter + refine path (refine.h); NULL unless the shape is the fused one and the table fits the budget
   float* cbR = nullptr;         // [m][K][S] row-major codebook for the exact stage
   float* rterm = nullptr;       // [blocks*64] sum_p (|c|^2 + 2 co_p . c) of every row
+  int64_t rterm_bytes = 0;      // its share of `bytes` (refresh_row_terms)
   float* pmax = nullptr;        // [m]        max |co_p| + max |c_p|, rounded up
   float* cmaxp = nullptr;       // [m]        max |c_p|, rounded up
   float* cbF = nullptr;         // [m][8 groups][7 steps][64 lanes][8] the codebook in the B-fragment order of the table kernel's matrix instructions (fused5.h query_codebook5_body)

@@ -284,9 +284,13 @@ static int derive_codebook_tables_into(freddy_gpu_index* ix, const float* codebo
 // rterm[slot] for every row slot of the pinned lists (the (cell, row) part of the filter's cheap distance)
 static int refresh_row_terms(freddy_gpu_index* ix) {
   if (ix->rterm) { (void)hipFree(ix->rterm); ix->rterm = nullptr; }
+  ix->bytes -= ix->rterm_bytes;   // (rebuilt after append_rows / update_codebook: the old array no longer counts)
+  ix->rterm_bytes = 0;
   if (!ix->cbR) return 0;
   const int64_t n_slots = std::max<int64_t>(ix->n_blocks, 1) * 64;
   if (hipMalloc((void**)&ix->rterm, sizeof(float) * (size_t)n_slots) != hipSuccess) return fail(FREDDY_E_NOMEM, "device allocation failed");
+  ix->rterm_bytes = (int64_t)sizeof(float) * n_slots;
+  ix->bytes += ix->rterm_bytes;
   if (ix->n_blocks > 0) {
     hipLaunchKernelGGL(row_term_kernel, dim3((unsigned)((ix->n_blocks * 64 + 255) / 256)), dim3(256), 0, ix->stream, ix->packed,
                        ix->blk_cell, ix->coarse, ix->cbR, ix->rterm, ix->n_blocks * 64, ix->M2, ix->d, ix->m, ix->K, ix->S);
@@ -452,10 +456,8 @@ extern "C" int freddy_gpu_pin_ivf(const freddy_ivf_desc* t, int device, freddy_g
   if (!rc) rc = pack_lists(ix, t->C, t->list_off, t->codes, t->ids);
   if (!rc) rc = build_packed8(ix);
   if (!rc) rc = refresh_row_terms(ix);   // one float per row slot: the (cell, row) part of the filter's cheap distance
-  if (!rc) {
-    if (ix->rterm) ix->bytes += (int64_t)sizeof(float) * std::max<int64_t>(ix->n_blocks, 1) * 64;
+  if (!rc)
     for (int64_t r = 0; r < t->N; ++r) ix->max_id = std::max(ix->max_id, t->ids[r]);
-  }
   if (rc) { free_index(ix); return rc; }
   *out = ix;
   return FREDDY_OK;
@@ -516,11 +518,13 @@ __global__ __launch_bounds__(256) void place_vectors_kernel(const float* __restr
 }
 
 template <class T>
-static int grow_device_array(T** arr, size_t old_n, size_t new_n, const T* append_host, size_t append_n) {
+static int grow_device_array(T** arr, size_t old_n, size_t new_n, const T* append_host, size_t append_n, int64_t* bytes) {
   T* fresh = nullptr;
   if (hipMalloc((void**)&fresh, sizeof(T) * std::max<size_t>(new_n, 1)) != hipSuccess) return -1;
   if (old_n && hipMemcpy(fresh, *arr, sizeof(T) * old_n, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(fresh); return -2; }
   if (append_n && hipMemcpy(fresh + old_n, append_host, sizeof(T) * append_n, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(fresh); return -2; }
+  // (the footprint as upload() counts it: an empty array is one element)
+  *bytes += (int64_t)(sizeof(T) * std::max<size_t>(new_n, 1)) - (*arr ? (int64_t)(sizeof(T) * std::max<size_t>(old_n, 1)) : 0);
   if (*arr) (void)hipFree(*arr);
   *arr = fresh;
   return 0;
@@ -590,6 +594,10 @@ static int append_packed_rows(freddy_gpu_index* ix, int n_lists, int64_t n, cons
   }
   void* old[] = {ix->packed, ix->pos, ix->blk_cell, ix->blk_off, ix->list_off};
   for (void* p : old) if (p) (void)hipFree(p);
+  {   // the footprint follows the block count (pack_lists counts packed, pos and blk_cell with one block at least; blk_off and list_off keep their size)
+    const int64_t ob = std::max<int64_t>(ix->n_blocks, 1), nb = std::max<int64_t>(n_new_blocks, 1);
+    ix->bytes += (nb - ob) * (int64_t)(sizeof(uint32_t) * M2 * 64 + sizeof(int32_t) * 64 + sizeof(int32_t));
+  }
   ix->packed = packed; ix->pos = pos; ix->blk_cell = d_blk_cell; ix->blk_off = d_new_blk; ix->list_off = d_list_off;
   ix->n_blocks = n_new_blocks;
   ix->max_list_blocks = max_blocks;
@@ -634,7 +642,7 @@ extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const i
       const int64_t old_n = ix->N;
       if (ix->pq_shadow) { free_index(ix->pq_shadow); ix->pq_shadow = nullptr; }   // (rebuilt by the next batch search)
       if (int rc = append_packed_rows(ix, 1, n, nullptr, row_pos.data(), codes)) return rc;
-      if (grow_device_array(&ix->ids, (size_t)old_n, (size_t)(old_n + n), ids, (size_t)n)) return fail(FREDDY_E_NOMEM, "device allocation failed");
+      if (grow_device_array(&ix->ids, (size_t)old_n, (size_t)(old_n + n), ids, (size_t)n, &ix->bytes)) return fail(FREDDY_E_NOMEM, "device allocation failed");
       ix->h_ids.insert(ix->h_ids.end(), ids, ids + n);
       ix->max_id = ids[n - 1];
       return FREDDY_OK;
@@ -654,9 +662,9 @@ extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const i
           if (codes[(size_t)i * j.m + l] < 0 || codes[(size_t)i * j.m + l] >= j.K) return fail(FREDDY_E_ARG, "code out of range at new row %lld", (long long)i);
       }
       const size_t o = (size_t)j.N, nn = (size_t)(j.N + n);
-      if (grow_device_array(&j.ids, o, nn, ids, (size_t)n) || grow_device_array(&j.cell, o, nn, coarse_id, (size_t)n) ||
-          grow_device_array(&j.codes, o * j.MP, nn * j.MP, join_pad_codes(codes, n, j.m, j.MP).data(), (size_t)n * j.MP) ||
-          (j.has_vectors && grow_device_array(&j.vectors, o * j.d, nn * j.d, vectors, (size_t)n * j.d)))
+      if (grow_device_array(&j.ids, o, nn, ids, (size_t)n, &ix->bytes) || grow_device_array(&j.cell, o, nn, coarse_id, (size_t)n, &ix->bytes) ||
+          grow_device_array(&j.codes, o * j.MP, nn * j.MP, join_pad_codes(codes, n, j.m, j.MP).data(), (size_t)n * j.MP, &ix->bytes) ||
+          (j.has_vectors && grow_device_array(&j.vectors, o * j.d, nn * j.d, vectors, (size_t)n * j.d, &ix->bytes)))
         return fail(FREDDY_E_NOMEM, "device allocation failed");
       if (j.markbits) (void)hipFree(j.markbits);
       j.markbits = nullptr;
@@ -676,7 +684,7 @@ extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const i
       HIP_TRY(hipMalloc((void**)&xb, sizeof(float) * (size_t)new_blocks * d * 64));
       HIP_TRY(hipMemset(xb, 0, sizeof(float) * (size_t)new_blocks * d * 64));
       if (ix->n_blocks) HIP_TRY(hipMemcpy(xb, ix->xb, sizeof(float) * (size_t)ix->n_blocks * d * 64, hipMemcpyDeviceToDevice));
-      if (grow_device_array(&ix->coarse, o * d, nn * d, vectors, (size_t)n * d) || grow_device_array(&ix->ids, o, nn, ids, (size_t)n)) {
+      if (grow_device_array(&ix->coarse, o * d, nn * d, vectors, (size_t)n * d, &ix->bytes) || grow_device_array(&ix->ids, o, nn, ids, (size_t)n, &ix->bytes)) {
         (void)hipFree(xb);
         return fail(FREDDY_E_NOMEM, "device allocation failed");
       }
@@ -684,6 +692,7 @@ extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const i
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipStreamSynchronize(ix->stream));
       if (ix->xb) (void)hipFree(ix->xb);
+      ix->bytes += (int64_t)sizeof(float) * d * 64 * (new_blocks - std::max<int64_t>(ix->n_blocks, 1));   // (pin_vectors counts one block at least)
       ix->xb = xb; ix->n_blocks = new_blocks; ix->N += n;
       ix->h_ids.insert(ix->h_ids.end(), ids, ids + n);
       return exf_table_stats(ix, (int64_t)o, n);   // (the filter's scale and norm bound cover the new rows)

@@ -185,6 +185,7 @@ class _Index:
         cd = None if codes is None else _i16(codes)
         v = None if vectors is None else _f32(vectors)
         _check(self.lib.freddy_gpu_append_rows(self.h, ids.size, _p(ids), _p(cid), _p(cd), _p(v)))
+        self.N += ids.size   # (grouping() sizes its output arrays by it)
 
     def update_codebook(self, codebook):
         cb = _f32(codebook)
