@@ -198,6 +198,22 @@ int freddy_gpu_exact_analogy(freddy_gpu_index_t* vecs, int32_t method, const int
  * the all-exact path (a candidate buffer overflowed or the pass's vectors were not finite).  NULL pointers are skipped. */
 int freddy_gpu_last_analogy_stats(const freddy_gpu_index_t* vecs, int64_t* filter_passes, int64_t* candidates, int64_t* redone_passes);
 
+/* ---- the exact kNN-join on the same handle (exact_join.h) -------------------------------------------------------------
+ * knn_search_in_batch (freddy--0.0.1.sql:456-501), the reference's default knn_join(): one knn_in_exact per query over the
+ * target set "id = ANY(target_ids)" (duplicates / unknown ids ignored).  For every input the lists are bit for bit those of
+ * freddy_gpu_exact_search(vecs, queries, Q, k, target_ids, n_targets, ...): ORDER BY cosine_similarity_bytea DESC, id ASC, the
+ * similarity bits of the binary32 chain, (-1, -inf) beyond the rows.  n_targets == 0 is the EMPTY set (every slot empty);
+ * target_ids == NULL with n_targets > 0 is FREDDY_E_ARG.  Any Q, k <= 4096; argument and limit errors are reported before any
+ * device work.  Filter + refine on the matrix cores over the target set, one gather and five launches per pass of >= 10 880 queries, when k <= 32, d % 4 == 0,
+ * 16 <= d <= 512, table and queries finite, option exact_filter != 0 and the set has >= 8000 known rows (exact_filter = 1: any
+ * size); the all-exact subset path otherwise, and for every single query whose candidate buffer overflowed. */
+int freddy_gpu_exact_join(freddy_gpu_index_t* vecs, const float* queries /*[Q][d]*/, int32_t Q, int32_t k,
+                          const int32_t* target_ids, int64_t n_targets, int32_t* out_ids /*[Q][k]*/, float* out_sim /*[Q][k]*/);
+/* What the last freddy_gpu_exact_join call on this handle did: queries the filter + refine path ran for (0: the all-exact path
+ * answered the call), the candidates it refined (summed over the queries it answered), and the queries answered again on the
+ * all-exact path because their candidate buffer overflowed.  NULL pointers are skipped. */
+int freddy_gpu_last_exact_join_stats(const freddy_gpu_index_t* vecs, int64_t* filter_queries, int64_t* candidates, int64_t* redone_queries);
+
 /* ---- next row: grouping_pq ---------------------------------------------------------
  * Body of grouping_pq (freddy.c:1176-1401): for every row of the PQ table (subset_ids == NULL) or of
  * "id IN (subset_ids)" the nearest of G group vectors by ADC distance -- one LUT per group from the PQ
@@ -350,9 +366,10 @@ int freddy_gpu_abi_version(void);
  *                byte per code by the kernel that keeps a whole work entry's slab in LDS; 2: one byte per code, the six-phase kernel;
  *                0: the int16 layout), "exact_filter" (exact brute-force kNN as f16-split MFMA filter + exact
  *                refine: -1 = tables of >= 8192 rows and k <= 32, 0 never -- and no fragment copy of a table pinned with it --,
- *                1 always)
+ *                1 always), "exact_join_tile" (queries per workgroup of the exact join's filter: 0 = 128 when Q > 64 and
+ *                d <= 320, else 64; 64 = never 128)
  *   self-checks (tests):  "check_brackets" (bit 0: the scan keeps and the merge refines EVERY probed row, bit 1: the cell
- *                selection refines every cell, bit 2: exact kNN refines every row -- each with its proven bracket compared with
+ *                selection refines every cell, bit 2: exact kNN and the exact join refine every row -- each with its proven bracket compared with
  *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines
  *                every row for every analogy, counted the same way), "join_host_traversal",
  *                "join_libm_margin_ppm" */

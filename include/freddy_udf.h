@@ -197,6 +197,30 @@ const char* freddy_get_analogy_in_function(const freddy_session_t* s);
 int analogy(freddy_session_t* s, int32_t a, int32_t b, int32_t c, int32_t* result);
 int analogy_in(freddy_session_t* s, int32_t w1, int32_t w2, int32_t w3, const int32_t* input_ids, int32_t n_ids, int32_t* result);
 
+/* The exact kNN-join and the grouping dispatcher, by row id (the device entry point freddy_gpu_exact_join).
+ * knn_search_in_batch(bytea[], int, varchar[])             freddy--0.0.1.sql:480-501
+ *   query_id = 1-based index of the query; rows query-major, rank-minor; fewer than k rows for a query when fewer targets
+ *   exist; row.distance carries the SIMILARITY.  out must hold n_queries * k rows.
+ * knn_search_in_batch(varchar[], int, varchar[])           freddy--0.0.1.sql:456-478
+ *   queries are rows of google_vecs_norm; query_id = the query's id; an unknown query id yields no rows (the INNER JOIN is
+ *   empty); duplicates are answered once each, in argument order.
+ * grouping_func(tokens, groups)                            freddy--0.0.1.sql:1462-1484
+ *   (token id, group id) for every token that is a row, table order: knn_in(token, 1, groups) with the default knn_in_exact --
+ *   ONE exact join, queries = the tokens' vectors, k = 1, targets = the groups (no rows when no group is a row: knn_in is empty).
+ * groups(tokens, groups)                                   freddy--0.0.1.sql:299-311
+ *   calls the function set_groups_function named (default grouping_func, :200): grouping_func | grouping_func_pq (= grouping_pq).
+ *   Any other name fails at call time: "function <name>(character varying[], character varying[]) does not exist". */
+int knn_search_in_batch(freddy_session_t* s, const float* queries, int32_t n_queries, int32_t dim, int32_t k,
+                        const int32_t* input_ids, int32_t n_ids, freddy_row3* out, int32_t* n_rows);
+int knn_search_in_batch_ids(freddy_session_t* s, const int32_t* query_ids, int32_t n_queries, int32_t k,
+                            const int32_t* input_ids, int32_t n_ids, freddy_row3* out, int32_t* n_rows);
+int grouping_func(freddy_session_t* s, const int32_t* token_ids, int32_t n_tokens, const int32_t* group_ids,
+                  int32_t n_groups, freddy_group_row* out, int32_t* n_rows);
+int freddy_set_groups_function(freddy_session_t* s, const char* name);       /* default "grouping_func" */
+const char* freddy_get_groups_function(const freddy_session_t* s);
+int groups(freddy_session_t* s, const int32_t* token_ids, int32_t n_tokens, const int32_t* group_ids, int32_t n_groups,
+           freddy_group_row* out, int32_t* n_rows);
+
 /* Next row: insert_batch(varchar[]) -> int4                  freddy.c:1403-1658
  * The tokenisation sub-query (:1503-1519: tokenize(term) for the terms NOT yet in the vocabulary) stays with SQL;
  * the caller passes its result, the normalised vectors of the new terms.  Per vector: PQ code, coarse cell +

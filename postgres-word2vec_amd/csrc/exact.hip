@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "exact.h"
 #include "exact2.h"
+#include "exact_join.h"
 #include "analogy.h"
 
 // ---------------------------------------------------------------------------------------
@@ -231,14 +232,10 @@ static int vec_subset(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const 
   return 0;
 }
 
-extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k,
-                                       const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_sim) {
-  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
-  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
-  if (Q < 0 || k <= 0 || n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad sizes");
-  if (Q > 0 && (!queries || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
-  if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
-  if (Q == 0) return FREDDY_OK;
+// Exact kNN of checked arguments (Q > 0) over all rows (sub_rows == NULL) or over the table rows *sub_rows (rows_of_ids' result;
+// the exact join hands over the rows it has resolved).
+static int exact_search_rows(freddy_gpu_index* ix, const float* queries, int32_t Q, int32_t k, const std::vector<int32_t>* sub_rows,
+                             int32_t* out_ids, float* out_sim) {
   HIP_TRY(hipSetDevice(ix->device));
   Workspace* ws = workspace_for(ix, ix->stream);
   hipStream_t s = ix->stream;
@@ -246,10 +243,10 @@ extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* quer
   const float* xb = ix->xb;
   const int32_t* pos = nullptr;
   int64_t n_rows = ix->N, n_blocks = ix->n_blocks;
-  if (subset_ids)   // (an empty subset: the scan below finds nothing)
-    if (int rc = vec_subset(ix, ws, s, rows_of_ids(ix->h_ids, subset_ids, n_subset), &xb, &pos, &n_rows, &n_blocks)) return rc;
+  if (sub_rows)   // (an empty subset: the scan below finds nothing)
+    if (int rc = vec_subset(ix, ws, s, *sub_rows, &xb, &pos, &n_rows, &n_blocks)) return rc;
   // Filter + refine (exact2.h): the whole table, k <= 32, finite rows of a supported shape; identical lists.
-  const bool want_filter = !subset_ids && ix->exf_ok && k <= 32 && ix->tune.exact_filter != 0 &&
+  const bool want_filter = !sub_rows && ix->exf_ok && k <= 32 && ix->tune.exact_filter != 0 &&
                            (ix->tune.exact_filter == 1 || n_rows >= 8192) && n_rows >= 1;
   if (want_filter) {
     // one block of mapped host memory: [lists][verdict words][the queries, when they are few]: the kernels read a handful of
@@ -335,6 +332,196 @@ extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* quer
   HIP_TRY(hipMemcpyAsync(out_ids, ws->w_out_ids.p, sizeof(int32_t) * (size_t)Q * k, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(out_sim, ws->w_out_dist.p, sizeof(float) * (size_t)Q * k, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  return FREDDY_OK;
+}
+
+extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k,
+                                       const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_sim) {
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (Q < 0 || k <= 0 || n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad sizes");
+  if (Q > 0 && (!queries || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
+  if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
+  if (Q == 0) return FREDDY_OK;
+  if (!subset_ids) return exact_search_rows(ix, queries, Q, k, nullptr, out_ids, out_sim);
+  const std::vector<int32_t> rows = rows_of_ids(ix->h_ids, subset_ids, n_subset);
+  return exact_search_rows(ix, queries, Q, k, &rows, out_ids, out_sim);
+}
+
+// ---- the exact kNN-join (exact_join.h) ---------------------------------------------------------------------------------
+// Target sets below this many rows take the all-exact subset path unless option exact_filter = 1 forces the filter: the smallest
+// set size of tools/exact_join_timing.py's sweep (profiles/exact_join_timing.txt: n_targets x Q, filter forced, against the parent
+// commit's subset path) at which filter + refine is not slower at any Q -- at 1 000 and 4 000 targets it loses at Q >= 1024.
+static constexpr int64_t EXJ_MIN_TARGETS = 8000;
+
+// Device memory the per-query buffers of one pass may take (the threshold sample and the candidate buffers): more queries than
+// fit are answered in passes over the same gathered copy (10 880 queries per pass for sets of 32 768 rows or more).
+// A pass is never smaller than 128 queries: under check_brackets bit 2 (tests), where a candidate buffer holds the whole set, a
+// pass over a large set takes 128 n_targets 8 bytes however that compares with this budget.
+static constexpr size_t EXJ_PASS_BYTES = (size_t)2 << 30;
+
+// Filter + refine over the target rows `rows` (table order, distinct) for all Q queries: one gather, then five launches per pass
+// of queries.  cnt_out[q] = candidates the filter found for query q (> cap: its list is not valid, the caller redoes it);
+// *qbad_out: a query was not finite (no list is valid, the passes stop).
+static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const std::vector<int32_t>& rows, const float* queries, int Q, int k,
+                             int32_t* out_ids, float* out_sim, std::vector<int32_t>& cnt_out, int* cap_out, bool* qbad_out) {
+  const int d = ix->d, T = (d + 15) / 16, V = pick_V(k);
+  const int64_t nT = (int64_t)rows.size(), strips = (nT + 31) / 32;
+  const bool all = (ix->tune.check_brackets & 4) != 0;
+  const FilterPlan fp = filter_plan(nT, all);
+  const int n_sample = fp.n_sample, cap = fp.cap;
+  *cap_out = cap;
+  *qbad_out = false;
+  // the query tile: 128 queries (NT = 4) when more than one 64-tile is needed and four tiles' fragments fit the LDS
+  int NT = Q <= 32 ? 1 : 2;
+  const size_t tile_lds = (size_t)T * 2 * 64 * 16;
+  if (Q > 64 && 4 * tile_lds <= AN_MAX_LDS && ix->tune.exact_join_tile != 64) NT = 4;
+  const int QT = 32 * NT;
+  const size_t per_query = sizeof(float) * (size_t)std::max(n_sample, 1) + sizeof(uint2) * (size_t)cap;
+  const int Qc = (int)std::min<int64_t>(Q, std::max<int64_t>(128, (int64_t)(EXJ_PASS_BYTES / per_query) / 128 * 128));   // queries per pass
+  const int QcPad = (Qc + QT - 1) / QT * QT;
+  // per-pass state in w_found: [QcPad] thr, qeps, qunscale, cand_cnt, then the refine kernel's two verdict words
+  if (ix->exf_small.ensure(4096) || ws->w_found.ensure(sizeof(float) * (4 * (size_t)QcPad + 2)) || ws->w_sub_rows.ensure(sizeof(int32_t) * (size_t)nT) ||
+      ws->w_resid.ensure((size_t)strips * T * 2 * 64 * 16) || ix->exf_qfrag.ensure((size_t)(QcPad / 32) * tile_lds) || ws->w_q.ensure(sizeof(float) * (size_t)Q * d) ||
+      ix->exf_sample.ensure(sizeof(float) * (size_t)QcPad * std::max(n_sample, 1)) || ix->exf_cand.ensure(sizeof(uint2) * (size_t)Qc * cap) ||
+      ws->w_out_ids.ensure(sizeof(int32_t) * (size_t)Qc * k) || ws->w_out_dist.ensure(sizeof(float) * (size_t)Qc * k))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  if (int rc = ensure_viol(ix)) return rc;
+  float* sm = ix->exf_small.as<float>();
+  int32_t* qbad = reinterpret_cast<int32_t*>(sm + 256);       // (exact kNN's words: one protocol, exf_dirty)
+  int32_t* arrived = reinterpret_cast<int32_t*>(sm + 257);
+  if (ix->exf_dirty) {
+    HIP_TRY(hipMemsetAsync(sm + 256, 0, 8, s));
+    HIP_TRY(hipMemsetAsync(ix->viol + 3, 0, 4, s));
+  }
+  ix->exf_dirty = true;
+  float* thr = ws->w_found.as<float>();
+  float* qeps = thr + QcPad; float* qunscale = qeps + QcPad;
+  int32_t* cand_cnt = reinterpret_cast<int32_t*>(qunscale + QcPad);
+  int32_t* flags = cand_cnt + QcPad;
+  const int32_t* map = ws->w_sub_rows.as<int32_t>();
+  h8v* xf = ws->w_resid.as<h8v>();
+  HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, rows.data(), sizeof(int32_t) * (size_t)nT, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(ws->w_q.p, queries, sizeof(float) * (size_t)Q * d, hipMemcpyHostToDevice, s));
+  const int64_t gthreads = strips * T * 64;
+  timed_launch(ix, s, "exact_join_gather", [&] {
+    hipLaunchKernelGGL(exj_gather_kernel, dim3((unsigned)((gthreads + 255) / 256)), dim3(256), 0, s, ix->coarse, map, nT, d, T, ix->exf_ex, xf);
+  });
+  HIP_TRY(hipGetLastError());
+  cnt_out.assign((size_t)Q, 0);
+  const size_t rlds = exf_refine_lds(d, V == 1 ? 1 : 2);
+  for (int q0 = 0; q0 < Q; q0 += Qc) {
+    const int nq = std::min(Qc, Q - q0), qtiles = (nq + QT - 1) / QT, Qpad = qtiles * QT;
+    const float* d_q = ws->w_q.as<float>() + (size_t)q0 * d;
+    HIP_TRY(hipMemsetAsync(flags, 0xFF, 8, s));   // (-1, -1: the pass's last refine workgroup overwrites both)
+    ExfPrepArgs pa;
+    pa.queries = d_q; pa.nq = nq; pa.d = d; pa.T = T; pa.xmax_norm = ix->exf_xnorm; pa.ex = ix->exf_ex; pa.eps_factor = exf_eps_factor(d);
+    pa.qfrag = ix->exf_qfrag.as<h8v>(); pa.qeps = qeps; pa.qunscale = qunscale; pa.qbad = qbad; pa.copy_out = nullptr;
+    timed_launch(ix, s, "exact_join_prep", [&] { hipLaunchKernelGGL(exf_prep_kernel, dim3((unsigned)Qpad), dim3(256), 0, s, pa); });
+    HIP_TRY(hipGetLastError());
+    ExjArgs fa;
+    fa.xf = xf; fa.map = map; fa.n_rows = n_sample; fa.strip_stride = fp.sample_stride; fa.T = T; fa.nq = nq; fa.qfrag = ix->exf_qfrag.as<h8v>();
+    fa.qunscale = qunscale; fa.sample_out = ix->exf_sample.as<float>(); fa.thr = thr; fa.cand_cnt = cand_cnt; fa.cand = ix->exf_cand.as<uint2>(); fa.cap = cap;
+    // strip chunks: a workgroup's 8 waves take 8 strips per step; with many query tiles every workgroup stays long enough (>= 64
+    // strips) to pay for its LDS image of the tile
+    auto launch = [&](auto sample, int64_t n_rows) {
+      constexpr bool SAMPLE = decltype(sample)::value;
+      const int64_t wg_steps = (n_rows + 255) / 256;
+      const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(wg_steps, std::max<int64_t>((int64_t)ix->n_cus * 2 / qtiles, (wg_steps + 7) / 8)));
+      const dim3 grid((unsigned)gx, (unsigned)qtiles);
+      switch (NT) {
+        case 1: hipLaunchKernelGGL((exj_filter_kernel<1, SAMPLE>), grid, dim3(EXF_WG), tile_lds, s, fa); break;
+        case 2: hipLaunchKernelGGL((exj_filter_kernel<2, SAMPLE>), grid, dim3(EXF_WG), 2 * tile_lds, s, fa); break;
+        default: hipLaunchKernelGGL((exj_filter_kernel<4, SAMPLE>), grid, dim3(EXF_WG), 4 * tile_lds, s, fa); break;
+      }
+    };
+    if (n_sample > 0) {
+      timed_launch(ix, s, "exact_join_sample", [&] { launch(std::true_type(), n_sample); });
+      HIP_TRY(hipGetLastError());
+    }
+    ExfThrArgs ta;
+    ta.sample = fa.sample_out; ta.n_sample = n_sample; ta.nq = nq; ta.k = k; ta.qeps = qeps; ta.qunscale = qunscale; ta.thr = thr; ta.refine_all = all ? 1 : 0; ta.cand_cnt = cand_cnt;
+    timed_launch(ix, s, "exact_join_threshold", [&] { hipLaunchKernelGGL(exf_threshold_kernel, dim3((unsigned)Qpad), dim3(64 * EXF_TW), 0, s, ta); });
+    HIP_TRY(hipGetLastError());
+    fa.n_rows = nT; fa.strip_stride = 1; fa.sample_out = nullptr;
+    timed_launch(ix, s, "exact_join_filter", [&] { launch(std::false_type(), nT); });
+    HIP_TRY(hipGetLastError());
+    ExfRefineArgs ra;
+    ra.rows = ix->coarse; ra.queries = d_q; ra.cand = fa.cand; ra.cand_cnt = cand_cnt; ra.qeps = qeps; ra.viol = ix->viol; ra.cap = cap; ra.d = d; ra.L = k;
+    ra.count_checked = all ? 1 : 0; ra.ids = ix->ids; ra.out_ids = ws->w_out_ids.as<int32_t>(); ra.out_sim = ws->w_out_dist.as<float>(); ra.k = k;
+    ra.arrived = arrived; ra.total_wgs = nq; ra.qbad = qbad; ra.flags_out = flags;
+    timed_launch(ix, s, "exact_join_refine", [&] {
+      if (V == 1) hipLaunchKernelGGL((exf_refine_kernel<1>), dim3((unsigned)nq), dim3(64 * EXF_TW), rlds, s, ra);
+      else hipLaunchKernelGGL((exf_refine_kernel<2>), dim3((unsigned)nq), dim3(64 * EXF_TW), rlds, s, ra);
+    });
+    HIP_TRY(hipGetLastError());
+    int32_t h_flags[2] = {-1, -1};
+    const size_t n_out = (size_t)nq * k;
+    HIP_TRY(hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cnt_out.data() + q0, cand_cnt, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_ids + (size_t)q0 * k, ws->w_out_ids.p, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_sim + (size_t)q0 * k, ws->w_out_dist.p, sizeof(float) * n_out, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_flags[0] == -1 || h_flags[1] == -1) return fail(FREDDY_E_HIP, "exact join: the verdict words did not arrive");
+    if (h_flags[1]) { *qbad_out = true; break; }   // (the refine kernel has cleared its device-side words)
+  }
+  ix->exf_dirty = false;
+  return 0;
+}
+
+extern "C" int freddy_gpu_exact_join(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k, const int32_t* target_ids,
+                                     int64_t n_targets, int32_t* out_ids, float* out_sim) {
+  // (the scalar arguments first: they are checked before the handle is looked at, so no device is needed to see these errors)
+  if (Q < 0 || k <= 0 || n_targets < 0) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, k=%d, n_targets=%lld)", Q, k, (long long)n_targets);
+  if (n_targets > 0 && !target_ids) return fail(FREDDY_E_ARG, "NULL target_ids with n_targets=%lld", (long long)n_targets);
+  if (Q > 0 && (!queries || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
+  if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  ix->exj_stats[0] = ix->exj_stats[1] = ix->exj_stats[2] = 0;
+  if (Q == 0) return FREDDY_OK;
+  // the target ids resolved once: the filter and every all-exact answer (fall-back, redo) share the rows
+  const std::vector<int32_t> rows = rows_of_ids(ix->h_ids, target_ids, n_targets);
+  const int64_t nT = (int64_t)rows.size();
+  const bool want_filter = ix->exf_ok && k <= 32 && ix->tune.exact_filter != 0 && (ix->tune.exact_filter == 1 || nT >= EXJ_MIN_TARGETS) && nT >= 1;
+  if (!want_filter) return exact_search_rows(ix, queries, Q, k, &rows, out_ids, out_sim);
+  HIP_TRY(hipSetDevice(ix->device));
+  Workspace* ws = workspace_for(ix, ix->stream);
+  std::vector<int32_t> cnt;
+  int cap = 0;
+  bool qbad = false;
+  if (int rc = exact_join_filter(ix, ws, ix->stream, rows, queries, Q, k, out_ids, out_sim, cnt, &cap, &qbad)) return rc;
+  // a query is not finite: every list all-exact.  (Found by the prep kernel, which reads every query anyway; a host-side scan
+  // would put Q d comparisons in front of every call for the sake of this one.)
+  if (qbad) return exact_search_rows(ix, queries, Q, k, &rows, out_ids, out_sim);
+  // the queries whose candidate buffer overflowed: answered again, all-exact, in one call
+  std::vector<int32_t> redo;
+  int64_t cands = 0;
+  for (int q = 0; q < Q; ++q) {
+    if (cnt[(size_t)q] > cap) redo.push_back(q);
+    else cands += cnt[(size_t)q];
+  }
+  ix->exj_stats[0] = Q; ix->exj_stats[1] = cands; ix->exj_stats[2] = (int64_t)redo.size();
+  if (!redo.empty()) {
+    const int d = ix->d, nr = (int)redo.size();
+    std::vector<float> rq((size_t)nr * d), rs((size_t)nr * k);
+    std::vector<int32_t> ri((size_t)nr * k);
+    for (int i = 0; i < nr; ++i) memcpy(&rq[(size_t)i * d], queries + (size_t)redo[(size_t)i] * d, sizeof(float) * d);
+    if (int rc = exact_search_rows(ix, rq.data(), nr, k, &rows, ri.data(), rs.data())) return rc;
+    for (int i = 0; i < nr; ++i) {
+      memcpy(out_ids + (size_t)redo[(size_t)i] * k, &ri[(size_t)i * k], sizeof(int32_t) * k);
+      memcpy(out_sim + (size_t)redo[(size_t)i] * k, &rs[(size_t)i * k], sizeof(float) * k);
+    }
+  }
+  return FREDDY_OK;
+}
+
+extern "C" int freddy_gpu_last_exact_join_stats(const freddy_gpu_index_t* ix, int64_t* filter_queries, int64_t* candidates, int64_t* redone_queries) {
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (filter_queries) *filter_queries = ix->exj_stats[0];
+  if (candidates) *candidates = ix->exj_stats[1];
+  if (redone_queries) *redone_queries = ix->exj_stats[2];
   return FREDDY_OK;
 }
 
@@ -544,6 +731,8 @@ extern "C" int freddy_gpu_last_analogy_stats(const freddy_gpu_index_t* ix, int64
 std::vector<LdsLimit> lds_limits_exact() {
   const int b = (int)AN_MAX_LDS;
   return {{&exf_filter_kernel<1, false>, b}, {&exf_filter_kernel<2, false>, b}, {&exf_filter_kernel<1, true>, b}, {&exf_filter_kernel<2, true>, b},
+          {&exj_filter_kernel<1, false>, b}, {&exj_filter_kernel<2, false>, b}, {&exj_filter_kernel<4, false>, b},
+          {&exj_filter_kernel<1, true>, b},  {&exj_filter_kernel<2, true>, b},  {&exj_filter_kernel<4, true>, b},
           {&an_filter_kernel<1, false>, b},  {&an_filter_kernel<3, false>, b},  {&an_filter_kernel<1, true>, b},  {&an_filter_kernel<3, true>, b},
           {&an_scan_kernel<1, 8>, b},        {&an_scan_kernel<3, 4>, b},
           // (the all-exact scan: more than 64 KiB from d = 513 on with tiles of 16 queries, from d = 1537 on with tiles of 8)

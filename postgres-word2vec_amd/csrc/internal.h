@@ -76,6 +76,7 @@ struct Tuning {
                                // (FilterArgs::tau_run): fewer survivors for the merge; 0 = every (item, chunk) cuts at its own threshold
   int codes_u8 = 1;            // FREDDY_GPU_CODES_U8: K <= 256: the integer-slab scans read one byte per code (packed8, 16 instead of 28 B per row) -- 1: the scan with the whole entry's slab in LDS (fused8.h), 2: the six-phase scan (fused5.h); 0 = the int16 layout
   int exact_filter = -1;       // FREDDY_GPU_EXACT_FILTER: exact kNN as MFMA filter + exact refine (exact2.h): -1 auto (tables of >= 8192 rows, k <= 32), 0 never, 1 always
+  int exact_join_tile = 0;     // option exact_join_tile: queries per workgroup of the exact join's filter (exact_join.h): 0 auto (128 when Q > 64 and d <= 320), 64
   // -- self-checks (tests): bit 0 = the scan keeps every row and the merge refines every row (every probed row's bracket is checked),
   //    bit 1 = the cell selection refines every cell, bit 2 = exact kNN refines every row
   int check_brackets = 0;
@@ -268,6 +269,8 @@ struct freddy_gpu_index {
   std::map<std::string, ProfRec> prof;
   // the last exact analogy call (freddy_gpu_last_analogy_stats): filter passes, candidates they refined, passes redone all-exact
   int64_t an_stats[3] = {0, 0, 0};
+  // the last exact join call (freddy_gpu_last_exact_join_stats): queries the filter answered for, candidates refined, queries redone all-exact
+  int64_t exj_stats[3] = {0, 0, 0};
 };
 
 template <class F>

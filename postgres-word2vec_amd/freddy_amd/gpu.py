@@ -28,7 +28,7 @@ EXPORTS = [
     "freddy_gpu_insert_quantize", "freddy_gpu_append_rows", "freddy_gpu_update_codebook", "freddy_gpu_kmeans",
     "freddy_gpu_host_alloc", "freddy_gpu_host_free", "freddy_gpu_pin_ivf_multi", "freddy_gpu_replica_count",
     "freddy_gpu_last_track_sized", "freddy_gpu_abi_version", "freddy_gpu_exact_analogy",
-    "freddy_gpu_last_analogy_stats",
+    "freddy_gpu_last_analogy_stats", "freddy_gpu_exact_join", "freddy_gpu_last_exact_join_stats",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 
@@ -63,11 +63,16 @@ class IVPQDesc(C.Structure):
 _lib = None
 
 
-def load():
-    """dlopen the library (once).  Raises if it has not been built."""
-    global _lib
+def load(path=None, optional=()):
+    """dlopen the library (once).  Raises if it has not been built.  path / optional: a tool that times a build of an earlier
+    commit beside this one loads that library instead, which may lack the entry points named in `optional` (calling one fails)."""
+    global _lib, LIB_PATH
     if _lib is not None:
+        if path and os.path.abspath(path) != os.path.abspath(LIB_PATH):
+            raise FreddyGpuError(f"{LIB_PATH} is already loaded: a process binds one library, {path} needs a process of its own")
         return _lib
+    if path:
+        LIB_PATH = path
     try:
         # torch wheels bundle their own libamdhip64.so (same SONAME as /opt/rocm's).  Two HIP
         # runtimes in one process fight over the device, so when torch is around let its copy
@@ -109,6 +114,11 @@ def load():
     lib.freddy_gpu_exact_analogy.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                              C.c_void_p, C.c_void_p]
     lib.freddy_gpu_last_analogy_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name, types in (("freddy_gpu_exact_join", [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_last_exact_join_stats", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
+        if name in optional and not hasattr(lib, name):
+            continue
+        getattr(lib, name).argtypes = types
     lib.freddy_gpu_pq_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.freddy_gpu_ivfadc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -312,6 +322,23 @@ class VectorIndex(_Index):
         v = [C.c_int64(0) for _ in range(3)]
         _check(self.lib.freddy_gpu_last_analogy_stats(self.h, *(C.byref(x) for x in v)))
         return {"filter_passes": v[0].value, "candidates": v[1].value, "redone_passes": v[2].value}
+
+    def join(self, queries, k, target_ids):
+        """The exact kNN-join (freddy_gpu_exact_join): (ids[Q,k], similarity[Q,k]) of every query over the rows whose id is in
+        target_ids -- bit for bit search(queries, k, subset_ids=target_ids); an empty target_ids is the empty set."""
+        qs = _f32(queries).reshape(-1, self.d)
+        Q = qs.shape[0]
+        out_i = np.empty((Q, k), np.int32)
+        out_s = np.empty((Q, k), np.float32)
+        t = _i32(target_ids).reshape(-1)
+        _check(self.lib.freddy_gpu_exact_join(self.h, _p(qs), Q, k, _p(t) if t.size else None, t.size, _p(out_i), _p(out_s)))
+        return out_i, out_s
+
+    def last_join_stats(self):
+        """The last join() call (freddy_gpu_last_exact_join_stats): queries the filter ran for, candidates refined, queries redone all-exact."""
+        v = [C.c_int64(0) for _ in range(3)]
+        _check(self.lib.freddy_gpu_last_exact_join_stats(self.h, *(C.byref(x) for x in v)))
+        return {"filter_queries": v[0].value, "candidates": v[1].value, "redone_queries": v[2].value}
 
     def bound_checked(self):
         """Rows the self-check has compared with their bracket (option check_brackets bits 2 / 3 refine every row)."""

@@ -40,6 +40,7 @@ def load():
         _lib.freddy_set_confidence_value.argtypes = [C.c_void_p, C.c_float]
         _lib.freddy_get_analogy_function.restype = C.c_char_p
         _lib.freddy_get_analogy_in_function.restype = C.c_char_p
+        _lib.freddy_get_groups_function.restype = C.c_char_p
     return _lib
 
 
@@ -206,6 +207,41 @@ class Session:
         n = C.c_int32(0)
         self._check(self.lib.grouping_pq(self.h, _p(ids), ids.size, _p(groups), groups.size, _p(out), C.byref(n)))
         return out[:n.value]
+
+    def knn_search_in_batch(self, queries, k, input_ids):
+        """freddy--0.0.1.sql:480-501, the exact kNN-join: rows (1-based query index, id, similarity)."""
+        qs, ids = _f32(queries), _i32(input_ids)
+        qs = qs.reshape(-1, qs.shape[-1]) if qs.size else qs.reshape(0, 0)
+        out = np.empty(max(qs.shape[0], 1) * k, ROW3)
+        n = C.c_int32(0)
+        self._check(self.lib.knn_search_in_batch(self.h, _p(qs), qs.shape[0], qs.shape[1], k, _p(ids), ids.size, _p(out), C.byref(n)))
+        return out[:n.value]
+
+    def knn_search_in_batch_ids(self, query_ids, k, input_ids):
+        """freddy--0.0.1.sql:456-478: the queries are rows of google_vecs_norm; rows (query id, id, similarity)."""
+        qid, ids = _i32(query_ids), _i32(input_ids)
+        out = np.empty(max(qid.size, 1) * k, ROW3)
+        n = C.c_int32(0)
+        self._check(self.lib.knn_search_in_batch_ids(self.h, _p(qid), qid.size, k, _p(ids), ids.size, _p(out), C.byref(n)))
+        return out[:n.value]
+
+    def _groups(self, fn, token_ids, group_ids):
+        toks, groups = _i32(token_ids), _i32(group_ids)
+        out = np.empty(max(toks.size, 1), GROUP_ROW)
+        n = C.c_int32(0)
+        self._check(fn(self.h, _p(toks), toks.size, _p(groups), groups.size, _p(out), C.byref(n)))
+        return out[:n.value]
+
+    def grouping_func(self, token_ids, group_ids):
+        """freddy--0.0.1.sql:1462-1484: rows (token id, group id), the exact nearest group of every token."""
+        return self._groups(self.lib.grouping_func, token_ids, group_ids)
+
+    def groups(self, token_ids, group_ids):
+        """freddy--0.0.1.sql:299-311: the function set_groups_function named."""
+        return self._groups(self.lib.groups, token_ids, group_ids)
+
+    def set_groups_function(self, name): self._check(self.lib.freddy_set_groups_function(self.h, str(name).encode()))
+    def get_groups_function_name(self): return self.lib.freddy_get_groups_function(self.h).decode()
 
     def analogy_3cosadd_pq(self, id1, id2, id3):
         r = C.c_int32(-1)

@@ -88,6 +88,8 @@ struct freddy_session {
   int32_t pq_max_id = 0, fine_max_id = 0, ivpq_max_id = 0;
   // set_analogy_function / set_analogy_in_function (freddy--0.0.1.sql:198-199)
   std::string analogy_fn = "analogy_3cosadd", analogy_in_fn = "analogy_3cosadd_in";
+  // set_groups_function (:200)
+  std::string groups_fn = "grouping_func";
 };
 
 extern "C" {
@@ -967,6 +969,81 @@ int analogy_in(freddy_session_t* s, int32_t w1, int32_t w2, int32_t w3, const in
   return fail(-1, "function %s(unknown, unknown, unknown, character varying[]) does not exist", f.c_str());
 }
 
+// ---- the exact kNN-join and the grouping dispatcher          freddy--0.0.1.sql:456-501, 1462-1484, 299-311 --------------
+// one freddy_gpu_exact_join over `queries`; rows of query i carry qids[i]
+static int exact_join_rows(freddy_session_t* s, const float* queries, const int32_t* qids, int32_t nq, int32_t k, const int32_t* input_ids,
+                           int32_t n_ids, freddy_row3* out, int32_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  if (k > 4096) return fail(-1, "k=%d exceeds this build's limit of 4096", k);   // (the device call's limit, before the table is pinned)
+  if (nq == 0) return 0;
+  if (int rc = ensure_vecs(s)) return rc;
+  std::vector<int32_t> ids((size_t)nq * k); std::vector<float> sim((size_t)nq * k);
+  if (int rc = freddy_gpu_exact_join(s->vecs, queries, nq, k, input_ids, n_ids, ids.data(), sim.data())) return gpu_fail(rc);
+  int32_t n = 0;
+  for (int32_t q = 0; q < nq; ++q)
+    for (int32_t r = 0; r < k && ids[(size_t)q * k + r] >= 0; ++r) out[n++] = {qids[q], ids[(size_t)q * k + r], sim[(size_t)q * k + r]};
+  if (n_rows) *n_rows = n;
+  return 0;
+}
+
+int knn_search_in_batch(freddy_session_t* s, const float* queries, int32_t n_queries, int32_t dim, int32_t k, const int32_t* input_ids,
+                        int32_t n_ids, freddy_row3* out, int32_t* n_rows) {
+  if (!s || s->norm_ids.empty()) return fail(-1, "google_vecs_norm is not loaded");
+  if (dim != s->d) return fail(-1, "query has %d dimensions, table has %d", dim, s->d);
+  if (k <= 0 || n_queries < 0 || n_ids < 0 || !out || (n_queries > 0 && !queries) || (n_ids > 0 && !input_ids)) return fail(-1, "bad argument");
+  std::vector<int32_t> qids((size_t)n_queries);
+  std::iota(qids.begin(), qids.end(), 1);
+  return exact_join_rows(s, queries, qids.data(), n_queries, k, input_ids, n_ids, out, n_rows);
+}
+
+int knn_search_in_batch_ids(freddy_session_t* s, const int32_t* query_ids, int32_t n_queries, int32_t k, const int32_t* input_ids,
+                            int32_t n_ids, freddy_row3* out, int32_t* n_rows) {
+  if (!s || s->norm_ids.empty()) return fail(-1, "google_vecs_norm is not loaded");
+  if (k <= 0 || n_queries < 0 || n_ids < 0 || !out || (n_queries > 0 && !query_ids) || (n_ids > 0 && !input_ids)) return fail(-1, "bad argument");
+  std::vector<int32_t> qids;
+  std::vector<float> qv;
+  for (int32_t i = 0; i < n_queries; ++i)
+    if (const float* v = norm_vec_of(s, query_ids[i])) { qids.push_back(query_ids[i]); qv.insert(qv.end(), v, v + s->d); }
+  return exact_join_rows(s, qv.data(), qids.data(), (int32_t)qids.size(), k, input_ids, n_ids, out, n_rows);
+}
+
+int grouping_func(freddy_session_t* s, const int32_t* token_ids, int32_t n_tokens, const int32_t* group_ids, int32_t n_groups,
+                  freddy_group_row* out, int32_t* n_rows) {
+  if (!s || s->norm_ids.empty()) return fail(-1, "google_vecs_norm is not loaded");
+  if (n_tokens < 0 || n_groups < 0 || !out || (n_tokens > 0 && !token_ids) || (n_groups > 0 && !group_ids)) return fail(-1, "bad argument");
+  // "FROM google_vecs_norm AS v1 ... WHERE v1.word = ANY(tokens)": every token that is a row, once, in table order
+  std::vector<int32_t> toks(token_ids, token_ids + n_tokens);
+  std::sort(toks.begin(), toks.end());
+  toks.erase(std::unique(toks.begin(), toks.end()), toks.end());
+  std::vector<int32_t> qids;
+  std::vector<float> qv;
+  for (int32_t id : toks)
+    if (const float* v = norm_vec_of(s, id)) { qids.push_back(id); qv.insert(qv.end(), v, v + s->d); }
+  std::vector<freddy_row3> rows(qids.size());
+  int32_t n = 0;
+  if (int rc = exact_join_rows(s, qv.data(), qids.data(), (int32_t)qids.size(), 1, group_ids, n_groups, rows.data(), &n)) return rc;
+  for (int32_t i = 0; i < n; ++i) out[i] = {rows[(size_t)i].query_id, rows[(size_t)i].id};
+  if (n_rows) *n_rows = n;
+  return 0;
+}
+
+int freddy_set_groups_function(freddy_session_t* s, const char* name) {
+  if (!s || !name) return fail(-1, "bad argument");
+  s->groups_fn = name;
+  return 0;
+}
+const char* freddy_get_groups_function(const freddy_session_t* s) { return s ? s->groups_fn.c_str() : ""; }
+
+// EXECUTE format('SELECT * FROM %s(''%s''::varchar(100)[], ''%s''::varchar(100)[])', get_groups_function_name(), ...)
+int groups(freddy_session_t* s, const int32_t* token_ids, int32_t n_tokens, const int32_t* group_ids, int32_t n_groups,
+           freddy_group_row* out, int32_t* n_rows) {
+  if (!s) return fail(-1, "bad argument");
+  const std::string& f = s->groups_fn;
+  if (f == "grouping_func") return grouping_func(s, token_ids, n_tokens, group_ids, n_groups, out, n_rows);
+  if (f == "grouping_func_pq") return grouping_pq(s, token_ids, n_tokens, group_ids, n_groups, out, n_rows);
+  return fail(-1, "function %s(character varying[], character varying[]) does not exist", f.c_str());
+}
+
 // ---- cluster_exact / cluster_pq / cluster_ivpq = generic_cluster      freddy--0.0.1.sql:1086-1209 --------------
 namespace {
 struct SimRow { float sim; int qid; int tid; };
@@ -980,7 +1057,7 @@ static int cluster_knn(freddy_session_t* s, int method, const std::vector<float>
   std::vector<int32_t> ids((size_t)kc * n); std::vector<float> val((size_t)kc * n);
   if (method == 0) {          // knn_in_exact per centroid: cosine_similarity_bytea DESC (freddy--0.0.1.sql:456-476, 1041-1054)
     if (int rc = ensure_vecs(s)) return rc;
-    if (int rc = freddy_gpu_exact_search(s->vecs, centroids.data(), kc, n, token_ids, n, ids.data(), val.data())) return gpu_fail(rc);
+    if (int rc = freddy_gpu_exact_join(s->vecs, centroids.data(), kc, n, token_ids, n, ids.data(), val.data())) return gpu_fail(rc);
   } else if (method == 1) {   // pq_search_in_batch (:880-902)
     if (!s->pq) return fail(-1, "pq_quantization / pq_codebook are not loaded");
     if (int rc = freddy_gpu_pq_search(s->pq, centroids.data(), kc, n, 1000.0f, token_ids, n, ids.data(), val.data())) return gpu_fail(rc);
