@@ -34,7 +34,7 @@ extern "C" {
 #define FREDDY_E_NOMEM (-3)    /* host or device allocation failed */
 #define FREDDY_E_KIND (-4)     /* index handle of the wrong kind for this call */
 #define FREDDY_E_LIMIT (-5)    /* parameter beyond what this build supports (see message): k > 4096, W > 512 probes per round,
-                                * k * pvf > 8192 (or k > 512) in the kNN-join, K > 32767, d > 1024 for training */
+                                * k * pvf > 8192 (or k > 512) in the kNN-join, k * pvf > 4096 in the post verification, K > 32767, d > 1024 for training */
 
 /* found_rule for freddy_gpu_ivfadc_search */
 #define FREDDY_FOUND_ROWS 0      /* ivfadc_search:       found += rows retrieved  (freddy.c:377) */
@@ -213,6 +213,31 @@ int freddy_gpu_exact_join(freddy_gpu_index_t* vecs, const float* queries /*[Q][d
  * answered the call), the candidates it refined (summed over the queries it answered), and the queries answered again on the
  * all-exact path because their candidate buffer overflowed.  NULL pointers are skipped. */
 int freddy_gpu_last_exact_join_stats(const freddy_gpu_index_t* vecs, int64_t* filter_queries, int64_t* candidates, int64_t* redone_queries);
+
+/* ---- batched post verification: the ANN handles and the raw-vector handle in one call (pv.h) ----------------------------
+ * k_nearest_neighbour_ivfadc_pv / k_nearest_neighbour_pq_pv (freddy--0.0.1.sql:556-662) for Q queries: fetch k * pvf candidates
+ * with the approximate search, re-rank them by cosine_similarity_bytea against the raw vectors, keep the first k.
+ * Contract: for every query q let L be the list freddy_gpu_ivfadc_search (freddy_gpu_pq_search) returns for the same arguments with
+ * k * pvf in place of k -- stage one IS that entry point: every path, every probing round, the passes of k * pvf > 512.  The
+ * output row is bit for bit that of freddy_gpu_exact_search(vecs, q, 1, k, the ids of L that are >= 0, ...): ORDER BY similarity
+ * DESC, id ASC (non-finite values as that call orders them: the same key); the similarity bits of the binary32 chain
+ * "scalar += v1[i] * v2[i]", i ascending, no contraction; (-1, -inf) in the slots beyond the rows.  The (-1, sentinel) fillers of L
+ * are dropped; a candidate id with no row in vecs is dropped; an empty candidate set gives a row of (-1, -inf), never a search of
+ * the whole table.  Candidate vectors never travel to the host: ids are resolved to rows, similarities computed and the k best
+ * selected on the device (kernel pv_rerank: one workgroup per query, one lane per candidate); the host receives [Q][k] only.
+ * Errors, all before any device work: FREDDY_E_ARG for bad sizes (k < 1, pvf < 1, Q < 0, W < 1, n_subset < 0) and NULL buffers;
+ * FREDDY_E_LIMIT for k * pvf > 4096 (the message names the product); FREDDY_E_KIND for handles of the wrong kinds; FREDDY_E_ARG
+ * for vecs on another device or of another d, and for an ivf handle with replicas (freddy_gpu_replica_count > 1; the message
+ * says so).  Q == 0 succeeds and does nothing.  Any Q (passes of queries whose lists hold at most 8 M entries). */
+int freddy_gpu_ivfadc_search_pv(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const float* queries, int32_t Q, int32_t k,
+                                int32_t pvf, int32_t W, float sentinel, int32_t found_rule, int32_t* out_ids /*[Q][k]*/,
+                                float* out_sim /*[Q][k]*/);
+int freddy_gpu_pq_search_pv(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const float* queries, int32_t Q, int32_t k,
+                            int32_t pvf, float sentinel, const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids,
+                            float* out_sim);
+/* The last post-verification call on this pq / ivf handle: list entries with id >= 0, summed over the queries, and how many of
+ * them had a vector row (were scored).  NULL pointers are skipped. */
+int freddy_gpu_last_pv_stats(const freddy_gpu_index_t* ann, int64_t* candidates, int64_t* scored);
 
 /* ---- next row: grouping_pq ---------------------------------------------------------
  * Body of grouping_pq (freddy.c:1176-1401): for every row of the PQ table (subset_ids == NULL) or of

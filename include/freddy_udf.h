@@ -158,6 +158,24 @@ int knn_in_pq(freddy_session_t* s, const float* query, int32_t dim, int32_t k, c
 int k_nearest_neighbour_ivfadc_batch(freddy_session_t* s, const int32_t* query_ids, int32_t n_query_ids, int32_t k,
                                      freddy_row3* out, int32_t* n_rows);
 
+/* The batch form of the two post-verification functions, by query ids, and the reference's knn_batch() dispatcher.
+ * k_nearest_neighbour_ivfadc_pv_batch / k_nearest_neighbour_pq_pv_batch (varchar[], int)
+ *   queries = the rows of google_vecs_norm whose id is in query_ids, in table order, duplicates and unknown ids dropped (as
+ *   ivfadc_batch_search chooses its queries); for each the rows of k_nearest_neighbour_ivfadc_pv (_pq_pv) for that vector with
+ *   get_pvf() / get_w(), as (query_id, id, similarity), query-major; fewer than k rows for a query when fewer of its candidates
+ *   have vectors.  ONE device call (freddy_gpu_ivfadc_search_pv / freddy_gpu_pq_search_pv): candidates are re-ranked on the device.
+ *   get_pvf() * k > 4096 fails as the single-query functions do.  out must hold n_query_ids * k rows.
+ * knn_batch(query_set, k)                                  freddy--0.0.1.sql:92-98, 197, 232-246
+ *   calls the function set_knn_batch_function named (default k_nearest_neighbour_ivfadc_batch): that one or one of the two above.
+ *   Any other name fails at call time: "function <name>(character varying[], integer) does not exist". */
+int k_nearest_neighbour_ivfadc_pv_batch(freddy_session_t* s, const int32_t* query_ids, int32_t n_query_ids, int32_t k,
+                                        freddy_row3* out, int32_t* n_rows);
+int k_nearest_neighbour_pq_pv_batch(freddy_session_t* s, const int32_t* query_ids, int32_t n_query_ids, int32_t k,
+                                    freddy_row3* out, int32_t* n_rows);
+int freddy_set_knn_batch_function(freddy_session_t* s, const char* name);    /* default "k_nearest_neighbour_ivfadc_batch" */
+const char* freddy_get_knn_batch_function(const freddy_session_t* s);
+int knn_batch(freddy_session_t* s, const int32_t* query_ids, int32_t n_query_ids, int32_t k, freddy_row3* out, int32_t* n_rows);
+
 /* Next row (remainder): analogy over an input set and the clustering functions, by row id.
  * analogy_3cosadd_in_pq / analogy_3cosadd_in_ivpq                        freddy--0.0.1.sql:1348-1426
  *   as analogy_3cosadd_pq, candidates from pq_search_in(q, get_pvf() + 3, input ids) resp.

@@ -95,6 +95,7 @@ void free_index(freddy_gpu_index* ix) {
   for (Workspace& w : ix->ws) w.release();
   for (DevBuf* b : {&ix->exf_qfrag, &ix->exf_small, &ix->exf_sample, &ix->exf_cand, &ix->exf_xf}) b->release();
   ix->hio_in.release(); ix->hio_out.release();
+  ix->pv_io.release(); ix->pv_q.release();
   for (Lane& l : ix->lanes) {
     if (l.stream && l.stream != ix->stream) (void)hipStreamDestroy(l.stream);
     for (LaneSlot& c : l.slot) {

@@ -1,5 +1,5 @@
-// exact.hip -- pin_vectors, exact brute-force kNN (core_functions.c:67-81, freddy--0.0.1.sql:426-454) and the
-// exact analogies on the same handle (freddy--0.0.1.sql:1231-1315; analogy.h).
+// exact.hip -- pin_vectors, exact brute-force kNN (core_functions.c:67-81, freddy--0.0.1.sql:426-454), the
+// exact analogies on the same handle (freddy--0.0.1.sql:1231-1315; analogy.h) and the post verification of pq / ivf lists against it (pv.h).
 #include "internal.h"
 
 #include "kernels.h"
@@ -7,6 +7,7 @@
 #include "exact2.h"
 #include "exact_join.h"
 #include "analogy.h"
+#include "pv.h"
 
 // ---------------------------------------------------------------------------------------
 // exact brute-force kNN
@@ -727,6 +728,92 @@ extern "C" int freddy_gpu_last_analogy_stats(const freddy_gpu_index_t* ix, int64
   return FREDDY_OK;
 }
 
+// ---- post verification of pq / ivf result lists (pv.h) -------------------------------------------------------------------
+// Everything both entry points refuse, in the order of the header's table; nothing here touches a device.
+static int pv_check(const freddy_gpu_index* ann, int kind, const freddy_gpu_index* vecs, const float* queries, int32_t Q, int32_t k, int32_t pvf,
+                    const int32_t* out_ids, const float* out_sim) {
+  if (Q < 0 || k < 1 || pvf < 1) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, k=%d, pvf=%d)", Q, k, pvf);
+  if (Q > 0 && (!queries || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
+  if ((int64_t)k * pvf > PV_MAX_CAND) return fail(FREDDY_E_LIMIT, "k * pvf = %lld exceeds this build's limit of %d candidates", (long long)k * pvf, PV_MAX_CAND);
+  if (!ann || !vecs) return fail(FREDDY_E_ARG, "NULL index");
+  if (ann->kind != kind || vecs->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (!ann->replicas.empty())
+    return fail(FREDDY_E_ARG, "post verification does not take a handle with replicas (%d devices): the vectors are pinned on one device", 1 + (int)ann->replicas.size());
+  if (vecs->device != ann->device) return fail(FREDDY_E_ARG, "the vectors are pinned on device %d, the index on device %d", vecs->device, ann->device);
+  if (vecs->d != ann->d) return fail(FREDDY_E_ARG, "the vectors have %d dimensions, the index has %d", vecs->d, ann->d);
+  return 0;
+}
+
+// Stage one (`search`: the public entry point at k * pvf, writing its lists into the pinned block) and stage two (pv_rerank) for
+// passes of queries that bound the pinned block; the kernel reads the lists where stage one left them and writes the result lists
+// and the counts beside them, one synchronisation per pass.
+template <class F>
+static int pv_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const float* queries, int32_t Q, int32_t k, int32_t pvf, int32_t* out_ids,
+                     float* out_sim, F&& search) {
+  ann->pv_stats[0] = ann->pv_stats[1] = 0;
+  if (Q == 0) return FREDDY_OK;
+  const int kc = k * pvf, P = pv_pad(kc), NW = P == 64 ? 1 : 4, d = ann->d;
+  const int Qc = (int)std::min<int64_t>(Q, std::max<int64_t>(1, ((int64_t)8 << 20) / kc));   // queries per pass: lists of at most 8 M entries
+  HIP_TRY(hipSetDevice(ann->device));
+  const size_t n_list = (size_t)Qc * kc, n_out = (size_t)Qc * k;
+  if (ann->pv_io.ensure(4 * (2 * n_list + 2 * n_out + 2 * (size_t)Qc)) || ann->pv_q.ensure(sizeof(float) * (size_t)Qc * d))
+    return fail(FREDDY_E_NOMEM, "post verification: staging allocation failed");
+  int32_t* const l_ids = ann->pv_io.as<int32_t>();
+  float* const l_dist = reinterpret_cast<float*>(l_ids + n_list);
+  int32_t* const o_ids = l_ids + 2 * n_list;
+  float* const o_sim = reinterpret_cast<float*>(o_ids + n_out);
+  int32_t* const o_cnt = o_ids + 2 * n_out;
+  hipStream_t s = ann->stream;
+  for (int q0 = 0; q0 < Q; q0 += Qc) {
+    const int nq = std::min(Qc, Q - q0);
+    const float* qp = queries + (size_t)q0 * d;
+    if (int rc = search(qp, nq, kc, l_ids, l_dist)) return rc;
+    HIP_TRY(hipSetDevice(ann->device));
+    HIP_TRY(hipMemcpyAsync(ann->pv_q.p, qp, sizeof(float) * (size_t)nq * d, hipMemcpyHostToDevice, s));
+    PvArgs pa;
+    pa.cand = l_ids; pa.vec_ids = vecs->ids; pa.rows = vecs->coarse; pa.queries = ann->pv_q.as<float>(); pa.out_ids = o_ids; pa.out_sim = o_sim;
+    pa.counts = o_cnt; pa.N = vecs->N; pa.n_cand = kc; pa.k = k; pa.d = d; pa.P = P;
+    timed_launch(ann, s, "pv_rerank", [&] {
+      if (NW == 1) hipLaunchKernelGGL((pv_rerank_kernel<1>), dim3((unsigned)nq), dim3(64), pv_lds_bytes(1, P, d), s, pa);
+      else hipLaunchKernelGGL((pv_rerank_kernel<4>), dim3((unsigned)nq), dim3(256), pv_lds_bytes(4, P, d), s, pa);
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(out_ids + (size_t)q0 * k, o_ids, sizeof(int32_t) * (size_t)nq * k);
+    memcpy(out_sim + (size_t)q0 * k, o_sim, sizeof(float) * (size_t)nq * k);
+    for (int q = 0; q < nq; ++q) { ann->pv_stats[0] += o_cnt[2 * q]; ann->pv_stats[1] += o_cnt[2 * q + 1]; }
+  }
+  return FREDDY_OK;
+}
+
+extern "C" int freddy_gpu_ivfadc_search_pv(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const float* queries, int32_t Q, int32_t k, int32_t pvf,
+                                           int32_t W, float sentinel, int32_t found_rule, int32_t* out_ids, float* out_sim) {
+  if (int rc = pv_check(ivf, KIND_IVF, vecs, queries, Q, k, pvf, out_ids, out_sim)) return rc;
+  if (W <= 0) return fail(FREDDY_E_ARG, "W must be positive");
+  if (found_rule < 0 || found_rule > 2 || (found_rule == FREDDY_FOUND_BATCH_UDF && W != 1))
+    return fail(FREDDY_E_ARG, "bad found_rule (FREDDY_FOUND_BATCH_UDF needs W == 1)");
+  return pv_search(ivf, vecs, queries, Q, k, pvf, out_ids, out_sim, [&](const float* qp, int nq, int kc, int32_t* l_ids, float* l_dist) {
+    return freddy_gpu_ivfadc_search(ivf, qp, nq, kc, W, sentinel, found_rule, l_ids, l_dist);
+  });
+}
+
+extern "C" int freddy_gpu_pq_search_pv(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const float* queries, int32_t Q, int32_t k, int32_t pvf,
+                                       float sentinel, const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_sim) {
+  if (n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad subset (n_subset=%lld)", (long long)n_subset);
+  if (int rc = pv_check(pq, KIND_PQ, vecs, queries, Q, k, pvf, out_ids, out_sim)) return rc;
+  return pv_search(pq, vecs, queries, Q, k, pvf, out_ids, out_sim, [&](const float* qp, int nq, int kc, int32_t* l_ids, float* l_dist) {
+    return freddy_gpu_pq_search(pq, qp, nq, kc, sentinel, subset_ids, n_subset, l_ids, l_dist);
+  });
+}
+
+extern "C" int freddy_gpu_last_pv_stats(const freddy_gpu_index_t* ann, int64_t* candidates, int64_t* scored) {
+  if (!ann) return fail(FREDDY_E_ARG, "NULL index");
+  if (ann->kind != KIND_PQ && ann->kind != KIND_IVF) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (candidates) *candidates = ann->pv_stats[0];
+  if (scored) *scored = ann->pv_stats[1];
+  return FREDDY_OK;
+}
+
 // The kernels of this unit that want more than the default 64 KiB of dynamic LDS.
 std::vector<LdsLimit> lds_limits_exact() {
   const int b = (int)AN_MAX_LDS;
@@ -738,5 +825,7 @@ std::vector<LdsLimit> lds_limits_exact() {
           // (the all-exact scan: more than 64 KiB from d = 513 on with tiles of 16 queries, from d = 1537 on with tiles of 8)
           &exact_scan_kernel<1, 16>, &exact_scan_kernel<2, 16>, &exact_scan_kernel<4, 16>,
           &exact_scan_kernel<1, 8>, &exact_scan_kernel<2, 8>, &exact_scan_kernel<4, 8>, &exact_scan_kernel<8, 8>, &exact_scan_kernel<16, 8>,
-          &exact_scan_kernel<16, 8, true>};
+          &exact_scan_kernel<16, 8, true>,
+          // (4096 keys + four tiles + the query: 66 KiB at d = 300, 83 KiB at EX_MAX_D; the kernel has static LDS beside the dynamic)
+          {&pv_rerank_kernel<4>, (int)pv_lds_bytes(4, PV_MAX_CAND, EX_MAX_D)}};
 }

@@ -6,7 +6,7 @@
 //   pq.hip      pq_search (+ subsets, pseudo-list batches, one-query launch), grouping_pq
 //   join.hip    pin_ivpq, knn_join (join.h: overview; join_kernels.h and join_traverse.h the kernels, join_host.h the host heap, join_run.h the run
 //               record of a call and its stages)
-//   exact.hip   pin_vectors, exact kNN
+//   exact.hip   pin_vectors, exact kNN, the exact join, analogies, post verification of pq / ivf lists (pv.h)
 //   build.hip   encode, insert_quantize, k-means
 // Kernel headers are included by the unit that launches them (kernels shared by two units are static or templates).
 #pragma once
@@ -271,6 +271,11 @@ struct freddy_gpu_index {
   int64_t an_stats[3] = {0, 0, 0};
   // the last exact join call (freddy_gpu_last_exact_join_stats): queries the filter answered for, candidates refined, queries redone all-exact
   int64_t exj_stats[3] = {0, 0, 0};
+  // post verification on a pq / ivf handle (pv.h): pinned block [stage one's lists][the re-ranked lists][per-query counts] of one pass of
+  // queries, the device copy of the queries, and the last call's counts (freddy_gpu_last_pv_stats): candidates, candidates with a row
+  PinnedBuf pv_io;
+  DevBuf pv_q;
+  int64_t pv_stats[2] = {0, 0};
 };
 
 template <class F>

@@ -29,6 +29,7 @@ EXPORTS = [
     "freddy_gpu_host_alloc", "freddy_gpu_host_free", "freddy_gpu_pin_ivf_multi", "freddy_gpu_replica_count",
     "freddy_gpu_last_track_sized", "freddy_gpu_abi_version", "freddy_gpu_exact_analogy",
     "freddy_gpu_last_analogy_stats", "freddy_gpu_exact_join", "freddy_gpu_last_exact_join_stats",
+    "freddy_gpu_ivfadc_search_pv", "freddy_gpu_pq_search_pv", "freddy_gpu_last_pv_stats",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 
@@ -115,7 +116,12 @@ def load(path=None, optional=()):
                                              C.c_void_p, C.c_void_p]
     lib.freddy_gpu_last_analogy_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name, types in (("freddy_gpu_exact_join", [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_last_exact_join_stats", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
+                        ("freddy_gpu_last_exact_join_stats", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_ivfadc_search_pv", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                                         C.c_int32, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_pq_search_pv", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                                     C.c_int64, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_last_pv_stats", [C.c_void_p, C.c_void_p, C.c_void_p])):
         if name in optional and not hasattr(lib, name):
             continue
         getattr(lib, name).argtypes = types
@@ -222,6 +228,13 @@ class _Index:
             _check(n)
         return {names[i].value.decode(): (int(launches[i]), float(ms[i])) for i in range(min(n, cap))}
 
+    def last_pv_stats(self):
+        """The last search_pv() call on this pq / ivf handle (freddy_gpu_last_pv_stats): list entries with id >= 0 summed over the
+        queries, and how many of them had a vector row."""
+        v = [C.c_int64(0) for _ in range(2)]
+        _check(self.lib.freddy_gpu_last_pv_stats(self.h, *(C.byref(x) for x in v)))
+        return {"candidates": v[0].value, "scored": v[1].value}
+
 
 class PQIndex(_Index):
     """pq_codebook + pq_quantization pinned in HBM."""
@@ -246,6 +259,18 @@ class PQIndex(_Index):
         _check(self.lib.freddy_gpu_pq_search(self.h, _p(qs), Q, k, C.c_float(sentinel), _p(sub),
                                              0 if sub is None else sub.size, _p(out_i), _p(out_d)))
         return out_i, out_d
+
+    def search_pv(self, vecs, queries, k, pvf, sentinel=100.0, subset_ids=None):
+        """pq_search at k * pvf, re-ranked on the device against the VectorIndex `vecs` (freddy_gpu_pq_search_pv):
+        (ids[Q,k], similarity[Q,k]), bit for bit vecs.search(q, k, subset_ids=<the candidates of q>) per query."""
+        qs = _f32(queries).reshape(-1, self.d)
+        Q = qs.shape[0]
+        out_i = np.empty((Q, k), np.int32)
+        out_s = np.empty((Q, k), np.float32)
+        sub = None if subset_ids is None else _i32(subset_ids)
+        _check(self.lib.freddy_gpu_pq_search_pv(self.h, vecs.h, _p(qs), Q, k, pvf, C.c_float(sentinel), _p(sub),
+                                                0 if sub is None else sub.size, _p(out_i), _p(out_s)))
+        return out_i, out_s
 
     def bind_search(self, queries, k, sentinel=100.0):
         """pq_search through the host-buffer call with every argument converted ONCE (the caller's loop then costs what a C
@@ -376,6 +401,17 @@ class IVFIndex(_Index):
         _check(self.lib.freddy_gpu_ivfadc_search(self.h, _p(qs), Q, k, W, C.c_float(sentinel), found_rule,
                                                  _p(out_i), _p(out_d)))
         return out_i, out_d
+
+    def search_pv(self, vecs, queries, k, pvf, W, sentinel=1000.0, found_rule=FOUND_ROWS):
+        """ivfadc_search at k * pvf, re-ranked on the device against the VectorIndex `vecs` (freddy_gpu_ivfadc_search_pv):
+        (ids[Q,k], similarity[Q,k]), bit for bit vecs.search(q, k, subset_ids=<the candidates of q>) per query."""
+        qs = _f32(queries).reshape(-1, self.d)
+        Q = qs.shape[0]
+        out_i = np.empty((Q, k), np.int32)
+        out_s = np.empty((Q, k), np.float32)
+        _check(self.lib.freddy_gpu_ivfadc_search_pv(self.h, vecs.h, _p(qs), Q, k, pvf, W, C.c_float(sentinel), found_rule,
+                                                    _p(out_i), _p(out_s)))
+        return out_i, out_s
 
     def search_dev(self, d_queries_ptr, Q, k, W, sentinel, found_rule, d_out_ids_ptr, d_out_dist_ptr,
                    d_status_ptr=0, stream=None):

@@ -41,6 +41,7 @@ def load():
         _lib.freddy_get_analogy_function.restype = C.c_char_p
         _lib.freddy_get_analogy_in_function.restype = C.c_char_p
         _lib.freddy_get_groups_function.restype = C.c_char_p
+        _lib.freddy_get_knn_batch_function.restype = C.c_char_p
     return _lib
 
 
@@ -199,6 +200,27 @@ class Session:
         n = C.c_int32(0)
         self._check(self.lib.k_nearest_neighbour_ivfadc_batch(self.h, _p(qid), qid.size, k, _p(out), C.byref(n)))
         return out[:n.value]
+
+    def _batch3(self, fn, query_ids, k):
+        qid = _i32(query_ids)
+        out = np.empty(max(qid.size, 1) * max(k, 1), ROW3)
+        n = C.c_int32(0)
+        self._check(fn(self.h, _p(qid), qid.size, k, _p(out), C.byref(n)))
+        return out[:n.value]
+
+    def k_nearest_neighbour_ivfadc_pv_batch(self, query_ids, k):
+        """k_nearest_neighbour_ivfadc_pv for every row of google_vecs_norm whose id is in query_ids: one device call."""
+        return self._batch3(self.lib.k_nearest_neighbour_ivfadc_pv_batch, query_ids, k)
+
+    def k_nearest_neighbour_pq_pv_batch(self, query_ids, k):
+        return self._batch3(self.lib.k_nearest_neighbour_pq_pv_batch, query_ids, k)
+
+    def knn_batch(self, query_ids, k):
+        """freddy--0.0.1.sql:232-246: the function set_knn_batch_function named."""
+        return self._batch3(self.lib.knn_batch, query_ids, k)
+
+    def set_knn_batch_function(self, name): self._check(self.lib.freddy_set_knn_batch_function(self.h, str(name).encode()))
+    def get_knn_batch_function_name(self): return self.lib.freddy_get_knn_batch_function(self.h).decode()
 
     def grouping_pq(self, input_ids, group_ids):
         """freddy.c:1176-1401: rows (id, group_id)."""

@@ -90,6 +90,8 @@ struct freddy_session {
   std::string analogy_fn = "analogy_3cosadd", analogy_in_fn = "analogy_3cosadd_in";
   // set_groups_function (:200)
   std::string groups_fn = "grouping_func";
+  // set_knn_batch_function (:197)
+  std::string knn_batch_fn = "k_nearest_neighbour_ivfadc_batch";
 };
 
 extern "C" {
@@ -749,6 +751,64 @@ int k_nearest_neighbour_ivfadc_batch(freddy_session_t* s, const int32_t* query_i
     if (rows[i].id >= 0) { out[m] = rows[i]; out[m].distance = similarity_of(rows[i].distance); ++m; }
   if (n_rows) *n_rows = m;
   return 0;
+}
+
+// ---- the batch form of the two post-verification functions, and knn_batch()      freddy--0.0.1.sql:556-662, 232-246 ----------
+// Queries chosen as ivfadc_batch_search chooses them (rows of google_vecs_norm with id IN query_ids, table order); per query the rows
+// of knn_pv for that vector with get_pvf() / get_w(): ONE device call (freddy_gpu_*_search_pv) instead of a call and a host loop each.
+static int knn_pv_batch(freddy_session_t* s, bool ivf, const int32_t* query_ids, int32_t n_query_ids, int32_t k, freddy_row3* out, int32_t* n_rows) {
+  if (n_rows) *n_rows = 0;
+  if (!s || (ivf ? !s->ivf : !s->pq)) return fail(-1, ivf ? "coarse_quantization / residual_codebook / fine_quantization are not loaded"
+                                                          : "pq_quantization / pq_codebook are not loaded");
+  if (s->norm_ids.empty() || s->d != (ivf ? s->ivf_d : s->pq_d)) return fail(-1, "google_vecs_norm is not loaded");
+  if (k <= 0 || n_query_ids < 0 || !out || (n_query_ids > 0 && !query_ids)) return fail(-1, "bad argument");
+  const int pvf = std::max(s->pvf, 1);
+  const int64_t kc = (int64_t)k * pvf;
+  if (kc > 4096) return fail(-1, "pvf * k = %lld exceeds this build's limit of 4096 candidates", (long long)kc);
+  std::vector<int32_t> rows;
+  for (int i = 0; i < n_query_ids; ++i) {
+    auto it = std::lower_bound(s->norm_ids.begin(), s->norm_ids.end(), query_ids[i]);
+    if (it != s->norm_ids.end() && *it == query_ids[i]) rows.push_back((int32_t)(it - s->norm_ids.begin()));
+  }
+  std::sort(rows.begin(), rows.end());
+  rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+  const int Q = (int)rows.size(), d = s->d;
+  if (Q == 0) return 0;
+  std::vector<float> qv((size_t)Q * d);
+  for (int i = 0; i < Q; ++i) memcpy(&qv[(size_t)i * d], &s->norm_vecs[(size_t)rows[i] * d], sizeof(float) * d);
+  if (int rc = ensure_vecs(s)) return rc;
+  std::vector<int32_t> ids((size_t)Q * k); std::vector<float> sim((size_t)Q * k);
+  const int rc = ivf ? freddy_gpu_ivfadc_search_pv(s->ivf, s->vecs, qv.data(), Q, k, pvf, s->w, 1000.0f, FREDDY_FOUND_ROWS, ids.data(), sim.data())
+                     : freddy_gpu_pq_search_pv(s->pq, s->vecs, qv.data(), Q, k, pvf, 100.0f, nullptr, 0, ids.data(), sim.data());
+  if (rc) return gpu_fail(rc);
+  int32_t n = 0;   // fewer than k rows for a query when fewer of its candidates have vectors
+  for (int q = 0; q < Q; ++q)
+    for (int r = 0; r < k && ids[(size_t)q * k + r] >= 0; ++r) out[n++] = {s->norm_ids[rows[q]], ids[(size_t)q * k + r], sim[(size_t)q * k + r]};
+  if (n_rows) *n_rows = n;
+  return 0;
+}
+int k_nearest_neighbour_ivfadc_pv_batch(freddy_session_t* s, const int32_t* query_ids, int32_t n_query_ids, int32_t k, freddy_row3* out, int32_t* n_rows) {
+  return knn_pv_batch(s, true, query_ids, n_query_ids, k, out, n_rows);
+}
+int k_nearest_neighbour_pq_pv_batch(freddy_session_t* s, const int32_t* query_ids, int32_t n_query_ids, int32_t k, freddy_row3* out, int32_t* n_rows) {
+  return knn_pv_batch(s, false, query_ids, n_query_ids, k, out, n_rows);
+}
+
+int freddy_set_knn_batch_function(freddy_session_t* s, const char* name) {
+  if (!s || !name) return fail(-1, "bad argument");
+  s->knn_batch_fn = name;
+  return 0;
+}
+const char* freddy_get_knn_batch_function(const freddy_session_t* s) { return s ? s->knn_batch_fn.c_str() : ""; }
+
+// EXECUTE format('SELECT * FROM %s(''%s'', %s)', get_knn_batch_function_name(), query_set, k)
+int knn_batch(freddy_session_t* s, const int32_t* query_ids, int32_t n_query_ids, int32_t k, freddy_row3* out, int32_t* n_rows) {
+  if (!s) return fail(-1, "bad argument");
+  const std::string& f = s->knn_batch_fn;
+  if (f == "k_nearest_neighbour_ivfadc_batch") return k_nearest_neighbour_ivfadc_batch(s, query_ids, n_query_ids, k, out, n_rows);
+  if (f == "k_nearest_neighbour_ivfadc_pv_batch") return k_nearest_neighbour_ivfadc_pv_batch(s, query_ids, n_query_ids, k, out, n_rows);
+  if (f == "k_nearest_neighbour_pq_pv_batch") return k_nearest_neighbour_pq_pv_batch(s, query_ids, n_query_ids, k, out, n_rows);
+  return fail(-1, "function %s(character varying[], integer) does not exist", f.c_str());
 }
 
 // ---- insert_batch --------------------------------------------------------------------
