@@ -189,6 +189,12 @@ int freddy_gpu_exact_search(freddy_gpu_index_t* vecs, const float* queries, int3
  * Any Q (processed in passes); k <= 32 (FREDDY_E_LIMIT above).  Argument errors are reported before any device work. */
 #define FREDDY_ANALOGY_3COSADD 0
 #define FREDDY_ANALOGY_3COSMUL 1
+/* analogy_pair_direction (freddy--0.0.1.sql:1212-1229): score = cosine_similarity_bytea(vec_normalize(v1 - v2), vec_normalize(v3 - v4)),
+ * every operation in binary32 as core_functions.c does it, the float widened.  The reference runs it on the ORIGINAL table
+ * (get_vecs_name_original()); any freddy_gpu_pin_vectors handle is accepted.  A row with v3's vector under another id scores NaN
+ * and comes first; w1 == w2 makes every score NaN (the k lowest ids that are not inputs).  Always the all-exact scan: no filter
+ * passes are reported, exact_filter and check_brackets have no effect. */
+#define FREDDY_ANALOGY_PAIR_DIRECTION 2
 int freddy_gpu_exact_analogy(freddy_gpu_index_t* vecs, int32_t method, const int32_t* triples /*[Q][3] ids w1,w2,w3*/,
                              int32_t Q, int32_t k, const int32_t* subset_ids, int64_t n_subset,
                              int32_t* out_ids /*[Q][k]*/, double* out_score /*[Q][k]; 3CosAdd: the float widened*/);

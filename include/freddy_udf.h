@@ -203,8 +203,17 @@ int cluster_ivpq(freddy_session_t* s, const int32_t* token_ids, int32_t n, int32
  *   call the function set_analogy_function / set_analogy_in_function named (defaults analogy_3cosadd / analogy_3cosadd_in,
  *   :198-199).  The setters accept any name, as the SQL ones do; a name this library does not implement fails at call time
  *   with PostgreSQL's wording: "function <name>(unknown, unknown, unknown) does not exist" (analogy_in: "..., character
- *   varying[])").  analogy(): analogy_3cosadd, analogy_3cosmul, analogy_3cosadd_pq, analogy_3cosadd_ivfadc; analogy_in():
- *   analogy_3cosadd_in, analogy_3cosadd_in_pq, analogy_3cosadd_in_ivpq. */
+ *   varying[])").  analogy(): analogy_3cosadd, analogy_3cosmul, analogy_pair_direction, analogy_3cosadd_pq,
+ *   analogy_3cosadd_ivfadc; analogy_in(): analogy_3cosadd_in, analogy_3cosadd_in_pq, analogy_3cosadd_in_ivpq (the reference has
+ *   no _in form of analogy_pair_direction: that name fails there with the four-argument wording).
+ * analogy_pair_direction                                    freddy--0.0.1.sql:1212-1229
+ *   the row v4 (v4 not w1, w2, w3) with the largest cosine_similarity_bytea(vec_normalize(v1 - v2), vec_normalize(v3 - v4)) over
+ *   google_vecs, the ORIGINAL (un-normalised) table (get_vecs_name_original()): freddy_load_vecs_original, rows in any order,
+ *   pinned as a second vector handle on first use.  Error "google_vecs is not loaded" before that.  A row that repeats v3's
+ *   vector under another id scores NaN and wins (NaN sorts first); *result = -1 where the SQL returns NULL.  insert_batch
+ *   receives only normalised vectors and does not extend google_vecs: an id it created is unknown here and gives -1. */
+int freddy_load_vecs_original(freddy_session_t* s, const int32_t* ids, const float* vectors, int64_t N, int32_t d);
+int analogy_pair_direction(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, int32_t* result);
 int analogy_3cosadd(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, int32_t* result);
 int analogy_3cosmul(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, int32_t* result);
 int analogy_3cosadd_in(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids, int32_t n_ids, int32_t* result);

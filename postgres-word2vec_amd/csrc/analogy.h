@@ -1,6 +1,6 @@
 // analogy.h -- exact word analogies: analogy_3cosadd / analogy_3cosadd_in / analogy_3cosmul
 // (freddy--0.0.1.sql:1270-1315, 1231-1249), the functions analogy(a, b, c) / analogy_in(...) dispatch to by default
-// (:198-199, :269-297).
+// (:198-199, :269-297), and analogy_pair_direction (:1212-1229; its contract further down).
 //
 // Contract.  Inputs are rows w1, w2, w3 of the table (v1, v2, v3); v4 runs over the candidate rows.  cos(a, b) is
 // cosine_similarity_bytea (core_functions.c:67-81): the binary32 chain "s += a[i] * b[i]", i ascending, multiply and add
@@ -50,6 +50,35 @@
 //   * Refine: the reference's chains from the row-major copy (exact.h's arithmetic), the double combination, the selection.
 //     check_brackets bit 3 makes every row a candidate (inputs included, for the check only) and counts rows with a c_i
 //     outside its bracket in freddy_gpu_filter_bound_violations / _checked.
+//
+// PAIR DIRECTION (analogy_pair_direction, freddy--0.0.1.sql:1212-1229; method FREDDY_ANALOGY_PAIR_DIRECTION).  The one search
+// function of the reference that scans the ORIGINAL (un-normalised) table, get_vecs_name_original(); the device does not care
+// which table the handle holds.  For rows w1, w2, w3 and every candidate row v4 whose id is none of the three inputs:
+//   A  = vec_normalize_bytea(vec_minus_bytea(v1, v2))      once per analogy
+//   U4 = vec_normalize_bytea(vec_minus_bytea(v3, v4))      per candidate row
+//   score = cosine_similarity_bytea(A, U4)                  a binary32 value (reported widened to double, as 3CosAdd's)
+//   ORDER BY score DESC, FETCH FIRST 1 (here: the first k; ties by id ASC, the pinned tie-break).
+// All arithmetic is binary32, operation by operation, as core_functions.c does it (no contraction: -ffp-contract=off):
+//   vec_minus_bytea (:120-139)      t[i] = a[i] - b[i]
+//   vec_normalize_bytea (:243-269)  sq += t[i] * t[i], i ascending, multiply and add each rounded; length = (float)sqrt((double)sq);
+//                                   out[i] = t[i] / length, a correctly rounded binary32 division (the v_div_scale / v_div_fmas /
+//                                   v_div_fixup sequence with fp32 denormals on -- never a reciprocal multiply).  The kernels
+//                                   take the square root in the reference's own form, the double square root rounded to float
+//                                   (equal to the correctly rounded float square root for every float: 53 >= 2 * 24 + 2 bits);
+//                                   it runs once per (row, analogy) against d divisions, so its cost does not show.
+//   cosine_similarity_bytea         s += A[i] * U4[i], i ascending: exact.h's chain.
+// What follows from that, none of it special-cased:
+//   * a row with v3's vector under another id has length 0, every component of U4 is 0/0, its score is NaN, and NaN sorts FIRST
+//     (an_ord): such a duplicate wins;
+//   * w1 == w2 (or equal vectors) makes A all NaN and every score NaN: the answer is the k lowest ids that are not inputs;
+//   * -0 and +0 are one value, reported as +0; an unknown input id gives (-1, -inf) in every slot with no device work;
+//   * non-finite tables need no other path: there is no filter, the arithmetic just runs.
+// The score is not a dot product against a fixed query column (the candidate row is normalised per (analogy, row) before the
+// chain), so neither the MFMA filter nor an_scan_kernel's accumulate loop expresses it: an_pair_columns_kernel writes A and a copy
+// of v3 per analogy, an_pair_scan_kernel makes two sweeps over a row's dimensions (the sums of squares of v3 - x, then the
+// chain with the difference recomputed -- the same rounded value), an_merge_kernel merges as for the other methods.  There is
+// no filter + refine path: an MFMA bound on A . (v3 - v4) / |v3 - v4| loses its grip exactly where rows are close to v3;
+// exact_filter and check_brackets have no effect on this method.
 //
 // Selection key: (score DESC, row ASC) does not fit exact.h's u64 (float, row) key for a double score, and the double is not
 // rounded to a float: an_ord maps the double to an order-preserving u64, and the selection (AnTop) compares (ord, row) pairs
@@ -286,6 +315,118 @@ __global__ __launch_bounds__(AN_WG) void an_scan_kernel(AnScanArgs a) {
   }
 }
 
+// ---- pair direction ------------------------------------------------------------------------------------------------------
+// A row's d values (lane = row of a 64-row block, xrow = the block's base + lane) handed to f(i, x) in ascending i, eight loads
+// in flight ahead of their use.
+template <class F>
+__device__ __forceinline__ void an_stream_row(const float* __restrict__ xrow, int d, F&& f) {
+  constexpr int DB = 8;
+  float xn[DB];
+#pragma unroll
+  for (int u = 0; u < DB; ++u) xn[u] = (u < d) ? xrow[(size_t)u * 64] : 0.0f;
+  for (int i0 = 0; i0 < d; i0 += DB) {
+    float xc[DB];
+#pragma unroll
+    for (int u = 0; u < DB; ++u) xc[u] = xn[u];
+#pragma unroll
+    for (int u = 0; u < DB; ++u) xn[u] = (i0 + DB + u < d) ? xrow[(size_t)(i0 + DB + u) * 64] : 0.0f;
+#pragma unroll
+    for (int u = 0; u < DB; ++u)
+      if (i0 + u < d) f(i0 + u, xc[u]);
+  }
+}
+
+// The columns of the pair-direction scan, one workgroup (one wave) per analogy: out[a][0][d] = A = vec_normalize(v1 - v2),
+// out[a][1][d] = v3.  The sum of squares is the reference's sequential chain: one lane walks it.
+__global__ __launch_bounds__(64) void an_pair_columns_kernel(const float* __restrict__ rows, int d, const int32_t* __restrict__ in_rows,
+                                                            float* __restrict__ out) {
+  __shared__ float len_s;
+  const int a = blockIdx.x, lane = threadIdx.x;
+  const int32_t* r = in_rows + (size_t)a * 3;
+  const float *v1 = rows + (size_t)r[0] * d, *v2 = rows + (size_t)r[1] * d, *v3 = rows + (size_t)r[2] * d;
+  float* A = out + (size_t)a * 2 * d;
+  for (int i = lane; i < d; i += 64) { A[i] = v1[i] - v2[i]; A[d + i] = v3[i]; }   // vec_minus_bytea(v1, v2)
+  __syncthreads();
+  if (lane == 0) {
+    float sq = 0.0f;
+    for (int i = 0; i < d; ++i) { const float p = A[i] * A[i]; sq = sq + p; }       // core_functions.c:255-257
+    len_s = (float)sqrt((double)sq);
+  }
+  __syncthreads();
+  const float len = len_s;
+  for (int i = lane; i < d; i += 64) A[i] = A[i] / len;
+}
+
+// The pair-direction scan: an_scan_kernel's layout (64-row blocks, lane = row, AT analogies per workgroup, one AnTop per (wave,
+// analogy), partial lists for an_merge_kernel) around two sweeps over the row's dimensions.  a.cols = an_pair_columns_kernel's
+// output; in LDS dimension i holds [A_0 .. A_AT-1, v3_0 .. v3_AT-1].
+template <int AT>
+__global__ __launch_bounds__(AN_WG) void an_pair_scan_kernel(AnScanArgs a) {
+  constexpr int QC = 2 * AT;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* qs = reinterpret_cast<float*>(smem);                                                    // [d][QC]
+  u64* lo = reinterpret_cast<u64*>(smem + (((size_t)a.d * QC * 4 + 15) & ~(size_t)15));          // [waves][AT][AN_SLOTS]
+  uint32_t* lr = reinterpret_cast<uint32_t*>(lo + AN_WAVES * AT * AN_SLOTS);
+  const int chunk = blockIdx.x, a0 = blockIdx.y * AT;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, d = a.d;
+  for (int i = threadIdx.x; i < d * QC; i += AN_WG) {
+    const int c = i / d, dim = i - c * d;        // c = h * AT + t: h = 0 the A column, 1 the v3 column of analogy a0 + t
+    const int h = c / AT, t = c - h * AT;
+    const int an = (a0 + t < a.na) ? a0 + t : a.na - 1;
+    qs[dim * QC + c] = a.cols[((size_t)an * 2 + h) * d + dim];
+  }
+  int32_t ex[AT][3];
+#pragma unroll
+  for (int t = 0; t < AT; ++t)
+#pragma unroll
+    for (int m = 0; m < 3; ++m) ex[t][m] = (a0 + t < a.na) ? a.in_rows[(size_t)(a0 + t) * 3 + m] : -2;
+  __syncthreads();
+  AnTop top[AT];
+#pragma unroll
+  for (int t = 0; t < AT; ++t) top[t].init(lo + ((size_t)wave * AT + t) * AN_SLOTS, lr + ((size_t)wave * AT + t) * AN_SLOTS, a.k);
+  const int b0 = chunk * a.chunk_blocks;
+  const int b1 = (b0 + a.chunk_blocks < a.n_blocks) ? b0 + a.chunk_blocks : a.n_blocks;
+  for (int b = b0 + wave; b < b1; b += AN_WAVES) {
+    const float* xrow = a.xb + (size_t)b * d * 64 + lane;
+    float sq[AT], len[AT], acc[AT];
+#pragma unroll
+    for (int t = 0; t < AT; ++t) { sq[t] = 0.0f; acc[t] = 0.0f; }
+    an_stream_row(xrow, d, [&](int i, float x) {            // sweep 1: vec_normalize_bytea's sum of squares of v3 - v4
+      const float* q = qs + i * QC + AT;
+#pragma unroll
+      for (int t = 0; t < AT; ++t) { const float df = q[t] - x; const float p = df * df; sq[t] = sq[t] + p; }
+    });
+#pragma unroll
+    for (int t = 0; t < AT; ++t) len[t] = (float)sqrt((double)sq[t]);                            // core_functions.c:259
+    an_stream_row(xrow, d, [&](int i, float x) {            // sweep 2: the cosine chain over A and (v3 - v4) / length
+      const float* q = qs + i * QC;
+#pragma unroll
+      for (int t = 0; t < AT; ++t) {
+        const float df = q[AT + t] - x;                     // (recomputed: the same rounded value as in sweep 1)
+        const float u = df / len[t];
+        const float p = q[t] * u;
+        acc[t] = acc[t] + p;
+      }
+    });
+    const int64_t slot = (int64_t)b * 64 + lane;
+    const int32_t row = a.pos ? a.pos[slot] : (slot < a.n_rows ? (int32_t)slot : -1);
+#pragma unroll
+    for (int t = 0; t < AT; ++t) {
+      const bool ok = row >= 0 && a0 + t < a.na && row != ex[t][0] && row != ex[t][1] && row != ex[t][2];
+      top[t].push(an_ord((double)acc[t]), (uint32_t)row, ok);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < AT; ++t) {
+    if (a0 + t >= a.na) continue;
+    AnEnt* out = a.part + (((size_t)(a0 + t) * a.nchunk + chunk) * AN_WAVES + wave) * a.k;
+    for (int r = lane; r < a.k; r += 64) {
+      const bool v = r < top[t].cnt;
+      out[r] = AnEnt{v ? top[t].ord[r] : 0ull, v ? top[t].row[r] : AN_NO_ROW, 0u};
+    }
+  }
+}
+
 // One workgroup per analogy: the partial lists -> the analogy's k best, (id, score) in order, (-1, -inf) beyond the rows.
 __global__ __launch_bounds__(AN_WG) void an_merge_kernel(const AnEnt* __restrict__ part, int parts, int k, const int32_t* __restrict__ ids,
                                                         int32_t* __restrict__ out_ids, double* __restrict__ out_score) {
@@ -504,6 +645,11 @@ static inline size_t an_refine_lds(int M, int d) {
 template <int M, int AT>
 static inline size_t an_scan_lds(int d) {
   return (((size_t)d * M * AT * 4 + 15) & ~(size_t)15) + (size_t)AN_WAVES * AT * AN_SLOTS * (sizeof(u64) + sizeof(uint32_t));
+}
+
+template <int AT>
+static inline size_t an_pair_lds(int d) {
+  return (((size_t)d * 2 * AT * 4 + 15) & ~(size_t)15) + (size_t)AN_WAVES * AT * AN_SLOTS * (sizeof(u64) + sizeof(uint32_t));
 }
 
 }  // namespace freddy

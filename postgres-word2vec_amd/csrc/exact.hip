@@ -558,6 +558,50 @@ static int analogy_scan(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, int 
   return 0;
 }
 
+// Analogies per workgroup of the pair-direction scan: the smallest tile of 1, 2, 4, 8 that holds the call (a tile's spare columns
+// repeat the last analogy: their divisions are done and thrown away), 8 beyond -- per (row, analogy) the kernel keeps a sum, a
+// length and three excluded rows in registers and 8 d bytes + 4.5 KiB of lists in LDS, so 8 analogies stay far from either budget
+// up to d = 1983; wider tables halve the tile until its columns fit (4 fits every d the entry point accepts).
+static int an_pair_tile(int na, int d) {
+  int at = na >= 8 ? 8 : na > 2 ? 4 : na;
+  while (at > 1 && (at == 8 ? an_pair_lds<8>(d) : at == 4 ? an_pair_lds<4>(d) : an_pair_lds<2>(d)) > AN_MAX_LDS) at /= 2;
+  return at;
+}
+
+// analogy_scan for FREDDY_ANALOGY_PAIR_DIRECTION: the columns (A, v3) per analogy, the two-sweep scan, the same merge.  Enqueued only.
+static int analogy_pair_scan(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const int32_t* d_in_rows, int na, int k, const float* xb,
+                             const int32_t* pos, int64_t n_rows, int64_t n_blocks, int32_t* d_ids, double* d_score) {
+  const int d = ix->d;
+  const int AT = an_pair_tile(na, d);
+  const int groups = (na + AT - 1) / AT;
+  int chunk_blocks = 8;
+  while ((n_blocks + chunk_blocks - 1) / chunk_blocks * (int64_t)groups > 8192 && chunk_blocks < 1024) chunk_blocks *= 2;
+  const int nchunk = (int)std::max<int64_t>(1, (n_blocks + chunk_blocks - 1) / chunk_blocks);
+  if (ws->w_qc.ensure(sizeof(float) * (size_t)na * 2 * d) || ws->w_part.ensure(sizeof(AnEnt) * (size_t)na * nchunk * AN_WAVES * k))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  float* cols = ws->w_qc.as<float>();
+  timed_launch(ix, s, "analogy_pair_columns", [&] { hipLaunchKernelGGL(an_pair_columns_kernel, dim3((unsigned)na), dim3(64), 0, s, ix->coarse, d, d_in_rows, cols); });
+  HIP_TRY(hipGetLastError());
+  AnScanArgs sa;
+  sa.xb = xb; sa.pos = pos; sa.n_rows = n_rows; sa.n_blocks = (int)n_blocks; sa.chunk_blocks = chunk_blocks; sa.nchunk = nchunk;
+  sa.cols = cols; sa.in_rows = d_in_rows; sa.na = na; sa.d = d; sa.k = k; sa.part = ws->w_part.as<AnEnt>();
+  const dim3 grid((unsigned)nchunk, (unsigned)groups);
+  timed_launch(ix, s, "analogy_pair_scan", [&] {
+    switch (AT) {
+      case 8: hipLaunchKernelGGL((an_pair_scan_kernel<8>), grid, dim3(AN_WG), an_pair_lds<8>(d), s, sa); break;
+      case 4: hipLaunchKernelGGL((an_pair_scan_kernel<4>), grid, dim3(AN_WG), an_pair_lds<4>(d), s, sa); break;
+      case 2: hipLaunchKernelGGL((an_pair_scan_kernel<2>), grid, dim3(AN_WG), an_pair_lds<2>(d), s, sa); break;
+      default: hipLaunchKernelGGL((an_pair_scan_kernel<1>), grid, dim3(AN_WG), an_pair_lds<1>(d), s, sa); break;
+    }
+  });
+  HIP_TRY(hipGetLastError());
+  timed_launch(ix, s, "analogy_merge", [&] {
+    hipLaunchKernelGGL(an_merge_kernel, dim3((unsigned)na), dim3(AN_WG), 0, s, (const AnEnt*)sa.part, nchunk * AN_WAVES, k, ix->ids, d_ids, d_score);
+  });
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // The filter + refine path over the whole table, passes of AN_PASS analogies.  flags[p] (device, zeroed here) != 0: pass p's
 // results are not valid (its columns were not finite, or a candidate buffer overflowed) -- the caller redoes it; flags[passes + p]
 // receives the number of candidates pass p refined.  Enqueued only.
@@ -632,7 +676,8 @@ static int analogy_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, in
 extern "C" int freddy_gpu_exact_analogy(freddy_gpu_index_t* ix, int32_t method, const int32_t* triples, int32_t Q, int32_t k,
                                         const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, double* out_score) {
   // (the scalar arguments first: they are checked before the handle is looked at, so no device is needed to see these errors)
-  if (method != FREDDY_ANALOGY_3COSADD && method != FREDDY_ANALOGY_3COSMUL) return fail(FREDDY_E_ARG, "unknown analogy method %d", method);
+  if (method != FREDDY_ANALOGY_3COSADD && method != FREDDY_ANALOGY_3COSMUL && method != FREDDY_ANALOGY_PAIR_DIRECTION)
+    return fail(FREDDY_E_ARG, "unknown analogy method %d", method);
   if (Q < 0 || k <= 0 || n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad sizes");
   if (Q > 0 && (!triples || !out_ids || !out_score)) return fail(FREDDY_E_ARG, "NULL buffer");
   if (k > AN_MAXK) return fail(FREDDY_E_LIMIT, "k=%d exceeds the exact analogy's limit of %d", k, AN_MAXK);
@@ -677,7 +722,9 @@ extern "C" int freddy_gpu_exact_analogy(freddy_gpu_index_t* ix, int32_t method, 
   HIP_TRY(hipMemcpyAsync(d_rows, rows3.data(), sizeof(int32_t) * rows3.size(), hipMemcpyHostToDevice, s));
   // filter + refine: the whole table, k <= 32, finite rows of a supported shape (exact kNN's eligibility)
   // and the pass's query fragments must fit the LDS of a CU (an_filter_kernel holds all M tiles: 3CosMul with d > 416 does not)
-  const bool want_filter = !subset_ids && ix->exf_ok && ix->tune.exact_filter != 0 && (ix->tune.exact_filter == 1 || n_rows >= 8192) &&
+  // pair direction has no filter: its score is no dot product against a fixed column (analogy.h)
+  const bool pair = method == FREDDY_ANALOGY_PAIR_DIRECTION;
+  const bool want_filter = !pair && !subset_ids && ix->exf_ok && ix->tune.exact_filter != 0 && (ix->tune.exact_filter == 1 || n_rows >= 8192) &&
                            an_filter_lds(M, d) <= AN_MAX_LDS;
   std::vector<int32_t> redo;   // passes the all-exact path computes
   if (want_filter) {
@@ -697,8 +744,9 @@ extern "C" int freddy_gpu_exact_analogy(freddy_gpu_index_t* ix, int32_t method, 
   auto scan_range = [&](int a0, int n) -> int {
     for (int c0 = a0; c0 < a0 + n; c0 += chunk) {
       const int nc = std::min(chunk, a0 + n - c0);
-      if (int rc = analogy_scan(ix, ws, s, M, d_rows + (size_t)c0 * 3, nc, k, xb, pos, n_rows, n_blocks, d_ids + (size_t)c0 * k, d_score + (size_t)c0 * k))
-        return rc;
+      const int rc = pair ? analogy_pair_scan(ix, ws, s, d_rows + (size_t)c0 * 3, nc, k, xb, pos, n_rows, n_blocks, d_ids + (size_t)c0 * k, d_score + (size_t)c0 * k)
+                          : analogy_scan(ix, ws, s, M, d_rows + (size_t)c0 * 3, nc, k, xb, pos, n_rows, n_blocks, d_ids + (size_t)c0 * k, d_score + (size_t)c0 * k);
+      if (rc) return rc;
     }
     return 0;
   };
@@ -822,6 +870,7 @@ std::vector<LdsLimit> lds_limits_exact() {
           {&exj_filter_kernel<1, true>, b},  {&exj_filter_kernel<2, true>, b},  {&exj_filter_kernel<4, true>, b},
           {&an_filter_kernel<1, false>, b},  {&an_filter_kernel<3, false>, b},  {&an_filter_kernel<1, true>, b},  {&an_filter_kernel<3, true>, b},
           {&an_scan_kernel<1, 8>, b},        {&an_scan_kernel<3, 4>, b},
+          {&an_pair_scan_kernel<1>, b},      {&an_pair_scan_kernel<2>, b},      {&an_pair_scan_kernel<4>, b},     {&an_pair_scan_kernel<8>, b},
           // (the all-exact scan: more than 64 KiB from d = 513 on with tiles of 16 queries, from d = 1537 on with tiles of 8)
           &exact_scan_kernel<1, 16>, &exact_scan_kernel<2, 16>, &exact_scan_kernel<4, 16>,
           &exact_scan_kernel<1, 8>, &exact_scan_kernel<2, 8>, &exact_scan_kernel<4, 8>, &exact_scan_kernel<8, 8>, &exact_scan_kernel<16, 8>,

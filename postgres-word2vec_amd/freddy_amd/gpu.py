@@ -16,7 +16,7 @@ FOUND_ROWS = 0
 FOUND_ACCEPTED = 1
 FOUND_BATCH_UDF = 2   # ivfadc_batch_search itself (W == 1): accepted-rows rule + its argmin cell limit of 1000
 METHOD_PQ, METHOD_EXACT, METHOD_PQ_PV = 0, 1, 2
-ANALOGY_METHODS = {"3cosadd": 0, "3cosmul": 1}   # include/freddy_gpu.h FREDDY_ANALOGY_*
+ANALOGY_METHODS = {"3cosadd": 0, "3cosmul": 1, "pair_direction": 2}   # include/freddy_gpu.h FREDDY_ANALOGY_*
 
 EXPORTS = [
     "freddy_gpu_pin_pq", "freddy_gpu_pin_ivf", "freddy_gpu_pin_ivpq", "freddy_gpu_unpin",
@@ -330,7 +330,8 @@ class VectorIndex(_Index):
     def analogy(self, triples, k=1, method="3cosmul", subset_ids=None):
         """Exact analogies (freddy_gpu_exact_analogy): triples [Q][3] of row ids (w1, w2, w3) -> (ids[Q,k], scores[Q,k] float64),
         ORDER BY score DESC, id ASC, the three inputs excluded; (-1, -inf) where there is no row (or an input id is unknown).
-        method: "3cosadd" (the binary32 score widened) or "3cosmul" (float8)."""
+        method: "3cosadd" (the binary32 score widened), "3cosmul" (float8) or "pair_direction" (analogy_pair_direction: binary32
+        widened; meant for a handle that holds the original, un-normalised table)."""
         if method not in ANALOGY_METHODS:
             raise ValueError(f"method must be one of {sorted(ANALOGY_METHODS)}")
         t = _i32(triples).reshape(-1, 3)

@@ -97,6 +97,11 @@ class Session:
         ids, v = _i32(ids), _f32(vectors)
         self._check(self.lib.freddy_load_vecs_norm(self.h, _p(ids), _p(v), C.c_int64(ids.size), v.shape[1]))
 
+    def load_vecs_original(self, ids, vectors):
+        """google_vecs, the un-normalised table analogy_pair_direction scans (rows in any order)."""
+        ids, v = _i32(ids), _f32(vectors)
+        self._check(self.lib.freddy_load_vecs_original(self.h, _p(ids), _p(v), C.c_int64(ids.size), v.shape[1]))
+
     def load_pq(self, codebook, ids, codes):
         pos, code, vec, n, s = _entries(codebook)
         ids, codes = _i32(ids), _i16(codes)
@@ -298,6 +303,7 @@ class Session:
 
     def analogy_3cosadd(self, id1, id2, id3): return self._analogy3(self.lib.analogy_3cosadd, id1, id2, id3)
     def analogy_3cosmul(self, id1, id2, id3): return self._analogy3(self.lib.analogy_3cosmul, id1, id2, id3)
+    def analogy_pair_direction(self, id1, id2, id3): return self._analogy3(self.lib.analogy_pair_direction, id1, id2, id3)
     def analogy_3cosadd_in(self, id1, id2, id3, input_ids): return self._analogy4(self.lib.analogy_3cosadd_in, id1, id2, id3, input_ids)
     def analogy(self, a, b, c): return self._analogy3(self.lib.analogy, a, b, c)
     def analogy_in(self, w1, w2, w3, input_ids): return self._analogy4(self.lib.analogy_in, w1, w2, w3, input_ids)

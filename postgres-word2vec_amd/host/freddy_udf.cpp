@@ -78,6 +78,11 @@ struct freddy_session {
   freddy_gpu_index_t* ivf = nullptr;
   freddy_gpu_index_t* ivpq = nullptr;
   freddy_gpu_index_t* vecs = nullptr;  // google_vecs_norm pinned for the exact kNN functions (lazily)
+  // google_vecs (get_vecs_name_original()): the un-normalised table analogy_pair_direction scans, pinned lazily as a second handle
+  int orig_d = 0;
+  std::vector<int32_t> orig_ids;      // ascending
+  std::vector<float> orig_vecs;       // [N][orig_d] in that order
+  freddy_gpu_index_t* vecs_orig = nullptr;
   int pq_d = 0, ivf_d = 0, ivpq_d = 0;
   // what insert_batch reads and writes besides the rows (freddy.c:1545-1560): the codebooks with their
   // count column, the coarse quantizers, and the largest id of each table ("SELECT max(id) + 1")
@@ -112,6 +117,7 @@ int freddy_session_close(freddy_session_t* s) {
   if (s->ivf) freddy_gpu_unpin(s->ivf);
   if (s->ivpq) freddy_gpu_unpin(s->ivpq);
   if (s->vecs) freddy_gpu_unpin(s->vecs);
+  if (s->vecs_orig) freddy_gpu_unpin(s->vecs_orig);
   delete s;
   return 0;
 }
@@ -127,6 +133,20 @@ int freddy_load_vecs_norm(freddy_session_t* s, const int32_t* ids, const float* 
     memcpy(&s->norm_vecs[(size_t)i * d], vectors + (size_t)ord[i] * d, sizeof(float) * d);
   }
   if (s->vecs) { freddy_gpu_unpin(s->vecs); s->vecs = nullptr; }
+  return 0;
+}
+
+int freddy_load_vecs_original(freddy_session_t* s, const int32_t* ids, const float* vectors, int64_t N, int32_t d) {
+  if (!s || !ids || !vectors || N < 0 || d <= 0) return fail(-1, "bad argument");
+  std::vector<int64_t> ord = order_by_id(ids, N);
+  s->orig_d = d;
+  s->orig_ids.resize((size_t)N);
+  s->orig_vecs.resize((size_t)N * d);
+  for (int64_t i = 0; i < N; ++i) {
+    s->orig_ids[i] = ids[ord[i]];
+    memcpy(&s->orig_vecs[(size_t)i * d], vectors + (size_t)ord[i] * d, sizeof(float) * d);
+  }
+  if (s->vecs_orig) { freddy_gpu_unpin(s->vecs_orig); s->vecs_orig = nullptr; }
   return 0;
 }
 
@@ -995,6 +1015,20 @@ int analogy_3cosmul(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, 
 int analogy_3cosadd_in(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids, int32_t n_ids, int32_t* result) {
   return exact_analogy(s, FREDDY_ANALOGY_3COSADD, id1, id2, id3, input_ids, n_ids, true, result);
 }
+// freddy--0.0.1.sql:1212-1229: the one exact function that reads get_vecs_name_original(); google_vecs pinned on first use
+int analogy_pair_direction(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, int32_t* result) {
+  if (!s || !result) return fail(-1, "bad argument");
+  if (s->orig_ids.empty()) return fail(-1, "google_vecs is not loaded");
+  *result = -1;
+  if (!s->vecs_orig) {
+    freddy_vec_desc desc = {s->orig_d, (int64_t)s->orig_ids.size(), s->orig_ids.data(), s->orig_vecs.data()};
+    if (int rc = freddy_gpu_pin_vectors(&desc, s->device, &s->vecs_orig)) return gpu_fail(rc);
+  }
+  const int32_t triple[3] = {id1, id2, id3};
+  double score = 0;
+  if (int rc = freddy_gpu_exact_analogy(s->vecs_orig, FREDDY_ANALOGY_PAIR_DIRECTION, triple, 1, 1, nullptr, 0, result, &score)) return gpu_fail(rc);
+  return 0;
+}
 
 int freddy_set_analogy_function(freddy_session_t* s, const char* name) {
   if (!s || !name) return fail(-1, "bad argument");
@@ -1015,6 +1049,7 @@ int analogy(freddy_session_t* s, int32_t a, int32_t b, int32_t c, int32_t* resul
   const std::string& f = s->analogy_fn;
   if (f == "analogy_3cosadd") return analogy_3cosadd(s, a, b, c, result);
   if (f == "analogy_3cosmul") return analogy_3cosmul(s, a, b, c, result);
+  if (f == "analogy_pair_direction") return analogy_pair_direction(s, a, b, c, result);
   if (f == "analogy_3cosadd_pq") return analogy_3cosadd_pq(s, a, b, c, result);
   if (f == "analogy_3cosadd_ivfadc") return analogy_3cosadd_ivfadc(s, a, b, c, result);
   return fail(-1, "function %s(unknown, unknown, unknown) does not exist", f.c_str());
