@@ -827,7 +827,13 @@ float fo_cosine_similarity_bytea(const float* v1, const float* v2, int n) {
   return scalar;
 }
 
-/* ORDER BY similarity DESC (ties: ascending id) FETCH FIRST k   freddy--0.0.1.sql:426-454,991-1084 */
+/* ORDER BY similarity DESC (ties: ascending id) FETCH FIRST k   freddy--0.0.1.sql:426-454,991-1084
+ * The ORDER BY is PostgreSQL's float4 order, in which a NaN is equal to a NaN and above every number: NaN similarities come
+ * first, by ascending id.  (C's "<" alone would leave a NaN wherever its row arrived and let no later row pass it.) */
+static int sim_below(float a, float b) {
+  if (b != b) return a == a;
+  return a < b;          /* (false for a NaN a) */
+}
 int fo_exact_knn(const float* vectors, const int32_t* ids, int64_t N, int d, const float* q, int k,
                  const int32_t* input_ids, int n_ids, fo_entry* out) {
   int64_t* rows = NULL;
@@ -839,7 +845,7 @@ int fo_exact_knn(const float* vectors, const int32_t* ids, int64_t N, int d, con
     const float sim = fo_cosine_similarity_bytea(q, vectors + (size_t)r * d, d);
     /* insertion into a descending list; rows arrive in ascending id, an equal similarity stays behind */
     int slot = n_out;
-    while (slot > 0 && out[slot - 1].dist < sim) --slot;
+    while (slot > 0 && sim_below(out[slot - 1].dist, sim)) --slot;
     if (slot >= k) continue;
     const int last = (n_out < k) ? n_out : k - 1;
     for (int j = last; j > slot; --j) out[j] = out[j - 1];

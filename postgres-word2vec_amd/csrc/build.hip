@@ -7,9 +7,10 @@
 // index build: encoding
 // ---------------------------------------------------------------------------------------
 // limit_coarse / limit_code < +inf: insert_batch's searches start from that distance (strict "<"); *n_too_far
-// counts the (vector[, position]) pairs with no centroid nearer than the limit.
+// counts the (vector[, position]) pairs with no centroid nearer than the limit.  first_sticks: the searches start at the FIRST
+// entry instead (the index build, pq_index.py:78-86): a NaN distance there is never left (non-finite inputs).
 static int encode_impl(const freddy_encode_desc* t, int device, const float* vectors, int64_t N, int32_t* out_cell,
-                       int16_t* out_codes, float limit_coarse, float limit_code, int32_t* n_too_far) {
+                       int16_t* out_codes, float limit_coarse, float limit_code, int32_t* n_too_far, int first_sticks = 0) {
   if (!t || !t->codebook || !out_codes || N < 0 || (N > 0 && !vectors)) return fail(FREDDY_E_ARG, "NULL argument");
   if (t->d <= 0 || t->m <= 0 || t->K <= 0 || t->d % t->m) return fail(FREDDY_E_ARG, "bad shape d=%d m=%d K=%d", t->d, t->m, t->K);
   if (t->K > 32767) return fail(FREDDY_E_LIMIT, "K=%d does not fit an int16 code", t->K);
@@ -67,16 +68,16 @@ static int encode_impl(const freddy_encode_desc* t, int device, const float* vec
     ENC_TRY(hipMemcpyAsync(d_vec, vectors + (size_t)i0 * d, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, s));
     const float* src = d_vec;
     if (C) {
-      hipLaunchKernelGGL(assign_coarse_kernel, dim3((unsigned)n), dim3(64), 0, s, (const float*)d_vec, (const float*)d_cT, d_cell, n, C, Cpad, d, limit_coarse, d_far);
+      hipLaunchKernelGGL(assign_coarse_kernel, dim3((unsigned)n), dim3(64), 0, s, (const float*)d_vec, (const float*)d_cT, d_cell, n, C, Cpad, d, limit_coarse, d_far, first_sticks);
       hipLaunchKernelGGL(residual_kernel, dim3((unsigned)n), dim3(WG), 0, s, (const float*)d_vec, (const float*)d_coarse,
                          (const int32_t*)d_cell, (const int32_t*)nullptr, d_res, d, S, S);
       src = d_res;
     }
     const int ipw = 64;
     const dim3 grid((unsigned)m, (unsigned)((n + ipw - 1) / ipw));
-    if (S == 25) hipLaunchKernelGGL((encode_pq_kernel<25, 4>), grid, dim3(WG), 0, s, src, (const float*)d_cbT, d_codes, n, ipw, m, K, d, S, limit_code, d_far);
-    else if (S == 10) hipLaunchKernelGGL((encode_pq_kernel<10, 4>), grid, dim3(WG), 0, s, src, (const float*)d_cbT, d_codes, n, ipw, m, K, d, S, limit_code, d_far);
-    else hipLaunchKernelGGL((encode_pq_kernel<0, 4>), grid, dim3(WG), 0, s, src, (const float*)d_cbT, d_codes, n, ipw, m, K, d, S, limit_code, d_far);
+    if (S == 25) hipLaunchKernelGGL((encode_pq_kernel<25, 4>), grid, dim3(WG), 0, s, src, (const float*)d_cbT, d_codes, n, ipw, m, K, d, S, limit_code, d_far, first_sticks);
+    else if (S == 10) hipLaunchKernelGGL((encode_pq_kernel<10, 4>), grid, dim3(WG), 0, s, src, (const float*)d_cbT, d_codes, n, ipw, m, K, d, S, limit_code, d_far, first_sticks);
+    else hipLaunchKernelGGL((encode_pq_kernel<0, 4>), grid, dim3(WG), 0, s, src, (const float*)d_cbT, d_codes, n, ipw, m, K, d, S, limit_code, d_far, first_sticks);
     ENC_TRY(hipGetLastError());
     ENC_TRY(hipMemcpyAsync(out_codes + (size_t)i0 * m, d_codes, sizeof(int16_t) * (size_t)n * m, hipMemcpyDeviceToHost, s));
     if (C) ENC_TRY(hipMemcpyAsync(out_cell + i0, d_cell, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
@@ -91,7 +92,7 @@ static int encode_impl(const freddy_encode_desc* t, int device, const float* vec
 extern "C" int freddy_gpu_encode(const freddy_encode_desc* t, int device, const float* vectors, int64_t N, int32_t* out_cell,
                                  int16_t* out_codes) {
   const float inf = std::numeric_limits<float>::infinity();
-  return encode_impl(t, device, vectors, N, out_cell, out_codes, inf, inf, nullptr);
+  return encode_impl(t, device, vectors, N, out_cell, out_codes, inf, inf, nullptr, 1);
 }
 
 // insert_batch, quantisation of the new vectors (freddy.c:1557-1623): codes against the PQ codebook, coarse
@@ -174,7 +175,7 @@ extern "C" int freddy_gpu_kmeans(int device, const float* vectors, int64_t n, in
   for (int it = 0; it <= iters; ++it) {
     hipLaunchKernelGGL(kmeans_transpose_kernel, dim3((unsigned)(((size_t)d * kpad + 255) / 256)), dim3(256), 0, s, (const float*)d_cent, d_centT, k, kpad, d);
     hipLaunchKernelGGL(assign_coarse_kernel, dim3((unsigned)n), dim3(64), 0, s, (const float*)d_vec, (const float*)d_centT, d_assign, (int)n, k, kpad, d,
-                       inf, (int32_t*)nullptr);
+                       inf, (int32_t*)nullptr, 1);
     if (it == iters) break;
     hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)k), dim3(256), 0, s, (const float*)d_vec, (const int32_t*)d_assign, n, d, d_cent);
     KM_TRY(hipGetLastError());

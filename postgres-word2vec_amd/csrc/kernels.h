@@ -496,7 +496,8 @@ __global__ __launch_bounds__(WG) void lut_build_kernel(const float* __restrict__
 template <int S, int E>
 __global__ __launch_bounds__(WG) void encode_pq_kernel(const float* __restrict__ vecs, const float* __restrict__ cbT,
                                                       int16_t* __restrict__ codes, int n_items, int items_per_wg, int m,
-                                                      int K, int d, int S_rt, float limit, int32_t* __restrict__ too_far) {
+                                                      int K, int d, int S_rt, float limit, int32_t* __restrict__ too_far,
+                                                      int first_sticks) {
   __shared__ u64 wmin[WG / 64];
   const int p = blockIdx.x;
   const int it0 = blockIdx.y * items_per_wg;
@@ -506,6 +507,7 @@ __global__ __launch_bounds__(WG) void encode_pq_kernel(const float* __restrict__
   for (int it = it0; it < it1; ++it) {
     const float* r = vecs + (size_t)it * d + (size_t)p * Sr;
     u64 best = KEY_INF;
+    bool first_nan = false;   // (thread 0 only) code 0 is at a NaN distance
     for (int c0 = 0; c0 < K; c0 += WG * E) {
       // (for K <= WG*E, i.e. every configuration of the reference, this loop runs once and the compiler
       // keeps the codebook slice in registers across the items of the workgroup)
@@ -542,6 +544,7 @@ __global__ __launch_bounds__(WG) void encode_pq_kernel(const float* __restrict__
       for (int e = 0; e < E; ++e) {
         const int c = c0 + e * WG + (int)threadIdx.x;
         if (c < K) best = umin64(best, make_key(acc[e], (uint32_t)c));
+        if (c == 0) first_nan = acc[e] != acc[e];
       }
     }
 #pragma unroll
@@ -553,9 +556,12 @@ __global__ __launch_bounds__(WG) void encode_pq_kernel(const float* __restrict__
       u64 b = wmin[0];
 #pragma unroll
       for (int w = 1; w < WG / 64; ++w) b = umin64(b, wmin[w]);
-      codes[(size_t)it * m + p] = (int16_t)key_pos(b);
+      // A NaN key is above every other, so the minimum is the argmin by strict "<" over the distances that are numbers.  The
+      // search that starts at the FIRST entry (pq_index.py:78-86, first_sticks) never leaves a NaN there: nothing is < NaN.
+      codes[(size_t)it * m + p] = (first_sticks && first_nan) ? (int16_t)0 : (int16_t)key_pos(b);
       // insert_batch searches from minDist = 100 by strict "<" (index_utils.c:925-939): the same code unless NO
       // entry is nearer than the limit, which the reference leaves undefined -- reported
+      // (the count reads the minimum, not the stored code: the callers that count search from the limit, first_sticks = 0)
       if (too_far && !(key_dist(b) < limit)) atomicAdd(too_far, 1);
     }
   }
@@ -565,11 +571,12 @@ __global__ __launch_bounds__(WG) void encode_pq_kernel(const float* __restrict__
 // ties (faiss IndexFlatL2 search k=1 / ivfadc.py); one wave per vector, lane <-> centroid.
 static __global__ __launch_bounds__(64) void assign_coarse_kernel(const float* __restrict__ vecs, const float* __restrict__ coarseT,
                                                           int32_t* __restrict__ cell, int n, int C, int Cpad, int d,
-                                                          float limit, int32_t* __restrict__ too_far) {
+                                                          float limit, int32_t* __restrict__ too_far, int first_sticks) {
   const int it = blockIdx.x, lane = threadIdx.x;
   if (it >= n) return;
   const float* v = vecs + (size_t)it * d;
   u64 best = KEY_INF;
+  bool first_nan = false;   // (lane 0 only) centroid 0 is at a NaN distance: the search that starts there never leaves it
   for (int c = lane; c < C; c += 64) {
     float acc = 0.0f;
     for (int j = 0; j < d; ++j) {
@@ -578,12 +585,14 @@ static __global__ __launch_bounds__(64) void assign_coarse_kernel(const float* _
       acc = acc + pr;
     }
     best = umin64(best, make_key(acc, (uint32_t)c));
+    if (c == 0) first_nan = acc != acc;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) best = umin64(best, __shfl_xor(best, o, 64));
   if (lane == 0) {
-    cell[it] = (int32_t)key_pos(best);
-    if (too_far && !(key_dist(best) < limit)) atomicAdd(too_far, 1);   // (freddy.c:1568-1575: minDistCoarse = 100)
+    cell[it] = (first_sticks && first_nan) ? 0 : (int32_t)key_pos(best);
+    // (freddy.c:1568-1575: minDistCoarse = 100; the count reads the minimum, not the stored cell: counting callers pass first_sticks = 0)
+    if (too_far && !(key_dist(best) < limit)) atomicAdd(too_far, 1);
   }
 }
 

@@ -210,6 +210,10 @@ static int build_fragment_codebook(freddy_gpu_index* ix, const float* codebook) 
   if (upload(&ix->cbF, f.data(), f.size(), &ix->bytes)) return fail(FREDDY_E_NOMEM, "device allocation failed");
   return 0;
 }
+// The largest norm so far, a NaN included and kept: std::max drops a NaN operand, and the filter's margin E must turn non-finite
+// when any codeword or centroid is (refine.h: every row then goes to the exact stage) -- a finite E over a table with a NaN in
+// it emptied the lists of the queries whose smallest cheap distances came from the rows that use the NaN codeword.
+static inline double norm_max(double a, double b) { return (b != b || b > a) ? b : a; }
 static int derive_codebook_tables_into(freddy_gpu_index* ix, const float* codebook) {
   std::vector<float> cbT = transpose_codebook(codebook, ix->m, ix->K, ix->S);
   if (upload(&ix->cbT, cbT.data(), cbT.size(), &ix->bytes)) return fail(FREDDY_E_NOMEM, "device allocation failed");
@@ -223,7 +227,7 @@ static int derive_codebook_tables_into(freddy_gpu_index* ix, const float* codebo
         for (int c = 0; c < ix->K; ++c) {
           double n2 = 0.0;
           for (int j = 0; j < ix->S; ++j) { const double v = codebook[((size_t)p * ix->K + c) * ix->S + j]; n2 += v * v; }
-          cmax = std::max(cmax, std::sqrt(n2));
+          cmax = norm_max(cmax, std::sqrt(n2));
         }
         cmaxp[p] = (float)(cmax * (1.0 + 1e-6));
       }
@@ -262,12 +266,12 @@ static int derive_codebook_tables_into(freddy_gpu_index* ix, const float* codebo
       for (int c = 0; c < C; ++c) {
         double n2 = 0.0;
         for (int j = 0; j < ix->S; ++j) { const double v = ix->h_coarse[(size_t)c * d + p * ix->S + j]; n2 += v * v; }
-        comax = std::max(comax, std::sqrt(n2));
+        comax = norm_max(comax, std::sqrt(n2));
       }
       for (int c = 0; c < ix->K; ++c) {
         double n2 = 0.0;
         for (int j = 0; j < ix->S; ++j) { const double v = codebook[((size_t)p * ix->K + c) * ix->S + j]; n2 += v * v; }
-        cmax = std::max(cmax, std::sqrt(n2));
+        cmax = norm_max(cmax, std::sqrt(n2));
       }
       pmax[p] = (float)((comax + cmax) * (1.0 + 1e-6));
       cmaxp[p] = (float)(cmax * (1.0 + 1e-6));

@@ -76,3 +76,70 @@ def assert_same_lists(got_ids, got_dist, exp, what=""):
     bad = np.argwhere(exp_ids != got_ids)
     assert bad.size == 0, f"{what}: id mismatch at {bad[:5].tolist()} exp {exp_ids[tuple(bad[0])]} got {got_ids[tuple(bad[0])]}"
     assert np.array_equal(exp_d.view(np.uint32), got_dist.view(np.uint32)), f"{what}: distance bits differ"
+
+
+# ---- non-finite inputs (tests/test_nonfinite_cpu.py, tests/test_gpu_nonfinite.py) ----
+NEG_NAN = np.array([0xffc00000], np.uint32).view(np.float32)[0]     # a quiet NaN with the sign bit set
+QUERY_POISONS = ("nan", "neg_nan", "pos_inf", "neg_inf", "both_inf", "all_nan")
+
+
+def poison_query(q, kind, m, rng, where="first"):
+    """A copy of q with the poison `kind`: the component is drawn by rng inside the first or the last of the m sub-vectors
+    (`where`); both_inf puts +Inf into the first and -Inf into the last."""
+    q = np.array(q, np.float32)
+    d = q.size
+    s = d // m
+    first, last = int(rng.integers(0, s)), d - s + int(rng.integers(0, s))
+    at = first if where == "first" else last
+    if kind == "nan":
+        q[at] = np.nan
+    elif kind == "neg_nan":
+        q[at] = NEG_NAN
+    elif kind == "pos_inf":
+        q[at] = np.inf
+    elif kind == "neg_inf":
+        q[at] = -np.inf
+    elif kind == "both_inf":
+        q[first], q[last] = np.inf, -np.inf
+    elif kind == "all_nan":
+        q[:] = np.nan
+    else:
+        raise ValueError(kind)
+    return q
+
+
+PLACEMENTS = ("every8", "run64", "ends")
+
+
+def poisoned_rows(Q, placement, seed=0):
+    """Indices of the poisoned queries of a batch of Q >= 128: one in every group of 8, the aligned run [64, 128), or both ends."""
+    rng = np.random.default_rng(seed)
+    if placement == "every8":
+        return np.array([g + int(rng.integers(0, min(8, Q - g))) for g in range(0, Q, 8)])
+    if placement == "run64":
+        assert Q >= 128
+        return np.arange(64, 128)
+    if placement == "ends":
+        return np.array([0, Q - 1])
+    raise ValueError(placement)
+
+
+def poison_batch(qs, placement, m, seed=0):
+    """(poisoned copy of qs, bool mask of the poisoned rows).  The poisoned rows cycle through QUERY_POISONS, alternating
+    between the first and the last sub-vector, so every batch holds every kind at both ends (from six poisoned rows on)."""
+    rng = np.random.default_rng(1000 + seed)
+    out = np.array(qs, np.float32)
+    rows = poisoned_rows(out.shape[0], placement, seed)
+    for j, r in enumerate(rows):
+        kind = QUERY_POISONS[j % len(QUERY_POISONS)]
+        out[r] = poison_query(out[r], kind, m, rng, where="first" if (j // len(QUERY_POISONS)) % 2 == 0 else "last")
+    mask = np.zeros(out.shape[0], bool)
+    mask[rows] = True
+    return out, mask
+
+
+def assert_rows_bit_equal(a, b, rows, what=""):
+    """(ids, floats) pairs a and b agree bit for bit on `rows` (the cross-contamination check: no oracle involved)."""
+    (ai, ad), (bi, bd) = a, b
+    assert np.array_equal(ai[rows], bi[rows]), f"{what}: a healthy query's ids changed with its neighbours' poison"
+    assert np.array_equal(ad[rows].view(np.uint32), bd[rows].view(np.uint32)), f"{what}: a healthy query's distances changed with its neighbours' poison"
