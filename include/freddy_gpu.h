@@ -34,7 +34,7 @@ extern "C" {
 #define FREDDY_E_NOMEM (-3)    /* host or device allocation failed */
 #define FREDDY_E_KIND (-4)     /* index handle of the wrong kind for this call */
 #define FREDDY_E_LIMIT (-5)    /* parameter beyond what this build supports (see message): k > 4096, W > 512 probes per round,
-                                * k * pvf > 8192 (or k > 512) in the kNN-join, k * pvf > 4096 in the post verification, K > 32767, d > 1024 for training */
+                                * k * pvf > 8192 (or k > 512) in the kNN-join, k * pvf > 4096 in the post verification, n_cand > 4096 in the approximate analogies, K > 32767, d > 1024 for training */
 
 /* found_rule for freddy_gpu_ivfadc_search */
 #define FREDDY_FOUND_ROWS 0      /* ivfadc_search:       found += rows retrieved  (freddy.c:377) */
@@ -245,6 +245,35 @@ int freddy_gpu_pq_search_pv(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, co
  * them had a vector row (were scored).  NULL pointers are skipped. */
 int freddy_gpu_last_pv_stats(const freddy_gpu_index_t* ann, int64_t* candidates, int64_t* scored);
 
+/* ---- batched approximate analogies: 3CosAdd over the candidates of an approximate search (approx_analogy.h) ----------------
+ * analogy_3cosadd_ivfadc (freddy--0.0.1.sql:1428-1460), analogy_3cosadd_pq (:1317-1346) and, with subset_ids, analogy_3cosadd_in_pq
+ * (:1348-1384) for Q triples of row ids (w1, w2, w3) at once; the reference calls them with n_cand = get_pvf() + 3 and k = 1.
+ * Contract, per triple whose three ids have a row (v1, v2, v3) in `vecs`:
+ *   raw[i] = (v3[i] - v1[i]) + v2[i], both rounded binary32; unit = vec_normalize_bytea(raw): sq += raw[i] * raw[i] in ascending i,
+ *   length = (float)sqrt((double)sq), unit[i] = raw[i] / length (a correctly rounded division);
+ *   L = the list freddy_gpu_ivfadc_search(ivf, unit, 1, n_cand, W, sentinel, found_rule) (freddy_gpu_pq_search(pq, unit, 1, n_cand,
+ *   sentinel, subset_ids, n_subset)) returns -- stage one IS that entry point, every path of it;
+ *   the output row is bit for bit freddy_gpu_exact_search(vecs, raw, 1, k, S) with S = the ids of L that are >= 0, have a row in
+ *   vecs and are none of w1, w2, w3: similarity (the binary32 chain against RAW, not unit) DESC, id ASC, (-1, -inf) beyond its
+ *   rows, and a row of (-1, -inf) for an empty S (never a search of the table).
+ * A triple with an id that has no row in vecs is the SQL's empty join: its row is all (-1, -inf), it is not searched and does not
+ * disturb its neighbours (the other triples are compacted before stage one); a batch of such triples launches nothing.  Nothing
+ * is special-cased: raw == 0 makes unit all NaN and the search does what it does for a NaN query; ids may repeat inside a triple.
+ * Errors, all before any device work: FREDDY_E_ARG for Q < 0, k < 1, n_cand < k, W < 1, a bad found_rule, a bad subset, NULL
+ * buffers with Q > 0; FREDDY_E_LIMIT for n_cand > 4096 (the message names the value); FREDDY_E_KIND for handles of the wrong kinds;
+ * FREDDY_E_ARG for vecs on another device or of another d, and for an ivf handle with replicas.  Q == 0 succeeds and does nothing.
+ * Any Q (passes of triples whose lists hold at most 8 M entries; option "analogy_pass" sets the triples per pass).
+ * analogy_3cosadd_in_ivpq goes through the kNN-join (freddy_gpu_knn_join with the literal k = 4) and has no entry point here. */
+int freddy_gpu_ivfadc_analogy(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const int32_t* triples /*[Q][3] ids w1,w2,w3*/,
+                              int32_t Q, int32_t k, int32_t n_cand, int32_t W, float sentinel, int32_t found_rule,
+                              int32_t* out_ids /*[Q][k]*/, float* out_sim /*[Q][k]*/);
+int freddy_gpu_pq_analogy(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const int32_t* triples, int32_t Q, int32_t k,
+                          int32_t n_cand, float sentinel, const int32_t* subset_ids, int64_t n_subset,
+                          int32_t* out_ids, float* out_sim);
+/* The last approximate-analogy call on this pq / ivf handle: triples that reached stage one, their list entries with id >= 0, and
+ * how many of those had a vector row and were not an input of their triple (were scored).  NULL pointers are skipped. */
+int freddy_gpu_last_approx_analogy_stats(const freddy_gpu_index_t* ann, int64_t* searched, int64_t* candidates, int64_t* scored);
+
 /* ---- next row: grouping_pq ---------------------------------------------------------
  * Body of grouping_pq (freddy.c:1176-1401): for every row of the PQ table (subset_ids == NULL) or of
  * "id IN (subset_ids)" the nearest of G group vectors by ADC distance -- one LUT per group from the PQ
@@ -398,7 +427,8 @@ int freddy_gpu_abi_version(void);
  *                0: the int16 layout), "exact_filter" (exact brute-force kNN as f16-split MFMA filter + exact
  *                refine: -1 = tables of >= 8192 rows and k <= 32, 0 never -- and no fragment copy of a table pinned with it --,
  *                1 always), "exact_join_tile" (queries per workgroup of the exact join's filter: 0 = 128 when Q > 64 and
- *                d <= 320, else 64; 64 = never 128)
+ *                d <= 320, else 64; 64 = never 128), "analogy_pass" (triples per pass of the approximate analogies: 0 = as many as
+ *                keep a pass's lists within 8 M entries)
  *   self-checks (tests):  "check_brackets" (bit 0: the scan keeps and the merge refines EVERY probed row, bit 1: the cell
  *                selection refines every cell, bit 2: exact kNN and the exact join refine every row -- each with its proven bracket compared with
  *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines

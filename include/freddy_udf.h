@@ -31,6 +31,10 @@ typedef struct freddy_group_row { int32_t id; int32_t group_id; } freddy_group_r
 int freddy_session_open(int device, freddy_session_t** out);
 int freddy_session_close(freddy_session_t* s);
 const char* freddy_udf_last_error(void);
+/* The device handle behind a table group, for the diagnostics of include/freddy_gpu.h (freddy_gpu_profile_*, freddy_gpu_last_*):
+ * "pq", "ivfadc", "ivpq" or "vecs" (google_vecs_norm, pinned by the first function that needs it); NULL while it is not pinned.
+ * The session keeps the handle: the caller must not unpin it.  (void*: this header does not include freddy_gpu.h.) */
+void* freddy_session_gpu_index(const freddy_session_t* s, const char* table);
 
 /* ---- tables (what the index_creation scripts insert; rows may come in any order) -------- */
 /* google_vecs_norm (id, vector)                                   vec2database.py:47-58 */
@@ -189,6 +193,14 @@ int knn_batch(freddy_session_t* s, const int32_t* query_ids, int32_t n_query_ids
  *   cluster and round): a caller-supplied sequence makes a run reproducible; once it is used up (or NULL) an
  *   internal generator continues.  cluster_out[i] = 1..k for token i (0: no centroid listed it). */
 int analogy_3cosadd_in_pq(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids, int32_t n_ids, int32_t* result);
+/* The batch forms of the approximate analogies: results[i] = what the single-triple function returns for triples[i] (-1 where the SQL
+ * returns NULL), all n triples in ONE device call (freddy_gpu_ivfadc_analogy / freddy_gpu_pq_analogy, approx_analogy.h) with
+ * n_cand = get_pvf() + 3, k = 1 and the sentinels and W of the single-triple functions -- instead of a search and a host loop over
+ * the candidates per triple.  analogy_3cosadd_in_ivpq goes through the kNN-join with the literal k = 4 and has no batch form. */
+int analogy_3cosadd_pq_batch(freddy_session_t* s, const int32_t* triples /*[n][3]*/, int32_t n, int32_t* results /*[n]*/);
+int analogy_3cosadd_ivfadc_batch(freddy_session_t* s, const int32_t* triples /*[n][3]*/, int32_t n, int32_t* results /*[n]*/);
+int analogy_3cosadd_in_pq_batch(freddy_session_t* s, const int32_t* triples /*[n][3]*/, int32_t n, const int32_t* input_ids, int32_t n_ids,
+                                int32_t* results /*[n]*/);
 int analogy_3cosadd_in_ivpq(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids, int32_t n_ids, int32_t* result);
 int cluster_exact(freddy_session_t* s, const int32_t* token_ids, int32_t n, int32_t k, const double* draws, int32_t n_draws, int32_t* cluster_out);
 int cluster_pq(freddy_session_t* s, const int32_t* token_ids, int32_t n, int32_t k, const double* draws, int32_t n_draws, int32_t* cluster_out);

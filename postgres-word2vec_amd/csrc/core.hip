@@ -248,6 +248,7 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   else if (n == "lut_budget_mb") t.lut_budget_mb = std::max<int64_t>(1, value);
   else if (n == "exact_filter") t.exact_filter = (int)value;
   else if (n == "exact_join_tile") t.exact_join_tile = (int)value;
+  else if (n == "analogy_pass") t.analogy_pass = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
   else if (n == "codes_u8") t.codes_u8 = (int)value;
   else if (n == "running_bound") t.running_bound = (int)value;
   else if (n == "coarse_pieces") t.coarse_pieces = (int)value;

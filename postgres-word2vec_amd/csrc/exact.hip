@@ -1,5 +1,6 @@
 // exact.hip -- pin_vectors, exact brute-force kNN (core_functions.c:67-81, freddy--0.0.1.sql:426-454), the
-// exact analogies on the same handle (freddy--0.0.1.sql:1231-1315; analogy.h) and the post verification of pq / ivf lists against it (pv.h).
+// exact analogies on the same handle (freddy--0.0.1.sql:1231-1315; analogy.h), the post verification of pq / ivf lists against it (pv.h)
+// and the approximate analogies over such lists (approx_analogy.h).
 #include "internal.h"
 
 #include "kernels.h"
@@ -8,6 +9,7 @@
 #include "exact_join.h"
 #include "analogy.h"
 #include "pv.h"
+#include "approx_analogy.h"
 
 // ---------------------------------------------------------------------------------------
 // exact brute-force kNN
@@ -777,19 +779,25 @@ extern "C" int freddy_gpu_last_analogy_stats(const freddy_gpu_index_t* ix, int64
 }
 
 // ---- post verification of pq / ivf result lists (pv.h) -------------------------------------------------------------------
+// The handles of a call that takes a pq / ivf handle and the raw-vector handle it re-ranks against (post verification, approximate
+// analogies); nothing here touches a device.
+static int pv_check_handles(const freddy_gpu_index* ann, int kind, const freddy_gpu_index* vecs, const char* what) {
+  if (!ann || !vecs) return fail(FREDDY_E_ARG, "NULL index");
+  if (ann->kind != kind || vecs->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (!ann->replicas.empty())
+    return fail(FREDDY_E_ARG, "%s does not take a handle with replicas (%d devices): the vectors are pinned on one device", what, 1 + (int)ann->replicas.size());
+  if (vecs->device != ann->device) return fail(FREDDY_E_ARG, "the vectors are pinned on device %d, the index on device %d", vecs->device, ann->device);
+  if (vecs->d != ann->d) return fail(FREDDY_E_ARG, "the vectors have %d dimensions, the index has %d", vecs->d, ann->d);
+  return 0;
+}
+
 // Everything both entry points refuse, in the order of the header's table; nothing here touches a device.
 static int pv_check(const freddy_gpu_index* ann, int kind, const freddy_gpu_index* vecs, const float* queries, int32_t Q, int32_t k, int32_t pvf,
                     const int32_t* out_ids, const float* out_sim) {
   if (Q < 0 || k < 1 || pvf < 1) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, k=%d, pvf=%d)", Q, k, pvf);
   if (Q > 0 && (!queries || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
   if ((int64_t)k * pvf > PV_MAX_CAND) return fail(FREDDY_E_LIMIT, "k * pvf = %lld exceeds this build's limit of %d candidates", (long long)k * pvf, PV_MAX_CAND);
-  if (!ann || !vecs) return fail(FREDDY_E_ARG, "NULL index");
-  if (ann->kind != kind || vecs->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
-  if (!ann->replicas.empty())
-    return fail(FREDDY_E_ARG, "post verification does not take a handle with replicas (%d devices): the vectors are pinned on one device", 1 + (int)ann->replicas.size());
-  if (vecs->device != ann->device) return fail(FREDDY_E_ARG, "the vectors are pinned on device %d, the index on device %d", vecs->device, ann->device);
-  if (vecs->d != ann->d) return fail(FREDDY_E_ARG, "the vectors have %d dimensions, the index has %d", vecs->d, ann->d);
-  return 0;
+  return pv_check_handles(ann, kind, vecs, "post verification");
 }
 
 // Stage one (`search`: the public entry point at k * pvf, writing its lists into the pinned block) and stage two (pv_rerank) for
@@ -819,7 +827,7 @@ static int pv_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const float*
     HIP_TRY(hipSetDevice(ann->device));
     HIP_TRY(hipMemcpyAsync(ann->pv_q.p, qp, sizeof(float) * (size_t)nq * d, hipMemcpyHostToDevice, s));
     PvArgs pa;
-    pa.cand = l_ids; pa.vec_ids = vecs->ids; pa.rows = vecs->coarse; pa.queries = ann->pv_q.as<float>(); pa.out_ids = o_ids; pa.out_sim = o_sim;
+    pa.cand = l_ids; pa.vec_ids = vecs->ids; pa.rows = vecs->coarse; pa.queries = ann->pv_q.as<float>(); pa.exclude = nullptr; pa.out_ids = o_ids; pa.out_sim = o_sim;
     pa.counts = o_cnt; pa.N = vecs->N; pa.n_cand = kc; pa.k = k; pa.d = d; pa.P = P;
     timed_launch(ann, s, "pv_rerank", [&] {
       if (NW == 1) hipLaunchKernelGGL((pv_rerank_kernel<1>), dim3((unsigned)nq), dim3(64), pv_lds_bytes(1, P, d), s, pa);
@@ -862,6 +870,124 @@ extern "C" int freddy_gpu_last_pv_stats(const freddy_gpu_index_t* ann, int64_t* 
   return FREDDY_OK;
 }
 
+// ---- approximate analogies: 3CosAdd over the candidates of pq / ivf lists (approx_analogy.h) ---------------------------------------
+// Everything both entry points refuse, scalars before handles; nothing here touches a device.
+static int aa_check(const freddy_gpu_index* ann, int kind, const freddy_gpu_index* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand,
+                    const int32_t* out_ids, const float* out_sim) {
+  if (Q < 0 || k < 1 || n_cand < k) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, k=%d, n_cand=%d)", Q, k, n_cand);
+  if (Q > 0 && (!triples || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
+  if (n_cand > PV_MAX_CAND) return fail(FREDDY_E_LIMIT, "n_cand = %d exceeds this build's limit of %d candidates", n_cand, PV_MAX_CAND);
+  return pv_check_handles(ann, kind, vecs, "the approximate analogy");
+}
+
+// The triples whose three ids have a row, compacted, in passes that bound the pinned block as pv_search's do: aa_query writes a
+// pass's raw rows to device memory and its unit rows into the pinned block, stage one (`search`: the public entry point at n_cand,
+// reading its queries from that block and writing its lists into it) runs once the kernel has finished, and the re-rank scores the
+// lists against the raw rows without the inputs; the result rows are scattered back to their triples.
+template <class F>
+static int aa_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand, int32_t* out_ids,
+                     float* out_sim, F&& search) {
+  ann->aa_stats[0] = ann->aa_stats[1] = ann->aa_stats[2] = 0;
+  for (size_t i = 0; i < (size_t)Q * k; ++i) { out_ids[i] = -1; out_sim[i] = -HUGE_VALF; }
+  // the INNER JOINs: a triple with an unknown id has no rows at all; the others, compacted
+  // (serial ids -- strictly ascending and last - first + 1 of them -- make the row a subtraction: 3 Q binary searches over a table of
+  // millions of ids otherwise cost more than the device work of a batch)
+  const std::vector<int32_t>& hid = vecs->h_ids;
+  const bool serial = !hid.empty() && (int64_t)hid.back() - hid.front() + 1 == (int64_t)hid.size();
+  auto row = [&](int32_t id) -> int32_t {
+    if (serial) return id >= hid.front() && id <= hid.back() ? id - hid.front() : -1;
+    return row_of(hid, id);
+  };
+  std::vector<int32_t> live, rows3, ids3;
+  live.reserve((size_t)Q); rows3.reserve((size_t)Q * 3); ids3.reserve((size_t)Q * 3);
+  for (int32_t q = 0; q < Q; ++q) {
+    const int32_t* t = triples + (size_t)q * 3;
+    int32_t r[3];
+    bool ok = true;
+    for (int m = 0; m < 3 && ok; ++m) ok = (r[m] = row(t[m])) >= 0;
+    if (!ok) continue;
+    live.push_back(q);
+    rows3.insert(rows3.end(), r, r + 3);
+    ids3.insert(ids3.end(), t, t + 3);
+  }
+  const int na = (int)live.size();
+  if (na == 0) return FREDDY_OK;   // (before any launch)
+  const int P = pv_pad(n_cand), NW = P == 64 ? 1 : 4, d = ann->d;
+  int Qc = (int)std::min<int64_t>(na, std::max<int64_t>(1, ((int64_t)8 << 20) / n_cand));   // triples per pass: lists of at most 8 M entries
+  if (ann->tune.analogy_pass > 0) Qc = std::min(Qc, ann->tune.analogy_pass);
+  HIP_TRY(hipSetDevice(ann->device));
+  // the pinned block: [unit rows, padded to 16 bytes][stage one's lists][the result lists][per-triple counts][input rows][input ids]
+  const size_t n_unit = ((size_t)Qc * d + 3) / 4 * 4, n_list = (size_t)Qc * n_cand, n_out = (size_t)Qc * k;
+  if (ann->pv_io.ensure(4 * (n_unit + 2 * n_list + 2 * n_out + 2 * (size_t)Qc + 6 * (size_t)Qc)) || ann->pv_q.ensure(sizeof(float) * (size_t)Qc * d))
+    return fail(FREDDY_E_NOMEM, "approximate analogy: staging allocation failed");
+  float* const unit = ann->pv_io.as<float>();
+  int32_t* const l_ids = reinterpret_cast<int32_t*>(unit + n_unit);
+  float* const l_dist = reinterpret_cast<float*>(l_ids + n_list);
+  int32_t* const o_ids = l_ids + 2 * n_list;
+  float* const o_sim = reinterpret_cast<float*>(o_ids + n_out);
+  int32_t* const o_cnt = o_ids + 2 * n_out;
+  int32_t* const p_rows = o_cnt + 2 * (size_t)Qc;
+  int32_t* const p_excl = p_rows + 3 * (size_t)Qc;
+  hipStream_t s = ann->stream;
+  for (int q0 = 0; q0 < na; q0 += Qc) {
+    const int nq = std::min(Qc, na - q0);
+    memcpy(p_rows, rows3.data() + (size_t)q0 * 3, sizeof(int32_t) * 3 * (size_t)nq);
+    memcpy(p_excl, ids3.data() + (size_t)q0 * 3, sizeof(int32_t) * 3 * (size_t)nq);
+    AaQueryArgs qa;
+    qa.rows = vecs->coarse; qa.in_rows = p_rows; qa.raw = ann->pv_q.as<float>(); qa.unit = unit; qa.d = d;
+    timed_launch(ann, s, "aa_query", [&] { hipLaunchKernelGGL(aa_query_kernel, dim3((unsigned)nq), dim3(64), aa_query_lds(d), s, qa); });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));   // (stage one reads the unit rows on streams of its own)
+    if (int rc = search(unit, nq, l_ids, l_dist)) return rc;
+    HIP_TRY(hipSetDevice(ann->device));
+    PvArgs pa;
+    pa.cand = l_ids; pa.vec_ids = vecs->ids; pa.rows = vecs->coarse; pa.queries = ann->pv_q.as<float>(); pa.exclude = p_excl; pa.out_ids = o_ids;
+    pa.out_sim = o_sim; pa.counts = o_cnt; pa.N = vecs->N; pa.n_cand = n_cand; pa.k = k; pa.d = d; pa.P = P;
+    timed_launch(ann, s, "aa_rerank", [&] {
+      if (NW == 1) hipLaunchKernelGGL((aa_rerank_kernel<1>), dim3((unsigned)nq), dim3(64), pv_lds_bytes(1, P, d), s, pa);
+      else hipLaunchKernelGGL((aa_rerank_kernel<4>), dim3((unsigned)nq), dim3(256), pv_lds_bytes(4, P, d), s, pa);
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < nq; ++q) {
+      memcpy(out_ids + (size_t)live[(size_t)q0 + q] * k, o_ids + (size_t)q * k, sizeof(int32_t) * k);
+      memcpy(out_sim + (size_t)live[(size_t)q0 + q] * k, o_sim + (size_t)q * k, sizeof(float) * k);
+      ann->aa_stats[1] += o_cnt[2 * q]; ann->aa_stats[2] += o_cnt[2 * q + 1];
+    }
+    ann->aa_stats[0] += nq;
+  }
+  return FREDDY_OK;
+}
+
+extern "C" int freddy_gpu_ivfadc_analogy(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand,
+                                         int32_t W, float sentinel, int32_t found_rule, int32_t* out_ids, float* out_sim) {
+  if (W <= 0) return fail(FREDDY_E_ARG, "W must be positive");
+  if (found_rule < 0 || found_rule > 2 || (found_rule == FREDDY_FOUND_BATCH_UDF && W != 1))
+    return fail(FREDDY_E_ARG, "bad found_rule (FREDDY_FOUND_BATCH_UDF needs W == 1)");
+  if (int rc = aa_check(ivf, KIND_IVF, vecs, triples, Q, k, n_cand, out_ids, out_sim)) return rc;
+  return aa_search(ivf, vecs, triples, Q, k, n_cand, out_ids, out_sim, [&](const float* qp, int nq, int32_t* l_ids, float* l_dist) {
+    return freddy_gpu_ivfadc_search(ivf, qp, nq, n_cand, W, sentinel, found_rule, l_ids, l_dist);
+  });
+}
+
+extern "C" int freddy_gpu_pq_analogy(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand,
+                                     float sentinel, const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_sim) {
+  if (n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad subset (n_subset=%lld)", (long long)n_subset);
+  if (int rc = aa_check(pq, KIND_PQ, vecs, triples, Q, k, n_cand, out_ids, out_sim)) return rc;
+  return aa_search(pq, vecs, triples, Q, k, n_cand, out_ids, out_sim, [&](const float* qp, int nq, int32_t* l_ids, float* l_dist) {
+    return freddy_gpu_pq_search(pq, qp, nq, n_cand, sentinel, subset_ids, n_subset, l_ids, l_dist);
+  });
+}
+
+extern "C" int freddy_gpu_last_approx_analogy_stats(const freddy_gpu_index_t* ann, int64_t* searched, int64_t* candidates, int64_t* scored) {
+  if (!ann) return fail(FREDDY_E_ARG, "NULL index");
+  if (ann->kind != KIND_PQ && ann->kind != KIND_IVF) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (searched) *searched = ann->aa_stats[0];
+  if (candidates) *candidates = ann->aa_stats[1];
+  if (scored) *scored = ann->aa_stats[2];
+  return FREDDY_OK;
+}
+
 // The kernels of this unit that want more than the default 64 KiB of dynamic LDS.
 std::vector<LdsLimit> lds_limits_exact() {
   const int b = (int)AN_MAX_LDS;
@@ -876,5 +1002,5 @@ std::vector<LdsLimit> lds_limits_exact() {
           &exact_scan_kernel<1, 8>, &exact_scan_kernel<2, 8>, &exact_scan_kernel<4, 8>, &exact_scan_kernel<8, 8>, &exact_scan_kernel<16, 8>,
           &exact_scan_kernel<16, 8, true>,
           // (4096 keys + four tiles + the query: 66 KiB at d = 300, 83 KiB at EX_MAX_D; the kernel has static LDS beside the dynamic)
-          {&pv_rerank_kernel<4>, (int)pv_lds_bytes(4, PV_MAX_CAND, EX_MAX_D)}};
+          {&pv_rerank_kernel<4>, (int)pv_lds_bytes(4, PV_MAX_CAND, EX_MAX_D)}, {&aa_rerank_kernel<4>, (int)pv_lds_bytes(4, PV_MAX_CAND, EX_MAX_D)}};
 }

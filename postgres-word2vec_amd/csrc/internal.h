@@ -6,7 +6,7 @@
 //   pq.hip      pq_search (+ subsets, pseudo-list batches, one-query launch), grouping_pq
 //   join.hip    pin_ivpq, knn_join (join.h: overview; join_kernels.h and join_traverse.h the kernels, join_host.h the host heap, join_run.h the run
 //               record of a call and its stages)
-//   exact.hip   pin_vectors, exact kNN, the exact join, analogies, post verification of pq / ivf lists (pv.h)
+//   exact.hip   pin_vectors, exact kNN, the exact join, analogies, post verification of pq / ivf lists (pv.h), approximate analogies (approx_analogy.h)
 //   build.hip   encode, insert_quantize, k-means
 // Kernel headers are included by the unit that launches them (kernels shared by two units are static or templates).
 #pragma once
@@ -77,6 +77,7 @@ struct Tuning {
   int codes_u8 = 1;            // FREDDY_GPU_CODES_U8: K <= 256: the integer-slab scans read one byte per code (packed8, 16 instead of 28 B per row) -- 1: the scan with the whole entry's slab in LDS (fused8.h), 2: the six-phase scan (fused5.h); 0 = the int16 layout
   int exact_filter = -1;       // FREDDY_GPU_EXACT_FILTER: exact kNN as MFMA filter + exact refine (exact2.h): -1 auto (tables of >= 8192 rows, k <= 32), 0 never, 1 always
   int exact_join_tile = 0;     // option exact_join_tile: queries per workgroup of the exact join's filter (exact_join.h): 0 auto (128 when Q > 64 and d <= 320), 64
+  int analogy_pass = 0;        // option analogy_pass: triples per pass of the approximate analogies (approx_analogy.h): 0 = pv_search's bound (lists of at most 8 M entries)
   // -- self-checks (tests): bit 0 = the scan keeps every row and the merge refines every row (every probed row's bracket is checked),
   //    bit 1 = the cell selection refines every cell, bit 2 = exact kNN refines every row
   int check_brackets = 0;
@@ -276,6 +277,9 @@ struct freddy_gpu_index {
   PinnedBuf pv_io;
   DevBuf pv_q;
   int64_t pv_stats[2] = {0, 0};
+  // the last approximate-analogy call on a pq / ivf handle (freddy_gpu_last_approx_analogy_stats; it shares pv_io / pv_q): triples
+  // searched, their candidates, candidates scored
+  int64_t aa_stats[3] = {0, 0, 0};
 };
 
 template <class F>

@@ -3,7 +3,8 @@
 // and the first k kept.  Stage one is the public search itself (freddy_gpu_ivfadc_search / freddy_gpu_pq_search at k * pvf, every
 // path of it); this header is stage two: one workgroup per query
 //   1. resolves the query's candidate ids to rows of the vector handle (binary search over its ascending device ids; the
-//      (-1, sentinel) fillers and ids without a row drop out),
+//      (-1, sentinel) fillers and ids without a row drop out -- and, for the approximate analogies of approx_analogy.h, the three
+//      ids of PvArgs::exclude),
 //   2. scores the rows: similarity = the binary32 chain "scalar += v1[i] * v2[i]", i ascending (core_functions.c:67-81), one lane
 //      per candidate.  A wave takes 64 candidates at a time and PV_DCH dimensions of them per step: the 64 row pieces are read
 //      from the row-major copy with 16-byte loads (8 consecutive lanes = 128 contiguous bytes of one row), stored transposed into
@@ -37,9 +38,10 @@ struct PvArgs {
   const int32_t* vec_ids;    // [N] ascending ids of the vector handle
   const float* rows;         // [N][d] its row-major copy
   const float* queries;      // [Q][d]
+  const int32_t* exclude;    // aa_rerank_kernel only: [Q][3] ids that are no candidates of their query (approx_analogy.h: the analogy's inputs)
   int32_t* out_ids;          // [Q][k]
   float* out_sim;            // [Q][k]
-  int32_t* counts;           // [Q][2]: candidates with id >= 0, and how many of them have a row
+  int32_t* counts;           // [Q][2]: candidates with id >= 0, and how many of them have a row (and are not excluded)
   int64_t N;
   int n_cand, k, d, P;       // P: n_cand padded to a power of two >= 64
 };
@@ -59,27 +61,35 @@ __device__ __forceinline__ void pv_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// NW = 1: up to 64 candidates, the sort is wave_sort64; NW = 4: up to 4096, a bitonic sort in LDS
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void pv_rerank_kernel(PvArgs a) {
+// NW = 1: up to 64 candidates, the sort is wave_sort64; NW = 4: up to 4096, a bitonic sort in LDS.  EX: PvArgs::exclude is read
+// (a compile-time switch, so that the post-verification kernels below stay instruction for instruction what they were before the
+// exclusion came: the three ids and their pointer cost scalar registers, and tests/golden/pv_codegen_ceilings.json pins those).
+template <int NW, bool EX>
+__device__ __forceinline__ void pv_rerank_body(const PvArgs& a) {
   constexpr int T = NW * 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char pv_smem[];
   u64* keys = reinterpret_cast<u64*>(pv_smem);                              // [P]: the row of every candidate, then its key
   float* tiles = reinterpret_cast<float*>(keys + a.P);                      // [NW][PV_DCH][PV_STRIDE]
   float* qs = tiles + NW * PV_TILE;                                         // [d]
   __shared__ int sh_cnt[2];
+  __shared__ int32_t sh_ex[3];
   const int q = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int d = a.d, P = a.P;
   if (tid < 2) sh_cnt[tid] = 0;
+  if constexpr (EX) {
+    if (tid < 3) sh_ex[tid] = a.exclude[(size_t)q * 3 + tid];
+  }
   __syncthreads();
   // 1. ids -> rows
+  int32_t ex0 = -1, ex1 = -1, ex2 = -1;   // (-1: no candidate that gets this far is negative)
+  if constexpr (EX) { ex0 = sh_ex[0]; ex1 = sh_ex[1]; ex2 = sh_ex[2]; }
   int n_ids = 0, n_rows = 0;
   for (int i = tid; i < P; i += T) {
     int32_t row = -1;
     if (i < a.n_cand) {
       const int32_t id = a.cand[(size_t)q * a.n_cand + i];
-      if (id >= 0) {
-        ++n_ids;
+      if (id >= 0) ++n_ids;
+      if (id >= 0 && id != ex0 && id != ex1 && id != ex2) {
         int64_t lo = 0, hi = a.N;
         while (lo < hi) {
           const int64_t mid = (lo + hi) >> 1;
@@ -175,5 +185,11 @@ __global__ __launch_bounds__(NW * 64) void pv_rerank_kernel(PvArgs a) {
   }
   if (tid < 2) a.counts[(size_t)q * 2 + tid] = sh_cnt[tid];
 }
+
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void pv_rerank_kernel(PvArgs a) { pv_rerank_body<NW, false>(a); }
+// the re-rank of the approximate analogies (approx_analogy.h): a.exclude[q] holds the three input ids of query q
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void aa_rerank_kernel(PvArgs a) { pv_rerank_body<NW, true>(a); }
 
 }  // namespace freddy

@@ -30,6 +30,7 @@ EXPORTS = [
     "freddy_gpu_last_track_sized", "freddy_gpu_abi_version", "freddy_gpu_exact_analogy",
     "freddy_gpu_last_analogy_stats", "freddy_gpu_exact_join", "freddy_gpu_last_exact_join_stats",
     "freddy_gpu_ivfadc_search_pv", "freddy_gpu_pq_search_pv", "freddy_gpu_last_pv_stats",
+    "freddy_gpu_ivfadc_analogy", "freddy_gpu_pq_analogy", "freddy_gpu_last_approx_analogy_stats",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 
@@ -121,7 +122,12 @@ def load(path=None, optional=()):
                                                          C.c_int32, C.c_void_p, C.c_void_p]),
                         ("freddy_gpu_pq_search_pv", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                                      C.c_int64, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_last_pv_stats", [C.c_void_p, C.c_void_p, C.c_void_p])):
+                        ("freddy_gpu_last_pv_stats", [C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_ivfadc_analogy", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                                       C.c_int32, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_pq_analogy", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                                   C.c_int64, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_last_approx_analogy_stats", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
         if name in optional and not hasattr(lib, name):
             continue
         getattr(lib, name).argtypes = types
@@ -235,6 +241,13 @@ class _Index:
         _check(self.lib.freddy_gpu_last_pv_stats(self.h, *(C.byref(x) for x in v)))
         return {"candidates": v[0].value, "scored": v[1].value}
 
+    def last_approx_analogy_stats(self):
+        """The last analogy() call on this pq / ivf handle (freddy_gpu_last_approx_analogy_stats): triples that reached stage one,
+        their list entries with id >= 0, and how many of those had a vector row and were not an input of their triple."""
+        v = [C.c_int64(0) for _ in range(3)]
+        _check(self.lib.freddy_gpu_last_approx_analogy_stats(self.h, *(C.byref(x) for x in v)))
+        return {"searched": v[0].value, "candidates": v[1].value, "scored": v[2].value}
+
 
 class PQIndex(_Index):
     """pq_codebook + pq_quantization pinned in HBM."""
@@ -270,6 +283,19 @@ class PQIndex(_Index):
         sub = None if subset_ids is None else _i32(subset_ids)
         _check(self.lib.freddy_gpu_pq_search_pv(self.h, vecs.h, _p(qs), Q, k, pvf, C.c_float(sentinel), _p(sub),
                                                 0 if sub is None else sub.size, _p(out_i), _p(out_s)))
+        return out_i, out_s
+
+    def analogy(self, vecs, triples, k=1, n_cand=23, sentinel=100.0, subset_ids=None):
+        """Approximate 3CosAdd analogies (freddy_gpu_pq_analogy): triples [Q][3] of row ids (w1, w2, w3) -> (ids[Q,k], similarity[Q,k]);
+        per triple bit for bit vecs.search(v3 - v1 + v2, k, subset_ids=<the n_cand candidates of pq_search for the normalised sum,
+        without the inputs>); (-1, -inf) where there is no row or an input id has no vector.  subset_ids: analogy_3cosadd_in_pq."""
+        t = _i32(triples).reshape(-1, 3)
+        Q = t.shape[0]
+        out_i = np.empty((Q, k), np.int32)
+        out_s = np.empty((Q, k), np.float32)
+        sub = None if subset_ids is None else _i32(subset_ids)
+        _check(self.lib.freddy_gpu_pq_analogy(self.h, vecs.h, _p(t), Q, k, n_cand, C.c_float(sentinel), _p(sub),
+                                              0 if sub is None else sub.size, _p(out_i), _p(out_s)))
         return out_i, out_s
 
     def bind_search(self, queries, k, sentinel=100.0):
@@ -412,6 +438,18 @@ class IVFIndex(_Index):
         out_s = np.empty((Q, k), np.float32)
         _check(self.lib.freddy_gpu_ivfadc_search_pv(self.h, vecs.h, _p(qs), Q, k, pvf, W, C.c_float(sentinel), found_rule,
                                                     _p(out_i), _p(out_s)))
+        return out_i, out_s
+
+    def analogy(self, vecs, triples, k=1, n_cand=23, W=3, sentinel=1000.0, found_rule=FOUND_ROWS):
+        """Approximate 3CosAdd analogies (freddy_gpu_ivfadc_analogy): triples [Q][3] of row ids (w1, w2, w3) -> (ids[Q,k],
+        similarity[Q,k]); per triple bit for bit vecs.search(v3 - v1 + v2, k, subset_ids=<the n_cand candidates of ivfadc_search for
+        the normalised sum, without the inputs>); (-1, -inf) where there is no row or an input id has no vector."""
+        t = _i32(triples).reshape(-1, 3)
+        Q = t.shape[0]
+        out_i = np.empty((Q, k), np.int32)
+        out_s = np.empty((Q, k), np.float32)
+        _check(self.lib.freddy_gpu_ivfadc_analogy(self.h, vecs.h, _p(t), Q, k, n_cand, W, C.c_float(sentinel), found_rule,
+                                                  _p(out_i), _p(out_s)))
         return out_i, out_s
 
     def search_dev(self, d_queries_ptr, Q, k, W, sentinel, found_rule, d_out_ids_ptr, d_out_dist_ptr,

@@ -42,6 +42,8 @@ def load():
         _lib.freddy_get_analogy_in_function.restype = C.c_char_p
         _lib.freddy_get_groups_function.restype = C.c_char_p
         _lib.freddy_get_knn_batch_function.restype = C.c_char_p
+        _lib.freddy_session_gpu_index.restype = C.c_void_p
+        _lib.freddy_session_gpu_index.argtypes = [C.c_void_p, C.c_char_p]
     return _lib
 
 
@@ -289,6 +291,31 @@ class Session:
         r, ids = C.c_int32(-1), _i32(input_ids)
         self._check(self.lib.analogy_3cosadd_in_ivpq(self.h, int(id1), int(id2), int(id3), _p(ids), ids.size, C.byref(r)))
         return r.value
+
+    # the batch forms: triples [n][3] of row ids -> int32[n], element i = the single-triple function's result for triples[i]; one device call
+    def _analogy_batch(self, fn, triples, *more):
+        t = _i32(triples).reshape(-1, 3)
+        out = np.empty(t.shape[0], np.int32)
+        self._check(fn(self.h, _p(t), t.shape[0], *more, _p(out)))
+        return out
+
+    def analogy_3cosadd_pq_batch(self, triples): return self._analogy_batch(self.lib.analogy_3cosadd_pq_batch, triples)
+    def analogy_3cosadd_ivfadc_batch(self, triples): return self._analogy_batch(self.lib.analogy_3cosadd_ivfadc_batch, triples)
+
+    def analogy_3cosadd_in_pq_batch(self, triples, input_ids):
+        ids = _i32(input_ids)
+        return self._analogy_batch(self.lib.analogy_3cosadd_in_pq_batch, triples, _p(ids), ids.size)
+
+    def gpu_index(self, table):
+        """The pinned handle behind "pq", "ivfadc", "ivpq" or "vecs" as a borrowed gpu index object (profile_enable / profile_read /
+        last_*_stats); None while that table is not pinned.  The session keeps the handle."""
+        h = self.lib.freddy_session_gpu_index(self.h, table.encode())
+        if not h:
+            return None
+        ix = _gpu._Index()
+        ix.h = C.c_void_p(h)
+        ix.close = lambda: None
+        return ix
 
     # exact analogies and the dispatchers (freddy--0.0.1.sql:1231-1315, 269-297); -1 where the SQL returns NULL
     def _analogy3(self, fn, id1, id2, id3):

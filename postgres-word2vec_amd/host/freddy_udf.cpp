@@ -111,6 +111,12 @@ int freddy_session_open(int device, freddy_session_t** out) {
   return 0;
 }
 
+void* freddy_session_gpu_index(const freddy_session_t* s, const char* table) {
+  if (!s || !table) return nullptr;
+  const std::string t(table);
+  return t == "pq" ? s->pq : t == "ivfadc" ? s->ivf : t == "ivpq" ? s->ivpq : t == "vecs" ? s->vecs : nullptr;
+}
+
 int freddy_session_close(freddy_session_t* s) {
   if (!s) return 0;
   if (s->pq) freddy_gpu_unpin(s->pq);
@@ -989,6 +995,34 @@ int analogy_3cosadd_in_pq(freddy_session_t* s, int32_t id1, int32_t id2, int32_t
 }
 int analogy_3cosadd_in_ivpq(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids, int32_t n_ids, int32_t* result) {
   return analogy_in_common(s, true, id1, id2, id3, input_ids, n_ids, result);
+}
+
+// ---- the batch forms of analogy_3cosadd_pq / _ivfadc / _in_pq: ONE device call for n triples (approx_analogy.h) instead of a search
+// and analogy_common's host loop per triple; the arguments are the ones analogy_common / analogy_in_common pass
+static int analogy_batch_common(freddy_session_t* s, bool ivf, bool in, const int32_t* triples, int32_t n, const int32_t* input_ids, int32_t n_ids,
+                                int32_t* results) {
+  if (!s || n < 0 || (n > 0 && (!triples || !results)) || n_ids < 0 || (n_ids > 0 && !input_ids)) return fail(-1, "bad argument");
+  if (ivf ? !s->ivf : !s->pq) return fail(-1, ivf ? "coarse_quantization / residual_codebook / fine_quantization are not loaded"
+                                                  : "pq_quantization / pq_codebook are not loaded");
+  if (s->norm_ids.empty() || s->d != (ivf ? s->ivf_d : s->pq_d)) return fail(-1, "google_vecs_norm is not loaded");
+  if (n == 0) return 0;
+  if (int rc = ensure_vecs(s)) return rc;
+  const int n_cand = s->pvf + 3;
+  std::vector<float> sim((size_t)n);
+  const int32_t none = -1;   // (an empty input set is an empty set, not "the whole table")
+  const int rc = ivf  ? freddy_gpu_ivfadc_analogy(s->ivf, s->vecs, triples, n, 1, n_cand, s->w, 1000.0f, FREDDY_FOUND_ROWS, results, sim.data())
+                 : in ? freddy_gpu_pq_analogy(s->pq, s->vecs, triples, n, 1, n_cand, 1000.0f, n_ids ? input_ids : &none, n_ids ? n_ids : 1, results, sim.data())
+                      : freddy_gpu_pq_analogy(s->pq, s->vecs, triples, n, 1, n_cand, 100.0f, nullptr, 0, results, sim.data());
+  return rc ? gpu_fail(rc) : 0;
+}
+int analogy_3cosadd_pq_batch(freddy_session_t* s, const int32_t* triples, int32_t n, int32_t* results) {
+  return analogy_batch_common(s, false, false, triples, n, nullptr, 0, results);
+}
+int analogy_3cosadd_ivfadc_batch(freddy_session_t* s, const int32_t* triples, int32_t n, int32_t* results) {
+  return analogy_batch_common(s, true, false, triples, n, nullptr, 0, results);
+}
+int analogy_3cosadd_in_pq_batch(freddy_session_t* s, const int32_t* triples, int32_t n, const int32_t* input_ids, int32_t n_ids, int32_t* results) {
+  return analogy_batch_common(s, false, true, triples, n, input_ids, n_ids, results);
 }
 
 // ---- exact analogies and the dispatchers      freddy--0.0.1.sql:1231-1315, 269-297 --------------------------------
