@@ -1,12 +1,11 @@
 /*
  * freddy_oracle.c -- CPU ORACLE (test infrastructure only; see freddy_oracle.h).
  *
- * PARITY UNPINNED: restated from reading the reference, never checked against a run
- * of the reference itself (its sources need PostgreSQL headers that are absent here)
- * nor against upstream golden vectors (upstream has none).
+ * Restated from reading the reference and pinned to a run of the reference's own C code by
+ * tests/test_ref_pin_cpu.py (oracle/ref/); upstream has no golden vectors.
  *
  * Every function cites the reference lines it restates; paths are relative to
- * /root/reference/freddy_extension/.  Compile with:  gcc -O2 -ffp-contract=off -fopenmp
+ * the reference's freddy_extension/.  Compile with:  gcc -O2 -ffp-contract=off -fopenmp
  * (no -march=native, no -ffast-math: mirrors the PGXS default flags of the
  * reference's Makefile, so there is no FMA contraction and no reassociation).
  */

@@ -5,14 +5,11 @@
  * and bench.py's cpu_baseline leg may load it.  The product path (libfreddy_gpu.so)
  * never links, loads or calls anything in oracle/.
  *
- * PARITY UNPINNED: the reference (guenthermi/postgres-word2vec) ships no tests, no
- * golden vectors and no fixtures for this path, and its C sources cannot be built in
- * this image (every file includes PostgreSQL server headers -- postgres.h, fmgr.h,
- * funcapi.h, executor/spi.h, utils/array.h -- that are absent, and writing stand-ins
- * for them is not allowed).  This oracle is therefore a from-scratch restatement of
- * the reference algorithm, each function citing the reference file:line it follows
- * (paths relative to /root/reference/freddy_extension/), checked by hand-derived
- * known-answer tests and brute-force property tests only.
+ * The reference (guenthermi/postgres-word2vec) ships no tests, no golden vectors and no fixtures for this path.
+ * This oracle is a from-scratch restatement of the reference algorithm, each function citing the reference
+ * file:line it follows (paths relative to the reference's freddy_extension/).  It is pinned to the reference's own
+ * C code: oracle/ref/ compiles that code beside this file and tests/test_ref_pin_cpu.py compares the two bit for bit
+ * (DESIGN.md section 2); hand-derived known-answer tests and brute-force property tests hold it as well.
  *
  * Arithmetic contract (reference is built by PGXS with default flags, x86-64 SSE2,
  * no -ffast-math, no FMA): every float operation below is a separately rounded

@@ -1,8 +1,8 @@
 """ctypes binding of the CPU oracle (oracle/libfreddy_oracle.so).
 
 TEST INFRASTRUCTURE ONLY -- may be imported by tests/, __graft_entry__.smoke() and
-bench.py's cpu_baseline leg, never by the product package.  PARITY UNPINNED (see
-freddy_oracle.h): the oracle restates the reference, it was never run against it.
+bench.py's cpu_baseline leg, never by the product package.  The oracle restates the reference;
+tests/test_ref_pin_cpu.py pins it to the reference's own C code (oracle/ref.py).
 """
 import ctypes as C
 import os
@@ -134,6 +134,16 @@ class Oracle:
         maxd = np.array([sentinel], np.float32)
         for dd, ii in zip(np.asarray(dists, np.float32), np.asarray(ids, np.int32)):
             self.lib.fo_offer(_p(tk), k, _p(maxd), C.c_float(float(dd)), int(ii))
+        return tk
+
+    def postverify(self, q, k, cand_ids, cand_vecs, sentinel):
+        """postverify of one query over its candidate buffer (id -1 = hole), from a list of sentinels."""
+        q, ci, cv = _f32(q), _i32(cand_ids), _f32(cand_vecs)
+        tk = np.empty(k, ENTRY)
+        self.lib.fo_topk_init(_p(tk), k, C.c_float(sentinel))
+        ptrs = (C.c_void_p * max(ci.size, 1))(*[cv[j].ctypes.data for j in range(ci.size)])
+        self.lib.fo_postverify.restype = None
+        self.lib.fo_postverify(_p(q), C.c_int(q.size), C.c_int(k), C.c_int(ci.size), _p(ci), ptrs, C.c_float(sentinel), _p(tk))
         return tk
 
     def cosine_similarity_bytea(self, a, b):

@@ -1,8 +1,8 @@
 """Regenerates tests/golden/freddy_small.npz.
 
-The reference ships no golden vectors and cannot be run here, so these vectors
-do NOT pin the oracle to the reference.  They are inputs plus the ORACLE's outputs at the time of
-writing: a regression pin for both implementations (a compiler flag that lets an FMA in, a changed tie
+The reference ships no golden vectors.  These are inputs plus the ORACLE's outputs at the time of writing; the
+oracle itself is pinned to the reference's C code by tests/test_ref_pin_cpu.py.  They are
+a regression pin for both implementations (a compiler flag that lets an FMA in, a changed tie
 rule or summation order shows up as a mismatch against committed data, on the CPU and on the GPU box).
 Inputs are stored, not re-derived, so no RNG or library version is part of the contract.
 

@@ -43,8 +43,13 @@ def test_product_never_references_the_oracle():
             if f.endswith((".py", ".h", ".hip", ".cpp", ".c")):
                 txt = open(os.path.join(base, f), errors="ignore").read()
                 assert "freddy_oracle" not in txt and "from oracle" not in txt and "import oracle" not in txt, f
+                # nor the reference build beside the oracle: the directory `_ref` as a name of its own (merge_refine_kernel and
+                # its like are the product's), the library, the driver's prefix
+                assert not re.search(r"(?<![A-Za-z0-9])_ref(?![A-Za-z0-9_])", txt) and "libfreddy_ref" not in txt, f
+                assert "ref_driver" not in txt and "pgshim" not in txt, f
     so = open(os.path.join(pkg, "libfreddy_gpu.so"), "rb").read()
     assert b"fo_sqdist" not in so and b"libfreddy_oracle" not in so
+    assert b"libfreddy_ref" not in so and b"fr_sqdist" not in so and b"pgshim" not in so
 
 
 def test_host_mirror_exports_every_declared_symbol():

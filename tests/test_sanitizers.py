@@ -47,6 +47,19 @@ def test_oracle_under_asan_and_ubsan():
     assert " passed" in cp.stdout
 
 
+def test_reference_stand_in_runtime_under_asan_and_ubsan():
+    """oracle/ref/pgshim_rt.c and ref_driver.c (the in-memory SPI, the arena, the SRF loop, the error trap) under ASan + UBSan,
+    the reference's files beside them under ASan: tests/test_ref_pin_cpu.py re-run against that build."""
+    from oracle import ref as R
+    if not R.tree_present():
+        pytest.skip("the reference tree is not here: nothing to compile the stand-in runtime against")
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "asan", "ref-asan"])
+    cp = _run_under_asan(["tests/test_ref_pin_cpu.py"],
+                         {"FREDDY_ORACLE_SO": os.path.join(ROOT, "oracle", "_asan", "libfreddy_oracle_asan.so"),
+                          "FREDDY_REF_SO": os.path.join(ROOT, "oracle", "_asan", "libfreddy_ref_asan.so")})
+    assert cp.returncode == 0 and " passed" in cp.stdout and "failed" not in cp.stdout and "skipped" not in cp.stdout
+
+
 def test_pg_pure_under_asan_and_ubsan():
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "asan"])
     so = os.path.join(ROOT, "oracle", "_asan", "libfreddy_oracle_asan.so")
