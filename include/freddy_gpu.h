@@ -34,7 +34,7 @@ extern "C" {
 #define FREDDY_E_NOMEM (-3)    /* host or device allocation failed */
 #define FREDDY_E_KIND (-4)     /* index handle of the wrong kind for this call */
 #define FREDDY_E_LIMIT (-5)    /* parameter beyond what this build supports (see message): k > 4096, W > 512 probes per round,
-                                * k * pvf > 8192 (or k > 512) in the kNN-join, k * pvf > 4096 in the post verification, n_cand > 4096 in the approximate analogies, K > 32767, d > 1024 for training */
+                                * k * pvf > 8192 (or k > 512) in the kNN-join, k * pvf > 4096 in the post verification, n_cand > 4096 in the approximate analogies, Q > 65536 in the assign calls, K > 32767, d > 1024 for training */
 
 /* found_rule for freddy_gpu_ivfadc_search */
 #define FREDDY_FOUND_ROWS 0      /* ivfadc_search:       found += rows retrieved  (freddy.c:377) */
@@ -219,6 +219,39 @@ int freddy_gpu_exact_join(freddy_gpu_index_t* vecs, const float* queries /*[Q][d
  * answered the call), the candidates it refined (summed over the queries it answered), and the queries answered again on the
  * all-exact path because their candidate buffer overflowed.  NULL pointers are skipped. */
 int freddy_gpu_last_exact_join_stats(const freddy_gpu_index_t* vecs, int64_t* filter_queries, int64_t* candidates, int64_t* redone_queries);
+
+/* ---- the assignment step of the clustering functions (assign.h) ---------------------------------------------------------
+ * generic_cluster (freddy--0.0.1.sql:1086-1170; cluster_exact :1172-1183, cluster_pq :1198-1209) sends every token to the centroid
+ * that lists it with the highest similarity (:1115-1127): it asks knn_search_in_batch (:480-501) resp. knn_in_pq_batch (:846-867
+ * over pq_search_in_batch :386-387) for ALL n tokens per centroid, orders the kc * n rows by similarity DESC and keeps the first
+ * row of every token.  These two calls return what that keeps, for any number of targets: per target the first query under
+ * "similarity DESC, query index ASC", i.e. the lists of freddy_gpu_exact_join / freddy_gpu_pq_search at k = n_targets reduced per
+ * target -- without the lists and without their k <= 4096.
+ * Outputs are POSITIONAL: slot i answers target_ids[i]; a duplicated id gets its answer in every slot (the INNER JOIN of the
+ * tokens with the rows, :1119).
+ * freddy_gpu_exact_assign, for a target with a row v in `vecs`:
+ *   sim(q) = the binary32 chain "scalar += q[j] * v[j]", j ascending, no contraction (core_functions.c:67-81) -- the bits
+ *   freddy_gpu_exact_join returns; out_query[i] = the q that comes first under sim DESC, q ASC, DESC being PostgreSQL's float4
+ *   order (a NaN above every number, all NaNs equal, +-Inf as numbers); out_sim[i] = that similarity.  A target id without a row:
+ *   (-1, -inf).
+ * freddy_gpu_pq_assign, for a target with a row in `pq`:
+ *   dist(q) = the ADC distance freddy_gpu_pq_search computes (the same LUT entries, positions summed in order); q is a candidate
+ *   iff dist(q) < sentinel (strict: a NaN distance never is); its key is freddy_similarity_of(dist) (include/freddy_similarity.h:
+ *   the "%f" text round trip of the SRF, then (float)(1.0 - y / 2.0), freddy--0.0.1.sql:862 -- what the host mirror's
+ *   similarity_of() computes with snprintf / strtof); out_query[i] = the candidate that comes first under key DESC, q ASC -- the
+ *   ROUNDED key is compared, so of two distances the round trip merges the lower query index wins; out_sim[i] = that key.
+ *   (-1, -inf) when no query is a candidate or the id is not in the table.
+ *   That key is defined for 0 <= dist < 2^24, and only distances below the sentinel are evaluated (an ADC distance is a sum of
+ *   squares, never negative): a sentinel above 2^24 (16777216) or NaN is refused with FREDDY_E_ARG.
+ * Errors, all before any device work and the scalars before the handle: FREDDY_E_ARG for Q < 0, n_targets < 0, a NULL buffer
+ * when Q > 0 and n_targets > 0, the sentinel above; FREDDY_E_LIMIT for Q > 65536 (the message names the value); FREDDY_E_ARG for a
+ * NULL handle, FREDDY_E_KIND for one of the wrong kind.  Q == 0 or n_targets == 0 succeeds and writes nothing.  Any n_targets
+ * (passes of 2^22 targets); only n_targets integers and floats leave the device. */
+int freddy_gpu_exact_assign(freddy_gpu_index_t* vecs, const float* queries /*[Q][d]*/, int32_t Q, const int32_t* target_ids,
+                            int64_t n_targets, int32_t* out_query /*[n_targets]*/, float* out_sim /*[n_targets]*/);
+int freddy_gpu_pq_assign(freddy_gpu_index_t* pq, const float* queries /*[Q][d]*/, int32_t Q, float sentinel,
+                         const int32_t* target_ids, int64_t n_targets, int32_t* out_query /*[n_targets]*/,
+                         float* out_sim /*[n_targets]*/);
 
 /* ---- batched post verification: the ANN handles and the raw-vector handle in one call (pv.h) ----------------------------
  * k_nearest_neighbour_ivfadc_pv / k_nearest_neighbour_pq_pv (freddy--0.0.1.sql:556-662) for Q queries: fetch k * pvf candidates

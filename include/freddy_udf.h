@@ -191,7 +191,10 @@ int knn_batch(freddy_session_t* s, const int32_t* query_ids, int32_t n_query_ids
  *   re-estimated by centroid_bytea over 10 random members -- empty clusters draw their samples and keep their
  *   centroid, as the reference does.  `draws` are the values random() returns, in call order (k, then 10 per
  *   cluster and round): a caller-supplied sequence makes a run reproducible; once it is used up (or NULL) an
- *   internal generator continues.  cluster_out[i] = 1..k for token i (0: no centroid listed it). */
+ *   internal generator continues.  cluster_out[i] = 1..k for token i (0: no centroid listed it).
+ *   cluster_exact and cluster_pq take any number of tokens: the assignment is one device call per round that returns the first
+ *   centroid of every token (exact_assign / pq_assign below; freddy_gpu_exact_assign / freddy_gpu_pq_assign), not lists of all
+ *   tokens per centroid.  cluster_ivpq needs the kNN-join's lists themselves and keeps freddy_gpu_knn_join's limits on k = n. */
 int analogy_3cosadd_in_pq(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids, int32_t n_ids, int32_t* result);
 /* The batch forms of the approximate analogies: results[i] = what the single-triple function returns for triples[i] (-1 where the SQL
  * returns NULL), all n triples in ONE device call (freddy_gpu_ivfadc_analogy / freddy_gpu_pq_analogy, approx_analogy.h) with
@@ -205,6 +208,14 @@ int analogy_3cosadd_in_ivpq(freddy_session_t* s, int32_t id1, int32_t id2, int32
 int cluster_exact(freddy_session_t* s, const int32_t* token_ids, int32_t n, int32_t k, const double* draws, int32_t n_draws, int32_t* cluster_out);
 int cluster_pq(freddy_session_t* s, const int32_t* token_ids, int32_t n, int32_t k, const double* draws, int32_t n_draws, int32_t* cluster_out);
 int cluster_ivpq(freddy_session_t* s, const int32_t* token_ids, int32_t n, int32_t k, const double* draws, int32_t n_draws, int32_t* cluster_out);
+/* The assignment step of cluster_exact / cluster_pq on its own (freddy--0.0.1.sql:1115-1127): out_query[i] = the 0-based index of the
+ * query (centroid) that lists target_ids[i] first under "similarity DESC, query ASC", out_sim[i] its similarity -- the
+ * cosine_similarity_bytea bits for exact_assign, (1.0 - (distance / 2.0))::float4 of the emitted ADC distance for pq_assign
+ * (sentinel 1000, as knn_in_pq_batch's pq_search_in_batch); (-1, -inf) for a target no query lists.  Any n_targets. */
+int exact_assign(freddy_session_t* s, const float* queries /*[n_queries][dim]*/, int32_t n_queries, int32_t dim, const int32_t* target_ids,
+                 int64_t n_targets, int32_t* out_query /*[n_targets]*/, float* out_sim /*[n_targets]*/);
+int pq_assign(freddy_session_t* s, const float* queries /*[n_queries][dim]*/, int32_t n_queries, int32_t dim, const int32_t* target_ids,
+              int64_t n_targets, int32_t* out_query /*[n_targets]*/, float* out_sim /*[n_targets]*/);
 
 /* Exact analogies and the analogy dispatchers, by row id (analogy.h; the device entry point freddy_gpu_exact_analogy).
  * analogy_3cosadd / analogy_3cosadd_in                      freddy--0.0.1.sql:1270-1315

@@ -1,0 +1,278 @@
+// assign.h -- the assignment step of cluster_exact / cluster_pq (generic_cluster, freddy--0.0.1.sql:1086-1209): "every token goes
+// to the centroid that lists it with the highest similarity" (:1115-1127) is, per token, an argmax over the centroids.  The SQL
+// asks the kNN-join for a list of ALL n tokens per centroid (k = n), sorts the kc * n rows by similarity DESC and keeps the first
+// row of every token; these kernels compute what that keeps -- one (centroid index, similarity) per token -- for any n:
+//
+//   assign_exact_kernel  (freddy_gpu_exact_assign, rows of knn_search_in_batch :480-501): similarity = the binary32 chain
+//       "scalar += v1[i] * v2[i]", i ascending (core_functions.c:67-81), first under "similarity DESC (PostgreSQL's float4 order: a
+//       NaN above every number, all NaNs equal), query index ASC".
+//   assign_pq_kernel     (freddy_gpu_pq_assign, rows of pq_search_in_batch as knn_in_pq_batch :846-867 reads them): the ADC
+//       distance of freddy_gpu_pq_search (LUT entry = squareDistance, index_utils.c:445-455, positions summed in order), a
+//       candidate iff distance < sentinel, key = freddy_similarity_of(distance) (include/freddy_similarity.h: the SRF's "%f" round
+//       trip, then 1 - y / 2), first under "key DESC, query index ASC".
+//
+// assign_exact_kernel: one lane per target, one wave per workgroup (64 targets; the waves share nothing, so nothing is gained by
+// larger workgroups and a small set still spreads over n / 64 CUs).  Ids are resolved by binary search over the handle's ascending
+// device ids (as pv.h does).  The rows are a gather of 4 d-byte rows; pv_rerank's staging: per step 64 targets x AS_DCH = 32
+// dimensions are read with 16-byte loads (8 consecutive lanes = 128 contiguous bytes of one row; a scalar path for d % 4 != 0)
+// and stored transposed into the tile [32][65] (dimension-major: stores hit banks 4 * piece + target (mod 32), reads are
+// lane-consecutive -- both conflict free).  Beside it a tile of AS_QT = 16 queries x 32 dimensions, [32][16], loaded as 16-byte
+// pieces too (16 consecutive lanes = one piece of each of the 16 queries) and stored with its rows permuted (as_qrow) so that a
+// store's 64 lanes write 64 consecutive floats -- conflict free as well.  Every lane reads the same 16 consecutive floats of a
+// dimension (four broadcast ds_read_b128), multiplies them by its own row element and adds into 16 accumulators in registers -- a row piece is loaded once per 16 queries, and each chain stays sequential in its lane.  (The bit
+// contract fixes the summation order, so the matrix cores cannot produce these values.)
+// LDS: 8 320 B + 2 048 B = 10 368 B static per workgroup of one wave (15 waves per CU by LDS); registers: 16 accumulators + 8
+// float4 of row pieces + 2 of query pieces in flight.  No workgroup reads what another wrote.
+//
+// assign_pq_kernel: grouping_kernel's shape (kernels.h).  A workgroup of 256 threads owns RPT * 256 targets, one or four per
+// thread, their code dwords in registers (M2 = 6: m = 12; M2 = 0: any m, the codes re-read per query), and walks the queries'
+// LUTs (lut_build, the search's own entries), staging LT of them at a time in LDS (LT * m * K * 4 bytes: as many as fit 64 KiB,
+// at least one -- a single LUT may take up to 156 KiB, check_pq_shape).  Per (target, query): the sum, then "dist < best distance
+// so far" (which starts at the sentinel, so it is the sentinel test too); only then the key is computed and compared.  That skips
+// no winner: freddy_similarity_of is monotone (a distance that is not smaller has a key that is not larger) and the queries come
+// in ascending order, so a later query wins only with a strictly larger key, which needs a strictly smaller distance.  The state
+// (best key, its query, the smallest distance) lives in out_sim / out_query / best_dist between the launches of a call whose LUTs
+// do not fit the workspace at once.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "freddy_similarity.h"
+
+namespace freddy {
+
+static constexpr int AS_MAX_Q = 65536;     // queries per assign call
+static constexpr int AS_QT = 16;           // queries per tile of assign_exact_kernel
+static constexpr int AS_DCH = 32;          // dimensions per step
+static constexpr int AS_STRIDE = 65;       // floats per dimension of the row tile: 64 targets + 1
+static constexpr int AS_TILE = AS_DCH * AS_STRIDE;
+static constexpr int AS_QTILE = AS_DCH * AS_QT;
+static constexpr int AS_PQ_WG = 256;
+
+// the row of `id` in a table of N ascending ids, -1 if it has none
+__device__ __forceinline__ int32_t assign_row_of(const int32_t* __restrict__ ids, int64_t N, int32_t id) {
+  int64_t lo = 0, hi = N;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (ids[mid] < id) lo = mid + 1; else hi = mid;
+  }
+  return (lo < N && ids[lo] == id) ? (int32_t)lo : -1;
+}
+
+// writes of the wave's lanes to its tiles become visible to its other lanes (pv.h pv_wave_sync)
+__device__ __forceinline__ void assign_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The row of dimension j (of a step's 32) in the query tile: element c of the 16-byte piece p = j / 4 goes to row 8 c + p, so that
+// the lanes of one store -- 16 queries x 4 pieces, c fixed -- write rows p, p + 1, p + 2, p + 3: 64 consecutive floats.
+__device__ __forceinline__ constexpr int as_qrow(int j) { return (j & 3) * 8 + (j >> 2); }
+
+// PostgreSQL's float4 order as an unsigned number: ascending with the float, every NaN the one largest value; never 0
+__device__ __forceinline__ uint32_t assign_ord(float sim) {
+  const uint32_t b = __float_as_uint(sim);
+  if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+struct AssignExactArgs {
+  const int32_t* targets;    // [n_targets] ids
+  const int32_t* vec_ids;    // [N] ascending ids of the vector handle
+  const float* rows;         // [N][d] its row-major copy
+  const float* queries;      // [Q][d]
+  int32_t* out_query;        // [n_targets]
+  float* out_sim;            // [n_targets]
+  int64_t N;
+  int n_targets, Q, d;
+};
+
+// (static: the header is included by two units, exact.hip launches it)
+static __global__ __launch_bounds__(64) void assign_exact_kernel(AssignExactArgs a) {
+  __shared__ __attribute__((aligned(16))) float tile[AS_TILE];     // [AS_DCH][AS_STRIDE]
+  __shared__ __attribute__((aligned(16))) float qs[AS_QTILE];      // [AS_DCH][AS_QT]
+  const int lane = threadIdx.x, d = a.d;
+  const int i = blockIdx.x * 64 + lane;
+  int32_t row = -1;
+  if (i < a.n_targets) row = assign_row_of(a.vec_ids, a.N, a.targets[i]);
+  uint32_t best_ord = 0;   // (no similarity's image)
+  int32_t best_q = -1;
+  float best_sim = -__builtin_huge_valf();
+  if (__ballot(row >= 0) != 0ull) {
+    const bool vec4 = (d & 3) == 0;   // every row and query 16-byte aligned and no piece crosses its end
+    for (int q0 = 0; q0 < a.Q; q0 += AS_QT) {
+      float acc[AS_QT];
+#pragma unroll
+      for (int t = 0; t < AS_QT; ++t) acc[t] = 0.0f;
+      for (int c0 = 0; c0 < d; c0 += AS_DCH) {
+        const int nd = (d - c0 < AS_DCH) ? d - c0 : AS_DCH;
+        float4 v[8], qv[2];
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {   // piece (it * 64 + lane): target (it * 8 + lane / 8), dimensions c0 + 4 (lane % 8) ..
+          const int cl = it * 8 + (lane >> 3), dim0 = (lane & 7) * 4;
+          const int32_t r = __shfl(row, cl, 64);
+          v[it] = float4{0.0f, 0.0f, 0.0f, 0.0f};
+          if (r >= 0 && dim0 < nd) {
+            const float* src = a.rows + (size_t)r * d + c0 + dim0;
+            if (vec4) v[it] = *reinterpret_cast<const float4*>(src);
+            else {
+              v[it].x = src[0];
+              if (dim0 + 1 < nd) v[it].y = src[1];
+              if (dim0 + 2 < nd) v[it].z = src[2];
+              if (dim0 + 3 < nd) v[it].w = src[3];
+            }
+          }
+        }
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {   // query (q0 + lane % 16), dimensions c0 + 4 (it * 4 + lane / 16) ..
+          const int t = lane & 15, dim0 = (it * 4 + (lane >> 4)) * 4;
+          qv[it] = float4{0.0f, 0.0f, 0.0f, 0.0f};
+          if (q0 + t < a.Q && dim0 < nd) {
+            const float* src = a.queries + (size_t)(q0 + t) * d + c0 + dim0;
+            if (vec4) qv[it] = *reinterpret_cast<const float4*>(src);
+            else {
+              qv[it].x = src[0];
+              if (dim0 + 1 < nd) qv[it].y = src[1];
+              if (dim0 + 2 < nd) qv[it].z = src[2];
+              if (dim0 + 3 < nd) qv[it].w = src[3];
+            }
+          }
+        }
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+          const int cl = it * 8 + (lane >> 3), dim0 = (lane & 7) * 4;
+          float* dst = tile + dim0 * AS_STRIDE + cl;
+          dst[0] = v[it].x; dst[AS_STRIDE] = v[it].y; dst[2 * AS_STRIDE] = v[it].z; dst[3 * AS_STRIDE] = v[it].w;
+        }
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {   // piece p, element c (dimension 4 p + c) -> row as_qrow(4 p + c) = 8 c + p
+          float* dst = qs + (it * 4 + (lane >> 4)) * AS_QT + (lane & 15);
+          dst[0] = qv[it].x; dst[8 * AS_QT] = qv[it].y; dst[16 * AS_QT] = qv[it].z; dst[24 * AS_QT] = qv[it].w;
+        }
+        assign_wave_sync();
+        const float* col = tile + lane;
+        if (nd == AS_DCH) {
+#pragma unroll
+          for (int j = 0; j < AS_DCH; ++j) {
+            const float x = col[j * AS_STRIDE];
+#pragma unroll
+            for (int t4 = 0; t4 < AS_QT / 4; ++t4) {
+              const float4 qq = *reinterpret_cast<const float4*>(qs + as_qrow(j) * AS_QT + t4 * 4);
+              float p;
+              p = qq.x * x; acc[t4 * 4 + 0] = acc[t4 * 4 + 0] + p;   // core_functions.c:77: scalar += v1[i] * v2[i]
+              p = qq.y * x; acc[t4 * 4 + 1] = acc[t4 * 4 + 1] + p;
+              p = qq.z * x; acc[t4 * 4 + 2] = acc[t4 * 4 + 2] + p;
+              p = qq.w * x; acc[t4 * 4 + 3] = acc[t4 * 4 + 3] + p;
+            }
+          }
+        } else {
+          for (int j = 0; j < nd; ++j) {
+            const float x = col[j * AS_STRIDE];
+#pragma unroll
+            for (int t4 = 0; t4 < AS_QT / 4; ++t4) {
+              const float4 qq = *reinterpret_cast<const float4*>(qs + as_qrow(j) * AS_QT + t4 * 4);
+              float p;
+              p = qq.x * x; acc[t4 * 4 + 0] = acc[t4 * 4 + 0] + p;
+              p = qq.y * x; acc[t4 * 4 + 1] = acc[t4 * 4 + 1] + p;
+              p = qq.z * x; acc[t4 * 4 + 2] = acc[t4 * 4 + 2] + p;
+              p = qq.w * x; acc[t4 * 4 + 3] = acc[t4 * 4 + 3] + p;
+            }
+          }
+        }
+        assign_wave_sync();
+      }
+#pragma unroll
+      for (int t = 0; t < AS_QT; ++t) {   // ascending query index: only a strictly larger similarity replaces the best
+        const uint32_t o = assign_ord(acc[t]);
+        if (q0 + t < a.Q && o > best_ord) { best_ord = o; best_q = q0 + t; best_sim = acc[t]; }
+      }
+    }
+  }
+  if (i < a.n_targets) {
+    a.out_query[i] = row >= 0 ? best_q : -1;
+    a.out_sim[i] = row >= 0 ? best_sim : -__builtin_huge_valf();
+  }
+}
+
+struct AssignPqArgs {
+  const float* lut;          // [nq][m][K] the LUTs of queries q_base .. q_base + nq - 1
+  const int32_t* targets;    // [n_targets] ids
+  const int32_t* ids;        // [N] ascending ids of the pq handle (position -> id)
+  const uint32_t* packed;    // [blocks][M2][64] its codes
+  int32_t* out_query;        // [n_targets]  state between launches, and the result
+  float* out_sim;            // [n_targets]
+  float* best_dist;          // [n_targets]  the smallest candidate distance so far
+  int64_t N;
+  int n_targets, q_base, nq, m, K, LT, first;
+  float sentinel;
+};
+
+template <int M2, int RPT>   // dwords of codes per row (0: read the codes from memory for every query, any m); targets per thread
+__global__ __launch_bounds__(AS_PQ_WG) void assign_pq_kernel(AssignPqArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char as_smem[];
+  float* sl = reinterpret_cast<float*>(as_smem);   // [LT][m][K]
+  const int tid = threadIdx.x, m = a.m, K = a.K, lutN = m * K;
+  const int m2 = M2 ? M2 : (m + 1) / 2;
+  int32_t row[RPT], bq[RPT];
+  uint32_t cw[RPT][M2 ? M2 : 1];
+  float bkey[RPT], bdist[RPT];
+#pragma unroll
+  for (int r = 0; r < RPT; ++r) {
+    const int i = (blockIdx.x * RPT + r) * AS_PQ_WG + tid;
+    row[r] = -1; bq[r] = -1; bkey[r] = -__builtin_huge_valf(); bdist[r] = a.sentinel;
+    if (i < a.n_targets) {
+      row[r] = assign_row_of(a.ids, a.N, a.targets[i]);
+      if (!a.first) { bq[r] = a.out_query[i]; bkey[r] = a.out_sim[i]; bdist[r] = a.best_dist[i]; }
+    }
+#pragma unroll
+    for (int j = 0; j < (M2 ? M2 : 1); ++j)
+      cw[r][j] = (M2 && row[r] >= 0) ? a.packed[((size_t)(row[r] >> 6) * m2 + j) * 64 + (row[r] & 63)] : 0u;
+  }
+  for (int l0 = 0; l0 < a.nq; l0 += a.LT) {
+    const int nl = (a.nq - l0 < a.LT) ? a.nq - l0 : a.LT;
+    __syncthreads();
+    const float* src = a.lut + (size_t)l0 * lutN;
+    if ((lutN & 3) == 0) {
+      const int n4 = nl * (lutN >> 2);
+      for (int x = tid; x < n4; x += AS_PQ_WG) reinterpret_cast<float4*>(sl)[x] = reinterpret_cast<const float4*>(src)[x];
+    } else {
+      for (int x = tid; x < nl * lutN; x += AS_PQ_WG) sl[x] = src[x];
+    }
+    __syncthreads();
+    for (int l = 0; l < nl; ++l) {
+      const float* lt = sl + (size_t)l * lutN;
+#pragma unroll
+      for (int r = 0; r < RPT; ++r) {
+        if (row[r] < 0) continue;
+        float dist = 0.0f;
+        if (M2) {
+#pragma unroll
+          for (int j = 0; j < (M2 ? M2 : 1); ++j) {
+            const uint32_t w = cw[r][j];
+            dist = dist + lt[(2 * j) * K + (int)(w & 0xffffu)];
+            if (2 * j + 1 < m) dist = dist + lt[(2 * j + 1) * K + (int)(w >> 16)];
+          }
+        } else {
+          for (int j = 0; j < m2; ++j) {
+            const uint32_t w = a.packed[((size_t)(row[r] >> 6) * m2 + j) * 64 + (row[r] & 63)];
+            dist = dist + lt[(2 * j) * K + (int)(w & 0xffffu)];
+            if (2 * j + 1 < m) dist = dist + lt[(2 * j + 1) * K + (int)(w >> 16)];
+          }
+        }
+        if (dist < bdist[r]) {   // (false for a NaN; bdist starts at the sentinel)
+          bdist[r] = dist;
+          const float key = freddy_similarity_of(dist);
+          if (key > bkey[r]) { bkey[r] = key; bq[r] = a.q_base + l0 + l; }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < RPT; ++r) {
+    const int i = (blockIdx.x * RPT + r) * AS_PQ_WG + tid;
+    if (i < a.n_targets) { a.out_query[i] = bq[r]; a.out_sim[i] = bkey[r]; a.best_dist[i] = bdist[r]; }
+  }
+}
+
+}  // namespace freddy

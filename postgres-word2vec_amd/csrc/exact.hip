@@ -1,6 +1,6 @@
 // exact.hip -- pin_vectors, exact brute-force kNN (core_functions.c:67-81, freddy--0.0.1.sql:426-454), the
 // exact analogies on the same handle (freddy--0.0.1.sql:1231-1315; analogy.h), the post verification of pq / ivf lists against it (pv.h)
-// and the approximate analogies over such lists (approx_analogy.h).
+// the approximate analogies over such lists (approx_analogy.h) and the assignment step of cluster_exact (assign.h).
 #include "internal.h"
 
 #include "kernels.h"
@@ -10,6 +10,7 @@
 #include "analogy.h"
 #include "pv.h"
 #include "approx_analogy.h"
+#include "assign.h"
 
 // ---------------------------------------------------------------------------------------
 // exact brute-force kNN
@@ -985,6 +986,43 @@ extern "C" int freddy_gpu_last_approx_analogy_stats(const freddy_gpu_index_t* an
   if (searched) *searched = ann->aa_stats[0];
   if (candidates) *candidates = ann->aa_stats[1];
   if (scored) *scored = ann->aa_stats[2];
+  return FREDDY_OK;
+}
+
+// ---- the assignment step of cluster_exact (assign.h) ----------------------------------------------------------------------
+// Targets per pass: the ids go up and the two result arrays come back through workspace buffers of this many entries.
+static constexpr int64_t AS_PASS = (int64_t)1 << 22;
+
+extern "C" int freddy_gpu_exact_assign(freddy_gpu_index_t* ix, const float* queries, int32_t Q, const int32_t* target_ids, int64_t n_targets,
+                                       int32_t* out_query, float* out_sim) {
+  // (the scalar arguments first: they are checked before the handle is looked at, so no device is needed to see these errors)
+  if (Q < 0 || n_targets < 0) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, n_targets=%lld)", Q, (long long)n_targets);
+  if (Q > 0 && n_targets > 0 && (!queries || !target_ids || !out_query || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
+  if (Q > AS_MAX_Q) return fail(FREDDY_E_LIMIT, "Q=%d exceeds this build's limit of %d queries per assign call", Q, AS_MAX_Q);
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (Q == 0 || n_targets == 0) return FREDDY_OK;
+  HIP_TRY(hipSetDevice(ix->device));
+  Workspace* ws = workspace_for(ix, ix->stream);
+  hipStream_t s = ix->stream;
+  const int d = ix->d;
+  const int64_t pass = std::min(AS_PASS, n_targets);
+  if (ws->w_q.ensure(sizeof(float) * (size_t)Q * d) || ws->w_sub_rows.ensure(sizeof(int32_t) * (size_t)pass) ||
+      ws->w_out_ids.ensure(sizeof(int32_t) * (size_t)pass) || ws->w_out_dist.ensure(sizeof(float) * (size_t)pass))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  HIP_TRY(hipMemcpyAsync(ws->w_q.p, queries, sizeof(float) * (size_t)Q * d, hipMemcpyHostToDevice, s));
+  for (int64_t t0 = 0; t0 < n_targets; t0 += pass) {
+    const int n = (int)std::min(pass, n_targets - t0);
+    HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, target_ids + t0, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+    AssignExactArgs aa;
+    aa.targets = ws->w_sub_rows.as<int32_t>(); aa.vec_ids = ix->ids; aa.rows = ix->coarse; aa.queries = ws->w_q.as<float>();
+    aa.out_query = ws->w_out_ids.as<int32_t>(); aa.out_sim = ws->w_out_dist.as<float>(); aa.N = ix->N; aa.n_targets = n; aa.Q = Q; aa.d = d;
+    timed_launch(ix, s, "assign_exact_kernel", [&] { hipLaunchKernelGGL(assign_exact_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, aa); });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_query + t0, ws->w_out_ids.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_sim + t0, ws->w_out_dist.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));   // (the next pass overwrites the three buffers)
+  }
   return FREDDY_OK;
 }
 

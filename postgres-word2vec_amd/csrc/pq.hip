@@ -1,4 +1,5 @@
-// pq.hip -- pq_search / pq_search_in(_batch) (freddy.c:28-152, :1028-1157, :414-653) and grouping_pq (freddy.c:1176-1401).
+// pq.hip -- pq_search / pq_search_in(_batch) (freddy.c:28-152, :1028-1157, :414-653), grouping_pq (freddy.c:1176-1401) and the
+// assignment step of cluster_pq (assign.h).
 #include "internal.h"
 
 #include "kernels.h"
@@ -6,6 +7,7 @@
 #include "fused5.h"   // query_codebook5_body: the table units of pq_front_kernel
 #include "one.h"
 #include "io_kernels.h"
+#include "assign.h"
 
 // ---------------------------------------------------------------------------------------
 // exhaustive / subset PQ
@@ -539,5 +541,75 @@ extern "C" int freddy_gpu_grouping_pq(freddy_gpu_index_t* ix, const float* group
   return FREDDY_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// the assignment step of cluster_pq (assign.h)
+// ---------------------------------------------------------------------------------------
+// Targets per pass (ids up, three state arrays) and the bytes of LUTs built at once: more queries than fit are walked in chunks,
+// the kernel carrying every target's best between the launches.  The LUT buffer stays on the handle's workspace, so it is kept
+// small: 64 MiB hold 5461 LUTs of the 300-d shape (m = 12, K = 256), 1365 at K = 1024.
+static constexpr int64_t AS_PQ_PASS = (int64_t)1 << 22;
+static constexpr size_t AS_PQ_LUT_BYTES = (size_t)64 << 20;
+
+extern "C" int freddy_gpu_pq_assign(freddy_gpu_index_t* ix, const float* queries, int32_t Q, float sentinel, const int32_t* target_ids,
+                                    int64_t n_targets, int32_t* out_query, float* out_sim) {
+  // (the scalar arguments first: they are checked before the handle is looked at, so no device is needed to see these errors)
+  if (Q < 0 || n_targets < 0) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, n_targets=%lld)", Q, (long long)n_targets);
+  if (Q > 0 && n_targets > 0 && (!queries || !target_ids || !out_query || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
+  // (freddy_similarity.h is proven for distances below 2^24, and only distances below the sentinel reach it)
+  if (!(sentinel <= 16777216.0f)) return fail(FREDDY_E_ARG, "sentinel=%g is not a number or above 2^24, the range the similarity of a distance is defined for", (double)sentinel);
+  if (Q > AS_MAX_Q) return fail(FREDDY_E_LIMIT, "Q=%d exceeds this build's limit of %d queries per assign call", Q, AS_MAX_Q);
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (ix->kind != KIND_PQ) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (Q == 0 || n_targets == 0) return FREDDY_OK;
+  HIP_TRY(hipSetDevice(ix->device));
+  Workspace* ws = workspace_for(ix, ix->stream);
+  hipStream_t s = ix->stream;
+  const int m = ix->m, K = ix->K, d = ix->d;
+  const size_t lutN = (size_t)m * K, lut_bytes = lutN * sizeof(float);
+  const int LT = (int)std::min<size_t>(8, std::max<size_t>(1, ((size_t)64 << 10) / lut_bytes));   // LUTs staged in LDS at a time
+  const int Qc = (int)std::min<size_t>((size_t)Q, std::max<size_t>(1, AS_PQ_LUT_BYTES / lut_bytes));   // LUTs built at a time
+  const int64_t pass = std::min(AS_PQ_PASS, n_targets);
+  if (ws->w_q.ensure(sizeof(float) * (size_t)Q * d) || ws->w_lut.ensure(lut_bytes * (size_t)Qc) || ws->w_sub_rows.ensure(sizeof(int32_t) * (size_t)pass) ||
+      ws->w_out_ids.ensure(sizeof(int32_t) * (size_t)pass) || ws->w_out_dist.ensure(sizeof(float) * (size_t)pass) ||
+      ws->w_found.ensure(sizeof(float) * (size_t)pass))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  HIP_TRY(hipMemcpyAsync(ws->w_q.p, queries, sizeof(float) * (size_t)Q * d, hipMemcpyHostToDevice, s));
+  int lut_q0 = -1;   // the chunk of queries whose LUTs are in w_lut
+  for (int64_t t0 = 0; t0 < n_targets; t0 += pass) {
+    const int n = (int)std::min(pass, n_targets - t0);
+    HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, target_ids + t0, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+    // four targets per thread once that still gives every CU two workgroups: a staged LUT then serves 1024 targets
+    const int RPT = (int64_t)n >= (int64_t)ix->n_cus * 2 * 4 * AS_PQ_WG ? 4 : 1;
+    const dim3 grid((unsigned)((n + RPT * AS_PQ_WG - 1) / (RPT * AS_PQ_WG)));
+    for (int q0 = 0; q0 < Q; q0 += Qc) {
+      const int nq = std::min(Qc, Q - q0);
+      if (lut_q0 != q0) {
+        if (int rc = launch_lut(ix, s, ws->w_q.as<float>() + (size_t)q0 * d, nullptr, ws->w_lut.as<float>(), nq)) return rc;   // freddy.c:1288-1299
+        lut_q0 = q0;
+      }
+      AssignPqArgs aa;
+      aa.lut = ws->w_lut.as<float>(); aa.targets = ws->w_sub_rows.as<int32_t>(); aa.ids = ix->ids; aa.packed = ix->packed;
+      aa.out_query = ws->w_out_ids.as<int32_t>(); aa.out_sim = ws->w_out_dist.as<float>(); aa.best_dist = ws->w_found.as<float>();
+      aa.N = ix->N; aa.n_targets = n; aa.q_base = q0; aa.nq = nq; aa.m = m; aa.K = K; aa.LT = LT; aa.first = q0 == 0 ? 1 : 0; aa.sentinel = sentinel;
+      const size_t lds = (size_t)LT * lut_bytes;
+      timed_launch(ix, s, "assign_pq_kernel", [&] {
+        if (ix->M2 == 6 && RPT == 4) hipLaunchKernelGGL((assign_pq_kernel<6, 4>), grid, dim3(AS_PQ_WG), lds, s, aa);
+        else if (ix->M2 == 6) hipLaunchKernelGGL((assign_pq_kernel<6, 1>), grid, dim3(AS_PQ_WG), lds, s, aa);
+        else if (RPT == 4) hipLaunchKernelGGL((assign_pq_kernel<0, 4>), grid, dim3(AS_PQ_WG), lds, s, aa);
+        else hipLaunchKernelGGL((assign_pq_kernel<0, 1>), grid, dim3(AS_PQ_WG), lds, s, aa);
+      });
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(out_query + t0, ws->w_out_ids.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_sim + t0, ws->w_out_dist.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));   // (the next pass overwrites the buffers)
+  }
+  return FREDDY_OK;
+}
+
 // The kernels of this unit that want more than the default 64 KiB of dynamic LDS.
-std::vector<LdsLimit> lds_limits_pq() { return {&grouping_kernel<6>, &grouping_kernel<15>, &grouping_kernel<0>}; }
+std::vector<LdsLimit> lds_limits_pq() {
+  return {&grouping_kernel<6>, &grouping_kernel<15>, &grouping_kernel<0>,
+          // (LUTs staged up to 64 KiB, but at least one: up to 156 KiB for a table at the LUT limit)
+          &assign_pq_kernel<6, 1>, &assign_pq_kernel<6, 4>, &assign_pq_kernel<0, 1>, &assign_pq_kernel<0, 4>};
+}

@@ -31,6 +31,7 @@ EXPORTS = [
     "freddy_gpu_last_analogy_stats", "freddy_gpu_exact_join", "freddy_gpu_last_exact_join_stats",
     "freddy_gpu_ivfadc_search_pv", "freddy_gpu_pq_search_pv", "freddy_gpu_last_pv_stats",
     "freddy_gpu_ivfadc_analogy", "freddy_gpu_pq_analogy", "freddy_gpu_last_approx_analogy_stats",
+    "freddy_gpu_exact_assign", "freddy_gpu_pq_assign",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 
@@ -127,7 +128,9 @@ def load(path=None, optional=()):
                                                        C.c_int32, C.c_void_p, C.c_void_p]),
                         ("freddy_gpu_pq_analogy", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                                    C.c_int64, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_last_approx_analogy_stats", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
+                        ("freddy_gpu_last_approx_analogy_stats", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_exact_assign", [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_pq_assign", [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])):
         if name in optional and not hasattr(lib, name):
             continue
         getattr(lib, name).argtypes = types
@@ -325,10 +328,26 @@ class PQIndex(_Index):
                                                _p(oi), _p(og), C.byref(n)))
         return oi[:n.value], og[:n.value]
 
+    def assign(self, queries, target_ids, sentinel=1000.0):
+        """The assignment step of cluster_pq (freddy_gpu_pq_assign): (query index[n], similarity[n]), slot i for target_ids[i] -- the
+        first query under "freddy_similarity_of(ADC distance) DESC, query index ASC" among those with distance < sentinel;
+        (-1, -inf) where there is none or the id has no row."""
+        return _assign(self, self.lib.freddy_gpu_pq_assign, queries, target_ids, (C.c_float(sentinel),))
+
     def search_dev(self, d_queries_ptr, Q, k, sentinel, d_out_ids_ptr, d_out_dist_ptr, stream=None):
         _check(self.lib.freddy_gpu_pq_search_dev(self.h, C.c_void_p(d_queries_ptr), Q, k, C.c_float(sentinel),
                                                  C.c_void_p(d_out_ids_ptr), C.c_void_p(d_out_dist_ptr),
                                                  C.c_void_p(stream or 0)))
+
+
+def _assign(ix, fn, queries, target_ids, extra, d=None):
+    """The two assign entry points on a handle object (ix.h; d: the table's dimension where the object does not know it)."""
+    qs = _f32(queries).reshape(-1, d or ix.d)
+    t = _i32(target_ids).reshape(-1)
+    out_q = np.empty(t.size, np.int32)
+    out_s = np.empty(t.size, np.float32)
+    _check(fn(ix.h, _p(qs) if qs.size else None, qs.shape[0], *extra, _p(t) if t.size else None, t.size, _p(out_q), _p(out_s)))
+    return out_q, out_s
 
 
 class VectorIndex(_Index):
@@ -385,6 +404,12 @@ class VectorIndex(_Index):
         t = _i32(target_ids).reshape(-1)
         _check(self.lib.freddy_gpu_exact_join(self.h, _p(qs), Q, k, _p(t) if t.size else None, t.size, _p(out_i), _p(out_s)))
         return out_i, out_s
+
+    def assign(self, queries, target_ids):
+        """The assignment step of cluster_exact (freddy_gpu_exact_assign): (query index[n], similarity[n]), slot i for
+        target_ids[i] -- the first query under "cosine_similarity_bytea DESC (PostgreSQL's float4 order), query index ASC", the
+        similarity bits of join(); (-1, -inf) where the id has no row."""
+        return _assign(self, self.lib.freddy_gpu_exact_assign, queries, target_ids, ())
 
     def last_join_stats(self):
         """The last join() call (freddy_gpu_last_exact_join_stats): queries the filter ran for, candidates refined, queries redone all-exact."""

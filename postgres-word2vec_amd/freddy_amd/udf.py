@@ -346,6 +346,23 @@ class Session:
         self._check(fn(self.h, _p(ids), ids.size, int(k), _p(dr), 0 if dr is None else dr.size, _p(out)))
         return out
 
+    def _assign(self, fn, queries, target_ids):
+        qs = np.ascontiguousarray(queries, dtype=np.float32)
+        qs = qs.reshape(1, -1) if qs.ndim == 1 else qs
+        t = _i32(target_ids).reshape(-1)
+        out_q = np.empty(t.size, np.int32)
+        out_s = np.empty(t.size, np.float32)
+        self._check(fn(self.h, _p(qs), qs.shape[0], qs.shape[1], _p(t), C.c_int64(t.size), _p(out_q), _p(out_s)))
+        return out_q, out_s
+
+    def exact_assign(self, queries, target_ids):
+        """The assignment step of cluster_exact: (0-based query index[n], similarity[n]) per target id; (-1, -inf) for an id without a vector."""
+        return self._assign(self.lib.exact_assign, queries, target_ids)
+
+    def pq_assign(self, queries, target_ids):
+        """The assignment step of cluster_pq: as exact_assign over the PQ table, similarity = (1.0 - (distance / 2.0))::float4."""
+        return self._assign(self.lib.pq_assign, queries, target_ids)
+
     def cluster_exact(self, token_ids, k, draws=None): return self._cluster(self.lib.cluster_exact, token_ids, k, draws)
     def cluster_pq(self, token_ids, k, draws=None): return self._cluster(self.lib.cluster_pq, token_ids, k, draws)
     def cluster_ivpq(self, token_ids, k, draws=None): return self._cluster(self.lib.cluster_ivpq, token_ids, k, draws)

@@ -691,6 +691,8 @@ static float emitted(float distance) {
   return strtof(buf, nullptr);
 }
 // (1.0 - (distance / 2.0))::float4 -- float4 / numeric is evaluated in float8   freddy--0.0.1.sql:527,617
+// (The text round trip stays the definition here; include/freddy_similarity.h restates it in exact arithmetic for the device --
+// freddy_gpu_pq_assign's key -- and tests/assign_sim_check.c compares the two bit for bit.)
 static float similarity_of(float distance) { return (float)(1.0 - (double)emitted(distance) / 2.0); }
 
 static int knn_plain(freddy_session_t* s, bool ivf, const float* query, int32_t dim, int32_t k, freddy_row2* out, int32_t* n_rows) {
@@ -1178,24 +1180,18 @@ namespace {
 struct SimRow { float sim; int qid; int tid; };
 }
 
-// (query, target, similarity) rows of knn_search_in_batch / knn_in_pq_batch / knn_in_ivpq_batch (bytea[] overloads:
-// query = 1-based centroid index) for k = all tokens; target as 1-based token index
-static int cluster_knn(freddy_session_t* s, int method, const std::vector<float>& centroids, int kc, const int32_t* token_ids, int n,
+// cluster_ivpq: (query, target, similarity) rows of knn_in_ivpq_batch (bytea[] overload: query = 1-based centroid index) for
+// k = all tokens; target as 1-based token index.  Its lists are the kNN-join's approximation, not "all tokens", so the rows
+// themselves are needed; cluster_exact and cluster_pq take cluster_assign below.
+static int cluster_knn(freddy_session_t* s, const std::vector<float>& centroids, int kc, const int32_t* token_ids, int n,
                        std::vector<SimRow>& rows) {
   rows.clear();
   std::vector<int32_t> ids((size_t)kc * n); std::vector<float> val((size_t)kc * n);
-  if (method == 0) {          // knn_in_exact per centroid: cosine_similarity_bytea DESC (freddy--0.0.1.sql:456-476, 1041-1054)
-    if (int rc = ensure_vecs(s)) return rc;
-    if (int rc = freddy_gpu_exact_join(s->vecs, centroids.data(), kc, n, token_ids, n, ids.data(), val.data())) return gpu_fail(rc);
-  } else if (method == 1) {   // pq_search_in_batch (:880-902)
-    if (!s->pq) return fail(-1, "pq_quantization / pq_codebook are not loaded");
-    if (int rc = freddy_gpu_pq_search(s->pq, centroids.data(), kc, n, 1000.0f, token_ids, n, ids.data(), val.data())) return gpu_fail(rc);
-  } else {                    // ivpq_search_in through knn_in_iv_batch (:754-795)
-    if (!s->ivpq) return fail(-1, "the ivpq tables are not loaded");
-    if (int rc = freddy_gpu_knn_join(s->ivpq, centroids.data(), kc, n, token_ids, n, s->alpha, s->pvf, s->method_flag, s->use_targetlist,
-                                     s->confidence, s->long_codes_threshold, ids.data(), val.data(), nullptr))
-      return gpu_fail(rc);
-  }
+  // ivpq_search_in through knn_in_iv_batch (:754-795)
+  if (!s->ivpq) return fail(-1, "the ivpq tables are not loaded");
+  if (int rc = freddy_gpu_knn_join(s->ivpq, centroids.data(), kc, n, token_ids, n, s->alpha, s->pvf, s->method_flag, s->use_targetlist,
+                                   s->confidence, s->long_codes_threshold, ids.data(), val.data(), nullptr))
+    return gpu_fail(rc);
   // token id -> 1-based token index (INNER JOIN unnest(token_ids, tokens) ON token = target; duplicates: every index)
   std::vector<std::pair<int32_t, int>> by_id((size_t)n);
   for (int i = 0; i < n; ++i) by_id[(size_t)i] = {token_ids[i], i + 1};
@@ -1204,7 +1200,7 @@ static int cluster_knn(freddy_session_t* s, int method, const std::vector<float>
     for (int r = 0; r < n; ++r) {
       const int32_t id = ids[(size_t)qi * n + r];
       if (id < 0) continue;   // the joins drop the (-1, sentinel) filler rows
-      const float sim = method == 0 ? val[(size_t)qi * n + r] : similarity_of(val[(size_t)qi * n + r]);
+      const float sim = similarity_of(val[(size_t)qi * n + r]);
       auto it = std::lower_bound(by_id.begin(), by_id.end(), std::make_pair(id, 0));
       for (; it != by_id.end() && it->first == id; ++it) rows.push_back({sim, qi + 1, it->second});
     }
@@ -1214,6 +1210,22 @@ static int cluster_knn(freddy_session_t* s, int method, const std::vector<float>
     if (a.qid != b.qid) return a.qid < b.qid;
     return a.tid < b.tid;
   });
+  return 0;
+}
+
+// cluster_exact (method 0) and cluster_pq (method 1): what the loop over such sorted rows of ALL tokens keeps -- per token the first
+// centroid under "similarity DESC, centroid ASC" -- straight from the device (freddy_gpu_exact_assign / freddy_gpu_pq_assign, csrc/assign.h), for any n.
+// best[i] = 0-based centroid of token i, -1: no centroid lists it.
+static int cluster_assign(freddy_session_t* s, int method, const std::vector<float>& centroids, int kc, const int32_t* token_ids, int n,
+                          std::vector<int32_t>& best, std::vector<float>& sim) {
+  best.resize((size_t)n); sim.resize((size_t)n);
+  if (method == 0) {   // knn_search_in_batch (freddy--0.0.1.sql:480-501)
+    if (int rc = ensure_vecs(s)) return rc;
+    if (int rc = freddy_gpu_exact_assign(s->vecs, centroids.data(), kc, token_ids, n, best.data(), sim.data())) return gpu_fail(rc);
+  } else {             // knn_in_pq_batch over pq_search_in_batch (:846-867)
+    if (!s->pq) return fail(-1, "pq_quantization / pq_codebook are not loaded");
+    if (int rc = freddy_gpu_pq_assign(s->pq, centroids.data(), kc, 1000.0f, token_ids, n, best.data(), sim.data())) return gpu_fail(rc);
+  }
   return 0;
 }
 
@@ -1243,14 +1255,26 @@ static int generic_cluster(freddy_session_t* s, int method, const int32_t* token
   std::vector<char> processed((size_t)n, 0);
   for (int I = 0; I < k; ++I) memcpy(&centroids[(size_t)I * d], tok[(size_t)pick(n) - 1], sizeof(float) * d);   // :1107-1112
   std::vector<SimRow> rows;
+  std::vector<int32_t> best;
+  std::vector<float> best_sim;
   for (int J = 1; J <= 10; ++J) {                                                                                  // :1114
-    if (int rc = cluster_knn(s, method, centroids, k, token_ids, n, rows)) return rc;
-    for (const SimRow& r : rows)                                                                                   // :1122-1128
-      if (!processed[(size_t)r.tid - 1]) {
-        clusters[(size_t)r.tid - 1] = r.qid;
-        lens[(size_t)r.qid - 1] += 1;
-        processed[(size_t)r.tid - 1] = 1;
-      }
+    if (method == 2) {
+      if (int rc = cluster_knn(s, centroids, k, token_ids, n, rows)) return rc;
+      for (const SimRow& r : rows)                                                                                 // :1122-1128
+        if (!processed[(size_t)r.tid - 1]) {
+          clusters[(size_t)r.tid - 1] = r.qid;
+          lens[(size_t)r.qid - 1] += 1;
+          processed[(size_t)r.tid - 1] = 1;
+        }
+    } else {   // the first row of every token, from the device; a token no centroid lists keeps its cluster
+      if (int rc = cluster_assign(s, method, centroids, k, token_ids, n, best, best_sim)) return rc;
+      for (int i = 0; i < n; ++i)
+        if (best[(size_t)i] >= 0) {
+          clusters[(size_t)i] = best[(size_t)i] + 1;
+          lens[(size_t)best[(size_t)i]] += 1;
+          processed[(size_t)i] = 1;
+        }
+    }
     if (J < 10) {
       for (int I = 1; I <= k; ++I) {                                                                               // :1131-1156
         if (lens[(size_t)I - 1] == 0) {
@@ -1279,6 +1303,23 @@ static int generic_cluster(freddy_session_t* s, int method, const int32_t* token
   for (int i = 0; i < n; ++i) cluster_out[i] = clusters[(size_t)i];
   return 0;
 }
+// The assignment step on its own, by row id (include/freddy_gpu.h: freddy_gpu_exact_assign / freddy_gpu_pq_assign).
+int exact_assign(freddy_session_t* s, const float* queries, int32_t n_queries, int32_t dim, const int32_t* target_ids, int64_t n_targets,
+                 int32_t* out_query, float* out_sim) {
+  if (!s || s->norm_ids.empty()) return fail(-1, "google_vecs_norm is not loaded");
+  if (dim != s->d) return fail(-1, "query has %d dimensions, table has %d", dim, s->d);
+  if (int rc = ensure_vecs(s)) return rc;
+  if (int rc = freddy_gpu_exact_assign(s->vecs, queries, n_queries, target_ids, n_targets, out_query, out_sim)) return gpu_fail(rc);
+  return 0;
+}
+int pq_assign(freddy_session_t* s, const float* queries, int32_t n_queries, int32_t dim, const int32_t* target_ids, int64_t n_targets,
+              int32_t* out_query, float* out_sim) {
+  if (!s || !s->pq) return fail(-1, "pq_quantization / pq_codebook are not loaded");
+  if (dim != s->pq_d) return fail(-1, "query has %d dimensions, index has %d", dim, s->pq_d);
+  if (int rc = freddy_gpu_pq_assign(s->pq, queries, n_queries, 1000.0f, target_ids, n_targets, out_query, out_sim)) return gpu_fail(rc);
+  return 0;
+}
+
 int cluster_exact(freddy_session_t* s, const int32_t* token_ids, int32_t n, int32_t k, const double* draws, int32_t n_draws, int32_t* cluster_out) {
   return generic_cluster(s, 0, token_ids, n, k, draws, n_draws, cluster_out);
 }
