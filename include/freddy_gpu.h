@@ -369,6 +369,21 @@ int freddy_gpu_insert_quantize(const freddy_insert_desc* desc, int device, const
  * list, the block layout is rebuilt on the device; ivpq: (ids, coarse_id, codes[, vectors]); vectors: (ids, vectors). */
 int freddy_gpu_append_rows(freddy_gpu_index_t* index, int64_t n, const int32_t* ids, const int32_t* coarse_id,
                            const int16_t* codes, const float* vectors);
+/* Remove rows from a pinned index in HBM (a DELETE on the table behind it): every pinned row whose id is one of ids[0..n)
+ * leaves, on every handle kind (pq, ivf with its replicas, ivpq, vectors).  Afterwards every entry point that takes the handle
+ * answers bit for bit as a fresh pin of the same table without those rows; the rows that stay keep their order (inside its
+ * list, for an ivf row), and a later append_rows may start above the largest id that is LEFT, as on a fresh pin.  ids may come
+ * in any order; an id listed twice counts once; an id that no pinned row has is skipped; *removed (may be NULL) receives the
+ * number of rows that left.  Emptying a cell or the whole handle is allowed.  Refused with FREDDY_E_ARG before anything has
+ * changed: a negative id (-1 is the filler of the result lists; the message names the id and its position), n < 0, ids == NULL
+ * with n > 0, a NULL handle.  n == 0 changes nothing.
+ * Like append_rows the call synchronises the handle's own stream first and rebuilds the layouts on the device beside the old
+ * ones: it must NOT run beside *_dev searches the caller has in flight on other streams -- drain them first.  Replicas follow
+ * append_rows' rule: the primary first; a failure after the first device has changed poisons the handle.
+ * freddy_gpu_index_bytes afterwards equals a fresh pin's for pq, ivf and ivpq; a vector handle's fragment-order copy keeps
+ * its capacity (at least a fresh pin's figure, at most the figure before the call).  A compacted ivf list loses part of the
+ * bank-conflict arrangement a fresh pin gives it: speed only, never a result. */
+int freddy_gpu_remove_rows(freddy_gpu_index_t* index, int64_t n, const int32_t* ids, int64_t* removed /* may be NULL */);
 /* Replace the codebook of a pinned pq / ivf / ivpq index (updateCodebookRelation, index_utils.c:959-991) and
  * re-derive everything on the device that depends on it. */
 int freddy_gpu_update_codebook(freddy_gpu_index_t* index, const float* codebook /*[m][K][d/m]*/);

@@ -281,6 +281,13 @@ int groups(freddy_session_t* s, const int32_t* token_ids, int32_t n_tokens, cons
  * unless freddy_set_codebook_counts (table: 0 pq_codebook, 1 residual_codebook, 2 codebook_ivpq) has set it. */
 int freddy_set_codebook_counts(freddy_session_t* s, int32_t table, const int32_t* pos, const int32_t* code, const int32_t* count, int32_t n);
 int insert_batch(freddy_session_t* s, const float* norm_vectors, int32_t n, int32_t dim, int32_t* new_ids);
+/* The mirror of DELETE FROM <table> WHERE id = ANY(ids) on EVERY table of the session (google_vecs_norm, google_vecs,
+ * pq_quantization, fine_quantization, fine_quantization_ivpq): the rows leave the session's host tables, and every handle the
+ * session has pinned loses them in HBM (freddy_gpu_remove_rows) instead of being pinned again.  ids in any order; duplicates
+ * and ids no table has are skipped; a negative id is refused before anything changes.  *removed (may be NULL) receives the
+ * number of rows that left google_vecs_norm.  Afterwards every UDF, and a following insert_batch (whose "max(id) + 1" sees
+ * the rows that are left), behaves as on a session loaded from the remaining rows.  The codebooks and their count columns stay. */
+int delete_rows(freddy_session_t* s, const int32_t* ids, int64_t n, int64_t* removed);
 
 /* per-call row emit: snprintf("%d") / snprintf("%f") into 16-byte buffers   freddy.c:154-169,1001-1023 */
 void freddy_emit_row2(const freddy_row2* row, char values[2][16]);

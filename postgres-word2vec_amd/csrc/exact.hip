@@ -20,7 +20,7 @@
 int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n) {
   const bool shape_ok = ix->d % 4 == 0 && ix->d <= 512 && ix->d >= 16;
   if (!shape_ok) { ix->exf_ok = false; return 0; }
-  if (ix->tune.exact_filter == 0) { ix->exf_ok = false; return 0; }   // (option exact_filter = 0 when the table is pinned: no third copy of it)
+  if (ix->tune.exact_filter == 0 || ix->exf_never) { ix->exf_never = true; ix->exf_ok = false; return 0; }   // (option exact_filter = 0 when the table is pinned: no third copy of it -- nor later, when remove_rows takes the statistics again from row 0)
   if (n <= 0) return 0;
   if (ix->exf_small.ensure(4096)) return fail(FREDDY_E_NOMEM, "device allocation failed");
   uint32_t* st = ix->exf_small.as<uint32_t>() + 512;   // (the upper part of the small buffer; the lower one is per-call state)

@@ -1,7 +1,7 @@
 // internal.h -- what the translation units of libfreddy_gpu.so share on the HOST side: the handle, its workspaces and
 // options, error reporting, and the functions one unit calls in another.  The C ABI is include/freddy_gpu.h; the units:
 //   core.hip    errors, options, workspaces, profiling records, unpin, counters
-//   pin.hip     pin_pq / pin_ivf(_multi): table layouts; append_rows / update_codebook (HBM index mutation)
+//   pin.hip     pin_pq / pin_ivf(_multi): table layouts; append_rows / remove_rows / update_codebook (HBM index mutation; remove_kernels.h)
 //   ivfadc.hip  the IVFADC search: cell selection, work table, scans, merge; *_dev entry, host-buffer pipeline, one-query launch
 //   pq.hip      pq_search (+ subsets, pseudo-list batches, one-query launch), grouping_pq
 //   join.hip    pin_ivpq, knn_join (join.h: overview; join_kernels.h and join_traverse.h the kernels, join_host.h the host heap, join_run.h the run
@@ -233,6 +233,7 @@ struct freddy_gpu_index {
   float* xb = nullptr;
   // exact kNN as filter + refine (exact2.h): the table's statistics (pin time / append) and the per-call buffers
   bool exf_ok = false;          // every element finite, d % 4 == 0, d <= 512
+  bool exf_never = false;       // the statistics were once taken with option exact_filter = 0: rows are missing from them, the filter stays off for good
   bool exf_dirty = true;        // no filter + refine call has completed yet, or the last one failed part-way: its device-side words are cleared before the next
   float exf_xnorm = 0.0f;       // largest row norm, rounded up
   int exf_ex = 0;               // power-of-two scale of the rows for the f16 split
@@ -260,7 +261,7 @@ struct freddy_gpu_index {
   // replicas of this index on further devices (freddy_gpu_pin_ivf_multi): a host batch is split contiguously over
   // this handle and its replicas; every replica is a complete pinned index of its own
   std::vector<freddy_gpu_index*> replicas;
-  // set when a mutation (append_rows / update_codebook / set_option) failed after it had already changed some of the devices
+  // set when a mutation (append_rows / remove_rows / update_codebook / set_option) failed after it had already changed some of the devices
   // behind this handle: the replicas no longer hold the same tables, so every search fails loudly until the handle is unpinned
   bool registered = false;        // counted in the registry of backends (core.hip backend_handles)
   bool poisoned = false;

@@ -1,9 +1,10 @@
-// pin.hip -- pin_pq / pin_ivf / pin_ivf_multi: the pinned tables' layouts in HBM; append_rows / update_codebook.
+// pin.hip -- pin_pq / pin_ivf / pin_ivf_multi: the pinned tables' layouts in HBM; append_rows / remove_rows / update_codebook.
 #include "internal.h"
 
 #include "kernels.h"
 #include "scan_common.h"
 #include "coarse.h"   // fragment layouts of the centroids; refine.h: row_term_kernel
+#include "remove_kernels.h"
 
 static std::vector<float> transpose_codebook(const float* cb, int m, int K, int S) {
   std::vector<float> t((size_t)m * S * K);
@@ -703,6 +704,271 @@ extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const i
     }
   }
   return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+}
+
+// ---------------------------------------------------------------------------------------
+// remove_rows: the DELETE beside insert_batch's INSERTs (kernels in remove_kernels.h)
+// ---------------------------------------------------------------------------------------
+// device scratch of one call, freed when it goes out of scope
+struct RemoveScratch {
+  std::vector<void*> held;
+  ~RemoveScratch() { for (void* p : held) if (p) (void)hipFree(p); }
+  template <class T> T* get(size_t n) {
+    void* p = nullptr;
+    if (hipMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)) != hipSuccess) return nullptr;
+    held.push_back(p);
+    return static_cast<T*>(p);
+  }
+  template <class T> T* put(const T* src, size_t n) {
+    T* p = get<T>(n);
+    if (p && n && hipMemcpy(p, src, sizeof(T) * n, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return p;
+  }
+};
+
+// rows `rows` (ascending, distinct) out of a host array of `e` elements per row
+template <class T>
+static void erase_rows(std::vector<T>& a, const std::vector<int32_t>& rows, size_t e = 1) {
+  size_t w = (size_t)rows[0], next = 0;
+  const size_t n = a.size() / e;
+  for (size_t r = (size_t)rows[0]; r < n; ++r) {
+    if (next < rows.size() && (size_t)rows[next] == r) { ++next; continue; }
+    if (w != r) std::copy(a.begin() + r * e, a.begin() + (r + 1) * e, a.begin() + w * e);
+    ++w;
+  }
+  a.resize(w * e);
+}
+
+// A fresh device array of the rows that stay (max(n_new * e, 1) elements, as upload() sizes it), enqueued on `s`: *out is the
+// caller's to swap in or free.  A row is e elements of T, a whole number of 4-byte words.
+template <class T>
+static int gather_rows(hipStream_t s, const T* src, int64_t n_new, int e, const int32_t* d_rm, int n_rm, T** out) {
+  *out = nullptr;
+  if (hipMalloc((void**)out, sizeof(T) * std::max<size_t>((size_t)n_new * e, 1)) != hipSuccess) { *out = nullptr; return fail(FREDDY_E_NOMEM, "device allocation failed while removing rows"); }
+  if (n_new > 0) {
+    hipLaunchKernelGGL(rm_gather_rows_kernel, dim3((unsigned)((n_new + 63) / 64)), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(src),
+                       reinterpret_cast<uint32_t*>(*out), d_rm, n_rm, n_new, (int)(sizeof(T) * e / 4));
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+// what `bytes` gains when an array that upload() counted goes from old_n to new_n elements
+template <class T>
+static int64_t resized_bytes(size_t old_n, size_t new_n) { return (int64_t)sizeof(T) * ((int64_t)std::max<size_t>(new_n, 1) - (int64_t)std::max<size_t>(old_n, 1)); }
+
+// rows of a pq / ivf index: every slot whose pos is in `rm` (ascending, distinct: ids of an ivf handle, row indices of the flat
+// table) leaves; the rows that stay keep their order inside their list.  The new block layout is built beside the old one on
+// the device and swapped in; nothing changes when no slot matches.  *removed: the rows that left; *max_pos: the largest pos
+// that stays (-1: none).  The lists lose part of arrange_list_rows' bank-conflict arrangement (speed only).
+static int remove_packed_rows(freddy_gpu_index* ix, int n_lists, const std::vector<int32_t>& rm, bool renumber, int64_t* removed, int32_t* max_pos) {
+  const int M2 = ix->M2;
+  const int64_t ob = ix->n_blocks;
+  *removed = 0;
+  if (ob <= 0 || rm.empty()) return 0;
+  RemoveScratch tmp;
+  const int32_t minus_one = -1;
+  int32_t* d_rm = tmp.put(rm.data(), rm.size());
+  unsigned long long* keep_mask = tmp.get<unsigned long long>((size_t)ob);
+  int32_t *keep_cnt = tmp.get<int32_t>((size_t)ob), *prefix = tmp.get<int32_t>((size_t)ob), *list_keep = tmp.get<int32_t>((size_t)n_lists);
+  int32_t* d_max = tmp.put(&minus_one, 1);
+  if (!d_rm || !keep_mask || !keep_cnt || !prefix || !list_keep || !d_max) return fail(FREDDY_E_NOMEM, "device allocation failed while removing rows");
+  hipLaunchKernelGGL(rm_mark_kernel, dim3((unsigned)((ob + 3) / 4)), dim3(256), 0, ix->stream, ix->pos, ob, d_rm, (int)rm.size(), keep_mask, keep_cnt, d_max);
+  hipLaunchKernelGGL(rm_list_scan_kernel, dim3((unsigned)n_lists), dim3(256), 0, ix->stream, ix->blk_off, keep_cnt, prefix, list_keep);
+  HIP_TRY(hipGetLastError());
+  std::vector<int32_t> keep((size_t)n_lists);
+  HIP_TRY(hipMemcpyAsync(keep.data(), list_keep, sizeof(int32_t) * (size_t)n_lists, hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipMemcpyAsync(max_pos, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  std::vector<int32_t> new_list_off((size_t)n_lists + 1, 0), new_blk((size_t)n_lists + 1, 0);
+  int max_blocks = 0;
+  for (int c = 0; c < n_lists; ++c) {
+    if (keep[(size_t)c] < 0 || keep[(size_t)c] > ix->h_list_off[(size_t)c + 1] - ix->h_list_off[(size_t)c])
+      return fail(FREDDY_E_HIP, "list %d keeps %d of its %d rows: the pinned layout is inconsistent", c, keep[(size_t)c], ix->h_list_off[(size_t)c + 1] - ix->h_list_off[(size_t)c]);
+    new_list_off[(size_t)c + 1] = new_list_off[(size_t)c] + keep[(size_t)c];
+    const int nb = (keep[(size_t)c] + 63) / 64;
+    new_blk[(size_t)c + 1] = new_blk[(size_t)c] + nb;
+    max_blocks = std::max(max_blocks, nb);
+  }
+  const int64_t kept = new_list_off[(size_t)n_lists];
+  if (kept == ix->N) return 0;   // (no pinned row has one of the ids)
+  const int64_t nnb = new_blk[(size_t)n_lists], alloc_blocks = std::max<int64_t>(nnb, 1);
+  std::vector<int32_t> blk_cell((size_t)alloc_blocks, 0);
+  for (int c = 0; c < n_lists; ++c)
+    for (int b = new_blk[(size_t)c]; b < new_blk[(size_t)c + 1]; ++b) blk_cell[(size_t)b] = c;
+  uint32_t* packed = nullptr;
+  int32_t *pos = nullptr, *d_blk_cell = nullptr, *d_new_blk = nullptr, *d_list_off = nullptr;
+  int64_t junk = 0;
+  int rc = 0;
+  if (hipMalloc((void**)&packed, sizeof(uint32_t) * (size_t)alloc_blocks * M2 * 64) != hipSuccess ||
+      hipMalloc((void**)&pos, sizeof(int32_t) * (size_t)alloc_blocks * 64) != hipSuccess ||
+      upload(&d_blk_cell, blk_cell.data(), blk_cell.size(), &junk) || upload(&d_new_blk, new_blk.data(), new_blk.size(), &junk) ||
+      upload(&d_list_off, new_list_off.data(), new_list_off.size(), &junk))
+    rc = fail(FREDDY_E_NOMEM, "device allocation failed while removing rows");
+  if (!rc && nnb == 0 &&   // (an empty table keeps one block of padding, as pack_lists leaves it)
+      (hipMemsetAsync(packed, 0, sizeof(uint32_t) * (size_t)M2 * 64, ix->stream) != hipSuccess || hipMemsetAsync(pos, 0xff, sizeof(int32_t) * 64, ix->stream) != hipSuccess))
+    rc = fail(FREDDY_E_HIP, "clearing the empty table failed");
+  if (!rc && nnb > 0) {
+    hipLaunchKernelGGL(rm_scatter_kernel, dim3((unsigned)((ob + 3) / 4)), dim3(256), 0, ix->stream, ix->packed, ix->pos, ix->blk_cell, d_new_blk, keep_mask,
+                       prefix, ob, nnb * 64, M2, renumber ? 1 : 0, packed, pos);
+    hipLaunchKernelGGL(rm_fill_tail_kernel, dim3((unsigned)((n_lists + 3) / 4)), dim3(256), 0, ix->stream, d_list_off, d_new_blk, n_lists, M2, packed, pos);
+  }
+  if (!rc && (hipGetLastError() != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess)) rc = fail(FREDDY_E_HIP, "compacting the lists failed");
+  if (rc) {
+    void* fresh[] = {packed, pos, d_blk_cell, d_new_blk, d_list_off};
+    for (void* p : fresh) if (p) (void)hipFree(p);
+    return rc;
+  }
+  void* old[] = {ix->packed, ix->pos, ix->blk_cell, ix->blk_off, ix->list_off};
+  for (void* p : old) if (p) (void)hipFree(p);
+  ix->bytes += (alloc_blocks - std::max<int64_t>(ob, 1)) * (int64_t)(sizeof(uint32_t) * M2 * 64 + sizeof(int32_t) * 64 + sizeof(int32_t));
+  ix->packed = packed; ix->pos = pos; ix->blk_cell = d_blk_cell; ix->blk_off = d_new_blk; ix->list_off = d_list_off;
+  ix->n_blocks = nnb;
+  ix->max_list_blocks = max_blocks;
+  ix->h_list_off = new_list_off;
+  *removed = ix->N - kept;
+  ix->N = kept;
+  return build_packed8(ix);
+}
+
+extern "C" int freddy_gpu_remove_rows(freddy_gpu_index_t* ix, int64_t n, const int32_t* ids, int64_t* removed) {
+  if (n < 0 || (n > 0 && !ids)) return fail(FREDDY_E_ARG, "bad argument: n = %lld ids%s", (long long)n, ids ? "" : ", no ids");
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (removed) *removed = 0;
+  if (n == 0) return FREDDY_OK;
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] < 0) return fail(FREDDY_E_ARG, "id %d at position %lld is negative (-1 is the filler of a result list)", ids[i], (long long)i);
+  if (!ix->replicas.empty()) {   // the rule of append_rows: the primary first, a failure after the first device has changed poisons the handle
+    std::vector<freddy_gpu_index*> reps;
+    reps.swap(ix->replicas);
+    int rc = freddy_gpu_remove_rows(ix, n, ids, removed);
+    reps.swap(ix->replicas);
+    if (rc) { if (rc == FREDDY_E_HIP || rc == FREDDY_E_NOMEM) ix->poisoned = true; return rc; }
+    for (freddy_gpu_index* r : ix->replicas)
+      if ((rc = freddy_gpu_remove_rows(r, n, ids, nullptr))) { ix->poisoned = true; return rc; }
+    return FREDDY_OK;
+  }
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  std::vector<int32_t> want(ids, ids + n);   // any order, an id listed twice counts once
+  std::sort(want.begin(), want.end());
+  want.erase(std::unique(want.begin(), want.end()), want.end());
+  int64_t gone = 0;
+  switch (ix->kind) {
+    case KIND_PQ: {
+      const std::vector<int32_t> rows = rows_of_ids(ix->h_ids, want.data(), (int64_t)want.size());   // flat table: pos = row index
+      if (rows.empty()) return FREDDY_OK;
+      const int64_t old_n = ix->N, new_n = old_n - (int64_t)rows.size();
+      RemoveScratch tmp;
+      int32_t* d_rm = tmp.put(rows.data(), rows.size());
+      if (!d_rm) return fail(FREDDY_E_NOMEM, "device allocation failed while removing rows");
+      int32_t* new_ids = nullptr;
+      if (int rc = gather_rows(ix->stream, ix->ids, new_n, 1, d_rm, (int)rows.size(), &new_ids)) { if (new_ids) (void)hipFree(new_ids); return rc; }
+      // views of the flat table are rebuilt from the new layout on next use
+      if (ix->pq_shadow) { free_index(ix->pq_shadow); ix->pq_shadow = nullptr; }
+      if (ix->pq_sub_view) { free_index(ix->pq_sub_view); ix->pq_sub_view = nullptr; }
+      int32_t unused = -1;
+      if (int rc = remove_packed_rows(ix, 1, rows, true, &gone, &unused)) { (void)hipFree(new_ids); return rc; }   // (synchronises the stream: new_ids is complete)
+      if (ix->ids) (void)hipFree(ix->ids);
+      ix->ids = new_ids;
+      ix->bytes += resized_bytes<int32_t>((size_t)old_n, (size_t)new_n);
+      erase_rows(ix->h_ids, rows);
+      ix->max_id = ix->h_ids.empty() ? -1 : ix->h_ids.back();
+      break;
+    }
+    case KIND_IVF: {
+      int32_t max_pos = -1;
+      if (int rc = remove_packed_rows(ix, ix->C, want, false, &gone, &max_pos)) return rc;   // (pos holds the ids)
+      if (gone > 0) {
+        ix->max_id = max_pos;   // a later append may start above the largest id that is left, as on a fresh pin
+        if (int rc = refresh_row_terms(ix)) return rc;
+      }
+      break;
+    }
+    case KIND_IVPQ: {
+      JoinIndex& j = ix->join;
+      const std::vector<int32_t> rows = rows_of_ids(j.h_ids, want.data(), (int64_t)want.size());
+      if (rows.empty()) return FREDDY_OK;
+      const size_t o = (size_t)j.N, nn = o - rows.size();
+      RemoveScratch tmp;
+      int32_t* d_rm = tmp.put(rows.data(), rows.size());
+      uint32_t* markbits = tmp.get<uint32_t>((nn + 31) / 32 + 1);
+      if (!d_rm || !markbits) return fail(FREDDY_E_NOMEM, "device allocation failed while removing rows");
+      int32_t *new_ids = nullptr, *new_cell = nullptr;
+      int16_t* new_codes = nullptr;
+      float* new_vec = nullptr;
+      int rc = gather_rows(ix->stream, j.ids, (int64_t)nn, 1, d_rm, (int)rows.size(), &new_ids);
+      if (!rc) rc = gather_rows(ix->stream, j.cell, (int64_t)nn, 1, d_rm, (int)rows.size(), &new_cell);
+      if (!rc) rc = gather_rows(ix->stream, j.codes, (int64_t)nn, j.MP, d_rm, (int)rows.size(), &new_codes);
+      if (!rc && j.has_vectors) rc = gather_rows(ix->stream, j.vectors, (int64_t)nn, j.d, d_rm, (int)rows.size(), &new_vec);
+      if (!rc && hipStreamSynchronize(ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "compacting the ivpq rows failed");
+      if (rc) {
+        void* fresh[] = {new_ids, new_cell, new_codes, new_vec};
+        for (void* p : fresh) if (p) (void)hipFree(p);
+        return rc;
+      }
+      void* old[] = {j.ids, j.cell, j.codes, j.vectors, j.markbits};
+      for (void* p : old) if (p) (void)hipFree(p);
+      j.ids = new_ids; j.cell = new_cell; j.codes = new_codes; j.vectors = new_vec;
+      j.markbits = markbits; tmp.held.erase(std::find(tmp.held.begin(), tmp.held.end(), (void*)markbits));
+      ix->bytes += 2 * resized_bytes<int32_t>(o, nn) + resized_bytes<int16_t>(o * j.MP, nn * j.MP) + (j.has_vectors ? resized_bytes<float>(o * j.d, nn * j.d) : 0);
+      erase_rows(j.h_ids, rows);
+      erase_rows(j.h_cell, rows);
+      j.N = (int64_t)nn; ix->N = j.N;
+      j.ids_affine = j.N > 0 && (int64_t)j.h_ids.back() - j.h_ids.front() == j.N - 1;   // (a hole in the middle: binary search from now on)
+      j.tl_valid = false;   // (the cached "id IN (targets)" resolution refers to the rows as they were)
+      gone = (int64_t)rows.size();
+      break;
+    }
+    case KIND_VEC: {
+      const std::vector<int32_t> rows = rows_of_ids(ix->h_ids, want.data(), (int64_t)want.size());
+      if (rows.empty()) return FREDDY_OK;
+      const int d = ix->d;
+      const size_t o = (size_t)ix->N, nn = o - rows.size();
+      const int64_t new_blocks = (int64_t)((nn + 63) / 64), alloc_blocks = std::max<int64_t>(new_blocks, 1);
+      const int64_t same_blocks = std::min<int64_t>(rows[0] / 64, new_blocks);   // (the blocks before the first row that leaves stay as they are)
+      const size_t blk = sizeof(float) * (size_t)d * 64;
+      RemoveScratch tmp;
+      int32_t* d_rm = tmp.put(rows.data(), rows.size());
+      if (!d_rm) return fail(FREDDY_E_NOMEM, "device allocation failed while removing rows");
+      int32_t* new_ids = nullptr;
+      float *new_rows = nullptr, *xb = nullptr;
+      int rc = gather_rows(ix->stream, ix->ids, (int64_t)nn, 1, d_rm, (int)rows.size(), &new_ids);
+      if (!rc) rc = gather_rows(ix->stream, ix->coarse, (int64_t)nn, d, d_rm, (int)rows.size(), &new_rows);
+      if (!rc && hipMalloc((void**)&xb, blk * (size_t)alloc_blocks) != hipSuccess) { xb = nullptr; rc = fail(FREDDY_E_NOMEM, "device allocation failed while removing rows"); }
+      if (!rc && same_blocks > 0 && hipMemcpyAsync(xb, ix->xb, blk * (size_t)same_blocks, hipMemcpyDeviceToDevice, ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "copying the row blocks failed");
+      if (!rc && alloc_blocks > same_blocks && hipMemsetAsync(xb + (size_t)same_blocks * d * 64, 0, blk * (size_t)(alloc_blocks - same_blocks), ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "clearing the row blocks failed");
+      if (!rc && (int64_t)nn > same_blocks * 64) {
+        const int64_t first = same_blocks * 64, cnt = (int64_t)nn - first;
+        hipLaunchKernelGGL(place_vectors_kernel, dim3((unsigned)cnt), dim3(256), 0, ix->stream, new_rows + (size_t)first * d, first, cnt, xb, d);
+        if (hipGetLastError() != hipSuccess) rc = fail(FREDDY_E_HIP, "re-blocking the rows failed");
+      }
+      if (!rc && hipStreamSynchronize(ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "compacting the vector rows failed");
+      if (rc) {
+        void* fresh[] = {new_ids, new_rows, xb};
+        for (void* p : fresh) if (p) (void)hipFree(p);
+        return rc;
+      }
+      void* old[] = {ix->ids, ix->coarse, ix->xb};
+      for (void* p : old) if (p) (void)hipFree(p);
+      ix->bytes += resized_bytes<int32_t>(o, nn) + (int64_t)blk * (alloc_blocks - std::max<int64_t>(ix->n_blocks, 1));
+      if (nn == 0) {   // (pin_vectors keeps no row-major copy of an empty table)
+        (void)hipFree(new_rows); new_rows = nullptr;
+        ix->bytes -= (int64_t)sizeof(float) * (int64_t)o * d;
+      } else ix->bytes += (int64_t)sizeof(float) * d * ((int64_t)nn - (int64_t)o);
+      ix->ids = new_ids; ix->coarse = new_rows; ix->xb = xb;
+      ix->n_blocks = new_blocks; ix->N = (int64_t)nn;
+      erase_rows(ix->h_ids, rows);
+      gone = (int64_t)rows.size();
+      // the exact filter's state over the rows that are left, as a fresh pin computes it: a larger scale once the row with the
+      // largest element has gone, the filter back on once the only non-finite row has (the fragment copy keeps its capacity)
+      if (nn == 0) ix->exf_ok = false;
+      else if (int rc2 = exf_table_stats(ix, 0, (int64_t)nn)) return rc2;
+      break;
+    }
+    default: return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  }
+  if (removed) *removed = gone;
+  return FREDDY_OK;
 }
 
 extern "C" int freddy_gpu_update_codebook(freddy_gpu_index_t* ix, const float* codebook) {

@@ -31,7 +31,7 @@ EXPORTS = [
     "freddy_gpu_last_analogy_stats", "freddy_gpu_exact_join", "freddy_gpu_last_exact_join_stats",
     "freddy_gpu_ivfadc_search_pv", "freddy_gpu_pq_search_pv", "freddy_gpu_last_pv_stats",
     "freddy_gpu_ivfadc_analogy", "freddy_gpu_pq_analogy", "freddy_gpu_last_approx_analogy_stats",
-    "freddy_gpu_exact_assign", "freddy_gpu_pq_assign",
+    "freddy_gpu_exact_assign", "freddy_gpu_pq_assign", "freddy_gpu_remove_rows",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 
@@ -151,6 +151,8 @@ def load(path=None, optional=()):
                                                C.c_void_p, C.c_void_p]
     lib.freddy_gpu_append_rows.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.freddy_gpu_update_codebook.argtypes = [C.c_void_p, C.c_void_p]
+    if "freddy_gpu_remove_rows" not in optional:
+        lib.freddy_gpu_remove_rows.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.freddy_gpu_kmeans.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.freddy_gpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     lib.freddy_gpu_last_track.argtypes = [C.c_void_p, C.c_void_p]
@@ -211,6 +213,18 @@ class _Index:
         v = None if vectors is None else _f32(vectors)
         _check(self.lib.freddy_gpu_append_rows(self.h, ids.size, _p(ids), _p(cid), _p(cd), _p(v)))
         self.N += ids.size   # (grouping() sizes its output arrays by it)
+
+    def remove_rows(self, ids):
+        """DELETE of rows from the pinned tables (freddy_gpu_remove_rows): ids in any order, unknown ids are skipped, an id listed
+        twice counts once.  -> the number of rows that left."""
+        ids = np.asarray(ids)
+        if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
+            raise FreddyGpuError("row ids are 32-bit integers")
+        ids = _i32(ids).reshape(-1)
+        gone = C.c_int64(0)
+        _check(self.lib.freddy_gpu_remove_rows(self.h, ids.size, _p(ids), C.byref(gone)))
+        self.N -= gone.value   # (grouping() sizes its output arrays by it)
+        return int(gone.value)
 
     def update_codebook(self, codebook):
         cb = _f32(codebook)

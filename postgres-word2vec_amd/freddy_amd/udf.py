@@ -374,6 +374,14 @@ class Session:
         pos, code = np.divmod(np.arange(m * K, dtype=np.int32), K)
         self._check(self.lib.freddy_set_codebook_counts(self.h, int(table), _p(_i32(pos)), _p(_i32(code)), _p(c.reshape(-1)), m * K))
 
+    def delete_rows(self, ids):
+        """DELETE ... WHERE id = ANY(ids) on every table of the session; the pinned handles lose the rows in HBM.
+        -> rows that left google_vecs_norm."""
+        ids = _i32(ids).reshape(-1)
+        gone = C.c_int64(0)
+        self._check(self.lib.delete_rows(self.h, _p(ids), C.c_int64(ids.size), C.byref(gone)))
+        return int(gone.value)
+
     def insert_batch(self, norm_vectors):
         """freddy.c:1403-1658 for the normalised vectors of NEW terms; returns the ids given in google_vecs_norm."""
         v = _f32(norm_vectors)

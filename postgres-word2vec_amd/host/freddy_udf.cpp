@@ -91,6 +91,9 @@ struct freddy_session {
   std::vector<float> coarse;                                 // [C][d]
   int C = 0;
   int32_t pq_max_id = 0, fine_max_id = 0, ivpq_max_id = 0;
+  // the ids of pq_quantization, fine_quantization and fine_quantization_ivpq, ascending: delete_rows takes ids out of them, and the
+  // largest id that is left is where the next insert_batch goes on
+  std::vector<int32_t> pq_ids, fine_ids, ivpq_ids;
   // set_analogy_function / set_analogy_in_function (freddy--0.0.1.sql:198-199)
   std::string analogy_fn = "analogy_3cosadd", analogy_in_fn = "analogy_3cosadd_in";
   // set_groups_function (:200)
@@ -175,6 +178,7 @@ int freddy_load_pq(freddy_session_t* s, const int32_t* cb_pos, const int32_t* cb
   s->pq_cb = cb;
   s->pq_counts.assign((size_t)cb.m * cb.K, 1);
   s->pq_max_id = N ? sid[(size_t)N - 1] : 0;
+  s->pq_ids = std::move(sid);
   return 0;
 }
 
@@ -220,6 +224,8 @@ int freddy_load_ivfadc(freddy_session_t* s, const int32_t* coarse_ids_tbl, const
   s->C = C;
   s->fine_max_id = 0;
   for (int64_t i = 0; i < N; ++i) s->fine_max_id = std::max(s->fine_max_id, ids[i]);
+  s->fine_ids.assign(ids, ids + N);
+  std::sort(s->fine_ids.begin(), s->fine_ids.end());
   return 0;
 }
 
@@ -271,6 +277,7 @@ int freddy_load_ivpq(freddy_session_t* s, const int32_t* cb_pos, const int32_t* 
   s->ivpq_counts.assign((size_t)cb.m * cb.K, 1);
   s->cq_multi = cq;
   s->ivpq_max_id = N ? sid[(size_t)N - 1] : 0;
+  s->ivpq_ids = std::move(sid);
   return 0;
 }
 
@@ -953,9 +960,61 @@ int insert_batch(freddy_session_t* s, const float* norm_vectors, int32_t n, int3
   s->pq_cb = std::move(pq_cb); s->res_cb = std::move(res_cb); s->ivpq_cb = std::move(ivpq_cb);
   s->pq_counts = std::move(pq_counts); s->res_counts = std::move(res_counts); s->ivpq_counts = std::move(ivpq_counts);
   s->pq_max_id += n; s->fine_max_id += n; s->ivpq_max_id += n;
+  s->pq_ids.insert(s->pq_ids.end(), id_pq.begin(), id_pq.end());
+  s->fine_ids.insert(s->fine_ids.end(), id_fine.begin(), id_fine.end());
+  s->ivpq_ids.insert(s->ivpq_ids.end(), id_iv.begin(), id_iv.end());
   s->norm_ids.insert(s->norm_ids.end(), id_norm.begin(), id_norm.end());
   s->norm_vecs.insert(s->norm_vecs.end(), stored.begin(), stored.end());
   if (new_ids) memcpy(new_ids, id_norm.data(), sizeof(int32_t) * (size_t)n);
+  return 0;
+}
+
+// ---- delete_rows: DELETE FROM <every table of the session> WHERE id = ANY(ids) ----------------------------------
+// ascending, distinct `want` out of an ascending id list (and the rows of `e` floats that go with it); -> rows dropped
+static int64_t drop_ids(std::vector<int32_t>& ids, std::vector<float>* rows, int e, const std::vector<int32_t>& want) {
+  size_t w = 0;
+  for (size_t r = 0; r < ids.size(); ++r) {
+    if (std::binary_search(want.begin(), want.end(), ids[r])) continue;
+    if (w != r) {
+      ids[w] = ids[r];
+      if (rows) std::copy(rows->begin() + r * e, rows->begin() + (r + 1) * e, rows->begin() + w * e);
+    }
+    ++w;
+  }
+  const int64_t gone = (int64_t)(ids.size() - w);
+  ids.resize(w);
+  if (rows) rows->resize(w * (size_t)e);
+  return gone;
+}
+
+int delete_rows(freddy_session_t* s, const int32_t* ids, int64_t n, int64_t* removed) {
+  if (!s || n < 0 || (n > 0 && !ids)) return fail(-1, "bad argument");
+  if (removed) *removed = 0;
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] < 0) return fail(-1, "id %d at position %lld is negative", ids[i], (long long)i);
+  if (n == 0) return 0;
+  // the pinned handles first: a failure there drops them (they may have lost part of the rows) and leaves the host tables as they were
+  freddy_gpu_index_t** handles[] = {&s->pq, &s->ivf, &s->ivpq, &s->vecs, &s->vecs_orig};
+  for (freddy_gpu_index_t** h : handles)
+    if (*h)
+      if (int rc = freddy_gpu_remove_rows(*h, n, ids, nullptr)) {
+        const int code = gpu_fail(rc);
+        for (freddy_gpu_index_t** g : handles) if (*g) { freddy_gpu_unpin(*g); *g = nullptr; }
+        return code;
+      }
+  std::vector<int32_t> want(ids, ids + n);
+  std::sort(want.begin(), want.end());
+  want.erase(std::unique(want.begin(), want.end()), want.end());
+  const int64_t gone = drop_ids(s->norm_ids, &s->norm_vecs, s->d, want);
+  drop_ids(s->orig_ids, &s->orig_vecs, s->orig_d, want);
+  drop_ids(s->pq_ids, nullptr, 0, want);
+  drop_ids(s->fine_ids, nullptr, 0, want);
+  drop_ids(s->ivpq_ids, nullptr, 0, want);
+  // "SELECT max(id) + 1" of the next insert_batch sees the rows that are left (0 as after loading an empty table)
+  s->pq_max_id = s->pq_ids.empty() ? 0 : s->pq_ids.back();
+  s->fine_max_id = s->fine_ids.empty() ? 0 : s->fine_ids.back();
+  s->ivpq_max_id = s->ivpq_ids.empty() ? 0 : s->ivpq_ids.back();
+  if (removed) *removed = gone;
   return 0;
 }
 
