@@ -1,6 +1,6 @@
 // exact.hip -- pin_vectors, exact brute-force kNN (core_functions.c:67-81, freddy--0.0.1.sql:426-454), the
 // exact analogies on the same handle (freddy--0.0.1.sql:1231-1315; analogy.h), the post verification of pq / ivf lists against it (pv.h)
-// the approximate analogies over such lists (approx_analogy.h) and the assignment step of cluster_exact (assign.h).
+// the approximate analogies over such lists (approx_analogy.h) and the assignment step of cluster_exact (assign.h); exact_host.h: what they share.
 #include "internal.h"
 
 #include "kernels.h"
@@ -11,11 +11,9 @@
 #include "pv.h"
 #include "approx_analogy.h"
 #include "assign.h"
+#include "exact_host.h"
 
-// ---------------------------------------------------------------------------------------
-// exact brute-force kNN
-// ---------------------------------------------------------------------------------------
-// ---- exact kNN as filter + refine (exact2.h) ----------------------------------------------------------------------
+// ---- exact brute-force kNN as filter + refine (exact2.h) ----------------------------------------------------------------------
 // The table's largest |element| / largest row norm over rows [r0, r0 + n) of the row-major copy, folded into the handle's.
 int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n) {
   const bool shape_ok = ix->d % 4 == 0 && ix->d <= 512 && ix->d >= 16;
@@ -65,109 +63,47 @@ int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n) {
   return 0;
 }
 
-// What the filter passes over the whole table (exact kNN, analogies) share.  The threshold's sample: whole 32-row strips of
-// REAL rows (a zero-padded row would be a similarity of 0 that no row has), spread evenly over the table; the candidate
-// buffer: 8192 rows per query (every row under the self-check that refines every row).
-struct FilterPlan {
-  int n_sample;
-  int64_t sample_stride;
-  int cap;
-};
-static FilterPlan filter_plan(int64_t N, bool refine_all) {
-  const int64_t full_strips = N / 32;
-  const int n_sample = (int)(std::min<int64_t>(full_strips, EXF_SAMPLE / 32) * 32);
-  return {n_sample, n_sample > 0 ? std::max<int64_t>(1, full_strips / (n_sample / 32)) : 1, (int)(refine_all ? N : std::min<int64_t>(N, 8192))};
-}
-// workgroups of a filter kernel over `rows` rows: one per 256 rows, at most two per CU
-static unsigned filter_grid(const freddy_gpu_index* ix, int64_t rows) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, (int64_t)ix->n_cus * 2));
-}
-// the self-check counters the refine kernels write (allocated by the handle's first filter + refine call)
-static int ensure_viol(freddy_gpu_index* ix) {
-  if (ix->viol) return 0;
-  HIP_TRY(hipMalloc((void**)&ix->viol, 4 * sizeof(int32_t)));
-  HIP_TRY(hipMemset(ix->viol, 0, 4 * sizeof(int32_t)));
-  return 0;
-}
-
-// The filter + refine path for all rows of the table.  *fell_back = 1: a candidate buffer overflowed or a query was not
-// finite -- nothing was written, the caller runs the all-exact kernels.
+// The filter + refine path for all rows of the table (exact_host.h: the chain).  *fell_back = 1: a candidate buffer overflowed or
+// a query was not finite -- nothing was written, the caller runs the all-exact kernels.
 // q_copy: NULL, or device memory for the queries when d_queries is mapped host memory (exf_prep_kernel copies them).
 // h_out: mapped host memory [Q*k ids][Q*k similarities][2 verdict words], p_out the same block as the device sees it: the merge
 // writes there, ONE synchronisation ends the call (four 12-us copies and a second synchronisation before).
-static int exact_filter_search(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const float* d_queries, int Q, int k, int* fell_back,
-                               int32_t* h_out, int32_t* p_out, float* q_copy) {
+static int exact_filter_search(freddy_gpu_index* ix, hipStream_t s, const float* d_queries, int Q, int k, int* fell_back, int32_t* h_out, int32_t* p_out,
+                               float* q_copy) {
   *fell_back = 0;
-  const int d = ix->d, T = (d + 15) / 16, L = k, V = pick_V(L);
+  const int d = ix->d, T = (d + 15) / 16;
   const int64_t N = ix->N;
-  const bool all = (ix->tune.check_brackets & 4) != 0;
-  const FilterPlan fp = filter_plan(N, all);
-  const int n_sample = fp.n_sample, cap = fp.cap;
-  // small per-call state: [0..63] thr, [64..127] qeps, [128..191] qunscale, [192..255] cand_cnt, [256] qbad
-  if (ix->exf_small.ensure(4096) || ix->exf_qfrag.ensure((size_t)2 * T * 2 * 64 * 16) ||
-      ix->exf_sample.ensure(sizeof(float) * (size_t)EXF_QT * n_sample) || ix->exf_cand.ensure(sizeof(uint2) * (size_t)EXF_QT * cap))
+  const FilterPlan fp = filter_plan(N, (ix->tune.check_brackets & 4) != 0);
+  const size_t tile_lds = (size_t)T * 2 * 64 * 16;
+  if (ix->exf_qfrag.ensure(2 * tile_lds) || ix->exf_sample.ensure(sizeof(float) * (size_t)EXF_QT * fp.n_sample) ||
+      ix->exf_cand.ensure(sizeof(uint2) * (size_t)EXF_QT * fp.cap))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  if (int rc = ensure_viol(ix)) return rc;
-  if (ix->exf_dirty) {   // (the handle's first call, or the one after a call that failed part-way: the verdict words and the arrival counter may be anything; a call's last workgroup leaves them at zero)
-    HIP_TRY(hipMemsetAsync(ix->exf_small.as<float>() + 256, 0, 8, s));
-    HIP_TRY(hipMemsetAsync(ix->viol + 3, 0, 4, s));
-  }
-  ix->exf_dirty = true;
+  if (int rc = exf_begin(ix, s)) return rc;
   int32_t* const flags = h_out + 2 * (size_t)Q * k;
   flags[0] = flags[1] = -1;   // (before anything is enqueued: the call's last workgroup overwrites both)
+  // small per-call state: [0..63] thr, [64..127] qeps, [128..191] qunscale, [192..255] cand_cnt, [256] qbad, [257] arrived
   float* sm = ix->exf_small.as<float>();
-  float* thr = sm; float* qeps = sm + 64; float* qunscale = sm + 128;
-  int32_t* cand_cnt = reinterpret_cast<int32_t*>(sm + 192);
-  int32_t* qbad = reinterpret_cast<int32_t*>(sm + 256);
-  int32_t* arrived = reinterpret_cast<int32_t*>(sm + 257);
-  int32_t* const o_ids = p_out;
-  float* const o_sim = reinterpret_cast<float*>(p_out + (size_t)Q * k);
-  int32_t* const o_flags = p_out + 2 * (size_t)Q * k;
-  const size_t lds1 = (size_t)1 * T * 2 * 64 * 16, lds2 = 2 * lds1;
+  ExfPass p;
+  p.labels = &EXF_KNN_LABELS; p.fp = fp; p.thr = sm; p.qeps = sm + 64; p.qunscale = sm + 128; p.cand_cnt = reinterpret_cast<int32_t*>(sm + 192);
+  p.flags = p_out + 2 * (size_t)Q * k; p.k = k; p.grid_q = EXF_QT; p.total_wgs = Q; p.sample_when_empty = true;
+  ExfArgs fa;
+  fa.xf = ix->exf_xf.as<h8v>(); fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>(); fa.qunscale = p.qunscale; fa.thr = p.thr; fa.cand_cnt = p.cand_cnt;
+  fa.cand = ix->exf_cand.as<uint2>(); fa.cap = fp.cap;
   for (int q0 = 0; q0 < Q; q0 += EXF_QT) {
-    const int nq = std::min(EXF_QT, Q - q0);
-    const int NT = nq <= 32 ? 1 : 2;
-    ExfPrepArgs pa;
-    pa.queries = d_queries + (size_t)q0 * d; pa.nq = nq; pa.d = d; pa.T = T; pa.xmax_norm = ix->exf_xnorm; pa.ex = ix->exf_ex;
-    pa.eps_factor = exf_eps_factor(d); pa.qfrag = ix->exf_qfrag.as<h8v>(); pa.qeps = qeps; pa.qunscale = qunscale; pa.qbad = qbad;
-    pa.copy_out = q_copy ? q_copy + (size_t)q0 * d : nullptr;
-    timed_launch(ix, s, "exact_prep", [&] { hipLaunchKernelGGL(exf_prep_kernel, dim3(EXF_QT), dim3(256), 0, s, pa); });
-    HIP_TRY(hipGetLastError());
-    ExfArgs fa;
-    fa.xf = ix->exf_xf.as<h8v>(); fa.n_rows = n_sample; fa.strip_stride = fp.sample_stride; fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>();
-    fa.qunscale = qunscale; fa.sample_out = ix->exf_sample.as<float>(); fa.thr = thr; fa.cand_cnt = cand_cnt; fa.cand = ix->exf_cand.as<uint2>(); fa.cap = cap;
-    timed_launch(ix, s, "exact_sample", [&] {
-      if (NT == 1) hipLaunchKernelGGL((exf_filter_kernel<1, true>), dim3(filter_grid(ix, n_sample)), dim3(EXF_WG), lds1, s, fa);
-      else hipLaunchKernelGGL((exf_filter_kernel<2, true>), dim3(filter_grid(ix, n_sample)), dim3(EXF_WG), lds2, s, fa);
-    });
-    HIP_TRY(hipGetLastError());
-    ExfThrArgs ta;
-    ta.sample = fa.sample_out; ta.n_sample = n_sample; ta.nq = nq; ta.k = k; ta.qeps = qeps; ta.qunscale = qunscale; ta.thr = thr; ta.refine_all = all ? 1 : 0; ta.cand_cnt = cand_cnt;
-    timed_launch(ix, s, "exact_threshold", [&] { hipLaunchKernelGGL(exf_threshold_kernel, dim3(EXF_QT), dim3(64 * EXF_TW), 0, s, ta); });
-    HIP_TRY(hipGetLastError());
-    fa.n_rows = N; fa.strip_stride = 1; fa.sample_out = nullptr;
-    timed_launch(ix, s, "exact_filter", [&] {
-      if (NT == 1) hipLaunchKernelGGL((exf_filter_kernel<1, false>), dim3(filter_grid(ix, N)), dim3(EXF_WG), lds1, s, fa);
-      else hipLaunchKernelGGL((exf_filter_kernel<2, false>), dim3(filter_grid(ix, N)), dim3(EXF_WG), lds2, s, fa);
-    });
-    HIP_TRY(hipGetLastError());
-    ExfRefineArgs ra;
-    ra.rows = ix->coarse; ra.queries = (q_copy ? q_copy : d_queries) + (size_t)q0 * d; ra.cand = fa.cand; ra.cand_cnt = cand_cnt; ra.qeps = qeps;
-    ra.viol = ix->viol; ra.cap = cap; ra.d = d; ra.L = L; ra.count_checked = all ? 1 : 0;
-    ra.ids = ix->ids; ra.out_ids = o_ids + (size_t)q0 * k; ra.out_sim = o_sim + (size_t)q0 * k; ra.k = k; ra.arrived = arrived; ra.total_wgs = Q;
-    ra.qbad = qbad; ra.flags_out = o_flags;
-    const size_t rlds = exf_refine_lds(d, V == 1 ? 1 : 2);
-    timed_launch(ix, s, "exact_refine", [&] {
-      switch (V) {
-        case 1: hipLaunchKernelGGL((exf_refine_kernel<1>), dim3(nq), dim3(64 * EXF_TW), rlds, s, ra); break;
-        default: hipLaunchKernelGGL((exf_refine_kernel<2>), dim3(nq), dim3(64 * EXF_TW), rlds, s, ra); break;
-      }
-    });
-    HIP_TRY(hipGetLastError());
+    p.nq = std::min(EXF_QT, Q - q0);
+    p.queries = d_queries + (size_t)q0 * d; p.copy_out = q_copy ? q_copy + (size_t)q0 * d : nullptr;
+    p.out_ids = p_out + (size_t)q0 * k; p.out_sim = reinterpret_cast<float*>(p_out + (size_t)Q * k) + (size_t)q0 * k;
+    if (int rc = exf_chain(ix, s, p, N, [&](auto sample, int64_t n_rows) {
+      constexpr bool SAMPLE = decltype(sample)::value;
+      filter_rows(fa, fp, SAMPLE, n_rows, ix->exf_sample.as<float>());
+      const dim3 grid(filter_grid(ix, n_rows));
+      if (p.nq <= 32) hipLaunchKernelGGL((exf_filter_kernel<1, SAMPLE>), grid, dim3(EXF_WG), tile_lds, s, fa);
+      else hipLaunchKernelGGL((exf_filter_kernel<2, SAMPLE>), grid, dim3(EXF_WG), 2 * tile_lds, s, fa);
+    })) return rc;
   }
   HIP_TRY(hipStreamSynchronize(s));
-  if (flags[0] == -1 || flags[1] == -1) return fail(FREDDY_E_HIP, "exact search: the verdict words did not arrive");
-  ix->exf_dirty = false;
+  if (int rc = exf_verdict_arrived(flags, "exact search")) return rc;
+  exf_complete(ix);
   if (flags[0] || flags[1]) *fell_back = 1;
   return 0;
 }
@@ -272,19 +208,18 @@ static int exact_search_rows(freddy_gpu_index* ix, const float* queries, int32_t
       d_q = ws->w_q.as<float>();
     }
     int fell_back = 0;
-    if (int rc = exact_filter_search(ix, ws, s, d_q, Q, k, &fell_back, h_out, static_cast<int32_t*>(dp), q_pinned ? ws->w_q.as<float>() : nullptr)) return rc;
+    if (int rc = exact_filter_search(ix, s, d_q, Q, k, &fell_back, h_out, static_cast<int32_t*>(dp), q_pinned ? ws->w_q.as<float>() : nullptr)) return rc;
     if (!fell_back) {
       memcpy(out_ids, h_out, n_out * 4);
       memcpy(out_sim, h_out + n_out, n_out * 4);
       return FREDDY_OK;
     }
   }
-  int chunk_blocks = 8;   // 512 rows per workgroup-chunk; longer chunks once the grid is large enough
   int EX_QT = ex_qt(V, Q);
   if (EX_QT == 16 && exact_scan_lds(d, 16) > EX_MAX_LDS) EX_QT = 8;   // (d > 2048: sixteen queries do not fit the LDS; d <= EX_MAX_D: eight do)
   const int qgroups = (Q + EX_QT - 1) / EX_QT;
-  while ((n_blocks + chunk_blocks - 1) / chunk_blocks * (int64_t)qgroups > 8192 && chunk_blocks < 1024) chunk_blocks *= 2;
-  const int nchunk = (int)std::max<int64_t>(1, (n_blocks + chunk_blocks - 1) / chunk_blocks);
+  int chunk_blocks;
+  const int nchunk = scan_chunks(n_blocks, qgroups, &chunk_blocks);
   if (ws->w_q.ensure(sizeof(float) * (size_t)Q * d) || ws->w_out_ids.ensure(sizeof(int32_t) * (size_t)Q * k) ||
       ws->w_out_dist.ensure(sizeof(float) * (size_t)Q * k) ||
       ws->w_part.ensure(sizeof(u64) * (size_t)Q * nchunk * EX_WAVES * L))
@@ -369,13 +304,11 @@ static constexpr size_t EXJ_PASS_BYTES = (size_t)2 << 30;
 // *qbad_out: a query was not finite (no list is valid, the passes stop).
 static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const std::vector<int32_t>& rows, const float* queries, int Q, int k,
                              int32_t* out_ids, float* out_sim, std::vector<int32_t>& cnt_out, int* cap_out, bool* qbad_out) {
-  const int d = ix->d, T = (d + 15) / 16, V = pick_V(k);
+  const int d = ix->d, T = (d + 15) / 16;
   const int64_t nT = (int64_t)rows.size(), strips = (nT + 31) / 32;
-  const bool all = (ix->tune.check_brackets & 4) != 0;
-  const FilterPlan fp = filter_plan(nT, all);
+  const FilterPlan fp = filter_plan(nT, (ix->tune.check_brackets & 4) != 0);
   const int n_sample = fp.n_sample, cap = fp.cap;
-  *cap_out = cap;
-  *qbad_out = false;
+  *cap_out = cap; *qbad_out = false;
   // the query tile: 128 queries (NT = 4) when more than one 64-tile is needed and four tiles' fragments fit the LDS
   int NT = Q <= 32 ? 1 : 2;
   const size_t tile_lds = (size_t)T * 2 * 64 * 16;
@@ -385,24 +318,16 @@ static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s,
   const int Qc = (int)std::min<int64_t>(Q, std::max<int64_t>(128, (int64_t)(EXJ_PASS_BYTES / per_query) / 128 * 128));   // queries per pass
   const int QcPad = (Qc + QT - 1) / QT * QT;
   // per-pass state in w_found: [QcPad] thr, qeps, qunscale, cand_cnt, then the refine kernel's two verdict words
-  if (ix->exf_small.ensure(4096) || ws->w_found.ensure(sizeof(float) * (4 * (size_t)QcPad + 2)) || ws->w_sub_rows.ensure(sizeof(int32_t) * (size_t)nT) ||
+  if (ws->w_found.ensure(sizeof(float) * (4 * (size_t)QcPad + 2)) || ws->w_sub_rows.ensure(sizeof(int32_t) * (size_t)nT) ||
       ws->w_resid.ensure((size_t)strips * T * 2 * 64 * 16) || ix->exf_qfrag.ensure((size_t)(QcPad / 32) * tile_lds) || ws->w_q.ensure(sizeof(float) * (size_t)Q * d) ||
       ix->exf_sample.ensure(sizeof(float) * (size_t)QcPad * std::max(n_sample, 1)) || ix->exf_cand.ensure(sizeof(uint2) * (size_t)Qc * cap) ||
       ws->w_out_ids.ensure(sizeof(int32_t) * (size_t)Qc * k) || ws->w_out_dist.ensure(sizeof(float) * (size_t)Qc * k))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  if (int rc = ensure_viol(ix)) return rc;
-  float* sm = ix->exf_small.as<float>();
-  int32_t* qbad = reinterpret_cast<int32_t*>(sm + 256);       // (exact kNN's words: one protocol, exf_dirty)
-  int32_t* arrived = reinterpret_cast<int32_t*>(sm + 257);
-  if (ix->exf_dirty) {
-    HIP_TRY(hipMemsetAsync(sm + 256, 0, 8, s));
-    HIP_TRY(hipMemsetAsync(ix->viol + 3, 0, 4, s));
-  }
-  ix->exf_dirty = true;
-  float* thr = ws->w_found.as<float>();
-  float* qeps = thr + QcPad; float* qunscale = qeps + QcPad;
-  int32_t* cand_cnt = reinterpret_cast<int32_t*>(qunscale + QcPad);
-  int32_t* flags = cand_cnt + QcPad;
+  if (int rc = exf_begin(ix, s)) return rc;
+  ExfPass p;
+  p.labels = &EXF_JOIN_LABELS; p.fp = fp; p.thr = ws->w_found.as<float>(); p.qeps = p.thr + QcPad; p.qunscale = p.qeps + QcPad;
+  p.cand_cnt = reinterpret_cast<int32_t*>(p.qunscale + QcPad); p.flags = p.cand_cnt + QcPad;
+  p.copy_out = nullptr; p.k = k; p.out_ids = ws->w_out_ids.as<int32_t>(); p.out_sim = ws->w_out_dist.as<float>(); p.sample_when_empty = false;
   const int32_t* map = ws->w_sub_rows.as<int32_t>();
   h8v* xf = ws->w_resid.as<h8v>();
   HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, rows.data(), sizeof(int32_t) * (size_t)nT, hipMemcpyHostToDevice, s));
@@ -413,23 +338,18 @@ static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s,
   });
   HIP_TRY(hipGetLastError());
   cnt_out.assign((size_t)Q, 0);
-  const size_t rlds = exf_refine_lds(d, V == 1 ? 1 : 2);
+  ExjArgs fa;
+  fa.xf = xf; fa.map = map; fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>(); fa.qunscale = p.qunscale; fa.thr = p.thr; fa.cand_cnt = p.cand_cnt;
+  fa.cand = ix->exf_cand.as<uint2>(); fa.cap = cap;
   for (int q0 = 0; q0 < Q; q0 += Qc) {
-    const int nq = std::min(Qc, Q - q0), qtiles = (nq + QT - 1) / QT, Qpad = qtiles * QT;
-    const float* d_q = ws->w_q.as<float>() + (size_t)q0 * d;
-    HIP_TRY(hipMemsetAsync(flags, 0xFF, 8, s));   // (-1, -1: the pass's last refine workgroup overwrites both)
-    ExfPrepArgs pa;
-    pa.queries = d_q; pa.nq = nq; pa.d = d; pa.T = T; pa.xmax_norm = ix->exf_xnorm; pa.ex = ix->exf_ex; pa.eps_factor = exf_eps_factor(d);
-    pa.qfrag = ix->exf_qfrag.as<h8v>(); pa.qeps = qeps; pa.qunscale = qunscale; pa.qbad = qbad; pa.copy_out = nullptr;
-    timed_launch(ix, s, "exact_join_prep", [&] { hipLaunchKernelGGL(exf_prep_kernel, dim3((unsigned)Qpad), dim3(256), 0, s, pa); });
-    HIP_TRY(hipGetLastError());
-    ExjArgs fa;
-    fa.xf = xf; fa.map = map; fa.n_rows = n_sample; fa.strip_stride = fp.sample_stride; fa.T = T; fa.nq = nq; fa.qfrag = ix->exf_qfrag.as<h8v>();
-    fa.qunscale = qunscale; fa.sample_out = ix->exf_sample.as<float>(); fa.thr = thr; fa.cand_cnt = cand_cnt; fa.cand = ix->exf_cand.as<uint2>(); fa.cap = cap;
+    const int nq = std::min(Qc, Q - q0), qtiles = (nq + QT - 1) / QT;
+    p.nq = fa.nq = nq; p.grid_q = (unsigned)(qtiles * QT); p.total_wgs = nq; p.queries = ws->w_q.as<float>() + (size_t)q0 * d;
+    HIP_TRY(hipMemsetAsync(p.flags, 0xFF, 8, s));   // (-1, -1: the pass's last refine workgroup overwrites both)
     // strip chunks: a workgroup's 8 waves take 8 strips per step; with many query tiles every workgroup stays long enough (>= 64
     // strips) to pay for its LDS image of the tile
-    auto launch = [&](auto sample, int64_t n_rows) {
+    if (int rc = exf_chain(ix, s, p, nT, [&](auto sample, int64_t n_rows) {
       constexpr bool SAMPLE = decltype(sample)::value;
+      filter_rows(fa, fp, SAMPLE, n_rows, ix->exf_sample.as<float>());
       const int64_t wg_steps = (n_rows + 255) / 256;
       const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(wg_steps, std::max<int64_t>((int64_t)ix->n_cus * 2 / qtiles, (wg_steps + 7) / 8)));
       const dim3 grid((unsigned)gx, (unsigned)qtiles);
@@ -438,38 +358,18 @@ static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s,
         case 2: hipLaunchKernelGGL((exj_filter_kernel<2, SAMPLE>), grid, dim3(EXF_WG), 2 * tile_lds, s, fa); break;
         default: hipLaunchKernelGGL((exj_filter_kernel<4, SAMPLE>), grid, dim3(EXF_WG), 4 * tile_lds, s, fa); break;
       }
-    };
-    if (n_sample > 0) {
-      timed_launch(ix, s, "exact_join_sample", [&] { launch(std::true_type(), n_sample); });
-      HIP_TRY(hipGetLastError());
-    }
-    ExfThrArgs ta;
-    ta.sample = fa.sample_out; ta.n_sample = n_sample; ta.nq = nq; ta.k = k; ta.qeps = qeps; ta.qunscale = qunscale; ta.thr = thr; ta.refine_all = all ? 1 : 0; ta.cand_cnt = cand_cnt;
-    timed_launch(ix, s, "exact_join_threshold", [&] { hipLaunchKernelGGL(exf_threshold_kernel, dim3((unsigned)Qpad), dim3(64 * EXF_TW), 0, s, ta); });
-    HIP_TRY(hipGetLastError());
-    fa.n_rows = nT; fa.strip_stride = 1; fa.sample_out = nullptr;
-    timed_launch(ix, s, "exact_join_filter", [&] { launch(std::false_type(), nT); });
-    HIP_TRY(hipGetLastError());
-    ExfRefineArgs ra;
-    ra.rows = ix->coarse; ra.queries = d_q; ra.cand = fa.cand; ra.cand_cnt = cand_cnt; ra.qeps = qeps; ra.viol = ix->viol; ra.cap = cap; ra.d = d; ra.L = k;
-    ra.count_checked = all ? 1 : 0; ra.ids = ix->ids; ra.out_ids = ws->w_out_ids.as<int32_t>(); ra.out_sim = ws->w_out_dist.as<float>(); ra.k = k;
-    ra.arrived = arrived; ra.total_wgs = nq; ra.qbad = qbad; ra.flags_out = flags;
-    timed_launch(ix, s, "exact_join_refine", [&] {
-      if (V == 1) hipLaunchKernelGGL((exf_refine_kernel<1>), dim3((unsigned)nq), dim3(64 * EXF_TW), rlds, s, ra);
-      else hipLaunchKernelGGL((exf_refine_kernel<2>), dim3((unsigned)nq), dim3(64 * EXF_TW), rlds, s, ra);
-    });
-    HIP_TRY(hipGetLastError());
+    })) return rc;
     int32_t h_flags[2] = {-1, -1};
     const size_t n_out = (size_t)nq * k;
-    HIP_TRY(hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(cnt_out.data() + q0, cand_cnt, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_flags, p.flags, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cnt_out.data() + q0, p.cand_cnt, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(out_ids + (size_t)q0 * k, ws->w_out_ids.p, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(out_sim + (size_t)q0 * k, ws->w_out_dist.p, sizeof(float) * n_out, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (h_flags[0] == -1 || h_flags[1] == -1) return fail(FREDDY_E_HIP, "exact join: the verdict words did not arrive");
+    if (int rc = exf_verdict_arrived(h_flags, "exact join")) return rc;
     if (h_flags[1]) { *qbad_out = true; break; }   // (the refine kernel has cleared its device-side words)
   }
-  ix->exf_dirty = false;
+  exf_complete(ix);
   return 0;
 }
 
@@ -530,37 +430,6 @@ extern "C" int freddy_gpu_last_exact_join_stats(const freddy_gpu_index_t* ix, in
 }
 
 // ---- exact analogies (analogy.h) ----------------------------------------------------------------------------------------
-// The all-exact path for the na analogies at d_in_rows (device [na][3] table rows): scores of every eligible row, per-wave lists,
-// one merge per analogy into d_ids / d_score ([na][k]).  Enqueued only.
-static int analogy_scan(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, int M, const int32_t* d_in_rows, int na, int k, const float* xb,
-                        const int32_t* pos, int64_t n_rows, int64_t n_blocks, int32_t* d_ids, double* d_score) {
-  const int d = ix->d;
-  const int AT = M == 1 ? 8 : 4;
-  const int groups = (na + AT - 1) / AT;
-  int chunk_blocks = 8;
-  while ((n_blocks + chunk_blocks - 1) / chunk_blocks * (int64_t)groups > 8192 && chunk_blocks < 1024) chunk_blocks *= 2;
-  const int nchunk = (int)std::max<int64_t>(1, (n_blocks + chunk_blocks - 1) / chunk_blocks);
-  if (ws->w_qc.ensure(sizeof(float) * (size_t)na * M * d) || ws->w_part.ensure(sizeof(AnEnt) * (size_t)na * nchunk * AN_WAVES * k))
-    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  float* cols = ws->w_qc.as<float>();
-  timed_launch(ix, s, "analogy_gather", [&] { hipLaunchKernelGGL(an_gather_kernel, dim3((unsigned)(na * M)), dim3(256), 0, s, ix->coarse, d, d_in_rows, na, M, 0, cols); });
-  HIP_TRY(hipGetLastError());
-  AnScanArgs sa;
-  sa.xb = xb; sa.pos = pos; sa.n_rows = n_rows; sa.n_blocks = (int)n_blocks; sa.chunk_blocks = chunk_blocks; sa.nchunk = nchunk;
-  sa.cols = cols; sa.in_rows = d_in_rows; sa.na = na; sa.d = d; sa.k = k; sa.part = ws->w_part.as<AnEnt>();
-  const dim3 grid((unsigned)nchunk, (unsigned)groups);
-  timed_launch(ix, s, "analogy_scan", [&] {
-    if (M == 1) hipLaunchKernelGGL((an_scan_kernel<1, 8>), grid, dim3(AN_WG), (an_scan_lds<1, 8>(d)), s, sa);
-    else hipLaunchKernelGGL((an_scan_kernel<3, 4>), grid, dim3(AN_WG), (an_scan_lds<3, 4>(d)), s, sa);
-  });
-  HIP_TRY(hipGetLastError());
-  timed_launch(ix, s, "analogy_merge", [&] {
-    hipLaunchKernelGGL(an_merge_kernel, dim3((unsigned)na), dim3(AN_WG), 0, s, (const AnEnt*)sa.part, nchunk * AN_WAVES, k, ix->ids, d_ids, d_score);
-  });
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
 // Analogies per workgroup of the pair-direction scan: the smallest tile of 1, 2, 4, 8 that holds the call (a tile's spare columns
 // repeat the last analogy: their divisions are done and thrown away), 8 beyond -- per (row, analogy) the kernel keeps a sum, a
 // length and three excluded rows in registers and 8 d bytes + 4.5 KiB of lists in LDS, so 8 analogies stay far from either budget
@@ -571,31 +440,33 @@ static int an_pair_tile(int na, int d) {
   return at;
 }
 
-// analogy_scan for FREDDY_ANALOGY_PAIR_DIRECTION: the columns (A, v3) per analogy, the two-sweep scan, the same merge.  Enqueued only.
-static int analogy_pair_scan(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const int32_t* d_in_rows, int na, int k, const float* xb,
-                             const int32_t* pos, int64_t n_rows, int64_t n_blocks, int32_t* d_ids, double* d_score) {
+// The all-exact path for the na analogies at d_in_rows (device [na][3] table rows): their columns, scores of every eligible row and
+// per-wave lists, one merge per analogy into d_ids / d_score ([na][k]).  Enqueued only.  M = 1 (3CosAdd: one column, 8 analogies per
+// workgroup), 3 (3CosMul: 4 analogies) or 0: FREDDY_ANALOGY_PAIR_DIRECTION, the columns (A, v3) per analogy and the two-sweep scan.
+static int analogy_scan(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, int M, const int32_t* d_in_rows, int na, int k, const float* xb,
+                        const int32_t* pos, int64_t n_rows, int64_t n_blocks, int32_t* d_ids, double* d_score) {
   const int d = ix->d;
-  const int AT = an_pair_tile(na, d);
+  const int AT = M == 0 ? an_pair_tile(na, d) : M == 1 ? 8 : 4, ncols = M == 0 ? 2 : M;
   const int groups = (na + AT - 1) / AT;
-  int chunk_blocks = 8;
-  while ((n_blocks + chunk_blocks - 1) / chunk_blocks * (int64_t)groups > 8192 && chunk_blocks < 1024) chunk_blocks *= 2;
-  const int nchunk = (int)std::max<int64_t>(1, (n_blocks + chunk_blocks - 1) / chunk_blocks);
-  if (ws->w_qc.ensure(sizeof(float) * (size_t)na * 2 * d) || ws->w_part.ensure(sizeof(AnEnt) * (size_t)na * nchunk * AN_WAVES * k))
+  int chunk_blocks;
+  const int nchunk = scan_chunks(n_blocks, groups, &chunk_blocks);
+  if (ws->w_qc.ensure(sizeof(float) * (size_t)na * ncols * d) || ws->w_part.ensure(sizeof(AnEnt) * (size_t)na * nchunk * AN_WAVES * k))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   float* cols = ws->w_qc.as<float>();
-  timed_launch(ix, s, "analogy_pair_columns", [&] { hipLaunchKernelGGL(an_pair_columns_kernel, dim3((unsigned)na), dim3(64), 0, s, ix->coarse, d, d_in_rows, cols); });
+  if (M == 0) timed_launch(ix, s, "analogy_pair_columns", [&] { hipLaunchKernelGGL(an_pair_columns_kernel, dim3((unsigned)na), dim3(64), 0, s, ix->coarse, d, d_in_rows, cols); });
+  else timed_launch(ix, s, "analogy_gather", [&] { hipLaunchKernelGGL(an_gather_kernel, dim3((unsigned)(na * M)), dim3(256), 0, s, ix->coarse, d, d_in_rows, na, M, 0, cols); });
   HIP_TRY(hipGetLastError());
   AnScanArgs sa;
   sa.xb = xb; sa.pos = pos; sa.n_rows = n_rows; sa.n_blocks = (int)n_blocks; sa.chunk_blocks = chunk_blocks; sa.nchunk = nchunk;
   sa.cols = cols; sa.in_rows = d_in_rows; sa.na = na; sa.d = d; sa.k = k; sa.part = ws->w_part.as<AnEnt>();
   const dim3 grid((unsigned)nchunk, (unsigned)groups);
-  timed_launch(ix, s, "analogy_pair_scan", [&] {
-    switch (AT) {
-      case 8: hipLaunchKernelGGL((an_pair_scan_kernel<8>), grid, dim3(AN_WG), an_pair_lds<8>(d), s, sa); break;
-      case 4: hipLaunchKernelGGL((an_pair_scan_kernel<4>), grid, dim3(AN_WG), an_pair_lds<4>(d), s, sa); break;
-      case 2: hipLaunchKernelGGL((an_pair_scan_kernel<2>), grid, dim3(AN_WG), an_pair_lds<2>(d), s, sa); break;
-      default: hipLaunchKernelGGL((an_pair_scan_kernel<1>), grid, dim3(AN_WG), an_pair_lds<1>(d), s, sa); break;
-    }
+  timed_launch(ix, s, M == 0 ? "analogy_pair_scan" : "analogy_scan", [&] {
+    if (M == 1) hipLaunchKernelGGL((an_scan_kernel<1, 8>), grid, dim3(AN_WG), (an_scan_lds<1, 8>(d)), s, sa);
+    else if (M == 3) hipLaunchKernelGGL((an_scan_kernel<3, 4>), grid, dim3(AN_WG), (an_scan_lds<3, 4>(d)), s, sa);
+    else if (AT == 8) hipLaunchKernelGGL((an_pair_scan_kernel<8>), grid, dim3(AN_WG), an_pair_lds<8>(d), s, sa);
+    else if (AT == 4) hipLaunchKernelGGL((an_pair_scan_kernel<4>), grid, dim3(AN_WG), an_pair_lds<4>(d), s, sa);
+    else if (AT == 2) hipLaunchKernelGGL((an_pair_scan_kernel<2>), grid, dim3(AN_WG), an_pair_lds<2>(d), s, sa);
+    else hipLaunchKernelGGL((an_pair_scan_kernel<1>), grid, dim3(AN_WG), an_pair_lds<1>(d), s, sa);
   });
   HIP_TRY(hipGetLastError());
   timed_launch(ix, s, "analogy_merge", [&] {
@@ -607,14 +478,14 @@ static int analogy_pair_scan(freddy_gpu_index* ix, Workspace* ws, hipStream_t s,
 
 // The filter + refine path over the whole table, passes of AN_PASS analogies.  flags[p] (device, zeroed here) != 0: pass p's
 // results are not valid (its columns were not finite, or a candidate buffer overflowed) -- the caller redoes it; flags[passes + p]
-// receives the number of candidates pass p refined.  Enqueued only.
+// receives the number of candidates pass p refined.  Enqueued only.  Its filter, threshold and refine kernels and its double
+// thresholds are its own; the plan, the prep kernel and the sample / filter launch pair are exact kNN's (exact_host.h).
 static int analogy_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, int M, const int32_t* d_in_rows, int na, int k,
                           int32_t* d_ids, double* d_score, int32_t* flags) {
   const int d = ix->d, T = (d + 15) / 16;
   const int64_t N = ix->N;
-  const bool all = (ix->tune.check_brackets & 8) != 0;
-  const FilterPlan fp = filter_plan(N, all);
-  const int n_sample = fp.n_sample, cap = fp.cap;
+  const FilterPlan fp = filter_plan(N, (ix->tune.check_brackets & 8) != 0);
+  const int n_sample = fp.n_sample, cap = fp.cap, all = fp.refine_all ? 1 : 0;
   const int passes = (na + AN_PASS - 1) / AN_PASS;
   // per-pass state: [0, 256) tau (double [32]), [256, 640) eps, [640, 1024) unscale (float [96]), [1024, 1152) candidate counts
   if (ws->w_found.ensure(2048) || ix->exf_qfrag.ensure((size_t)M * T * 2 * 64 * 16) || ws->w_qc.ensure(sizeof(float) * (size_t)M * AN_PASS * d) ||
@@ -627,6 +498,7 @@ static int analogy_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, in
   float* qunscale = reinterpret_cast<float*>(sm + 640);
   int32_t* cand_cnt = reinterpret_cast<int32_t*>(sm + 1024);
   float* cols = ws->w_qc.as<float>();
+  double* sample = ix->exf_sample.as<double>();
   HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int32_t) * 2 * passes, s));
   const size_t flds = an_filter_lds(M, d);
   for (int p = 0; p < passes; ++p) {
@@ -636,36 +508,31 @@ static int analogy_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, in
       hipLaunchKernelGGL(an_gather_kernel, dim3((unsigned)(M * AN_PASS)), dim3(256), 0, s, ix->coarse, d, in_rows, np, M, 1, cols);
     });
     HIP_TRY(hipGetLastError());
-    ExfPrepArgs pa;
-    pa.queries = cols; pa.nq = M * AN_PASS; pa.d = d; pa.T = T; pa.xmax_norm = ix->exf_xnorm; pa.ex = ix->exf_ex;
-    pa.eps_factor = exf_eps_factor(d); pa.qfrag = ix->exf_qfrag.as<h8v>(); pa.qeps = qeps; pa.qunscale = qunscale; pa.qbad = flags + p;
-    pa.copy_out = nullptr;
+    const ExfPrepArgs pa = exf_prep_args(ix, cols, M * AN_PASS, qeps, qunscale, flags + p, nullptr);
     timed_launch(ix, s, "analogy_prep", [&] { hipLaunchKernelGGL(exf_prep_kernel, dim3((unsigned)(M * AN_PASS)), dim3(256), 0, s, pa); });
     HIP_TRY(hipGetLastError());
     AnFilterArgs fa;
-    fa.xf = ix->exf_xf.as<h8v>(); fa.n_rows = n_sample; fa.strip_stride = fp.sample_stride; fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>();
-    fa.qunscale = qunscale; fa.qeps = qeps; fa.in_rows = in_rows; fa.na = np; fa.sample_out = ix->exf_sample.as<double>();
-    fa.thr = thr; fa.cand_cnt = cand_cnt; fa.cand = ix->exf_cand.as<uint4>(); fa.cap = cap; fa.refine_all = all ? 1 : 0;
+    fa.xf = ix->exf_xf.as<h8v>(); fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>(); fa.qunscale = qunscale; fa.qeps = qeps; fa.in_rows = in_rows; fa.na = np;
+    fa.thr = thr; fa.cand_cnt = cand_cnt; fa.cand = ix->exf_cand.as<uint4>(); fa.cap = cap; fa.refine_all = all;
+    auto filter = [&](auto smp, int64_t n_rows) {
+      constexpr bool SAMPLE = decltype(smp)::value;
+      filter_rows(fa, fp, SAMPLE, n_rows, sample);
+      if (M == 1) hipLaunchKernelGGL((an_filter_kernel<1, SAMPLE>), dim3(filter_grid(ix, n_rows)), dim3(EXF_WG), flds, s, fa);
+      else hipLaunchKernelGGL((an_filter_kernel<3, SAMPLE>), dim3(filter_grid(ix, n_rows)), dim3(EXF_WG), flds, s, fa);
+    };
     if (n_sample > 0) {
-      timed_launch(ix, s, "analogy_sample", [&] {
-        if (M == 1) hipLaunchKernelGGL((an_filter_kernel<1, true>), dim3(filter_grid(ix, n_sample)), dim3(EXF_WG), flds, s, fa);
-        else hipLaunchKernelGGL((an_filter_kernel<3, true>), dim3(filter_grid(ix, n_sample)), dim3(EXF_WG), flds, s, fa);
-      });
+      timed_launch(ix, s, "analogy_sample", [&] { filter(std::true_type(), n_sample); });
       HIP_TRY(hipGetLastError());
     }
     timed_launch(ix, s, "analogy_threshold", [&] {
-      hipLaunchKernelGGL(an_threshold_kernel, dim3(AN_PASS), dim3(AN_WG), 0, s, (const double*)fa.sample_out, n_sample, np, k, all ? 1 : 0, thr, cand_cnt);
+      hipLaunchKernelGGL(an_threshold_kernel, dim3(AN_PASS), dim3(AN_WG), 0, s, (const double*)sample, n_sample, np, k, all, thr, cand_cnt);
     });
     HIP_TRY(hipGetLastError());
-    fa.n_rows = N; fa.strip_stride = 1; fa.sample_out = nullptr;
-    timed_launch(ix, s, "analogy_filter", [&] {
-      if (M == 1) hipLaunchKernelGGL((an_filter_kernel<1, false>), dim3(filter_grid(ix, N)), dim3(EXF_WG), flds, s, fa);
-      else hipLaunchKernelGGL((an_filter_kernel<3, false>), dim3(filter_grid(ix, N)), dim3(EXF_WG), flds, s, fa);
-    });
+    timed_launch(ix, s, "analogy_filter", [&] { filter(std::false_type(), N); });
     HIP_TRY(hipGetLastError());
     AnRefineArgs ra;
     ra.rows = ix->coarse; ra.cols = cols; ra.cand = fa.cand; ra.cand_cnt = cand_cnt; ra.qeps = qeps; ra.in_rows = in_rows; ra.viol = ix->viol;
-    ra.flag = flags + p; ra.cand_total = flags + passes + p; ra.cap = cap; ra.d = d; ra.k = k; ra.count_checked = all ? 1 : 0; ra.ids = ix->ids;
+    ra.flag = flags + p; ra.cand_total = flags + passes + p; ra.cap = cap; ra.d = d; ra.k = k; ra.count_checked = all; ra.ids = ix->ids;
     ra.out_ids = d_ids + (size_t)a0 * k; ra.out_score = d_score + (size_t)a0 * k;
     timed_launch(ix, s, "analogy_refine", [&] {
       if (M == 1) hipLaunchKernelGGL((an_refine_kernel<1>), dim3((unsigned)np), dim3(64 * AN_RW), an_refine_lds(1, d), s, ra);
@@ -692,16 +559,8 @@ extern "C" int freddy_gpu_exact_analogy(freddy_gpu_index_t* ix, int32_t method, 
   if (std::max(an_scan_lds<1, 8>(d), an_scan_lds<3, 4>(d)) > AN_MAX_LDS) return fail(FREDDY_E_LIMIT, "d=%d too large for the exact analogy", d);
   for (size_t i = 0; i < (size_t)Q * k; ++i) { out_ids[i] = -1; out_score[i] = -HUGE_VAL; }
   if (Q == 0) return FREDDY_OK;
-  // the INNER JOINs: an analogy with an unknown id has no rows at all; the others, compacted
   std::vector<int32_t> live, rows3;
-  for (int32_t q = 0; q < Q; ++q) {
-    int32_t r[3];
-    bool ok = true;
-    for (int m = 0; m < 3 && ok; ++m) ok = (r[m] = row_of(ix->h_ids, triples[(size_t)q * 3 + m])) >= 0;
-    if (!ok) continue;
-    live.push_back(q);
-    rows3.insert(rows3.end(), r, r + 3);
-  }
+  resolve_triples(ix->h_ids, triples, Q, live, rows3);
   const int na = (int)live.size();
   if (na == 0) return FREDDY_OK;
   HIP_TRY(hipSetDevice(ix->device));
@@ -747,9 +606,8 @@ extern "C" int freddy_gpu_exact_analogy(freddy_gpu_index_t* ix, int32_t method, 
   auto scan_range = [&](int a0, int n) -> int {
     for (int c0 = a0; c0 < a0 + n; c0 += chunk) {
       const int nc = std::min(chunk, a0 + n - c0);
-      const int rc = pair ? analogy_pair_scan(ix, ws, s, d_rows + (size_t)c0 * 3, nc, k, xb, pos, n_rows, n_blocks, d_ids + (size_t)c0 * k, d_score + (size_t)c0 * k)
-                          : analogy_scan(ix, ws, s, M, d_rows + (size_t)c0 * 3, nc, k, xb, pos, n_rows, n_blocks, d_ids + (size_t)c0 * k, d_score + (size_t)c0 * k);
-      if (rc) return rc;
+      if (int rc = analogy_scan(ix, ws, s, pair ? 0 : M, d_rows + (size_t)c0 * 3, nc, k, xb, pos, n_rows, n_blocks, d_ids + (size_t)c0 * k, d_score + (size_t)c0 * k))
+        return rc;
     }
     return 0;
   };
@@ -809,36 +667,23 @@ static int pv_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const float*
                      float* out_sim, F&& search) {
   ann->pv_stats[0] = ann->pv_stats[1] = 0;
   if (Q == 0) return FREDDY_OK;
-  const int kc = k * pvf, P = pv_pad(kc), NW = P == 64 ? 1 : 4, d = ann->d;
-  const int Qc = (int)std::min<int64_t>(Q, std::max<int64_t>(1, ((int64_t)8 << 20) / kc));   // queries per pass: lists of at most 8 M entries
+  const int kc = k * pvf, d = ann->d;
+  const int Qc = rerank_pass(Q, kc);
   HIP_TRY(hipSetDevice(ann->device));
-  const size_t n_list = (size_t)Qc * kc, n_out = (size_t)Qc * k;
-  if (ann->pv_io.ensure(4 * (2 * n_list + 2 * n_out + 2 * (size_t)Qc)) || ann->pv_q.ensure(sizeof(float) * (size_t)Qc * d))
-    return fail(FREDDY_E_NOMEM, "post verification: staging allocation failed");
-  int32_t* const l_ids = ann->pv_io.as<int32_t>();
-  float* const l_dist = reinterpret_cast<float*>(l_ids + n_list);
-  int32_t* const o_ids = l_ids + 2 * n_list;
-  float* const o_sim = reinterpret_cast<float*>(o_ids + n_out);
-  int32_t* const o_cnt = o_ids + 2 * n_out;
+  RerankBlock b;
+  if (int rc = rerank_block(ann, Qc, kc, k, false, "post verification", &b)) return rc;
   hipStream_t s = ann->stream;
   for (int q0 = 0; q0 < Q; q0 += Qc) {
     const int nq = std::min(Qc, Q - q0);
     const float* qp = queries + (size_t)q0 * d;
-    if (int rc = search(qp, nq, kc, l_ids, l_dist)) return rc;
+    if (int rc = search(qp, nq, kc, b.l_ids, b.l_dist)) return rc;
     HIP_TRY(hipSetDevice(ann->device));
     HIP_TRY(hipMemcpyAsync(ann->pv_q.p, qp, sizeof(float) * (size_t)nq * d, hipMemcpyHostToDevice, s));
-    PvArgs pa;
-    pa.cand = l_ids; pa.vec_ids = vecs->ids; pa.rows = vecs->coarse; pa.queries = ann->pv_q.as<float>(); pa.exclude = nullptr; pa.out_ids = o_ids; pa.out_sim = o_sim;
-    pa.counts = o_cnt; pa.N = vecs->N; pa.n_cand = kc; pa.k = k; pa.d = d; pa.P = P;
-    timed_launch(ann, s, "pv_rerank", [&] {
-      if (NW == 1) hipLaunchKernelGGL((pv_rerank_kernel<1>), dim3((unsigned)nq), dim3(64), pv_lds_bytes(1, P, d), s, pa);
-      else hipLaunchKernelGGL((pv_rerank_kernel<4>), dim3((unsigned)nq), dim3(256), pv_lds_bytes(4, P, d), s, pa);
-    });
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_rerank(ann, vecs, s, "pv_rerank", pv_rerank_kernel<1>, pv_rerank_kernel<4>, b, nullptr, nq, kc, k)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
-    memcpy(out_ids + (size_t)q0 * k, o_ids, sizeof(int32_t) * (size_t)nq * k);
-    memcpy(out_sim + (size_t)q0 * k, o_sim, sizeof(float) * (size_t)nq * k);
-    for (int q = 0; q < nq; ++q) { ann->pv_stats[0] += o_cnt[2 * q]; ann->pv_stats[1] += o_cnt[2 * q + 1]; }
+    memcpy(out_ids + (size_t)q0 * k, b.o_ids, sizeof(int32_t) * (size_t)nq * k);
+    memcpy(out_sim + (size_t)q0 * k, b.o_sim, sizeof(float) * (size_t)nq * k);
+    for (int q = 0; q < nq; ++q) { ann->pv_stats[0] += b.o_cnt[2 * q]; ann->pv_stats[1] += b.o_cnt[2 * q + 1]; }
   }
   return FREDDY_OK;
 }
@@ -890,70 +735,34 @@ static int aa_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const int32_
                      float* out_sim, F&& search) {
   ann->aa_stats[0] = ann->aa_stats[1] = ann->aa_stats[2] = 0;
   for (size_t i = 0; i < (size_t)Q * k; ++i) { out_ids[i] = -1; out_sim[i] = -HUGE_VALF; }
-  // the INNER JOINs: a triple with an unknown id has no rows at all; the others, compacted
-  // (serial ids -- strictly ascending and last - first + 1 of them -- make the row a subtraction: 3 Q binary searches over a table of
-  // millions of ids otherwise cost more than the device work of a batch)
-  const std::vector<int32_t>& hid = vecs->h_ids;
-  const bool serial = !hid.empty() && (int64_t)hid.back() - hid.front() + 1 == (int64_t)hid.size();
-  auto row = [&](int32_t id) -> int32_t {
-    if (serial) return id >= hid.front() && id <= hid.back() ? id - hid.front() : -1;
-    return row_of(hid, id);
-  };
   std::vector<int32_t> live, rows3, ids3;
-  live.reserve((size_t)Q); rows3.reserve((size_t)Q * 3); ids3.reserve((size_t)Q * 3);
-  for (int32_t q = 0; q < Q; ++q) {
-    const int32_t* t = triples + (size_t)q * 3;
-    int32_t r[3];
-    bool ok = true;
-    for (int m = 0; m < 3 && ok; ++m) ok = (r[m] = row(t[m])) >= 0;
-    if (!ok) continue;
-    live.push_back(q);
-    rows3.insert(rows3.end(), r, r + 3);
-    ids3.insert(ids3.end(), t, t + 3);
-  }
+  resolve_triples(vecs->h_ids, triples, Q, live, rows3, &ids3);
   const int na = (int)live.size();
   if (na == 0) return FREDDY_OK;   // (before any launch)
-  const int P = pv_pad(n_cand), NW = P == 64 ? 1 : 4, d = ann->d;
-  int Qc = (int)std::min<int64_t>(na, std::max<int64_t>(1, ((int64_t)8 << 20) / n_cand));   // triples per pass: lists of at most 8 M entries
+  const int d = ann->d;
+  int Qc = rerank_pass(na, n_cand);   // triples per pass
   if (ann->tune.analogy_pass > 0) Qc = std::min(Qc, ann->tune.analogy_pass);
   HIP_TRY(hipSetDevice(ann->device));
-  // the pinned block: [unit rows, padded to 16 bytes][stage one's lists][the result lists][per-triple counts][input rows][input ids]
-  const size_t n_unit = ((size_t)Qc * d + 3) / 4 * 4, n_list = (size_t)Qc * n_cand, n_out = (size_t)Qc * k;
-  if (ann->pv_io.ensure(4 * (n_unit + 2 * n_list + 2 * n_out + 2 * (size_t)Qc + 6 * (size_t)Qc)) || ann->pv_q.ensure(sizeof(float) * (size_t)Qc * d))
-    return fail(FREDDY_E_NOMEM, "approximate analogy: staging allocation failed");
-  float* const unit = ann->pv_io.as<float>();
-  int32_t* const l_ids = reinterpret_cast<int32_t*>(unit + n_unit);
-  float* const l_dist = reinterpret_cast<float*>(l_ids + n_list);
-  int32_t* const o_ids = l_ids + 2 * n_list;
-  float* const o_sim = reinterpret_cast<float*>(o_ids + n_out);
-  int32_t* const o_cnt = o_ids + 2 * n_out;
-  int32_t* const p_rows = o_cnt + 2 * (size_t)Qc;
-  int32_t* const p_excl = p_rows + 3 * (size_t)Qc;
+  RerankBlock b;
+  if (int rc = rerank_block(ann, Qc, n_cand, k, true, "approximate analogy", &b)) return rc;
   hipStream_t s = ann->stream;
   for (int q0 = 0; q0 < na; q0 += Qc) {
     const int nq = std::min(Qc, na - q0);
-    memcpy(p_rows, rows3.data() + (size_t)q0 * 3, sizeof(int32_t) * 3 * (size_t)nq);
-    memcpy(p_excl, ids3.data() + (size_t)q0 * 3, sizeof(int32_t) * 3 * (size_t)nq);
+    memcpy(b.p_rows, rows3.data() + (size_t)q0 * 3, sizeof(int32_t) * 3 * (size_t)nq);
+    memcpy(b.p_excl, ids3.data() + (size_t)q0 * 3, sizeof(int32_t) * 3 * (size_t)nq);
     AaQueryArgs qa;
-    qa.rows = vecs->coarse; qa.in_rows = p_rows; qa.raw = ann->pv_q.as<float>(); qa.unit = unit; qa.d = d;
+    qa.rows = vecs->coarse; qa.in_rows = b.p_rows; qa.raw = ann->pv_q.as<float>(); qa.unit = b.unit; qa.d = d;
     timed_launch(ann, s, "aa_query", [&] { hipLaunchKernelGGL(aa_query_kernel, dim3((unsigned)nq), dim3(64), aa_query_lds(d), s, qa); });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));   // (stage one reads the unit rows on streams of its own)
-    if (int rc = search(unit, nq, l_ids, l_dist)) return rc;
+    if (int rc = search(b.unit, nq, b.l_ids, b.l_dist)) return rc;
     HIP_TRY(hipSetDevice(ann->device));
-    PvArgs pa;
-    pa.cand = l_ids; pa.vec_ids = vecs->ids; pa.rows = vecs->coarse; pa.queries = ann->pv_q.as<float>(); pa.exclude = p_excl; pa.out_ids = o_ids;
-    pa.out_sim = o_sim; pa.counts = o_cnt; pa.N = vecs->N; pa.n_cand = n_cand; pa.k = k; pa.d = d; pa.P = P;
-    timed_launch(ann, s, "aa_rerank", [&] {
-      if (NW == 1) hipLaunchKernelGGL((aa_rerank_kernel<1>), dim3((unsigned)nq), dim3(64), pv_lds_bytes(1, P, d), s, pa);
-      else hipLaunchKernelGGL((aa_rerank_kernel<4>), dim3((unsigned)nq), dim3(256), pv_lds_bytes(4, P, d), s, pa);
-    });
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_rerank(ann, vecs, s, "aa_rerank", aa_rerank_kernel<1>, aa_rerank_kernel<4>, b, b.p_excl, nq, n_cand, k)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     for (int q = 0; q < nq; ++q) {
-      memcpy(out_ids + (size_t)live[(size_t)q0 + q] * k, o_ids + (size_t)q * k, sizeof(int32_t) * k);
-      memcpy(out_sim + (size_t)live[(size_t)q0 + q] * k, o_sim + (size_t)q * k, sizeof(float) * k);
-      ann->aa_stats[1] += o_cnt[2 * q]; ann->aa_stats[2] += o_cnt[2 * q + 1];
+      memcpy(out_ids + (size_t)live[(size_t)q0 + q] * k, b.o_ids + (size_t)q * k, sizeof(int32_t) * k);
+      memcpy(out_sim + (size_t)live[(size_t)q0 + q] * k, b.o_sim + (size_t)q * k, sizeof(float) * k);
+      ann->aa_stats[1] += b.o_cnt[2 * q]; ann->aa_stats[2] += b.o_cnt[2 * q + 1];
     }
     ann->aa_stats[0] += nq;
   }

@@ -15,7 +15,7 @@
 //   exj_filter_kernel   <NT, false>: candidates (TABLE row, a) of every query into its own buffer
 //   exf_refine_kernel   (exact2.h, one workgroup per query) the reference's chain, the bracket self-check, the list
 //
-// one gather and five launches per pass of queries (a pass holds 10 880 or more: exact.hip EXJ_PASS_BYTES).  A query whose
+// one gather and five launches per pass of queries (a pass holds 10 880 or more: exact.hip EXJ_PASS_BYTES; the five are exact kNN's chain, exact_host.h exf_chain).  A query whose
 // candidate buffer overflowed is answered again by the all-exact subset path (the host reads the counters); nothing is dropped.
 //
 // Query-tile width: a workgroup's 8 waves share one LDS image of NT 32-column tiles and every wave streams its own 32-row

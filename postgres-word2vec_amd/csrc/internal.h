@@ -6,7 +6,8 @@
 //   pq.hip      pq_search (+ subsets, pseudo-list batches, one-query launch), grouping_pq
 //   join.hip    pin_ivpq, knn_join (join.h: overview; join_kernels.h and join_traverse.h the kernels, join_host.h the host heap, join_run.h the run
 //               record of a call and its stages)
-//   exact.hip   pin_vectors, exact kNN, the exact join, analogies, post verification of pq / ivf lists (pv.h), approximate analogies (approx_analogy.h)
+//   exact.hip   pin_vectors, exact kNN, the exact join, analogies, post verification of pq / ivf lists (pv.h), approximate analogies (approx_analogy.h),
+//               exact_assign (assign.h); exact_host.h the host sequences they share: the filter + refine chain, scan chunking, the re-rank stage, triple resolution
 //   build.hip   encode, insert_quantize, k-means
 // Kernel headers are included by the unit that launches them (kernels shared by two units are static or templates).
 #pragma once

@@ -1,5 +1,5 @@
 """Degenerate inputs for the redo paths of the exact filter + refine design (exact2.h, analogy.h, exact_join.h; the host side in
-exact.hip), shared by tests/test_redo_inputs_cpu.py (which proves on the CPU that they are what they claim to be) and
+exact.hip and exact_host.h), shared by tests/test_redo_inputs_cpu.py (which proves on the CPU that they are what they claim to be) and
 tests/test_gpu_redo_paths.py (which runs them).  Inputs and expected lists only: nothing here touches a device.
 
 The table: 20 000 x 300 rows of util.corpus with rows 5000 .. 14999 overwritten by row 4999 -- 10 001 equal rows, more than the
@@ -24,7 +24,7 @@ import util
 N, D = 20000, 300
 ORIGINAL = 4999                                   # the row that is copied ...
 COPY_ROWS = np.arange(4999, 15000)                # ... and every row that holds its vector (itself included)
-CAP = 8192                                        # rows of a candidate buffer (exact.hip: filter_plan)
+CAP = 8192                                        # rows of a candidate buffer (exact_host.h: filter_plan)
 K_MAX = 32                                        # the filter's largest k
 GAP = 0.05
 UNKNOWN_IDS = (4, 10**8, -7)
