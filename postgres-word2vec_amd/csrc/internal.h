@@ -4,6 +4,7 @@
 //   pin.hip     pin_pq / pin_ivf(_multi): table layouts; append_rows / remove_rows / update_codebook (HBM index mutation; remove_kernels.h)
 //   ivfadc.hip  the IVFADC search: cell selection, work table, scans, merge; *_dev entry, host-buffer pipeline, one-query launch
 //   pq.hip      pq_search (+ subsets, pseudo-list batches, one-query launch), grouping_pq
+//               ivf_host.h what these two share on the host: shape predicates and sizes, the query table's layout, the run state of a chain, merge arguments
 //   join.hip    pin_ivpq, knn_join (join.h: overview; join_kernels.h and join_traverse.h the kernels, join_host.h the host heap, join_run.h the run
 //               record of a call and its stages)
 //   exact.hip   pin_vectors, exact kNN, the exact join, analogies, post verification of pq / ivf lists (pv.h), approximate analogies (approx_analogy.h),
@@ -158,6 +159,7 @@ struct IvfRun {
   bool approx;         // cell selection as filter + refine: MFMA distances with a proven bracket, exact ones for the candidates
   bool records_ready;  // a batch over the flat PQ table: the entry records were written by pq_front_kernel (no work-table / record kernels)
   int merge_slices;    // > 0: the merge of such a batch as `merge_slices` partial merges per query + merge_replay_kernel
+  bool running_bound;  // a query's entries share its running bound (FilterArgs::tau_run; option running_bound, IVFADC batches only)
   // per round
   int n_active, round;
   const int32_t* active;

@@ -17,10 +17,42 @@
 #include "multi.h"
 #include "io_kernels.h"
 #include "bigk.h"
+#include "ivf_host.h"
 
 // ---------------------------------------------------------------------------------------
-// kernel dispatch helpers
+// kernel dispatch helpers.  A chooser maps the run-time facts to the instantiation (NULL: there is none); the launch site launches
+// the pointer and lds_limits_ivfadc() walks the same function over its domain: nothing is launched without its LDS limit.
 // ---------------------------------------------------------------------------------------
+// adc_scan_kernel<M, V, FLOOR>: m = 12 or any m; V = pick_V(L); FLOOR: a later selection pass of a long list (bigk.h), 1024 keys wide
+static void (*scan_kernel(bool m12, int V, bool floor))(ScanArgs) {
+  void (*k)(ScanArgs) = nullptr;
+  if (floor) return V != 16 ? nullptr : m12 ? &adc_scan_kernel<12, 16, true> : &adc_scan_kernel<0, 16, true>;
+  with_V(V, [&](auto v) { k = m12 ? &adc_scan_kernel<12, decltype(v)::value> : &adc_scan_kernel<0, decltype(v)::value>; });
+  return k;
+}
+// ivf_filter8_kernel (whole: the entry's slab stays in LDS, one-byte codes) / ivf_filter5_kernel<12, FULLK, CAND, PROF, U8>.  CAND: the
+// accepted-rows rule doubles the selection code of a kernel larger than the instruction cache; prof (lab): one instantiation per kernel
+static void (*filter_kernel(bool whole, bool u8, bool k1024, bool counts_rows, bool prof))(FilterArgs) {
+  if ((u8 && k1024) || (whole && !u8)) return nullptr;   // (one byte per code: K <= 256)
+#ifdef FREDDY_LAB
+  if (prof && !counts_rows && whole) return &ivf_filter8_kernel<12, false, true>;
+  if (prof && !counts_rows && k1024) return &ivf_filter5_kernel<12, true, false, true>;
+#endif
+  (void)prof;
+  if (whole) return counts_rows ? &ivf_filter8_kernel<12, true> : &ivf_filter8_kernel<12, false>;
+  if (u8) return counts_rows ? &ivf_filter5_kernel<12, false, true, false, true> : &ivf_filter5_kernel<12, false, false, false, true>;
+  if (k1024) return counts_rows ? &ivf_filter5_kernel<12, true, true> : &ivf_filter5_kernel<12, true, false>;
+  return counts_rows ? &ivf_filter5_kernel<12, false, true> : &ivf_filter5_kernel<12, false, false>;
+}
+// (cell, chunk) units of one or two items (pairs: the rows of a two-item cell are read once) / of one item (sparse5.h)
+static void (*sparse_kernel(bool pairs, bool u8, bool counts_rows))(SparseArgs) {
+  if (pairs) return u8 ? (counts_rows ? &sparse_pair5_kernel<12, true, true> : &sparse_pair5_kernel<12, false, true>)
+                       : (counts_rows ? &sparse_pair5_kernel<12, true, false> : &sparse_pair5_kernel<12, false, false>);
+  return u8 ? (counts_rows ? &sparse_item5_kernel<12, true, true> : &sparse_item5_kernel<12, false, true>)
+            : (counts_rows ? &sparse_item5_kernel<12, true> : &sparse_item5_kernel<12, false>);
+}
+static void (*spec2_kernel(bool k1024))(FusedArgs) { return k1024 ? &ivf_spec2_kernel<25, 12, true> : &ivf_spec2_kernel<25, 12, false>; }
+
 int pick_V(int L) {
   if (L <= 64) return 1;
   if (L <= 128) return 2;
@@ -36,22 +68,10 @@ int launch_scan(freddy_gpu_index* ix, hipStream_t s, const ScanArgs& a, int n_it
   const size_t lds = std::max((((size_t)a.m * a.K * 4 + 15) & ~(size_t)15) + (size_t)SCAN_WAVES * 64 * sizeof(u64),
                               (size_t)SCAN_WAVES * 64 * V * sizeof(u64));
   dim3 grid((unsigned)a.nchunk, (unsigned)n_items);
-  if (a.floor) {   // a later selection pass of a list of more than 512 entries (bigk.h)
-    if (V != 16) return fail(FREDDY_E_ARG, "selection passes are 1024 keys wide");
-    timed_launch(ix, s, "adc_scan", [&] {
-      if (a.m == 12) hipLaunchKernelGGL((adc_scan_kernel<12, 16, true>), grid, dim3(SCAN_WG), lds, s, a);
-      else hipLaunchKernelGGL((adc_scan_kernel<0, 16, true>), grid, dim3(SCAN_WG), lds, s, a);
-    });
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
-  const bool known = with_V(V, [&](auto v) {
-    timed_launch(ix, s, "adc_scan", [&] {
-      if (a.m == 12) hipLaunchKernelGGL((adc_scan_kernel<12, decltype(v)::value>), grid, dim3(SCAN_WG), lds, s, a);
-      else hipLaunchKernelGGL((adc_scan_kernel<0, decltype(v)::value>), grid, dim3(SCAN_WG), lds, s, a);
-    });
-  });
-  if (!known) return fail(FREDDY_E_LIMIT, "unsupported selection width");
+  if (a.floor && V != 16) return fail(FREDDY_E_ARG, "selection passes are 1024 keys wide");   // (a later pass of a list of more than 512 entries, bigk.h)
+  const auto kernel = scan_kernel(a.m == 12, V, a.floor != nullptr);
+  if (!kernel) return fail(FREDDY_E_LIMIT, "unsupported selection width");
+  timed_launch(ix, s, "adc_scan", [&] { hipLaunchKernelGGL(kernel, grid, dim3(SCAN_WG), lds, s, a); });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -132,9 +152,6 @@ int launch_lut(freddy_gpu_index* ix, hipStream_t s, const float* vecs, const int
 // per-batch query x codebook table beside them on the side stream
 // (q_lo, q_n): the combined MFMA cell-selection + table launch for the queries [q_lo, q_lo + q_n) of the chunk only -- the host-buffer
 // pipeline launches it piece by piece behind the pieces of the staged queries (q_lo a multiple of 32); q_n < 0: the whole chunk
-// K <= 256 with one-byte codes: the scan that keeps the whole entry's slab in LDS (fused8.h) reads a compact copy of the query table,
-// written by the table kernel behind the general one (w_qc: [Q][m][512] + [Q][m][128] dwords)
-static bool scan_whole_slab(const freddy_gpu_index* ix) { return ix->packed8 && ix->tune.codes_u8 == 1 && ix->K <= 256 && ix->m == 12; }
 static bool ivf_coarse_by_pieces(const IvfRun& r) { return r.approx && r.fused && r.scan_kernel == 5; }
 static int ivf_coarse(IvfRun& r, int q_lo = 0, int q_n = -1) {
   Workspace* ws = r.ws;
@@ -144,7 +161,6 @@ static int ivf_coarse(IvfRun& r, int q_lo = 0, int q_n = -1) {
   if (q_n < 0) { q_lo = 0; q_n = Q; }
   if ((q_lo != 0 || q_n != Q) && !ivf_coarse_by_pieces(r)) return fail(FREDDY_E_ARG, "internal: this path launches its coarse kernel once");
   const int used_words = (C + 31) / 32;
-  const size_t items = (size_t)Q * r.W;
   // round-one scratch that must start at zero: the probe bitmaps, the counters (n_next, n_groups, work
   // counter), the per-cell item counts and the accepted-candidate counts: every coarse kernel clears them itself
   // (ZeroArgs) -- except the small-batch kernel for vectors of more than 1024 dimensions, which gets memsets.
@@ -159,7 +175,7 @@ static int ivf_coarse(IvfRun& r, int q_lo = 0, int q_n = -1) {
   za.p[2] = r.fused ? ws->w_cellcnt.as<uint32_t>() : nullptr; za.n[2] = r.fused ? C * 2 : 0;
   za.p[3] = ws->w_cand.as<uint32_t>(); za.n[3] = 2 * Q;   // accepted-row counts, then the queries' running bounds (FilterArgs::tau_run)
   // survivor counts: regions of chunks a list does not have, or of items without a cell, stay at zero
-  za.p[4] = r.fused ? ws->w_surv_cnt.as<uint32_t>() : nullptr; za.n[4] = r.fused ? (int)(items * r.upi * FUSED_NW) : 0;
+  za.p[4] = r.fused ? ws->w_surv_cnt.as<uint32_t>() : nullptr; za.n[4] = r.fused ? (int)surv_regions(r, (size_t)Q * r.W) : 0;
 
   // more than 1024 cells: the (query, 128-cell tile) minima for the plan's two-level selection (round one: no cell is used yet)
   float* tile_min = nullptr;
@@ -167,39 +183,18 @@ static int ivf_coarse(IvfRun& r, int q_lo = 0, int q_n = -1) {
     if (ws->w_tmin.ensure(sizeof(float) * (size_t)Q * (Cpad / 128))) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
     tile_min = ws->w_tmin.as<float>();
   }
-  auto launch_coarse = [&]() -> int {
-    timed_launch(ix, s, "coarse_dist", [&] {
-      if (r.approx && ix->coarseH)
-        hipLaunchKernelGGL(coarse_approx16_kernel, dim3(Cpad / 128, (Q + COARSE_TQ - 1) / COARSE_TQ), dim3(256), coarse_approx16_lds(d), s, r.d_q,
-                           (const ch8v*)ix->coarseH, ix->coarse_ec, ix->cn2, ws->w_distT.as<float>(), ws->w_qn2.as<float>(), Q, Cpad, d, za, tile_min, C);
-      else if (r.approx)
-        hipLaunchKernelGGL(coarse_approx_kernel, dim3(Cpad / 128, (Q + COARSE_TQ - 1) / COARSE_TQ), dim3(256),
-                           (size_t)(COARSE_TQ * (ix->dp + 4) + 128) * sizeof(float), s, r.d_q, ix->coarseP, ix->cn2,
-                           ws->w_distT.as<float>(), ws->w_qn2.as<float>(), Q, Cpad, d, ix->dp, za, tile_min, C);
-      else if (r.tiled)
-        hipLaunchKernelGGL((coarse_tile_kernel<2, 16>), dim3(Cpad / 32, (Q + 63) / 64), dim3(256), 0, s, r.d_q, ix->coarseT,
-                           ws->w_distT.as<float>(), Q, Cpad, d, za);
-      else if (small_zero)
-        hipLaunchKernelGGL((coarse_small_kernel<50>), dim3(Cpad / 64, Q), dim3(64), 0, s, r.d_q, ix->coarseT, ws->w_distT.as<float>(), Q, Cpad, d, za);
-      else
-        hipLaunchKernelGGL((coarse_dist_kernel<16>), dim3(Cpad / WG, (Q + 15) / 16), dim3(WG), (size_t)d * 16 * sizeof(float), s, r.d_q,
-                           ix->coarseT, ws->w_distT.as<float>(), Q, Cpad, d);
-    });
-    HIP_TRY(hipGetLastError());
-    return 0;
-  };
   // The query x codebook table is independent of the coarse distances: with the MFMA cell selection the coarse tiles and
   // the table units are the workgroups of ONE launch (fused5.h coarse_table5_kernel); otherwise the table kernel runs in
   // line before the coarse kernel.
-  if (r.approx && r.fused && r.scan_kernel == 5) {
+  if (ivf_coarse_by_pieces(r)) {
     CoarseTableArgs ct;   // (every array is query-major: a piece is the same launch on offset pointers)
     ct.queries = r.d_q + (size_t)q_lo * d; ct.coarseF = ix->coarseP; ct.cn2 = ix->cn2; ct.dist = ws->w_distT.as<float>() + (size_t)q_lo * Cpad;
     ct.qn2 = ws->w_qn2.as<float>() + q_lo;
     ct.Q = q_n; ct.Cpad = Cpad; ct.d = d; ct.dp = ix->dp; ct.z = za; ct.coarse_gx = Cpad / 128; ct.coarse_gy = (q_n + COARSE_TQ - 1) / COARSE_TQ;
-    ct.cbT = ix->cbF; ct.cmax = ix->cmaxp; ct.qn = ws->w_qn.as<float>() + (size_t)q_lo * m; ct.qscale = ws->w_qn.as<float>() + (size_t)Q * m + q_lo;
-    ct.qc = ws->w_qc.as<uint32_t>() + (size_t)q_lo * m * 512; ct.m = m; ct.K = K; ct.tmin = tile_min ? tile_min + (size_t)q_lo * (Cpad / 128) : nullptr; ct.C = C;
+    const QueryTable qt = query_table_piece(query_table(ws, ix, Q), ix, q_lo);
+    ct.cbT = ix->cbF; ct.cmax = ix->cmaxp; ct.qn = qt.qn; ct.qscale = qt.qscale; ct.qc = qt.qc; ct.qc8 = qt.qc8;
+    ct.m = m; ct.K = K; ct.tmin = tile_min ? tile_min + (size_t)q_lo * (Cpad / 128) : nullptr; ct.C = C;
     ct.coarseH = (const ch8v*)ix->coarseH; ct.ec = ix->coarse_ec;
-    ct.qc8 = scan_whole_slab(ix) ? ws->w_qc.as<uint32_t>() + (size_t)Q * m * 512 + (size_t)q_lo * m * 128 : nullptr;
     const size_t lds = std::max<size_t>(ix->coarseH ? coarse_approx16_lds(d) : (size_t)(COARSE_TQ * (ix->dp + 4) + 128) * sizeof(float), (size_t)query_codebook5_lds<25, 16>());
     const unsigned grid = (unsigned)(ct.coarse_gx * ct.coarse_gy + m * ((q_n + 15) / 16));
     timed_launch(ix, s, "coarse_table", [&] {
@@ -210,14 +205,32 @@ static int ivf_coarse(IvfRun& r, int q_lo = 0, int q_n = -1) {
     return 0;
   }
   if (r.fused && r.scan_kernel == 5) {
+    const QueryTable qt = query_table(ws, ix, Q);
     timed_launch(ix, s, "query_codebook", [&] {
       hipLaunchKernelGGL((query_codebook5_kernel<25, 16>), dim3(m, (Q + 15) / 16), dim3(256), 0, s, r.d_q, ix->cbF, ix->cmaxp,
-                         ws->w_qn.as<float>(), ws->w_qn.as<float>() + (size_t)Q * m, ws->w_qc.as<uint32_t>(), Q, d, m, K,
-                         scan_whole_slab(ix) ? ws->w_qc.as<uint32_t>() + (size_t)Q * m * 512 : nullptr);
+                         qt.qn, qt.qscale, qt.qc, Q, d, m, K, qt.qc8);
     });
     HIP_TRY(hipGetLastError());
   }
-  return launch_coarse();
+  timed_launch(ix, s, "coarse_dist", [&] {
+    if (r.approx && ix->coarseH)
+      hipLaunchKernelGGL(coarse_approx16_kernel, dim3(Cpad / 128, (Q + COARSE_TQ - 1) / COARSE_TQ), dim3(256), coarse_approx16_lds(d), s, r.d_q,
+                         (const ch8v*)ix->coarseH, ix->coarse_ec, ix->cn2, ws->w_distT.as<float>(), ws->w_qn2.as<float>(), Q, Cpad, d, za, tile_min, C);
+    else if (r.approx)
+      hipLaunchKernelGGL(coarse_approx_kernel, dim3(Cpad / 128, (Q + COARSE_TQ - 1) / COARSE_TQ), dim3(256),
+                         (size_t)(COARSE_TQ * (ix->dp + 4) + 128) * sizeof(float), s, r.d_q, ix->coarseP, ix->cn2,
+                         ws->w_distT.as<float>(), ws->w_qn2.as<float>(), Q, Cpad, d, ix->dp, za, tile_min, C);
+    else if (r.tiled)
+      hipLaunchKernelGGL((coarse_tile_kernel<2, 16>), dim3(Cpad / 32, (Q + 63) / 64), dim3(256), 0, s, r.d_q, ix->coarseT,
+                         ws->w_distT.as<float>(), Q, Cpad, d, za);
+    else if (small_zero)
+      hipLaunchKernelGGL((coarse_small_kernel<50>), dim3(Cpad / 64, Q), dim3(64), 0, s, r.d_q, ix->coarseT, ws->w_distT.as<float>(), Q, Cpad, d, za);
+    else
+      hipLaunchKernelGGL((coarse_dist_kernel<16>), dim3(Cpad / WG, (Q + 15) / 16), dim3(WG), (size_t)d * 16 * sizeof(float), s, r.d_q,
+                         ix->coarseT, ws->w_distT.as<float>(), Q, Cpad, d);
+  });
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 // a7: the W nearest not-yet-used cells of every active query (+ their items appended to the cells' buckets)
@@ -226,19 +239,16 @@ static int ivf_plan(IvfRun& r, PlanArgs& pa) {
   freddy_gpu_index* ix = r.ix;
   hipStream_t s = r.s;
   const int C = ix->C, W = r.W;
+  pa = plan_items(r, C);
   pa.dist = ws->w_distT.as<float>(); pa.active = r.active; pa.list_off = ix->list_off;
-  pa.used = ws->w_used.as<uint32_t>();
-  pa.item_cell = ws->w_item_cell.as<int32_t>(); pa.item_query = ws->w_item_query.as<int32_t>();
-  pa.item_dist = ws->w_item_dist.as<float>();
-  pa.round_rows = ws->w_rows.as<int32_t>();
-  pa.n_active = r.n_active; pa.Cpad = ix->Cpad; pa.C = C; pa.W = W; pa.used_words = (C + 31) / 32;
+  pa.used = ws->w_used.as<uint32_t>(); pa.Cpad = ix->Cpad; pa.used_words = (C + 31) / 32;
   pa.cell_count = r.fused ? ws->w_cellcnt.as<int32_t>() : nullptr;
   pa.cell_items = r.fused ? ws->w_sorted.as<int32_t>() : nullptr; pa.cell_cap = r.n_active;
   pa.cell_limit = r.cell_limit;
   const int n_items = r.n_active * W;
   if (r.fused && !(r.zeroed && r.first())) {
     HIP_TRY(hipMemsetAsync(ws->w_cellcnt.p, 0, sizeof(int32_t) * (size_t)C * 2, s));   // counts + fill cursors
-    HIP_TRY(hipMemsetAsync(ws->w_surv_cnt.p, 0, sizeof(int32_t) * (size_t)n_items * r.upi * FUSED_NW, s));
+    HIP_TRY(hipMemsetAsync(ws->w_surv_cnt.p, 0, sizeof(int32_t) * surv_regions(r, (size_t)n_items), s));
   }
   const int PV = pick_V(2 * W);
   const size_t plan_lds = (size_t)(64 + 64 * PV) * sizeof(u64) + (size_t)W * 8;
@@ -267,13 +277,9 @@ int ivf_work_table(IvfRun& r, WorkTable& wt) {
   freddy_gpu_index* ix = r.ix;
   hipStream_t s = r.s;
   const int n_items = r.n_active * r.W;
-  wt.max_groups = ((size_t)n_items / MULTI_G + (size_t)ix->C + 1) * r.upi;   // (group, chunk) work entries (the smallest group size: a bound for every scan)
+  wt = work_counters(ws, ((size_t)n_items / MULTI_G + (size_t)ix->C + 1) * r.upi);   // (group, chunk) work entries (the smallest group size: a bound for every scan)
   int32_t* base = ws->w_groups.as<int32_t>();
   wt.group_cell = base; wt.group_first = base + wt.max_groups; wt.group_cnt = base + 2 * wt.max_groups;
-  wt.n_groups = ws->w_cnt.as<int32_t>() + 1;
-  wt.work_counter = ws->w_cnt.as<int32_t>() + 2;
-  wt.sp_counter = ws->w_cnt.as<int32_t>() + 3;
-  wt.n_sparse = ws->w_cnt.as<int32_t>() + 4;
   // cells that one or two queries probe are scanned item by item -- where such cells are the rule (fewer than four items per
   // cell on average: a corpus with more cells than the batch has probes) and there are enough of them to fill the chip's
   // workgroup slots several times (the item-wise scan is built for throughput: a 256-query batch on 1000 cells took 0.187
@@ -295,17 +301,17 @@ int ivf_work_table(IvfRun& r, WorkTable& wt) {
   return 0;
 }
 
-static int scan_prof_buffer(freddy_gpu_index* ix, Workspace* ws, long long** prof) {
+// the lab builds' aids of a scan: the counters' buffer (option fused_prof) and the filter scan's fence (option scan_fence)
+static int scan_prof_buffer(freddy_gpu_index* ix, Workspace* ws, long long** prof, uint32_t* fence = nullptr) {
   *prof = nullptr;
-#ifndef FREDDY_LAB
-  (void)ix; (void)ws;
-  return 0;
-#else
+#ifdef FREDDY_LAB
+  if (fence) *fence = (uint32_t)ix->tune.scan_fence;
   if (!ix->tune.scan_prof) return 0;
   if (ws->w_prof.ensure(sizeof(long long) * 8 * 1024)) return fail(FREDDY_E_NOMEM, "profile buffer");
   *prof = ws->w_prof.as<long long>();
-  return 0;
 #endif
+  (void)ix; (void)ws; (void)fence;
+  return 0;
 }
 
 #ifdef FREDDY_LAB
@@ -326,6 +332,27 @@ static int scan_prof_print(freddy_gpu_index* ix, hipStream_t s, const long long*
   (void)ix;
   return 0;
 }
+// The counters of the filter scan's profiling instantiations (filter_kernel), once the scan of a round is enqueued: ivf_filter5_kernel's
+// as above, ivf_filter8_kernel's (fused8.h) are gatherer wave 0's stages
+static int filter_prof_print(freddy_gpu_index* ix, hipStream_t s, const FilterArgs& fl, bool whole, unsigned n_persist) {
+  if (!fl.prof || fl.cand_count || !(whole || fl.K == 1024)) return 0;
+  if (!whole) return scan_prof_print(ix, s, fl.prof, n_persist);
+  std::vector<long long> h(8 * (size_t)n_persist);
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(h.data(), fl.prof, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
+  double sum[8] = {0}, life_max = 0, life_min = 1e30;
+  for (unsigned b = 0; b < n_persist; ++b) {
+    for (int i = 0; i < 8; ++i) sum[i] += (double)h[b * 8 + i];
+    life_max = std::max(life_max, (double)h[b * 8 + 7]); life_min = std::min(life_min, (double)h[b * 8 + 7]);
+  }
+  int32_t ng = 0;
+  HIP_TRY(hipMemcpy(&ng, fl.n_groups, 4, hipMemcpyDeviceToHost));
+  const double e = std::max(1, ng);
+  fprintf(stderr, "[scan8 prof] wgs=%u entries=%d  gatherer wave 0 cycles/entry (slots 0-5): gather=%.0f B1=%.0f colmin=%.0f B2=%.0f S1=%.0f B3+S2+B4=%.0f | per workgroup: prologue (slot 6) %.0f, stages (0-5) %.0f, life (slot 7) mean %.0f min %.0f max %.0f\n",
+          n_persist, ng, sum[0] / e, sum[1] / e, sum[2] / e, sum[3] / e, sum[4] / e, sum[5] / e, sum[6] / n_persist,
+          (sum[0] + sum[1] + sum[2] + sum[3] + sum[4] + sum[5]) / n_persist, sum[7] / n_persist, life_min, life_max);
+  return 0;
+}
 #endif
 
 // Default scan: filter + refine.  entry records -> ivf_filter5_kernel (+ the item-wise scan of thin cells) -> merge_refine_kernel.
@@ -333,35 +360,33 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   Workspace* ws = r.ws;
   freddy_gpu_index* ix = r.ix;
   hipStream_t s = r.s;
-  const int Q = r.Q, m = ix->m, K = ix->K;
-  if (!r.records_ready && ws->w_records.ensure(sizeof(int32_t) * REC_DW * wt.max_groups)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  RecordArgs ra;
-  ra.group_cell = wt.group_cell; ra.group_first = wt.group_first; ra.group_cnt = wt.group_cnt; ra.n_groups = wt.n_groups;
-  ra.sorted_item = ws->w_sorted.as<int32_t>(); ra.item_query = pa.item_query; ra.blk_off = ix->blk_off; ra.list_off = ix->list_off;
-  ra.item_dist = pa.item_dist; ra.qn = ws->w_qn.as<float>(); ra.qscale = ws->w_qn.as<float>() + (size_t)Q * m; ra.pmax = ix->pmax;
-  ra.records = ws->w_records.as<int32_t>(); ra.sentinel = r.sentinel;
-  if (!r.records_ready) {
+  const int K = ix->K;
+  const QueryTable qt = query_table(ws, ix, r.Q);
+  if (!r.records_ready) {   // (a batch over the flat PQ table: pq_front_kernel has written them)
+    if (ws->w_records.ensure(sizeof(int32_t) * REC_DW * wt.max_groups)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+    RecordArgs ra;
+    ra.group_cell = wt.group_cell; ra.group_first = wt.group_first; ra.group_cnt = wt.group_cnt; ra.n_groups = wt.n_groups;
+    ra.sorted_item = ws->w_sorted.as<int32_t>(); ra.item_query = pa.item_query; ra.blk_off = ix->blk_off; ra.list_off = ix->list_off;
+    ra.item_dist = pa.item_dist; ra.qn = qt.qn; ra.qscale = qt.qscale; ra.pmax = ix->pmax;
+    ra.records = ws->w_records.as<int32_t>(); ra.sentinel = r.sentinel;
     timed_launch(ix, s, "entry_records", [&] {
       hipLaunchKernelGGL((entry_record5_kernel<12>), dim3((unsigned)((wt.max_groups + 3) / 4)), dim3(256), 0, s, ra);
     });
     HIP_TRY(hipGetLastError());
   }
   FilterArgs fl;
-  fl.qc = ws->w_qc.as<uint32_t>(); fl.qc8 = ws->w_qc.as<uint32_t>() + (size_t)Q * m * 512; fl.rterm = ix->rterm; fl.records = ws->w_records.as<int32_t>(); fl.n_groups = wt.n_groups;
+  fl.qc = qt.qc; fl.qc8 = qt.qc8; fl.rterm = ix->rterm; fl.records = ws->w_records.as<int32_t>(); fl.n_groups = wt.n_groups;
   fl.work_counter = wt.work_counter; fl.packed = ix->packed; fl.surv = ws->w_surv.as<u64>(); fl.surv_count = ws->w_surv_cnt.as<int32_t>();
-  fl.cand_count = (r.found_rule == 1) ? ws->w_cand.as<int32_t>() : nullptr;
+  fl.cand_count = rows_counter(r);
   fl.K = K; fl.L = r.L; fl.upi = r.upi; fl.sentinel = r.sentinel; fl.keep_all = (ix->tune.check_brackets & 1) ? 1 : 0; fl.fence = 0;
-#ifdef FREDDY_LAB
-  fl.fence = (uint32_t)ix->tune.scan_fence;
-#endif
   // (not for a batch over the flat PQ table: a few dozen queries x a thousand entries read and update the same two cache lines --
   // 96 -> 128 us -- and its merge gains nothing; an IVFADC batch: +2.6 % queries/s with four batches in flight)
-  fl.tau_run = (ix->tune.running_bound && !r.records_ready) ? ws->w_cand.as<uint32_t>() + Q : nullptr;
-  if (int rc = scan_prof_buffer(ix, ws, &fl.prof)) return rc;
+  fl.tau_run = r.running_bound ? ws->w_cand.as<uint32_t>() + r.Q : nullptr;
+  if (int rc = scan_prof_buffer(ix, ws, &fl.prof, &fl.fence)) return rc;
   // K <= 256: one byte per code (packed8) unless option codes_u8 = 0 asks for the int16 layout
   const bool u8 = ix->packed8 && ix->tune.codes_u8 != 0 && K <= 256;
   // ... and by default the kernel that keeps the WHOLE entry's slab in LDS (fused8.h; option codes_u8 = 2: fused5.h's one-byte instantiation)
-  const bool whole = u8 && scan_whole_slab(ix);
+  const bool whole = u8 && qt.qc8;
   // LDS: slabs [2 buffers][2 positions][K][16 items] int16 (whole: [12 positions][2 halves][256][8 items]), then column minima /
   // thresholds, two entry records, row terms
   const size_t desc_off = whole ? (size_t)scan8_slab_bytes(12) : (size_t)4 * SCAN5_G * 2 * K;
@@ -374,78 +399,31 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   const int scan_cus = std::max(ix->n_cus / std::max(1, r.share), std::min(ix->n_cus, 32)) - ix->tune.reserve_cus;
   const unsigned n_persist = (unsigned)std::min<size_t>(wt.max_groups, (size_t)std::max(1, scan_cus));
   fl.packed8 = u8 ? ix->packed8 : nullptr;
-  timed_launch(ix, s, "ivf_filter", [&] {
-    // (instantiations: the rule that counts accepted rows doubles the selection code, and the kernel is larger than the
-    // instruction cache as it is)
-    if (whole) {
-#ifdef FREDDY_LAB
-      if (fl.prof && !fl.cand_count) hipLaunchKernelGGL((ivf_filter8_kernel<12, false, true>), dim3(n_persist), dim3(SPEC2_T), flds, s, fl);
-      else
-#endif
-      if (fl.cand_count) hipLaunchKernelGGL((ivf_filter8_kernel<12, true>), dim3(n_persist), dim3(SPEC2_T), flds, s, fl);
-      else hipLaunchKernelGGL((ivf_filter8_kernel<12, false>), dim3(n_persist), dim3(SPEC2_T), flds, s, fl);
-    } else if (u8) {
-      if (fl.cand_count) hipLaunchKernelGGL((ivf_filter5_kernel<12, false, true, false, true>), dim3(n_persist), dim3(SPEC2_T), flds, s, fl);
-      else hipLaunchKernelGGL((ivf_filter5_kernel<12, false, false, false, true>), dim3(n_persist), dim3(SPEC2_T), flds, s, fl);
-    } else if (fl.cand_count) {
-      if (K == 1024) hipLaunchKernelGGL((ivf_filter5_kernel<12, true, true>), dim3(n_persist), dim3(SPEC2_T), flds, s, fl);
-      else hipLaunchKernelGGL((ivf_filter5_kernel<12, false, true>), dim3(n_persist), dim3(SPEC2_T), flds, s, fl);
-    }
-#ifdef FREDDY_LAB
-    else if (K == 1024 && fl.prof) hipLaunchKernelGGL((ivf_filter5_kernel<12, true, false, true>), dim3(n_persist), dim3(SPEC2_T), flds, s, fl);
-#endif
-    else if (K == 1024) hipLaunchKernelGGL((ivf_filter5_kernel<12, true, false>), dim3(n_persist), dim3(SPEC2_T), flds, s, fl);
-    else hipLaunchKernelGGL((ivf_filter5_kernel<12, false, false>), dim3(n_persist), dim3(SPEC2_T), flds, s, fl);
-  });
+  const auto filter = filter_kernel(whole, u8, K == 1024, fl.cand_count != nullptr, fl.prof != nullptr);
+  if (!filter) return fail(FREDDY_E_ARG, "internal: no filter scan for this shape");
+  timed_launch(ix, s, "ivf_filter", [&] { hipLaunchKernelGGL(filter, dim3(n_persist), dim3(SPEC2_T), flds, s, fl); });
   HIP_TRY(hipGetLastError());
   if (wt.sp_cap > 0) {
     // cells that one or two queries of the batch probe: item by item (sparse5.h), six workgroups of four waves per CU
     SparseArgs sp;
-    sp.qc = fl.qc; sp.qscale = ra.qscale; sp.qn = ra.qn; sp.pmax = ix->pmax; sp.rterm = ix->rterm; sp.packed = ix->packed;
-    sp.blk_off = ix->blk_off; sp.list_off = ix->list_off; sp.sorted_item = ra.sorted_item; sp.item_query = pa.item_query;
+    sp.qc = qt.qc; sp.qscale = qt.qscale; sp.qn = qt.qn; sp.pmax = ix->pmax; sp.rterm = ix->rterm; sp.packed = ix->packed;
+    sp.blk_off = ix->blk_off; sp.list_off = ix->list_off; sp.sorted_item = ws->w_sorted.as<int32_t>(); sp.item_query = pa.item_query;
     sp.item_dist = pa.item_dist; sp.sp_cell = wt.sp_cell; sp.sp_first = wt.sp_first; sp.sp_chunk = wt.sp_chunk;
     sp.n_units = wt.n_sparse; sp.work_counter = wt.sp_counter; sp.surv = fl.surv; sp.surv_count = fl.surv_count; sp.packed8 = fl.packed8;
     sp.cand_count = fl.cand_count; sp.K = K; sp.L = r.L; sp.upi = r.upi; sp.sentinel = r.sentinel; sp.keep_all = fl.keep_all; sp.tau_run = fl.tau_run;
     const unsigned sp_grid = (unsigned)std::min<size_t>(wt.sp_cap, (size_t)std::max(1, scan_cus) * (wt.sp_pairs ? 3 : 6));
-    timed_launch(ix, s, "sparse_items", [&] {
-      if (wt.sp_pairs) {   // (cell, chunk) units of one or two items: the rows of a two-item cell are read once
-        if (u8) {
-          if (fl.cand_count) hipLaunchKernelGGL((sparse_pair5_kernel<12, true, true>), dim3(sp_grid), dim3(256), 0, s, sp);
-          else hipLaunchKernelGGL((sparse_pair5_kernel<12, false, true>), dim3(sp_grid), dim3(256), 0, s, sp);
-        } else if (fl.cand_count) hipLaunchKernelGGL((sparse_pair5_kernel<12, true, false>), dim3(sp_grid), dim3(256), 0, s, sp);
-        else hipLaunchKernelGGL((sparse_pair5_kernel<12, false, false>), dim3(sp_grid), dim3(256), 0, s, sp);
-      } else if (u8) {
-        if (fl.cand_count) hipLaunchKernelGGL((sparse_item5_kernel<12, true, true>), dim3(sp_grid), dim3(256), 0, s, sp);
-        else hipLaunchKernelGGL((sparse_item5_kernel<12, false, true>), dim3(sp_grid), dim3(256), 0, s, sp);
-      } else if (fl.cand_count) hipLaunchKernelGGL((sparse_item5_kernel<12, true>), dim3(sp_grid), dim3(256), 0, s, sp);
-      else hipLaunchKernelGGL((sparse_item5_kernel<12, false>), dim3(sp_grid), dim3(256), 0, s, sp);
-    });
+    const auto sparse = sparse_kernel(wt.sp_pairs, u8, fl.cand_count != nullptr);
+    timed_launch(ix, s, "sparse_items", [&] { hipLaunchKernelGGL(sparse, dim3(sp_grid), dim3(256), 0, s, sp); });
     HIP_TRY(hipGetLastError());
   }
 #ifdef FREDDY_LAB
-  if (fl.prof && K == 1024 && !fl.cand_count) if (int rc = scan_prof_print(ix, s, fl.prof, n_persist)) return rc;   // (the counters live in one instantiation)
-  if (fl.prof && whole && !fl.cand_count) {   // fused8.h: gatherer wave 0's stages
-    std::vector<long long> h(8 * (size_t)n_persist);
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(h.data(), fl.prof, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
-    double sum[8] = {0}, life_max = 0, life_min = 1e30;
-    for (unsigned b = 0; b < n_persist; ++b) {
-      for (int i = 0; i < 8; ++i) sum[i] += (double)h[b * 8 + i];
-      life_max = std::max(life_max, (double)h[b * 8 + 7]); life_min = std::min(life_min, (double)h[b * 8 + 7]);
-    }
-    int32_t ng = 0;
-    HIP_TRY(hipMemcpy(&ng, wt.n_groups, 4, hipMemcpyDeviceToHost));
-    const double e = std::max(1, ng);
-    fprintf(stderr, "[scan8 prof] wgs=%u entries=%d  gatherer wave 0 cycles/entry (slots 0-5): gather=%.0f B1=%.0f colmin=%.0f B2=%.0f S1=%.0f B3+S2+B4=%.0f | per workgroup: prologue (slot 6) %.0f, stages (0-5) %.0f, life (slot 7) mean %.0f min %.0f max %.0f\n",
-            n_persist, ng, sum[0] / e, sum[1] / e, sum[2] / e, sum[3] / e, sum[4] / e, sum[5] / e, sum[6] / n_persist,
-            (sum[0] + sum[1] + sum[2] + sum[3] + sum[4] + sum[5]) / n_persist, sum[7] / n_persist, life_min, life_max);
-  }
+  if (int rc = filter_prof_print(ix, s, fl, whole, n_persist)) return rc;
 #endif
 
   MergeRefineArgs mr;
   mr.surv = fl.surv; mr.surv_count = fl.surv_count; mr.active = r.active; mr.round_rows = pa.round_rows;
   mr.item_cell = pa.item_cell; mr.queries = r.d_q; mr.coarse = ix->coarse; mr.cbR = ix->cbR;
-  mr.qn = ws->w_qn.as<float>(); mr.pmax = ix->pmax; mr.qscale5 = ws->w_qn.as<float>() + (size_t)Q * m; mr.packed = ix->packed; mr.pos = ix->pos; mr.blk_cell = ix->blk_cell;
+  mr.qn = qt.qn; mr.pmax = ix->pmax; mr.qscale5 = qt.qscale; mr.packed = ix->packed; mr.pos = ix->pos; mr.blk_cell = ix->blk_cell;
   mr.cand_count = fl.cand_count; mr.violations = ix->viol; mr.out_ids = r.d_out_ids; mr.out_dist = r.d_out_dist;
   mr.found = ws->w_found.as<int32_t>(); mr.next_active = r.next; mr.n_next = ws->w_cnt.as<int32_t>();
   mr.status = r.d_status;
@@ -463,11 +441,7 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
       hipLaunchKernelGGL((merge_refine_kernel<25, 12, 12, true, true>), dim3(r.n_active * SL), dim3(768), 0, s, mr);
     });
     HIP_TRY(hipGetLastError());
-    MergeArgs ma;
-    ma.part = ws->w_part.as<u64>(); ma.active = nullptr; ma.pos_to_id = nullptr; ma.round_rows = nullptr; ma.cand_count = nullptr;
-    ma.out_ids = r.d_out_ids; ma.out_dist = r.d_out_dist; ma.found = nullptr; ma.next_active = nullptr; ma.n_next = nullptr; ma.status = nullptr;
-    ma.n_active = r.n_active; ma.parts_per_query = SL; ma.L = r.L; ma.k = r.k; ma.found_rule = 0; ma.first_round = 1; ma.sentinel = r.sentinel;
-    return launch_merge(ix, s, ma);
+    return launch_merge(ix, s, merge_args_flat(mr.part, r.n_active, SL, r.L, r.k, r.sentinel, nullptr, r.d_out_ids, r.d_out_dist));
   }
   timed_launch(ix, s, "merge_refine", [&] {
     // (one batch at a time: four waves per query, the shortest latency; batches in flight: one wave per query, the smallest footprint)
@@ -486,8 +460,8 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   return 0;
 }
 
-// merge_surv_kernel's arguments for a round whose scan (exact or multi) left its survivors in (surv, surv_count)
-static MergeSurvArgs merge_surv_args(const IvfRun& r, const PlanArgs& pa, const u64* surv, const int32_t* surv_count, const int32_t* cand_count) {
+// merge_surv_kernel for a round whose scan (exact or multi) left its survivors in (surv, surv_count)
+static int launch_merge_surv(const IvfRun& r, const PlanArgs& pa, const u64* surv, const int32_t* surv_count, const int32_t* cand_count) {
   MergeSurvArgs ms;
   ms.surv = surv; ms.surv_count = surv_count; ms.active = r.active; ms.round_rows = pa.round_rows;
   ms.cand_count = cand_count; ms.out_ids = r.d_out_ids; ms.out_dist = r.d_out_dist;
@@ -495,7 +469,9 @@ static MergeSurvArgs merge_surv_args(const IvfRun& r, const PlanArgs& pa, const 
   ms.status = r.d_status;
   ms.n_active = r.n_active; ms.W = r.W; ms.upi = r.upi; ms.L = r.L; ms.k = r.k; ms.found_rule = r.found_rule;
   ms.first_round = r.first() ? 1 : 0; ms.sentinel = r.sentinel;
-  return ms;
+  timed_launch(r.ix, r.s, "merge_surv", [&] { hipLaunchKernelGGL(merge_surv_kernel, dim3(r.n_active), dim3(64), 0, r.s, ms); });
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 // The yardstick: the reference's arithmetic for every probed row (fused3.h).  ivf_spec2_kernel -> merge_surv_kernel.
@@ -510,7 +486,7 @@ static int ivf_scan_exact(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   fa.group_cnt = wt.group_cnt; fa.n_groups = wt.n_groups; fa.work_counter = wt.work_counter;
   fa.cbP = ix->cbP; fa.blk_off = ix->blk_off; fa.packed = ix->packed; fa.pos = ix->pos;
   fa.surv = ws->w_surv.as<u64>(); fa.surv_count = ws->w_surv_cnt.as<int32_t>();
-  fa.cand_count = (r.found_rule == 1) ? ws->w_cand.as<int32_t>() : nullptr;
+  fa.cand_count = rows_counter(r);
   fa.d = ix->d; fa.K = K; fa.L = r.L; fa.upi = r.upi;
   memcpy(&fa.sentinel_bits, &r.sentinel, 4);
   if (int rc = scan_prof_buffer(ix, ws, &fa.prof)) return rc;
@@ -518,18 +494,12 @@ static int ivf_scan_exact(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   const size_t flds = desc_off + 4096 + 64 + 512 + (size_t)SPEC2_G * 12 * 28 * sizeof(float);
   fa.desc_offset = (uint32_t)desc_off;
   const unsigned n_persist = (unsigned)std::min<size_t>(wt.max_groups, (size_t)ix->n_cus);
-  timed_launch(ix, s, "ivf_exact_scan", [&] {
-    if (K == 1024) hipLaunchKernelGGL((ivf_spec2_kernel<25, 12, true>), dim3(n_persist), dim3(SPEC2_T), flds, s, fa);
-    else hipLaunchKernelGGL((ivf_spec2_kernel<25, 12, false>), dim3(n_persist), dim3(SPEC2_T), flds, s, fa);
-  });
+  timed_launch(ix, s, "ivf_exact_scan", [&] { hipLaunchKernelGGL(spec2_kernel(K == 1024), dim3(n_persist), dim3(SPEC2_T), flds, s, fa); });
   HIP_TRY(hipGetLastError());
 #ifdef FREDDY_LAB
   if (fa.prof) if (int rc = scan_prof_print(ix, s, fa.prof, n_persist)) return rc;
 #endif
-  const MergeSurvArgs ms = merge_surv_args(r, pa, fa.surv, fa.surv_count, fa.cand_count);
-  timed_launch(ix, s, "merge_surv", [&] { hipLaunchKernelGGL(merge_surv_kernel, dim3(r.n_active), dim3(64), 0, s, ms); });
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launch_merge_surv(r, pa, fa.surv, fa.surv_count, fa.cand_count);
 }
 
 // Every other index shape (multi.h): exact LUTs of all items -> ivf_multi_kernel -> merge_surv_kernel.
@@ -544,7 +514,7 @@ static int ivf_scan_multi(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   ma.group_cell = wt.group_cell; ma.group_first = wt.group_first; ma.group_cnt = wt.group_cnt; ma.n_groups = wt.n_groups;
   ma.work_counter = wt.work_counter; ma.blk_off = ix->blk_off; ma.packed = ix->packed; ma.pos = ix->pos;
   ma.surv = ws->w_surv.as<u64>(); ma.surv_count = ws->w_surv_cnt.as<int32_t>();
-  ma.cand_count = (r.found_rule == 1) ? ws->w_cand.as<int32_t>() : nullptr;
+  ma.cand_count = rows_counter(r);
   ma.m = ix->m; ma.M2 = ix->M2; ma.K = ix->K; ma.L = r.L; ma.upi = r.upi;
   memcpy(&ma.sentinel_bits, &r.sentinel, 4);
   const size_t lds = multi_lds_bytes(ix->m, ix->K);
@@ -553,16 +523,8 @@ static int ivf_scan_multi(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   const unsigned grid = (unsigned)std::min<size_t>(wt.max_groups, (size_t)ix->n_cus * per_cu);
   timed_launch(ix, s, "ivf_multi_scan", [&] { hipLaunchKernelGGL(ivf_multi_kernel, dim3(grid), dim3(MULTI_T), lds, s, ma); });
   HIP_TRY(hipGetLastError());
-  const MergeSurvArgs ms = merge_surv_args(r, pa, ma.surv, ma.surv_count, ma.cand_count);
-  timed_launch(ix, s, "merge_surv", [&] { hipLaunchKernelGGL(merge_surv_kernel, dim3(r.n_active), dim3(64), 0, s, ms); });
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launch_merge_surv(r, pa, ma.surv, ma.surv_count, ma.cand_count);
 }
-
-// row blocks per workgroup of the generic scan: one workgroup per (query, probed cell) unless the list is huge -- but a
-// handful of items (the reference's single-query ivfadc_search: W of them) would leave the chip to W workgroups: 32-block
-// chunks then (one query over 10 lists of 3 000 rows: 30 instead of 10 workgroups)
-static int generic_chunk_blocks(int n_items) { return n_items <= 64 ? 32 : 256; }
 
 // Generic path (small batches, other m / S / K, k > 32): lut_build (residual inline) -> adc_scan -> merge_replay;
 // the LUTs round-trip through memory.
@@ -571,23 +533,16 @@ static int ivf_scan_generic(IvfRun& r, const PlanArgs& pa) {
   freddy_gpu_index* ix = r.ix;
   hipStream_t s = r.s;
   const int n_items = r.n_active * r.W;
-  const int chunk_blocks = generic_chunk_blocks(n_items);
-  const int nchunk = std::max(1, (ix->max_list_blocks + chunk_blocks - 1) / chunk_blocks);
+  const Chunks ch = generic_chunks(ix, (size_t)n_items);
   // (the residual r = q - coarse[cell] is formed by the LUT kernel: one launch less in a single query's chain)
   if (int rc = launch_lut(ix, s, r.d_q, pa.item_cell, ws->w_lut.as<float>(), n_items, ix->coarse, pa.item_query)) return rc;
   ScanArgs sa;
   sa.lut = ws->w_lut.as<float>(); sa.item_list = pa.item_cell; sa.item_query = pa.item_query;
   sa.blk_off = ix->blk_off; sa.packed = ix->packed; sa.pos = ix->pos; sa.part = ws->w_part.as<u64>();
   sa.cand_count = ws->w_cand.as<int32_t>();
-  sa.m = ix->m; sa.K = ix->K; sa.chunk_blocks = chunk_blocks; sa.nchunk = nchunk; sa.L = r.L;
+  sa.m = ix->m; sa.K = ix->K; sa.chunk_blocks = ch.blocks; sa.nchunk = ch.n; sa.L = r.L;
   memcpy(&sa.sentinel_bits, &r.sentinel, 4);
-  MergeArgs ma;
-  ma.part = sa.part; ma.active = r.active; ma.pos_to_id = nullptr; ma.round_rows = pa.round_rows;
-  ma.cand_count = sa.cand_count; ma.out_ids = r.d_out_ids; ma.out_dist = r.d_out_dist;
-  ma.found = ws->w_found.as<int32_t>(); ma.next_active = r.next; ma.n_next = ws->w_cnt.as<int32_t>();
-  ma.status = r.d_status;
-  ma.n_active = r.n_active; ma.parts_per_query = r.W * nchunk; ma.L = r.L; ma.k = r.k;
-  ma.found_rule = r.found_rule; ma.first_round = r.first() ? 1 : 0; ma.sentinel = r.sentinel;
+  const MergeArgs ma = merge_args_round(r, pa, sa.part, r.W * ch.n, sa.cand_count);
   if (2 * r.k > 1024) return bigk_select_replay(ix, s, ws, sa, n_items, ma, r.Q);
   if (int rc = launch_scan(ix, s, sa, n_items)) return rc;
   return launch_merge(ix, s, ma);
@@ -616,9 +571,7 @@ static int ivfadc_begin(freddy_gpu_index* ix, hipStream_t s, int share, const fl
   Workspace* ws = workspace_for(ix, s);
   const int C = ix->C, m = ix->m, K = ix->K;
   if (2 * W > 1024) return fail(FREDDY_E_LIMIT, "W=%d exceeds this build's limit of 512 probes per round", W);
-  r.ix = ix; r.ws = ws; r.s = s; r.d_q = d_q; r.Q = Q; r.k = k; r.W = W; r.L = std::min(2 * k, 64 * 16);
-  r.sentinel = sentinel; r.d_out_ids = d_out_ids; r.d_out_dist = d_out_dist; r.d_status = d_status;
-  r.share = std::max(1, share);
+  r = ivf_run(ix, ws, s, share, d_q, Q, k, W, sentinel, d_out_ids, d_out_dist, d_status);
   // FREDDY_FOUND_BATCH_UDF = the accepted-rows rule + the batch UDF's cell limit (argmin from minDist = 1000,
   // freddy.c:853-866); ivfadc_search's cell list starts at 100.0 (freddy.c:266-283)
   r.found_rule = found_rule == FREDDY_FOUND_ROWS ? 0 : 1;
@@ -628,53 +581,35 @@ static int ivfadc_begin(freddy_gpu_index* ix, hipStream_t s, int share, const fl
   // (2k <= 64); lists longer than 8 chunks of 4096 rows would need survivor buffers out of proportion.  They
   // pay off once several (query, cell) items share a cell, i.e. for batches; option fused = 1 / 0 forces
   // them / the generic lut_build + adc_scan kernels (the tests run both).
-  r.upi = std::max(1, (ix->max_list_blocks + FUSED_UNIT_BLOCKS - 1) / FUSED_UNIT_BLOCKS);
-  r.fused = ix->tune.fused != 0 && m == 12 && ix->S == 25 && K <= 1024 && ix->cbP && r.L <= 64 && r.upi <= 8 &&
-            (ix->tune.fused == 1 || items >= 256);
+  r.fused = ix->tune.fused != 0 && fused_shape(ix) && r.L <= 64 && r.upi <= 8 && (ix->tune.fused == 1 || items >= 256);
   r.scan_kernel = (ix->tune.scan_kernel == 3 || !ix->rterm) ? 3 : 5;
   if (!r.fused) {
     // every other shape whose interleaved LUT slab fits the LDS: the cell-grouped exact scan of multi.h (option fused = 0
     // keeps the generic kernels, fused = 1 takes it for small batches too)
-    const bool special = m == 12 && ix->S == 25 && K <= 1024 && ix->cbP;
     // (lists of up to 32 chunks: the reference's shipped 32-cell configuration has 37 000 rows per list)
-    r.fused = ix->tune.fused != 0 && !special && multi_lds_bytes(m, K) <= (size_t)150 * 1024 && r.L <= 64 && r.upi <= 32 &&
+    r.fused = ix->tune.fused != 0 && !fused_shape(ix) && multi_lds_bytes(m, K) <= (size_t)150 * 1024 && r.L <= 64 && r.upi <= 32 &&
               (ix->tune.fused == 1 || items >= 256);
     if (r.fused) r.scan_kernel = 2;
   }
   r.tiled = Q >= 32;
   r.zeroed = r.tiled || ix->d <= 1024;
-  r.records_ready = false; r.merge_slices = 0;
+  r.running_bound = ix->tune.running_bound != 0;
   // (the MFMA tile is 64 queries wide and the plan keeps a query's distances in registers: batches, <= 1024 cells)
   r.approx = ix->tune.coarse_approx != 0 && r.tiled && ix->Cpad <= COARSE_STREAM_MAX_CPAD && 2 * W <= 64 && ix->d <= 300 && ix->d % 4 == 0 && ix->coarseP;
-  const int Cpad = ix->Cpad, used_words = (C + 31) / 32;
-  if (ws->w_distT.ensure(sizeof(float) * (size_t)Q * Cpad) ||
-      ws->w_used.ensure(sizeof(uint32_t) * (size_t)Q * used_words) ||
-      ws->w_item_cell.ensure(sizeof(int32_t) * items) || ws->w_item_query.ensure(sizeof(int32_t) * items) ||
-      ws->w_rows.ensure(sizeof(int32_t) * Q) || ws->w_cand.ensure(sizeof(int32_t) * 2 * Q) ||
-      ws->w_qn2.ensure(sizeof(float) * Q) || ws->w_item_dist.ensure(sizeof(float) * items) ||
-      ws->w_found.ensure(sizeof(int32_t) * Q) || ws->w_act0.ensure(sizeof(int32_t) * Q) ||
-      ws->w_act1.ensure(sizeof(int32_t) * Q) || ws->w_cnt.ensure(sizeof(int32_t) * 8))
-    return fail(FREDDY_E_NOMEM, "workspace allocation failed (Q=%d, W=%d)", Q, W);
+  bool nomem = ivf_run_ensure(r) || ws->w_distT.ensure(sizeof(float) * (size_t)Q * ix->Cpad) ||
+               ws->w_used.ensure(sizeof(uint32_t) * (size_t)Q * ((C + 31) / 32)) || ws->w_qn2.ensure(sizeof(float) * Q);
   if (r.fused) {
-    // cell_count[C] + cursors; cell_items[C][Q]; work table: 3 arrays of (items/G + C + 1) * upi entries
-    if (ws->w_cellcnt.ensure(sizeof(int32_t) * (size_t)C * 3) || ws->w_sorted.ensure(sizeof(int32_t) * (size_t)C * Q) ||
-        ws->w_groups.ensure(sizeof(int32_t) * 3 * ((items / MULTI_G + (size_t)C + 1) * r.upi + items * r.upi)) ||   // + the (item, chunk) units of sparse cells
-        ws->w_surv.ensure(sizeof(u64) * items * r.upi * FUSED_NW * FUSED_RMAX * 64) ||
-        ws->w_surv_cnt.ensure(sizeof(int32_t) * items * r.upi * FUSED_NW))
-      return fail(FREDDY_E_NOMEM, "workspace allocation failed (Q=%d, W=%d)", Q, W);
-    if (r.scan_kernel == 2 && ws->w_lut.ensure(sizeof(float) * items * (size_t)m * K))
-      return fail(FREDDY_E_NOMEM, "workspace allocation failed (Q=%d, W=%d)", Q, W);
-    if (r.scan_kernel == 5 &&
-        (ws->w_qc.ensure(sizeof(uint32_t) * (size_t)Q * m * 640) || ws->w_qn.ensure(sizeof(float) * (size_t)Q * m * 2)))   // (512 + 128: the compact copy, fused8.h)
-      return fail(FREDDY_E_NOMEM, "workspace allocation failed (Q=%d, W=%d)", Q, W);
+    // cell_count[C] + cursors; cell_items[C][Q]; work table: 3 arrays of (items/G + C + 1) * upi entries + the (item, chunk) units of sparse cells
+    nomem = nomem || ws->w_cellcnt.ensure(sizeof(int32_t) * (size_t)C * 3) || ws->w_sorted.ensure(sizeof(int32_t) * (size_t)C * Q) ||
+            ws->w_groups.ensure(sizeof(int32_t) * 3 * ((items / MULTI_G + (size_t)C + 1) * r.upi + items * r.upi)) ||
+            (r.scan_kernel == 2 && ws->w_lut.ensure(sizeof(float) * items * (size_t)m * K));
   } else {
     // (a later probing round has fewer items and may take the finer chunks: room for either)
-    const size_t nchunk_big = (size_t)std::max(1, (ix->max_list_blocks + 255) / 256), nchunk_small = (size_t)std::max(1, (ix->max_list_blocks + 31) / 32);
-    const size_t parts = std::max(items * nchunk_big, std::min<size_t>(items, 64) * nchunk_small);
-    if (ws->w_resid.ensure(sizeof(float) * items * (size_t)ix->d) || ws->w_lut.ensure(sizeof(float) * items * (size_t)m * K) ||
-        ws->w_part.ensure(sizeof(u64) * parts * r.L))   // (adc_scan_kernel leaves ONE list of L keys per (item, chunk): kernels.h)
-      return fail(FREDDY_E_NOMEM, "workspace allocation failed (Q=%d, W=%d)", Q, W);
+    const size_t parts = std::max(items * generic_chunks(ix, items).n, std::min<size_t>(items, GENERIC_FEW_ITEMS) * generic_chunks(ix, GENERIC_FEW_ITEMS).n);
+    nomem = nomem || ws->w_resid.ensure(sizeof(float) * items * (size_t)ix->d) || ws->w_lut.ensure(sizeof(float) * items * (size_t)m * K) ||
+            ws->w_part.ensure(sizeof(u64) * parts * r.L);   // (adc_scan_kernel leaves ONE list of L keys per (item, chunk): kernels.h)
   }
+  if (nomem) return fail(FREDDY_E_NOMEM, "workspace allocation failed (Q=%d, W=%d)", Q, W);
 
   // pieces of whole 32-query tiles; a piece of fewer than 128 queries is not worth a launch of its own
   const int pieces = (stage && by_pieces && ix->tune.coarse_pieces && ivf_coarse_by_pieces(r) && Q >= 512) ? 4 : 1;
@@ -685,8 +620,6 @@ static int ivfadc_begin(freddy_gpu_index* ix, hipStream_t s, int share, const fl
     if (int rc = ivf_coarse(r, q_lo, q_n)) return rc;
   }
   ix->last_Q = Q;
-  r.n_active = Q; r.active = nullptr; r.next = ws->w_act0.as<int32_t>();
-  r.round = 0;
   return ivfadc_round(r);
 }
 
@@ -718,16 +651,16 @@ static int ivfadc_finish(IvfRun& r, int n_next) {
 
 int max_queries_per_chunk(const freddy_gpu_index* ix, int W, int k) {
   // workspace per query: the LUTs of its W items (generic path) or their survivor regions (fused path)
-  const size_t upi = (size_t)std::max(1, (ix->max_list_blocks + FUSED_UNIT_BLOCKS - 1) / FUSED_UNIT_BLOCKS);
+  const size_t upi = (size_t)units_per_item(ix);
   size_t lut_bytes = sizeof(float) * (size_t)ix->m * ix->K * (size_t)W;
   if (2 * k > 64) {
     // lists beyond the cell-grouped scans' selection width take the generic kernels: one list of L keys per (item, chunk) beside
     // the LUTs, and from k = 513 on the passes' selected keys (bigk.h: ceil(2k / 1024) x 1024 per query)
-    const size_t L = (size_t)std::min(2 * k, 1024), nchunk = (size_t)std::max(1, (ix->max_list_blocks + 255) / 256);
+    const size_t L = (size_t)std::min(2 * k, 1024), nchunk = (size_t)generic_chunks(ix, SIZE_MAX).n;   // (a chunk of many items: the coarse chunks)
     lut_bytes += sizeof(u64) * (size_t)W * nchunk * L;
     if (2 * k > 1024) lut_bytes += sizeof(u64) * (size_t)((2 * k + BIGK_PASS - 1) / BIGK_PASS) * BIGK_PASS;
   }
-  const bool special = ix->m == 12 && ix->S == 25 && ix->K <= 1024 && ix->cbP;
+  const bool special = fused_shape(ix);
   const size_t surv_bytes = upi <= (special ? 8u : 32u) ? sizeof(u64) * (size_t)W * upi * FUSED_NW * FUSED_RMAX * 64 : 0;
   const size_t per_query = special ? std::max(lut_bytes, surv_bytes) : lut_bytes + surv_bytes;   // (multi.h: the LUTs of all items AND their survivor regions)
   size_t n = ((size_t)ix->tune.lut_budget_mb << 20) / std::max<size_t>(per_query, 1);
@@ -741,22 +674,14 @@ int max_queries_per_chunk(const freddy_gpu_index* ix, int W, int k) {
 extern "C" int freddy_gpu_ivfadc_search_dev(freddy_gpu_index_t* ix, const float* d_queries, int32_t Q, int32_t k,
                                             int32_t W, float sentinel, int32_t found_rule, int32_t* d_out_ids,
                                             float* d_out_dist, int32_t* d_status, void* hip_stream) {
-  if (int rc = check_search_args(ix, KIND_IVF, d_queries, Q, k, d_out_ids, d_out_dist)) return rc;
-  if (W <= 0) return fail(FREDDY_E_ARG, "W must be positive");
-  if (found_rule < 0 || found_rule > 2 || (found_rule == FREDDY_FOUND_BATCH_UDF && W != 1))
-    return fail(FREDDY_E_ARG, "bad found_rule (FREDDY_FOUND_BATCH_UDF needs W == 1)");
-  if (W > ix->C) W = ix->C;
+  if (int rc = check_ivfadc_args(ix, d_queries, Q, k, &W, found_rule, d_out_ids, d_out_dist)) return rc;
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ix->stream;
-  const int qc = max_queries_per_chunk(ix, W, k);
-  for (int q0 = 0; q0 < Q; q0 += qc) {
-    const int n = std::min(qc, Q - q0);
+  return for_chunks(Q, max_queries_per_chunk(ix, W, k), [&](int q0, int n) {
     IvfRun r;
-    if (int rc = ivfadc_begin(ix, s, scan_share_now(ix->tune.scan_share, false, ix->device), d_queries + (size_t)q0 * ix->d, n, k, W, sentinel, found_rule,
-                              d_out_ids + (size_t)q0 * k, d_out_dist + (size_t)q0 * k, d_status, r))
-      return rc;
-  }
-  return FREDDY_OK;
+    return ivfadc_begin(ix, s, scan_share_now(ix->tune.scan_share, false, ix->device), d_queries + (size_t)q0 * ix->d, n, k, W, sentinel, found_rule,
+                        d_out_ids + (size_t)q0 * k, d_out_dist + (size_t)q0 * k, d_status, r);
+  });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -794,15 +719,14 @@ static int ivfadc_sync_search(freddy_gpu_index* ix, const float* queries, int Q,
       ws->w_out_dist.ensure(sizeof(float) * (size_t)Q * k))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   HIP_TRY(hipMemcpyAsync(ws->w_q.p, queries, sizeof(float) * (size_t)Q * ix->d, hipMemcpyHostToDevice, s));
-  const int qc = max_queries_per_chunk(ix, W, k);
-  for (int q0 = 0; q0 < Q; q0 += qc) {
-    const int n = std::min(qc, Q - q0);
-    IvfRun r;
-    if (int rc = ivfadc_begin(ix, s, scan_share_now(ix->tune.scan_share, true, ix->device), ws->w_q.as<float>() + (size_t)q0 * ix->d, n, k, W, sentinel, found_rule,
-                              ws->w_out_ids.as<int32_t>() + (size_t)q0 * k, ws->w_out_dist.as<float>() + (size_t)q0 * k, nullptr, r))
-      return rc;
-    if (int rc = ivfadc_finish(r, -1)) return rc;
-  }
+  if (int rc = for_chunks(Q, max_queries_per_chunk(ix, W, k), [&](int q0, int n) {
+        IvfRun r;
+        if (int rc = ivfadc_begin(ix, s, scan_share_now(ix->tune.scan_share, true, ix->device), ws->w_q.as<float>() + (size_t)q0 * ix->d, n, k, W, sentinel, found_rule,
+                                  ws->w_out_ids.as<int32_t>() + (size_t)q0 * k, ws->w_out_dist.as<float>() + (size_t)q0 * k, nullptr, r))
+          return rc;
+        return ivfadc_finish(r, -1);
+      }))
+    return rc;
   HIP_TRY(hipMemcpyAsync(out_ids, ws->w_out_ids.p, sizeof(int32_t) * (size_t)Q * k, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(out_dist, ws->w_out_dist.p, sizeof(float) * (size_t)Q * k, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -906,8 +830,7 @@ int one_finish(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, volatile cons
 // out_dist; anything else = not answered here (shape not covered, the reference would probe a second time, or the grid
 // never met at a barrier): the caller takes the multi-round path.
 static bool ivf_one_shape(const freddy_gpu_index* ix, int Q, int k, int W, int found_rule) {
-  return ix->tune.one_launch && !ix->one_launch_failed && Q == 1 && ix->kind == KIND_IVF && ix->m == 12 && ix->S == 25 && ix->d == 300 &&
-         ix->K <= 1024 && (ix->K & 3) == 0 && W <= 32 && 2 * k <= 64 && ix->C <= 4096 && ix->coarse && ix->cbT &&
+  return ix->tune.one_launch && !ix->one_launch_failed && Q == 1 && ix->kind == KIND_IVF && fused_dims(ix) && ix->d == 300 && (ix->K & 3) == 0 && W <= 32 && 2 * k <= 64 && ix->C <= 4096 && ix->coarse && ix->cbT &&
          found_rule != FREDDY_FOUND_BATCH_UDF && ix->replicas.empty();
 }
 static int ivf_one(freddy_gpu_index* ix, const float* queries, int k, int W, float sentinel, int found_rule, int32_t* out_ids,
@@ -1070,11 +993,7 @@ static int ivfadc_host_search(freddy_gpu_index* ix, const float* queries, int Q,
 // for every part but the first; the first failure's code and message are returned on the caller's thread.
 extern "C" int freddy_gpu_ivfadc_search(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k, int32_t W,
                                         float sentinel, int32_t found_rule, int32_t* out_ids, float* out_dist) {
-  if (int rc = check_search_args(ix, KIND_IVF, queries, Q, k, out_ids, out_dist)) return rc;
-  if (W <= 0) return fail(FREDDY_E_ARG, "W must be positive");
-  if (found_rule < 0 || found_rule > 2 || (found_rule == FREDDY_FOUND_BATCH_UDF && W != 1))
-    return fail(FREDDY_E_ARG, "bad found_rule (FREDDY_FOUND_BATCH_UDF needs W == 1)");
-  if (W > ix->C) W = ix->C;
+  if (int rc = check_ivfadc_args(ix, queries, Q, k, &W, found_rule, out_ids, out_dist)) return rc;
   if (Q == 0) return FREDDY_OK;
   return over_replicas(ix, Q, [&](freddy_gpu_index* part, int lo, int hi) {
     return ivfadc_host_search(part, queries + (size_t)lo * ix->d, hi - lo, k, W, sentinel, found_rule, out_ids + (size_t)lo * k,
@@ -1084,19 +1003,15 @@ extern "C" int freddy_gpu_ivfadc_search(freddy_gpu_index_t* ix, const float* que
 
 // The kernels of this unit that want more than the default 64 KiB of dynamic LDS.
 std::vector<LdsLimit> lds_limits_ivfadc() {
-  return {&adc_scan_kernel<12, 1>, &adc_scan_kernel<12, 2>, &adc_scan_kernel<12, 4>, &adc_scan_kernel<12, 8>, &adc_scan_kernel<12, 16>,
-          &adc_scan_kernel<0, 1>, &adc_scan_kernel<0, 2>, &adc_scan_kernel<0, 4>, &adc_scan_kernel<0, 8>, &adc_scan_kernel<0, 16>,
-          &adc_scan_kernel<12, 16, true>, &adc_scan_kernel<0, 16, true>,
-          &ivf_spec2_kernel<25, 12, true>, &ivf_spec2_kernel<25, 12, false>,
-          &ivf_filter5_kernel<12, true, false>, &ivf_filter5_kernel<12, false, false>,
-          &ivf_filter5_kernel<12, true, true>, &ivf_filter5_kernel<12, false, true>,
-          &ivf_filter5_kernel<12, false, false, false, true>, &ivf_filter5_kernel<12, false, true, false, true>,
-          &ivf_filter8_kernel<12, false>, &ivf_filter8_kernel<12, true>,
-#ifdef FREDDY_LAB
-          &ivf_filter5_kernel<12, true, false, true>, &ivf_filter8_kernel<12, false, true>,
-#endif
-          &coarse_approx_kernel, &coarse_approx16_kernel, &ivf_multi_kernel,
-          &coarse_dist_kernel<16>,   // (small batches over vectors of more than 1024 dimensions: 64 bytes per dimension)
-          // (static LDS beside the dynamic: 16384 keys + 4096 carried ids = 144 KB)
-          {&bigk_replay_kernel, (int)bigk_lds_bytes(16384, BIGK_KMAX)}};
+  std::vector<LdsLimit> l = {
+      &ivf_spec2_kernel<25, 12, true>, &ivf_spec2_kernel<25, 12, false>,
+      &coarse_approx_kernel, &coarse_approx16_kernel, &ivf_multi_kernel,
+      &coarse_dist_kernel<16>,   // (small batches over vectors of more than 1024 dimensions: 64 bytes per dimension)
+      // (static LDS beside the dynamic: 16384 keys + 4096 carried ids = 144 KB)
+      {&bigk_replay_kernel, (int)bigk_lds_bytes(16384, BIGK_KMAX)}};
+  for (int i = 0; i < 32; ++i) {   // every kernel the choosers return (one that comes up twice gets its limit twice)
+    if (const auto k = scan_kernel(i & 1, 1 << (i >> 2), i & 2)) l.emplace_back(k);   // (V = 1 .. 128: none beyond 16)
+    if (const auto k = filter_kernel(i & 1, i & 2, i & 4, i & 8, i & 16)) l.emplace_back(k);
+  }
+  return l;
 }

@@ -8,6 +8,16 @@
 #include "one.h"
 #include "io_kernels.h"
 #include "assign.h"
+#include "ivf_host.h"
+
+// kernel choosers (ivfadc.hip).  M2: dwords of codes per row with an instantiation of its own, else 0 = any m
+static decltype(&grouping_kernel<0>) grouping_kernel_for(int M2) {
+  return M2 == 6 ? &grouping_kernel<6> : M2 == 15 ? &grouping_kernel<15> : &grouping_kernel<0>;
+}
+static void (*assign_pq_kernel_for(int M2, int RPT))(AssignPqArgs) {   // RPT: targets per thread, 4 or 1
+  if (M2 == 6) return RPT == 4 ? &assign_pq_kernel<6, 4> : &assign_pq_kernel<6, 1>;
+  return RPT == 4 ? &assign_pq_kernel<0, 4> : &assign_pq_kernel<0, 1>;
+}
 
 // ---------------------------------------------------------------------------------------
 // exhaustive / subset PQ
@@ -39,6 +49,7 @@ __global__ __launch_bounds__(256) void pq_shadow_meta_kernel(const int32_t* __re
   if (i < n_blocks * 64) { const int32_t r = pos[i]; pos_ids[i] = r >= 0 ? ids[r] : -1; }
 }
 
+// (not fused_shape(): a PQ handle has no paired codebook; the exact stage's cbR and the kernels' own K limit are what this path needs)
 static bool pq_fused_shape(const freddy_gpu_index* ix) {
   return ix->kind == KIND_PQ && ix->cbR && ix->m == 12 && ix->S == 25 && ix->K <= FUSED_T * FUSED_E && ix->n_blocks > 0 && ix->N > 0;
 }
@@ -219,51 +230,34 @@ static int pq_fused_chunk(freddy_gpu_index* ix, freddy_gpu_index* fx, hipStream_
                           int32_t* d_out_ids, float* d_out_dist) {
   fx->tune = ix->tune;
   Workspace* ws = workspace_for(fx, s);
-  const int lists = fx->C, m = fx->m, K = fx->K;
+  const int lists = fx->C, m = fx->m;
   // the merge of a small batch over many pseudo-lists: four workgroups per query, each over a quarter of the lists (64 queries
   // x 1 960 survivor regions on 64 workgroups took 62 us on a quarter of the chip); the item space of a query is padded to
   // a multiple of the slices
   const int SL = (lists >= 32 && Q <= 256 && (size_t)lists * FUSED_NW > 256) ? 4 : 0;
   const int W = SL ? ((lists + SL - 1) / SL) * SL : lists;
-  IvfRun r;
-  r.ix = fx; r.ws = ws; r.s = s; r.d_q = d_q; r.Q = Q; r.k = k; r.W = W; r.L = 2 * k;
-  r.sentinel = sentinel; r.cell_limit = 0.0f; r.d_out_ids = d_out_ids; r.d_out_dist = d_out_dist; r.d_status = nullptr;
-  r.found_rule = 0; r.upi = 1; r.fused = true; r.scan_kernel = 5; r.tiled = false; r.zeroed = false; r.approx = false;
-  r.records_ready = true; r.merge_slices = SL;
-  r.n_active = Q; r.round = 0; r.active = nullptr;
-  r.share = scan_share_now(ix->tune.scan_share, false, ix->device);   // (the caller's contract: its batches in flight on this handle)
-  const size_t items = (size_t)Q * W;
+  // filter + refine over the items (query, pseudo-list): records from pq_front_kernel, no found rule, no running bounds (a few dozen queries x
+  // a thousand entries would update the same two cache lines: 96 -> 128 us).  share: the caller's contract, its batches in flight on this handle
+  IvfRun r = ivf_run(fx, ws, s, scan_share_now(ix->tune.scan_share, false, ix->device), d_q, Q, k, W, sentinel, d_out_ids, d_out_dist, nullptr);
+  r.fused = true; r.records_ready = true; r.merge_slices = SL;
   const size_t n_entries = (size_t)((Q + SCAN5_G - 1) / SCAN5_G) * lists;
-  if (ws->w_item_cell.ensure(sizeof(int32_t) * items) || ws->w_item_query.ensure(sizeof(int32_t) * items) ||
-      ws->w_item_dist.ensure(sizeof(float) * items) || ws->w_rows.ensure(sizeof(int32_t) * Q) || ws->w_cand.ensure(sizeof(int32_t) * 2 * Q) ||
-      ws->w_found.ensure(sizeof(int32_t) * Q) || ws->w_act0.ensure(sizeof(int32_t) * Q) || ws->w_act1.ensure(sizeof(int32_t) * Q) ||
-      ws->w_cnt.ensure(sizeof(int32_t) * 8) || ws->w_records.ensure(sizeof(int32_t) * REC_DW * n_entries) ||
-      ws->w_surv.ensure(sizeof(u64) * items * r.upi * FUSED_NW * FUSED_RMAX * 64) ||
-      ws->w_surv_cnt.ensure(sizeof(int32_t) * items * r.upi * FUSED_NW) ||
-      ws->w_qc.ensure(sizeof(uint32_t) * (size_t)Q * m * 640) || ws->w_qn.ensure(sizeof(float) * (size_t)Q * m * 2))   // (512 + 128: the compact copy for K <= 256, fused8.h)
+  if (ivf_run_ensure(r) || ws->w_records.ensure(sizeof(int32_t) * REC_DW * n_entries))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed (Q=%d over %d pseudo-lists)", Q, lists);
-  r.next = ws->w_act0.as<int32_t>();
-  PlanArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.item_cell = ws->w_item_cell.as<int32_t>(); pa.item_query = ws->w_item_query.as<int32_t>(); pa.item_dist = ws->w_item_dist.as<float>();
-  pa.round_rows = ws->w_rows.as<int32_t>(); pa.n_active = Q; pa.C = lists; pa.W = W;
-  WorkTable wt;
-  wt.max_groups = n_entries; wt.group_cell = wt.group_first = wt.group_cnt = nullptr;
-  wt.n_groups = ws->w_cnt.as<int32_t>() + 1; wt.work_counter = ws->w_cnt.as<int32_t>() + 2;
-  wt.sp_cap = 0; wt.sp_cell = wt.sp_first = wt.sp_chunk = nullptr; wt.sp_counter = ws->w_cnt.as<int32_t>() + 3; wt.n_sparse = ws->w_cnt.as<int32_t>() + 4;
+  const PlanArgs pa = plan_items(r, lists);
+  const WorkTable wt = work_counters(ws, n_entries);   // (no tables: the entries are the records, and no cell is scanned item by item)
+  const QueryTable qt = query_table(ws, fx, Q);
   // ONE launch: the table units (query x codebook, int16) and the record workgroups -- the entry records straight from the
   // queries' table scales: no item / work-table / record kernels (pq_front_kernel)
   PqFrontArgs fa;
   fa.queries = d_q; fa.Q = Q; fa.d = fx->d; fa.lists = lists; fa.W = W; fa.n_rows = fx->N; fa.blk_off = fx->blk_off; fa.list_off = fx->list_off;
-  fa.cbT = fx->cbF; fa.cmax = fx->cmaxp; fa.pmax = fx->pmax; fa.qn = ws->w_qn.as<float>(); fa.qscale = ws->w_qn.as<float>() + (size_t)Q * m;
-  fa.qc = ws->w_qc.as<uint32_t>(); fa.m = m; fa.K = K; fa.sentinel = sentinel;
-  fa.qc8 = (fx->packed8 && fx->tune.codes_u8 == 1 && K <= 256 && m == 12) ? ws->w_qc.as<uint32_t>() + (size_t)Q * m * 512 : nullptr; fa.item_cell = pa.item_cell; fa.item_query = pa.item_query;
+  fa.cbT = fx->cbF; fa.cmax = fx->cmaxp; fa.pmax = fx->pmax; fa.qn = qt.qn; fa.qscale = qt.qscale; fa.qc = qt.qc; fa.qc8 = qt.qc8;
+  fa.m = m; fa.K = fx->K; fa.sentinel = sentinel; fa.item_cell = pa.item_cell; fa.item_query = pa.item_query;
   fa.item_dist = pa.item_dist; fa.round_rows = pa.round_rows; fa.records = ws->w_records.as<int32_t>(); fa.n_groups = wt.n_groups;
   // (w_cnt[1] = n_groups is WRITTEN by this launch's record workgroups: not among the words it clears)
   fa.z.p[0] = ws->w_cnt.as<uint32_t>(); fa.z.n[0] = 1;
   fa.z.p[1] = ws->w_cnt.as<uint32_t>() + 2; fa.z.n[1] = 6;
   fa.z.p[2] = ws->w_cand.as<uint32_t>() + Q; fa.z.n[2] = Q;   // the queries' running bounds (FilterArgs::tau_run)
-  fa.z.p[3] = ws->w_surv_cnt.as<uint32_t>(); fa.z.n[3] = (int)(items * r.upi * FUSED_NW);
+  fa.z.p[3] = ws->w_surv_cnt.as<uint32_t>(); fa.z.n[3] = (int)surv_regions(r, (size_t)Q * W);
   fa.z.p[4] = nullptr; fa.z.n[4] = 0;
   const size_t front_lds = std::max<size_t>((size_t)query_codebook5_lds<25, 16>(), (size_t)(1024 + 16 + 2) * sizeof(float));
   timed_launch(fx, s, "pq_front", [&] {
@@ -277,7 +271,7 @@ static int pq_fused_chunk(freddy_gpu_index* ix, freddy_gpu_index* fx, hipStream_
 // word of mapped host memory the kernel sets when one of its bounded polls ran out (the grid was not co-resident): the
 // caller then re-arms the counters and takes the three-launch path.
 static bool pq_one_shape(const freddy_gpu_index* ix, int Q, int k, int64_t n_blocks) {
-  return ix->tune.one_launch && !ix->one_launch_failed && Q == 1 && ix->m == 12 && ix->S == 25 && ix->K <= 1024 && (ix->K & 3) == 0 && ix->d == 300 &&
+  return ix->tune.one_launch && !ix->one_launch_failed && Q == 1 && fused_dims(ix) && (ix->K & 3) == 0 && ix->d == 300 &&
          2 * k <= 64 && n_blocks >= 64 && (int64_t)ix->h_ids.size() == ix->N;
 }
 static int pq_one(freddy_gpu_index* ix, hipStream_t s, const float* h_q, int k, float sentinel, const int32_t* blk_off,
@@ -340,15 +334,20 @@ static int pq_chunk(freddy_gpu_index* ix, hipStream_t s, const float* d_q, int Q
   sa.cand_count = nullptr;
   sa.m = m; sa.K = K; sa.chunk_blocks = chunk_blocks; sa.nchunk = nchunk; sa.L = L;
   memcpy(&sa.sentinel_bits, &sentinel, 4);
-  MergeArgs ma;
-  ma.part = sa.part; ma.active = nullptr; ma.pos_to_id = ix->ids; ma.round_rows = nullptr; ma.cand_count = nullptr;
-  ma.out_ids = d_out_ids; ma.out_dist = d_out_dist; ma.found = nullptr; ma.next_active = nullptr; ma.n_next = nullptr;
-  ma.status = nullptr;
-  ma.n_active = Q; ma.parts_per_query = nchunk; ma.L = L; ma.k = k; ma.found_rule = 0; ma.first_round = 1;
-  ma.sentinel = sentinel;
+  const MergeArgs ma = merge_args_flat(sa.part, Q, nchunk, L, k, sentinel, ix->ids, d_out_ids, d_out_dist);
   if (2 * k > 1024) return bigk_select_replay(ix, s, ws, sa, Q, ma, Q);   // (k > 512: bigk.h)
   if (int rc = launch_scan(ix, s, sa, Q)) return rc;
   return launch_merge(ix, s, ma);
+}
+
+// The chunks of a batch: through the cell-grouped scan of `view` (an IVF-shaped view of the rows), or view == NULL: the generic scan.
+static int pq_batch(freddy_gpu_index* ix, freddy_gpu_index* view, hipStream_t s, const float* d_q, int Q, int k, float sentinel, const int32_t* blk_off,
+                    const uint32_t* packed, const int32_t* pos, int64_t n_blocks, int32_t* d_oi, float* d_od) {
+  return for_chunks(Q, view ? pq_fused_queries_per_chunk(ix, n_blocks) : pq_queries_per_chunk(ix, n_blocks, k), [&](int q0, int n) {
+    const float* q = d_q + (size_t)q0 * ix->d;
+    if (view) return pq_fused_chunk(ix, view, s, q, n, k, sentinel, d_oi + (size_t)q0 * k, d_od + (size_t)q0 * k);
+    return pq_chunk(ix, s, q, n, k, sentinel, blk_off, packed, pos, n_blocks, d_oi + (size_t)q0 * k, d_od + (size_t)q0 * k);
+  });
 }
 
 extern "C" int freddy_gpu_pq_search_dev(freddy_gpu_index_t* ix, const float* d_queries, int32_t Q, int32_t k,
@@ -357,24 +356,9 @@ extern "C" int freddy_gpu_pq_search_dev(freddy_gpu_index_t* ix, const float* d_q
   if (Q == 0) return FREDDY_OK;
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ix->stream;
-  if (pq_use_fused(ix, Q, k)) {
-    if (int rc = pq_shadow_build(ix)) return rc;
-    const int qf = pq_fused_queries_per_chunk(ix, ix->n_blocks);
-    for (int q0 = 0; q0 < Q; q0 += qf) {
-      const int n = std::min(qf, Q - q0);
-      if (int rc = pq_fused_chunk(ix, ix->pq_shadow, s, d_queries + (size_t)q0 * ix->d, n, k, sentinel, d_out_ids + (size_t)q0 * k, d_out_dist + (size_t)q0 * k))
-        return rc;
-    }
-    return FREDDY_OK;
-  }
-  const int qc = pq_queries_per_chunk(ix, ix->n_blocks, k);
-  for (int q0 = 0; q0 < Q; q0 += qc) {
-    const int n = std::min(qc, Q - q0);
-    if (int rc = pq_chunk(ix, s, d_queries + (size_t)q0 * ix->d, n, k, sentinel, ix->blk_off, ix->packed, ix->pos,
-                          ix->n_blocks, d_out_ids + (size_t)q0 * k, d_out_dist + (size_t)q0 * k))
-      return rc;
-  }
-  return FREDDY_OK;
+  const bool fused_path = pq_use_fused(ix, Q, k);
+  if (fused_path) if (int rc = pq_shadow_build(ix)) return rc;
+  return pq_batch(ix, fused_path ? ix->pq_shadow : nullptr, s, d_queries, Q, k, sentinel, ix->blk_off, ix->packed, ix->pos, ix->n_blocks, d_out_ids, d_out_dist);
 }
 
 // "WHERE id IN (...)" over the flat PQ table: unknown ids vanish, duplicates collapse, order = table
@@ -445,13 +429,9 @@ extern "C" int freddy_gpu_pq_search(freddy_gpu_index_t* ix, const float* queries
     if (int rc = pq_subset(ix, s, subset_ids, n_subset, &blk_off, &packed, &pos, &n_blocks, &n_rows)) return rc;
   // (a subset of at least one full pseudo-list: its gathered rows get a view of their own, refreshed on this stream)
   const bool fused_path = pq_use_fused(ix, Q, k) && (!subset_ids || n_blocks >= FUSED_UNIT_BLOCKS);
-  freddy_gpu_index* view = nullptr;
-  if (fused_path && !subset_ids) { if (int rc = pq_shadow_build(ix)) return rc; view = ix->pq_shadow; }
-  if (fused_path && subset_ids) {
-    if (int rc = pq_view_refresh(ix, &ix->pq_sub_view, s, packed, pos, n_blocks, n_rows)) return rc;
-    view = ix->pq_sub_view;
-  }
-  const int qc = fused_path ? pq_fused_queries_per_chunk(ix, n_blocks) : pq_queries_per_chunk(ix, n_blocks, k);
+  if (fused_path && !subset_ids) if (int rc = pq_shadow_build(ix)) return rc;
+  if (fused_path && subset_ids) if (int rc = pq_view_refresh(ix, &ix->pq_sub_view, s, packed, pos, n_blocks, n_rows)) return rc;
+  freddy_gpu_index* const view = !fused_path ? nullptr : subset_ids ? ix->pq_sub_view : ix->pq_shadow;
   if (!fused_path && direct && pq_one_shape(ix, Q, k, n_blocks)) {
     int32_t* err = reinterpret_cast<int32_t*>(ix->hio_out.as<char>() + n_out * 8);   // (the staging block's spare 16 bytes)
     *err = 0;
@@ -470,17 +450,7 @@ extern "C" int freddy_gpu_pq_search(freddy_gpu_index_t* ix, const float* queries
       return FREDDY_OK;
     }
   }
-  for (int q0 = 0; q0 < Q; q0 += qc) {
-    const int n = std::min(qc, Q - q0);
-    if (fused_path) {
-      if (int rc = pq_fused_chunk(ix, view, s, d_q + (size_t)q0 * ix->d, n, k, sentinel, d_oi + (size_t)q0 * k, d_od + (size_t)q0 * k))
-        return rc;
-      continue;
-    }
-    if (int rc = pq_chunk(ix, s, d_q + (size_t)q0 * ix->d, n, k, sentinel, blk_off, packed, pos, n_blocks, d_oi + (size_t)q0 * k,
-                          d_od + (size_t)q0 * k))
-      return rc;
-  }
+  if (int rc = pq_batch(ix, view, s, d_q, Q, k, sentinel, blk_off, packed, pos, n_blocks, d_oi, d_od)) return rc;
   if (!direct) {
     hipLaunchKernelGGL(host_io_out_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, d_oi, d_od, ix->hio_out.as<int32_t>(), (int)n_out);
     HIP_TRY(hipGetLastError());
@@ -522,12 +492,7 @@ extern "C" int freddy_gpu_grouping_pq(freddy_gpu_index_t* ix, const float* group
   if (int rc = launch_lut(ix, s, ws->w_q.as<float>(), nullptr, ws->w_lut.as<float>(), G)) return rc;   // freddy.c:1288-1299
   const dim3 grid((unsigned)((n_blocks + GROUP_BLOCKS - 1) / GROUP_BLOCKS));
   timed_launch(ix, s, "grouping", [&] {
-    if (ix->M2 == 6)
-      hipLaunchKernelGGL((grouping_kernel<6>), grid, dim3(WG), lutN * sizeof(float), s, ws->w_lut.as<float>(), G, m, K, packed, (int)n_blocks, ws->w_out_ids.as<int32_t>());
-    else if (ix->M2 == 15)
-      hipLaunchKernelGGL((grouping_kernel<15>), grid, dim3(WG), lutN * sizeof(float), s, ws->w_lut.as<float>(), G, m, K, packed, (int)n_blocks, ws->w_out_ids.as<int32_t>());
-    else
-      hipLaunchKernelGGL((grouping_kernel<0>), grid, dim3(WG), lutN * sizeof(float), s, ws->w_lut.as<float>(), G, m, K, packed, (int)n_blocks, ws->w_out_ids.as<int32_t>());
+    hipLaunchKernelGGL(grouping_kernel_for(ix->M2), grid, dim3(WG), lutN * sizeof(float), s, ws->w_lut.as<float>(), G, m, K, packed, (int)n_blocks, ws->w_out_ids.as<int32_t>());
   });
   HIP_TRY(hipGetLastError());
   std::vector<int32_t> h_grp((size_t)n_blocks * 64), h_pos((size_t)n_blocks * 64);
@@ -592,12 +557,7 @@ extern "C" int freddy_gpu_pq_assign(freddy_gpu_index_t* ix, const float* queries
       aa.out_query = ws->w_out_ids.as<int32_t>(); aa.out_sim = ws->w_out_dist.as<float>(); aa.best_dist = ws->w_found.as<float>();
       aa.N = ix->N; aa.n_targets = n; aa.q_base = q0; aa.nq = nq; aa.m = m; aa.K = K; aa.LT = LT; aa.first = q0 == 0 ? 1 : 0; aa.sentinel = sentinel;
       const size_t lds = (size_t)LT * lut_bytes;
-      timed_launch(ix, s, "assign_pq_kernel", [&] {
-        if (ix->M2 == 6 && RPT == 4) hipLaunchKernelGGL((assign_pq_kernel<6, 4>), grid, dim3(AS_PQ_WG), lds, s, aa);
-        else if (ix->M2 == 6) hipLaunchKernelGGL((assign_pq_kernel<6, 1>), grid, dim3(AS_PQ_WG), lds, s, aa);
-        else if (RPT == 4) hipLaunchKernelGGL((assign_pq_kernel<0, 4>), grid, dim3(AS_PQ_WG), lds, s, aa);
-        else hipLaunchKernelGGL((assign_pq_kernel<0, 1>), grid, dim3(AS_PQ_WG), lds, s, aa);
-      });
+      timed_launch(ix, s, "assign_pq_kernel", [&] { hipLaunchKernelGGL(assign_pq_kernel_for(ix->M2, RPT), grid, dim3(AS_PQ_WG), lds, s, aa); });
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(out_query + t0, ws->w_out_ids.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
@@ -609,7 +569,9 @@ extern "C" int freddy_gpu_pq_assign(freddy_gpu_index_t* ix, const float* queries
 
 // The kernels of this unit that want more than the default 64 KiB of dynamic LDS.
 std::vector<LdsLimit> lds_limits_pq() {
-  return {&grouping_kernel<6>, &grouping_kernel<15>, &grouping_kernel<0>,
-          // (LUTs staged up to 64 KiB, but at least one: up to 156 KiB for a table at the LUT limit)
-          &assign_pq_kernel<6, 1>, &assign_pq_kernel<6, 4>, &assign_pq_kernel<0, 1>, &assign_pq_kernel<0, 4>};
+  std::vector<LdsLimit> l;
+  for (int M2 : {6, 15, 0}) l.emplace_back(grouping_kernel_for(M2));
+  // (LUTs staged up to 64 KiB, but at least one: up to 156 KiB for a table at the LUT limit)
+  for (int M2 : {6, 0}) { l.emplace_back(assign_pq_kernel_for(M2, 4)); l.emplace_back(assign_pq_kernel_for(M2, 1)); }
+  return l;
 }
