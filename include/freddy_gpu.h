@@ -151,7 +151,12 @@ int freddy_gpu_replica_count(const freddy_gpu_index_t* index);
 
 /* Body of ivpq_search_in (ivpq_search_in.c:61-699), the kNN-join.  Arguments are the
  * SRF's own (ivpq_search_in.c:168-208).  iterations_out (may be NULL) receives the
- * number of alpha-doubling rounds.  out_*: [Q][k], sentinel 1000.0. */
+ * number of alpha-doubling rounds.  out_*: [Q][k], sentinel 1000.0.
+ * Bounds, refused with FREDDY_E_LIMIT before any device work (the message names the value): method 0 (ADC) and method 1
+ * (exact) take k <= 4096 -- up to k = 512 one workgroup selects and replays a query's 2k candidates, beyond that the 2k keys are
+ * selected 1024 per pass over the query's target rows and a second launch writes the lists in closed form (bigk.h; a workspace
+ * of 16 k bytes per scanned query: 328 MB at 5 000 queries and k = 4096); method 2 (post verification) takes k * pvf <= 8192.
+ * The lists are the reference's at every k: ids, ranks and distance bits. */
 int freddy_gpu_knn_join(freddy_gpu_index_t* ivpq, const float* queries, int32_t Q, int32_t k,
                         const int32_t* target_ids, int64_t n_targets, int32_t alpha, int32_t pvf,
                         int32_t method, int32_t use_target_lists, float confidence,
@@ -430,7 +435,8 @@ typedef struct freddy_track {
   double join_kernel_time;                   /* HIP-event time of the join kernel launches alone (inside computation_time) */
   int64_t candidate_rows;                    /* sum over queries of the target rows in their selected cells (what the kernel scans) */
   int32_t iterations;                        /* alpha-doubling rounds */
-  int32_t reserved;
+  int32_t replay_us;                         /* HIP-event time, in microseconds, of the list-writing launches behind the join kernels of a call
+                                              * with methods 0 / 1 and k > 512 (inside join_kernel_time); 0 otherwise (was: reserved, always 0) */
   int64_t host_traversals;                   /* (query, round) pairs whose multi-index traversal ran on the host heap: every one with more than
                                               * 1024 cells; with the device traversal only those it hands back (equal keys in the taken prefix,
                                               * or the host's libm disagreeing with the proposed stop) */

@@ -19,6 +19,8 @@
 //          accepted row at d*.  With A accepted ties and lt rows below d*: the first e = A + lt - k ties are pushed out again;
 //        * order: ascending distance, equal distances by DEscending arrival.
 // One workgroup per query sorts carried list + selected keys (<= 12288 keys, bitonic in LDS) and writes the list.
+// The kNN-join (methods 0 / 1, k > 512) launches step 2 alone behind join_query_kernel<16, true>, which selects its 2k (distance,
+// row) keys inside one kernel: no carried list (first_round), arrival = row number (join_run.h: launch_replay).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

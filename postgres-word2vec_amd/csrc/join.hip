@@ -101,5 +101,7 @@ extern "C" int freddy_gpu_last_track_sized(const freddy_gpu_index_t* ix, void* o
 // The kernels of this unit that want more than the default 64 KiB of dynamic LDS.
 std::vector<LdsLimit> lds_limits_join() {
   return {&join_query_kernel<1>, &join_query_kernel<2>, &join_query_kernel<4>, &join_query_kernel<8>, &join_query_kernel<16>,
-          &join_query_kernel<16, true>};
+          &join_query_kernel<16, true>,
+          // (this unit's copy of the replay kernel: k = 4096 with its 8192 keys sorts 16384 slots)
+          {&bigk_replay_kernel, (int)bigk_lds_bytes(16384, BIGK_KMAX)}};
 }

@@ -61,8 +61,8 @@ enum JoinSlot {
   JW_ACTIVE,       // int32 [Q]           the round's active list
   JW_QCELLS,       // int32 [Q][cells]    device traversal: row q = the cells query q takes
   JW_QCELL_CNT,    // int32 [Q]           device traversal: how many
-  JW_BIG_KEYS,     // u64   [n_scan][L]   BIG: post verification's candidates ...
-  JW_BIG_EXACT,    // float [n_scan][L]   ... and their exact distances
+  JW_BIG_KEYS,     // u64   [n_scan][L]   BIG: the candidates (post verification's, or the 2k keys of methods 0 / 1) ...
+  JW_BIG_EXACT,    // float [n_scan][L]   ... and, for post verification, their exact distances
   JW_SLOTS
 };
 
@@ -101,7 +101,7 @@ struct JoinIndex {
   bool host_traversal = false;   // option join_host_traversal / FREDDY_GPU_JOIN_HOST_TRAVERSAL: every traversal on the host heap
   // stage timers of the last call under the reference's TRACK names (ivpq_search_in.c:234-697)
   freddy_track track;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_replay = nullptr;   // around the join launches; in front of the replay launch
 };
 
 template <class T>
@@ -126,6 +126,7 @@ static inline void join_free(JoinIndex* j) {
   for (int i = 0; i < JW_SLOTS; ++i) if (j->w[i]) (void)hipFree(j->w[i]);
   if (j->ev0) (void)hipEventDestroy(j->ev0);
   if (j->ev1) (void)hipEventDestroy(j->ev1);
+  if (j->ev_replay) (void)hipEventDestroy(j->ev_replay);
   *j = JoinIndex();
 }
 

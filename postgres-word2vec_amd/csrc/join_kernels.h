@@ -175,9 +175,10 @@ struct JoinArgs {
   int32_t* out_ids;           // [n_scan][k]
   float* out_dist;            // [n_scan][k]
   int d, m, K, S, k, L, method, double_codes;
-  // BIG instantiation (post verification of more than 1024 candidates: k * pvf up to 8192): the candidates and their exact distances
+  // BIG instantiation (more than 1024 candidates: k * pvf or 2k up to 8192): the candidates and, for post verification, their
+  // exact distances
   u64* big_keys = nullptr;    // [n_scan][L]
-  float* big_exact = nullptr; // [n_scan][L]
+  float* big_exact = nullptr; // [n_scan][L] (method 2 only)
 };
 
 // The dynamic LDS of join_query_kernel<V>, array by array in the order they lie: X(element type, name, bytes; every size a
@@ -225,9 +226,10 @@ __device__ __forceinline__ float sqdist_seq4(const float* a, const float* __rest
   return acc;
 }
 
-// BIG (method 2 with 1024 < k * pvf <= 8192; V = 16): the k * pvf smallest (ADC distance, row) keys are selected 1024 at a time
-// -- pass p walks the query's candidate rows again and admits only keys above the largest key of pass p - 1 (keys are unique:
-// the row is part of them) -- into a list in memory; post verification and the replay read it there.
+// BIG (V = 16; method 2 with 1024 < k * pvf <= 8192, methods 0 / 1 with 1024 < 2k <= 8192): the L smallest (ADC or exact distance,
+// row) keys are selected 1024 at a time -- pass p walks the query's candidate rows again and admits only keys above the largest
+// key of pass p - 1 (keys are unique: the row is part of them) -- into a list in memory.  Method 2's post verification and
+// replay read it there; for methods 0 / 1 the kernel ends with the passes and bigk_replay_kernel (bigk.h) writes the lists.
 template <int V, bool BIG = false>
 __global__ __launch_bounds__(JOIN_WG) void join_query_kernel(JoinArgs a) {
   static_assert(!BIG || V == 16, "selection passes are 1024 keys wide");
@@ -397,6 +399,8 @@ __global__ __launch_bounds__(JOIN_WG) void join_query_kernel(JoinArgs a) {
     }
   }
   }   // passes
+  // (methods 0 / 1 select only: bigk_replay_kernel, launched behind this kernel, turns the query's keys into its list)
+  if constexpr (BIG) { if (a.method != FREDDY_METHOD_PQ_PV) return; }
   const u64* const cand = BIG ? a.big_keys + (size_t)x * L : lists;
   float* const exact_d = BIG ? a.big_exact + (size_t)x * L : exact;
   for (int i = threadIdx.x; i < k; i += JOIN_WG) { s_d[i] = JOIN_MAX_DIST; s_id[i] = -1; }

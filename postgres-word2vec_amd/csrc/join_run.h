@@ -5,6 +5,7 @@
 #pragma once
 
 #include "internal.h"
+#include "bigk.h"
 #include "join.h"
 
 namespace freddy {
@@ -58,6 +59,7 @@ struct JoinRun {
   // ---- its shape
   int L, V;                // candidates the replay / post verification walks, selection width of join_query_kernel
   bool big, double_codes;  // join_query_kernel<16, true>; pair codes
+  bool replay;             // methods 0 / 1 of a big call: bigk_replay_kernel writes the lists behind the join kernel
   size_t lds;
   int SV, TV;              // widths of side_sort_kernel (Kc codes) and join_traverse_kernel (cells)
   bool dev_trav;           // the multi-index traversal runs on the device
@@ -87,6 +89,7 @@ struct JoinRun {
   bool host_sides_all = false;
   // ---- this round
   int iterations = 0, n_active = 0, min_target = 0;
+  double replay_ms = 0.0;                       // HIP-event time of the replay launches (inside join_kernel_time)
   bool last = false;
   std::vector<int32_t> fb;                      // queries the host heap has to traverse
   std::vector<int32_t> scan, scan_fb, qoff, flat;
@@ -113,6 +116,7 @@ struct JoinRun {
   int fetch_sides(const std::vector<int32_t>& need);
   int launch_traverse(int n_act, int min_target);
   int launch_query(const JoinArgs& a, int n);
+  int launch_replay(const u64* keys);
   bool stop_confirmed(const int32_t* sm);
   int enqueue_fb_rows();
   int enqueue_join();
@@ -148,12 +152,15 @@ inline int JoinRun::begin(JoinIndex* j_, hipStream_t s_, const float* queries_, 
   if (pvf < 1) pvf = 1;                                                                       // :207-209
   double_codes = method != FREDDY_METHOD_EXACT && (int64_t)alpha * k > double_threshold;      // :262-266
   if (double_codes && (int64_t)j->K * j->K > 32768) return join_fail(FREDDY_E_LIMIT, "pair codes of K=%d overflow the reference's int16", j->K);
-  const int64_t Lw = (method == FREDDY_METHOD_PQ_PV) ? (int64_t)k * pvf : 2 * (int64_t)k;
-  // (post verification walks its candidates in (ADC distance, row) order whatever their number: up to 8192 of them, selected 1024
-  // per pass -- join_query_kernel<16, true>; the replay of methods 0 / 1 holds 2k keys in one wave's registers)
-  big = method == FREDDY_METHOD_PQ_PV && Lw > 1024;
-  if (Lw > (big ? 8192 : 1024))
-    return join_fail(FREDDY_E_LIMIT, big ? "k*pvf=%lld exceeds this build's limit of 8192" : "2k=%lld exceeds this build's limit of 1024", (long long)Lw);
+  const bool pv = method == FREDDY_METHOD_PQ_PV;
+  const int64_t Lw = pv ? (int64_t)k * pvf : 2 * (int64_t)k;
+  // (more than 1024 candidates, up to 8192, are selected 1024 per pass -- join_query_kernel<16, true>: post verification walks
+  // them in (ADC distance, row) order whatever their number; the replay of methods 0 / 1 holds up to 1024 keys in one wave's
+  // registers, and beyond that bigk_replay_kernel computes the list the replay would leave -- bigk.h)
+  if (!pv && k > BIGK_KMAX) return join_fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of %d", k, BIGK_KMAX);
+  if (pv && Lw > 8192) return join_fail(FREDDY_E_LIMIT, "k*pvf=%lld exceeds this build's limit of 8192", (long long)Lw);
+  big = Lw > 1024;
+  replay = big && !pv;
   L = (int)Lw;
   V = big ? 16 : pick_V(L);
   for (int i = 0; i < Q * k; ++i) { out_ids[i] = -1; out_dist[i] = JOIN_MAX_DIST; }            // initTopKs :238
@@ -481,9 +488,24 @@ inline void JoinRun::scan_list() {
 // ---- the round's join launch(es)
 inline int JoinRun::launch_query(const JoinArgs& a, int n) {
   const dim3 grid((unsigned)n), block(JOIN_WG);
-  if (a.big_keys) hipLaunchKernelGGL((join_query_kernel<16, true>), grid, block, lds, s, a);
+  if (big) hipLaunchKernelGGL((join_query_kernel<16, true>), grid, block, lds, s, a);
   else if (!with_V(V, [&](auto v) { hipLaunchKernelGGL((join_query_kernel<decltype(v)::value>), grid, block, lds, s, a); }))
     return join_fail(FREDDY_E_LIMIT, "unsupported selection width");
+  JOIN_HIP(hipGetLastError());
+  return 0;
+}
+
+// Methods 0 / 1 of a big call: the round's lists in closed form from the 2k keys join_query_kernel<16, true> left per scanned
+// query.  A round starts from empty lists (first_round), a row's arrival is its row number (the key's low word), and the lists go
+// to the landing zone, row x of the scan list.
+inline int JoinRun::launch_replay(const u64* keys) {
+  BigkArgs b;
+  b.sel = keys; b.active = nullptr; b.pos_to_id = j->ids; b.round_rows = nullptr; b.cand_count = nullptr;
+  b.out_ids = p.out_ids; b.out_dist = p.out_dist; b.found = nullptr; b.next_active = nullptr; b.n_next = nullptr; b.status = nullptr;
+  b.n_active = n_scan; b.nsel = L; b.k = k; b.found_rule = 0; b.first_round = 1; b.sentinel = JOIN_MAX_DIST;
+  b.npad = 2048;
+  while (b.npad < k + L) b.npad *= 2;   // (<= 16384: k <= BIGK_KMAX, L = 2k)
+  hipLaunchKernelGGL(bigk_replay_kernel, dim3((unsigned)n_scan), dim3(BIGK_T), bigk_lds_bytes(b.npad, k), s, b);
   JOIN_HIP(hipGetLastError());
   return 0;
 }
@@ -512,9 +534,11 @@ inline int JoinRun::enqueue_join() {
   a.queries = d_q; a.tcell_off = d_tcell; a.trow = d_trow;
   a.ids = j->ids; a.codes = j->codes; a.MP = j->MP; a.vectors = j->vectors; a.cbT = j->cbT;
   a.d = j->d; a.m = j->m; a.K = j->K; a.S = j->S; a.k = k; a.L = L; a.method = method; a.double_codes = double_codes ? 1 : 0;
-  if (big && (join_buf(j, JW_BIG_KEYS, (size_t)n_scan * L, &a.big_keys) || join_buf(j, JW_BIG_EXACT, (size_t)n_scan * L, &a.big_exact)))
+  if (big && (join_buf(j, JW_BIG_KEYS, (size_t)n_scan * L, &a.big_keys) ||
+              (!replay && join_buf(j, JW_BIG_EXACT, (size_t)n_scan * L, &a.big_exact))))
     return FREDDY_E_NOMEM;
-  if (!j->ev0) { JOIN_HIP(hipEventCreate(&j->ev0)); JOIN_HIP(hipEventCreate(&j->ev1)); }
+  u64* const big_keys = a.big_keys;
+  if (!j->ev0) { JOIN_HIP(hipEventCreate(&j->ev0)); JOIN_HIP(hipEventCreate(&j->ev1)); JOIN_HIP(hipEventCreate(&j->ev_replay)); }
   JOIN_HIP(hipEventRecord(j->ev0, s));
   // (a separate launch for the host-traversed queries ran behind the main one -- a lone workgroup's 45 us -- and its two
   // list uploads were SDMA hops: a query with a tie cost the call 0.1 ms)
@@ -532,7 +556,12 @@ inline int JoinRun::enqueue_join() {
     if (!flat.empty()) JOIN_HIP(hipMemcpyAsync(d_flat, flat.data(), sizeof(int32_t) * flat.size(), hipMemcpyHostToDevice, s));
     a.scan_query = d_scan + n_dev; a.qcell_off = d_qoff; a.qcell_cnt = nullptr; a.qstride = 0;
     a.qcells = d_flat; a.out_ids = p.out_ids + (size_t)n_dev * k; a.out_dist = p.out_dist + (size_t)n_dev * k;
+    if (big) { a.big_keys += (size_t)n_dev * L; if (a.big_exact) a.big_exact += (size_t)n_dev * L; }   // (rows x of the scan list, as the lists)
     if (int rc = launch_query(a, n_fb)) return rc;
+  }
+  if (replay) {
+    JOIN_HIP(hipEventRecord(j->ev_replay, s));
+    if (int rc = launch_replay(big_keys)) return rc;
   }
   JOIN_HIP(hipEventRecord(j->ev1, s));
   if (dev_trav && !last && (int64_t)k * alpha * 2 < INT32_MAX) {   // the next round's cells for everyone still active (see spec_index)
@@ -551,6 +580,7 @@ inline int JoinRun::scan_round() {
     JOIN_HIP(hipStreamSynchronize(s));
     mark("join synchronised");
     { float ms = 0.0f; if (hipEventElapsedTime(&ms, j->ev0, j->ev1) == hipSuccess) j->track.join_kernel_time += 1e-3 * ms; }
+    if (replay) { float ms = 0.0f; if (hipEventElapsedTime(&ms, j->ev_replay, j->ev1) == hipSuccess) replay_ms += ms; }
     for (int x = 0; x < n_scan; ++x) {
       memcpy(out_ids + (size_t)scan[x] * k, h.out_ids + (size_t)x * k, sizeof(int32_t) * k);
       memcpy(out_dist + (size_t)scan[x] * k, h.out_dist + (size_t)x * k, sizeof(float) * k);
@@ -582,6 +612,7 @@ inline void JoinRun::requeue() {
 inline void JoinRun::end() {
   if (!tl_hit) j->tl_valid = true;   // (the offsets arrived with the first synchronisation)
   j->track.iterations = iterations;
+  j->track.replay_us = (int32_t)std::min(replay_ms * 1e3 + 0.5, (double)INT32_MAX);
   j->track.total_time = std::chrono::duration<double>(Clock::now() - t_start).count();
   if (iterations_out) *iterations_out = iterations;
 }

@@ -565,7 +565,7 @@ class IVPQIndex(_Index):
         n = self.lib.freddy_gpu_last_track_sized(self.h, C.byref(t), C.sizeof(t))
         if n < 0:
             _check(n)
-        return {n: getattr(t, n) for n, _ in Track._fields_ if n != "reserved"}
+        return {n: getattr(t, n) for n, _ in Track._fields_}
 
 
 class Track(C.Structure):
@@ -575,7 +575,7 @@ class Track(C.Structure):
                 ("computation_time", C.c_double), ("pv_computation_time", C.c_double),
                 ("recalculate_query_indices_time", C.c_double), ("total_time", C.c_double),
                 ("join_kernel_time", C.c_double), ("candidate_rows", C.c_int64),
-                ("iterations", C.c_int32), ("reserved", C.c_int32), ("host_traversals", C.c_int64),
+                ("iterations", C.c_int32), ("replay_us", C.c_int32), ("host_traversals", C.c_int64),
                 ("libm_checks", C.c_int64)]
 
 
