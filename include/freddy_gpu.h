@@ -389,6 +389,31 @@ int freddy_gpu_append_rows(freddy_gpu_index_t* index, int64_t n, const int32_t* 
  * its capacity (at least a fresh pin's figure, at most the figure before the call).  A compacted ivf list loses part of the
  * bank-conflict arrangement a fresh pin gives it: speed only, never a result. */
 int freddy_gpu_remove_rows(freddy_gpu_index_t* index, int64_t n, const int32_t* ids, int64_t* removed /* may be NULL */);
+/* Update rows of a pinned index in HBM (an UPDATE of rows of the table behind it: a row keeps its id and gets a new vector, and
+ * with it new codes and possibly a new coarse cell).  For every i whose ids[i] is the id of a pinned row, that row's payload
+ * becomes the i-th one given; its id stays.  The payload arrays are those append_rows takes for the handle's kind -- pq: codes;
+ * ivf (with its replicas): coarse_id, codes; ivpq: coarse_id, codes, and vectors if the handle was pinned with vectors; a vector
+ * handle: vectors.  Afterwards every entry point that takes the handle answers bit for bit as a fresh pin of the same table with
+ * those rows replaced, served by the same kernels.  N, the ids and the largest pinned id do not change: a later append_rows must
+ * still start above the same id.  ids may come in any order; an id that no pinned row has is skipped (its payload is still
+ * validated); *updated (may be NULL) receives the number of rows that changed.  n == 0 succeeds and changes nothing; a call in
+ * which no id is known changes nothing, the footprint included.
+ * Refused with FREDDY_E_ARG before anything on the device has changed (the message names the value and its position): an id
+ * listed twice (which payload would win is undefined), a negative id, n < 0, ids == NULL with n > 0, a NULL handle, a payload
+ * array the kind needs but did not get, a coarse_id outside the cells, a code outside [0, K); n above INT32_MAX is refused with
+ * FREDDY_E_LIMIT at the same point.  *updated is written on success only (with replicas: once every one has followed).  Vectors are accepted whatever
+ * their values, as a fresh pin accepts them: the exact filter's statistics are taken again over all rows (the filter goes off
+ * when a row turns non-finite and comes back when the only such row turns finite).
+ * pq: the row's code words are rewritten in its slot; ivf: in its slot while the cell stays, else the row leaves its list
+ * (a stable compaction, as remove_rows) and joins the end of the new one (as append_rows) -- the order inside a list affects
+ * speed only, never a result; ivpq and vectors: the rows are overwritten in place.
+ * Like append_rows and remove_rows the call synchronises the handle's own stream first; it must NOT run beside *_dev searches
+ * the caller has in flight on other streams -- drain them first.  Replicas follow append_rows' rule: the primary first; a
+ * failure after the first device has changed poisons the handle.  Once the arguments have passed, arrays are written in
+ * place: a HIP failure after the first write poisons the handle too.  freddy_gpu_index_bytes afterwards equals a fresh pin's
+ * for pq, ivf and ivpq; a vector handle's figure does not move unless the filter's state does. */
+int freddy_gpu_update_rows(freddy_gpu_index_t* index, int64_t n, const int32_t* ids, const int32_t* coarse_id,
+                           const int16_t* codes, const float* vectors, int64_t* updated /* may be NULL */);
 /* Replace the codebook of a pinned pq / ivf / ivpq index (updateCodebookRelation, index_utils.c:959-991) and
  * re-derive everything on the device that depends on it. */
 int freddy_gpu_update_codebook(freddy_gpu_index_t* index, const float* codebook /*[m][K][d/m]*/);

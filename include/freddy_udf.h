@@ -288,6 +288,16 @@ int insert_batch(freddy_session_t* s, const float* norm_vectors, int32_t n, int3
  * number of rows that left google_vecs_norm.  Afterwards every UDF, and a following insert_batch (whose "max(id) + 1" sees
  * the rows that are left), behaves as on a session loaded from the remaining rows.  The codebooks and their count columns stay. */
 int delete_rows(freddy_session_t* s, const int32_t* ids, int64_t n, int64_t* removed);
+/* The mirror of UPDATE google_vecs_norm SET vector = ... WHERE id = ... together with the re-quantisation of the same ids in
+ * pq_quantization, fine_quantization and fine_quantization_ivpq: the rows keep their ids; their codes and cells come from
+ * freddy_gpu_insert_quantize against the session's CURRENT codebooks (the multi-index cell by insert_batch's formula), and the
+ * vectors are stored as given.  The codebooks and their count columns do not change: plain DML does not run updateCodebook.
+ * Every handle the session has pinned is updated in HBM (freddy_gpu_update_rows) instead of being pinned again, and the host
+ * copy of google_vecs_norm follows; google_vecs (the original table) is not touched.  ids are handled per table as delete_rows
+ * handles them -- an id a table does not have is skipped there -- but an id listed twice, like a negative one, is refused
+ * before anything changes.  *updated (may be NULL) receives the number of rows of google_vecs_norm that changed.  A device
+ * failure drops the handles and leaves the host tables as they were, as in insert_batch. */
+int update_rows(freddy_session_t* s, const int32_t* ids, const float* norm_vectors, int64_t n, int32_t dim, int64_t* updated);
 
 /* per-call row emit: snprintf("%d") / snprintf("%f") into 16-byte buffers   freddy.c:154-169,1001-1023 */
 void freddy_emit_row2(const freddy_row2* row, char values[2][16]);

@@ -15,7 +15,9 @@
 
 // ---- exact brute-force kNN as filter + refine (exact2.h) ----------------------------------------------------------------------
 // The table's largest |element| / largest row norm over rows [r0, r0 + n) of the row-major copy, folded into the handle's.
-int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n) {
+// changed_strips (update_rows, r0 = 0): the 32-row strips that hold a rewritten row -- all that is laid out again when the state
+// the statistics lead to is the one the fragment copy was built for.
+int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n, const std::vector<int32_t>* changed_strips) {
   const bool shape_ok = ix->d % 4 == 0 && ix->d <= 512 && ix->d >= 16;
   if (!shape_ok) { ix->exf_ok = false; return 0; }
   if (ix->tune.exact_filter == 0 || ix->exf_never) { ix->exf_never = true; ix->exf_ok = false; return 0; }   // (option exact_filter = 0 when the table is pinned: no third copy of it -- nor later, when remove_rows takes the statistics again from row 0)
@@ -32,6 +34,8 @@ int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n) {
   float amax, n2;
   memcpy(&amax, &h[0], 4); memcpy(&n2, &h[1], 4);
   const bool first = r0 == 0;
+  const bool was_ok = ix->exf_ok;
+  const int ex_before = ix->exf_ex;
   if (h[2] || !(n2 < 1e30f)) { ix->exf_ok = false; return 0; }
   const float xn = std::sqrt(n2) * (1.0f + 1e-5f);
   int64_t relayout_from = r0;
@@ -54,9 +58,30 @@ int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n) {
     ix->exf_xf.release();
     ix->exf_xf = bigger;
   }
+  // update_rows: the scale and the strip count are those of the copy that is there -> only the strips that hold a changed row
+  // (exf_xf_strips already equals `strips` on this path, so it stays; a list that names a strip outside the copy is not used: every
+  // strip is laid out below instead)
+  bool listed = first && changed_strips && was_ok && ex_before == ix->exf_ex && ix->exf_xf_strips == strips && need <= ix->exf_xf.cap;
+  if (listed)
+    for (int32_t st : *changed_strips) listed = listed && st >= 0 && st < strips;
+  if (listed) {
+    if (changed_strips->empty()) return 0;
+    DevBuf list;
+    if (list.ensure(sizeof(int32_t) * changed_strips->size())) return fail(FREDDY_E_NOMEM, "device allocation failed");
+    int rc = 0;
+    if (hipMemcpyAsync(list.p, changed_strips->data(), sizeof(int32_t) * changed_strips->size(), hipMemcpyHostToDevice, ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "hipMemcpy failed");
+    if (!rc) {
+      const int64_t threads = (int64_t)changed_strips->size() * T * 64;
+      hipLaunchKernelGGL(exf_layout_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ix->stream, ix->coarse, n_total, ix->d, T, ix->exf_ex,
+                         (int64_t)0, (int64_t)changed_strips->size(), list.as<int32_t>(), ix->exf_xf.as<h8v>());
+      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "laying out the changed strips failed");
+    }
+    list.release();
+    return rc;
+  }
   const int64_t threads = (strips - strip0) * T * 64;
   hipLaunchKernelGGL(exf_layout_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ix->stream, ix->coarse, n_total, ix->d, T, ix->exf_ex,
-                     strip0, strips - strip0, ix->exf_xf.as<h8v>());
+                     strip0, strips - strip0, (const int32_t*)nullptr, ix->exf_xf.as<h8v>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ix->stream));
   ix->exf_xf_strips = strips;

@@ -101,13 +101,13 @@ __global__ __launch_bounds__(256) void exf_table_stats_kernel(const float* __res
 // 64 cache-line lookups per load instruction: 4.7 instead of 6.0 TB/s -- measured with lane-linear addresses), and the
 // conversion leaves the kernel.  Same bytes as the fp32 rows.
 __global__ __launch_bounds__(256) void exf_layout_kernel(const float* __restrict__ rows, int64_t n_rows, int d, int T, int ex,
-                                                        int64_t strip0, int64_t n_strips, h8v* __restrict__ xf) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;      // (strip - strip0, t, lane)
+                                                        int64_t strip0, int64_t n_strips, const int32_t* __restrict__ strip_list, h8v* __restrict__ xf) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;      // (strip - strip0, t, lane); strip_list: its n_strips entries instead of the range
   if (i >= n_strips * T * 64) return;
   const int lane = (int)(i & 63);
   const int64_t st = i >> 6;
   const int t = (int)(st % T);
-  const int64_t strip = strip0 + st / T;
+  const int64_t strip = strip_list ? (int64_t)strip_list[st / T] : strip0 + st / T;
   const int64_t row = strip * 32 + (lane & 31);
   const int g = lane >> 5;
   h8v hi, lo;

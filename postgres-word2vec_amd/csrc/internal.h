@@ -1,7 +1,7 @@
 // internal.h -- what the translation units of libfreddy_gpu.so share on the HOST side: the handle, its workspaces and
 // options, error reporting, and the functions one unit calls in another.  The C ABI is include/freddy_gpu.h; the units:
 //   core.hip    errors, options, workspaces, profiling records, unpin, counters
-//   pin.hip     pin_pq / pin_ivf(_multi): table layouts; append_rows / remove_rows / update_codebook (HBM index mutation; remove_kernels.h)
+//   pin.hip     pin_pq / pin_ivf(_multi): table layouts; append_rows / remove_rows / update_rows / update_codebook (HBM index mutation; remove_kernels.h, update_kernels.h)
 //   ivfadc.hip  the IVFADC search: cell selection, work table, scans, merge; *_dev entry, host-buffer pipeline, one-query launch
 //   pq.hip      pq_search (+ subsets, pseudo-list batches, one-query launch), grouping_pq
 //               ivf_host.h what these two share on the host: shape predicates and sizes, the query table's layout, the run state of a chain, merge arguments
@@ -264,7 +264,7 @@ struct freddy_gpu_index {
   // replicas of this index on further devices (freddy_gpu_pin_ivf_multi): a host batch is split contiguously over
   // this handle and its replicas; every replica is a complete pinned index of its own
   std::vector<freddy_gpu_index*> replicas;
-  // set when a mutation (append_rows / remove_rows / update_codebook / set_option) failed after it had already changed some of the devices
+  // set when a mutation (append_rows / remove_rows / update_rows / update_codebook / set_option) failed after it had already changed some of the devices
   // behind this handle: the replicas no longer hold the same tables, so every search fails loudly until the handle is unpinned
   bool registered = false;        // counted in the registry of backends (core.hip backend_handles)
   bool poisoned = false;
@@ -390,7 +390,7 @@ int one_finish(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, volatile cons
 int pq_shadow_build(freddy_gpu_index* ix);
 
 // ---- exact.hip ----
-int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n);
+int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n, const std::vector<int32_t>* changed_strips = nullptr);
 
 template <class F>
 static int over_replicas(freddy_gpu_index* ix, int Q, F&& fn) {

@@ -1,10 +1,11 @@
-// pin.hip -- pin_pq / pin_ivf / pin_ivf_multi: the pinned tables' layouts in HBM; append_rows / remove_rows / update_codebook.
+// pin.hip -- pin_pq / pin_ivf / pin_ivf_multi: the pinned tables' layouts in HBM; append_rows / remove_rows / update_rows / update_codebook.
 #include "internal.h"
 
 #include "kernels.h"
 #include "scan_common.h"
 #include "coarse.h"   // fragment layouts of the centroids; refine.h: row_term_kernel
 #include "remove_kernels.h"
+#include "update_kernels.h"
 
 static std::vector<float> transpose_codebook(const float* cb, int m, int K, int S) {
   std::vector<float> t((size_t)m * S * K);
@@ -968,6 +969,252 @@ extern "C" int freddy_gpu_remove_rows(freddy_gpu_index_t* ix, int64_t n, const i
     default: return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
   }
   if (removed) *removed = gone;
+  return FREDDY_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// update_rows: the UPDATE of a row -- the id stays, the payload changes (kernels in update_kernels.h)
+// ---------------------------------------------------------------------------------------
+// The slots (block * 64 + lane) and lists of the rows whose pos is one of `upd` (ascending, distinct), -1 where no slot has it.
+// Synchronises the stream.  Every pair is checked against the layout before the caller hands it to a kernel.
+static int locate_packed_rows(freddy_gpu_index* ix, int n_lists, const std::vector<int32_t>& upd, std::vector<int64_t>& slot, std::vector<int32_t>& cell) {
+  const size_t n = upd.size();
+  slot.assign(n, -1);
+  cell.assign(n, 0);
+  if (ix->n_blocks <= 0 || n == 0) return 0;
+  RemoveScratch tmp;
+  int32_t* d_upd = tmp.put(upd.data(), n);
+  int64_t* d_slot = tmp.get<int64_t>(n);
+  int32_t* d_cell = tmp.get<int32_t>(n);
+  if (!d_upd || !d_slot || !d_cell) return fail(FREDDY_E_NOMEM, "device allocation failed while updating rows");
+  HIP_TRY(hipMemsetAsync(d_slot, 0xff, sizeof(int64_t) * n, ix->stream));
+  HIP_TRY(hipMemsetAsync(d_cell, 0, sizeof(int32_t) * n, ix->stream));
+  hipLaunchKernelGGL(up_locate_kernel, dim3((unsigned)((ix->n_blocks + 3) / 4)), dim3(256), 0, ix->stream, ix->pos, ix->blk_cell, ix->n_blocks, d_upd, (int)n,
+                     d_slot, d_cell);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(slot.data(), d_slot, sizeof(int64_t) * n, hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipMemcpyAsync(cell.data(), d_cell, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  for (size_t j = 0; j < n; ++j)
+    if (slot[j] < -1 || slot[j] >= ix->n_blocks * 64 || (slot[j] >= 0 && (cell[j] < 0 || cell[j] >= n_lists)))
+      return fail(FREDDY_E_HIP, "row %d sits in slot %lld of list %d: the pinned layout is inconsistent", upd[j], (long long)slot[j], cell[j]);
+  return 0;
+}
+
+// the code words of n rows rewritten in their slots (pos keeps its value: row_pos[i] is what the slot holds already)
+static int rewrite_packed_rows(freddy_gpu_index* ix, const std::vector<int64_t>& slot, const std::vector<int32_t>& row_pos, const std::vector<int16_t>& codes) {
+  const size_t n = slot.size();
+  if (n == 0) return 0;
+  RemoveScratch tmp;
+  int64_t* d_slot = tmp.put(slot.data(), n);
+  int32_t* d_pos = tmp.put(row_pos.data(), n);
+  int16_t* d_codes = tmp.put(codes.data(), codes.size());
+  if (!d_slot || !d_pos || !d_codes) return fail(FREDDY_E_NOMEM, "device allocation failed while updating rows");
+  hipLaunchKernelGGL(place_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ix->stream, d_slot, d_pos, d_codes, (int64_t)n, ix->packed, ix->pos, ix->m, ix->M2);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess) return fail(FREDDY_E_HIP, "rewriting the rows' codes failed");
+  return 0;
+}
+
+// dst row rows[j] <- the j-th of n host rows of e elements of T (a whole number of 4-byte words), enqueued on the stream
+template <class T>
+static int scatter_rows(freddy_gpu_index* ix, RemoveScratch& tmp, const T* h_src, int64_t n, int e, const int32_t* d_rows, T* dst) {
+  T* d_src = tmp.put(h_src, (size_t)n * e);
+  if (!d_src) return fail(FREDDY_E_NOMEM, "device allocation failed while updating rows");
+  const int wpr = (int)(sizeof(T) * e / 4);
+  hipLaunchKernelGGL(up_scatter_rows_kernel, dim3((unsigned)((n * wpr + 255) / 256)), dim3(256), 0, ix->stream, reinterpret_cast<const uint32_t*>(d_src),
+                     reinterpret_cast<uint32_t*>(dst), d_rows, n, wpr);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// What the call does once its arguments have passed: known[] = positions (in the caller's arrays) of the ids a pinned row has,
+// rows[] = their row indices (flat kinds) -- both in ascending row order.  Arrays are written in place.
+static int update_rows_checked(freddy_gpu_index* ix, int64_t n, const int32_t* ids, const int32_t* coarse_id, const int16_t* codes, const float* vectors,
+                               int64_t* changed, bool* wrote) {
+  *changed = 0;
+  *wrote = false;
+  auto flat_rows = [&](const std::vector<int32_t>& h_ids, std::vector<int32_t>& rows, std::vector<int64_t>& known) {
+    std::vector<std::pair<int32_t, int64_t>> hit;
+    for (int64_t i = 0; i < n; ++i)
+      if (const int32_t r = row_of(h_ids, ids[i]); r >= 0) hit.emplace_back(r, i);
+    std::sort(hit.begin(), hit.end());
+    for (auto& h : hit) { rows.push_back(h.first); known.push_back(h.second); }
+  };
+  switch (ix->kind) {
+    case KIND_PQ: {
+      std::vector<int32_t> rows, cell;
+      std::vector<int64_t> known, slot;
+      flat_rows(ix->h_ids, rows, known);
+      if (rows.empty()) return 0;
+      if (int rc = locate_packed_rows(ix, 1, rows, slot, cell)) return rc;   // flat table: pos = row index
+      std::vector<int16_t> new_codes(rows.size() * (size_t)ix->m);
+      for (size_t j = 0; j < rows.size(); ++j) {
+        if (slot[j] < 0) return fail(FREDDY_E_HIP, "row %d has no slot: the pinned layout is inconsistent", rows[j]);
+        std::copy(codes + (size_t)known[j] * ix->m, codes + (size_t)(known[j] + 1) * ix->m, new_codes.begin() + j * (size_t)ix->m);
+      }
+      // views of the flat table are rebuilt from the new codes on next use
+      if (ix->pq_shadow) { free_index(ix->pq_shadow); ix->pq_shadow = nullptr; }
+      if (ix->pq_sub_view) { free_index(ix->pq_sub_view); ix->pq_sub_view = nullptr; }
+      *wrote = true;
+      if (int rc = rewrite_packed_rows(ix, slot, rows, new_codes)) return rc;
+      *changed = (int64_t)rows.size();
+      return build_packed8(ix);
+    }
+    case KIND_IVF: {
+      std::vector<std::pair<int32_t, int64_t>> by_id((size_t)n);
+      for (int64_t i = 0; i < n; ++i) by_id[(size_t)i] = {ids[i], i};
+      std::sort(by_id.begin(), by_id.end());
+      std::vector<int32_t> want((size_t)n), cell;
+      for (int64_t j = 0; j < n; ++j) want[(size_t)j] = by_id[(size_t)j].first;
+      std::vector<int64_t> slot;
+      if (int rc = locate_packed_rows(ix, ix->C, want, slot, cell)) return rc;   // (pos holds the ids; only the device knows an id's list)
+      std::vector<int64_t> stay_slot;
+      std::vector<int32_t> stay_id, move_id, move_cell;
+      std::vector<int16_t> stay_codes, move_codes;
+      for (int64_t j = 0; j < n; ++j) {
+        if (slot[(size_t)j] < 0) continue;
+        const int64_t i = by_id[(size_t)j].second;
+        const int16_t* row = codes + (size_t)i * ix->m;
+        if (coarse_id[i] == cell[(size_t)j]) {
+          stay_slot.push_back(slot[(size_t)j]); stay_id.push_back(ids[i]); stay_codes.insert(stay_codes.end(), row, row + ix->m);
+        } else {
+          move_id.push_back(ids[i]); move_cell.push_back(coarse_id[i]); move_codes.insert(move_codes.end(), row, row + ix->m);
+        }
+      }
+      if (stay_id.empty() && move_id.empty()) return 0;
+      const int32_t max_id = ix->max_id;
+      *wrote = true;
+      if (int rc = rewrite_packed_rows(ix, stay_slot, stay_id, stay_codes)) return rc;
+      *changed = (int64_t)stay_id.size();
+      if (!move_id.empty()) {   // out of the old lists (a stable compaction), then to the end of the new ones
+        int64_t gone = 0;
+        int32_t unused = -1;
+        if (int rc = remove_packed_rows(ix, ix->C, move_id, false, &gone, &unused)) return rc;
+        *changed += gone;
+        if (gone != (int64_t)move_id.size()) return fail(FREDDY_E_HIP, "%lld of %zu rows left their lists: the pinned layout is inconsistent", (long long)gone, move_id.size());
+        if (int rc = append_packed_rows(ix, ix->C, (int64_t)move_id.size(), move_cell.data(), move_id.data(), move_codes.data())) return rc;
+      } else if (int rc = build_packed8(ix)) return rc;
+      ix->max_id = max_id;      // no id has come or gone
+      return refresh_row_terms(ix);
+    }
+    case KIND_IVPQ: {
+      JoinIndex& j = ix->join;
+      std::vector<int32_t> rows;
+      std::vector<int64_t> known;
+      flat_rows(j.h_ids, rows, known);
+      if (rows.empty()) return 0;
+      const size_t k = rows.size();
+      std::vector<int32_t> new_cell(k);
+      std::vector<int16_t> new_codes(k * (size_t)j.m);
+      std::vector<float> new_vec(j.has_vectors ? k * (size_t)j.d : 0);
+      for (size_t r = 0; r < k; ++r) {
+        new_cell[r] = coarse_id[known[r]];
+        std::copy(codes + (size_t)known[r] * j.m, codes + (size_t)(known[r] + 1) * j.m, new_codes.begin() + r * (size_t)j.m);
+        if (j.has_vectors) std::copy(vectors + (size_t)known[r] * j.d, vectors + (size_t)(known[r] + 1) * j.d, new_vec.begin() + r * (size_t)j.d);
+      }
+      RemoveScratch tmp;
+      int32_t* d_rows = tmp.put(rows.data(), k);
+      if (!d_rows) return fail(FREDDY_E_NOMEM, "device allocation failed while updating rows");
+      j.tl_valid = false;   // (the cached target lists are bucketed by cell)
+      *wrote = true;
+      int rc = scatter_rows(ix, tmp, new_cell.data(), (int64_t)k, 1, d_rows, j.cell);
+      if (!rc) rc = scatter_rows(ix, tmp, join_pad_codes(new_codes.data(), (int64_t)k, j.m, j.MP).data(), (int64_t)k, j.MP, d_rows, j.codes);
+      if (!rc && j.has_vectors) rc = scatter_rows(ix, tmp, new_vec.data(), (int64_t)k, j.d, d_rows, j.vectors);
+      if (!rc) *changed = (int64_t)k;
+      if (hipStreamSynchronize(ix->stream) != hipSuccess && !rc) rc = fail(FREDDY_E_HIP, "rewriting the ivpq rows failed");
+      if (rc) return rc;
+      for (size_t r = 0; r < k; ++r) j.h_cell[(size_t)rows[r]] = new_cell[r];
+      return 0;
+    }
+    case KIND_VEC: {
+      std::vector<int32_t> rows;
+      std::vector<int64_t> known;
+      flat_rows(ix->h_ids, rows, known);
+      if (rows.empty()) return 0;
+      const size_t k = rows.size();
+      const int d = ix->d;
+      std::vector<float> new_vec(k * (size_t)d);
+      for (size_t r = 0; r < k; ++r) std::copy(vectors + (size_t)known[r] * d, vectors + (size_t)(known[r] + 1) * d, new_vec.begin() + r * (size_t)d);
+      {
+        RemoveScratch tmp;
+        int32_t* d_rows = tmp.put(rows.data(), k);
+        float* d_src = tmp.put(new_vec.data(), new_vec.size());
+        if (!d_rows || !d_src) return fail(FREDDY_E_NOMEM, "device allocation failed while updating rows");
+        *wrote = true;
+        hipLaunchKernelGGL(up_scatter_rows_kernel, dim3((unsigned)(((int64_t)k * d + 255) / 256)), dim3(256), 0, ix->stream, reinterpret_cast<const uint32_t*>(d_src),
+                           reinterpret_cast<uint32_t*>(ix->coarse), d_rows, (int64_t)k, d);
+        hipLaunchKernelGGL(up_place_vectors_kernel, dim3((unsigned)k), dim3(256), 0, ix->stream, d_src, d_rows, (int64_t)k, ix->xb, d);
+        *changed = (int64_t)k;
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess) return fail(FREDDY_E_HIP, "rewriting the vector rows failed");
+      }
+      // the exact filter's state over all rows, as a fresh pin computes it (the old values have left the statistics); the fragment
+      // copy: the strips of the updated rows, or every strip when the scale moved or the filter came back
+      std::vector<int32_t> strips;
+      for (int32_t r : rows)
+        if (strips.empty() || strips.back() != r / 32) strips.push_back(r / 32);
+      return exf_table_stats(ix, 0, ix->N, &strips);
+    }
+  }
+  return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+}
+
+extern "C" int freddy_gpu_update_rows(freddy_gpu_index_t* ix, int64_t n, const int32_t* ids, const int32_t* coarse_id, const int16_t* codes,
+                                      const float* vectors, int64_t* updated) {
+  if (n < 0 || (n > 0 && !ids)) return fail(FREDDY_E_ARG, "bad argument: n = %lld ids%s", (long long)n, ids ? "" : ", no ids");
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (updated) *updated = 0;
+  if (n == 0) return FREDDY_OK;
+  // everything that can be refused is refused here, before any device has changed
+  if (n > (int64_t)INT32_MAX) return fail(FREDDY_E_LIMIT, "n = %lld: one call updates at most %d rows (there are no more distinct ids)", (long long)n, INT32_MAX);
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] < 0) return fail(FREDDY_E_ARG, "id %d at position %lld is negative (-1 is the filler of a result list)", ids[i], (long long)i);
+  {
+    std::vector<std::pair<int32_t, int64_t>> by_id((size_t)n);
+    for (int64_t i = 0; i < n; ++i) by_id[(size_t)i] = {ids[i], i};
+    std::sort(by_id.begin(), by_id.end());
+    for (int64_t i = 1; i < n; ++i)
+      if (by_id[(size_t)i].first == by_id[(size_t)i - 1].first)
+        return fail(FREDDY_E_ARG, "id %d is listed twice, at positions %lld and %lld: which payload would win is undefined", by_id[(size_t)i].first,
+                    (long long)by_id[(size_t)i - 1].second, (long long)by_id[(size_t)i].second);
+  }
+  const bool flat = ix->kind == KIND_PQ, ivf = ix->kind == KIND_IVF, ivpq = ix->kind == KIND_IVPQ, vec = ix->kind == KIND_VEC;
+  if (!flat && !ivf && !ivpq && !vec) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (flat && !codes) return fail(FREDDY_E_ARG, "codes are required");
+  if (ivf && (!codes || !coarse_id)) return fail(FREDDY_E_ARG, "coarse_id and codes are required");
+  if (ivpq && (!codes || !coarse_id || (ix->join.has_vectors && !vectors))) return fail(FREDDY_E_ARG, "coarse_id, codes (and vectors, if pinned) are required");
+  if (vec && !vectors) return fail(FREDDY_E_ARG, "vectors are required");
+  if (!vec) {
+    const int m = ivpq ? ix->join.m : ix->m, K = ivpq ? ix->join.K : ix->K, cells = ivpq ? ix->join.cells : ix->C;
+    for (int64_t i = 0; i < n; ++i) {
+      if (!flat && (coarse_id[i] < 0 || coarse_id[i] >= cells))
+        return fail(FREDDY_E_ARG, "coarse_id %d of update row %lld is outside [0, %d)", coarse_id[i], (long long)i, cells);
+      for (int l = 0; l < m; ++l)
+        if (codes[(size_t)i * m + l] < 0 || codes[(size_t)i * m + l] >= K)
+          return fail(FREDDY_E_ARG, "code %d of update row %lld position %d is outside [0, %d)", (int)codes[(size_t)i * m + l], (long long)i, l, K);
+    }
+  }
+  if (!ix->replicas.empty()) {   // the rule of append_rows: the primary first, a failure after the first device has changed poisons the handle
+    std::vector<freddy_gpu_index*> reps;
+    reps.swap(ix->replicas);
+    int64_t changed = 0;
+    int rc = freddy_gpu_update_rows(ix, n, ids, coarse_id, codes, vectors, &changed);
+    reps.swap(ix->replicas);
+    if (rc) return rc;          // (the primary has poisoned itself if it had written anything)
+    for (freddy_gpu_index* r : ix->replicas)
+      if ((rc = freddy_gpu_update_rows(r, n, ids, coarse_id, codes, vectors, nullptr))) { ix->poisoned = true; return rc; }
+    if (updated) *updated = changed;   // (only once every replica has followed)
+    return FREDDY_OK;
+  }
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  int64_t changed = 0;
+  bool wrote = false;
+  const int rc = update_rows_checked(ix, n, ids, coarse_id, codes, vectors, &changed, &wrote);
+  if (rc) {
+    if (wrote) ix->poisoned = true;   // arrays are written in place: a failure after the first write leaves a table that is neither the old nor the new one
+    return rc;
+  }
+  if (updated) *updated = changed;
   return FREDDY_OK;
 }
 

@@ -31,7 +31,7 @@ EXPORTS = [
     "freddy_gpu_last_analogy_stats", "freddy_gpu_exact_join", "freddy_gpu_last_exact_join_stats",
     "freddy_gpu_ivfadc_search_pv", "freddy_gpu_pq_search_pv", "freddy_gpu_last_pv_stats",
     "freddy_gpu_ivfadc_analogy", "freddy_gpu_pq_analogy", "freddy_gpu_last_approx_analogy_stats",
-    "freddy_gpu_exact_assign", "freddy_gpu_pq_assign", "freddy_gpu_remove_rows",
+    "freddy_gpu_exact_assign", "freddy_gpu_pq_assign", "freddy_gpu_remove_rows", "freddy_gpu_update_rows",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 
@@ -153,6 +153,8 @@ def load(path=None, optional=()):
     lib.freddy_gpu_update_codebook.argtypes = [C.c_void_p, C.c_void_p]
     if "freddy_gpu_remove_rows" not in optional:
         lib.freddy_gpu_remove_rows.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    if "freddy_gpu_update_rows" not in optional:
+        lib.freddy_gpu_update_rows.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.freddy_gpu_kmeans.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.freddy_gpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     lib.freddy_gpu_last_track.argtypes = [C.c_void_p, C.c_void_p]
@@ -225,6 +227,25 @@ class _Index:
         _check(self.lib.freddy_gpu_remove_rows(self.h, ids.size, _p(ids), C.byref(gone)))
         self.N -= gone.value   # (grouping() sizes its output arrays by it)
         return int(gone.value)
+
+    def update_rows(self, ids, coarse_id=None, codes=None, vectors=None):
+        """UPDATE of rows of the pinned tables (freddy_gpu_update_rows): every pinned row whose id is ids[i] gets the i-th payload
+        (the arrays append_rows takes for the handle's kind) and keeps its id.  ids in any order, unknown ids are skipped, an id
+        listed twice is refused.  -> the number of rows that changed."""
+        ids = np.asarray(ids)
+        if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
+            raise FreddyGpuError("row ids are 32-bit integers")
+        ids = _i32(ids).reshape(-1)
+        cid = None if coarse_id is None else _i32(coarse_id)
+        cd = None if codes is None else _i16(codes)
+        v = None if vectors is None else _f32(vectors)
+        # the library reads ids.size rows of each array it is given: m codes, d floats (a borrowed handle knows neither: the caller's part)
+        for name, a, per_row in (("coarse_id", cid, 1), ("codes", cd, getattr(self, "m", None)), ("vectors", v, getattr(self, "d", None))):
+            if a is not None and per_row is not None and a.size != ids.size * per_row:
+                raise FreddyGpuError(f"{name} has {a.size} elements, {ids.size} ids need {ids.size * per_row}")
+        changed = C.c_int64(0)
+        _check(self.lib.freddy_gpu_update_rows(self.h, ids.size, _p(ids), _p(cid), _p(cd), _p(v), C.byref(changed)))
+        return int(changed.value)
 
     def update_codebook(self, codebook):
         cb = _f32(codebook)

@@ -382,6 +382,16 @@ class Session:
         self._check(self.lib.delete_rows(self.h, _p(ids), C.c_int64(ids.size), C.byref(gone)))
         return int(gone.value)
 
+    def update_rows(self, ids, vectors):
+        """UPDATE google_vecs_norm SET vector = ... WHERE id = ... with the same ids re-quantised in the code tables; the pinned
+        handles are updated in HBM.  -> rows of google_vecs_norm that changed."""
+        ids, v = _i32(ids).reshape(-1), _f32(vectors)
+        if v.ndim != 2 or v.shape[0] != ids.size:
+            raise ValueError(f"{ids.size} ids need a [{ids.size}, d] array of vectors, not {v.shape}")
+        changed = C.c_int64(0)
+        self._check(self.lib.update_rows(self.h, _p(ids), _p(v), C.c_int64(ids.size), v.shape[1], C.byref(changed)))
+        return int(changed.value)
+
     def insert_batch(self, norm_vectors):
         """freddy.c:1403-1658 for the normalised vectors of NEW terms; returns the ids given in google_vecs_norm."""
         v = _f32(norm_vectors)

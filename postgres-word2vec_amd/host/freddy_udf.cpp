@@ -1018,6 +1018,73 @@ int delete_rows(freddy_session_t* s, const int32_t* ids, int64_t n, int64_t* rem
   return 0;
 }
 
+// ---- update_rows: UPDATE google_vecs_norm SET vector = ... WHERE id = ..., and the same ids re-quantised in the three code tables ----
+int update_rows(freddy_session_t* s, const int32_t* ids, const float* norm_vectors, int64_t n, int32_t dim, int64_t* updated) {
+  if (!s || n < 0 || (n > 0 && (!ids || !norm_vectors))) return fail(-1, "bad argument");
+  if (updated) *updated = 0;
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] < 0) return fail(-1, "id %d at position %lld is negative", ids[i], (long long)i);
+  {
+    const std::vector<int64_t> ord = order_by_id(ids, n);
+    for (int64_t i = 1; i < n; ++i)
+      if (ids[ord[(size_t)i]] == ids[ord[(size_t)i - 1]])
+        return fail(-1, "id %d is listed twice, at positions %lld and %lld", ids[ord[(size_t)i]], (long long)ord[(size_t)i - 1], (long long)ord[(size_t)i]);
+  }
+  if (n == 0) return 0;
+  if (n > INT32_MAX) return fail(-1, "too many rows in one call");
+  for (int have : {s->d, s->pq ? s->pq_d : 0, s->ivf ? s->ivf_d : 0, s->ivpq ? s->ivpq_d : 0})
+    if (have && dim != have) return fail(-1, "vectors have %d dimensions, the tables %d", dim, have);
+  // the codes and cells of the new vectors against the codebooks as they are (a table that is not loaded is skipped)
+  std::vector<int16_t> pq_codes, res_codes, iv_codes, multi;
+  std::vector<int32_t> cq, cq_multi_id;
+  if (s->pq || s->ivf || s->ivpq) {
+    freddy_insert_desc desc = {dim, 0, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, nullptr};
+    if (s->pq) { desc.pq_m = s->pq_cb.m; desc.pq_K = s->pq_cb.K; desc.pq_codebook = s->pq_cb.dense.data(); pq_codes.resize((size_t)n * s->pq_cb.m); }
+    if (s->ivf) {
+      desc.res_m = s->res_cb.m; desc.res_K = s->res_cb.K; desc.residual_codebook = s->res_cb.dense.data(); desc.C = s->C; desc.coarse = s->coarse.data();
+      res_codes.resize((size_t)n * s->res_cb.m); cq.resize((size_t)n);
+    }
+    if (s->ivpq) {
+      desc.ivpq_m = s->ivpq_cb.m; desc.ivpq_K = s->ivpq_cb.K; desc.ivpq_codebook = s->ivpq_cb.dense.data();
+      desc.multi_positions = s->cq_multi.m; desc.multi_codes = s->cq_multi.K; desc.coarse_multi = s->cq_multi.dense.data();
+      iv_codes.resize((size_t)n * s->ivpq_cb.m); multi.resize((size_t)n * s->cq_multi.m);
+    }
+    if (int rc = freddy_gpu_insert_quantize(&desc, s->device, norm_vectors, n, s->pq ? pq_codes.data() : nullptr, s->ivf ? cq.data() : nullptr,
+                                            s->ivf ? res_codes.data() : nullptr, s->ivpq ? iv_codes.data() : nullptr, s->ivpq ? multi.data() : nullptr))
+      return gpu_fail(rc);
+    if (s->ivpq) {   // multi-index cell: insert_batch's formula (factor *= POSITIONS, freddy.c:1599)
+      cq_multi_id.assign((size_t)n, 0);
+      for (int64_t i = 0; i < n; ++i) {
+        int factor = 1;
+        for (int p = 0; p < s->cq_multi.m; ++p) { cq_multi_id[(size_t)i] += factor * multi[(size_t)i * s->cq_multi.m + p]; factor *= s->cq_multi.m; }
+      }
+    }
+  }
+  auto device_side = [&]() -> int {
+    if (s->pq) if (int rc = freddy_gpu_update_rows(s->pq, n, ids, nullptr, pq_codes.data(), nullptr, nullptr)) return rc;
+    if (s->ivf) if (int rc = freddy_gpu_update_rows(s->ivf, n, ids, cq.data(), res_codes.data(), nullptr, nullptr)) return rc;
+    if (s->ivpq) if (int rc = freddy_gpu_update_rows(s->ivpq, n, ids, cq_multi_id.data(), iv_codes.data(), norm_vectors, nullptr)) return rc;
+    if (s->vecs) if (int rc = freddy_gpu_update_rows(s->vecs, n, ids, nullptr, nullptr, norm_vectors, nullptr)) return rc;
+    return 0;
+  };
+  if (int rc = device_side()) {
+    const int code = gpu_fail(rc);     // (the message first: unpinning below may overwrite the library's)
+    // the handles may hold part of the update: drop them, the host tables of the session are unchanged
+    freddy_gpu_index_t** handles[] = {&s->pq, &s->ivf, &s->ivpq, &s->vecs};
+    for (freddy_gpu_index_t** h : handles) if (*h) { freddy_gpu_unpin(*h); *h = nullptr; }
+    return code;
+  }
+  int64_t changed = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    auto it = std::lower_bound(s->norm_ids.begin(), s->norm_ids.end(), ids[i]);
+    if (it == s->norm_ids.end() || *it != ids[i]) continue;
+    memcpy(&s->norm_vecs[(size_t)(it - s->norm_ids.begin()) * s->d], norm_vectors + (size_t)i * dim, sizeof(float) * (size_t)dim);
+    ++changed;
+  }
+  if (updated) *updated = changed;
+  return 0;
+}
+
 // ---- analogy_3cosadd_in_pq / analogy_3cosadd_in_ivpq      freddy--0.0.1.sql:1348-1426 --------------------
 static int analogy_in_common(freddy_session_t* s, bool ivpq, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids,
                              int32_t n_ids, int32_t* result) {
