@@ -1,10 +1,13 @@
 """-m gpu: randomised soak of the IVFADC scans against the oracle with a FIXED seed budget (the long version
 is tools/soak_fused.py): random shapes -- K from 4 to 1024, 1 to 40 cells incl. empty ones, 50 to 30 000
 rows, 1 to 5000 distinct code rows (i.e. from "every distance equal" to "all different"), 1 to 700 queries
--- both cell-grouped scans and the generic kernels, both found rules."""
+-- both cell-grouped scans and the generic kernels, both found rules.  Below them the fixed-seed forms of tools/soak_shapes.py,
+tools/soak_bigk.py and the kNN-join part of tools/soak_round3.py: the draws are tests/soak_inputs.py's, which those tools loop over
+too, and tests/test_soak_inputs_cpu.py proves which regimes the seed lists reach."""
 import numpy as np
 import pytest
 
+import soak_inputs as si
 import util
 
 pytestmark = pytest.mark.gpu
@@ -89,3 +92,72 @@ def test_soak_random_pq_table(gpu, oracle, seed):
             util.assert_same_lists(gi, gd, exp, f"seed={seed} subset K={K} N={N} Q={Q} pq_fused={mode}")
     assert idx.bound_violations() == 0
     idx.close()
+
+
+def run_shapes(gpu, d):
+    """index shapes other than m = 12 / S = 25: multi.h's cell-grouped exact scan, the generic kernels, filter + refine with and
+    without the running bound"""
+    idx = gpu.IVFIndex(*d["pin"])
+    for c in d["calls"]:
+        for fused, rb in si.SHAPES_CONFIGS:
+            idx.set_option("fused", fused)
+            idx.set_option("running_bound", rb)
+            gi, gd = idx.search(d["qs"], c["k"], c["W"], sentinel=c["sentinel"], found_rule=c["rule"])
+            util.assert_same_lists(gi, gd, c["exp"], f"{d['label']} @ W={c['W']} k={c['k']} rule={c['rule']} fused={fused} rb={rb}")
+    assert idx.bound_violations() == 0, d["label"]
+    idx.close()
+
+
+def run_bigk(gpu, d):
+    """lists of 513 .. 4096 entries (bigk.h) from ivfadc_search, pq_search and pq_search_in, and the kNN-join's post verification
+    of 1025 .. 8192 candidates, on tables with runs of equal distances"""
+    idx = gpu.IVFIndex(*d["ivf_pin"])
+    for c in d["ivf_calls"]:
+        gi, gd = idx.search(d["qs"], c["k"], c["W"], sentinel=c["sentinel"], found_rule=c["rule"])
+        util.assert_same_lists(gi, gd, c["exp"], f"{d['label']} @ ivfadc k={c['k']} W={c['W']} rule={c['rule']} sent={c['sentinel']}")
+    assert idx.bound_violations() == 0, d["label"]
+    idx.close()
+    pidx = gpu.PQIndex(*d["pq_pin"])
+    gi, gd = pidx.search(d["qs"], d["pq_k"], sentinel=100.0)
+    util.assert_same_lists(gi, gd, d["pq_exp"], f"{d['label']} @ pq_search")
+    gi, gd = pidx.search(d["qs"], d["pq_k"], sentinel=1000.0, subset_ids=d["pq_targets"])
+    util.assert_same_lists(gi, gd, d["pq_in_exp"], f"{d['label']} @ pq_search_in")
+    assert pidx.bound_violations() == 0, d["label"]
+    pidx.close()
+    if d["join"]:
+        j = d["join"]
+        jidx = gpu.IVPQIndex(*j["pin"])
+        for c in j["calls"]:
+            gi, gd, git = jidx.knn_join(j["qs"], c["k"], j["targets"], c["alpha"], c["pvf"], 2, use_target_lists=c["tl"], confidence=0.8)
+            what = f"{d['label']} @ join k={c['k']} pvf={c['pvf']} alpha={c['alpha']} tl={c['tl']}"
+            assert git == c["iterations"], (what, git, c["iterations"])
+            util.assert_same_lists(gi, gd, c["exp"], what)
+        jidx.close()
+
+
+def run_join(gpu, d):
+    """the kNN-join with the traversal on the device and on the host heap"""
+    jdx = gpu.IVPQIndex(*d["pin"])
+    for c in d["calls"]:
+        for host in (0, 1):
+            jdx.set_option("join_host_traversal", host)
+            gi, gd, git = jdx.knn_join(d["qs"], c["k"], d["targets"], c["alpha"], c["pvf"], c["method"], use_target_lists=c["tl"], confidence=c["confidence"])
+            what = f"{d['label']} @ k={c['k']} alpha={c['alpha']} pvf={c['pvf']} method={c['method']} conf={c['confidence']} tl={c['tl']} host={host}"
+            assert git == c["iterations"], (what, git, c["iterations"])
+            util.assert_same_lists(gi, gd, c["exp"], what)
+    jdx.close()
+
+
+@pytest.mark.parametrize("seed", si.SEEDS["shapes"])
+def test_soak_shapes(gpu, oracle, seed):
+    run_shapes(gpu, si.draw_shapes(seed, oracle))
+
+
+@pytest.mark.parametrize("seed", si.SEEDS["bigk"])
+def test_soak_bigk(gpu, oracle, seed):
+    run_bigk(gpu, si.draw_bigk(seed, oracle))
+
+
+@pytest.mark.parametrize("seed", si.SEEDS["join"])
+def test_soak_join(gpu, oracle, seed):
+    run_join(gpu, si.draw_join(seed, oracle))

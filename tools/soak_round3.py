@@ -2,7 +2,8 @@
   * the host-buffer pipeline of freddy_gpu_ivfadc_search (random batch sizes, sub-batch sizes, lanes, W, k, found rules,
     tiny cells that force extra probing rounds, pinned and pageable query buffers, single queries, replicated handles);
   * the kNN-join with the traversal on the device (random multi-index sizes incl. duplicate centroids, targets, k, alpha,
-    pvf, methods, confidences, target lists on / off; every call also with the host heap);
+    pvf, methods, confidences, target lists on / off; every call also with the host heap) -- the draws are
+    tests/soak_inputs.py's, of which the suite runs the first len(soak_inputs.SEEDS["join"]) seeds (tests/test_gpu_soak.py);
   * single-query pq_search through the pinned direct I/O;
   * the item-wise scan of thin cells forced on / off, the combined coarse + table launch on / off.
 usage: python tools/soak_round3.py [seeds]"""
@@ -13,6 +14,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "postgres-word2vec_amd"), os.path.join(
 import torch  # noqa: F401
 from freddy_amd import gpu, index_build as ib
 from oracle.oracle import Oracle
+import soak_inputs as si
+import test_gpu_soak as ts
 import util
 
 oracle = Oracle()
@@ -47,30 +50,10 @@ for seed in range(seeds):
         n_ivf += 1
     assert idx.bound_violations() == 0
     idx.close()
-    # ---- kNN-join
-    Nj = int(rng.choice([3000, 20000]))
-    kc = int(rng.choice([4, 8, 32]))
-    xj = ib.make_corpus(Nj, seed=200 + seed, n_clusters=40, dup_frac=0.02, device="cpu")
-    tj = dict(ib.build_ivpq_index(xj, m=30, K=32, k_coarse=kc, train_size=min(Nj, 3000), iters=3, seed=seed))
-    if seed % 4 == 1:   # duplicate multi-index centroids: equal keys among the nearest cells
-        co = tj["coarse"].copy(); co[0, 1] = co[0, 0]; co[1, kc - 1] = co[1, 0]; tj["coarse"] = co
-    otj = oracle.ivpq_table(tj["codebook"], tj["coarse"], tj["ids"], tj["coarse_id"], tj["codes"], tj["vectors"], tj["stats"])
-    jdx = gpu.IVPQIndex(tj["codebook"], tj["coarse"], tj["ids"], tj["coarse_id"], tj["codes"], tj["vectors"], tj["stats"])
-    Qj = int(rng.choice([1, 40, 300]))
-    qj = xj.numpy()[rng.integers(0, Nj, size=Qj)].astype(np.float32)
-    T = int(rng.choice([5, 200, Nj // 4]))
-    targets = rng.choice(np.arange(1, Nj + 1), size=T, replace=False).astype(np.int32)
-    for _ in range(3):
-        k = int(rng.choice([1, 5, 12])); alpha = int(rng.choice([1, 3, 50, 1000])); pvf = int(rng.choice([1, 4, 20]))
-        method = int(rng.choice([0, 1, 2])); conf = float(rng.choice([0.05, 0.5, 0.8, 0.99])); tl = bool(rng.integers(0, 2))
-        exp, eit = oracle.ivpq_search_in(otj, qj, k, targets, alpha, pvf, method, use_target_lists=tl, confidence=conf)
-        for host in (0, 1):
-            jdx.set_option("join_host_traversal", host)
-            gi, gd, git = jdx.knn_join(qj, k, targets, alpha, pvf, method, use_target_lists=tl, confidence=conf)
-            assert git == eit, (seed, git, eit)
-            util.assert_same_lists(gi, gd, exp, f"seed={seed} join kc={kc} Q={Qj} T={T} k={k} alpha={alpha} pvf={pvf} method={method} conf={conf} tl={tl} host={host}")
-            n_join += 1
-    jdx.close()
+    # ---- kNN-join: the draws of tests/soak_inputs.py (draw_join), compared as tests/test_gpu_soak.py does (run_join)
+    dj = si.draw_join(seed, oracle)
+    ts.run_join(gpu, dj)
+    n_join += 2 * len(dj["calls"])
     # ---- single-query / small-batch pq_search through the pinned direct I/O
     Np = int(rng.choice([60, 4097, 30000]))
     Kp = int(rng.choice([16, 256, 1024]))
