@@ -418,6 +418,44 @@ int freddy_gpu_update_rows(freddy_gpu_index_t* index, int64_t n, const int32_t* 
  * re-derive everything on the device that depends on it. */
 int freddy_gpu_update_codebook(freddy_gpu_index_t* index, const float* codebook /*[m][K][d/m]*/);
 
+/* ---- the statistics row of a pinned ivpq handle (freddy_ivpq_desc::stats, [cells + 1] floats) ----------------------------
+ * In the reference the statistics are a setting, not part of the index: getStatistics (index_utils.c:632-665) reads the table
+ * set_statistics_table (freddy--0.0.1.sql:70) names on every ivpq_search_in call, and create_statistics(table, column,
+ * coarse_table) (:150-171) builds such a table for any column of tokens.  The row decides how many cells a query of the
+ * kNN-join probes for a given confidence.  append_rows / remove_rows / update_rows / update_codebook leave it alone, and
+ * nothing here is ever installed implicitly: the caller decides when the row follows its table.
+ * All three calls take an ivpq handle: a NULL handle is FREDDY_E_ARG, a handle of another kind FREDDY_E_KIND, and argument
+ * errors are reported before any device work.  Like the mutation calls they synchronise the handle's own stream first and
+ * must NOT run beside searches the caller has in flight on other streams.
+ *
+ * set_statistics: the device side of set_statistics_table.  n_stats must be cells + 1 (else FREDDY_E_ARG; the message names
+ * both numbers); the values are accepted whatever they are, as a fresh pin accepts them.  The device copy of the row is
+ * overwritten in place and only then the host copy, so the two never disagree after a failure.  Afterwards
+ * freddy_gpu_knn_join answers bit for bit as a fresh pin of the same tables with that row (lists, iterations_out, the cells
+ * each query took).  freddy_gpu_index_bytes does not move, and the target list cached from the previous join stays valid (it
+ * does not depend on the statistics).
+ *
+ * get_statistics: the row the DEVICE holds, copied into out[n_stats]; n_stats must be cells + 1.
+ *
+ * create_statistics: create_statistics() over the pinned rows.  ids[0..n) is the multiset of row ids of the column's tokens
+ * (the host resolves words to ids as for every other call); ids == NULL with n == 0 means every pinned row once, the default
+ * stat_google_vecs_norm_word.  An id that no pinned row has is skipped; an id listed r times counts r times (the SQL is an
+ * INNER JOIN with the column, not IN).  With count[c] = entries whose row lies in cell c and total = entries that have a row:
+ *     stats[c]     = (float)((double)count[c] / (double)total)   for c < cells  ("count(*)::float / total_amount": float8, stored float4)
+ *     stats[cells] = (float)total                                               (bigint -> float4, round to nearest even)
+ * Counts are 64-bit integers on the device: a count above 2^24 is not rounded before the division and n above 2^31 does not
+ * wrap.  The reference takes total over the VECTOR table, not the ivpq table; the two are equal whenever the ivpq table covers
+ * the vector table, which index creation guarantees.
+ * out_stats ([cells + 1], may be NULL) receives the row, *matched (may be NULL) the total.  install != 0 makes the row the
+ * handle's row exactly as set_statistics would (a device-to-device copy; the host copy is filled from the floats that come
+ * back).  total == 0 is the SQL's division by zero: FREDDY_E_ARG, nothing is installed and nothing is written.  ids == NULL
+ * with n > 0, and n < 0, are FREDDY_E_ARG.  Any n is accepted: the ids are staged in passes, and only the row and the total
+ * leave the device. */
+int freddy_gpu_set_statistics(freddy_gpu_index_t* ivpq, const float* stats, int32_t n_stats);
+int freddy_gpu_get_statistics(const freddy_gpu_index_t* ivpq, float* out, int32_t n_stats);
+int freddy_gpu_create_statistics(freddy_gpu_index_t* ivpq, const int32_t* ids, int64_t n, int32_t install,
+                                 float* out_stats /*[cells+1], may be NULL*/, int64_t* matched /* may be NULL */);
+
 /* ---- device-resident variant used for throughput measurement ----------------------------
  * Same as freddy_gpu_ivfadc_search, but queries / outputs are DEVICE pointers on the
  * index's device and all work is enqueued on `hip_stream` (a hipStream_t; NULL = the

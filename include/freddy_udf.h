@@ -298,6 +298,18 @@ int delete_rows(freddy_session_t* s, const int32_t* ids, int64_t n, int64_t* rem
  * before anything changes.  *updated (may be NULL) receives the number of rows of google_vecs_norm that changed.  A device
  * failure drops the handles and leaves the host tables as they were, as in insert_batch. */
 int update_rows(freddy_session_t* s, const int32_t* ids, const float* norm_vectors, int64_t n, int32_t dim, int64_t* updated);
+/* set_statistics_table(regclass) (freddy--0.0.1.sql:70) for the loaded ivpq tables: the (coarse_id, coarse_freq) rows of a stat
+ * table, in the row form and under the checks of freddy_load_ivpq (cells + 1 rows, every coarse_id in [0, cells]), become the
+ * statistics row of the pinned handle (freddy_gpu_set_statistics) -- the handle is not pinned again.
+ * create_statistics(table, column, coarse_table) (:150-171) over the pinned rows: token_ids[0..n) are the row ids of the
+ * column's tokens with their multiplicity (ids no row has are skipped); token_ids == NULL with n == 0 is every row once, the
+ * default stat_google_vecs_norm_word.  The row is computed on the device, installed as the bootstrap block installs it
+ * (:183-184) and copied to out_stats ([cells + 1], may be NULL).  A column none of whose tokens has a row is the SQL's division
+ * by zero: an error, and the row in force stays.  freddy_statistics_rows: cells + 1 of the loaded ivpq tables (what n_stat
+ * must be and out_stats must hold), 0 while they are not loaded. */
+int32_t freddy_statistics_rows(const freddy_session_t* s);
+int freddy_set_statistics_table(freddy_session_t* s, const int32_t* stat_coarse_id, const float* stat_freq, int32_t n_stat);
+int create_statistics(freddy_session_t* s, const int32_t* token_ids, int64_t n, float* out_stats /* may be NULL */);
 
 /* per-call row emit: snprintf("%d") / snprintf("%f") into 16-byte buffers   freddy.c:154-169,1001-1023 */
 void freddy_emit_row2(const freddy_row2* row, char values[2][16]);

@@ -1,9 +1,11 @@
 // join.hip -- pin_ivpq and knn_join (ivpq_search_in.c:61-699): the entry points.  join.h says which header holds what; the
-// call itself is join_run() in join_run.h.
+// call itself is join_run() in join_run.h.  Behind them the statistics row of a pinned handle: set_statistics / get_statistics /
+// create_statistics (kernels in stat_kernels.h).
 #include "internal.h"
 
 #include "join.h"
 #include "join_run.h"
+#include "stat_kernels.h"
 
 // the ivpq tables in the layouts the kernels read (checked first: ascending ids, cells and codes in range)
 static int join_pin(JoinIndex* j, const freddy_ivpq_desc* t, int64_t* bytes) {
@@ -80,6 +82,121 @@ extern "C" int freddy_gpu_knn_join(freddy_gpu_index_t* ix, const float* queries,
   int rc = join_run(&ix->join, ix->stream, queries, Q, k, target_ids, n_targets, alpha, pvf, method,
                     use_target_lists, confidence, double_threshold, out_ids, out_dist, iterations_out);
   if (rc) return fail(rc, "%s", join_error());
+  return FREDDY_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// the statistics row of a pinned handle: set_statistics_table and create_statistics of the reference
+// ---------------------------------------------------------------------------------------
+// ids per pass of create_statistics: 16 MiB of pinned staging per half.  (freddy_amd/gpu.py keeps a copy, STAT_PASS, from which the
+// tests build a list of one pass + 1 ids: change both together.)
+static constexpr int64_t STAT_PASS = 1 << 22;
+static constexpr int64_t STAT_ROWS_PASS = 1 << 30;   // rows per launch when every pinned row counts once (nothing is staged)
+
+static int stat_handle(const freddy_gpu_index* ix) {
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (ix->kind != KIND_IVPQ) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  return 0;
+}
+
+// d_stats first, h_stats only once the device holds the row: the two copies never disagree after a failure
+static int stat_install(freddy_gpu_index* ix, const float* src, hipMemcpyKind kind, const float* host_row) {
+  JoinIndex& j = ix->join;
+  const size_t n = (size_t)j.cells + 1;
+  HIP_TRY(hipMemcpyAsync(j.d_stats, src, sizeof(float) * n, kind, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  j.h_stats.assign(host_row, host_row + n);
+  return 0;
+}
+
+extern "C" int freddy_gpu_set_statistics(freddy_gpu_index_t* ix, const float* stats, int32_t n_stats) {
+  if (int rc = stat_handle(ix)) return rc;
+  if (n_stats != ix->join.cells + 1)
+    return fail(FREDDY_E_ARG, "n_stats = %d: the statistics row of this index has cells + 1 = %d entries", n_stats, ix->join.cells + 1);
+  if (!stats) return fail(FREDDY_E_ARG, "NULL statistics");
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  return stat_install(ix, stats, hipMemcpyHostToDevice, stats);
+}
+
+extern "C" int freddy_gpu_get_statistics(const freddy_gpu_index_t* ix, float* out, int32_t n_stats) {
+  if (int rc = stat_handle(ix)) return rc;
+  if (n_stats != ix->join.cells + 1)
+    return fail(FREDDY_E_ARG, "n_stats = %d: the statistics row of this index has cells + 1 = %d entries", n_stats, ix->join.cells + 1);
+  if (!out) return fail(FREDDY_E_ARG, "NULL buffer");
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipMemcpyAsync(out, ix->join.d_stats, sizeof(float) * (size_t)n_stats, hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  return FREDDY_OK;
+}
+
+// one launch of the count kernel over n entries: ids staged in mapped host memory (d_tids), or the rows [row0, row0 + n)
+static int stat_count(freddy_gpu_index* ix, const int32_t* d_tids, int64_t n, int64_t row0, unsigned long long* d_count) {
+  const JoinIndex& j = ix->join;
+  const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>((n + STAT_WG * STAT_PER_LANE - 1) / (STAT_WG * STAT_PER_LANE), 1), STAT_MAX_GRID);
+  if (j.cells <= STAT_LDS_CELLS)
+    hipLaunchKernelGGL(stat_count_kernel<true>, dim3(grid), dim3(STAT_WG), sizeof(uint32_t) * (size_t)j.cells, ix->stream, d_tids, n, row0,
+                       (const int32_t*)j.ids, j.N, j.ids_affine ? 1 : 0, (const int32_t*)j.cell, j.cells, d_count);
+  else
+    hipLaunchKernelGGL(stat_count_kernel<false>, dim3(grid), dim3(STAT_WG), 0, ix->stream, d_tids, n, row0, (const int32_t*)j.ids, j.N,
+                       j.ids_affine ? 1 : 0, (const int32_t*)j.cell, j.cells, d_count);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int freddy_gpu_create_statistics(freddy_gpu_index_t* ix, const int32_t* ids, int64_t n, int32_t install, float* out_stats,
+                                            int64_t* matched) {
+  if (int rc = stat_handle(ix)) return rc;
+  if (n < 0 || (n > 0 && !ids)) return fail(FREDDY_E_ARG, "bad argument: n = %lld ids%s", (long long)n, ids ? "" : ", no ids");
+  if (ids && n == 0) return fail(FREDDY_E_ARG, "an empty list of ids has no row: the total is 0 (the reference divides by it)");
+  JoinIndex& j = ix->join;
+  if (j.N == 0) return fail(FREDDY_E_ARG, "no row is pinned: the total is 0 (the reference divides by it)");
+  const int cells = j.cells;
+  const size_t row_n = (size_t)cells + 1;
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  // device: the counts, then the row; pinned: the total, the row, then (ids given) one or two halves of a pass
+  unsigned long long* d_count = nullptr;
+  // (one block of u64: cells counts, then the row's cells + 1 floats, which fill ceil((cells + 1) / 2) <= row_n / 2 + 1 of them)
+  if (join_buf(&j, JW_STAT, (size_t)cells + row_n / 2 + 1, &d_count)) return fail(FREDDY_E_NOMEM, "%s", join_error());
+  float* d_row = reinterpret_cast<float*>(d_count + cells);
+  const size_t head = (sizeof(unsigned long long) + sizeof(float) * row_n + 255) & ~(size_t)255;
+  const int64_t pass = ids ? std::min(n, STAT_PASS) : 0;
+  const int halves = n > pass ? 2 : 1;
+  if (j.h_stat.ensure(head + sizeof(int32_t) * (size_t)pass * halves)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+  for (int h = 0; h < halves; ++h)
+    if (ids && !j.ev_stat[h]) HIP_TRY(hipEventCreateWithFlags(&j.ev_stat[h], hipEventDisableTiming));
+  void* p_dev = nullptr;
+  HIP_TRY(hipHostGetDevicePointer(&p_dev, j.h_stat.p, 0));
+  char* const h_base = j.h_stat.as<char>();
+  char* const d_base = static_cast<char*>(p_dev);
+  HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long) * (size_t)cells, ix->stream));
+  if (!ids) {
+    for (int64_t r0 = 0; r0 < j.N; r0 += STAT_ROWS_PASS)
+      if (int rc = stat_count(ix, nullptr, std::min(STAT_ROWS_PASS, j.N - r0), r0, d_count)) return rc;
+  } else {
+    int64_t p = 0;
+    for (int64_t a = 0; a < n; a += pass, ++p) {   // the host fills one half while the kernel of the pass before reads the other
+      const int h = (int)(p & 1);
+      const int64_t len = std::min(pass, n - a);
+      if (p >= 2) HIP_TRY(hipEventSynchronize(j.ev_stat[h]));
+      const size_t off = head + sizeof(int32_t) * (size_t)pass * h;
+      memcpy(h_base + off, ids + a, sizeof(int32_t) * (size_t)len);
+      if (int rc = stat_count(ix, reinterpret_cast<const int32_t*>(d_base + off), len, 0, d_count)) return rc;
+      HIP_TRY(hipEventRecord(j.ev_stat[h], ix->stream));
+    }
+  }
+  hipLaunchKernelGGL(stat_finish_kernel, dim3(1), dim3(STAT_WG), 0, ix->stream, (const unsigned long long*)d_count, cells, d_row,
+                     reinterpret_cast<float*>(d_base + sizeof(unsigned long long)), reinterpret_cast<unsigned long long*>(d_base));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  const unsigned long long total = *reinterpret_cast<const unsigned long long*>(h_base);
+  const float* h_row = reinterpret_cast<const float*>(h_base + sizeof(unsigned long long));
+  if (total == 0) return fail(FREDDY_E_ARG, "none of the %lld ids has a pinned row: the total is 0 (the reference divides by it)", (long long)n);
+  if (install)
+    if (int rc = stat_install(ix, d_row, hipMemcpyDeviceToDevice, h_row)) return rc;
+  if (out_stats) memcpy(out_stats, h_row, sizeof(float) * row_n);
+  if (matched) *matched = (int64_t)total;
   return FREDDY_OK;
 }
 

@@ -63,6 +63,7 @@ enum JoinSlot {
   JW_QCELL_CNT,    // int32 [Q]           device traversal: how many
   JW_BIG_KEYS,     // u64   [n_scan][L]   BIG: the candidates (post verification's, or the 2k keys of methods 0 / 1) ...
   JW_BIG_EXACT,    // float [n_scan][L]   ... and, for post verification, their exact distances
+  JW_STAT,         // u64 [cells] + float [cells + 1]   create_statistics: the counts per cell, then the row they give
   JW_SLOTS
 };
 
@@ -91,6 +92,10 @@ struct JoinIndex {
   // (kept in ONE pinned block: [cells + 1] bucket offsets, written by the offsets kernel, then the target array, which the mark
   // kernel reads over PCIe -- no SDMA copy in either direction, and the copy the next call is compared with is the staging copy)
   PinnedBuf h_tl;
+  // create_statistics: [cells + 1] floats and the exact total as the finish kernel writes them, then two halves of a pass of
+  // ids each (the count kernel reads a half over PCIe while the host fills the other); an event per half
+  PinnedBuf h_stat;
+  hipEvent_t ev_stat[2] = {nullptr, nullptr};
   int64_t tl_n = -1;
   int tl_cells = -1;
   bool tl_valid = false;
@@ -122,11 +127,12 @@ static inline int join_buf(JoinIndex* j, JoinSlot slot, size_t count, T** out) {
 static inline void join_free(JoinIndex* j) {
   void* ptrs[] = {j->cbT, j->coarseT, j->ids, j->codes, j->vectors, j->cell, j->markbits, j->d_stats};
   for (void* p : ptrs) if (p) (void)hipFree(p);
-  for (PinnedBuf* b : {&j->h_q, &j->h_sum, &j->h_tl}) b->release();
+  for (PinnedBuf* b : {&j->h_q, &j->h_sum, &j->h_tl, &j->h_stat}) b->release();
   for (int i = 0; i < JW_SLOTS; ++i) if (j->w[i]) (void)hipFree(j->w[i]);
   if (j->ev0) (void)hipEventDestroy(j->ev0);
   if (j->ev1) (void)hipEventDestroy(j->ev1);
   if (j->ev_replay) (void)hipEventDestroy(j->ev_replay);
+  for (hipEvent_t e : j->ev_stat) if (e) (void)hipEventDestroy(e);
   *j = JoinIndex();
 }
 

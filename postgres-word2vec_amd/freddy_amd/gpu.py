@@ -32,8 +32,10 @@ EXPORTS = [
     "freddy_gpu_ivfadc_search_pv", "freddy_gpu_pq_search_pv", "freddy_gpu_last_pv_stats",
     "freddy_gpu_ivfadc_analogy", "freddy_gpu_pq_analogy", "freddy_gpu_last_approx_analogy_stats",
     "freddy_gpu_exact_assign", "freddy_gpu_pq_assign", "freddy_gpu_remove_rows", "freddy_gpu_update_rows",
+    "freddy_gpu_set_statistics", "freddy_gpu_get_statistics", "freddy_gpu_create_statistics",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
+STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together): ids per pass of freddy_gpu_create_statistics
 
 
 class FreddyGpuError(RuntimeError):
@@ -155,6 +157,11 @@ def load(path=None, optional=()):
         lib.freddy_gpu_remove_rows.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     if "freddy_gpu_update_rows" not in optional:
         lib.freddy_gpu_update_rows.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name, types in (("freddy_gpu_set_statistics", [C.c_void_p, C.c_void_p, C.c_int32]),
+                        ("freddy_gpu_get_statistics", [C.c_void_p, C.c_void_p, C.c_int32]),
+                        ("freddy_gpu_create_statistics", [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p])):
+        if name not in optional:
+            getattr(lib, name).argtypes = types
     lib.freddy_gpu_kmeans.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.freddy_gpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     lib.freddy_gpu_last_track.argtypes = [C.c_void_p, C.c_void_p]
@@ -563,6 +570,7 @@ class IVPQIndex(_Index):
         m, K, s = cb.shape
         cpos, ccodes, _ = cq.shape
         self.d, self.m, self.K, self.N = m * s, m, K, ids.size
+        self.cells = ccodes * ccodes
         desc = IVPQDesc(self.d, m, K, cpos, ccodes, ids.size, _p(cb), _p(cq), _p(ids), _p(cid), _p(codes),
                         _p(vec), _p(st))
         _check(self.lib.freddy_gpu_pin_ivpq(C.byref(desc), device, C.byref(self.h)))
@@ -579,6 +587,35 @@ class IVPQIndex(_Index):
                                             1 if use_target_lists else 0, C.c_float(confidence),
                                             double_threshold, _p(out_i), _p(out_d), C.byref(iters)))
         return out_i, out_d, iters.value
+
+    def set_statistics(self, stats):
+        """set_statistics_table for the pinned handle (freddy_gpu_set_statistics): `stats` ([cells + 1] floats) becomes the row the
+        kNN-join reads, on the device and on the host; nothing else of the handle changes."""
+        st = _f32(stats).reshape(-1)
+        _check(self.lib.freddy_gpu_set_statistics(self.h, _p(st), st.size))
+
+    def statistics(self):
+        """The statistics row the device holds (freddy_gpu_get_statistics): [cells + 1] floats."""
+        out = np.empty(self.cells + 1, np.float32)
+        _check(self.lib.freddy_gpu_get_statistics(self.h, _p(out), out.size))
+        return out
+
+    def create_statistics(self, ids=None, install=False):
+        """create_statistics() over the pinned rows (freddy_gpu_create_statistics): ids = the row ids of a column's tokens, with
+        their multiplicity (unknown ids are skipped); None = every pinned row once.  install=True makes the row the handle's row.
+        -> (stats [cells + 1], matched = the entries that have a row)."""
+        if ids is not None:
+            ids = np.asarray(ids)
+            if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
+                raise FreddyGpuError("row ids are 32-bit integers")
+            ids = _i32(ids).reshape(-1)
+        n = 0 if ids is None else ids.size
+        # (an empty LIST is not "every row": the library gets a pointer that is not NULL with n = 0 and refuses it)
+        ptr = None if ids is None else _p(ids if n else np.zeros(1, np.int32))
+        out = np.empty(self.cells + 1, np.float32)
+        matched = C.c_int64(0)
+        _check(self.lib.freddy_gpu_create_statistics(self.h, ptr, C.c_int64(n), 1 if install else 0, _p(out), C.byref(matched)))
+        return out, int(matched.value)
 
     def last_track(self):
         """{stage name: seconds} of the most recent knn_join call (the reference's TRACK lines)."""

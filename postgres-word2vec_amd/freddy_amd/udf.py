@@ -392,6 +392,27 @@ class Session:
         self._check(self.lib.update_rows(self.h, _p(ids), _p(v), C.c_int64(ids.size), v.shape[1], C.byref(changed)))
         return int(changed.value)
 
+    def set_statistics_table(self, stats):
+        """set_statistics_table: stats[cells + 1] as the rows (coarse_id = position, coarse_freq) of a stat table; the pinned ivpq
+        handle takes the row in HBM and is not pinned again."""
+        st = _f32(stats).reshape(-1)
+        sid = _i32(np.arange(st.size))
+        self._check(self.lib.freddy_set_statistics_table(self.h, _p(sid), _p(st), st.size))
+
+    def create_statistics(self, token_ids=None):
+        """create_statistics over the pinned ivpq rows, installed: token_ids = the row ids of a column's tokens with their
+        multiplicity, None = every row once.  -> the row, [cells + 1] floats."""
+        rows = self.lib.freddy_statistics_rows(self.h)
+        if rows == 0:
+            raise FreddyError("the ivpq tables are not loaded")
+        ids = None if token_ids is None else _i32(token_ids).reshape(-1)
+        n = 0 if ids is None else ids.size
+        # (an empty LIST is not "every row": the mirror gets a pointer that is not NULL with n = 0, and the library refuses it)
+        ptr = None if ids is None else _p(ids if n else np.zeros(1, np.int32))
+        out = np.empty(rows, np.float32)
+        self._check(self.lib.create_statistics(self.h, ptr, C.c_int64(n), _p(out)))
+        return out
+
     def insert_batch(self, norm_vectors):
         """freddy.c:1403-1658 for the normalised vectors of NEW terms; returns the ids given in google_vecs_norm."""
         v = _f32(norm_vectors)

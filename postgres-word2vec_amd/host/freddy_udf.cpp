@@ -62,6 +62,17 @@ std::vector<int64_t> order_by_id(const int32_t* ids, int64_t N) {
   return ord;
 }
 
+// getStatistics (index_utils.c:632-665): result[coarse_id] = coarse_freq, from the (coarse_id, coarse_freq) rows of a stat table
+int stat_row(int cells, const int32_t* stat_coarse_id, const float* stat_freq, int32_t n_stat, std::vector<float>& stats) {
+  if (n_stat != cells + 1) return fail(-1, "statistics table has %d rows, expected %d", n_stat, cells + 1);
+  stats.assign((size_t)cells + 1, 0.0f);
+  for (int i = 0; i < n_stat; ++i) {
+    if (stat_coarse_id[i] < 0 || stat_coarse_id[i] > cells) return fail(-1, "statistics coarse_id out of range");
+    stats[stat_coarse_id[i]] = stat_freq[i];
+  }
+  return 0;
+}
+
 }  // namespace
 
 struct freddy_session {
@@ -244,13 +255,8 @@ int freddy_load_ivpq(freddy_session_t* s, const int32_t* cb_pos, const int32_t* 
   Codebook cq;
   if (int rc = cq.build(cq_pos, cq_code, cq_vectors, n_cq_entries, d / 2)) return rc;
   const int cells = cq.K * cq.K;
-  // getStatistics (index_utils.c:632-665): result[coarse_id] = coarse_freq
-  if (n_stat != cells + 1) return fail(-1, "statistics table has %d rows, expected %d", n_stat, cells + 1);
-  std::vector<float> stats((size_t)cells + 1, 0.0f);
-  for (int i = 0; i < n_stat; ++i) {
-    if (stat_coarse_id[i] < 0 || stat_coarse_id[i] > cells) return fail(-1, "statistics coarse_id out of range");
-    stats[stat_coarse_id[i]] = stat_freq[i];
-  }
+  std::vector<float> stats;
+  if (int rc = stat_row(cells, stat_coarse_id, stat_freq, n_stat, stats)) return rc;
   std::vector<int64_t> ord = order_by_id(ids, N);
   std::vector<int32_t> sid((size_t)N), scell((size_t)N);
   std::vector<int16_t> scodes((size_t)N * cb.m);
@@ -278,6 +284,26 @@ int freddy_load_ivpq(freddy_session_t* s, const int32_t* cb_pos, const int32_t* 
   s->cq_multi = cq;
   s->ivpq_max_id = N ? sid[(size_t)N - 1] : 0;
   s->ivpq_ids = std::move(sid);
+  return 0;
+}
+
+// ---- set_statistics_table / create_statistics (freddy--0.0.1.sql:70, :150-171): the statistics row of the pinned ivpq handle ----
+int freddy_set_statistics_table(freddy_session_t* s, const int32_t* stat_coarse_id, const float* stat_freq, int32_t n_stat) {
+  if (!s || !stat_coarse_id || !stat_freq) return fail(-1, "bad argument");
+  if (!s->ivpq) return fail(-1, "the ivpq tables are not loaded");
+  std::vector<float> stats;
+  if (int rc = stat_row(s->cq_multi.K * s->cq_multi.K, stat_coarse_id, stat_freq, n_stat, stats)) return rc;
+  if (int rc = freddy_gpu_set_statistics(s->ivpq, stats.data(), (int32_t)stats.size())) return gpu_fail(rc);
+  return 0;
+}
+
+int32_t freddy_statistics_rows(const freddy_session_t* s) { return s && s->ivpq ? s->cq_multi.K * s->cq_multi.K + 1 : 0; }
+
+// computed over the pinned rows and installed, as the bootstrap block does (:183-184: create_statistics, then set_statistics_table)
+int create_statistics(freddy_session_t* s, const int32_t* token_ids, int64_t n, float* out_stats) {
+  if (!s || n < 0 || (n > 0 && !token_ids)) return fail(-1, "bad argument");
+  if (!s->ivpq) return fail(-1, "the ivpq tables are not loaded");
+  if (int rc = freddy_gpu_create_statistics(s->ivpq, token_ids, n, 1, out_stats, nullptr)) return gpu_fail(rc);
   return 0;
 }
 
