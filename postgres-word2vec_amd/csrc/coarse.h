@@ -8,9 +8,10 @@
 //
 // ranks the cells, with a proven bracket |a - d| <= eps(q) around the reference's binary32 result d, and the
 // reference's chain -- (q_i - c_i) rounded, squared, added in order i = 0..d-1 from +0 (index_utils.c:500-508) --
-// is evaluated only for the cells whose bracket reaches the 2W-th smallest upper bound: a superset of the 2W
-// smallest exact (distance, cell) keys, which is all the reference's cell list can depend on (DESIGN.md 3,
-// "selection-then-replay"; same argument as probe_plan_kernel in kernels.h).  The approximate value never
+// is evaluated only for the cells whose bracket reaches the W-th smallest upper bound: a superset of the cells at or
+// below the W-th smallest exact distance, ties included, which is all the reference's cell list can depend on
+// ("selection-then-replay" and the threshold rank; the 2W smallest exact keys of that set are replayed, as
+// in probe_plan_kernel in kernels.h).  The approximate value never
 // reaches a result: the probe plan, the item bounds of the scan and the tie behaviour all use the exact d.
 //
 // The bracket (u = 2^-24, D = exact real |q - c|^2 <= (|q| + |c|)^2):
@@ -333,13 +334,14 @@ static __global__ __launch_bounds__(256) void coarse_approx_kernel(const float* 
 // time waiting on its own dependent instructions: 41 us for the batch, tools/lab/ubench_plan).
 //   1. wave w takes cells [256 w, 256 w + 256): approximate distances into registers (4 per lane), cells
 //      already probed masked;
-//   2. tau = the 2W-th smallest of the 64 per-lane minima over all four waves (>= the 2W-th smallest
-//      overall); candidates = cells with a <= tau + 2 eps: every cell among the 2W smallest EXACT keys is one
-//      of them (at least 2W cells have d <= a + eps <= tau + eps, so such a cell has a - eps <= d <= tau + eps);
+//   2. tau = the W-th smallest of the 64 per-lane minima over all four waves (>= the W-th smallest
+//      overall); candidates = cells with a <= tau + 2 eps: every cell at or below the W-th smallest EXACT distance d* is
+//      one of them (at least W cells have d <= a + eps <= tau + eps, so d* <= tau + eps and such a cell has
+//      a <= d + eps <= tau + 2 eps) -- the rank is W, the count of keys step 4 keeps is 2W;
 //   3. every wave refines ITS candidates with the reference's squareDistance, PLAN2_NCB at a time: lanes <->
 //      dimensions for the separately rounded (q_i - c_i)^2 (coalesced centroid rows, all loads of a batch in
 //      flight), staged in LDS, then lane <-> candidate for the sequential sum;
-//   4. wave 0 keeps the 2W smallest exact keys, orders them by cell id and replays updateTopK: identical to
+//   4. wave 0 keeps the 2W smallest exact keys of the candidates, orders them by cell id and replays updateTopK: identical to
 //      probe_plan_kernel from here on (same outputs, plus the exact distance of every item).
 // ---------------------------------------------------------------------------------------
 struct Plan2Args {
@@ -398,7 +400,7 @@ __global__ __launch_bounds__(64 * NWP, NWP == 1 ? 4 : 4) void probe_plan2_kernel
   const int x = blockIdx.x, lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int q = a.active ? a.active[x] : x;
-  const int W = a.W, L = 2 * W, d = g.d;
+  const int W = a.W, L = 2 * W, d = g.d;   // L: the KEEP count of exact keys (sel, the replay); the threshold's RANK is W (step B)
   uint32_t* used = a.used + (size_t)q * a.used_words;
   const float* drow = a.dist + (size_t)q * a.Cpad;
   const float INF = __uint_as_float(0x7f800000u);
@@ -453,8 +455,8 @@ __global__ __launch_bounds__(64 * NWP, NWP == 1 ? 4 : 4) void probe_plan2_kernel
       else av[u] = -INF;                          // NaN (non-finite table entries): always a candidate, never a threshold
     }
   } else if (g.tmin) {
-    // two-level: the threshold from the tiles' minima (every one of them is some cell's distance: the 2W-th smallest of them
-    // is >= the 2W-th smallest distance), the candidates from the tiles whose minimum can reach it
+    // two-level: the threshold from the tiles' minima (every one of them is some cell's distance: the W-th smallest of them
+    // is >= the W-th smallest distance), the candidates from the tiles whose minimum can reach it
     const int gx = a.Cpad >> 7;
     for (int i = threadIdx.x; i < gx; i += 64 * NW) {
       const float tm = g.tmin[(size_t)q * gx + i];
@@ -474,7 +476,11 @@ __global__ __launch_bounds__(64 * NWP, NWP == 1 ? 4 : 4) void probe_plan2_kernel
   tick(0);
   __syncthreads();
   if (ABL == 2) { if (mn == 12345.0f) g.item_dist[0] = mn; return; }
-  // ---- B (wave 0): tau = the 2W-th smallest of the 64 per-lane minima; thr = tau + 2 eps ----
+  // ---- B (wave 0): tau = the W-th smallest of the 64 per-lane minima; thr = tau + 2 eps ----
+  // (The rank is W, not the 2W keys step 4 keeps: tau >= the W-th smallest approximate distance a_W, at least W cells have
+  // d <= a_W + eps, so the W-th smallest exact distance d* <= tau + eps, and every cell with d <= d* -- all ties at d*
+  // included -- has a <= d + eps <= tau + 2 eps: it is a candidate.  Cells above d* change neither acceptance nor order of
+  // the others in the replay.)
   float eps = 0.0f;
   bool finite = true;
   if (wave == 0) {
@@ -490,7 +496,7 @@ __global__ __launch_bounds__(64 * NWP, NWP == 1 ? 4 : 4) void probe_plan2_kernel
       // what counts in wave 0 is the NUMBER of instructions -- counting ranks with 64 independent compares
       // measured twice the time of this 21-stage sort)
       const uint32_t k0 = wave_sort32(float_order_bits(m4));
-      const uint32_t tb = (uint32_t)__shfl((int)k0, L - 1 < 63 ? L - 1 : 63, 64);
+      const uint32_t tb = (uint32_t)__shfl((int)k0, W - 1 < 63 ? W - 1 : 63, 64);
       const float tau = __uint_as_float((tb & 0x80000000u) ? (tb & 0x7fffffffu) : ~tb);
       if (tau < 1e30f) thr = (tau + 2.0f * eps) * (1.0f + 1e-6f) + 1e-37f;
     }
@@ -695,8 +701,11 @@ __global__ __launch_bounds__(64 * NWP, NWP == 1 ? 4 : 4) void probe_plan2_kernel
   u64 byc = KEY_INF;   // candidates in cell order: (cell << 32) | distance bits
   if (n_all <= 64) {
     // The candidates ARE in ascending cell order already (lane i = candidate i), and replaying a superset of the
-    // 2W smallest keys gives the same list as replaying exactly those.  Without equal distances among the W + 1
-    // smallest the list is simply the W smallest below the limit, ascending: one sort instead of the replay.
+    // cells at or below the W-th smallest exact distance d* gives the same list as replaying every cell.  Without equal
+    // distances among the W + 1 smallest the list is simply the W smallest below the limit, ascending: one sort instead of
+    // the replay.  (With the threshold at rank W the candidates may be as few as W.  The shortcut still holds: every cell AT
+    // d* is a candidate by construction, so a tie at the W-th place is always between two candidates and is seen here; a
+    // cell that is no candidate lies strictly above d* and can neither tie with the W-th nor enter the list.)
     __builtin_amdgcn_wave_barrier();
     const bool v = lane < n_all;
     const uint32_t db = v ? __float_as_uint(cdist[lane]) : 0xffffffffu;

@@ -439,15 +439,15 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_filter5_kernel(FilterArgs a) {
         if (i0 < cnt) {
           uint32_t c0 = colmin[i0 * 64 + lane], c1 = colmin[i1 * 64 + lane];
           wave_sort32_x2(c0, c1);   // (order-preserving keys of the float column minima)
-          uint32_t t0 = __shfl(c0, a.L - 1, 64), t1 = __shfl(c1, a.L - 1, 64);
+          uint32_t t0 = __shfl(c0, a.Lt - 1, 64), t1 = __shfl(c1, a.Lt - 1, 64);
           if (lane == 0) {
             if (a.tau_run) {
               // The query's running bound (FilterArgs::tau_run).  tau' + A_up of this (item, chunk) is reported (no answer is
               // waited for); the bound read at the start of the last phase -- whatever other workgroups had reported by
-              // then -- lowers this item's cut to bound - A_lo.  Why any such value is valid: tau' is at least the L-th smallest s'
-              // of the chunk, s' + A is the cheap distance up to the item-independent part of its error, and the L-th smallest
-              // over MORE rows is never larger -- so every reported value is an upper bound of the query's L-th smallest cheap
-              // distance D_L, and the rows that can matter have s' + A <= D_L + 2 e.  (The three float roundings here are
+              // then -- lowers this item's cut to bound - A_lo.  Why any such value is valid: tau' is at least the k-th smallest s'
+              // of the chunk (k = a.Lt, the threshold rank), s' + A is the cheap distance up to the item-independent part of its
+              // error, and the k-th smallest over MORE rows is never larger -- so every reported value is an upper bound of the
+              // query's k-th smallest cheap distance D_k, and the rows that can matter have s' + A <= D_k + 2 e.  (The three float roundings here are
               // below 10 u B of the 2.2 e = 230 u B + 13 T that E leaves over 2 e.)
               auto lower = [&](uint32_t t, int i, uint32_t inv) -> uint32_t {
                 // (only a value that improves on what was read goes out: see running_bound5)

@@ -9,7 +9,7 @@
 //     gatherers are in the PREVIOUS entry's tail (column minima, thresholds, survivor pass: VALU work that needs no slab);
 //   * the gatherers read a row's twelve positions back to back -- no barrier inside the main loop, nobody stores meanwhile
 //     (tools/lab/ubench7.hip: 18.2 k instead of 20.0 k cycles per entry with random codes, 7.9 k instead of 10.4 k conflict-free);
-//   * the thresholds (the L-th smallest column minimum per item) are taken by the GATHERER waves, so the builders are free
+//   * the thresholds (the k-th smallest column minimum per item: FilterArgs::Lt) are taken by the GATHERER waves, so the builders are free
 //     for the whole tail; four barriers per entry instead of eight;
 //   * the table kernel writes a COMPACT copy of the table beside the general one (qc8: 512 B per (query, position), dword s =
 //     code s | code s + 128 << 16): a builder wave's load is 256 consecutive bytes, an entry's table words are 96 KB -- the
@@ -30,13 +30,13 @@ static constexpr uint32_t SCAN8_HALFB = 256u * 16u;         // one plane: the va
 static constexpr uint32_t SCAN8_POSB = 2u * SCAN8_HALFB;    // one position: two planes (items 0-7, 8-15)
 static constexpr uint32_t scan8_slab_bytes(int m) { return (uint32_t)m * SCAN8_POSB; }
 
-// S1 for ONE item (every wave of the workgroup takes one: builders items 0-7, gatherers 8-15): tau' = the L-th smallest of the
+// S1 for ONE item (every wave of the workgroup takes one: builders items 0-7, gatherers 8-15): tau' = the Lt-th smallest of the
 // item's 64 column minima, lowered by the query's running bound, widened by E -> thr_s[i]; the column is re-armed.  (The same split
 // in ivf_filter5_kernel, where the builders take two items each and the gatherers wait: measured, no gain -- 82.3 against 82.0 us.)
 __device__ __forceinline__ void scan8_threshold(const FilterArgs& a, const int32_t* rec, uint32_t* colmin, uint32_t* thr_s, int i, int lane, uint32_t run) {
   uint32_t c = colmin[i * 64 + lane];
   c = wave_sort32(c);   // (order-preserving keys of the float column minima)
-  uint32_t t = __shfl(c, a.L - 1, 64);
+  uint32_t t = __shfl(c, a.Lt - 1, 64);
   if (lane == 0) thr_s[i] = filter_threshold5(a, rec, i, t, run);
   colmin[i * 64 + lane] = 0xffffffffu;
 }

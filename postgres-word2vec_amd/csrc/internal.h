@@ -74,7 +74,7 @@ struct Tuning {
   int one_launch = 1;          // FREDDY_GPU_ONE_LAUNCH: a single query through the host-buffer calls as ONE launch (one.h) instead of a chain
   int pq_fused = -1;           // FREDDY_GPU_PQ_FUSED: batches over the flat PQ table through the cell-grouped filter + refine scan: -1 = from 16 queries on, 0 never, 1 always
   int sparse_items = 2;        // FREDDY_GPU_SPARSE_ITEMS: cells that at most this many queries of a batch probe are scanned item by item (sparse5.h) instead of as cell-grouped work entries (0 = never, < 0 = always for cells of up to that many items)
-  int running_bound = 1;       // FREDDY_GPU_RUNNING_BOUND: the scan's entries share a per-query running bound of the L-th smallest cheap distance
+  int running_bound = 1;       // FREDDY_GPU_RUNNING_BOUND: the scan's entries share a per-query running bound of the k-th smallest cheap distance
                                // (FilterArgs::tau_run): fewer survivors for the merge; 0 = every (item, chunk) cuts at its own threshold
   int codes_u8 = 1;            // FREDDY_GPU_CODES_U8: K <= 256: the integer-slab scans read one byte per code (packed8, 16 instead of 28 B per row) -- 1: the scan with the whole entry's slab in LDS (fused8.h), 2: the six-phase scan (fused5.h); 0 = the int16 layout
   int exact_filter = -1;       // FREDDY_GPU_EXACT_FILTER: exact kNN as MFMA filter + exact refine (exact2.h): -1 auto (tables of >= 8192 rows, k <= 32), 0 never, 1 always
@@ -148,7 +148,8 @@ struct IvfRun {
   hipStream_t s;       // the stream the search is enqueued on
   int share;           // batches in flight on this handle (the scan takes n_cus / share CUs)
   const float* d_q;
-  int Q, k, W, L, found_rule, upi;
+  int Q, k, W, L, found_rule, upi;   // L = 2k: the KEEP count (exact keys that selection-then-replay keeps, every workspace size)
+  int Lt;              // the threshold RANK: the order statistic of a cheap bound that becomes a cut (k)
   float sentinel, cell_limit;
   int32_t *d_out_ids, *d_status;
   float* d_out_dist;

@@ -49,6 +49,7 @@ static IvfRun ivf_run(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, int sh
                       int32_t* d_out_ids, float* d_out_dist, int32_t* d_status) {
   IvfRun r{};
   r.ix = ix; r.ws = ws; r.s = s; r.share = std::max(1, share); r.d_q = d_q; r.Q = Q; r.k = k; r.W = W; r.L = std::min(2 * k, 64 * 16);
+  r.Lt = std::min(k, r.L);
   r.sentinel = sentinel; r.d_out_ids = d_out_ids; r.d_out_dist = d_out_dist; r.d_status = d_status;
   r.upi = units_per_item(ix); r.scan_kernel = 5; r.n_active = Q;
   return r;

@@ -378,7 +378,7 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   fl.qc = qt.qc; fl.qc8 = qt.qc8; fl.rterm = ix->rterm; fl.records = ws->w_records.as<int32_t>(); fl.n_groups = wt.n_groups;
   fl.work_counter = wt.work_counter; fl.packed = ix->packed; fl.surv = ws->w_surv.as<u64>(); fl.surv_count = ws->w_surv_cnt.as<int32_t>();
   fl.cand_count = rows_counter(r);
-  fl.K = K; fl.L = r.L; fl.upi = r.upi; fl.sentinel = r.sentinel; fl.keep_all = (ix->tune.check_brackets & 1) ? 1 : 0; fl.fence = 0;
+  fl.K = K; fl.L = r.L; fl.Lt = r.Lt; fl.upi = r.upi; fl.sentinel = r.sentinel; fl.keep_all = (ix->tune.check_brackets & 1) ? 1 : 0; fl.fence = 0;
   // (not for a batch over the flat PQ table: a few dozen queries x a thousand entries read and update the same two cache lines --
   // 96 -> 128 us -- and its merge gains nothing; an IVFADC batch: +2.6 % queries/s with four batches in flight)
   fl.tau_run = r.running_bound ? ws->w_cand.as<uint32_t>() + r.Q : nullptr;
@@ -410,7 +410,7 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
     sp.blk_off = ix->blk_off; sp.list_off = ix->list_off; sp.sorted_item = ws->w_sorted.as<int32_t>(); sp.item_query = pa.item_query;
     sp.item_dist = pa.item_dist; sp.sp_cell = wt.sp_cell; sp.sp_first = wt.sp_first; sp.sp_chunk = wt.sp_chunk;
     sp.n_units = wt.n_sparse; sp.work_counter = wt.sp_counter; sp.surv = fl.surv; sp.surv_count = fl.surv_count; sp.packed8 = fl.packed8;
-    sp.cand_count = fl.cand_count; sp.K = K; sp.L = r.L; sp.upi = r.upi; sp.sentinel = r.sentinel; sp.keep_all = fl.keep_all; sp.tau_run = fl.tau_run;
+    sp.cand_count = fl.cand_count; sp.K = K; sp.L = r.L; sp.Lt = r.Lt; sp.upi = r.upi; sp.sentinel = r.sentinel; sp.keep_all = fl.keep_all; sp.tau_run = fl.tau_run;
     const unsigned sp_grid = (unsigned)std::min<size_t>(wt.sp_cap, (size_t)std::max(1, scan_cus) * (wt.sp_pairs ? 3 : 6));
     const auto sparse = sparse_kernel(wt.sp_pairs, u8, fl.cand_count != nullptr);
     timed_launch(ix, s, "sparse_items", [&] { hipLaunchKernelGGL(sparse, dim3(sp_grid), dim3(256), 0, s, sp); });

@@ -10,12 +10,13 @@
 //                       `----- summed over the row's codewords: rterm[row], pinned once (fp64 -> fp32)
 //                                        `---- qc[query][p][code] = -2 q_p.c   int16 fixed point, one table per batch (fused5.h)
 //
-// Selection keeps every row whose cheap value is within E of the item's L-th column minimum: that
-// set contains every row whose exact distance is <= the L-th smallest exact distance of the item,
-// ties included.  Survivors carry (d_lo, row location); merge_refine_kernel (four waves per query)
-// finds T = (L-th smallest d_lo) + E, recomputes the reference's distance -- sequential binary32
+// Selection keeps every row whose cheap value is within E of the item's k-th smallest column minimum: that
+// set contains every row whose exact distance is <= the k-th smallest exact distance of the item,
+// ties included -- all the list can depend on.  (The threshold's RANK is k; 2k is the COUNT of exact keys that
+// selection-then-replay keeps: DESIGN.md 3.)  Survivors carry (d_lo, row location); merge_refine_kernel (four waves per query)
+// finds T = (k-th smallest d_lo) + E, recomputes the reference's distance -- sequential binary32
 // squareDistance per position, positions added in order (index_utils.c:500-508, :1126-1133) -- for
-// the rows with d_lo <= T only (typically L + 1 of ~130 survivors), and runs the same 2k-smallest
+// the rows with d_lo <= T only (typically k + 1 of the survivors), and runs the same 2k-smallest
 // selection and updateTopK replay as merge_surv_kernel on those exact keys.  Rows whose bound
 // straddles the sentinel guard (freddy.c:971 counts them) are flagged and decided exactly as well.
 // Non-finite inputs make E non-finite, which sends every row to the exact stage (slow, still exact).
@@ -38,7 +39,7 @@ struct FilterArgs {
   u64* surv;                   // [items][upi][8 waves][512]: (bits(d_lo) << 32) | flag << 31 | row location
   int32_t* surv_count;
   int32_t* cand_count;         // [Q] or NULL: rows certainly below the sentinel (the flagged ones are added by the merge)
-  int K, L, upi;
+  int K, L, upi;               // (L = 2k, the keep count: the scans' cuts take the rank Lt below)
   float sentinel;
   uint32_t desc_offset;
   uint32_t fence;              // always 0: conditions the compiler cannot see through keep the code of ivf_filter5_kernel's phases in basic blocks of their own -- without them the register allocator spills in the main loop (86.5 instead of 82 us; sched_barriers do not have the same effect)
@@ -46,12 +47,16 @@ struct FilterArgs {
   long long* prof;
   const uint32_t* packed8;     // U8 instantiation: [blocks][3][64], one byte per code (K <= 256)
   // The query's RUNNING bound (ivf_filter5_kernel, S1): tau_run[q] = ~key of the smallest (tau' + A_up) any finished (item, chunk)
-  // of query q has reported this round -- an upper bound of the query's L-th smallest cheap distance over everything it probes;
+  // of query q has reported this round -- an upper bound of the query's Lt-th (= k-th) smallest cheap distance over everything it probes;
   // 0 = none yet.  A later entry cuts at min(tau', bound - A_lo) + E instead of tau' + E.  Purely opportunistic: a workgroup
   // reads whatever is there (no waiting, any stale value is a valid bound), so the survivors differ from run to run and the
   // lists never do.  NULL: off.
   uint32_t* tau_run;
   const uint32_t* qc8;         // fused8.h (K <= 256): [Q][M][128] the compact copy of the table: dword s = code s | code s + 128 << 16
+  // The threshold RANK (k): S1 cuts an (item, chunk) at its Lt-th smallest column minimum + E.  L above is the KEEP count (2k, what
+  // selection-then-replay keeps of EXACT keys: DESIGN.md 3); a cut on a cheap bound only has to let every row at or below the
+  // query's k-th smallest exact distance through.  (Appended: the fields above keep their offsets.)
+  int Lt;
 };
 
 // The integer-slab scan (fused5.h) quantises the table with one scale per query; its margin (derivation there):
@@ -173,6 +178,7 @@ struct MergeRefineArgs {
   const int32_t* blk_cell;     // [blocks] list (cell) of every row block
   int32_t* cand_count;
   int32_t* violations;         // [2] rows of the exact stage whose distance left the bracket [d_lo, d_lo + E] / rows checked
+                               // (slot 1 counts with refine_all only; a lab build with -DFREDDY_MERGE_STATS counts EVERY refined row there: tools/README.md)
   int32_t* out_ids;
   float* out_dist;
   int32_t* found;
@@ -186,7 +192,8 @@ struct MergeRefineArgs {
   // PARTIAL instantiation (a batch over the flat PQ table): workgroup x = (query x / slices, slice x % slices) merges the
   // survivors of ITS W items (the query's items are slices * W wide) and leaves its L smallest exact keys in part[x][L];
   // merge_replay_kernel selects among the slices' keys and replays.  (Each slice's 2k smallest exact keys contain the
-  // query's 2k smallest that lie in the slice: selection-then-replay as before, on 4 x as many workgroups.)
+  // query's 2k smallest that lie in the slice: selection-then-replay as before, on 4 x as many workgroups.  A slice's T is its
+  // OWN k-th smallest bound + E: the slice's k-th smallest exact distance is >= the query's, so no row at or below the query's is lost.)
   int slices;
   u64* part;
 };
@@ -494,10 +501,16 @@ __global__ __launch_bounds__(64 * NWV, 4) void merge_refine_kernel(MergeRefineAr
     __syncthreads();
     return;
   }
-  // T = (L-th smallest d_lo) + E, rounded up; every key of the query if there are fewer than L or E is not finite
+  // T = (k-th smallest d_lo) + E, rounded up; every key of the query if there are fewer than k or E is not finite.  The RANK of
+  // the threshold is k; a.L = 2k is the COUNT of exact keys sel2 keeps for the replay.  At least k rows have
+  // d <= (k-th smallest d_lo) + E, so the query's k-th smallest exact distance d* is <= T, and every row with d <= d* -- all ties
+  // at d* included -- has d_lo <= d <= T: rows above d* change neither acceptance nor order of the others in the replay.
+  // (The keys are moved up by a.L - k lanes and read at lane a.L - 1, the index sel2 reads its own threshold at: with an index
+  // of its own the four-wave instantiation spills more -- 80 instead of 76 B of scratch, tests/golden/codegen_ceilings.json.)
   uint32_t T_bits;
   {
-    const u64 kth = wave_topk_at<1>(sel.acc, a.L - 1);
+    const u64 up[1] = {__shfl(sel.acc[0], lane - (a.L - k), 64)};   // (lane a.L - 1 <- lane k - 1)
+    const u64 kth = wave_topk_at<1>(up, a.L - 1);
     T_bits = (kth == KEY_INF || a.refine_all) ? 0xfffffffeu : widen_threshold((uint32_t)(kth >> 32), E);   // (refine_all: tests, every row)
   }
   __builtin_amdgcn_wave_barrier();
@@ -517,7 +530,11 @@ __global__ __launch_bounds__(64 * NWV, 4) void merge_refine_kernel(MergeRefineAr
       {   // self-check of the bound (freddy_gpu_filter_bound_violations)
         const float dlo = __uint_as_float((uint32_t)(cq_key[lane] >> 32));
         if (E < 1e20f && (dsum < dlo || dsum > dlo + E)) atomicAdd(a.violations, 1);
+#ifdef FREDDY_MERGE_STATS   // (lab builds: rows of the exact stage per query, read as freddy_gpu_filter_bound_checked; as FREDDY_PLAN2_STATS)
+        atomicAdd(a.violations + 1, 1);
+#else
         if (a.refine_all) atomicAdd(a.violations + 1, 1);
+#endif
       }
       if (dsum < a.sentinel) {
         out_key = ((u64)__float_as_uint(dsum) << 32) | (u64)(uint32_t)pid;
@@ -573,7 +590,7 @@ __global__ __launch_bounds__(64 * NWV, 4) void merge_refine_kernel(MergeRefineAr
       __builtin_amdgcn_wave_barrier();
     }
   }
-  // More qualifying rows than were kept (a dense neighbourhood: hundreds of rows within E of the 2k-th smallest bound --
+  // More qualifying rows than were kept (a dense neighbourhood: hundreds of rows within E of the k-th smallest bound --
   // common for batches over the flat PQ table): all waves collect them, then the usual rounds of NC rows.  Only if
   // even that queue overflows does wave 0 walk the regions alone (below).
   auto round4 = [&](int n1) {     // the first n1 <= NC queue entries, refined by the four waves together
@@ -607,7 +624,7 @@ __global__ __launch_bounds__(64 * NWV, 4) void merge_refine_kernel(MergeRefineAr
   if (revisit) sweep([&](u64 kk, bool valid, int j) { offer(kk, valid, valid ? a.item_cell[(size_t)x * a.W + j / per_item] : 0); }, 0, PB);
   if (a.fence & 1) queued = 0;
   // the queued rows are refined by the four waves together, NC per round (normally one round: <= NC rows; a batch over
-  // the flat PQ table has 20 .. 60 rows within E of its 2k-th smallest bound)
+  // the flat PQ table has dozens of rows within E of its k-th smallest bound)
   if (NWV > 1) {
     while (queued > 0) round4(queued < NC ? queued : NC);
     if (lane == 0) sh_n = 0;

@@ -45,7 +45,7 @@ __device__ __forceinline__ uint32_t running_bound5(uint32_t* __restrict__ tau_ru
   return t;
 }
 
-// S1, lane 0's part for item i of a cell-grouped entry (rec: its record, entry_record5_kernel): t = the key of tau', the L-th
+// S1, lane 0's part for item i of a cell-grouped entry (rec: its record, entry_record5_kernel): t = the key of tau', the Lt-th
 // smallest of the item's sorted column minima; returns the bits of the float the item cuts at, tau' + E (+inf: keep_all).
 // inv = the query's running bound as read earlier.  (ivf_filter5_kernel's S1 takes two items per wave and keeps its own text: one
 // test of tau_run around both -- with two calls of this function that kernel compiled to other code.)

@@ -8,7 +8,7 @@
 //     in plain [position][code] order -- six workgroups per CU;
 //   * a lane holds 16 rows: per row six code dwords, twelve ds_read_u16 lookups, the sum (unsigned, see filt5_bias),
 //     s' = fma(scale, V, rterm[row]) -- the SAME value, bit for bit, as the cell-grouped scan forms, kept in registers;
-//   * threshold and survivors exactly as there: tau' = the L-th smallest of the 64 column minima, rows with
+//   * threshold and survivors exactly as there: tau' = the Lt-th (k-th) smallest of the 64 column minima, rows with
 //     s' <= tau' + E (and the sentinel rule's ambiguous rows) -> the item's survivor regions, surv_key5(d_lo, location) (the
 //     contract with the merge: scan_tail5.inc).
 //     Wave w's row slots r = 0 .. 15 are the blocks 4 r + w of the chunk, i.e. the cell-grouped scan's gatherer waves
@@ -47,6 +47,7 @@ struct SparseArgs {
   float sentinel;
   int keep_all;                // option filter_keep_all (tests): every row survives (as ivf_filter5_kernel)
   uint32_t* tau_run;           // [Q] the queries' running bounds (FilterArgs::tau_run), or NULL
+  int Lt;                      // the threshold rank (FilterArgs::Lt)
 };
 
 template <int M, bool CAND, bool U8 = false>   // U8: one byte per code (K <= 256), packed8[block][3][64]
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(256, 6) void sparse_item5_kernel(SparseArgs a) {
         sv[r0 + u] = live ? __builtin_fmaf(sc, (float)v, rt[u]) : __uint_as_float(0x7f800000u);
       }
     }
-    // column minima over the 4 waves x 16 rows of a lane index -> tau' = the L-th smallest -> threshold
+    // column minima over the 4 waves x 16 rows of a lane index -> tau' = the Lt-th smallest -> threshold
     {
       float mn = sv[0];
 #pragma unroll
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256, 6) void sparse_item5_kernel(SparseArgs a) {
     __syncthreads();
     if (wave == 0) {
       const uint32_t c0 = wave_sort32(colmin[lane]);
-      uint32_t t0 = __shfl(c0, a.L - 1, 64);
+      uint32_t t0 = __shfl(c0, a.Lt - 1, 64);
       if (lane == 0) {
         if (a.tau_run && ib.e < 1e30f && A >= 0.0f && A < 1e30f) t0 = running_bound5(a.tau_run, (uint32_t)q, t0, A * (1.0f + 2e-5f), A * (1.0f - 2e-5f), run_inv);
         thr_sh = a.keep_all ? 0x7f800000u : widen_threshold5(t0, ib.e);
@@ -322,7 +323,7 @@ __global__ __launch_bounds__(256, 3) void sparse_pair5_kernel(SparseArgs a) {
     const unsigned char* lut_b = reinterpret_cast<const unsigned char*>(&lut[0][0][0]);
     if (cnt == 1) sparse_rows5<M, CAND, U8, 1>(a, lut_b, b0, nb, last_blk, tail_rows, wave, lane, sc, sv);
     else sparse_rows5<M, CAND, U8, 2>(a, lut_b, b0, nb, last_blk, tail_rows, wave, lane, sc, sv);
-    // column minima over the 4 waves x 16 rows of a lane index -> tau' = the L-th smallest -> threshold
+    // column minima over the 4 waves x 16 rows of a lane index -> tau' = the Lt-th smallest -> threshold
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       if (i < cnt) {
@@ -337,7 +338,7 @@ __global__ __launch_bounds__(256, 3) void sparse_pair5_kernel(SparseArgs a) {
     for (int i = 0; i < NI; ++i) {
       if (wave == i && i < cnt) {     // (wave i: item i's threshold)
         const uint32_t c0 = wave_sort32(colmin[i][lane]);
-        uint32_t t0 = __shfl(c0, a.L - 1, 64);
+        uint32_t t0 = __shfl(c0, a.Lt - 1, 64);
         if (lane == 0) {
           if (a.tau_run && ib[i].e < 1e30f && Ad[i] >= 0.0f && Ad[i] < 1e30f)
             t0 = running_bound5(a.tau_run, (uint32_t)q[i], t0, Ad[i] * (1.0f + 2e-5f), Ad[i] * (1.0f - 2e-5f), run_inv[i]);
