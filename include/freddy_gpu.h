@@ -368,6 +368,18 @@ typedef struct freddy_insert_desc {
 int freddy_gpu_insert_quantize(const freddy_insert_desc* desc, int device, const float* vectors, int64_t n,
                                int16_t* pq_codes /*[n][pq_m]*/, int32_t* coarse_id /*[n]*/, int16_t* residual_codes /*[n][res_m]*/,
                                int16_t* ivpq_codes /*[n][ivpq_m]*/, int16_t* coarse_multi_codes /*[n][multi_positions]*/);
+/* ---- index mutation: append_rows, remove_rows, update_rows, update_codebook, set_statistics, create_statistics ------------
+ * THE CONTRACT OF A FAILED CALL, for all of them: after a non-zero return the handle is AS IT WAS, or POISONED.
+ *   as it was:  every entry point answers as before the call, freddy_gpu_index_bytes has not moved, and the same call may simply
+ *               be made again.  This is what a refused argument leaves, and what a failed allocation (FREDDY_E_NOMEM) leaves
+ *               wherever the new arrays are built beside the old ones and swapped in last: append_rows and remove_rows on pq,
+ *               ivf and ivpq handles, update_codebook on every kind, set_statistics, create_statistics.
+ *   poisoned:   arrays had been rewritten in place when the call failed (update_rows after its first write; append_rows /
+ *               remove_rows on a vector handle once the rows are in and the exact filter's statistics, which are rewritten in
+ *               place, could not follow; a replica that failed after another device had changed).  Every entry point that reads
+ *               the tables then refuses with FREDDY_E_HIP ("unpin it and pin again") without launching anything, and
+ *               freddy_gpu_unpin frees it as usual.
+ * There is no third state: no call returns an error and leaves a table that a search would read past its end. */
 /* Append rows to a pinned index in HBM (the INSERTs of updateProductQuantizationRelation /
  * updateWordVectorsRelation, index_utils.c:993-1074): ids must be larger than every id already pinned and
  * ascending.  pq: (ids, codes); ivf: (ids, coarse_id, codes) -- each row joins the end of its cell's inverted
@@ -511,6 +523,27 @@ int freddy_gpu_last_track(const freddy_gpu_index_t* ivpq, freddy_track* out);
  * header, whose freddy_track ends earlier, gets the fields it knows); returns the number of bytes written, or < 0.  Hosts
  * that are built separately from the library (the PostgreSQL extension) call this one. */
 int freddy_gpu_last_track_sized(const freddy_gpu_index_t* ivpq, void* out, size_t out_size);
+
+/* The allocation seam: every device and pinned-host allocation of the library passes one counter, and a test can make one of
+ * them fail.  Process-wide, for tests and diagnosis only; nothing reads the environment, and with nothing armed and tracking off
+ * an allocation costs one relaxed atomic add.
+ *   alloc_fail_nth(n, real): the n-th allocation from now fails ONCE (whichever thread makes it), then the seam is disarmed;
+ *     n <= 0 disarms.  real = 0: the failure is injected -- hipErrorOutOfMemory without a call into the runtime.  real != 0: the
+ *     runtime itself is made to fail, by a request for 2^60 bytes, so that its own error state is that of a real failure.
+ *     The caller sees what any failed allocation gives: FREDDY_E_NOMEM from the entry point that made it.
+ *   alloc_track(on): on != 0 starts tracking from an EMPTY live set (what was allocated before is unknown to it and never
+ *     counted); 0 stops it and drops the set.
+ *   alloc_stats(out, out_size): at most out_size bytes of the record; returns the number written.  calls = allocations requested
+ *     since the library was loaded, failed = those that returned an error; live / live_bytes = allocations made while tracking
+ *     and not yet freed; digest = a 64-bit value that depends on the live set {(address, bytes)} alone, not on the order in
+ *     which it came about (0 when it is empty). */
+typedef struct freddy_alloc_stats {
+  int64_t calls, failed, live, live_bytes;
+  uint64_t digest;
+} freddy_alloc_stats;
+int freddy_gpu_debug_alloc_fail_nth(int64_t n, int32_t real);
+int freddy_gpu_debug_alloc_track(int32_t on);
+int freddy_gpu_debug_alloc_stats(freddy_alloc_stats* out, size_t out_size);
 
 /* ABI version of the library: bumped whenever a struct of this header grows or an entry point changes meaning.  A host
  * compares it with the FREDDY_GPU_ABI_VERSION it was compiled against before its first other call into the library

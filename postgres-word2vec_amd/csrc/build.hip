@@ -38,28 +38,28 @@ static int encode_impl(const freddy_encode_desc* t, int device, const float* vec
   hipStream_t s = nullptr;
   auto cleanup = [&] {
     void* ptrs[] = {d_cbT, d_cT, d_coarse, d_vec, d_res, d_cell, d_codes, d_far};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (void* p : ptrs) if (p) (void)dev_free(p);
     if (s) (void)hipStreamDestroy(s);
   };
 #define ENC_TRY(expr)                                                                          \
   do {                                                                                         \
     hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) { cleanup(); return fail(FREDDY_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } \
+    if (e_ != hipSuccess) { cleanup(); return fail(e_ == hipErrorOutOfMemory ? FREDDY_E_NOMEM : FREDDY_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } \
   } while (0)
   ENC_TRY(hipStreamCreate(&s));
-  ENC_TRY(hipMalloc((void**)&d_cbT, sizeof(float) * cbT.size()));
-  ENC_TRY(hipMalloc((void**)&d_vec, sizeof(float) * (size_t)chunk * d));
-  ENC_TRY(hipMalloc((void**)&d_codes, sizeof(int16_t) * (size_t)chunk * m));
+  ENC_TRY(dev_malloc((void**)&d_cbT, sizeof(float) * cbT.size()));
+  ENC_TRY(dev_malloc((void**)&d_vec, sizeof(float) * (size_t)chunk * d));
+  ENC_TRY(dev_malloc((void**)&d_codes, sizeof(int16_t) * (size_t)chunk * m));
   ENC_TRY(hipMemcpyAsync(d_cbT, cbT.data(), sizeof(float) * cbT.size(), hipMemcpyHostToDevice, s));
   if (n_too_far) {
-    ENC_TRY(hipMalloc((void**)&d_far, sizeof(int32_t)));
+    ENC_TRY(dev_malloc((void**)&d_far, sizeof(int32_t)));
     ENC_TRY(hipMemsetAsync(d_far, 0, sizeof(int32_t), s));
   }
   if (C) {
-    ENC_TRY(hipMalloc((void**)&d_cT, sizeof(float) * cT.size()));
-    ENC_TRY(hipMalloc((void**)&d_coarse, sizeof(float) * (size_t)C * d));
-    ENC_TRY(hipMalloc((void**)&d_res, sizeof(float) * (size_t)chunk * d));
-    ENC_TRY(hipMalloc((void**)&d_cell, sizeof(int32_t) * (size_t)chunk));
+    ENC_TRY(dev_malloc((void**)&d_cT, sizeof(float) * cT.size()));
+    ENC_TRY(dev_malloc((void**)&d_coarse, sizeof(float) * (size_t)C * d));
+    ENC_TRY(dev_malloc((void**)&d_res, sizeof(float) * (size_t)chunk * d));
+    ENC_TRY(dev_malloc((void**)&d_cell, sizeof(int32_t) * (size_t)chunk));
     ENC_TRY(hipMemcpyAsync(d_cT, cT.data(), sizeof(float) * cT.size(), hipMemcpyHostToDevice, s));
     ENC_TRY(hipMemcpyAsync(d_coarse, t->coarse, sizeof(float) * (size_t)C * d, hipMemcpyHostToDevice, s));
   }
@@ -156,19 +156,19 @@ extern "C" int freddy_gpu_kmeans(int device, const float* vectors, int64_t n, in
   int rc = FREDDY_OK;
   auto cleanup = [&] {
     void* ptrs[] = {d_vec, d_cent, d_centT, d_assign};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (void* p : ptrs) if (p) (void)dev_free(p);
     if (s) (void)hipStreamDestroy(s);
   };
 #define KM_TRY(expr)                                                                           \
   do {                                                                                         \
     hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) { cleanup(); return fail(FREDDY_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } \
+    if (e_ != hipSuccess) { cleanup(); return fail(e_ == hipErrorOutOfMemory ? FREDDY_E_NOMEM : FREDDY_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } \
   } while (0)
   KM_TRY(hipStreamCreate(&s));
-  KM_TRY(hipMalloc((void**)&d_vec, sizeof(float) * (size_t)n * d));
-  KM_TRY(hipMalloc((void**)&d_cent, sizeof(float) * (size_t)k * d));
-  KM_TRY(hipMalloc((void**)&d_centT, sizeof(float) * (size_t)kpad * d));
-  KM_TRY(hipMalloc((void**)&d_assign, sizeof(int32_t) * (size_t)n));
+  KM_TRY(dev_malloc((void**)&d_vec, sizeof(float) * (size_t)n * d));
+  KM_TRY(dev_malloc((void**)&d_cent, sizeof(float) * (size_t)k * d));
+  KM_TRY(dev_malloc((void**)&d_centT, sizeof(float) * (size_t)kpad * d));
+  KM_TRY(dev_malloc((void**)&d_assign, sizeof(int32_t) * (size_t)n));
   KM_TRY(hipMemcpyAsync(d_vec, vectors, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, s));
   KM_TRY(hipMemcpyAsync(d_cent, init.data(), sizeof(float) * init.size(), hipMemcpyHostToDevice, s));
   const float inf = std::numeric_limits<float>::infinity();

@@ -109,14 +109,14 @@ void free_index(freddy_gpu_index* ix) {
   if (ix->shadow_of) {   // a PQ table's IVF-shaped view: its own arrays only (packed, codebook tables and the stream are the owner's)
     DevBuf* own[] = {&ix->v_coarse, &ix->v_list_off, &ix->v_blk_off, &ix->v_blk_cell, &ix->v_pos, &ix->v_rterm};
     for (DevBuf* b : own) b->release();
-    if (ix->viol) (void)hipFree(ix->viol);
+    if (ix->viol) (void)dev_free(ix->viol);
     delete ix;
     return;
   }
   if (ix->pq_shadow) { free_index(ix->pq_shadow); ix->pq_shadow = nullptr; }
   if (ix->pq_sub_view) { free_index(ix->pq_sub_view); ix->pq_sub_view = nullptr; }
   void* ptrs[] = {ix->xb, ix->coarse, ix->coarseT, ix->coarseP, ix->coarseH, ix->cn2, ix->cbT, ix->cbP, ix->cbR, ix->rterm, ix->pmax, ix->cmaxp, ix->cbF, ix->viol, ix->blk_cell, ix->list_off, ix->blk_off, ix->packed, ix->pos, ix->ids, ix->packed8_own ? ix->packed8 : nullptr};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
+  for (void* p : ptrs) if (p) (void)dev_free(p);
   join_free(&ix->join);
   for (auto& kv : ix->prof)
     for (auto& ev : kv.second.open) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -260,11 +260,16 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   return FREDDY_OK;
 }
 
+// A handle a mutation left half-done answers no search: its arrays are neither the old table's nor the new one's.
+int refuse_poisoned(const freddy_gpu_index* ix) {
+  return ix->poisoned ? fail(FREDDY_E_HIP, "this handle holds a table that is neither the old nor the new one, or its devices hold different tables (a mutation failed part-way): unpin it and pin again") : 0;
+}
+
 int check_search_args(const freddy_gpu_index* ix, int kind, const void* q, int Q, int k, const void* oi,
                              const void* od) {
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   if (ix->kind != kind) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
-  if (ix->poisoned) return fail(FREDDY_E_HIP, "this handle's devices hold different tables (an append / codebook update failed part-way): unpin it and pin again");
+  if (int rc = refuse_poisoned(ix)) return rc;
   if (Q < 0 || k <= 0) return fail(FREDDY_E_ARG, "Q must be >= 0 and k > 0");
   if (Q > 0 && (!q || !oi || !od)) return fail(FREDDY_E_ARG, "NULL buffer");
   if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
@@ -275,12 +280,33 @@ extern "C" int freddy_gpu_host_alloc(void** out, size_t bytes) {
   choose_hw_queues(-1);   // (as open_device: this call may be the process's first HIP call; -1: the device is not known here -- every registered backend counts)
   if (!out) return fail(FREDDY_E_ARG, "NULL argument");
   *out = nullptr;
-  if (hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) { *out = nullptr; return fail(FREDDY_E_NOMEM, "pinned host allocation of %zu bytes failed", bytes); }
+  if (host_malloc(out, bytes ? bytes : 1) != hipSuccess) { *out = nullptr; return fail(FREDDY_E_NOMEM, "pinned host allocation of %zu bytes failed", bytes); }
   return FREDDY_OK;
 }
 extern "C" int freddy_gpu_host_free(void* p) {
-  if (p) HIP_TRY(hipHostFree(p));
+  if (p) HIP_TRY(host_free(p));
   return FREDDY_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// the allocation seam's switches (alloc_hook.h; internal.h: the wrappers every allocation goes through)
+// ---------------------------------------------------------------------------------------
+extern "C" int freddy_gpu_debug_alloc_fail_nth(int64_t n, int32_t real) {
+  freddy::alloc_hook::fail_nth(n, real);
+  return FREDDY_OK;
+}
+extern "C" int freddy_gpu_debug_alloc_track(int32_t on) {
+  freddy::alloc_hook::track(on);
+  return FREDDY_OK;
+}
+extern "C" int freddy_gpu_debug_alloc_stats(freddy_alloc_stats* out, size_t out_size) {
+  if (!out) return fail(FREDDY_E_ARG, "NULL argument");
+  const freddy::alloc_hook::Stats s = freddy::alloc_hook::stats();
+  freddy_alloc_stats full;
+  full.calls = s.calls; full.failed = s.failed; full.live = s.live; full.live_bytes = s.live_bytes; full.digest = s.digest;
+  const size_t n = std::min(out_size, sizeof(full));
+  memcpy(out, &full, n);
+  return (int)n;
 }
 
 extern "C" int freddy_gpu_replica_count(const freddy_gpu_index_t* ix) { return ix ? 1 + (int)ix->replicas.size() : 0; }

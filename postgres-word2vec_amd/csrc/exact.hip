@@ -52,7 +52,10 @@ int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n, const std::vect
   const size_t need = (size_t)strips * T * 2 * 64 * 16;
   if (need > ix->exf_xf.cap) {
     DevBuf bigger;
-    if (bigger.ensure(need)) { ix->exf_ok = false; return 0; }   // (no room for the copy: the all-exact kernels stay)
+    // (no room for the copy is the call's failure, as any other allocation's: a handle that silently kept the all-exact kernels
+    // would differ from a fresh pin of its table.  The statistics above have moved already: a mutation that gets this answer
+    // poisons the handle, a pin fails)
+    if (bigger.ensure(need)) return fail(FREDDY_E_NOMEM, "device allocation of %zu bytes failed (the exact filter's copy of the rows)", need);
     if (ix->exf_xf.p && strip0 > 0) HIP_TRY(hipMemcpy(bigger.p, ix->exf_xf.p, (size_t)strip0 * T * 2 * 64 * 16, hipMemcpyDeviceToDevice));
     ix->bytes += (int64_t)bigger.cap - (int64_t)ix->exf_xf.cap;
     ix->exf_xf.release();
@@ -146,7 +149,7 @@ extern "C" int freddy_gpu_pin_vectors(const freddy_vec_desc* t, int device, fred
   if (!rc) {
     ix->n_blocks = (t->N + 63) / 64;
     const size_t xb_bytes = sizeof(float) * (size_t)std::max<int64_t>(ix->n_blocks, 1) * t->d * 64;
-    if (hipMalloc((void**)&ix->xb, xb_bytes) != hipSuccess) rc = fail(FREDDY_E_NOMEM, "device allocation of %zu bytes failed", xb_bytes);
+    if (dev_malloc((void**)&ix->xb, xb_bytes) != hipSuccess) rc = fail(FREDDY_E_NOMEM, "device allocation of %zu bytes failed", xb_bytes);
     else ix->bytes += (int64_t)xb_bytes;
     if (!rc && upload(&ix->ids, t->ids, (size_t)t->N, &ix->bytes)) rc = fail(FREDDY_E_NOMEM, "device allocation failed");
     // row-major rows go up in slices and are re-blocked on the device
@@ -303,6 +306,7 @@ extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* quer
                                        const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_sim) {
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(ix)) return rc;
   if (Q < 0 || k <= 0 || n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad sizes");
   if (Q > 0 && (!queries || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
   if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
@@ -407,6 +411,7 @@ extern "C" int freddy_gpu_exact_join(freddy_gpu_index_t* ix, const float* querie
   if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(ix)) return rc;
   ix->exj_stats[0] = ix->exj_stats[1] = ix->exj_stats[2] = 0;
   if (Q == 0) return FREDDY_OK;
   // the target ids resolved once: the filter and every all-exact answer (fall-back, redo) share the rows
@@ -578,6 +583,7 @@ extern "C" int freddy_gpu_exact_analogy(freddy_gpu_index_t* ix, int32_t method, 
   if (k > AN_MAXK) return fail(FREDDY_E_LIMIT, "k=%d exceeds the exact analogy's limit of %d", k, AN_MAXK);
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(ix)) return rc;
   const int M = method == FREDDY_ANALOGY_3COSMUL ? 3 : 1;
   const int d = ix->d;
   ix->an_stats[0] = ix->an_stats[1] = ix->an_stats[2] = 0;
@@ -668,6 +674,8 @@ extern "C" int freddy_gpu_last_analogy_stats(const freddy_gpu_index_t* ix, int64
 static int pv_check_handles(const freddy_gpu_index* ann, int kind, const freddy_gpu_index* vecs, const char* what) {
   if (!ann || !vecs) return fail(FREDDY_E_ARG, "NULL index");
   if (ann->kind != kind || vecs->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(ann)) return rc;
+  if (int rc = refuse_poisoned(vecs)) return rc;
   if (!ann->replicas.empty())
     return fail(FREDDY_E_ARG, "%s does not take a handle with replicas (%d devices): the vectors are pinned on one device", what, 1 + (int)ann->replicas.size());
   if (vecs->device != ann->device) return fail(FREDDY_E_ARG, "the vectors are pinned on device %d, the index on device %d", vecs->device, ann->device);
@@ -835,6 +843,7 @@ extern "C" int freddy_gpu_exact_assign(freddy_gpu_index_t* ix, const float* quer
   if (Q > AS_MAX_Q) return fail(FREDDY_E_LIMIT, "Q=%d exceeds this build's limit of %d queries per assign call", Q, AS_MAX_Q);
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(ix)) return rc;
   if (Q == 0 || n_targets == 0) return FREDDY_OK;
   HIP_TRY(hipSetDevice(ix->device));
   Workspace* ws = workspace_for(ix, ix->stream);

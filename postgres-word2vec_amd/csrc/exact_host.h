@@ -38,7 +38,7 @@ static ExfPrepArgs exf_prep_args(const freddy_gpu_index* ix, const float* querie
 // the self-check counters the refine kernels write (allocated by the handle's first filter + refine call)
 static int ensure_viol(freddy_gpu_index* ix) {
   if (ix->viol) return 0;
-  HIP_TRY(hipMalloc((void**)&ix->viol, 4 * sizeof(int32_t)));
+  HIP_TRY(dev_malloc((void**)&ix->viol, 4 * sizeof(int32_t)));
   HIP_TRY(hipMemset(ix->viol, 0, 4 * sizeof(int32_t)));
   return 0;
 }

@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "hip_alloc.h"    // dev_malloc / dev_free / host_malloc / host_free: the only callers of the runtime's allocation functions
 #include "join_index.h"
 #include "pinned.h"
 
@@ -44,8 +45,8 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
   do {                                                                                      \
     hipError_t e_ = (expr);                                                                 \
     if (e_ != hipSuccess)                                                                   \
-      return fail(FREDDY_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),      \
-                  __FILE__, __LINE__);                                                      \
+      return fail(e_ == hipErrorOutOfMemory ? FREDDY_E_NOMEM : FREDDY_E_HIP, "%s failed: %s (%s:%d)", #expr,   \
+                  hipGetErrorString(e_), __FILE__, __LINE__);                               \
   } while (0)
 
 enum { KIND_PQ = 1, KIND_IVF = 2, KIND_IVPQ = 3, KIND_VEC = 4 };
@@ -103,15 +104,15 @@ struct DevBuf {
   size_t cap = 0;
   int ensure(size_t bytes) {
     if (bytes <= cap) return 0;
-    if (p) (void)hipFree(p);
+    if (p) (void)dev_free(p);
     p = nullptr;
     cap = 0;
     size_t want = bytes + bytes / 8 + 256;
-    if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return -1; }
+    if (dev_malloc(&p, want) != hipSuccess) { p = nullptr; return -1; }
     cap = want;
     return 0;
   }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  void release() { if (p) (void)dev_free(p); p = nullptr; cap = 0; }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
@@ -310,13 +311,14 @@ template <class T>
 static int upload(T** dst, const T* src, size_t n, int64_t* bytes) {
   *dst = nullptr;
   size_t sz = sizeof(T) * (n ? n : 1);
-  if (hipMalloc((void**)dst, sz) != hipSuccess) return -1;
+  if (dev_malloc((void**)dst, sz) != hipSuccess) return -1;
   if (n && hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice) != hipSuccess) return -2;
   if (bytes) *bytes += (int64_t)sz;
   return 0;
 }
 
 void free_index(freddy_gpu_index* ix);
+int refuse_poisoned(const freddy_gpu_index* ix);   // != 0 (FREDDY_E_HIP, "unpin it and pin again"): a mutation failed part-way on this handle; every entry point that reads its tables asks first
 int check_search_args(const freddy_gpu_index* ix, int kind, const void* q, int Q, int k, const void* oi, const void* od);
 
 // ids -> rows of a table with ascending ids (h_ids): the row of one id (-1: absent), and the rows of "id IN (...)" -- unknown

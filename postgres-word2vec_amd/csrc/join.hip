@@ -40,7 +40,7 @@ static int join_pin(JoinIndex* j, const freddy_ivpq_desc* t, int64_t* bytes) {
   j->h_ids.assign(t->ids, t->ids + t->N);
   j->h_cell.assign(t->coarse_id, t->coarse_id + t->N);
   j->h_stats.assign(t->stats, t->stats + j->cells + 1);
-  if (hipMalloc((void**)&j->markbits, sizeof(uint32_t) * (size_t)((t->N + 31) / 32 + 1)) != hipSuccess)
+  if (dev_malloc((void**)&j->markbits, sizeof(uint32_t) * (size_t)((t->N + 31) / 32 + 1)) != hipSuccess)
     return join_fail(FREDDY_E_NOMEM, "device allocation failed while pinning the ivpq tables");
   j->ids_affine = t->N > 0 && (int64_t)t->ids[t->N - 1] - t->ids[0] == t->N - 1;   // strictly ascending => consecutive
   return 0;
@@ -75,6 +75,7 @@ extern "C" int freddy_gpu_knn_join(freddy_gpu_index_t* ix, const float* queries,
                                    int32_t* out_ids, float* out_dist, int32_t* iterations_out) {
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   if (ix->kind != KIND_IVPQ) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(ix)) return rc;
   if (Q < 0 || k <= 0 || n_targets < 0) return fail(FREDDY_E_ARG, "bad sizes");
   if (Q > 0 && (!queries || !out_ids || !out_dist)) return fail(FREDDY_E_ARG, "NULL buffer");
   if (n_targets > 0 && !target_ids) return fail(FREDDY_E_ARG, "NULL target ids");
@@ -96,6 +97,7 @@ static constexpr int64_t STAT_ROWS_PASS = 1 << 30;   // rows per launch when eve
 static int stat_handle(const freddy_gpu_index* ix) {
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   if (ix->kind != KIND_IVPQ) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(ix)) return rc;
   return 0;
 }
 

@@ -42,7 +42,7 @@ static inline int join_fail(int code, const char* fmt, ...) {
   do {                                                                                          \
     hipError_t e_ = (expr);                                                                     \
     if (e_ != hipSuccess)                                                                       \
-      return join_fail(FREDDY_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return join_fail(e_ == hipErrorOutOfMemory ? FREDDY_E_NOMEM : FREDDY_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
 // The device workspaces of a call (JoinIndex::w), grown on demand and kept between calls.  Every one is a buffer of its own:
@@ -113,11 +113,11 @@ template <class T>
 static inline int join_buf(JoinIndex* j, JoinSlot slot, size_t count, T** out) {
   const size_t bytes = sizeof(T) * count;
   if (bytes > j->wcap[slot]) {
-    if (j->w[slot]) (void)hipFree(j->w[slot]);
+    if (j->w[slot]) (void)dev_free(j->w[slot]);
     j->w[slot] = nullptr;
     j->wcap[slot] = 0;
     size_t want = bytes + bytes / 4 + 256;
-    if (hipMalloc(&j->w[slot], want) != hipSuccess) return join_fail(FREDDY_E_NOMEM, "workspace allocation of %zu bytes failed", want);
+    if (dev_malloc(&j->w[slot], want) != hipSuccess) return join_fail(FREDDY_E_NOMEM, "workspace allocation of %zu bytes failed", want);
     j->wcap[slot] = want;
   }
   *out = static_cast<T*>(j->w[slot]);
@@ -126,9 +126,9 @@ static inline int join_buf(JoinIndex* j, JoinSlot slot, size_t count, T** out) {
 
 static inline void join_free(JoinIndex* j) {
   void* ptrs[] = {j->cbT, j->coarseT, j->ids, j->codes, j->vectors, j->cell, j->markbits, j->d_stats};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
+  for (void* p : ptrs) if (p) (void)dev_free(p);
   for (PinnedBuf* b : {&j->h_q, &j->h_sum, &j->h_tl, &j->h_stat}) b->release();
-  for (int i = 0; i < JW_SLOTS; ++i) if (j->w[i]) (void)hipFree(j->w[i]);
+  for (int i = 0; i < JW_SLOTS; ++i) if (j->w[i]) (void)dev_free(j->w[i]);
   if (j->ev0) (void)hipEventDestroy(j->ev0);
   if (j->ev1) (void)hipEventDestroy(j->ev1);
   if (j->ev_replay) (void)hipEventDestroy(j->ev_replay);

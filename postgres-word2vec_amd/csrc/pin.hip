@@ -142,20 +142,37 @@ __global__ __launch_bounds__(256) void pack8_kernel(const uint32_t* __restrict__
   const uint32_t p0 = packed[((size_t)b * 6 + 2 * t) * 64 + lane], p1 = packed[((size_t)b * 6 + 2 * t + 1) * 64 + lane];
   packed8[i] = (p0 & 0xffu) | (((p0 >> 16) & 0xffu) << 8) | ((p1 & 0xffu) << 16) | (((p1 >> 16) & 0xffu) << 24);
 }
-// (Re)build the one-byte code array of a handle whose codes fit a byte (K <= 256, m = 12: the cell-grouped scans' shape).
+// The one-byte code array of a block array `packed` of a handle whose codes fit a byte (K <= 256, m = 12: the cell-grouped scans'
+// shape), built BESIDE whatever the handle holds: *out stays NULL (and *out_bytes 0) for every other shape.  The handle is not
+// touched; a failure leaves nothing behind.  (Until the allocation seam a failed allocation here was swallowed -- "the int16
+// layout serves" -- so that a handle could silently differ from a fresh pin of its table; now it is the call's failure.)
+static int make_packed8(const freddy_gpu_index* ix, const uint32_t* packed, int64_t n_blocks, uint32_t** out, int64_t* out_bytes) {
+  *out = nullptr; *out_bytes = 0;
+  if (ix->K > 256 || ix->m != 12 || ix->M2 != 6 || !packed || n_blocks <= 0) return 0;
+  const size_t bytes = sizeof(uint32_t) * (size_t)n_blocks * 3 * 64;
+  if (dev_malloc(out, bytes) != hipSuccess) { *out = nullptr; return fail(FREDDY_E_NOMEM, "device allocation of %zu bytes failed (one-byte codes)", bytes); }
+  const int64_t n = n_blocks * 3 * 64;
+  hipLaunchKernelGGL(pack8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ix->stream, packed, *out, n_blocks);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess) {
+    (void)dev_free(*out); *out = nullptr;
+    return fail(FREDDY_E_HIP, "building the one-byte codes failed");
+  }
+  *out_bytes = (int64_t)bytes;
+  return 0;
+}
+// the handle's array gives way to `p8` (NULL: none)
+static void install_packed8(freddy_gpu_index* ix, uint32_t* p8, int64_t bytes) {
+  if (ix->packed8 && ix->packed8_own) { (void)dev_free(ix->packed8); ix->bytes -= ix->packed8_bytes; }
+  ix->packed8 = p8; ix->packed8_own = p8 != nullptr; ix->packed8_bytes = bytes;
+  ix->bytes += bytes;
+}
+// (Re)build it from the handle's own block array (pin time; update_rows, which rewrites that array in place): the old copy stays
+// until the new one is complete.
 static int build_packed8(freddy_gpu_index* ix) {
-  if (ix->packed8 && ix->packed8_own) { (void)hipFree(ix->packed8); ix->bytes -= ix->packed8_bytes; }   // (rebuilt after append_rows: the old copy no longer counts)
-  ix->packed8 = nullptr; ix->packed8_own = false; ix->packed8_bytes = 0;
-  if (ix->K > 256 || ix->m != 12 || ix->M2 != 6 || !ix->packed || ix->n_blocks <= 0) return 0;
-  const size_t bytes = sizeof(uint32_t) * (size_t)ix->n_blocks * 3 * 64;
-  if (hipMalloc((void**)&ix->packed8, bytes) != hipSuccess) { ix->packed8 = nullptr; return 0; }   // (no room: the int16 layout serves)
-  ix->packed8_own = true;
-  ix->packed8_bytes = (int64_t)bytes;
-  ix->bytes += (int64_t)bytes;
-  const int64_t n = ix->n_blocks * 3 * 64;
-  hipLaunchKernelGGL(pack8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ix->stream, ix->packed, ix->packed8, ix->n_blocks);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(ix->stream));
+  uint32_t* p8 = nullptr;
+  int64_t bytes = 0;
+  if (int rc = make_packed8(ix, ix->packed, ix->n_blocks, &p8, &bytes)) return rc;
+  install_packed8(ix, p8, bytes);
   return 0;
 }
 
@@ -163,21 +180,28 @@ static int build_packed8(freddy_gpu_index* ix) {
 // LUT kernel, the paired layout of the exact fused scan, and -- for the filter + refine scan -- the row-major
 // copy and the norm bounds.  (Re)built at pin time and by freddy_gpu_update_codebook; the row terms follow
 // in refresh_row_terms once the rows are in place.
-// Everything that is derived from the codebook.  The new tables are built beside the old ones and swapped in only when
-// every upload has succeeded (freddy_gpu_update_codebook on a live handle: a failed call leaves the handle as it was).
+// Everything that is derived from the codebook.  The new tables -- and, with rows in place (with_row_terms:
+// freddy_gpu_update_codebook on a live ivf handle), the row terms that follow from them -- are built beside the old ones and
+// swapped in only when every allocation, upload and launch has succeeded: a failed call leaves the handle as it was.
 static int derive_codebook_tables_into(freddy_gpu_index* ix, const float* codebook);
-static int derive_codebook_tables(freddy_gpu_index* ix, const float* codebook) {
+static int make_row_terms(const freddy_gpu_index* ix, const uint32_t* packed, const int32_t* blk_cell, int64_t n_blocks, const float* cbR, float** out, int64_t* out_bytes);
+static void install_row_terms(freddy_gpu_index* ix, float* rterm, int64_t bytes);
+static int derive_codebook_tables(freddy_gpu_index* ix, const float* codebook, bool with_row_terms = false) {
   float* const old[] = {ix->cbT, ix->cbP, ix->cbR, ix->pmax, ix->cmaxp, ix->cbF};
   const int64_t bytes_before = ix->bytes;
   ix->cbT = ix->cbP = ix->cbR = ix->pmax = ix->cmaxp = ix->cbF = nullptr;
-  const int rc = derive_codebook_tables_into(ix, codebook);
+  int rc = derive_codebook_tables_into(ix, codebook);
+  float* rterm = nullptr;
+  int64_t rterm_bytes = 0;
+  if (!rc && with_row_terms) rc = make_row_terms(ix, ix->packed, ix->blk_cell, ix->n_blocks, ix->cbR, &rterm, &rterm_bytes);
   if (rc) {   // put the old tables back
     float* const fresh[] = {ix->cbT, ix->cbP, ix->cbR, ix->pmax, ix->cmaxp, ix->cbF};
-    for (float* p : fresh) if (p) (void)hipFree(p);
+    for (float* p : fresh) if (p) (void)dev_free(p);
     ix->cbT = old[0]; ix->cbP = old[1]; ix->cbR = old[2]; ix->pmax = old[3]; ix->cmaxp = old[4]; ix->cbF = old[5];
     ix->bytes = bytes_before;
     return rc;
   }
+  if (with_row_terms) install_row_terms(ix, rterm, rterm_bytes);
   int64_t old_bytes = 0;
   if (old[0]) old_bytes += (int64_t)sizeof(float) * ix->m * ix->S * ix->K;
   if (old[1]) old_bytes += (int64_t)sizeof(float) * ix->m * (((ix->S + 3) & ~3) / 4) * FUSED_T * 8;
@@ -186,7 +210,7 @@ static int derive_codebook_tables(freddy_gpu_index* ix, const float* codebook) {
   if (old[4]) old_bytes += (int64_t)sizeof(float) * ix->m;
   if (old[5]) old_bytes += (int64_t)sizeof(float) * ix->m * 8 * 7 * 64 * 8;
   ix->bytes -= old_bytes;       // (the footprint changes by the difference, not by a second copy)
-  for (float* p : old) if (p) (void)hipFree(p);
+  for (float* p : old) if (p) (void)dev_free(p);
   if (ix->kind == KIND_PQ) {    // views of the flat table are rebuilt from the new tables on next use
     if (ix->pq_shadow) { free_index(ix->pq_shadow); ix->pq_shadow = nullptr; }
     if (ix->pq_sub_view) { free_index(ix->pq_sub_view); ix->pq_sub_view = nullptr; }
@@ -287,22 +311,37 @@ static int derive_codebook_tables_into(freddy_gpu_index* ix, const float* codebo
   return 0;
 }
 
-// rterm[slot] for every row slot of the pinned lists (the (cell, row) part of the filter's cheap distance)
-static int refresh_row_terms(freddy_gpu_index* ix) {
-  if (ix->rterm) { (void)hipFree(ix->rterm); ix->rterm = nullptr; }
-  ix->bytes -= ix->rterm_bytes;   // (rebuilt after append_rows / update_codebook: the old array no longer counts)
-  ix->rterm_bytes = 0;
-  if (!ix->cbR) return 0;
-  const int64_t n_slots = std::max<int64_t>(ix->n_blocks, 1) * 64;
-  if (hipMalloc((void**)&ix->rterm, sizeof(float) * (size_t)n_slots) != hipSuccess) return fail(FREDDY_E_NOMEM, "device allocation failed");
-  ix->rterm_bytes = (int64_t)sizeof(float) * n_slots;
-  ix->bytes += ix->rterm_bytes;
-  if (ix->n_blocks > 0) {
-    hipLaunchKernelGGL(row_term_kernel, dim3((unsigned)((ix->n_blocks * 64 + 255) / 256)), dim3(256), 0, ix->stream, ix->packed,
-                       ix->blk_cell, ix->coarse, ix->cbR, ix->rterm, ix->n_blocks * 64, ix->M2, ix->d, ix->m, ix->K, ix->S);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess)
+// rterm[slot] for every row slot of the lists `packed` / `blk_cell` (the (cell, row) part of the filter's cheap distance) under the
+// row-major codebook cbR, built BESIDE what the handle holds: *out stays NULL without cbR (no filter + refine tables).  The handle
+// is not touched; a failure leaves nothing behind.
+static int make_row_terms(const freddy_gpu_index* ix, const uint32_t* packed, const int32_t* blk_cell, int64_t n_blocks, const float* cbR, float** out, int64_t* out_bytes) {
+  *out = nullptr; *out_bytes = 0;
+  if (!cbR) return 0;
+  const int64_t n_slots = std::max<int64_t>(n_blocks, 1) * 64;
+  if (dev_malloc(out, sizeof(float) * (size_t)n_slots) != hipSuccess) { *out = nullptr; return fail(FREDDY_E_NOMEM, "device allocation failed (row terms)"); }
+  if (n_blocks > 0) {
+    hipLaunchKernelGGL(row_term_kernel, dim3((unsigned)((n_blocks * 64 + 255) / 256)), dim3(256), 0, ix->stream, packed,
+                       blk_cell, ix->coarse, cbR, *out, n_blocks * 64, ix->M2, ix->d, ix->m, ix->K, ix->S);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess) {
+      (void)dev_free(*out); *out = nullptr;
       return fail(FREDDY_E_HIP, "building the row terms failed");
+    }
   }
+  *out_bytes = (int64_t)sizeof(float) * n_slots;
+  return 0;
+}
+// the handle's row terms give way to `rterm` (NULL: none)
+static void install_row_terms(freddy_gpu_index* ix, float* rterm, int64_t bytes) {
+  if (ix->rterm) (void)dev_free(ix->rterm);
+  ix->bytes += bytes - ix->rterm_bytes;
+  ix->rterm = rterm; ix->rterm_bytes = bytes;
+}
+// from the handle's own arrays (pin time; update_rows, which rewrites them in place): the old terms stay until the new ones are complete
+static int refresh_row_terms(freddy_gpu_index* ix) {
+  float* rterm = nullptr;
+  int64_t bytes = 0;
+  if (int rc = make_row_terms(ix, ix->packed, ix->blk_cell, ix->n_blocks, ix->cbR, &rterm, &bytes)) return rc;
+  install_row_terms(ix, rterm, bytes);
   return 0;
 }
 
@@ -454,7 +493,7 @@ extern "C" int freddy_gpu_pin_ivf(const freddy_ivf_desc* t, int device, freddy_g
       }
       if (rc) {} else
       if (upload(&ix->coarseP, cP.data(), cP.size(), &ix->bytes) || upload(&ix->cn2, cn2.data(), cn2.size(), &ix->bytes) ||
-          hipMalloc((void**)&ix->viol, 4 * sizeof(int32_t)) != hipSuccess || hipMemset(ix->viol, 0, 4 * sizeof(int32_t)) != hipSuccess)
+          dev_malloc((void**)&ix->viol, 4 * sizeof(int32_t)) != hipSuccess || hipMemset(ix->viol, 0, 4 * sizeof(int32_t)) != hipSuccess)
         rc = fail(FREDDY_E_NOMEM, "device allocation failed");
     }
     if (!rc) { ix->h_coarse.assign(t->coarse, t->coarse + (size_t)t->C * t->d); rc = derive_codebook_tables(ix, t->codebook); }
@@ -523,22 +562,79 @@ __global__ __launch_bounds__(256) void place_vectors_kernel(const float* __restr
   for (int dim = threadIdx.x; dim < d; dim += 256) xb[((r >> 6) * d + dim) * 64 + (r & 63)] = src[(size_t)i * d + dim];
 }
 
+// A longer copy of a device array BESIDE it: the old_n elements of `arr`, then append_n elements from the host.  *fresh is the
+// caller's to swap in (swap_grown) or free; -1: no memory, -2: a copy failed -- nothing is left behind either way.
 template <class T>
-static int grow_device_array(T** arr, size_t old_n, size_t new_n, const T* append_host, size_t append_n, int64_t* bytes) {
-  T* fresh = nullptr;
-  if (hipMalloc((void**)&fresh, sizeof(T) * std::max<size_t>(new_n, 1)) != hipSuccess) return -1;
-  if (old_n && hipMemcpy(fresh, *arr, sizeof(T) * old_n, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(fresh); return -2; }
-  if (append_n && hipMemcpy(fresh + old_n, append_host, sizeof(T) * append_n, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(fresh); return -2; }
+static int grown_copy(const T* arr, size_t old_n, size_t new_n, const T* append_host, size_t append_n, T** fresh) {
+  *fresh = nullptr;
+  if (dev_malloc(fresh, sizeof(T) * std::max<size_t>(new_n, 1)) != hipSuccess) { *fresh = nullptr; return -1; }
+  if ((old_n && hipMemcpy(*fresh, arr, sizeof(T) * old_n, hipMemcpyDeviceToDevice) != hipSuccess) ||
+      (append_n && hipMemcpy(*fresh + old_n, append_host, sizeof(T) * append_n, hipMemcpyHostToDevice) != hipSuccess)) {
+    (void)dev_free(*fresh); *fresh = nullptr;
+    return -2;
+  }
+  return 0;
+}
+template <class T>
+static void swap_grown(T** arr, size_t old_n, size_t new_n, T* fresh, int64_t* bytes) {
   // (the footprint as upload() counts it: an empty array is one element)
   *bytes += (int64_t)(sizeof(T) * std::max<size_t>(new_n, 1)) - (*arr ? (int64_t)(sizeof(T) * std::max<size_t>(old_n, 1)) : 0);
-  if (*arr) (void)hipFree(*arr);
+  if (*arr) (void)dev_free(*arr);
   *arr = fresh;
-  return 0;
+}
+static int grow_failed(int rc) { return rc == -1 ? fail(FREDDY_E_NOMEM, "device allocation failed while appending rows") : fail(FREDDY_E_HIP, "copying the rows failed"); }
+
+// The arrays of a pq / ivf handle that follow its rows -- the block layout, the one-byte codes and (ivf) the row terms -- as
+// append_packed_rows / remove_packed_rows build them BESIDE the pinned ones.  install_layout swaps them in, and only then does the
+// handle change; what is never installed is freed when the record goes out of scope.  So a call that fails before install_layout
+// leaves the handle as it was.
+struct FreshLayout {
+  uint32_t *packed = nullptr, *packed8 = nullptr;
+  int32_t *pos = nullptr, *blk_cell = nullptr, *blk_off = nullptr, *list_off = nullptr;
+  float* rterm = nullptr;
+  int64_t packed8_bytes = 0, rterm_bytes = 0;
+  int64_t n_blocks = 0, N = 0;
+  int max_list_blocks = 0;
+  std::vector<int32_t> h_list_off;
+  bool ready = false;      // complete: install_layout may run (false after a call that found nothing to change)
+  void drop() {
+    void* all[] = {packed, packed8, pos, blk_cell, blk_off, list_off, rterm};
+    for (void* p : all) if (p) (void)dev_free(p);
+    packed = packed8 = nullptr; pos = blk_cell = blk_off = list_off = nullptr; rterm = nullptr;
+    ready = false;
+  }
+  ~FreshLayout() { drop(); }
+};
+// what follows from the fresh block arrays: the one-byte codes, and the row terms of an ivf handle
+static int finish_layout(freddy_gpu_index* ix, FreshLayout& L) {
+  int rc = 0;
+  if (!ix->shadow_of) rc = make_packed8(ix, L.packed, L.n_blocks, &L.packed8, &L.packed8_bytes);
+  if (!rc && ix->kind == KIND_IVF) rc = make_row_terms(ix, L.packed, L.blk_cell, L.n_blocks, ix->cbR, &L.rterm, &L.rterm_bytes);
+  if (rc) L.drop(); else L.ready = true;
+  return rc;
+}
+static void install_layout(freddy_gpu_index* ix, FreshLayout& L) {
+  void* old[] = {ix->packed, ix->pos, ix->blk_cell, ix->blk_off, ix->list_off};
+  for (void* p : old) if (p) (void)dev_free(p);
+  {   // the footprint follows the block count (pack_lists counts packed, pos and blk_cell with one block at least; blk_off and list_off keep their size)
+    const int64_t ob = std::max<int64_t>(ix->n_blocks, 1), nb = std::max<int64_t>(L.n_blocks, 1);
+    ix->bytes += (nb - ob) * (int64_t)(sizeof(uint32_t) * ix->M2 * 64 + sizeof(int32_t) * 64 + sizeof(int32_t));
+  }
+  ix->packed = L.packed; ix->pos = L.pos; ix->blk_cell = L.blk_cell; ix->blk_off = L.blk_off; ix->list_off = L.list_off;
+  ix->n_blocks = L.n_blocks;
+  ix->max_list_blocks = L.max_list_blocks;
+  ix->h_list_off.swap(L.h_list_off);
+  ix->N = L.N;
+  if (!ix->shadow_of) install_packed8(ix, L.packed8, L.packed8_bytes);
+  if (ix->kind == KIND_IVF) install_row_terms(ix, L.rterm, L.rterm_bytes);
+  L.packed = L.packed8 = nullptr; L.pos = L.blk_cell = L.blk_off = L.list_off = nullptr; L.rterm = nullptr;
+  L.ready = false;
 }
 
 // rows of a pq / ivf index: each new row goes to the end of its list; the 64-row block layout is rebuilt on
-// the device (old blocks copied to their new places, new rows written into the free slots behind them)
-static int append_packed_rows(freddy_gpu_index* ix, int n_lists, int64_t n, const int32_t* cell, const int32_t* row_pos, const int16_t* codes) {
+// the device (old blocks copied to their new places, new rows written into the free slots behind them) into L; the handle is
+// not touched
+static int append_packed_rows(freddy_gpu_index* ix, int n_lists, int64_t n, const int32_t* cell, const int32_t* row_pos, const int16_t* codes, FreshLayout& L) {
   const int m = ix->m, M2 = ix->M2;
   std::vector<int32_t> new_list_off((size_t)n_lists + 1, 0), add((size_t)n_lists, 0);
   for (int64_t i = 0; i < n; ++i) {
@@ -578,8 +674,8 @@ static int append_packed_rows(freddy_gpu_index* ix, int n_lists, int64_t n, cons
   int16_t* d_codes = nullptr;
   int64_t junk = 0;
   int rc = 0;
-  if (hipMalloc((void**)&packed, sizeof(uint32_t) * (size_t)std::max<int64_t>(n_new_blocks, 1) * M2 * 64) != hipSuccess ||
-      hipMalloc((void**)&pos, sizeof(int32_t) * (size_t)std::max<int64_t>(n_new_blocks, 1) * 64) != hipSuccess ||
+  if (dev_malloc((void**)&packed, sizeof(uint32_t) * (size_t)std::max<int64_t>(n_new_blocks, 1) * M2 * 64) != hipSuccess ||
+      dev_malloc((void**)&pos, sizeof(int32_t) * (size_t)std::max<int64_t>(n_new_blocks, 1) * 64) != hipSuccess ||
       upload(&d_blk_cell, blk_cell.data(), blk_cell.size(), &junk) || upload(&d_new_blk, new_blk.data(), new_blk.size(), &junk) ||
       upload(&d_list_off, new_list_off.data(), new_list_off.size(), &junk) || upload(&d_slot, slot.data(), slot.size(), &junk) ||
       upload(&d_row_pos, row_pos, (size_t)n, &junk) || upload(&d_codes, codes, (size_t)n * m, &junk))
@@ -592,25 +688,14 @@ static int append_packed_rows(freddy_gpu_index* ix, int n_lists, int64_t n, cons
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "re-blocking the lists failed");
   }
   void* tmp[] = {d_slot, d_row_pos, d_codes};
-  for (void* p : tmp) if (p) (void)hipFree(p);
-  if (rc) {
-    void* fresh[] = {packed, pos, d_blk_cell, d_new_blk, d_list_off};
-    for (void* p : fresh) if (p) (void)hipFree(p);
-    return rc;
-  }
-  void* old[] = {ix->packed, ix->pos, ix->blk_cell, ix->blk_off, ix->list_off};
-  for (void* p : old) if (p) (void)hipFree(p);
-  {   // the footprint follows the block count (pack_lists counts packed, pos and blk_cell with one block at least; blk_off and list_off keep their size)
-    const int64_t ob = std::max<int64_t>(ix->n_blocks, 1), nb = std::max<int64_t>(n_new_blocks, 1);
-    ix->bytes += (nb - ob) * (int64_t)(sizeof(uint32_t) * M2 * 64 + sizeof(int32_t) * 64 + sizeof(int32_t));
-  }
-  ix->packed = packed; ix->pos = pos; ix->blk_cell = d_blk_cell; ix->blk_off = d_new_blk; ix->list_off = d_list_off;
-  ix->n_blocks = n_new_blocks;
-  ix->max_list_blocks = max_blocks;
-  ix->h_list_off = new_list_off;
-  ix->N += n;
-  if (!ix->shadow_of) { if (int rc = build_packed8(ix)) return rc; }
-  return 0;
+  for (void* p : tmp) if (p) (void)dev_free(p);
+  L.packed = packed; L.pos = pos; L.blk_cell = d_blk_cell; L.blk_off = d_new_blk; L.list_off = d_list_off;   // (L frees them if it is never installed)
+  if (rc) { L.drop(); return rc; }
+  L.n_blocks = n_new_blocks;
+  L.max_list_blocks = max_blocks;
+  L.h_list_off = new_list_off;
+  L.N = ix->N + n;
+  return finish_layout(ix, L);
 }
 
 extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const int32_t* ids, const int32_t* coarse_id,
@@ -626,7 +711,7 @@ extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const i
     reps.swap(ix->replicas);
     int rc = freddy_gpu_append_rows(ix, n, ids, coarse_id, codes, vectors);
     reps.swap(ix->replicas);
-    if (rc) { if (rc == FREDDY_E_HIP || rc == FREDDY_E_NOMEM) ix->poisoned = true; return rc; }
+    if (rc) return rc;   // (the primary is as it was, or has poisoned itself: no other device has changed)
     for (freddy_gpu_index* r : ix->replicas)
       if ((rc = freddy_gpu_append_rows(r, n, ids, coarse_id, codes, vectors))) { ix->poisoned = true; return rc; }
     return FREDDY_OK;
@@ -646,18 +731,26 @@ extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const i
       std::vector<int32_t> row_pos((size_t)n);
       for (int64_t i = 0; i < n; ++i) row_pos[(size_t)i] = (int32_t)(ix->N + i);   // flat table: position = row index
       const int64_t old_n = ix->N;
-      if (ix->pq_shadow) { free_index(ix->pq_shadow); ix->pq_shadow = nullptr; }   // (rebuilt by the next batch search)
-      if (int rc = append_packed_rows(ix, 1, n, nullptr, row_pos.data(), codes)) return rc;
-      if (grow_device_array(&ix->ids, (size_t)old_n, (size_t)(old_n + n), ids, (size_t)n, &ix->bytes)) return fail(FREDDY_E_NOMEM, "device allocation failed");
+      // everything is built beside the pinned arrays; the handle changes only once nothing can fail any more
+      FreshLayout L;
+      if (int rc = append_packed_rows(ix, 1, n, nullptr, row_pos.data(), codes, L)) return rc;
+      int32_t* new_ids = nullptr;
+      if (int rc = grown_copy(ix->ids, (size_t)old_n, (size_t)(old_n + n), ids, (size_t)n, &new_ids)) return grow_failed(rc);
+      ix->h_ids.reserve(ix->h_ids.size() + (size_t)n);   // (may throw: before anything has changed)
+      install_layout(ix, L);
+      swap_grown(&ix->ids, (size_t)old_n, (size_t)(old_n + n), new_ids, &ix->bytes);
       ix->h_ids.insert(ix->h_ids.end(), ids, ids + n);
       ix->max_id = ids[n - 1];
+      if (ix->pq_shadow) { free_index(ix->pq_shadow); ix->pq_shadow = nullptr; }   // (rebuilt by the next batch search)
       return FREDDY_OK;
     }
     case KIND_IVF: {
       if (!codes || !coarse_id) return fail(FREDDY_E_ARG, "coarse_id and codes are required");
-      if (int rc = append_packed_rows(ix, ix->C, n, coarse_id, ids, codes)) return rc;
+      FreshLayout L;   // (the block layout, the one-byte codes and the row terms: all beside the pinned ones)
+      if (int rc = append_packed_rows(ix, ix->C, n, coarse_id, ids, codes, L)) return rc;
+      install_layout(ix, L);
       ix->max_id = ids[n - 1];
-      return refresh_row_terms(ix);
+      return FREDDY_OK;
     }
     case KIND_IVPQ: {
       JoinIndex& j = ix->join;
@@ -668,13 +761,28 @@ extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const i
           if (codes[(size_t)i * j.m + l] < 0 || codes[(size_t)i * j.m + l] >= j.K) return fail(FREDDY_E_ARG, "code out of range at new row %lld", (long long)i);
       }
       const size_t o = (size_t)j.N, nn = (size_t)(j.N + n);
-      if (grow_device_array(&j.ids, o, nn, ids, (size_t)n, &ix->bytes) || grow_device_array(&j.cell, o, nn, coarse_id, (size_t)n, &ix->bytes) ||
-          grow_device_array(&j.codes, o * j.MP, nn * j.MP, join_pad_codes(codes, n, j.m, j.MP).data(), (size_t)n * j.MP, &ix->bytes) ||
-          (j.has_vectors && grow_device_array(&j.vectors, o * j.d, nn * j.d, vectors, (size_t)n * j.d, &ix->bytes)))
-        return fail(FREDDY_E_NOMEM, "device allocation failed");
-      if (j.markbits) (void)hipFree(j.markbits);
-      j.markbits = nullptr;
-      HIP_TRY(hipMalloc((void**)&j.markbits, sizeof(uint32_t) * ((nn + 31) / 32 + 1)));
+      // every longer array and the longer scratch bitmap beside the pinned ones; the handle changes only once all of them exist
+      int32_t *new_ids = nullptr, *new_cell = nullptr;
+      int16_t* new_codes = nullptr;
+      float* new_vec = nullptr;
+      uint32_t* new_mark = nullptr;
+      int rc = grown_copy(j.ids, o, nn, ids, (size_t)n, &new_ids);
+      if (!rc) rc = grown_copy(j.cell, o, nn, coarse_id, (size_t)n, &new_cell);
+      if (!rc) rc = grown_copy(j.codes, o * j.MP, nn * j.MP, join_pad_codes(codes, n, j.m, j.MP).data(), (size_t)n * j.MP, &new_codes);
+      if (!rc && j.has_vectors) rc = grown_copy(j.vectors, o * j.d, nn * j.d, vectors, (size_t)n * j.d, &new_vec);
+      if (!rc && dev_malloc(&new_mark, sizeof(uint32_t) * ((nn + 31) / 32 + 1)) != hipSuccess) { new_mark = nullptr; rc = -1; }
+      if (rc) {
+        void* fresh[] = {new_ids, new_cell, new_codes, new_vec, new_mark};
+        for (void* p : fresh) if (p) (void)dev_free(p);
+        return grow_failed(rc);
+      }
+      j.h_ids.reserve(j.h_ids.size() + (size_t)n); j.h_cell.reserve(j.h_cell.size() + (size_t)n);
+      swap_grown(&j.ids, o, nn, new_ids, &ix->bytes);
+      swap_grown(&j.cell, o, nn, new_cell, &ix->bytes);
+      swap_grown(&j.codes, o * j.MP, nn * j.MP, new_codes, &ix->bytes);
+      if (j.has_vectors) swap_grown(&j.vectors, o * j.d, nn * j.d, new_vec, &ix->bytes);
+      if (j.markbits) (void)dev_free(j.markbits);
+      j.markbits = new_mark;
       j.h_ids.insert(j.h_ids.end(), ids, ids + n);
       j.h_cell.insert(j.h_cell.end(), coarse_id, coarse_id + n);
       j.N += n; ix->N = j.N;
@@ -686,22 +794,36 @@ extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const i
       const int d = ix->d;
       const size_t o = (size_t)ix->N, nn = (size_t)(ix->N + n);
       const int64_t new_blocks = (int64_t)((nn + 63) / 64);
-      float* xb = nullptr;
-      HIP_TRY(hipMalloc((void**)&xb, sizeof(float) * (size_t)new_blocks * d * 64));
-      HIP_TRY(hipMemset(xb, 0, sizeof(float) * (size_t)new_blocks * d * 64));
-      if (ix->n_blocks) HIP_TRY(hipMemcpy(xb, ix->xb, sizeof(float) * (size_t)ix->n_blocks * d * 64, hipMemcpyDeviceToDevice));
-      if (grow_device_array(&ix->coarse, o * d, nn * d, vectors, (size_t)n * d, &ix->bytes) || grow_device_array(&ix->ids, o, nn, ids, (size_t)n, &ix->bytes)) {
-        (void)hipFree(xb);
-        return fail(FREDDY_E_NOMEM, "device allocation failed");
+      // the longer blocked copy, row-major copy and ids beside the pinned ones; the handle changes only once all three are complete
+      float *xb = nullptr, *new_rows = nullptr;
+      int32_t* new_ids = nullptr;
+      int rc = 0;
+      if (dev_malloc(&xb, sizeof(float) * (size_t)new_blocks * d * 64) != hipSuccess) { xb = nullptr; rc = fail(FREDDY_E_NOMEM, "device allocation failed while appending rows"); }
+      if (!rc && (hipMemset(xb, 0, sizeof(float) * (size_t)new_blocks * d * 64) != hipSuccess ||
+                  (ix->n_blocks && hipMemcpy(xb, ix->xb, sizeof(float) * (size_t)ix->n_blocks * d * 64, hipMemcpyDeviceToDevice) != hipSuccess)))
+        rc = fail(FREDDY_E_HIP, "copying the row blocks failed");
+      if (!rc) { if (const int g = grown_copy(ix->coarse, o * d, nn * d, vectors, (size_t)n * d, &new_rows)) rc = grow_failed(g); }
+      if (!rc) { if (const int g = grown_copy(ix->ids, o, nn, ids, (size_t)n, &new_ids)) rc = grow_failed(g); }
+      if (!rc) {
+        hipLaunchKernelGGL(place_vectors_kernel, dim3((unsigned)n), dim3(256), 0, ix->stream, new_rows + o * d, (int64_t)o, n, xb, d);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "re-blocking the new rows failed");
       }
-      hipLaunchKernelGGL(place_vectors_kernel, dim3((unsigned)n), dim3(256), 0, ix->stream, ix->coarse + o * d, (int64_t)o, n, xb, d);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipStreamSynchronize(ix->stream));
-      if (ix->xb) (void)hipFree(ix->xb);
+      if (rc) {
+        void* fresh[] = {xb, new_rows, new_ids};
+        for (void* p : fresh) if (p) (void)dev_free(p);
+        return rc;
+      }
+      ix->h_ids.reserve(ix->h_ids.size() + (size_t)n);
+      swap_grown(&ix->coarse, o * d, nn * d, new_rows, &ix->bytes);
+      swap_grown(&ix->ids, o, nn, new_ids, &ix->bytes);
+      if (ix->xb) (void)dev_free(ix->xb);
       ix->bytes += (int64_t)sizeof(float) * d * 64 * (new_blocks - std::max<int64_t>(ix->n_blocks, 1));   // (pin_vectors counts one block at least)
       ix->xb = xb; ix->n_blocks = new_blocks; ix->N += n;
       ix->h_ids.insert(ix->h_ids.end(), ids, ids + n);
-      return exf_table_stats(ix, (int64_t)o, n);   // (the filter's scale and norm bound cover the new rows)
+      // the filter's scale and norm bound cover the new rows.  The statistics and the fragment copy are rewritten in place: a
+      // failure from here on leaves rows the filter's state does not cover -> the handle is poisoned
+      if (int rc2 = exf_table_stats(ix, (int64_t)o, n)) { ix->poisoned = true; return rc2; }
+      return FREDDY_OK;
     }
   }
   return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
@@ -713,10 +835,10 @@ extern "C" int freddy_gpu_append_rows(freddy_gpu_index_t* ix, int64_t n, const i
 // device scratch of one call, freed when it goes out of scope
 struct RemoveScratch {
   std::vector<void*> held;
-  ~RemoveScratch() { for (void* p : held) if (p) (void)hipFree(p); }
+  ~RemoveScratch() { for (void* p : held) if (p) (void)dev_free(p); }
   template <class T> T* get(size_t n) {
     void* p = nullptr;
-    if (hipMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)) != hipSuccess) return nullptr;
+    if (dev_malloc(&p, sizeof(T) * std::max<size_t>(n, 1)) != hipSuccess) return nullptr;
     held.push_back(p);
     return static_cast<T*>(p);
   }
@@ -745,7 +867,7 @@ static void erase_rows(std::vector<T>& a, const std::vector<int32_t>& rows, size
 template <class T>
 static int gather_rows(hipStream_t s, const T* src, int64_t n_new, int e, const int32_t* d_rm, int n_rm, T** out) {
   *out = nullptr;
-  if (hipMalloc((void**)out, sizeof(T) * std::max<size_t>((size_t)n_new * e, 1)) != hipSuccess) { *out = nullptr; return fail(FREDDY_E_NOMEM, "device allocation failed while removing rows"); }
+  if (dev_malloc((void**)out, sizeof(T) * std::max<size_t>((size_t)n_new * e, 1)) != hipSuccess) { *out = nullptr; return fail(FREDDY_E_NOMEM, "device allocation failed while removing rows"); }
   if (n_new > 0) {
     hipLaunchKernelGGL(rm_gather_rows_kernel, dim3((unsigned)((n_new + 63) / 64)), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(src),
                        reinterpret_cast<uint32_t*>(*out), d_rm, n_rm, n_new, (int)(sizeof(T) * e / 4));
@@ -761,7 +883,8 @@ static int64_t resized_bytes(size_t old_n, size_t new_n) { return (int64_t)sizeo
 // table) leaves; the rows that stay keep their order inside their list.  The new block layout is built beside the old one on
 // the device and swapped in; nothing changes when no slot matches.  *removed: the rows that left; *max_pos: the largest pos
 // that stays (-1: none).  The lists lose part of arrange_list_rows' bank-conflict arrangement (speed only).
-static int remove_packed_rows(freddy_gpu_index* ix, int n_lists, const std::vector<int32_t>& rm, bool renumber, int64_t* removed, int32_t* max_pos) {
+// Everything is built into L: the handle is not touched, and L.ready stays false when there is nothing to change.
+static int remove_packed_rows(freddy_gpu_index* ix, int n_lists, const std::vector<int32_t>& rm, bool renumber, int64_t* removed, int32_t* max_pos, FreshLayout& L) {
   const int M2 = ix->M2;
   const int64_t ob = ix->n_blocks;
   *removed = 0;
@@ -800,8 +923,8 @@ static int remove_packed_rows(freddy_gpu_index* ix, int n_lists, const std::vect
   int32_t *pos = nullptr, *d_blk_cell = nullptr, *d_new_blk = nullptr, *d_list_off = nullptr;
   int64_t junk = 0;
   int rc = 0;
-  if (hipMalloc((void**)&packed, sizeof(uint32_t) * (size_t)alloc_blocks * M2 * 64) != hipSuccess ||
-      hipMalloc((void**)&pos, sizeof(int32_t) * (size_t)alloc_blocks * 64) != hipSuccess ||
+  if (dev_malloc((void**)&packed, sizeof(uint32_t) * (size_t)alloc_blocks * M2 * 64) != hipSuccess ||
+      dev_malloc((void**)&pos, sizeof(int32_t) * (size_t)alloc_blocks * 64) != hipSuccess ||
       upload(&d_blk_cell, blk_cell.data(), blk_cell.size(), &junk) || upload(&d_new_blk, new_blk.data(), new_blk.size(), &junk) ||
       upload(&d_list_off, new_list_off.data(), new_list_off.size(), &junk))
     rc = fail(FREDDY_E_NOMEM, "device allocation failed while removing rows");
@@ -814,21 +937,15 @@ static int remove_packed_rows(freddy_gpu_index* ix, int n_lists, const std::vect
     hipLaunchKernelGGL(rm_fill_tail_kernel, dim3((unsigned)((n_lists + 3) / 4)), dim3(256), 0, ix->stream, d_list_off, d_new_blk, n_lists, M2, packed, pos);
   }
   if (!rc && (hipGetLastError() != hipSuccess || hipStreamSynchronize(ix->stream) != hipSuccess)) rc = fail(FREDDY_E_HIP, "compacting the lists failed");
-  if (rc) {
-    void* fresh[] = {packed, pos, d_blk_cell, d_new_blk, d_list_off};
-    for (void* p : fresh) if (p) (void)hipFree(p);
-    return rc;
-  }
-  void* old[] = {ix->packed, ix->pos, ix->blk_cell, ix->blk_off, ix->list_off};
-  for (void* p : old) if (p) (void)hipFree(p);
-  ix->bytes += (alloc_blocks - std::max<int64_t>(ob, 1)) * (int64_t)(sizeof(uint32_t) * M2 * 64 + sizeof(int32_t) * 64 + sizeof(int32_t));
-  ix->packed = packed; ix->pos = pos; ix->blk_cell = d_blk_cell; ix->blk_off = d_new_blk; ix->list_off = d_list_off;
-  ix->n_blocks = nnb;
-  ix->max_list_blocks = max_blocks;
-  ix->h_list_off = new_list_off;
+  L.packed = packed; L.pos = pos; L.blk_cell = d_blk_cell; L.blk_off = d_new_blk; L.list_off = d_list_off;   // (L frees them if it is never installed)
+  if (rc) { L.drop(); return rc; }
+  L.n_blocks = nnb;
+  L.max_list_blocks = max_blocks;
+  L.h_list_off = new_list_off;
+  L.N = kept;
+  if (int rc2 = finish_layout(ix, L)) return rc2;
   *removed = ix->N - kept;
-  ix->N = kept;
-  return build_packed8(ix);
+  return 0;
 }
 
 extern "C" int freddy_gpu_remove_rows(freddy_gpu_index_t* ix, int64_t n, const int32_t* ids, int64_t* removed) {
@@ -843,7 +960,7 @@ extern "C" int freddy_gpu_remove_rows(freddy_gpu_index_t* ix, int64_t n, const i
     reps.swap(ix->replicas);
     int rc = freddy_gpu_remove_rows(ix, n, ids, removed);
     reps.swap(ix->replicas);
-    if (rc) { if (rc == FREDDY_E_HIP || rc == FREDDY_E_NOMEM) ix->poisoned = true; return rc; }
+    if (rc) return rc;   // (the primary is as it was, or has poisoned itself: no other device has changed)
     for (freddy_gpu_index* r : ix->replicas)
       if ((rc = freddy_gpu_remove_rows(r, n, ids, nullptr))) { ix->poisoned = true; return rc; }
     return FREDDY_OK;
@@ -863,13 +980,24 @@ extern "C" int freddy_gpu_remove_rows(freddy_gpu_index_t* ix, int64_t n, const i
       int32_t* d_rm = tmp.put(rows.data(), rows.size());
       if (!d_rm) return fail(FREDDY_E_NOMEM, "device allocation failed while removing rows");
       int32_t* new_ids = nullptr;
-      if (int rc = gather_rows(ix->stream, ix->ids, new_n, 1, d_rm, (int)rows.size(), &new_ids)) { if (new_ids) (void)hipFree(new_ids); return rc; }
+      if (int rc = gather_rows(ix->stream, ix->ids, new_n, 1, d_rm, (int)rows.size(), &new_ids)) {
+        (void)hipStreamSynchronize(ix->stream);   // (the gather may be in flight: it has left new_ids before the array goes back)
+        if (new_ids) (void)dev_free(new_ids);
+        return rc;
+      }
+      int32_t unused = -1;
+      FreshLayout L;
+      if (int rc = remove_packed_rows(ix, 1, rows, true, &gone, &unused, L)) {   // (synchronises the stream: new_ids is complete)
+        (void)hipStreamSynchronize(ix->stream);
+        (void)dev_free(new_ids);
+        return rc;
+      }
+      if (!L.ready) { (void)hipStreamSynchronize(ix->stream); (void)dev_free(new_ids); return fail(FREDDY_E_HIP, "rows %d.. have no slot: the pinned layout is inconsistent", rows[0]); }
+      install_layout(ix, L);
       // views of the flat table are rebuilt from the new layout on next use
       if (ix->pq_shadow) { free_index(ix->pq_shadow); ix->pq_shadow = nullptr; }
       if (ix->pq_sub_view) { free_index(ix->pq_sub_view); ix->pq_sub_view = nullptr; }
-      int32_t unused = -1;
-      if (int rc = remove_packed_rows(ix, 1, rows, true, &gone, &unused)) { (void)hipFree(new_ids); return rc; }   // (synchronises the stream: new_ids is complete)
-      if (ix->ids) (void)hipFree(ix->ids);
+      if (ix->ids) (void)dev_free(ix->ids);
       ix->ids = new_ids;
       ix->bytes += resized_bytes<int32_t>((size_t)old_n, (size_t)new_n);
       erase_rows(ix->h_ids, rows);
@@ -878,10 +1006,11 @@ extern "C" int freddy_gpu_remove_rows(freddy_gpu_index_t* ix, int64_t n, const i
     }
     case KIND_IVF: {
       int32_t max_pos = -1;
-      if (int rc = remove_packed_rows(ix, ix->C, want, false, &gone, &max_pos)) return rc;   // (pos holds the ids)
-      if (gone > 0) {
+      FreshLayout L;   // (the compacted lists, their one-byte codes and row terms: all beside the pinned ones)
+      if (int rc = remove_packed_rows(ix, ix->C, want, false, &gone, &max_pos, L)) return rc;   // (pos holds the ids)
+      if (L.ready) {
+        install_layout(ix, L);
         ix->max_id = max_pos;   // a later append may start above the largest id that is left, as on a fresh pin
-        if (int rc = refresh_row_terms(ix)) return rc;
       }
       break;
     }
@@ -904,11 +1033,11 @@ extern "C" int freddy_gpu_remove_rows(freddy_gpu_index_t* ix, int64_t n, const i
       if (!rc && hipStreamSynchronize(ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "compacting the ivpq rows failed");
       if (rc) {
         void* fresh[] = {new_ids, new_cell, new_codes, new_vec};
-        for (void* p : fresh) if (p) (void)hipFree(p);
+        for (void* p : fresh) if (p) (void)dev_free(p);
         return rc;
       }
       void* old[] = {j.ids, j.cell, j.codes, j.vectors, j.markbits};
-      for (void* p : old) if (p) (void)hipFree(p);
+      for (void* p : old) if (p) (void)dev_free(p);
       j.ids = new_ids; j.cell = new_cell; j.codes = new_codes; j.vectors = new_vec;
       j.markbits = markbits; tmp.held.erase(std::find(tmp.held.begin(), tmp.held.end(), (void*)markbits));
       ix->bytes += 2 * resized_bytes<int32_t>(o, nn) + resized_bytes<int16_t>(o * j.MP, nn * j.MP) + (j.has_vectors ? resized_bytes<float>(o * j.d, nn * j.d) : 0);
@@ -935,7 +1064,7 @@ extern "C" int freddy_gpu_remove_rows(freddy_gpu_index_t* ix, int64_t n, const i
       float *new_rows = nullptr, *xb = nullptr;
       int rc = gather_rows(ix->stream, ix->ids, (int64_t)nn, 1, d_rm, (int)rows.size(), &new_ids);
       if (!rc) rc = gather_rows(ix->stream, ix->coarse, (int64_t)nn, d, d_rm, (int)rows.size(), &new_rows);
-      if (!rc && hipMalloc((void**)&xb, blk * (size_t)alloc_blocks) != hipSuccess) { xb = nullptr; rc = fail(FREDDY_E_NOMEM, "device allocation failed while removing rows"); }
+      if (!rc && dev_malloc((void**)&xb, blk * (size_t)alloc_blocks) != hipSuccess) { xb = nullptr; rc = fail(FREDDY_E_NOMEM, "device allocation failed while removing rows"); }
       if (!rc && same_blocks > 0 && hipMemcpyAsync(xb, ix->xb, blk * (size_t)same_blocks, hipMemcpyDeviceToDevice, ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "copying the row blocks failed");
       if (!rc && alloc_blocks > same_blocks && hipMemsetAsync(xb + (size_t)same_blocks * d * 64, 0, blk * (size_t)(alloc_blocks - same_blocks), ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "clearing the row blocks failed");
       if (!rc && (int64_t)nn > same_blocks * 64) {
@@ -946,14 +1075,14 @@ extern "C" int freddy_gpu_remove_rows(freddy_gpu_index_t* ix, int64_t n, const i
       if (!rc && hipStreamSynchronize(ix->stream) != hipSuccess) rc = fail(FREDDY_E_HIP, "compacting the vector rows failed");
       if (rc) {
         void* fresh[] = {new_ids, new_rows, xb};
-        for (void* p : fresh) if (p) (void)hipFree(p);
+        for (void* p : fresh) if (p) (void)dev_free(p);
         return rc;
       }
       void* old[] = {ix->ids, ix->coarse, ix->xb};
-      for (void* p : old) if (p) (void)hipFree(p);
+      for (void* p : old) if (p) (void)dev_free(p);
       ix->bytes += resized_bytes<int32_t>(o, nn) + (int64_t)blk * (alloc_blocks - std::max<int64_t>(ix->n_blocks, 1));
       if (nn == 0) {   // (pin_vectors keeps no row-major copy of an empty table)
-        (void)hipFree(new_rows); new_rows = nullptr;
+        (void)dev_free(new_rows); new_rows = nullptr;
         ix->bytes -= (int64_t)sizeof(float) * (int64_t)o * d;
       } else ix->bytes += (int64_t)sizeof(float) * d * ((int64_t)nn - (int64_t)o);
       ix->ids = new_ids; ix->coarse = new_rows; ix->xb = xb;
@@ -963,7 +1092,7 @@ extern "C" int freddy_gpu_remove_rows(freddy_gpu_index_t* ix, int64_t n, const i
       // the exact filter's state over the rows that are left, as a fresh pin computes it: a larger scale once the row with the
       // largest element has gone, the filter back on once the only non-finite row has (the fragment copy keeps its capacity)
       if (nn == 0) ix->exf_ok = false;
-      else if (int rc2 = exf_table_stats(ix, 0, (int64_t)nn)) return rc2;
+      else if (int rc2 = exf_table_stats(ix, 0, (int64_t)nn)) { ix->poisoned = true; return rc2; }   // (the statistics are rewritten in place: the rows have gone, the filter's state has not followed)
       break;
     }
     default: return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
@@ -1089,12 +1218,18 @@ static int update_rows_checked(freddy_gpu_index* ix, int64_t n, const int32_t* i
       if (!move_id.empty()) {   // out of the old lists (a stable compaction), then to the end of the new ones
         int64_t gone = 0;
         int32_t unused = -1;
-        if (int rc = remove_packed_rows(ix, ix->C, move_id, false, &gone, &unused)) return rc;
+        FreshLayout out, in;
+        if (int rc = remove_packed_rows(ix, ix->C, move_id, false, &gone, &unused, out)) return rc;
+        if (out.ready) install_layout(ix, out);
         *changed += gone;
         if (gone != (int64_t)move_id.size()) return fail(FREDDY_E_HIP, "%lld of %zu rows left their lists: the pinned layout is inconsistent", (long long)gone, move_id.size());
-        if (int rc = append_packed_rows(ix, ix->C, (int64_t)move_id.size(), move_cell.data(), move_id.data(), move_codes.data())) return rc;
-      } else if (int rc = build_packed8(ix)) return rc;
-      ix->max_id = max_id;      // no id has come or gone
+        if (int rc = append_packed_rows(ix, ix->C, (int64_t)move_id.size(), move_cell.data(), move_id.data(), move_codes.data(), in)) return rc;
+        install_layout(ix, in);   // (with the one-byte codes and the row terms of the final layout)
+        ix->max_id = max_id;      // no id has come or gone
+        return 0;
+      }
+      if (int rc = build_packed8(ix)) return rc;
+      ix->max_id = max_id;
       return refresh_row_terms(ix);
     }
     case KIND_IVPQ: {
@@ -1232,15 +1367,14 @@ extern "C" int freddy_gpu_update_codebook(freddy_gpu_index_t* ix, const float* c
       if (!rc) return FREDDY_OK;
       done = ix->replicas.size();
     }
-    if (done > 0 || rc == FREDDY_E_HIP || rc == FREDDY_E_NOMEM) ix->poisoned = true;
+    if (done > 0) ix->poisoned = true;   // (a device that failed is as it was: only a device that HAS changed makes the handle inconsistent)
     return rc;
   }
   HIP_TRY(hipSetDevice(ix->device));
   HIP_TRY(hipDeviceSynchronize());   // (searches of every stream and lane have drained before the tables change)
   if (ix->kind == KIND_PQ) return derive_codebook_tables(ix, codebook);
   if (ix->kind == KIND_IVF) {
-    if (int rc = derive_codebook_tables(ix, codebook)) return rc;
-    return refresh_row_terms(ix);
+    return derive_codebook_tables(ix, codebook, true);   // (the row terms follow the codebook: built beside the old ones with the new tables)
   }
   if (ix->kind == KIND_IVPQ) {
     JoinIndex& j = ix->join;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hip_alloc.h"
+
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -16,11 +18,11 @@ struct PinnedBuf {
     if (bytes <= cap) return 0;
     release();
     const size_t want = bytes + bytes / 4 + 256;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return -1; }
+    if (host_malloc(&p, want) != hipSuccess) { p = nullptr; return -1; }
     cap = want;
     return 0;
   }
-  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+  void release() { if (p) (void)host_free(p); p = nullptr; cap = 0; }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 

@@ -185,7 +185,7 @@ static int pq_view_refresh(freddy_gpu_index* ix, freddy_gpu_index** view, hipStr
     fx->shadow_of = ix;
     fx->kind = KIND_IVF; fx->device = ix->device; fx->stream = ix->stream; fx->n_cus = ix->n_cus;
     fx->d = ix->d; fx->m = ix->m; fx->K = ix->K; fx->S = ix->S; fx->M2 = ix->M2;
-    if (hipMalloc((void**)&fx->viol, 4 * sizeof(int32_t)) != hipSuccess || hipMemset(fx->viol, 0, 4 * sizeof(int32_t)) != hipSuccess) {
+    if (dev_malloc((void**)&fx->viol, 4 * sizeof(int32_t)) != hipSuccess || hipMemset(fx->viol, 0, 4 * sizeof(int32_t)) != hipSuccess) {
       free_index(fx);
       return fail(FREDDY_E_NOMEM, "device allocation failed (PQ table as pseudo-lists)");
     }
@@ -468,6 +468,7 @@ extern "C" int freddy_gpu_grouping_pq(freddy_gpu_index_t* ix, const float* group
                                       int64_t n_subset, int32_t* out_ids, int32_t* out_group, int64_t* n_out) {
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   if (ix->kind != KIND_PQ) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(ix)) return rc;
   if (G <= 0 || !group_vectors || !out_ids || !out_group || !n_out) return fail(FREDDY_E_ARG, "bad argument");
   if (n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad subset");
   *n_out = 0;
@@ -525,6 +526,7 @@ extern "C" int freddy_gpu_pq_assign(freddy_gpu_index_t* ix, const float* queries
   if (Q > AS_MAX_Q) return fail(FREDDY_E_LIMIT, "Q=%d exceeds this build's limit of %d queries per assign call", Q, AS_MAX_Q);
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   if (ix->kind != KIND_PQ) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(ix)) return rc;
   if (Q == 0 || n_targets == 0) return FREDDY_OK;
   HIP_TRY(hipSetDevice(ix->device));
   Workspace* ws = workspace_for(ix, ix->stream);

@@ -33,13 +33,14 @@ EXPORTS = [
     "freddy_gpu_ivfadc_analogy", "freddy_gpu_pq_analogy", "freddy_gpu_last_approx_analogy_stats",
     "freddy_gpu_exact_assign", "freddy_gpu_pq_assign", "freddy_gpu_remove_rows", "freddy_gpu_update_rows",
     "freddy_gpu_set_statistics", "freddy_gpu_get_statistics", "freddy_gpu_create_statistics",
+    "freddy_gpu_debug_alloc_fail_nth", "freddy_gpu_debug_alloc_track", "freddy_gpu_debug_alloc_stats",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together): ids per pass of freddy_gpu_create_statistics
 
 
 class FreddyGpuError(RuntimeError):
-    pass
+    code = None   # the FREDDY_E_* value of the failed call, where there was one
 
 
 class PQDesc(C.Structure):
@@ -167,13 +168,46 @@ def load(path=None, optional=()):
     lib.freddy_gpu_last_track.argtypes = [C.c_void_p, C.c_void_p]
     lib.freddy_gpu_profile_enable.argtypes = [C.c_void_p, C.c_int32]
     lib.freddy_gpu_profile_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name, types in (("freddy_gpu_debug_alloc_fail_nth", [C.c_int64, C.c_int32]), ("freddy_gpu_debug_alloc_track", [C.c_int32]),
+                        ("freddy_gpu_debug_alloc_stats", [C.c_void_p, C.c_size_t])):
+        if name not in optional:
+            getattr(lib, name).argtypes = types
     _lib = lib
     return lib
 
 
+E_NOMEM = -3   # include/freddy_gpu.h FREDDY_E_NOMEM
+
+
+class AllocStats(C.Structure):
+    """freddy_alloc_stats (include/freddy_gpu.h)"""
+    _fields_ = [("calls", C.c_int64), ("failed", C.c_int64), ("live", C.c_int64), ("live_bytes", C.c_int64), ("digest", C.c_uint64)]
+
+
+def alloc_fail_nth(n, real=False):
+    """The n-th device / pinned-host allocation from now fails once (freddy_gpu_debug_alloc_fail_nth); n <= 0 disarms."""
+    _check(load().freddy_gpu_debug_alloc_fail_nth(int(n), 1 if real else 0))
+
+
+def alloc_track(on):
+    """Track the live allocations from an empty set (freddy_gpu_debug_alloc_track)."""
+    _check(load().freddy_gpu_debug_alloc_track(1 if on else 0))
+
+
+def alloc_stats():
+    """-> AllocStats: calls, failed, live, live_bytes, digest (freddy_gpu_debug_alloc_stats)."""
+    st = AllocStats()
+    n = load().freddy_gpu_debug_alloc_stats(C.byref(st), C.sizeof(st))
+    if n != C.sizeof(st):
+        raise FreddyGpuError(f"freddy_gpu_debug_alloc_stats wrote {n} of {C.sizeof(st)} bytes")
+    return st
+
+
 def _check(rc):
     if rc != 0:
-        raise FreddyGpuError(f"freddy_gpu error {rc}: {load().freddy_gpu_last_error().decode()}")
+        err = FreddyGpuError(f"freddy_gpu error {rc}: {load().freddy_gpu_last_error().decode()}")
+        err.code = rc   # (the FREDDY_E_* value, for callers that tell a failed allocation from the rest)
+        raise err
 
 
 def _f32(a):
