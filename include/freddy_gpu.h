@@ -476,6 +476,24 @@ int freddy_gpu_create_statistics(freddy_gpu_index_t* ivpq, const int32_t* ids, i
  * fewer than k rows); such queries keep partial results and the caller should re-run
  * them through freddy_gpu_ivfadc_search.  Single round only.
  *
+ * The status word, as tests/test_gpu_dev_contract.py pins it:
+ *   - d_status[0] becomes non-zero iff at least one query of the call has found < k after the first probing round (found by
+ *     the call's found_rule: rows retrieved, or accepted insertions).  The library only ever WRITES NON-ZERO and never clears
+ *     the word: the caller zeroes it, on the same stream, before the call (or outside a captured graph before a replay).
+ *   - A call that is cut into chunks (option lut_budget_mb) shares the one word among its chunks: it is set if a query of any
+ *     chunk is unfinished, and every chunk's lists land at the chunk's offset of the output buffers.
+ *   - d_status == NULL is allowed: the same lists, no report.
+ *   - "Partial results" are defined: the list of an unfinished query is the reference's list after its FIRST probing round
+ *     (freddy.c:262-377 stopped after one pass of its loop; oracle/freddy_oracle.h fo_ivfadc_search_capped with
+ *     max_rounds = 1), unfilled slots (-1, sentinel).  A finished query's list is its final list.  Re-running the unfinished
+ *     queries through freddy_gpu_ivfadc_search gives their final lists.
+ *   - With W >= C (W is cut to C) on a table of fewer than k rows every query has found < k after round one although no cell
+ *     is left to probe: the word IS set, every row is listed and the other slots hold (-1, sentinel); the host-buffer call
+ *     returns the same lists.
+ *   - Q == 0 succeeds, writes nothing and leaves the word alone.  A refused call (FREDDY_E_ARG / _KIND / _LIMIT: k < 1,
+ *     k > 4096, W < 1, more than 512 probes after the cut to C, a bad found_rule, a NULL buffer with Q > 0, a handle of another
+ *     kind) allocates nothing and enqueues nothing.  freddy_gpu_pq_search_dev has no status word: a flat scan is one round.
+ *
  * Concurrency: everything a search writes besides its outputs lives in a workspace that belongs to the stream
  * the search is enqueued on (twelve slots per handle; with all taken a new stream takes over the least recently
  * used one after the device has drained).  Searches enqueued on DIFFERENT streams may therefore be in flight

@@ -284,9 +284,12 @@ int fo_pq_search_in_batch(const fo_pq_table* t, const float* queries, int Q, int
 /* ------------------------------------------------------------------------------------
  * a7/a8  ivfadc_search                                              freddy.c:174-393
  * ------------------------------------------------------------------------------------ */
-int fo_ivfadc_search(const fo_ivf_table* t, const float* q, int k, int W, float sentinel,
-                     int found_rule, fo_entry* out) {
-  if (!t || !q || !out || k <= 0 || W <= 0 || t->m <= 0 || t->d % t->m) return -1;
+/* max_rounds > 0 stops the "while (found < k)" loop (:262) after that many probing rounds: the list, `found` and the number
+ * of rounds run are what the reference holds at that point of its loop.  0 = the reference's own loop. */
+int fo_ivfadc_search_capped(const fo_ivf_table* t, const float* q, int k, int W, float sentinel,
+                            int found_rule, int max_rounds, fo_entry* out, int32_t* found_out,
+                            int32_t* rounds_out) {
+  if (!t || !q || !out || k <= 0 || W <= 0 || max_rounds < 0 || t->m <= 0 || t->d % t->m) return -1;
   const int d = t->d, m = t->m, K = t->K, C = t->C, s = d / m;
   const size_t lut_n = (size_t)m * K;
   unsigned char* black = (unsigned char*)calloc((size_t)(C ? C : 1), 1);
@@ -299,7 +302,9 @@ int fo_ivfadc_search(const fo_ivf_table* t, const float* q, int k, int W, float 
   fo_topk_init(out, k, sentinel);                         /* :258-260 */
   float maxd = sentinel;
   long found = 0;
+  int rounds = 0;
   while (found < k) {                                     /* :262 */
+    if (max_rounds > 0 && rounds >= max_rounds) break;
     /* W best not-yet-used cells via updateTopK on cqSelection   :266-283
      * (list sentinel 100.0, running threshold starts at 1000.0) */
     float mind = 1000.0f;
@@ -319,6 +324,7 @@ int fo_ivfadc_search(const fo_ivf_table* t, const float* q, int k, int W, float 
     for (int i = 0; i < W; ++i)
       if (sel[i].id >= 0) { cell[n_sel++] = sel[i].id; black[sel[i].id] = 1; }
     if (n_sel == 0) break;
+    ++rounds;
     /* residuals and one LUT per probed cell                      :296-314 */
     for (int i = 0; i < n_sel; ++i) {
       const float* c = t->coarse + (size_t)cell[i] * d;
@@ -344,18 +350,27 @@ int fo_ivfadc_search(const fo_ivf_table* t, const float* q, int k, int W, float 
     found += found_rule ? accepted : rows;                                      /* :377 / :971 */
   }
   free(cell); free(cursor); free(luts); free(resid); free(sel); free(black);
+  if (found_out) *found_out = (int32_t)found;
+  if (rounds_out) *rounds_out = rounds;
   return 0;
 }
 
-int fo_ivfadc_search_many(const fo_ivf_table* t, const float* queries, int Q, int k, int W,
-                          float sentinel, int found_rule, int n_threads, fo_entry* out) {
+int fo_ivfadc_search(const fo_ivf_table* t, const float* q, int k, int W, float sentinel,
+                     int found_rule, fo_entry* out) {
+  return fo_ivfadc_search_capped(t, q, k, W, sentinel, found_rule, 0, out, NULL, NULL);
+}
+
+int fo_ivfadc_search_many_capped(const fo_ivf_table* t, const float* queries, int Q, int k, int W,
+                                 float sentinel, int found_rule, int max_rounds, int n_threads,
+                                 fo_entry* out, int32_t* found_out, int32_t* rounds_out) {
   if (!t || !queries || !out || Q < 0) return -1;
   int rc = 0;
   if (n_threads < 1) n_threads = 1;
 #pragma omp parallel for schedule(static) num_threads(n_threads) if (n_threads > 1)
   for (int i = 0; i < Q; ++i) {
-    int r = fo_ivfadc_search(t, queries + (size_t)i * t->d, k, W, sentinel, found_rule,
-                             out + (size_t)i * k);
+    int r = fo_ivfadc_search_capped(t, queries + (size_t)i * t->d, k, W, sentinel, found_rule, max_rounds,
+                                    out + (size_t)i * k, found_out ? found_out + i : NULL,
+                                    rounds_out ? rounds_out + i : NULL);
     if (r) {
 #pragma omp atomic write
       rc = r;
@@ -364,12 +379,19 @@ int fo_ivfadc_search_many(const fo_ivf_table* t, const float* queries, int Q, in
   return rc;
 }
 
+int fo_ivfadc_search_many(const fo_ivf_table* t, const float* queries, int Q, int k, int W,
+                          float sentinel, int found_rule, int n_threads, fo_entry* out) {
+  return fo_ivfadc_search_many_capped(t, queries, Q, k, W, sentinel, found_rule, 0, n_threads, out, NULL, NULL);
+}
+
 /* ------------------------------------------------------------------------------------
  * a6/a8  ivfadc_batch_search                                         freddy.c:679-999
+ * max_rounds > 0 leaves the "while (!finished)" loop (:835) after that many rounds; found_out / rounds_out [Q] (may be NULL):
+ * foundInstances (:971) at that point, and the rounds in which the query probed a cell.
  * ------------------------------------------------------------------------------------ */
-int fo_ivfadc_batch_search(const fo_ivf_table* t, const float* queries, int Q, int k,
-                           fo_entry* out) {
-  if (!t || !queries || !out || k <= 0 || Q < 0 || t->m <= 0 || t->d % t->m) return -1;
+int fo_ivfadc_batch_search_capped(const fo_ivf_table* t, const float* queries, int Q, int k, int max_rounds,
+                                  fo_entry* out, int32_t* found_out, int32_t* rounds_out) {
+  if (!t || !queries || !out || k <= 0 || Q < 0 || max_rounds < 0 || t->m <= 0 || t->d % t->m) return -1;
   const int d = t->d, m = t->m, K = t->K, C = t->C, s = d / m;
   const size_t lut_n = (size_t)m * K;
   const size_t Qn = (size_t)(Q ? Q : 1);
@@ -389,7 +411,11 @@ int fo_ivfadc_batch_search(const fo_ivf_table* t, const float* queries, int Q, i
     maxd[i] = 100;
   }
   int finished = 0;
+  int round = 0;
+  if (rounds_out) for (int i = 0; i < Q; ++i) rounds_out[i] = 0;
   while (!finished) {                                     /* :835 */
+    if (max_rounds > 0 && round >= max_rounds) break;
+    ++round;
     for (int c = 0; c < C; ++c) { count[c] = 0; table[c] = NULL; }
     for (int i = 0; i < Q; ++i) {                         /* :845-888 */
       if (found[i] >= k || stuck[i]) continue;
@@ -407,6 +433,7 @@ int fo_ivfadc_batch_search(const fo_ivf_table* t, const float* queries, int Q, i
         continue;
       }
       cq[i] = pick;
+      if (rounds_out) rounds_out[i] += 1;
       black[(size_t)i * C + pick] = 1;                    /* :868-872 */
       count[pick] += 1;                                   /* :873 */
       const float* c = t->coarse + (size_t)pick * d;      /* residual :876-879 */
@@ -448,9 +475,15 @@ int fo_ivfadc_batch_search(const fo_ivf_table* t, const float* queries, int Q, i
     for (int i = 0; i < Q; ++i)
       if (found[i] < k && !stuck[i]) finished = 0;
   }
+  if (found_out) for (int i = 0; i < Q; ++i) found_out[i] = found[i];
   free(table); free(count); free(resid); free(luts); free(stuck); free(black);
   free(maxd); free(cq); free(found);
   return 0;
+}
+
+int fo_ivfadc_batch_search(const fo_ivf_table* t, const float* queries, int Q, int k,
+                           fo_entry* out) {
+  return fo_ivfadc_batch_search_capped(t, queries, Q, k, 0, out, NULL, NULL);
 }
 
 /* ------------------------------------------------------------------------------------

@@ -125,11 +125,24 @@ int fo_pq_search_in_batch(const fo_pq_table* t, const float* queries, int Q, int
 int fo_ivfadc_search(const fo_ivf_table* t, const float* q, int k, int W, float sentinel,
                      int found_rule, fo_entry* out);
 
+/* The same with a cap on the probing rounds (max_rounds, 0 = none): the list the reference holds when its "while
+ * (foundInstances < k)" loop (freddy.c:262) has run that many rounds.  *found_out / *rounds_out (may be NULL): foundInstances
+ * after the last round run, and the number of rounds run (a round in which no cell was left does not count).
+ * A query is UNFINISHED after round one iff found < k with max_rounds = 1; its list then is its round-one list. */
+int fo_ivfadc_search_capped(const fo_ivf_table* t, const float* q, int k, int W, float sentinel,
+                            int found_rule, int max_rounds, fo_entry* out, int32_t* found_out,
+                            int32_t* rounds_out);
+
 /* The same per-query routine over Q queries (the build's nprobe generalisation of the
  * batch UDF); n_threads>1 splits queries statically with OpenMP
  * ("one backend per core" for the CPU baseline). */
 int fo_ivfadc_search_many(const fo_ivf_table* t, const float* queries, int Q, int k, int W,
                           float sentinel, int found_rule, int n_threads, fo_entry* out);
+
+/* ... capped: found_out / rounds_out are [Q] (may be NULL) */
+int fo_ivfadc_search_many_capped(const fo_ivf_table* t, const float* queries, int Q, int k, int W,
+                                 float sentinel, int found_rule, int max_rounds, int n_threads,
+                                 fo_entry* out, int32_t* found_out, int32_t* rounds_out);
 
 /* ivfadc_batch_search                    freddy.c:679-999  (1 probe / round, sentinel 100.0)
  * Restated with the reference's own loop structure (rounds over all unfinished
@@ -137,6 +150,10 @@ int fo_ivfadc_search_many(const fo_ivf_table* t, const float* queries, int Q, in
  * normalised vectors in fetch order; out is [Q][k]. */
 int fo_ivfadc_batch_search(const fo_ivf_table* t, const float* queries, int Q, int k,
                            fo_entry* out);
+/* ... with a cap on the rounds of its "while (!finished)" loop (freddy.c:835; 0 = none); found_out / rounds_out [Q] (may be
+ * NULL): foundInstances (:971) after the last round run, and the rounds in which the query probed a cell. */
+int fo_ivfadc_batch_search_capped(const fo_ivf_table* t, const float* queries, int Q, int k, int max_rounds,
+                                  fo_entry* out, int32_t* found_out, int32_t* rounds_out);
 
 /* determineCoarseIdsMultiWithStatisticsMulti   index_utils.c:252-443 (cpos == 2 only)
  * For every active query emits the visited cells in order.

@@ -79,6 +79,10 @@ class Oracle:
         L.fo_ivfadc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]
         L.fo_ivfadc_search_many.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                             C.c_int, C.c_int, C.c_void_p]
+        L.fo_ivfadc_search_many_capped.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fo_ivfadc_batch_search_capped.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]
         L.fo_ivpq_search_in.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                         C.c_void_p, C.c_void_p]
@@ -302,20 +306,38 @@ class Oracle:
         assert rc == 0, rc
         return out
 
-    def ivfadc_search_many(self, t, queries, k, W, sentinel=1000.0, found_rule=0, n_threads=1):
+    def ivfadc_search_many(self, t, queries, k, W, sentinel=1000.0, found_rule=0, n_threads=1, max_rounds=None):
+        """max_rounds None: the lists alone.  An integer (0 = no cap): (lists, found[Q], rounds[Q]) -- the lists after that many
+        probing rounds, foundInstances at that point and the rounds each query ran.  A query is unfinished after round one iff
+        found < k with max_rounds = 1."""
         qs = _f32(queries)
         out = np.empty((qs.shape[0], k), ENTRY)
-        rc = self.lib.fo_ivfadc_search_many(C.byref(t), _p(qs), qs.shape[0], k, W, C.c_float(sentinel),
-                                            found_rule, n_threads, _p(out))
+        if max_rounds is None:
+            rc = self.lib.fo_ivfadc_search_many(C.byref(t), _p(qs), qs.shape[0], k, W, C.c_float(sentinel),
+                                                found_rule, n_threads, _p(out))
+            assert rc == 0, rc
+            return out
+        found = np.full(qs.shape[0], -1, np.int32)
+        rounds = np.full(qs.shape[0], -1, np.int32)
+        rc = self.lib.fo_ivfadc_search_many_capped(C.byref(t), _p(qs), qs.shape[0], k, W, C.c_float(sentinel), found_rule,
+                                                   int(max_rounds), n_threads, _p(out), _p(found), _p(rounds))
         assert rc == 0, rc
-        return out
+        return out, found, rounds
 
-    def ivfadc_batch_search(self, t, queries, k):
+    def ivfadc_batch_search(self, t, queries, k, max_rounds=None):
+        """max_rounds as for ivfadc_search_many."""
         qs = _f32(queries)
         out = np.empty((qs.shape[0], k), ENTRY)
-        rc = self.lib.fo_ivfadc_batch_search(C.byref(t), _p(qs), qs.shape[0], k, _p(out))
+        if max_rounds is None:
+            rc = self.lib.fo_ivfadc_batch_search(C.byref(t), _p(qs), qs.shape[0], k, _p(out))
+            assert rc == 0, rc
+            return out
+        found = np.full(qs.shape[0], -1, np.int32)
+        rounds = np.full(qs.shape[0], -1, np.int32)
+        rc = self.lib.fo_ivfadc_batch_search_capped(C.byref(t), _p(qs), qs.shape[0], k, int(max_rounds), _p(out), _p(found),
+                                                    _p(rounds))
         assert rc == 0, rc
-        return out
+        return out, found, rounds
 
     def multi_index_select(self, t, queries, active, n_targets, min_target_count, confidence):
         qs, act = _f32(queries), _i32(active)

@@ -1279,6 +1279,18 @@ def test_running_bound_changes_survivors_not_lists(gpu, oracle, K, monkeypatch):
     idx.close()
 
 
+def _assert_dev_contract(res, status, one, found, exp, k, what):
+    """freddy_gpu_ivfadc_search_dev's contract (include/freddy_gpu.h; tests/test_gpu_dev_contract.py): every list is the oracle's
+    list after ONE probing round -- for a query with found >= k its final list --, and the status word is non-zero iff some
+    query has found < k.  res: the [2][Q][k] int32 buffer of ids and distance bits."""
+    import torch
+    gi, gd = res[0].cpu().numpy(), res[1].view(torch.float32).cpu().numpy()
+    util.assert_same_lists(gi, gd, one, what + ": round-one lists")
+    fin = found >= k
+    util.assert_same_lists(gi[fin], gd[fin], exp[fin], what + ": final lists of the finished queries")
+    assert (status != 0) == bool((~fin).any()), f"{what}: status word {status}, {int((~fin).sum())} queries unfinished by the oracle"
+
+
 @pytest.mark.parametrize("K", [256, 1024])
 def test_in_flight_instantiations_match_oracle(gpu, oracle, K, monkeypatch):
     """scan_share > 1 -- the caller keeps batches in flight -- selects the small-footprint instantiations: ONE wave per query
@@ -1298,16 +1310,15 @@ def test_in_flight_instantiations_match_oracle(gpu, oracle, K, monkeypatch):
     idx.set_option("scan_share", 4)
     for k, W, rule, sent in ((5, 10, 0, 1000.0), (10, 4, 1, 100.0), (5, 32, 0, 1000.0)):
         exp = oracle.ivfadc_search_many(ot, qa, k, W, sentinel=sent, found_rule=rule)
+        one, found, _ = oracle.ivfadc_search_many(ot, qa, k, W, sentinel=sent, found_rule=rule, max_rounds=1)
         for plan_waves in (0,):
             res = torch.zeros((2, 300, k), dtype=torch.int32, device=dev)
             with torch.cuda.stream(stream):
+                st.zero_()
                 idx.search_dev(dq.data_ptr(), 300, k, W, sent, rule, res[0].data_ptr(), res[1].data_ptr(), st.data_ptr(), stream.cuda_stream)
             torch.cuda.synchronize(dev)
-            if int(st[0].item()) != 0:   # (a query that needs another probing round: finished by the synchronous call -- not this test's subject)
-                st.zero_()
-                continue
-            util.assert_same_lists(res[0].cpu().numpy(), res[1].view(torch.float32).cpu().numpy(), exp,
-                                   f"in flight K={K} k={k} W={W} rule={rule} plan_waves={plan_waves}")
+            what = f"in flight K={K} k={k} W={W} rule={rule} plan_waves={plan_waves}"
+            _assert_dev_contract(res, int(st[0].item()), one, found, exp, k, what)
     assert idx.bound_violations() == 0
     idx.set_option("scan_share", 1)
     idx.close()
@@ -1336,18 +1347,57 @@ def test_search_dev_can_be_captured_into_a_graph(gpu, oracle):
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=stream):
         call()
-    for qs in (qa, qb, qa):
+    for n, qs in enumerate((qa, qb, qa)):
         dq.copy_(torch.from_numpy(qs).to(dev))
         res.zero_()
+        st.zero_()                          # (outside the graph: the library only ever sets the word)
         torch.cuda.synchronize(dev)
         with torch.cuda.stream(stream):
             g.replay()
         torch.cuda.synchronize(dev)
-        if int(st[0].item()) != 0:
-            st.zero_()
-            continue
         exp = oracle.ivfadc_search_many(ot, qs, 5, 4, sentinel=1000.0, found_rule=0)
-        util.assert_same_lists(res[0].cpu().numpy(), res[1].view(torch.float32).cpu().numpy(), exp, "graph replay")
+        one, found, _ = oracle.ivfadc_search_many(ot, qs, 5, 4, sentinel=1000.0, found_rule=0, max_rounds=1)
+        _assert_dev_contract(res, int(st[0].item()), one, found, exp, 5, f"graph replay {n}")
+    assert idx.bound_violations() == 0
+    del g
+    idx.close()
+
+
+def test_graph_replay_sets_and_leaves_the_status_word(gpu, oracle):
+    """A captured chain on a table with thinned cells (tests/dev_contract_inputs.py): a replay whose query buffer holds a mixed batch
+    sets the word that was zeroed outside the graph, the next replay with a batch of finished queries leaves it at 0, and a third
+    mixed one sets it again.  Round-one lists every time."""
+    import torch
+    import dev_contract_inputs as dci
+    dev = torch.device("cuda", 0)
+    key, W, k = ("300", 1024, 5, False), 4, 5
+    c = dci.case(*key)
+    idx = gpu.IVFIndex(c["coarse"], c["codebook"], c["list_off"], c["ids"], c["codes"])
+    b = dci.batches(*key, W)
+    mixed = b["mixed"][0]
+    none = np.concatenate([b["none"][0], b["none"][0]])     # (Q = 300 as captured; a finished query twice is finished twice)
+    dq = torch.from_numpy(mixed.copy()).to(dev)
+    st = torch.zeros(4, dtype=torch.int32, device=dev)
+    res = torch.zeros((2, 300, k), dtype=torch.int32, device=dev)
+    stream = torch.cuda.Stream(dev)
+    call = idx.bind_search_dev(dq.data_ptr(), 300, k, W, c["sentinel"], gpu.FOUND_ROWS, res[0].data_ptr(), res[1].data_ptr(), st.data_ptr(), stream.cuda_stream)
+    call()
+    torch.cuda.synchronize(dev)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=stream):
+        call()
+    for n, (qs, some) in enumerate(((mixed, True), (none, False), (mixed, True))):
+        one, found, _ = dci.search(c, qs, k, W, 0, 1)
+        exp = dci.search(c, qs, k, W, 0, 0)[0]
+        assert bool((found < k).any()) == some and (not some or ((found < k).sum() >= 5 and (found >= k).sum() >= 5)), "input"
+        dq.copy_(torch.from_numpy(qs.copy()).to(dev))
+        res.zero_()
+        st.zero_()
+        torch.cuda.synchronize(dev)
+        with torch.cuda.stream(stream):
+            g.replay()
+        torch.cuda.synchronize(dev)
+        _assert_dev_contract(res, int(st[0].item()), one, found, exp, k, f"graph replay {n} on the thinned table")
     assert idx.bound_violations() == 0
     del g
     idx.close()

@@ -570,3 +570,65 @@ def test_oracle_reproduces_committed_golden_vectors(oracle):
     assert same(np.stack([oracle.exact_knn(x, ids, q, 6) for q in qs]), g["exact_knn"])
     gi, gg = oracle.grouping_pq(pq, x[[9, 199, 349]], g["grouping_input"])
     assert np.array_equal(gi, g["grouping_ids"]) and np.array_equal(gg, g["grouping_group"])
+
+
+# ---- the round cap (fo_ivfadc_search_capped, fo_ivfadc_batch_search_capped) ----------------------------------------------
+def _capped_fixtures(oracle):
+    """(table dict, oracle handle, queries, k): the tables of the two tests above; the second has 150 cells of four rows on
+    average, so most of its queries need further rounds."""
+    for (N, C, k) in [(3000, 12, 5), (600, 150, 10)]:
+        t = util.ivf_tables(N=N, C=C, K=64)
+        ot = oracle.ivf_table(t["coarse"], t["codebook"], t["list_off"], t["ids"], t["codes"])
+        _, qs = util.queries_from_corpus(N, 40)
+        yield t, ot, qs, k
+
+
+def test_round_cap_zero_is_the_uncapped_search(oracle):
+    """max_rounds = 0 equals the entry points without a cap bit for bit, and reports found >= k or every cell used."""
+    for t, ot, qs, k in _capped_fixtures(oracle):
+        C = t["coarse"].shape[0]
+        for W in (1, 3):
+            for rule, sent in ((0, 1000.0), (1, 100.0)):
+                old = oracle.ivfadc_search_many(ot, qs, k, W, sentinel=sent, found_rule=rule)
+                new, found, rounds = oracle.ivfadc_search_many(ot, qs, k, W, sentinel=sent, found_rule=rule, max_rounds=0)
+                assert old.tobytes() == new.tobytes()
+                assert np.array_equal(np.stack([oracle.ivfadc_search(ot, q, k, W, sentinel=sent, found_rule=rule) for q in qs]), new)
+                assert ((found >= k) | (rounds == -(-C // W))).all() and (rounds >= 1).all()
+        old = oracle.ivfadc_batch_search(ot, qs, k)
+        new, found, rounds = oracle.ivfadc_batch_search(ot, qs, k, max_rounds=0)
+        assert old.tobytes() == new.tobytes() and ((found >= k) | (rounds == C)).all()
+        many = oracle.ivfadc_search_many(ot, qs, k, 1, sentinel=100.0, found_rule=1, max_rounds=0)
+        assert np.array_equal(many[1], found) and np.array_equal(many[2], rounds)
+
+
+@pytest.mark.parametrize("W", [1, 3])
+@pytest.mark.parametrize("rule", [0, 1])
+def test_round_one_list_is_the_search_of_the_first_cells_alone(oracle, W, rule):
+    """An independent derivation of the round-one list: empty every cell but the query's first W, and the UNCAPPED search of that
+    table (which goes on through the empty cells and finds nothing more) gives the capped search's list on the full table.
+    Under the rows rule found is the number of rows in those W cells."""
+    unfinished = 0
+    for t, ot, qs, k in _capped_fixtures(oracle):
+        C = t["coarse"].shape[0]
+        lo = np.asarray(t["list_off"]).astype(np.int64)
+        cell_of = np.repeat(np.arange(C), np.diff(lo))
+        one, found, rounds = oracle.ivfadc_search_many(ot, qs, k, W, found_rule=rule, max_rounds=1)
+        assert (rounds == 1).all()
+        for i, q in enumerate(qs):
+            cd = np.array([oracle.sqdist(q, c) for c in t["coarse"]], f32)
+            sel = [c for c, _ in py_stream(cd, np.arange(C), W, 100.0) if c >= 0]
+            keep = np.isin(cell_of, sel)
+            off = np.concatenate([[0], np.cumsum(np.bincount(cell_of[keep], minlength=C))]).astype(np.int32)
+            sub = oracle.ivf_table(t["coarse"], t["codebook"], off, t["ids"][keep], t["codes"][keep])
+            assert np.array_equal(oracle.ivfadc_search(sub, q, k, W, found_rule=rule), one[i]), (i, sel)
+            rows = int(sum(lo[c + 1] - lo[c] for c in sel))
+            if rule == 0:
+                assert found[i] == rows
+            else:
+                assert found[i] <= rows and (found[i] >= k) == (rows >= k)   # (sentinel 1000: the first k rows are all accepted)
+            unfinished += int(found[i] < k)
+        two = oracle.ivfadc_search_many(ot, qs, k, W, found_rule=rule, max_rounds=2)
+        full = oracle.ivfadc_search_many(ot, qs, k, W, found_rule=rule, max_rounds=0)
+        done = two[1] >= k
+        assert np.array_equal(two[0][done], full[0][done]) and (two[2] <= 2).all() and (two[2][found < k] == 2).all()
+    assert unfinished >= 5, "hardly a query of the fixtures needs a second round: the cap is not exercised"
