@@ -574,10 +574,17 @@ int freddy_gpu_abi_version(void);
  * changes a result.
  *   deployment:  "scan_share" (the batches that share the chip with one of this handle's: the batches the caller keeps in flight
  *                through the *_dev entry points, one stream each, or the other BACKENDS searching at the same time -- a persistent
- *                scan takes n_cus / scan_share CUs; default 0 = auto: the whole chip, or half of it for a host-buffer call that
+ *                scan takes at least n_cus / scan_share workgroups, one per CU, and with "scan_elastic" further ones while CUs are
+ *                free; default 0 = auto: the whole chip, or half of it for a host-buffer call that
  *                starts while another backend (process) of the same GPU is searching: the library keeps a registry of live backends per
  *                physical GPU in /dev/shm and also picks GPU_MAX_HW_QUEUES from it before its first HIP call -- 6 alone, 2 beside
  *                others),
+ *                "scan_elastic" (IVFADC batches with scan_share > 1 through the six-phase scan, i.e. not the whole-slab scan of
+ *                K <= 256 and not batches over a flat PQ table: 1 = a scan also launches extra workgroups, up to
+ *                n_cus - scan_elastic_reserve - reserve_cus * scan_share scan workgroups alive over all streams of the handle; an
+ *                extra takes work entries only while no other batch's scan is announced, and leaves when one is; 2 = every
+ *                extra leaves after its first entry (tests); 0 = off, the default: exactly n_cus / scan_share workgroups),
+ *                "scan_elastic_reserve" (CUs the elastic scans together leave to the other kernels of the batches in flight; 64),
  *                "reserve_cus" (CUs a persistent scan leaves free), "pipeline_batch" / "pipeline_lanes" (host-buffer IVFADC calls:
  *                queries per sub-batch, 2048; sub-batches in flight, 1..4), "coarse_pieces" (1: a call of one sub-batch launches its
  *                cell selection per staged piece of the queries), "lut_budget_mb" (workspace cap per call)
@@ -635,6 +642,11 @@ int64_t freddy_gpu_filter_bound_checked(const freddy_gpu_index_t* index);
  * INCLUDED in freddy_gpu_filter_bound_violations; this returns how many cells the tests' refine-every-cell mode
  * (option check_brackets, bit 1) has checked. */
 int64_t freddy_gpu_coarse_bound_checked(const freddy_gpu_index_t* index);
+/* The elastic scan's four device words (option "scan_elastic") after synchronising the device: out[0] = scan workgroups alive,
+ * out[1] = guaranteed workgroups announced and not yet started (both 0 once every search has finished), out[2] = extra
+ * workgroups that took work since the index was pinned, out[3] = extras that left because another scan was announced.  The
+ * words only steer speed: no result depends on them.  All 0 for a handle that is not an IVF index. */
+int freddy_gpu_scan_elastic_stats(const freddy_gpu_index_t* index, int64_t out[4]);
 
 #ifdef __cplusplus
 }

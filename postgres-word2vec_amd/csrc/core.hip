@@ -45,6 +45,8 @@ Tuning read_tuning() {
   t.scan_kernel = (int)env_int("FREDDY_GPU_FUSED_KERNEL", t.scan_kernel);
   t.reserve_cus = (int)env_int("FREDDY_GPU_RESERVE_CUS", 0);
   t.scan_share = (int)std::max<int64_t>(0, env_int("FREDDY_GPU_SCAN_SHARE", t.scan_share));
+  t.scan_elastic = (int)std::min<int64_t>(2, std::max<int64_t>(0, env_int("FREDDY_GPU_SCAN_ELASTIC", t.scan_elastic)));
+  t.scan_elastic_reserve = (int)std::max<int64_t>(0, env_int("FREDDY_GPU_SCAN_ELASTIC_RESERVE", t.scan_elastic_reserve));
   t.pipeline_batch = (int)std::max<int64_t>(16, env_int("FREDDY_GPU_PIPELINE_BATCH", t.pipeline_batch));
   t.pipeline_lanes = (int)std::min<int64_t>(4, std::max<int64_t>(1, env_int("FREDDY_GPU_PIPELINE_LANES", t.pipeline_lanes)));
   t.pq_fused = (int)env_int("FREDDY_GPU_PQ_FUSED", t.pq_fused);
@@ -184,6 +186,18 @@ extern "C" int64_t freddy_gpu_filter_bound_violations(const freddy_gpu_index_t* 
 extern "C" int64_t freddy_gpu_filter_bound_checked(const freddy_gpu_index_t* ix) { return read_viol(ix, 1); }
 extern "C" int64_t freddy_gpu_coarse_bound_checked(const freddy_gpu_index_t* ix) { return read_viol(ix, 3); }
 
+extern "C" int freddy_gpu_scan_elastic_stats(const freddy_gpu_index_t* ix, int64_t out[4]) {
+  if (!ix || !out) return fail(FREDDY_E_ARG, "NULL argument");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (!ix->elastic) return FREDDY_OK;
+  int32_t h[4] = {0, 0, 0, 0};
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h, ix->elastic, sizeof(h), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 4; ++i) out[i] = h[i];
+  return FREDDY_OK;
+}
+
 extern "C" int freddy_gpu_profile_enable(freddy_gpu_index_t* ix, int32_t enable) {
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   for (auto& kv : ix->prof)
@@ -236,6 +250,15 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   else if (n == "fused_kernel") t.scan_kernel = (int)value;
   else if (n == "reserve_cus") t.reserve_cus = (int)value;
   else if (n == "scan_share") t.scan_share = (int)std::max<int64_t>(0, value);
+  else if (n == "scan_elastic" || n == "scan_elastic_reserve") {
+    if (n == "scan_elastic") t.scan_elastic = (int)std::min<int64_t>(2, std::max<int64_t>(0, value));
+    else t.scan_elastic_reserve = (int)std::max<int64_t>(0, value);
+    if (ix->elastic) {   // the advisory counts start from zero again (a drifted value would only cost speed; no scan is running once the device has drained)
+      HIP_TRY(hipSetDevice(ix->device));
+      HIP_TRY(hipDeviceSynchronize());
+      HIP_TRY(hipMemset(ix->elastic, 0, 2 * sizeof(int32_t)));
+    }
+  }
   else if (n == "join_host_traversal") ix->join.host_traversal = value != 0;
   else if (n == "join_libm_margin_ppm") ix->join.libm_margin = (float)value * 1e-6f;
   else if (n == "sparse_items") t.sparse_items = std::max(-16, std::min(16, (int)value));

@@ -223,6 +223,8 @@ template <int M>
 __global__ __launch_bounds__(256) void entry_record5_kernel(RecordArgs a) {
   const int lane = threadIdx.x & 63;
   const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
+  // the scan behind this launch, announced: the other scans' extra workgroups stop claiming entries (FilterArgs::elastic)
+  if (a.elastic && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_fetch_add(a.elastic + EL_PENDING, a.n_announce, FREDDY_RLX_AGENT);
   if (e >= a.n_groups[0]) return;
   const int cell = a.group_cell[e], first = a.group_first[e], gc = a.group_cnt[e];
   const int cnt = gc & 0xff, chunk = gc >> 8;
@@ -268,8 +270,11 @@ __global__ __launch_bounds__(256) void entry_record5_kernel(RecordArgs a) {
 // U8: the rows' codes as one byte each (K <= 256: what the reference's shipped default indexes use) -- packed8[block][3][64],
 // dword t of a row = its codes 4 t .. 4 t + 3: 12 instead of 24 bytes of codes per row, three code loads per row and entry
 // instead of six (the dword of phases 2 t and 2 t + 1 is the same)
-template <int M, bool FULLK, bool CAND, bool PROF = false, bool U8 = false>
-__global__ __launch_bounds__(SPEC2_T) void ivf_filter5_kernel(FilterArgs a) {
+// ELASTIC: the scan with extra workgroups (FilterArgs::elastic) -- a kernel of its own, ivf_filter5_elastic_kernel: the extras'
+// prologue alone, whatever form it took, moved the register allocation of the whole kernel (scalar spills 28 -> 35 in the builders'
+// preamble), so ivf_filter5_kernel keeps the text and the code it had and a launch without extras runs exactly that
+template <int M, bool FULLK, bool CAND, bool PROF, bool U8, bool ELASTIC>
+__device__ __forceinline__ void ivf_filter5_body(const FilterArgs& a) {
   static_assert(!(U8 && FULLK), "one byte per code: K <= 256");
   constexpr int G = SCAN5_G, RMAX = FUSED_RMAX, NG = SPEC2_NG;
   constexpr int NP = M / 2;             // phases per entry
@@ -296,14 +301,52 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_filter5_kernel(FilterArgs a) {
   const int n_work = a.n_groups[0];
 
   int cur = 0, ei = 0;
-  // The first entry of a workgroup is its own number (the entries are ordered largest first: the grid takes the first gridDim.x of
-  // them, one each); the work counter deals out the entries BEYOND those.  A workgroup so starts with ONE round trip -- its record
+  // The first entry of a workgroup is its own number (the entries are ordered largest first: the grid -- its guaranteed workgroups,
+  // n_own, when it brings extras -- takes the first of them, one each); the work counter deals out the entries BEYOND those.  A workgroup so starts with ONE round trip -- its record
   // and the claim of its second entry together -- instead of two dependent atomics and then the record.
-  if (tid == 0) { gidq[0] = (int)blockIdx.x; gidq[1] = (int)gridDim.x + atomicAdd(a.work_counter, 1); }
-  if (tid < REC_DW) dsc[tid] = a.records[(size_t)blockIdx.x * REC_DW + tid];   // (before n_work is known: the grid never exceeds the records' capacity)
+  // ELASTIC: the first n_own workgroups are the scan's guaranteed ones and start as above; a workgroup beyond them is an EXTRA -- it looks
+  // at the handle's words first and takes an entry from the work counter (one more round trip) only if no other scan is announced and
+  // fewer than `cap` scan workgroups are alive; a declined extra touches no entry.  No workgroup waits for another one, and whatever the
+  // words hold every entry is claimed exactly once.
+  const int n_own = ELASTIC ? a.n_own : (int)gridDim.x;
+  const bool extra = ELASTIC && (int)blockIdx.x >= n_own;
+  if (!extra) {
+    if (tid == 0) {
+      gidq[0] = (int)blockIdx.x; gidq[1] = n_own + atomicAdd(a.work_counter, 1);
+      if constexpr (ELASTIC) {   // a guaranteed workgroup has started: no longer announced, alive if it has an entry
+        __hip_atomic_fetch_sub(a.elastic + EL_PENDING, 1, FREDDY_RLX_AGENT);
+        if ((int)blockIdx.x < n_work) __hip_atomic_fetch_add(a.elastic + EL_ACTIVE, 1, FREDDY_RLX_AGENT);
+      }
+    }
+    if (tid < REC_DW) dsc[tid] = a.records[(size_t)blockIdx.x * REC_DW + tid];   // (before n_work is known: the grid never exceeds the records' capacity)
+  } else if (tid == 0) {
+    // (`pending` still holds this scan's OWN guaranteed workgroups whose decrement has not landed -- on an idle chip the whole grid
+    // starts within a microsecond and every extra found itself announced, none took work.  Every guaranteed workgroup adds one to the
+    // work counter as it starts, so n_own - counter bounds those from above; it is 0 once any n_own claims were made.)
+    const int pend = __hip_atomic_load(a.elastic + EL_PENDING, FREDDY_RLX_AGENT);
+    const int claims = __hip_atomic_load(a.work_counter, FREDDY_RLX_AGENT);
+    const int alive = __hip_atomic_fetch_add(a.elastic + EL_ACTIVE, 1, FREDDY_RLX_AGENT);
+    int g = -1;
+    if (pend - (claims < n_own ? n_own - claims : 0) <= 0 && alive < a.cap) g = n_own + atomicAdd(a.work_counter, 1);
+    if (g < 0 || g >= n_work) {
+      g = -1;
+      __hip_atomic_fetch_sub(a.elastic + EL_ACTIVE, 1, FREDDY_RLX_AGENT);
+    } else {
+      __hip_atomic_fetch_add(a.elastic + EL_STARTED, 1, FREDDY_RLX_AGENT);
+    }
+    // (the tests' elastic_yield = 2: every extra ends after its first entry; otherwise its next look at `pending` is its next claim)
+    const bool leave = g >= 0 && a.elastic_yield == 2;
+    if (leave) __hip_atomic_fetch_add(a.elastic + EL_YIELDED, 1, FREDDY_RLX_AGENT);
+    gidq[0] = g; gidq[1] = (leave || g < 0) ? 0x7fffffff : n_own + atomicAdd(a.work_counter, 1); gidq[2] = leave ? 1 : 0;
+  }
   for (int i = tid; i < 16 * 64; i += SPEC2_T) colmin[i] = 0xffffffffu;
   __syncthreads();
-  if ((int)blockIdx.x >= n_work) return;
+  if (extra) {   // the entry thread 0 has claimed, if any -- and only now its record
+    const int first = __builtin_amdgcn_readfirstlane(gidq[0]);
+    if (first < 0) return;
+    if (tid < REC_DW) dsc[tid] = a.records[(size_t)first * REC_DW + tid];
+    __syncthreads();
+  } else if ((int)blockIdx.x >= n_work) return;
 
   if (builder) {
     // =====================================================================================
@@ -426,7 +469,20 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_filter5_kernel(FilterArgs a) {
           run1 = wave + NG < cn ? a.tau_run[(uint32_t)rc[24 + wave + NG]] : 0u;
         }
         if (j == 0 && tid < REC_DW && have_next) rr0 = a.records[(size_t)ngid * REC_DW + tid];
-        if (j == 0 && tid == 0) gid2 = (int)gridDim.x + atomicAdd(a.work_counter, 1);
+        if (j == 0 && tid == 0) {
+          // (an extra workgroup that finds another scan announced takes no further entry: it ends after the entry it has claimed)
+          // -- and from then on claims nothing: a claim made after the decision to leave would be an entry nobody scans (gidq[2]: the
+          // decision; an extra whose next entry is beyond the table is out of work and claims nothing either)
+          if (extra && (gidq[2] != 0 || !have_next)) {
+            gid2 = 0x7fffffff;
+          } else if (extra && __hip_atomic_load(a.elastic + EL_PENDING, FREDDY_RLX_AGENT) > 0) {
+            gid2 = 0x7fffffff;
+            gidq[2] = 1;
+            __hip_atomic_fetch_add(a.elastic + EL_YIELDED, 1, FREDDY_RLX_AGENT);
+          } else {
+            gid2 = n_own + atomicAdd(a.work_counter, 1);
+          }
+        }
         tick(0);
         lds_barrier();
         tick(1);
@@ -475,6 +531,7 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_filter5_kernel(FilterArgs a) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) qid[u] = nqid[u];
     }
+    if (ELASTIC && tid == 0) __hip_atomic_fetch_sub(a.elastic + EL_ACTIVE, 1, FREDDY_RLX_AGENT);   // (every workgroup that reaches the entry loop counted itself alive)
     if (PROF && a.prof && tid == 0) {
       for (int i = 0; i < 8; ++i) if (i != 2 && i != 4 && i != 5) a.prof[(size_t)blockIdx.x * 8 + i] = pt[i];   // (2, 4, 5: gatherer wave 0)
       a.prof[(size_t)blockIdx.x * 8 + 6] = wall_clock64();
@@ -620,6 +677,16 @@ __global__ __launch_bounds__(SPEC2_T) void ivf_filter5_kernel(FilterArgs a) {
       a.prof[(size_t)blockIdx.x * 8 + 5] = gt[2];
     }
   }
+}
+
+template <int M, bool FULLK, bool CAND, bool PROF = false, bool U8 = false>
+__global__ __launch_bounds__(SPEC2_T) void ivf_filter5_kernel(FilterArgs a) {
+  ivf_filter5_body<M, FULLK, CAND, PROF, U8, false>(a);
+}
+// (a.elastic != NULL, grid >= a.n_own)
+template <int M, bool FULLK, bool CAND, bool U8 = false>
+__global__ __launch_bounds__(SPEC2_T) void ivf_filter5_elastic_kernel(FilterArgs a) {
+  ivf_filter5_body<M, FULLK, CAND, false, U8, true>(a);
 }
 
 }  // namespace freddy

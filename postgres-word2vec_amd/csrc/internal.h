@@ -63,6 +63,10 @@ struct Tuning {
                                // the same time: a persistent scan takes n_cus / share CUs so that the scans run side by side.
                                // An explicit contract -- the library does not guess it; the host-buffer calls multiply it by their lane count
   int reserve_cus = 0;         // FREDDY_GPU_RESERVE_CUS: CUs the persistent scan leaves to the kernels of other streams (RCCL beside the scans)
+  int scan_elastic = 0;        // FREDDY_GPU_SCAN_ELASTIC: a scan with scan_share > 1 brings EXTRA workgroups beyond its n_cus / share, which take work only while
+                               // no other batch's scan is announced and fewer than the cap of scan workgroups are alive (ivfadc.hip ivf_scan_filter, fused5.h):
+                               // 0 off, 1 on, 2 = every extra leaves after its first entry (tests)
+  int scan_elastic_reserve = 64;   // FREDDY_GPU_SCAN_ELASTIC_RESERVE: CUs the elastic scans together leave to the small kernels of the batches in flight
   int pipeline_batch = 2048;   // FREDDY_GPU_PIPELINE_BATCH: queries per sub-batch of the host-buffer pipeline (freddy_gpu_ivfadc_search)
   int pipeline_lanes = 4;      // FREDDY_GPU_PIPELINE_LANES: sub-batches in flight inside one host-buffer call (1..4)
   int lane0_own = 0;           // FREDDY_GPU_LANE0_OWN: 1 = the first pipeline lane on a stream of its own (until round 6) instead of the handle's stream
@@ -221,6 +225,8 @@ struct freddy_gpu_index {
   float* cmaxp = nullptr;       // [m]        max |c_p|, rounded up
   float* cbF = nullptr;         // [m][8 groups][7 steps][64 lanes][8] the codebook in the B-fragment order of the table kernel's matrix instructions (fused5.h query_codebook5_body)
   int32_t* viol = nullptr;      // [4] self-check counters: scan bracket violations / rows checked, coarse bracket violations / cells checked
+  int32_t* elastic = nullptr;   // [4] the elastic scan's advisory words (IVF handles; a 64-byte line of viol's allocation): scan workgroups alive over all
+                                // streams, guaranteed workgroups announced and not yet started, extras that took work, extras that left for another scan
   int32_t* blk_cell = nullptr;  // [blocks]   list of every row block
   int32_t* list_off = nullptr;  // [lists+1] rows
   int32_t* blk_off = nullptr;   // [lists+1] row blocks

@@ -31,9 +31,13 @@ static void (*scan_kernel(bool m12, int V, bool floor))(ScanArgs) {
   return k;
 }
 // ivf_filter8_kernel (whole: the entry's slab stays in LDS, one-byte codes) / ivf_filter5_kernel<12, FULLK, CAND, PROF, U8>.  CAND: the
-// accepted-rows rule doubles the selection code of a kernel larger than the instruction cache; prof (lab): one instantiation per kernel
-static void (*filter_kernel(bool whole, bool u8, bool k1024, bool counts_rows, bool prof))(FilterArgs) {
-  if ((u8 && k1024) || (whole && !u8)) return nullptr;   // (one byte per code: K <= 256)
+// accepted-rows rule doubles the selection code of a kernel larger than the instruction cache; prof (lab): one instantiation per kernel;
+// elastic: ivf_filter5_elastic_kernel, the scan that brings extra workgroups (FilterArgs::elastic)
+static void (*filter_kernel(bool whole, bool u8, bool k1024, bool counts_rows, bool prof, bool elastic = false))(FilterArgs) {
+  if ((u8 && k1024) || (whole && !u8) || (elastic && (whole || prof))) return nullptr;   // (one byte per code: K <= 256)
+  if (elastic && u8) return counts_rows ? &ivf_filter5_elastic_kernel<12, false, true, true> : &ivf_filter5_elastic_kernel<12, false, false, true>;
+  if (elastic && k1024) return counts_rows ? &ivf_filter5_elastic_kernel<12, true, true> : &ivf_filter5_elastic_kernel<12, true, false>;
+  if (elastic) return counts_rows ? &ivf_filter5_elastic_kernel<12, false, true> : &ivf_filter5_elastic_kernel<12, false, false>;
 #ifdef FREDDY_LAB
   if (prof && !counts_rows && whole) return &ivf_filter8_kernel<12, false, true>;
   if (prof && !counts_rows && k1024) return &ivf_filter5_kernel<12, true, false, true>;
@@ -362,6 +366,27 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   hipStream_t s = r.s;
   const int K = ix->K;
   const QueryTable qt = query_table(ws, ix, r.Q);
+  // One persistent workgroup per CU (LDS admits exactly one), never more than there is work.  Batches in flight share the
+  // chip: a persistent scan that took every CU would hold up the small kernels of the other batches until it drains, and
+  // their scans behind them; with n_cus / share GUARANTEED workgroups each, the scans of `share` batches run side by side, the small
+  // kernels fit in between, and a scan's workgroups pull more entries each (a shorter tail).
+  const int scan_cus = std::max(ix->n_cus / std::max(1, r.share), std::min(ix->n_cus, 32)) - ix->tune.reserve_cus;
+  const unsigned n_own = (unsigned)std::min<size_t>(wt.max_groups, (size_t)std::max(1, scan_cus));
+  // K <= 256: one byte per code (packed8) unless option codes_u8 = 0 asks for the int16 layout
+  const bool u8 = ix->packed8 && ix->tune.codes_u8 != 0 && ix->K <= 256;
+  // ... and by default the kernel that keeps the WHOLE entry's slab in LDS (fused8.h; option codes_u8 = 2: fused5.h's one-byte instantiation)
+  const bool whole = u8 && qt.qc8;
+  // Option scan_elastic (an IVFADC batch through ivf_filter5_kernel that shares the chip): while the other batches walk through their
+  // small kernels their quarter of the CUs holds nothing, so the grid also brings EXTRA workgroups -- up to `cap` scan workgroups
+  // alive over all streams of the handle -- which take entries only while no other scan is announced (the record launch of a batch
+  // announces its scan's guaranteed workgroups, one launch ahead) and leave when one is (FilterArgs::elastic).  ivf_filter8_kernel
+  // keeps its fixed grid.
+  bool elastic = ix->tune.scan_elastic > 0 && r.share > 1 && !r.records_ready && !whole && ix->elastic != nullptr;
+#ifdef FREDDY_LAB
+  if (ix->tune.scan_prof) elastic = false;   // (the profiling instantiations have no extras)
+#endif
+  const int cap = ix->n_cus - ix->tune.scan_elastic_reserve - ix->tune.reserve_cus * r.share;
+  const unsigned n_persist = elastic ? (unsigned)std::min<size_t>(wt.max_groups, (size_t)std::max((int)n_own, cap)) : n_own;
   if (!r.records_ready) {   // (a batch over the flat PQ table: pq_front_kernel has written them)
     if (ws->w_records.ensure(sizeof(int32_t) * REC_DW * wt.max_groups)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
     RecordArgs ra;
@@ -369,6 +394,7 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
     ra.sorted_item = ws->w_sorted.as<int32_t>(); ra.item_query = pa.item_query; ra.blk_off = ix->blk_off; ra.list_off = ix->list_off;
     ra.item_dist = pa.item_dist; ra.qn = qt.qn; ra.qscale = qt.qscale; ra.pmax = ix->pmax;
     ra.records = ws->w_records.as<int32_t>(); ra.sentinel = r.sentinel;
+    ra.elastic = elastic ? ix->elastic : nullptr; ra.n_announce = (int)n_own;
     timed_launch(ix, s, "entry_records", [&] {
       hipLaunchKernelGGL((entry_record5_kernel<12>), dim3((unsigned)((wt.max_groups + 3) / 4)), dim3(256), 0, s, ra);
     });
@@ -383,23 +409,14 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   // 96 -> 128 us -- and its merge gains nothing; an IVFADC batch: +2.6 % queries/s with four batches in flight)
   fl.tau_run = r.running_bound ? ws->w_cand.as<uint32_t>() + r.Q : nullptr;
   if (int rc = scan_prof_buffer(ix, ws, &fl.prof, &fl.fence)) return rc;
-  // K <= 256: one byte per code (packed8) unless option codes_u8 = 0 asks for the int16 layout
-  const bool u8 = ix->packed8 && ix->tune.codes_u8 != 0 && K <= 256;
-  // ... and by default the kernel that keeps the WHOLE entry's slab in LDS (fused8.h; option codes_u8 = 2: fused5.h's one-byte instantiation)
-  const bool whole = u8 && qt.qc8;
+  fl.elastic = elastic ? ix->elastic : nullptr; fl.n_own = (int)n_own; fl.cap = cap; fl.elastic_yield = ix->tune.scan_elastic;
   // LDS: slabs [2 buffers][2 positions][K][16 items] int16 (whole: [12 positions][2 halves][256][8 items]), then column minima /
   // thresholds, two entry records, row terms
   const size_t desc_off = whole ? (size_t)scan8_slab_bytes(12) : (size_t)4 * SCAN5_G * 2 * K;
   const size_t flds = desc_off + 4096 + 64 + (2 * REC_DW + 4) * sizeof(int32_t) + 4096 * sizeof(float);
   fl.desc_offset = (uint32_t)desc_off;
-  // One persistent workgroup per CU (LDS admits exactly one), never more than there is work.  Batches in flight share the
-  // chip: a persistent scan that took every CU would hold up the small kernels of the other batches until it drains, and
-  // their scans behind them; with n_cus / share workgroups each, the scans of `share` batches run side by side, the small
-  // kernels fit in between, and a scan's workgroups pull more entries each (a shorter tail).
-  const int scan_cus = std::max(ix->n_cus / std::max(1, r.share), std::min(ix->n_cus, 32)) - ix->tune.reserve_cus;
-  const unsigned n_persist = (unsigned)std::min<size_t>(wt.max_groups, (size_t)std::max(1, scan_cus));
   fl.packed8 = u8 ? ix->packed8 : nullptr;
-  const auto filter = filter_kernel(whole, u8, K == 1024, fl.cand_count != nullptr, fl.prof != nullptr);
+  const auto filter = filter_kernel(whole, u8, K == 1024, fl.cand_count != nullptr, fl.prof != nullptr, elastic);
   if (!filter) return fail(FREDDY_E_ARG, "internal: no filter scan for this shape");
   timed_launch(ix, s, "ivf_filter", [&] { hipLaunchKernelGGL(filter, dim3(n_persist), dim3(SPEC2_T), flds, s, fl); });
   HIP_TRY(hipGetLastError());
@@ -1012,6 +1029,7 @@ std::vector<LdsLimit> lds_limits_ivfadc() {
   for (int i = 0; i < 32; ++i) {   // every kernel the choosers return (one that comes up twice gets its limit twice)
     if (const auto k = scan_kernel(i & 1, 1 << (i >> 2), i & 2)) l.emplace_back(k);   // (V = 1 .. 128: none beyond 16)
     if (const auto k = filter_kernel(i & 1, i & 2, i & 4, i & 8, i & 16)) l.emplace_back(k);
+    if (const auto k = filter_kernel(i & 1, i & 2, i & 4, i & 8, i & 16, true)) l.emplace_back(k);
   }
   return l;
 }

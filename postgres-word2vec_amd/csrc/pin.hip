@@ -493,8 +493,9 @@ extern "C" int freddy_gpu_pin_ivf(const freddy_ivf_desc* t, int device, freddy_g
       }
       if (rc) {} else
       if (upload(&ix->coarseP, cP.data(), cP.size(), &ix->bytes) || upload(&ix->cn2, cn2.data(), cn2.size(), &ix->bytes) ||
-          dev_malloc((void**)&ix->viol, 4 * sizeof(int32_t)) != hipSuccess || hipMemset(ix->viol, 0, 4 * sizeof(int32_t)) != hipSuccess)
+          dev_malloc((void**)&ix->viol, 256) != hipSuccess || hipMemset(ix->viol, 0, 256) != hipSuccess)
         rc = fail(FREDDY_E_NOMEM, "device allocation failed");
+      else ix->elastic = ix->viol + 32;   // the elastic scan's four words (internal.h): bytes 128..143 of the same allocation, a 64-byte line of their own
     }
     if (!rc) { ix->h_coarse.assign(t->coarse, t->coarse + (size_t)t->C * t->d); rc = derive_codebook_tables(ix, t->codebook); }
   }

@@ -57,7 +57,17 @@ struct FilterArgs {
   // selection-then-replay keeps of EXACT keys: DESIGN.md 3); a cut on a cheap bound only has to let every row at or below the
   // query's k-th smallest exact distance through.  (Appended: the fields above keep their offsets.)
   int Lt;
+  // The ELASTIC scan (ivf_filter5_kernel; ivfadc.hip ivf_scan_filter; appended likewise).  elastic = the handle's four advisory words
+  // {active, pending, started, yielded}, NULL: off -- the whole grid is guaranteed, as before.  Workgroups below n_own are the scan's
+  // GUARANTEED ones (own entry by number); those from n_own on are EXTRAS: one takes work only while no scan but its own is announced
+  // (pending) and fewer than `cap` scan workgroups are alive, and stops claiming entries once one is announced (elastic_yield = 2:
+  // after its first entry, whatever the words say -- tests).  Relaxed agent-scope atomics throughout; nobody waits for a value, and a
+  // stale or drifted one costs speed only: every entry is still claimed exactly once from the work counter.
+  int32_t* elastic;
+  int n_own, cap, elastic_yield;
 };
+enum { EL_ACTIVE = 0, EL_PENDING = 1, EL_STARTED = 2, EL_YIELDED = 3 };
+#define FREDDY_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // The integer-slab scan (fused5.h) quantises the table with one scale per query; its margin (derivation there):
 static constexpr int FILT5_VMAX = 2730;   // 12 positions x 2730 = 32760 < 2^15
@@ -156,6 +166,8 @@ struct RecordArgs {
   const float* pmax;
   int32_t* records;
   float sentinel;
+  int32_t* elastic;   // the elastic scan's words (FilterArgs::elastic) or NULL: one thread of the launch announces the scan behind it --
+  int n_announce;     // its guaranteed workgroups are added to `pending` a launch ahead of their start
 };
 
 // ---------------------------------------------------------------------------------------

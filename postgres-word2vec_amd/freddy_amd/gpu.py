@@ -34,6 +34,7 @@ EXPORTS = [
     "freddy_gpu_exact_assign", "freddy_gpu_pq_assign", "freddy_gpu_remove_rows", "freddy_gpu_update_rows",
     "freddy_gpu_set_statistics", "freddy_gpu_get_statistics", "freddy_gpu_create_statistics",
     "freddy_gpu_debug_alloc_fail_nth", "freddy_gpu_debug_alloc_track", "freddy_gpu_debug_alloc_stats",
+    "freddy_gpu_scan_elastic_stats",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together): ids per pass of freddy_gpu_create_statistics
@@ -106,6 +107,8 @@ def load(path=None, optional=()):
     lib.freddy_gpu_filter_bound_checked.argtypes = [C.c_void_p]
     lib.freddy_gpu_coarse_bound_checked.restype = C.c_int64
     lib.freddy_gpu_coarse_bound_checked.argtypes = [C.c_void_p]
+    if "freddy_gpu_scan_elastic_stats" not in optional:
+        lib.freddy_gpu_scan_elastic_stats.argtypes = [C.c_void_p, C.c_void_p]
     lib.freddy_gpu_pin_pq.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.freddy_gpu_pin_ivf.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.freddy_gpu_pin_ivpq.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -295,6 +298,13 @@ class _Index:
     def bound_violations(self):
         """Rows of the filter + refine scan's exact stage whose distance left the proven bracket (must be 0)."""
         return int(self.lib.freddy_gpu_filter_bound_violations(self.h))
+
+    def scan_elastic_stats(self):
+        """The elastic scan's device words (freddy_gpu_scan_elastic_stats; synchronises the device): scan workgroups alive and
+        announced (both 0 between searches), extras that took work and extras that left for another scan since the pin."""
+        v = (C.c_int64 * 4)()
+        _check(self.lib.freddy_gpu_scan_elastic_stats(self.h, v))
+        return {"active": int(v[0]), "pending": int(v[1]), "started": int(v[2]), "yielded": int(v[3])}
 
     def set_option(self, name, value):
         """Tuning / debug switch of this pinned index (include/freddy_gpu.h: freddy_gpu_set_option)."""
