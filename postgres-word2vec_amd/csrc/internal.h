@@ -1,7 +1,9 @@
 // internal.h -- what the translation units of libfreddy_gpu.so share on the HOST side: the handle, its workspaces and
 // options, error reporting, and the functions one unit calls in another.  The C ABI is include/freddy_gpu.h; the units:
 //   core.hip    errors, options, workspaces, profiling records, unpin, counters
-//   pin.hip     pin_pq / pin_ivf(_multi): table layouts; append_rows / remove_rows / update_rows / update_codebook (HBM index mutation; remove_kernels.h, update_kernels.h)
+//   pin.hip     pin_pq / pin_ivf(_multi): table layouts, the codebook's tables, update_codebook; append_rows / remove_rows / update_rows (HBM index mutation:
+//               mutate.h the entry points and one function per handle kind, mutate_host.h the staging owner and what else they share, block_plan.h lists ->
+//               blocks in plain C++, mutate_kernels.h / remove_kernels.h / update_kernels.h the kernels)
 //   ivfadc.hip  the IVFADC search: cell selection, work table, scans, merge; *_dev entry, host-buffer pipeline, one-query launch
 //   pq.hip      pq_search (+ subsets, pseudo-list batches, one-query launch), grouping_pq
 //               ivf_host.h what these two share on the host: shape predicates and sizes, the query table's layout, the run state of a chain, merge arguments
@@ -313,10 +315,13 @@ static inline void timed_launch(freddy_gpu_index* ix, hipStream_t s, const char*
 // The workspace of the stream a search is enqueued on (core.hip).
 Workspace* workspace_for(freddy_gpu_index* ix, hipStream_t s);
 
+// The footprint rule: a device array of n elements occupies, and counts in index_bytes as, one element at least.
+template <class T>
+static inline int64_t counted_bytes(size_t n) { return (int64_t)(sizeof(T) * std::max<size_t>(n, 1)); }
 template <class T>
 static int upload(T** dst, const T* src, size_t n, int64_t* bytes) {
   *dst = nullptr;
-  size_t sz = sizeof(T) * (n ? n : 1);
+  const size_t sz = (size_t)counted_bytes<T>(n);
   if (dev_malloc((void**)dst, sz) != hipSuccess) return -1;
   if (n && hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice) != hipSuccess) return -2;
   if (bytes) *bytes += (int64_t)sz;

@@ -1,4 +1,4 @@
-// remove_kernels.h -- the kernels of freddy_gpu_remove_rows (pin.hip): a stable compaction of the pinned layouts on the device.
+// remove_kernels.h -- the kernels of freddy_gpu_remove_rows (mutate.h): a stable compaction of the pinned layouts on the device.
 //   pq / ivf   64-row blocks [block][M2][64] + pos: keep mask and kept count per block (rm_mark_kernel), exclusive scan of the
 //              counts inside every list (rm_list_scan_kernel), the kept lanes to their new slots (rm_scatter_kernel), code 0 /
 //              pos -1 behind a list's last row (rm_fill_tail_kernel)

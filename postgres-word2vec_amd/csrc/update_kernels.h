@@ -1,6 +1,6 @@
-// update_kernels.h -- the kernels of freddy_gpu_update_rows (pin.hip): rows of a pinned index that keep their id and get a new payload.
+// update_kernels.h -- the kernels of freddy_gpu_update_rows (mutate.h): rows of a pinned index that keep their id and get a new payload.
 //   pq / ivf   64-row blocks [block][M2][64] + pos: where the rows of the update set sit (up_locate_kernel); their code words are
-//              then rewritten in their slots (place_rows_kernel, pin.hip).  An ivf row that changes its cell leaves its list
+//              then rewritten in their slots (place_rows_kernel, mutate_kernels.h).  An ivf row that changes its cell leaves its list
 //              (remove_kernels.h) and joins the end of the new one (append_packed_rows).
 //   ivpq / vectors   row-major arrays: dst[row[j]] <- src[j] (up_scatter_rows_kernel), the mirror of rm_gather_rows_kernel; the
 //              64-row blocks of a vector handle for a list of rows (up_place_vectors_kernel; place_vectors_kernel takes one run)

@@ -1,5 +1,5 @@
 """Plain-Python model of the tables behind a pinned handle under freddy_gpu_append_rows / freddy_gpu_update_codebook
-(include/freddy_gpu.h; postgres-word2vec_amd/csrc/pin.hip).
+(include/freddy_gpu.h; postgres-word2vec_amd/csrc/mutate.h, pin.hip).
 
 One class per handle kind.  Each holds the HOST arrays, applies a mutation the way the header documents it -- pq, ivpq and
 vector rows stay in id order, an ivf row joins the END of its cell's list -- and yields the arrays for a fresh pin

@@ -363,12 +363,12 @@ def _sweep_mutation(gpu, oracle, name, kind, make_model, mutate, mutate_model, f
 
 
 # =======================================================================================
-# scenarios.  FLOORS: device arrays the code path allocates, counted in postgres-word2vec_amd/csrc (pin.hip unless said otherwise)
+# scenarios.  FLOORS: device arrays the code path allocates, counted in postgres-word2vec_amd/csrc (pin.hip and mutate.h / mutate_host.h unless said otherwise)
 # =======================================================================================
 #   derive_codebook_tables_into: cbT always; pq / ivf of the filter shape (m = 12, S = 25): cbR, pmax, cmaxp, cbF (+ cbP: ivf, K <= 1024)
 #   pack_lists: blk_cell, blk_off, list_off, packed, pos = 5;  make_packed8 (K <= 256, m = 12): 1;  make_row_terms (cbR): 1
-#   append_packed_rows: packed, pos, blk_cell, blk_off, list_off + the staged slot, row_pos, codes = 8
-#   remove_packed_rows: d_rm, keep_mask, keep_cnt, prefix, list_keep, d_max = 6, then packed, pos, blk_cell, blk_off, list_off = 5
+#   append_packed_rows: packed, pos, blk_cell, blk_off, list_off (stage_plan) + the staged slot, row_pos, codes = 8
+#   remove_packed_rows: d_rm, keep_mask, keep_cnt, prefix, list_keep, d_max = 6, then packed, pos, blk_cell, blk_off, list_off (stage_plan) = 5
 #   locate_packed_rows: 3;  rewrite_packed_rows: 3
 PQ_SHAPES = {"300x12x256": ((300, 12, 256), 4200), "35x7x16": ((35, 7, 16), 700)}
 PQ_FLOORS = {   # (pin, append, remove, update_rows, update_codebook)
