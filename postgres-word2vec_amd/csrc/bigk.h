@@ -188,17 +188,7 @@ static __global__ __launch_bounds__(BIGK_T) void bigk_replay_kernel(BigkArgs a) 
     a.out_ids[(size_t)q * k + o] = id;
     a.out_dist[(size_t)q * k + o] = d;
   }
-  if (tid == 0) {   // "found" (freddy.c:377 rows rule, :971 accepted rule), as merge_replay_kernel
-    int f = (a.first_round || !a.found) ? 0 : a.found[q];
-    const int rows = a.round_rows ? a.round_rows[x] : 0;
-    f += (a.found_rule == 1 && a.cand_count) ? a.cand_count[q] : (rows > 0 ? rows : 0);
-    if (a.found) a.found[q] = f;
-    if (a.next_active && f < k && rows >= 0) {
-      const int slot = atomicAdd(a.n_next, 1);
-      a.next_active[slot] = q;
-      if (a.status) a.status[0] = 1;
-    }
-  }
+  if (tid == 0) round_end(a, x, q, 0);
 }
 
 }  // namespace freddy

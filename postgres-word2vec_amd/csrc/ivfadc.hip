@@ -856,18 +856,16 @@ static int ivf_one(freddy_gpu_index* ix, const float* queries, int k, int W, flo
   hipStream_t s = ix->stream;
   Workspace* ws = workspace_for(ix, s);
   const int K = ix->K, C = ix->C, L = 2 * k;
-  const size_t lutN = (size_t)12 * K, n_out = (size_t)k;
+  const size_t n_out = (size_t)k;
   const int G = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)ix->n_cus, (int64_t)256, (int64_t)(56 * 1024) / (8 * L)}));
   if (G < W) return 0;   // (an item per workgroup at least)
   const size_t need_out = n_out * 8 + 16;
   if (ix->hio_out.ensure(need_out)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
-  // the hand-off buffer: coarse distances | the W tables | the workgroups' lists | their accepted-row counts
-  const size_t lut_off = (sizeof(float) * ((size_t)C + 8) + 255) & ~(size_t)255;
-  const size_t part_off = (lut_off + sizeof(float) * (size_t)W * lutN + 255) & ~(size_t)255;
-  const size_t cnt_off = (part_off + sizeof(u64) * (size_t)G * L + 255) & ~(size_t)255;
+  // the hand-off buffer (coarse distances | the W tables | the workgroups' lists | their accepted-row counts) and the kernel's LDS
+  const OneLayout lay{K, C, W, L, G};
   uint32_t epoch = 0;
   if (int rc = one_buffer(ws, s, (2ull << 60) | ((uint64_t)C << 44) | ((uint64_t)K << 32) | ((uint64_t)W << 24) | ((uint64_t)G << 12) | (uint64_t)L,
-                          cnt_off + sizeof(uint32_t) * (size_t)G, &epoch)) return rc;
+                          lay.handoff_bytes(), &epoch)) return rc;
   if (one_prof() && ws->w_one.ensure(256)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   int32_t* h_ids = ix->hio_out.as<int32_t>();
   float* h_dist = reinterpret_cast<float*>(h_ids + n_out);
@@ -877,17 +875,14 @@ static int ivf_one(freddy_gpu_index* ix, const float* queries, int k, int W, flo
   memcpy(a.qv, queries, sizeof(a.qv));
   a.coarse = ix->coarse; a.cbT = ix->cbT; a.list_off = ix->list_off; a.blk_off = ix->blk_off; a.packed = ix->packed; a.pos = ix->pos;
   char* ob = ws->w_oneb.as<char>();
-  a.dist_g = reinterpret_cast<float*>(ob); a.lut_g = reinterpret_cast<float*>(ob + lut_off); a.part = reinterpret_cast<u64*>(ob + part_off);
-  a.cnt_g = reinterpret_cast<uint32_t*>(ob + cnt_off);
+  a.dist_g = reinterpret_cast<float*>(ob); a.lut_g = reinterpret_cast<float*>(ob + lay.lut_off()); a.part = reinterpret_cast<u64*>(ob + lay.part_off());
+  a.cnt_g = reinterpret_cast<uint32_t*>(ob + lay.cnt_off());
   a.out_ids = h_ids; a.out_dist = h_dist; a.epoch = epoch; a.err = err;
   a.C = C; a.K = K; a.W = W; a.L = L; a.k = k; a.found_rule = found_rule == FREDDY_FOUND_ROWS ? 0 : 1;
   a.cell_limit = 100.0f; a.sentinel = sentinel;
   a.prof = one_prof() ? ws->w_one.as<unsigned long long>() + 8 : nullptr;
   memcpy(&a.sentinel_bits, &sentinel, 4);
-  const size_t n_mine = ((size_t)C + G - 1) / G;
-  const size_t lds = std::max({(n_mine + 1) * 300 * sizeof(float), (size_t)C * 4 + 64 + 64 * sizeof(u64) + 64,
-                               ((lutN * 4 + 15) & ~(size_t)15) + (size_t)ONE_WAVES * 64 * sizeof(u64),
-                               (size_t)ONE_WAVES * 64 * sizeof(u64) + (size_t)G * L * sizeof(u64)});
+  const size_t lds = lay.lds_bytes();
   if (lds > 60 * 1024) return 0;
   timed_launch(ix, s, "ivf_one", [&] { hipLaunchKernelGGL((ivf_one_kernel<25>), dim3((unsigned)G), dim3(ONE_WG), lds, s, a); });
   HIP_TRY(hipGetLastError());

@@ -347,9 +347,7 @@ __global__ __launch_bounds__(64) void probe_plan_kernel(PlanArgs a) {
     int32_t c_slot = -1;
     wave_list_replay(d_slot, c_slot, W, byp[0], L, [](uint32_t hi) { return (int32_t)hi; });
     const bool have = lane < W && c_slot >= 0;
-    int rows = have ? (a.list_off[c_slot + 1] - a.list_off[c_slot]) : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o, 64);
+    const int rows = wave_round_rows(have, have ? (a.list_off[c_slot + 1] - a.list_off[c_slot]) : 0);   // -1: every cell already used
     if (have) {
       atomicOr(used + (c_slot >> 5), 1u << (c_slot & 31));
       if (a.cell_count) {
@@ -357,8 +355,7 @@ __global__ __launch_bounds__(64) void probe_plan_kernel(PlanArgs a) {
         a.cell_items[(size_t)c_slot * a.cell_cap + at] = x * W + lane;
       }
     }
-    const bool any_cell = __ballot(have) != 0ull;
-    if (lane == 0) a.round_rows[x] = any_cell ? rows : -1;   // -1: every cell already used, the query retires
+    if (lane == 0) a.round_rows[x] = rows;
     if (lane < W) {
       a.item_cell[(size_t)x * W + lane] = c_slot;
       a.item_query[(size_t)x * W + lane] = q;
@@ -906,32 +903,16 @@ __global__ __launch_bounds__(64) void merge_replay_kernel(MergeArgs a) {
     // First round, nothing carried: when no two of the L candidates are equally far, the order of the guarded insertions
     // (freddy.c:128-131) does not matter -- the list is the k nearest below the sentinel in ascending order, which is how
     // the accumulator already holds them.  (Equal distances: the replay in scan order below.)
-    const u64 top = lane < a.L ? acc[0] : KEY_INF;
-    const uint32_t db = (uint32_t)(top >> 32);
-    const uint32_t db_next = (uint32_t)__shfl_down((int)db, 1, 64);
-    const bool tie = lane + 1 < a.L && top != KEY_INF && db == db_next;
-    if (__ballot(tie) == 0ull) {
-      float d_slot = a.sentinel;
-      int32_t id_slot = -1;
-      if (lane < k && top != KEY_INF && __uint_as_float(db) < a.sentinel) {
-        d_slot = __uint_as_float(db);
-        id_slot = a.pos_to_id ? a.pos_to_id[(uint32_t)top] : (int32_t)(uint32_t)top;
-      }
+    float d_slot = a.sentinel;
+    int32_t id_slot = -1;
+    if (wave_list_ascending(d_slot, id_slot, k, lane < a.L ? acc[0] : KEY_INF, a.L,
+                            [&](u64 key) { return key_dist(key) < a.sentinel; },
+                            [&](uint32_t p) { return a.pos_to_id ? a.pos_to_id[p] : (int32_t)p; })) {
       if (lane < k) {
         a.out_ids[(size_t)q * k + lane] = id_slot;
         a.out_dist[(size_t)q * k + lane] = d_slot;
       }
-      if (lane == 0) {
-        int f = 0;
-        const int rows = a.round_rows ? a.round_rows[x] : 0;
-        f += (a.found_rule == 1 && a.cand_count) ? a.cand_count[q] : (rows > 0 ? rows : 0);
-        if (a.found) a.found[q] = f;
-        if (a.next_active && f < k && rows >= 0) {
-          const int slot = atomicAdd(a.n_next, 1);
-          a.next_active[slot] = q;
-          if (a.status) a.status[0] = 1;
-        }
-      }
+      if (lane == 0) round_end(a, x, q, 0);
       return;
     }
   }
@@ -941,17 +922,6 @@ __global__ __launch_bounds__(64) void merge_replay_kernel(MergeArgs a) {
   for (int v = 0; v < V; ++v)
     byp[v] = (acc[v] == KEY_INF || v * 64 + lane >= a.L) ? KEY_INF : ((acc[v] << 32) | (acc[v] >> 32));
   wave_sort_full<V>(byp);
-  auto bookkeeping = [&]() {   // "found" (freddy.c:377 rows rule, :971 accepted rule); one lane
-    int f = a.first_round ? 0 : a.found[q];
-    const int rows = a.round_rows ? a.round_rows[x] : 0;
-    f += (a.found_rule == 1 && a.cand_count) ? a.cand_count[q] : (rows > 0 ? rows : 0);
-    if (a.found) a.found[q] = f;
-    if (a.next_active && f < k && rows >= 0) {   // rows < 0: no cell left, the query retires
-      const int slot = atomicAdd(a.n_next, 1);
-      a.next_active[slot] = q;
-      if (a.status) a.status[0] = 1;
-    }
-  };
   if (V == 1 && k <= 64) {
     // lane i = slot i of the carried list; candidates replayed in scan order
     float d_slot = (a.first_round || lane >= k) ? a.sentinel : a.out_dist[(size_t)q * k + lane];
@@ -964,7 +934,7 @@ __global__ __launch_bounds__(64) void merge_replay_kernel(MergeArgs a) {
       a.out_ids[(size_t)q * k + lane] = id_slot;
       a.out_dist[(size_t)q * k + lane] = d_slot;
     }
-    if (lane == 0) bookkeeping();
+    if (lane == 0) round_end(a, x, q, 0);
     return;
   }
 #pragma unroll
@@ -992,7 +962,7 @@ __global__ __launch_bounds__(64) void merge_replay_kernel(MergeArgs a) {
         maxd = s_d[k - 1];
       }
     }
-    bookkeeping();
+    round_end(a, x, q, 0);
   }
   __syncthreads();
   for (int i = lane; i < k; i += 64) {

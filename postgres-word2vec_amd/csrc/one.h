@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "one_layout.h"
 #include "wave_topk.h"
 
 namespace freddy {
@@ -42,8 +43,7 @@ struct OneArgs {
   uint32_t sentinel_bits;
 };
 
-static constexpr int ONE_WG = 512;
-static constexpr int ONE_WAVES = ONE_WG / 64;
+// (ONE_WG, ONE_WAVES, where the LDS and the hand-off buffer hold what: one_layout.h, which the host reads too)
 // ---- hand-offs without counters: every published word carries the call's epoch ----
 // Distances are sums of squares: >= +0, so the sign bit of a published float -- and bit 63 of a published (distance,
 // position) key -- is free.  A producer stores (value | epoch << 31) with a write-through store and moves on: no drain, no
@@ -184,37 +184,185 @@ __device__ __forceinline__ u64 one_multiway4(const u64* rows, int n, int L, int 
   return out;
 }
 
+// ---------------------------------------------------------------------------------------
+// The stages both kernels run, each once.  (`a`, `tid`, `w` and STAMP_LAST are the kernel's.)
+// ---------------------------------------------------------------------------------------
+#define ONE_STAMP(i) do { if (a.prof && tid == 0 && w == 0) a.prof[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define ONE_STAMP_LAST(i) do { if (a.prof && tid == 0) a.prof[STAMP_LAST + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define ONE_GIVE_UP() do { if (tid == 0) a.err[0] = 1; return; } while (0)   // a bounded poll ran out
+
+template <typename T>
+__device__ __forceinline__ T* one_at(unsigned char* smem, OneRegion r) { return reinterpret_cast<T*>(smem + r.off); }
+
+// Slice poll.  A table of ONE_M * K words was written in slices of cw codes, n_slot per position: wave 0 polls the first word
+// of every slice (a few hundred bytes) until all carry this call's epoch; the full table is then staged and verified word by
+// word (and staged again in the rare case that a slice was still in flight).  All threads call; false: the poll ran out.
+// (a: the kernel's arguments -- the epoch is read from them where it is compared: handed in as a value it stays in a register
+// over the loop, which costs pq_one_kernel two more spilled SGPRs than tests/golden/codegen_ceilings.json allows)
+template <typename A>
+__device__ __forceinline__ bool one_poll_slices(const A& a, float* lut_g, int n_slot, int cw, int K, int wave, int lane, int* flag_sh) {
+  if (wave == 0) {
+    bool ok = false;
+    for (int round = 0; round < ONE_RETRY_LIMIT && !ok; ++round) {
+      bool bad = false;
+      for (int unit = lane; unit < ONE_M * n_slot; unit += 64) {
+        const int p = unit / n_slot, c0 = (unit - p * n_slot) * cw;
+        if (c0 < K) bad |= (__hip_atomic_load(reinterpret_cast<uint32_t*>(lut_g) + p * K + c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 31) != a.epoch;
+      }
+      ok = __ballot(bad) == 0ull;
+      if (!ok) __builtin_amdgcn_s_sleep(8);
+    }
+    if (lane == 0) *flag_sh = ok ? 1 : 0;
+  }
+  __syncthreads();
+  return *flag_sh != 0;
+}
+
+// Scan of the row blocks [b0, b1) by the workgroup's waves (wave x: b0 + x, b0 + x + ONE_WAVES, ...), adc_scan_kernel's loop:
+// a ring of PF row blocks per wave in flight, the ADC sum in position order (index_utils.c:1126-1133), WaveSelect of the L
+// smallest (distance, position) keys.  prime() requests the first PF blocks -- the kernels issue it BEFORE they poll for the
+// table, so that the rows fly across the hand-off; run() needs the table in LDS.
+template <int PF>
+struct OneScan {
+  static constexpr int M2T = ONE_M / 2;
+  RowBlock<M2T> ring[PF];
+  const uint32_t* packed;
+  const int32_t* pos;
+  int b, b1, lane;
+
+  __device__ __forceinline__ void init(const uint32_t* packed_, const int32_t* pos_, int b0, int b1_, int wave, int lane_) {
+    packed = packed_; pos = pos_; b = b0 + wave; b1 = b1_; lane = lane_;
+  }
+  __device__ __forceinline__ void fetch(RowBlock<M2T>& rb, int blk) const {
+    const int bc = blk < b1 ? blk : b1 - 1;           // (past the end: a repeat of the last block, never used)
+    const uint32_t* pk = packed + (size_t)bc * M2T * 64 + lane;
+#pragma unroll
+    for (int j = 0; j < M2T; ++j) rb.w[j] = pk[j * 64];
+    rb.p = pos[(size_t)bc * 64 + lane];
+  }
+  __device__ __forceinline__ void prime() {
+#pragma unroll
+    for (int u = 0; u < PF; ++u) fetch(ring[u], b + u * ONE_WAVES);
+  }
+  // COUNT: returns this wave's rows below the sentinel (the accepted-row count, freddy.c:971), in every lane; else 0.
+  template <bool COUNT>
+  __device__ __forceinline__ int run(const float* lut, int K, WaveSelect<1>& sel, u64 sentinel_key) {
+    int accepted = 0;
+    for (; b < b1; b += PF * ONE_WAVES) {
+      u64 keys[PF];
+      uint32_t mn = 0xffffffffu;   // this lane's smallest distance (bits) among the group's valid rows
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const RowBlock<M2T> cur = ring[u];
+        const int bu = b + u * ONE_WAVES;
+        if (bu + PF * ONE_WAVES < b1) fetch(ring[u], bu + PF * ONE_WAVES);   // (wave-uniform)
+        keys[u] = KEY_INF;
+        if (bu < b1) {   // wave-uniform
+          float dist = 0.0f;
+#pragma unroll
+          for (int l = 0; l < ONE_M; ++l) {
+            const uint32_t code = (l & 1) ? (cur.w[l >> 1] >> 16) : (cur.w[l >> 1] & 0xffffu);
+            dist = dist + lut[l * K + code];
+          }
+          if (cur.p >= 0) {
+            keys[u] = make_key(dist, (uint32_t)cur.p);
+            mn = min(mn, __float_as_uint(dist));
+          }
+          if (COUNT) accepted += __popcll(__ballot(cur.p >= 0 && keys[u] < sentinel_key));
+        }
+      }
+      // L rows of the group are at most as far as the L-th smallest lane minimum: nothing farther can be among the L
+      // smallest keys (one 32-bit sort instead of a 64-bit sort + merge per 64 passing keys while the threshold is loose)
+      const uint32_t dL = (uint32_t)__builtin_amdgcn_readlane((int)wave_sort32(mn), sel.L - 1);
+      const u64 bound = ((u64)dL << 32) | 0xffffffffull;
+      if (bound < sel.tau) sel.tau = bound;
+#pragma unroll
+      for (int u = 0; u < PF; ++u)
+        if (b + u * ONE_WAVES < b1) sel.push(keys[u], keys[u] != KEY_INF);
+    }
+    sel.finish();
+    return accepted;
+  }
+};
+
+// Publish.  The eight waves' lists meet in LDS (the table is dead by now), wave 0 merges them and publishes the workgroup's
+// list rank-major: part[r * G + w].  cnt_g != NULL: the workgroup's accepted-row count *acc_sh rides along, tagged.
+__device__ __forceinline__ void one_publish(u64* lists, u64 wave_list, int L, u64* part, uint32_t* cnt_g, const int* acc_sh, int G, int w,
+                                            uint32_t ep, int wave, int lane) {
+  __syncthreads();
+  lists[lane * ONE_WAVES + wave] = wave_list;   // [64 ranks][ONE_WAVES]
+  __syncthreads();
+  if (wave == 0) {
+    const u64 mine = one_multiway(lists, ONE_WAVES, ONE_WAVES, L, lane);
+    if (lane < L) __hip_atomic_store(part + (size_t)lane * G + w, one_tag_key(mine, ep), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cnt_g && lane == 0) __hip_atomic_store(cnt_g + w, (uint32_t)*acc_sh | (ep << 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// Collect, workgroup 0: the G published lists -> all[L][G] (as published), re-read until every word carries this call's
+// epoch.  cnt_g != NULL: the workgroups' counts are checked too and summed into *acc_sh.  False: the poll ran out.
+__device__ __forceinline__ bool one_collect(u64* part, u64* all, int total, uint32_t* cnt_g, int G, uint32_t ep, int tid, int* retry_sh, int* acc_sh) {
+  bool ok = false;
+  for (int round = 0; round < ONE_RETRY_LIMIT && !ok; ++round) {
+    if (tid == 0) { *retry_sh = 0; if (cnt_g) *acc_sh = 0; }
+    __syncthreads();
+    bool bad = false;
+    for (int i = tid; i < total; i += ONE_WG) {
+      const u64 word = __hip_atomic_load(part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      bad |= (uint32_t)(word >> 63) != ep;
+      all[i] = one_untag_key(word);
+    }
+    if (cnt_g) {
+      int cnt = 0;
+      for (int i = tid; i < G; i += ONE_WG) {
+        const uint32_t word = __hip_atomic_load(cnt_g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        bad |= (word >> 31) != ep;
+        cnt += (int)(word & 0x7fffffffu);
+      }
+      if (cnt) atomicAdd(acc_sh, cnt);
+    }
+    if (bad) *retry_sh = 1;
+    __syncthreads();
+    ok = *retry_sh == 0;
+    __syncthreads();   // (everyone has read the flag before the next round clears it)
+    if (!ok) __builtin_amdgcn_s_sleep(8);
+  }
+  return ok;
+}
+
+// Finish, one wave: the list goes to (mapped host) memory, and only when it is there the word the host polls.
+__device__ __forceinline__ void one_finish(int32_t* out_ids, float* out_dist, int k, int32_t id_slot, float d_slot, int32_t* err, int verdict,
+                                           int lane, unsigned long long* stamp) {
+  if (lane < k) {
+    out_ids[lane] = id_slot;
+    out_dist[lane] = d_slot;
+  }
+  if (stamp && lane == 0) *stamp = __builtin_amdgcn_s_memrealtime();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  if (lane == 0) __hip_atomic_store(err, verdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 template <int S>
 __global__ __launch_bounds__(ONE_WG) void pq_one_kernel(OneArgs a) {
-  constexpr int M = 12, M2T = 6;
+  constexpr int M = ONE_M, STAMP_LAST = 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int flag_sh, retry_sh;
-  const int K = a.K, lutN = M * K;
-  float* lut = reinterpret_cast<float*>(smem);
-  u64* stage = reinterpret_cast<u64*>(smem + (((size_t)lutN * 4 + 15) & ~(size_t)15));
+  const int K = a.K;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int w = blockIdx.x, G = gridDim.x;
-#define ONE_STAMP(i) do { if (a.prof && tid == 0 && w == 0) a.prof[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define ONE_STAMP_LAST(i) do { if (a.prof && tid == 0) a.prof[8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+  const OneLayout lay{K, 0, 1, a.L, G};
   ONE_STAMP(0);
 
   // (the first row blocks of every wave are requested between the drain of the table slice and the barrier's poll)
   const int b0 = a.blk_off[0] + w * a.chunk_blocks;
   int b1 = a.blk_off[1];
   if (b0 + a.chunk_blocks < b1) b1 = b0 + a.chunk_blocks;
-  constexpr int PF = 8;
-  RowBlock<M2T> ring[PF];
-  auto fetch = [&](RowBlock<M2T>& rb, int blk) {
-    const int bc = blk < b1 ? blk : b1 - 1;           // (past the end: a repeat of the last block, never used)
-    const uint32_t* pk = a.packed + (size_t)bc * M2T * 64 + lane;
-#pragma unroll
-    for (int j = 0; j < M2T; ++j) rb.w[j] = pk[j * 64];
-    rb.p = a.pos[(size_t)bc * 64 + lane];
-  };
-  int b = b0 + wave;
+  OneScan<8> scan;
+  scan.init(a.packed, a.pos, b0, b1, wave, lane);
   // ---- 1. this workgroup's slice of the table: unit = (position, range of codes) ----
   {
-    static_assert(M * S == 300, "the query travels as 300 floats");
+    static_assert(M * S == ONE_D, "the query travels as 300 floats");
     const int n_slot = G >= M ? G / M : 1, cw = (K + n_slot - 1) / n_slot;
     for (int unit = w; unit < M * n_slot; unit += G) {
       const int p = unit / n_slot, c0 = (unit - p * n_slot) * cw;   // (p: workgroup-uniform)
@@ -234,145 +382,41 @@ __global__ __launch_bounds__(ONE_WG) void pq_one_kernel(OneArgs a) {
       }
     }
     ONE_STAMP(1);
-    if (b0 < b1) {   // (the first row blocks of every wave: in flight while the table arrives)
-#pragma unroll
-      for (int u = 0; u < PF; ++u) fetch(ring[u], b + u * ONE_WAVES);
-    }
-    // the first word of every slice is polled (a few hundred bytes) until all carry this call's epoch; the full table is
-    // then staged and verified word by word (and staged again in the rare case that a slice was still in flight)
-    if (wave == 0) {
-      bool ok = false;
-      for (int round = 0; round < ONE_RETRY_LIMIT && !ok; ++round) {
-        bool bad = false;
-        for (int unit = lane; unit < M * n_slot; unit += 64) {
-          const int p = unit / n_slot, c0 = (unit - p * n_slot) * cw;
-          if (c0 < K) bad |= (__hip_atomic_load(reinterpret_cast<uint32_t*>(a.lut_g) + p * K + c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 31) != a.epoch;
-        }
-        ok = __ballot(bad) == 0ull;
-        if (!ok) __builtin_amdgcn_s_sleep(8);
-      }
-      if (lane == 0) flag_sh = ok ? 1 : 0;
-    }
-    __syncthreads();
-    if (!flag_sh) { if (tid == 0) a.err[0] = 1; return; }
+    if (b0 < b1) scan.prime();   // (the first row blocks of every wave: in flight while the table arrives)
+    if (!one_poll_slices(a, a.lut_g, n_slot, cw, K, wave, lane, &flag_sh)) ONE_GIVE_UP();
     ONE_STAMP(2);
   }
 
   // ---- 2. the table -> LDS, this workgroup's chunk of row blocks ----
   WaveSelect<1> sel;
   const u64 sentinel_key = (u64)a.sentinel_bits << 32;   // key < this  <=>  dist < sentinel
-  sel.init(stage + wave * 64, sentinel_key, a.L);
+  sel.init(one_at<u64>(smem, lay.wave_rows()) + wave * 64, sentinel_key, a.L);
   if (b0 < b1) {   // workgroup-uniform
-    if (!one_stage_tagged(a.lut_g, lut, lutN, lutN, a.epoch, tid, &retry_sh)) { if (tid == 0) a.err[0] = 1; return; }
+    float* lut = one_at<float>(smem, lay.table());
+    if (!one_stage_tagged(a.lut_g, lut, M * K, M * K, a.epoch, tid, &retry_sh)) ONE_GIVE_UP();
     ONE_STAMP(3);
-    for (; b < b1; b += PF * ONE_WAVES) {
-      u64 keys[PF];
-      uint32_t mn = 0xffffffffu;   // this lane's smallest distance (bits) among the group's valid rows
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const RowBlock<M2T> cur = ring[u];
-        const int bu = b + u * ONE_WAVES;
-        if (bu + PF * ONE_WAVES < b1) fetch(ring[u], bu + PF * ONE_WAVES);   // (wave-uniform)
-        keys[u] = KEY_INF;
-        if (bu < b1) {   // wave-uniform
-          float dist = 0.0f;
-#pragma unroll
-          for (int l = 0; l < M; ++l) {
-            const uint32_t code = (l & 1) ? (cur.w[l >> 1] >> 16) : (cur.w[l >> 1] & 0xffffu);
-            dist = dist + lut[l * K + code];
-          }
-          if (cur.p >= 0) {
-            keys[u] = make_key(dist, (uint32_t)cur.p);
-            mn = min(mn, __float_as_uint(dist));
-          }
-        }
-      }
-      // L rows of the group are at most as far as the L-th smallest lane minimum: nothing farther can be among the L
-      // smallest keys (one 32-bit sort instead of a 64-bit sort + merge per 64 passing keys while the threshold is loose)
-      const uint32_t dL = (uint32_t)__builtin_amdgcn_readlane((int)wave_sort32(mn), a.L - 1);
-      const u64 bound = ((u64)dL << 32) | 0xffffffffull;
-      if (bound < sel.tau) sel.tau = bound;
-#pragma unroll
-      for (int u = 0; u < PF; ++u)
-        if (b + u * ONE_WAVES < b1) sel.push(keys[u], keys[u] != KEY_INF);
-    }
-    sel.finish();
+    scan.run<false>(lut, K, sel, sentinel_key);
   }
   ONE_STAMP(4);
-  // the eight waves' lists meet in LDS (the table is dead by now), wave 0 merges them and publishes the workgroup's list
-  // rank-major: part[r * G + w]
-  __syncthreads();
-  u64* lists = reinterpret_cast<u64*>(smem);   // [64 ranks][ONE_WAVES]
-  lists[lane * ONE_WAVES + wave] = sel.acc[0];
-  __syncthreads();
-  if (wave == 0) {
-    const u64 mine = one_multiway(lists, ONE_WAVES, ONE_WAVES, a.L, lane);
-    if (lane < a.L) __hip_atomic_store(a.part + (size_t)lane * G + w, one_tag_key(mine, a.epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  one_publish(one_at<u64>(smem, lay.lists()), sel.acc[0], a.L, a.part, nullptr, nullptr, G, w, a.epoch, wave, lane);
   ONE_STAMP(5);
   if (w != 0) return;   // (workgroup 0 collects the lists)
   ONE_STAMP_LAST(0);
 
   // ---- 3. the last workgroup: multiway merge of the G lists (lane <-> list, 64 lists per wave), replay ----
-  {
-    u64* all = reinterpret_cast<u64*>(smem) + ONE_WAVES * 64;   // [L][G] as published; behind the waves' result rows
-    const int total = G * a.L;
-    {
-      bool ok = false;
-      for (int round = 0; round < ONE_RETRY_LIMIT && !ok; ++round) {
-        if (tid == 0) retry_sh = 0;
-        __syncthreads();
-        bool bad = false;
-        for (int i = tid; i < total; i += ONE_WG) {
-          const u64 word = __hip_atomic_load(a.part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          bad |= (uint32_t)(word >> 63) != a.epoch;
-          all[i] = one_untag_key(word);
-        }
-        if (bad) retry_sh = 1;
-        __syncthreads();
-        ok = retry_sh == 0;
-        __syncthreads();   // (everyone has read the flag before the next round clears it)
-        if (!ok) __builtin_amdgcn_s_sleep(8);
-      }
-      if (!ok) { if (tid == 0) a.err[0] = 1; return; }
-    }
-    // one wave, lane <-> the lists x = lane, lane + 64, ... (<= 4 for 256 CUs): each round takes the smallest head
-    if (wave != 0) return;
-    ONE_STAMP_LAST(1);
-    const u64 top = one_multiway4(all, G, a.L, lane);
-    // The reference's pass inserts in scan order behind a guard "dist < maxDist" (freddy.c:128-131): when no two of the 2k
-    // candidates have the same distance, the order of insertion does not matter and the list is the k smallest in ascending
-    // order (those below the sentinel).  Equal distances among them: re-key as (position, distance bits), sort, replay.
-    const uint32_t db = (uint32_t)(top >> 32);
-    const uint32_t db_next = (uint32_t)__shfl_down((int)db, 1, 64);
-    const bool tie = lane + 1 < a.L && top != KEY_INF && db == db_next;   // (top is ascending: equal distances are neighbours; KEY_INF's word is not a distance)
-    float d_slot = a.sentinel;
-    int32_t id_slot = -1;
-    if (__ballot(tie) == 0ull) {
-      if (lane < a.k && top != KEY_INF && __uint_as_float(db) < a.sentinel) {
-        d_slot = __uint_as_float(db);
-        id_slot = a.pos_to_id ? a.pos_to_id[(uint32_t)top] : (int32_t)(uint32_t)top;
-      }
-    } else {
-      u64 byp[1];
-      byp[0] = (top == KEY_INF || lane >= a.L) ? KEY_INF : ((top << 32) | (top >> 32));
-      wave_sort_full<1>(byp);
-      if (a.pos_to_id && byp[0] != KEY_INF) byp[0] = ((u64)(uint32_t)a.pos_to_id[(uint32_t)(byp[0] >> 32)] << 32) | (u64)(uint32_t)byp[0];
-      wave_list_replay(d_slot, id_slot, a.k, byp[0], a.L < 64 ? a.L : 64, [](uint32_t id) { return (int32_t)id; });
-    }
-    if (lane < a.k) {
-      a.out_ids[lane] = id_slot;
-      a.out_dist[lane] = d_slot;
-    }
-    ONE_STAMP_LAST(2);
-    // the list is in (mapped host) memory before the word the host polls
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    if (lane == 0) __hip_atomic_store(a.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  u64* all = one_at<u64>(smem, lay.all_lists());   // behind the waves' result rows
+  if (!one_collect(a.part, all, G * a.L, nullptr, G, a.epoch, tid, &retry_sh, nullptr)) ONE_GIVE_UP();
+  // one wave, lane <-> the lists x = lane, lane + 64, ... (<= 4 for 256 CUs): each round takes the smallest head
+  if (wave != 0) return;
+  ONE_STAMP_LAST(1);
+  const u64 top = one_multiway4(all, G, a.L, lane);
+  // The reference's pass inserts in scan order behind a guard "dist < maxDist" (freddy.c:128-131): wave_list_from_sorted
+  float d_slot = a.sentinel;
+  int32_t id_slot = -1;
+  wave_list_from_sorted(d_slot, id_slot, a.k, top, a.L, [&](u64 key) { return key_dist(key) < a.sentinel; },
+                        [&](uint32_t p) { return a.pos_to_id ? a.pos_to_id[p] : (int32_t)p; });
+  one_finish(a.out_ids, a.out_dist, a.k, id_slot, d_slot, a.err, 2, lane, a.prof ? a.prof + STAMP_LAST + 2 : nullptr);
 }
-#undef ONE_STAMP
-#undef ONE_STAMP_LAST
 
 // ---------------------------------------------------------------------------------------
 // ivfadc_search for ONE query as a single launch: the reference's own call shape (freddy.c:174-393).  The generic path is
@@ -412,23 +456,22 @@ struct IvfOneArgs {
 
 template <int S>
 __global__ __launch_bounds__(ONE_WG) void ivf_one_kernel(IvfOneArgs a) {
-  constexpr int M = 12, M2T = 6, D = M * S;
-  static_assert(D == 300, "the query travels as 300 floats");
+  constexpr int M = ONE_M, D = M * S, STAMP_LAST = 10;
+  static_assert(D == ONE_D, "the query travels as 300 floats");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int flag_sh, retry_sh, acc_sh;
   __shared__ int32_t cells_sh[32];
   const int K = a.K, lutN = M * K, C = a.C, W = a.W;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int w = blockIdx.x, G = gridDim.x;
-#define ONE_STAMP(i) do { if (a.prof && tid == 0 && w == 0) a.prof[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define ONE_STAMP_LAST(i) do { if (a.prof && tid == 0) a.prof[10 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+  const OneLayout lay{K, C, W, a.L, G};
   ONE_STAMP(0);
 
   // ---- A. coarse distances of the cells w, w + G, ... ----
   {
-    float* crow = reinterpret_cast<float*>(smem);   // [cells of this workgroup][D], then the query
     const int n_mine = w < C ? (C - w + G - 1) / G : 0;
-    float* qs = crow + n_mine * D;
+    float* crow = one_at<float>(smem, lay.coarse_rows(n_mine));   // [cells of this workgroup][D], then the query
+    float* qs = one_at<float>(smem, lay.query(n_mine));
     for (int i = tid; i < n_mine * D; i += ONE_WG) {
       const int ci = i / D, j = i - ci * D;
       crow[i] = a.coarse[(size_t)(w + ci * G) * D + j];
@@ -459,12 +502,11 @@ __global__ __launch_bounds__(ONE_WG) void ivf_one_kernel(IvfOneArgs a) {
   }
 
   // ---- B. the W nearest cells (every workgroup for itself) ----
-  int my_rows = 0;
-  bool any_cell = false;
+  int my_rows = 0;      // wave 0: the rows of this lane's cell (summed by the last arriver)
+  bool my_have = false;
   {
-    float* dl = reinterpret_cast<float*>(smem);                       // [C rounded up to 4]
-    u64* prow = reinterpret_cast<u64*>(smem + (((size_t)C * 4 + 63) & ~(size_t)15));   // [64] wave 0's staging row
-    if (!one_stage_tagged(a.dist_g, dl, (C + 3) & ~3, C, a.epoch, tid, &retry_sh)) { if (tid == 0) a.err[0] = 1; return; }
+    float* dl = one_at<float>(smem, lay.cell_dist());   // [C rounded up to 4]
+    if (!one_stage_tagged(a.dist_g, dl, (C + 3) & ~3, C, a.epoch, tid, &retry_sh)) ONE_GIVE_UP();
     ONE_STAMP(2);
     if (wave == 0) {
       const int L2 = 2 * W;
@@ -475,31 +517,19 @@ __global__ __launch_bounds__(ONE_WG) void ivf_one_kernel(IvfOneArgs a) {
       const uint32_t dL = (uint32_t)__builtin_amdgcn_readlane((int)wave_sort32(mn), L2 - 1);
       const u64 bound = ((u64)dL << 32) | 0xffffffffull;
       WaveSelect<1> sel;
-      sel.init(prow, bound < limit ? bound : limit, L2);
+      sel.init(one_at<u64>(smem, lay.cell_row()), bound < limit ? bound : limit, L2);
       for (int base = 0; base < C; base += 64) {
         const int j = base + lane;
         sel.push(make_key(dl[j < C ? j : C - 1], (uint32_t)j), j < C);
       }
       sel.finish();
-      // the reference keeps its W nearest cells by guarded insertion in cell order (freddy.c:266-283): with no two of the
-      // 2W candidates equally far that is the W smallest below the limit in ascending order; otherwise the replay
-      const u64 top = lane < L2 ? sel.acc[0] : KEY_INF;
-      const uint32_t db = (uint32_t)(top >> 32);
-      const uint32_t db_next = (uint32_t)__shfl_down((int)db, 1, 64);
-      const bool tie = lane + 1 < L2 && top != KEY_INF && db == db_next;
+      // the reference keeps its W nearest cells by guarded insertion in cell order (freddy.c:266-283)
       float d_slot = a.cell_limit;
       int32_t c_slot = -1;
-      if (__ballot(tie) == 0ull) {
-        if (lane < W && top != KEY_INF && top < limit) { d_slot = __uint_as_float(db); c_slot = (int32_t)(uint32_t)top; }
-      } else {
-        u64 byp[1];
-        byp[0] = top == KEY_INF ? KEY_INF : ((top << 32) | (top >> 32));
-        wave_sort_full<1>(byp);
-        wave_list_replay(d_slot, c_slot, W, byp[0], L2, [](uint32_t hi) { return (int32_t)hi; });
-      }
-      const bool have = lane < W && c_slot >= 0;
-      my_rows = have ? (a.list_off[c_slot + 1] - a.list_off[c_slot]) : 0;   // (summed by the last arriver's wave 0)
-      any_cell = __ballot(have) != 0ull;
+      wave_list_from_sorted(d_slot, c_slot, W, lane < L2 ? sel.acc[0] : KEY_INF, L2, [&](u64 key) { return key < limit; },
+                            [](uint32_t cell) { return (int32_t)cell; });
+      my_have = lane < W && c_slot >= 0;
+      my_rows = my_have ? (a.list_off[c_slot + 1] - a.list_off[c_slot]) : 0;
       if (lane < 32) cells_sh[lane] = lane < W ? c_slot : -1;
     }
     __syncthreads();
@@ -517,16 +547,8 @@ __global__ __launch_bounds__(ONE_WG) void ivf_one_kernel(IvfOneArgs a) {
     b0 = c0 + (w - my_item * P) * chunk;
     b1 = b0 + chunk < c1 ? b0 + chunk : c1;
   }
-  constexpr int PF = 4;
-  RowBlock<M2T> ring[PF];
-  auto fetch = [&](RowBlock<M2T>& rb, int blk) {
-    const int bc = blk < b1 ? blk : b1 - 1;
-    const uint32_t* pk = a.packed + (size_t)bc * M2T * 64 + lane;
-#pragma unroll
-    for (int j = 0; j < M2T; ++j) rb.w[j] = pk[j * 64];
-    rb.p = a.pos[(size_t)bc * 64 + lane];
-  };
-  int b = b0 + wave;
+  OneScan<4> scan;
+  scan.init(a.packed, a.pos, b0, b1, wave, lane);
 
   // ---- C. the items' tables in slices: unit = (item, position, range of codes) ----
   {
@@ -558,154 +580,49 @@ __global__ __launch_bounds__(ONE_WG) void ivf_one_kernel(IvfOneArgs a) {
       }
     }
     ONE_STAMP(4);
-    if (b0 < b1) {   // (the first row blocks in flight while the item's table arrives)
-#pragma unroll
-      for (int u = 0; u < PF; ++u) fetch(ring[u], b + u * ONE_WAVES);
-      // the first word of every slice of this workgroup's item is polled until all carry this call's epoch
-      if (wave == 0) {
-        bool ok = false;
-        for (int round = 0; round < ONE_RETRY_LIMIT && !ok; ++round) {
-          bool bad = false;
-          for (int unit = lane; unit < M * n_slot; unit += 64) {
-            const int p = unit / n_slot, c0 = (unit - p * n_slot) * cw;
-            if (c0 < K) bad |= (__hip_atomic_load(reinterpret_cast<uint32_t*>(a.lut_g) + (size_t)my_item * lutN + p * K + c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 31) != a.epoch;
-          }
-          ok = __ballot(bad) == 0ull;
-          if (!ok) __builtin_amdgcn_s_sleep(8);
-        }
-        if (lane == 0) flag_sh = ok ? 1 : 0;
-      }
-      __syncthreads();
-      if (!flag_sh) { if (tid == 0) a.err[0] = 1; return; }
+    if (b0 < b1) {   // (the first row blocks in flight while the item's table arrives: the slices of this workgroup's item are polled)
+      scan.prime();
+      if (!one_poll_slices(a, a.lut_g + (size_t)my_item * lutN, n_slot, cw, K, wave, lane, &flag_sh)) ONE_GIVE_UP();
     }
     ONE_STAMP(5);
   }
 
   // ---- D. the item's table -> LDS, this workgroup's row blocks ----
-  float* lut = reinterpret_cast<float*>(smem);
-  u64* stage = reinterpret_cast<u64*>(smem + (((size_t)lutN * 4 + 15) & ~(size_t)15));
   WaveSelect<1> sel;
   const u64 sentinel_key = (u64)a.sentinel_bits << 32;
-  sel.init(stage + wave * 64, sentinel_key, a.L);
+  sel.init(one_at<u64>(smem, lay.wave_rows()) + wave * 64, sentinel_key, a.L);
   int accepted = 0;
   if (b0 < b1) {   // workgroup-uniform
-    if (!one_stage_tagged(a.lut_g + (size_t)my_item * lutN, lut, lutN, lutN, a.epoch, tid, &retry_sh)) { if (tid == 0) a.err[0] = 1; return; }
+    float* lut = one_at<float>(smem, lay.table());
+    if (!one_stage_tagged(a.lut_g + (size_t)my_item * lutN, lut, lutN, lutN, a.epoch, tid, &retry_sh)) ONE_GIVE_UP();
     ONE_STAMP(6);
-    for (; b < b1; b += PF * ONE_WAVES) {
-      u64 keys[PF];
-      uint32_t mn = 0xffffffffu;
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const RowBlock<M2T> cur = ring[u];
-        const int bu = b + u * ONE_WAVES;
-        if (bu + PF * ONE_WAVES < b1) fetch(ring[u], bu + PF * ONE_WAVES);   // (wave-uniform)
-        keys[u] = KEY_INF;
-        if (bu < b1) {   // wave-uniform
-          float dist = 0.0f;
-#pragma unroll
-          for (int l = 0; l < M; ++l) {
-            const uint32_t code = (l & 1) ? (cur.w[l >> 1] >> 16) : (cur.w[l >> 1] & 0xffffu);
-            dist = dist + lut[l * K + code];
-          }
-          if (cur.p >= 0) {
-            keys[u] = make_key(dist, (uint32_t)cur.p);
-            mn = min(mn, __float_as_uint(dist));
-          }
-          accepted += __popcll(__ballot(cur.p >= 0 && keys[u] < sentinel_key));
-        }
-      }
-      const uint32_t dL = (uint32_t)__builtin_amdgcn_readlane((int)wave_sort32(mn), a.L - 1);
-      const u64 bound = ((u64)dL << 32) | 0xffffffffull;
-      if (bound < sel.tau) sel.tau = bound;
-#pragma unroll
-      for (int u = 0; u < PF; ++u)
-        if (b + u * ONE_WAVES < b1) sel.push(keys[u], keys[u] != KEY_INF);
-    }
-    sel.finish();
+    accepted = scan.run<true>(lut, K, sel, sentinel_key);
   }
   ONE_STAMP(7);
   if (lane == 0 && accepted) atomicAdd(&acc_sh, accepted);
-  __syncthreads();
-  u64* lists = reinterpret_cast<u64*>(smem);   // [64 ranks][ONE_WAVES]
-  lists[lane * ONE_WAVES + wave] = sel.acc[0];
-  __syncthreads();
-  if (wave == 0) {
-    const u64 mine = one_multiway(lists, ONE_WAVES, ONE_WAVES, a.L, lane);
-    if (lane < a.L) __hip_atomic_store(a.part + (size_t)lane * G + w, one_tag_key(mine, a.epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (lane == 0) __hip_atomic_store(a.cnt_g + w, (uint32_t)acc_sh | (a.epoch << 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  one_publish(one_at<u64>(smem, lay.lists()), sel.acc[0], a.L, a.part, a.cnt_g, &acc_sh, G, w, a.epoch, wave, lane);
   ONE_STAMP(8);
   if (w != 0) return;   // (workgroup 0 collects the lists)
   ONE_STAMP_LAST(0);
 
   // ---- E. the last workgroup: merge, replay, the list ----
-  {
-    u64* all = reinterpret_cast<u64*>(smem) + ONE_WAVES * 64;
-    const int total = G * a.L;
-    {
-      bool ok = false;
-      for (int round = 0; round < ONE_RETRY_LIMIT && !ok; ++round) {
-        if (tid == 0) { retry_sh = 0; acc_sh = 0; }
-        __syncthreads();
-        bool bad = false;
-        for (int i = tid; i < total; i += ONE_WG) {
-          const u64 word = __hip_atomic_load(a.part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          bad |= (uint32_t)(word >> 63) != a.epoch;
-          all[i] = one_untag_key(word);
-        }
-        int cnt = 0;
-        for (int i = tid; i < G; i += ONE_WG) {
-          const uint32_t word = __hip_atomic_load(a.cnt_g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          bad |= (word >> 31) != a.epoch;
-          cnt += (int)(word & 0x7fffffffu);
-        }
-        if (cnt) atomicAdd(&acc_sh, cnt);
-        if (bad) retry_sh = 1;
-        __syncthreads();
-        ok = retry_sh == 0;
-        __syncthreads();   // (everyone has read the flag before the next round clears it)
-        if (!ok) __builtin_amdgcn_s_sleep(8);
-      }
-      if (!ok) { if (tid == 0) a.err[0] = 1; return; }
-    }
-    if (wave != 0) return;
-    ONE_STAMP_LAST(1);
-    const u64 top = one_multiway4(all, G, a.L, lane);
-    const uint32_t db = (uint32_t)(top >> 32);
-    const uint32_t db_next = (uint32_t)__shfl_down((int)db, 1, 64);
-    const bool tie = lane + 1 < a.L && top != KEY_INF && db == db_next;
-    float d_slot = a.sentinel;
-    int32_t id_slot = -1;
-    if (__ballot(tie) == 0ull) {   // (no two candidates equally far: the order of insertion does not matter, pq_one_kernel)
-      if (lane < a.k && top != KEY_INF && __uint_as_float(db) < a.sentinel) {
-        d_slot = __uint_as_float(db);
-        id_slot = (int32_t)(uint32_t)top;
-      }
-    } else {
-      u64 byp[1];
-      byp[0] = (top == KEY_INF || lane >= a.L) ? KEY_INF : ((top << 32) | (top >> 32));
-      wave_sort_full<1>(byp);
-      wave_list_replay(d_slot, id_slot, a.k, byp[0], a.L < 64 ? a.L : 64, [](uint32_t id) { return (int32_t)id; });
-    }
-    if (lane < a.k) {
-      a.out_ids[lane] = id_slot;
-      a.out_dist[lane] = d_slot;
-    }
-    // "found" of the first round (freddy.c:377 rows rule, :971 accepted rule): fewer than k and a cell was probed -> the
-    // reference probes the next W cells; the host runs that path
-    int rows = my_rows;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o, 64);
-    if (!any_cell) rows = -1;   // no cell below the limit: the query retires
-    const int found = a.found_rule == 1 ? acc_sh : (rows > 0 ? rows : 0);
-    const int verdict = (found < a.k && rows >= 0) ? 3 : 2;
-    ONE_STAMP_LAST(2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    if (lane == 0) __hip_atomic_store(a.err, verdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  u64* all = one_at<u64>(smem, lay.all_lists());
+  if (!one_collect(a.part, all, G * a.L, a.cnt_g, G, a.epoch, tid, &retry_sh, &acc_sh)) ONE_GIVE_UP();
+  if (wave != 0) return;
+  ONE_STAMP_LAST(1);
+  const u64 top = one_multiway4(all, G, a.L, lane);
+  float d_slot = a.sentinel;
+  int32_t id_slot = -1;
+  wave_list_from_sorted(d_slot, id_slot, a.k, top, a.L, [&](u64 key) { return key_dist(key) < a.sentinel; },
+                        [](uint32_t id) { return (int32_t)id; });
+  // "found" of the first round: fewer than k and a cell was probed -> the reference probes the next W cells; the host runs
+  // that path (round_end's rule)
+  const int rows = wave_round_rows(my_have, my_rows);
+  const int verdict = round_again(round_found(a.found_rule == 1, acc_sh, rows), a.k, rows) ? 3 : 2;
+  one_finish(a.out_ids, a.out_dist, a.k, id_slot, d_slot, a.err, verdict, lane, a.prof ? a.prof + STAMP_LAST + 2 : nullptr);
 }
 #undef ONE_STAMP
 #undef ONE_STAMP_LAST
+#undef ONE_GIVE_UP
 
 }  // namespace freddy

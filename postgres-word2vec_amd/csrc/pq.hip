@@ -278,25 +278,22 @@ static int pq_one(freddy_gpu_index* ix, hipStream_t s, const float* h_q, int k, 
                   const uint32_t* packed, const int32_t* pos, int64_t n_blocks, int32_t* d_out_ids, float* d_out_dist, int32_t* err) {
   Workspace* ws = workspace_for(ix, s);
   const int K = ix->K, L = 2 * k;
-  const size_t lutN = (size_t)12 * K;
   // (one workgroup per CU at most: all co-resident; the last arriver stages every list in LDS: G * L keys within 56 KB)
   const int G = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)ix->n_cus, (int64_t)256, (n_blocks + ONE_WAVES - 1) / ONE_WAVES, (int64_t)(56 * 1024) / (8 * L)}));
   const int chunk_blocks = (int)((n_blocks + G - 1) / G);
-  const size_t part_off = (lutN * sizeof(float) + 255) & ~(size_t)255;
+  const OneLayout lay{K, 0, 1, L, G};   // (the table | the workgroups' lists; the kernel's LDS: one_layout.h)
   uint32_t epoch = 0;
-  if (int rc = one_buffer(ws, s, (1ull << 60) | ((uint64_t)K << 32) | ((uint64_t)G << 16) | (uint64_t)L, part_off + sizeof(u64) * (size_t)G * L, &epoch)) return rc;
+  if (int rc = one_buffer(ws, s, (1ull << 60) | ((uint64_t)K << 32) | ((uint64_t)G << 16) | (uint64_t)L, lay.handoff_bytes(), &epoch)) return rc;
   if (one_prof() && ws->w_one.ensure(256)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   OneArgs a;
   memcpy(a.qv, h_q, sizeof(a.qv)); a.cbT = ix->cbT; a.lut_g = ws->w_oneb.as<float>(); a.blk_off = blk_off; a.packed = packed; a.pos = pos;
   a.pos_to_id = nullptr;   // (positions out: the caller maps them through its host copy of the ids -- no dependent gather at the kernel's end)
-  a.part = reinterpret_cast<u64*>(ws->w_oneb.as<char>() + part_off); a.out_ids = d_out_ids; a.out_dist = d_out_dist;
+  a.part = reinterpret_cast<u64*>(ws->w_oneb.as<char>() + lay.part_off()); a.out_ids = d_out_ids; a.out_dist = d_out_dist;
   a.epoch = epoch; a.err = err;
   a.prof = one_prof() ? ws->w_one.as<unsigned long long>() + 8 : nullptr;
   a.K = K; a.L = L; a.k = k; a.chunk_blocks = chunk_blocks; a.sentinel = sentinel;
   memcpy(&a.sentinel_bits, &sentinel, 4);
-  const size_t lds = std::max(((lutN * 4 + 15) & ~(size_t)15) + (size_t)ONE_WAVES * 64 * sizeof(u64),
-                              (size_t)ONE_WAVES * 64 * sizeof(u64) + (size_t)G * L * sizeof(u64));
-  timed_launch(ix, s, "pq_one", [&] { hipLaunchKernelGGL((pq_one_kernel<25>), dim3((unsigned)G), dim3(ONE_WG), lds, s, a); });
+  timed_launch(ix, s, "pq_one", [&] { hipLaunchKernelGGL((pq_one_kernel<25>), dim3((unsigned)G), dim3(ONE_WG), lay.lds_bytes(), s, a); });
   HIP_TRY(hipGetLastError());
   ws->one_pending = false;
   return 0;

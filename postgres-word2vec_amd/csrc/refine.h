@@ -661,17 +661,7 @@ __global__ __launch_bounds__(64 * NWV, 4) void merge_refine_kernel(MergeRefineAr
   int amb_total = amb_accepted;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) amb_total += __shfl_xor(amb_total, o, 64);
-  if (lane == 0) {
-    int f = a.first_round ? 0 : a.found[q];
-    const int rows = a.round_rows[x];
-    f += (a.found_rule == 1 && a.cand_count) ? a.cand_count[q] + amb_total : (rows > 0 ? rows : 0);
-    a.found[q] = f;
-    if (f < k && rows >= 0) {
-      const int slot = atomicAdd(a.n_next, 1);
-      a.next_active[slot] = q;
-      if (a.status) a.status[0] = 1;
-    }
-  }
+  if (lane == 0) round_end(a, x, q, amb_total);
 }
 
 }  // namespace freddy

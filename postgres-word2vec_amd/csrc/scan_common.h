@@ -249,17 +249,7 @@ static __global__ __launch_bounds__(64) void merge_surv_kernel(MergeSurvArgs a) 
     a.out_ids[(size_t)q * k + lane] = id_slot;
     a.out_dist[(size_t)q * k + lane] = d_slot;
   }
-  if (lane == 0) {
-    int f = a.first_round ? 0 : a.found[q];
-    const int rows = a.round_rows[x];
-    f += (a.found_rule == 1 && a.cand_count) ? a.cand_count[q] : (rows > 0 ? rows : 0);
-    a.found[q] = f;
-    if (f < k && rows >= 0) {
-      const int slot = atomicAdd(a.n_next, 1);
-      a.next_active[slot] = q;
-      if (a.status) a.status[0] = 1;
-    }
-  }
+  if (lane == 0) round_end(a, x, q, 0);
 }
 
 }  // namespace freddy

@@ -252,6 +252,70 @@ __device__ __forceinline__ void wave_list_replay(float& d_slot, int32_t& id_slot
   }
 }
 
+// The list of an EMPTY n-slot list (d_slot = the limit, id_slot = -1 on entry) after the guarded insertion of `count` <= 64
+// candidates that arrive as ascending (distance bits, position) keys, lane r <- rank r, KEY_INF from `count` on.  When no two
+// of them are equally far the order of insertion does not matter: the list is the n smallest below the limit in ascending
+// order, which is how `top` already holds them -- wave_list_ascending forms it and returns true (equal distances are
+// neighbours; KEY_INF's upper word is not a distance).  Otherwise it touches nothing and returns false: the caller replays in
+// position order.  `below(key)` is the site's own test against its limit (the sites do not compare alike: a key against a key,
+// a float against a float -- these differ for a limit that is negative or not a number); `payload(position)` the stored id.
+template <typename B, typename F>
+__device__ __forceinline__ bool wave_list_ascending(float& d_slot, int32_t& id_slot, int n, u64 top, int count, B below, F payload) {
+  const int lane = lane_id();
+  const uint32_t db = (uint32_t)(top >> 32);
+  const uint32_t db_next = (uint32_t)__shfl_down((int)db, 1, 64);
+  const bool tie = lane + 1 < count && top != KEY_INF && db == db_next;
+  if (__ballot(tie) != 0ull) return false;
+  if (lane < n && top != KEY_INF && below(top)) {
+    d_slot = __uint_as_float(db);
+    id_slot = payload((uint32_t)top);
+  }
+  return true;
+}
+// The same with the replay: re-keyed as (position, distance bits), sorted, the ids gathered by all lanes at once (a load inside
+// the replay is a round trip per insertion), inserted in position order.
+template <typename B, typename F>
+__device__ __forceinline__ void wave_list_from_sorted(float& d_slot, int32_t& id_slot, int n, u64 top, int count, B below, F payload) {
+  if (wave_list_ascending(d_slot, id_slot, n, top, count, below, payload)) return;
+  u64 byp[1];
+  byp[0] = (top == KEY_INF || lane_id() >= count) ? KEY_INF : ((top << 32) | (top >> 32));
+  wave_sort_full<1>(byp);
+  if (byp[0] != KEY_INF) byp[0] = ((u64)(uint32_t)payload((uint32_t)(byp[0] >> 32)) << 32) | (u64)(uint32_t)byp[0];
+  wave_list_replay(d_slot, id_slot, n, byp[0], count < 64 ? count : 64, [](uint32_t id) { return (int32_t)id; });
+}
+
+// ---------------------------------------------------------------------------------------
+// The end of a probing round for one query: what the round retrieved, whether the reference would probe again (freddy.c:377
+// rows rule, :971 accepted rule), and the state the next round and the async API read.  Every merge kernel ends in
+// round_end(); probe_plan_kernel and ivf_one_kernel state the round's rows with wave_round_rows().
+// ---------------------------------------------------------------------------------------
+// Rows of the cells this wave's lanes take (`have`: the lane holds a cell of `rows` rows), in every lane; -1 when no lane holds
+// one: no cell is left below the limit and the query retires.
+__device__ __forceinline__ int wave_round_rows(bool have, int rows) {
+  rows = have ? rows : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o, 64);
+  return __ballot(have) != 0ull ? rows : -1;
+}
+__device__ __forceinline__ int round_found(bool by_accepted, int accepted, int rows) { return by_accepted ? accepted : (rows > 0 ? rows : 0); }
+__device__ __forceinline__ bool round_again(int found, int k, int rows) { return found < k && rows >= 0; }
+// One lane.  a: the merge's arguments (found, cand_count, round_rows, next_active, n_next, status: each may be NULL -- the
+// join's replay passes none); x: the query's place among the active ones, q: the query; extra: accepted rows the kernel
+// itself counted on top of cand_count[q].
+template <typename A>
+__device__ __forceinline__ void round_end(const A& a, int x, int q, int extra) {
+  int f = (a.first_round || !a.found) ? 0 : a.found[q];
+  const int rows = a.round_rows ? a.round_rows[x] : 0;
+  const bool by_accepted = a.found_rule == 1 && a.cand_count;
+  f += round_found(by_accepted, by_accepted ? a.cand_count[q] + extra : 0, rows);
+  if (a.found) a.found[q] = f;
+  if (a.next_active && round_again(f, a.k, rows)) {
+    const int slot = atomicAdd(a.n_next, 1);
+    a.next_active[slot] = q;
+    if (a.status) a.status[0] = 1;
+  }
+}
+
 // Streaming selection of the L smallest keys seen by one wave.  Keys below the running
 // threshold are compacted into a 64-entry LDS staging row (ballot + prefix popcount) and
 // absorbed by a bitonic merge only when the row fills up, which becomes rare once the

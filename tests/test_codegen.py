@@ -32,6 +32,8 @@ PROBES = {
     "merge_refine_kernel<25,12,4>": ("fused5.h", "merge_refine_kernel<25, 12, 4>", "merge_refine_kernelILi25ELi12ELi4ELb0ELb0EE"),
     "exf_filter_kernel<2,false>": ("exact2.h", "exf_filter_kernel<2, false>", "exf_filter_kernelILi2ELb0EE"),
     "join_query_kernel<1>": ("join.h", "join_query_kernel<1>", "join_query_kernelILi1ELb0EE"),
+    "pq_one_kernel<25>": ("one.h", "pq_one_kernel<25>", "pq_one_kernelILi25EE"),
+    "ivf_one_kernel<25>": ("one.h", "ivf_one_kernel<25>", "ivf_one_kernelILi25EE"),
 }
 FIELDS = {"VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch_bytes", "SGPRs Spill": "sgpr_spill",
           "VGPRs Spill": "vgpr_spill", "Occupancy [waves/SIMD]": "occupancy"}
@@ -67,7 +69,7 @@ def probe(name, tmp):
 
 
 def measure(tmp):
-    with ThreadPoolExecutor(max_workers=min(7, os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(PROBES), os.cpu_count() or 1)) as ex:
         return dict(zip(PROBES, ex.map(lambda n: probe(n, tmp), PROBES)))
 
 

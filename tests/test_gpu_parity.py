@@ -136,6 +136,66 @@ def test_ivfadc_single_query_one_launch(gpu, oracle, K):
     idx.close()
 
 
+def _guarded_cell_list(dist, W, limit=np.float32(100.0)):
+    """The reference's W nearest cells (freddy.c:266-283 restated): cells in order, each inserted behind the guard
+    "dist < the list's last entry" in front of the first entry that is not strictly nearer (updateTopK, index_utils.c:19-33)."""
+    cells, ds = [-1] * W, [limit] * W
+    for c, d in enumerate(dist):
+        if d < ds[-1]:
+            at = sum(1 for e in ds if e < d)
+            cells = cells[:at] + [c] + cells[at:-1]
+            ds = ds[:at] + [d] + ds[at:-1]
+    return cells
+
+
+def test_ivfadc_single_query_one_launch_equally_far_cells(gpu, oracle):
+    """Two CELLS equally far from the query among the 2W candidates of ivf_one_kernel's cell selection (stage B): the branch of
+    the "ascending or replay" list helper that no other single-query test is written to reach.  Centroids 2 and 5 are
+    bit-identical, as are 3 and 6; the rows of those cells keep their own codes, so a list tells which twin was taken.  The
+    smallest shape the one-launch kernels take (the golden fixture's).  16 queries are rows (two of every cell), 4 are not (the
+    twin centroids themselves, two midpoints).  Expectation: the oracle's ivfadc_search, every case."""
+    N, C, k = 4200, 8, 5
+    x, t = _shape_tables(300, 12, 256, C, N)
+    t = dict(t)
+    coarse = np.array(t["coarse"], np.float32)
+    coarse[5], coarse[6] = coarse[2], coarse[3]
+    t["coarse"] = coarse
+    lo, ids = np.asarray(t["list_off"]), np.asarray(t["ids"])
+    xn = x.numpy().astype(np.float32)
+    rows = [int(ids[lo[c] + j]) - 1 for c in range(C) for j in (0, int(lo[c + 1] - lo[c]) // 2)]
+    assert len(set(rows)) == 16
+    qs = np.concatenate([xn[rows], coarse[[2, 3]], (xn[rows[4]:rows[4] + 1] + xn[rows[10]]) * np.float32(0.5),
+                         (xn[rows[6]:rows[6] + 1] + xn[rows[1]]) * np.float32(0.5)]).astype(np.float32)
+    assert qs.shape == (20, 300)
+    Ws = (1, 2, 3, 8)
+    # the test proves something only if the twins matter: for some (query, W) the reference's cell list is not the ascending
+    # sort of (distance, cell), or one twin is taken and the other, equally far, is the next in line
+    dist = np.array([[oracle.sqdist(q, c) for c in coarse] for q in qs], np.float32)
+    assert np.array_equal(dist[:, 2].view(np.uint32), dist[:, 5].view(np.uint32)) and np.array_equal(dist[:, 3].view(np.uint32), dist[:, 6].view(np.uint32))
+    reordered = straddle = 0
+    for d in dist:
+        order = sorted(range(C), key=lambda c: (d[c], c))
+        for W in Ws:
+            ref = _guarded_cell_list(d, W)
+            reordered += ref != order[:W]
+            straddle += W < C and any(a in ref and b == order[W] for a, b in ((2, 5), (3, 6)))
+    assert reordered > 0 and straddle > 0, (reordered, straddle)
+    ot = oracle.ivf_table(t["coarse"], t["codebook"], t["list_off"], t["ids"], t["codes"])
+    idx = gpu.IVFIndex(t["coarse"], t["codebook"], t["list_off"], t["ids"], t["codes"])
+    idx.profile_enable(True)
+    idx.search(qs[:1], k, 2, sentinel=1000.0, found_rule=0)
+    prof = idx.profile_read()
+    idx.profile_enable(False)
+    assert "ivf_one" in prof, f"the one-launch kernel did not run: {sorted(prof)}"
+    exp = {(W, rule, i): oracle.ivfadc_search(ot, q, k, W, sentinel=1000.0, found_rule=rule)[None] for W in Ws for rule in (0, 1) for i, q in enumerate(qs)}
+    for one in (1, 0):
+        idx.set_option("one_launch", one)
+        for (W, rule, i), e in exp.items():
+            gi, gd = idx.search(qs[i][None], k, W, sentinel=1000.0, found_rule=rule)
+            util.assert_same_lists(gi, gd, e, f"twin cells, one_launch={one} W={W} rule={rule} query {i}")
+    idx.close()
+
+
 def test_pq_search_in_and_batch(gpu, oracle):
     N = 20000
     t = util.pq_tables(N=N, K=256)
