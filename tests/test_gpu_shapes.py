@@ -46,13 +46,7 @@ def _exact_expect(oracle, x, ids, qs, kmax, sub=None):
     return [oracle.exact_knn(x, ids, q, kmax, sub) for q in qs]
 
 
-def _exact_same(gi, gs, exp, k, what):
-    for qi, e in enumerate(exp[:gi.shape[0]]):
-        e = e[:k]
-        n = len(e)
-        assert gi[qi, :n].tolist() == e["id"].tolist(), (what, qi)
-        assert np.array_equal(gs[qi, :n].view(np.uint32), e["dist"].view(np.uint32)), (what, qi)
-        assert (gi[qi, n:] == -1).all() and np.isneginf(gs[qi, n:]).all(), (what, qi)
+_exact_same = util.assert_exact_lists   # (shared with tests/test_gpu_selection_widths.py)
 
 
 @pytest.mark.parametrize("d", [16, 64, 100, 304, 512])

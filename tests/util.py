@@ -78,6 +78,17 @@ def assert_same_lists(got_ids, got_dist, exp, what=""):
     assert np.array_equal(exp_d.view(np.uint32), got_dist.view(np.uint32)), f"{what}: distance bits differ"
 
 
+def assert_exact_lists(gi, gs, exp, k, what=""):
+    """Exact kNN: exp[q] is the oracle's list of query q with at least k entries, or with every row there is (ORDER BY similarity
+    DESC, id ASC is a total order: the list for k is the prefix).  Ids and similarity bits; (-1, -inf) behind the last row."""
+    for qi, e in enumerate(exp[:gi.shape[0]]):
+        e = e[:k]
+        n = len(e)
+        assert gi[qi, :n].tolist() == e["id"].tolist(), (what, qi)
+        assert np.array_equal(gs[qi, :n].view(np.uint32), e["dist"].view(np.uint32)), (what, qi)
+        assert (gi[qi, n:] == -1).all() and np.isneginf(gs[qi, n:]).all(), (what, qi)
+
+
 # ---- non-finite inputs (tests/test_nonfinite_cpu.py, tests/test_gpu_nonfinite.py) ----
 NEG_NAN = np.array([0xffc00000], np.uint32).view(np.float32)[0]     # a quiet NaN with the sign bit set
 QUERY_POISONS = ("nan", "neg_nan", "pos_inf", "neg_inf", "both_inf", "all_nan")
