@@ -283,6 +283,47 @@ int freddy_gpu_pq_search_pv(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, co
  * them had a vector row (were scored).  NULL pointers are skipped. */
 int freddy_gpu_last_pv_stats(const freddy_gpu_index_t* ann, int64_t* candidates, int64_t* scored);
 
+/* ---- searches by row id: the queries are rows of a pinned vector handle, gathered on the device (query_ids.h) ---------------
+ * The reference's callers start from ids, not floats: ivfadc_batch_search(int[] ids, k) selects "id, vector FROM <vecs> WHERE id IN
+ * (...)" itself (freddy.c:767-804), and the token forms resolve words to rows of the same table first.  These four calls take the
+ * ids; the vectors never cross PCIe: 4 bytes per query go up, and a kernel (query_gather) copies the rows of `vecs` into the
+ * search's query block.  From there everything the existing entry point runs, runs unchanged.
+ * Which ids are searched is decided by id_rule; let sel[0..Q) be the ids it selects and v[j] the row of `vecs` with id sel[j]:
+ *   FREDDY_QIDS_TABLE_ORDER  the SELECT above: Q = the distinct ids of query_ids that have a row, in ascending id order (duplicates
+ *                            collapse, ids without a row vanish).  Output slots >= Q are not written.  Q == 0 succeeds and launches
+ *                            nothing.
+ *   FREDDY_QIDS_POSITIONAL   Q = n_ids and sel = query_ids: slot j answers query_ids[j], a repeated id is answered again.  A slot
+ *                            whose id has no row holds k fillers -- (-1, sentinel), or (-1, -inf) for the _pv forms -- and is not
+ *                            searched: such slots are compacted away before anything is launched (as the approximate analogies do
+ *                            with unknown triples), cost nothing and disturb no neighbour; a batch of only such ids launches nothing.
+ * Contract: *n_queries = Q, out_query_ids[0..Q) = sel, and for every j with a row, list j is bit for bit (ids, ranks, distance or
+ * similarity bits) what freddy_gpu_ivfadc_search / freddy_gpu_pq_search / freddy_gpu_ivfadc_search_pv / freddy_gpu_pq_search_pv
+ * returns for the query v[j] with the same remaining arguments: every path (one launch, small batch, pipelined sub-batches, every
+ * scan, the passes of k > 512), every probing round, and the re-search of the queries round one leaves unfinished.  The query row
+ * need not be a row of the ANN index: `vecs` may hold more or fewer ids than ivf / pq.
+ * Errors, all before any device work and in this order: FREDDY_E_ARG for a NULL handle, n_ids < 0, a bad id_rule, a NULL n_queries,
+ * a NULL buffer with n_ids > 0; then what the entry point underneath refuses (k, W, found_rule, the subset, k * pvf), with its
+ * messages; FREDDY_E_KIND for handles of the wrong kinds; FREDDY_E_ARG for vecs on another device or of another d, and for an ivf
+ * handle with replicas; a poisoned handle of either kind is refused as everywhere.  n_ids == 0 succeeds with *n_queries = 0.
+ * Concurrency as for the _pv calls: synchronous, on the library's own streams; `vecs` is read while the call runs, so a mutation of
+ * `vecs` must not run beside it.  A mutation BEFORE the call is seen: after freddy_gpu_update_rows / append_rows / remove_rows on
+ * vecs a search by id answers as if the host had read the new table. */
+#define FREDDY_QIDS_TABLE_ORDER 0
+#define FREDDY_QIDS_POSITIONAL 1
+int freddy_gpu_ivfadc_search_ids(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids,
+                                 int32_t id_rule, int32_t k, int32_t W, float sentinel, int32_t found_rule,
+                                 int32_t* out_query_ids /*[n_ids]*/, int32_t* n_queries, int32_t* out_ids /*[n_ids][k]*/,
+                                 float* out_dist /*[n_ids][k]*/);
+int freddy_gpu_pq_search_ids(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids,
+                             int32_t id_rule, int32_t k, float sentinel, const int32_t* subset_ids, int64_t n_subset,
+                             int32_t* out_query_ids, int32_t* n_queries, int32_t* out_ids, float* out_dist);
+int freddy_gpu_ivfadc_search_pv_ids(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids,
+                                    int32_t id_rule, int32_t k, int32_t pvf, int32_t W, float sentinel, int32_t found_rule,
+                                    int32_t* out_query_ids, int32_t* n_queries, int32_t* out_ids, float* out_sim);
+int freddy_gpu_pq_search_pv_ids(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids,
+                                int32_t id_rule, int32_t k, int32_t pvf, float sentinel, const int32_t* subset_ids,
+                                int64_t n_subset, int32_t* out_query_ids, int32_t* n_queries, int32_t* out_ids, float* out_sim);
+
 /* ---- batched approximate analogies: 3CosAdd over the candidates of an approximate search (approx_analogy.h) ----------------
  * analogy_3cosadd_ivfadc (freddy--0.0.1.sql:1428-1460), analogy_3cosadd_pq (:1317-1346) and, with subset_ids, analogy_3cosadd_in_pq
  * (:1348-1384) for Q triples of row ids (w1, w2, w3) at once; the reference calls them with n_cand = get_pvf() + 3 and k = 1.

@@ -293,10 +293,9 @@ int check_search_args(const freddy_gpu_index* ix, int kind, const void* q, int Q
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
   if (ix->kind != kind) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
   if (int rc = refuse_poisoned(ix)) return rc;
-  if (Q < 0 || k <= 0) return fail(FREDDY_E_ARG, "Q must be >= 0 and k > 0");
+  if (int rc = check_list_count(Q, k)) return rc;
   if (Q > 0 && (!q || !oi || !od)) return fail(FREDDY_E_ARG, "NULL buffer");
-  if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
-  return 0;
+  return check_list_limit(k);
 }
 
 extern "C" int freddy_gpu_host_alloc(void** out, size_t bytes) {

@@ -11,6 +11,7 @@
 #include "pv.h"
 #include "approx_analogy.h"
 #include "assign.h"
+#include "query_ids.h"
 #include "exact_host.h"
 
 // ---- exact brute-force kNN as filter + refine (exact2.h) ----------------------------------------------------------------------
@@ -670,25 +671,23 @@ extern "C" int freddy_gpu_last_analogy_stats(const freddy_gpu_index_t* ix, int64
 
 // ---- post verification of pq / ivf result lists (pv.h) -------------------------------------------------------------------
 // The handles of a call that takes a pq / ivf handle and the raw-vector handle it re-ranks against (post verification, approximate
-// analogies); nothing here touches a device.
-static int pv_check_handles(const freddy_gpu_index* ann, int kind, const freddy_gpu_index* vecs, const char* what) {
-  if (!ann || !vecs) return fail(FREDDY_E_ARG, "NULL index");
-  if (ann->kind != kind || vecs->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
-  if (int rc = refuse_poisoned(ann)) return rc;
-  if (int rc = refuse_poisoned(vecs)) return rc;
-  if (!ann->replicas.empty())
-    return fail(FREDDY_E_ARG, "%s does not take a handle with replicas (%d devices): the vectors are pinned on one device", what, 1 + (int)ann->replicas.size());
-  if (vecs->device != ann->device) return fail(FREDDY_E_ARG, "the vectors are pinned on device %d, the index on device %d", vecs->device, ann->device);
-  if (vecs->d != ann->d) return fail(FREDDY_E_ARG, "the vectors have %d dimensions, the index has %d", vecs->d, ann->d);
-  return 0;
-}
+// analogies): check_ann_vecs (query_ids.h, which the searches by id share); nothing there touches a device.
+static int pv_check_handles(const freddy_gpu_index* ann, int kind, const freddy_gpu_index* vecs, const char* what) { return check_ann_vecs(ann, kind, vecs, what); }
 
+// The scalar refusals of post verification, each with its one message (the host-vector entry points and the ones by row id)
+static int pv_check_count(int32_t Q, int32_t k, int32_t pvf) { return (Q < 0 || k < 1 || pvf < 1) ? fail(FREDDY_E_ARG, "bad sizes (Q=%d, k=%d, pvf=%d)", Q, k, pvf) : 0; }
+static int pv_check_limit(int32_t k, int32_t pvf) {
+  return (int64_t)k * pvf > PV_MAX_CAND ? fail(FREDDY_E_LIMIT, "k * pvf = %lld exceeds this build's limit of %d candidates", (long long)k * pvf, PV_MAX_CAND) : 0;
+}
+static int pv_check_subset(const int32_t* subset_ids, int64_t n_subset) {
+  return (n_subset < 0 || (n_subset > 0 && !subset_ids)) ? fail(FREDDY_E_ARG, "bad subset (n_subset=%lld)", (long long)n_subset) : 0;
+}
 // Everything both entry points refuse, in the order of the header's table; nothing here touches a device.
 static int pv_check(const freddy_gpu_index* ann, int kind, const freddy_gpu_index* vecs, const float* queries, int32_t Q, int32_t k, int32_t pvf,
                     const int32_t* out_ids, const float* out_sim) {
-  if (Q < 0 || k < 1 || pvf < 1) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, k=%d, pvf=%d)", Q, k, pvf);
+  if (int rc = pv_check_count(Q, k, pvf)) return rc;
   if (Q > 0 && (!queries || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
-  if ((int64_t)k * pvf > PV_MAX_CAND) return fail(FREDDY_E_LIMIT, "k * pvf = %lld exceeds this build's limit of %d candidates", (long long)k * pvf, PV_MAX_CAND);
+  if (int rc = pv_check_limit(k, pvf)) return rc;
   return pv_check_handles(ann, kind, vecs, "post verification");
 }
 
@@ -696,7 +695,7 @@ static int pv_check(const freddy_gpu_index* ann, int kind, const freddy_gpu_inde
 // passes of queries that bound the pinned block; the kernel reads the lists where stage one left them and writes the result lists
 // and the counts beside them, one synchronisation per pass.
 template <class F>
-static int pv_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const float* queries, int32_t Q, int32_t k, int32_t pvf, int32_t* out_ids,
+static int pv_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const QuerySrc& queries, int32_t Q, int32_t k, int32_t pvf, int32_t* out_ids,
                      float* out_sim, F&& search) {
   ann->pv_stats[0] = ann->pv_stats[1] = 0;
   if (Q == 0) return FREDDY_OK;
@@ -708,10 +707,18 @@ static int pv_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const float*
   hipStream_t s = ann->stream;
   for (int q0 = 0; q0 < Q; q0 += Qc) {
     const int nq = std::min(Qc, Q - q0);
-    const float* qp = queries + (size_t)q0 * d;
+    const QuerySrc qp = queries.from((size_t)q0, d);
     if (int rc = search(qp, nq, kc, b.l_ids, b.l_dist)) return rc;
     HIP_TRY(hipSetDevice(ann->device));
-    HIP_TRY(hipMemcpyAsync(ann->pv_q.p, qp, sizeof(float) * (size_t)nq * d, hipMemcpyHostToDevice, s));
+    if (qp.host) {
+      HIP_TRY(hipMemcpyAsync(ann->pv_q.p, qp.host, sizeof(float) * (size_t)nq * d, hipMemcpyHostToDevice, s));
+    } else {
+      // queries by row id (query_ids.h): the raw queries are rows of `vecs` -- gathered, by row numbers staged in the handle's pinned
+      // block (stage one has returned: the block is free)
+      if (ann->hio_in.ensure(sizeof(int32_t) * (size_t)nq)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+      memcpy(ann->hio_in.p, qp.rows, sizeof(int32_t) * (size_t)nq);
+      if (int rc = launch_query_gather(ann, s, qp, ann->hio_in.as<const int32_t>(), ann->pv_q.as<float>(), nq, d)) return rc;
+    }
     if (int rc = launch_rerank(ann, vecs, s, "pv_rerank", pv_rerank_kernel<1>, pv_rerank_kernel<4>, b, nullptr, nq, kc, k)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     memcpy(out_ids + (size_t)q0 * k, b.o_ids, sizeof(int32_t) * (size_t)nq * k);
@@ -724,20 +731,55 @@ static int pv_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const float*
 extern "C" int freddy_gpu_ivfadc_search_pv(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const float* queries, int32_t Q, int32_t k, int32_t pvf,
                                            int32_t W, float sentinel, int32_t found_rule, int32_t* out_ids, float* out_sim) {
   if (int rc = pv_check(ivf, KIND_IVF, vecs, queries, Q, k, pvf, out_ids, out_sim)) return rc;
-  if (W <= 0) return fail(FREDDY_E_ARG, "W must be positive");
-  if (found_rule < 0 || found_rule > 2 || (found_rule == FREDDY_FOUND_BATCH_UDF && W != 1))
-    return fail(FREDDY_E_ARG, "bad found_rule (FREDDY_FOUND_BATCH_UDF needs W == 1)");
-  return pv_search(ivf, vecs, queries, Q, k, pvf, out_ids, out_sim, [&](const float* qp, int nq, int kc, int32_t* l_ids, float* l_dist) {
-    return freddy_gpu_ivfadc_search(ivf, qp, nq, kc, W, sentinel, found_rule, l_ids, l_dist);
+  if (int rc = check_probe_args(W, found_rule)) return rc;
+  return pv_search(ivf, vecs, QuerySrc::of_host(queries), Q, k, pvf, out_ids, out_sim, [&](const QuerySrc& qp, int nq, int kc, int32_t* l_ids, float* l_dist) {
+    return freddy_gpu_ivfadc_search(ivf, qp.host, nq, kc, W, sentinel, found_rule, l_ids, l_dist);
   });
 }
 
 extern "C" int freddy_gpu_pq_search_pv(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const float* queries, int32_t Q, int32_t k, int32_t pvf,
                                        float sentinel, const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_sim) {
-  if (n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad subset (n_subset=%lld)", (long long)n_subset);
+  if (int rc = pv_check_subset(subset_ids, n_subset)) return rc;
   if (int rc = pv_check(pq, KIND_PQ, vecs, queries, Q, k, pvf, out_ids, out_sim)) return rc;
-  return pv_search(pq, vecs, queries, Q, k, pvf, out_ids, out_sim, [&](const float* qp, int nq, int kc, int32_t* l_ids, float* l_dist) {
-    return freddy_gpu_pq_search(pq, qp, nq, kc, sentinel, subset_ids, n_subset, l_ids, l_dist);
+  return pv_search(pq, vecs, QuerySrc::of_host(queries), Q, k, pvf, out_ids, out_sim, [&](const QuerySrc& qp, int nq, int kc, int32_t* l_ids, float* l_dist) {
+    return freddy_gpu_pq_search(pq, qp.host, nq, kc, sentinel, subset_ids, n_subset, l_ids, l_dist);
+  });
+}
+
+// Post verification of queries named by row id (query_ids.h): stage one is the search by id's body (ivfadc_search_src / pq_search_src
+// at k * pvf), the raw queries of stage two are gathered from `vecs`.  The counts of freddy_gpu_last_pv_stats cover the searched slots.
+extern "C" int freddy_gpu_ivfadc_search_pv_ids(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule,
+                                               int32_t k, int32_t pvf, int32_t W, float sentinel, int32_t found_rule, int32_t* out_query_ids,
+                                               int32_t* n_queries, int32_t* out_ids, float* out_sim) {
+  if (int rc = check_query_ids_front(ivf, vecs, query_ids, n_ids, id_rule, out_query_ids, n_queries, out_ids, out_sim)) return rc;
+  if (int rc = pv_check_count(n_ids, k, pvf)) return rc;
+  if (int rc = pv_check_limit(k, pvf)) return rc;
+  if (int rc = check_probe_args(W, found_rule)) return rc;
+  if (int rc = check_ann_vecs(ivf, KIND_IVF, vecs, "a search by row id")) return rc;
+  if (W > ivf->C) W = ivf->C;
+  ivf->pv_stats[0] = ivf->pv_stats[1] = 0;
+  return search_selected_ids(vecs, query_ids, n_ids, id_rule, k, -HUGE_VALF, out_query_ids, n_queries, out_ids, out_sim,
+                             [&](const QuerySrc& qs, int n, int32_t* oi, float* os) {
+    return pv_search(ivf, vecs, qs, n, k, pvf, oi, os, [&](const QuerySrc& qp, int nq, int kc, int32_t* l_ids, float* l_dist) {
+      return ivfadc_search_src(ivf, qp, nq, kc, W, sentinel, found_rule, l_ids, l_dist);
+    });
+  });
+}
+
+extern "C" int freddy_gpu_pq_search_pv_ids(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule,
+                                           int32_t k, int32_t pvf, float sentinel, const int32_t* subset_ids, int64_t n_subset, int32_t* out_query_ids,
+                                           int32_t* n_queries, int32_t* out_ids, float* out_sim) {
+  if (int rc = check_query_ids_front(pq, vecs, query_ids, n_ids, id_rule, out_query_ids, n_queries, out_ids, out_sim)) return rc;
+  if (int rc = pv_check_subset(subset_ids, n_subset)) return rc;
+  if (int rc = pv_check_count(n_ids, k, pvf)) return rc;
+  if (int rc = pv_check_limit(k, pvf)) return rc;
+  if (int rc = check_ann_vecs(pq, KIND_PQ, vecs, "a search by row id")) return rc;
+  pq->pv_stats[0] = pq->pv_stats[1] = 0;
+  return search_selected_ids(vecs, query_ids, n_ids, id_rule, k, -HUGE_VALF, out_query_ids, n_queries, out_ids, out_sim,
+                             [&](const QuerySrc& qs, int n, int32_t* oi, float* os) {
+    return pv_search(pq, vecs, qs, n, k, pvf, oi, os, [&](const QuerySrc& qp, int nq, int kc, int32_t* l_ids, float* l_dist) {
+      return pq_search_src(pq, qp, nq, kc, sentinel, subset_ids, n_subset, l_ids, l_dist);
+    });
   });
 }
 
@@ -804,9 +846,7 @@ static int aa_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const int32_
 
 extern "C" int freddy_gpu_ivfadc_analogy(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand,
                                          int32_t W, float sentinel, int32_t found_rule, int32_t* out_ids, float* out_sim) {
-  if (W <= 0) return fail(FREDDY_E_ARG, "W must be positive");
-  if (found_rule < 0 || found_rule > 2 || (found_rule == FREDDY_FOUND_BATCH_UDF && W != 1))
-    return fail(FREDDY_E_ARG, "bad found_rule (FREDDY_FOUND_BATCH_UDF needs W == 1)");
+  if (int rc = check_probe_args(W, found_rule)) return rc;
   if (int rc = aa_check(ivf, KIND_IVF, vecs, triples, Q, k, n_cand, out_ids, out_sim)) return rc;
   return aa_search(ivf, vecs, triples, Q, k, n_cand, out_ids, out_sim, [&](const float* qp, int nq, int32_t* l_ids, float* l_dist) {
     return freddy_gpu_ivfadc_search(ivf, qp, nq, n_cand, W, sentinel, found_rule, l_ids, l_dist);
@@ -815,7 +855,7 @@ extern "C" int freddy_gpu_ivfadc_analogy(freddy_gpu_index_t* ivf, freddy_gpu_ind
 
 extern "C" int freddy_gpu_pq_analogy(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand,
                                      float sentinel, const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_sim) {
-  if (n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad subset (n_subset=%lld)", (long long)n_subset);
+  if (int rc = pv_check_subset(subset_ids, n_subset)) return rc;
   if (int rc = aa_check(pq, KIND_PQ, vecs, triples, Q, k, n_cand, out_ids, out_sim)) return rc;
   return aa_search(pq, vecs, triples, Q, k, n_cand, out_ids, out_sim, [&](const float* qp, int nq, int32_t* l_ids, float* l_dist) {
     return freddy_gpu_pq_search(pq, qp, nq, n_cand, sentinel, subset_ids, n_subset, l_ids, l_dist);

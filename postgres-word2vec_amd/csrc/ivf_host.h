@@ -109,9 +109,7 @@ static MergeArgs merge_args_round(const IvfRun& r, const PlanArgs& pa, const u64
 // what both IVFADC entry points ask of their arguments; W is cut to the number of cells
 static int check_ivfadc_args(const freddy_gpu_index* ix, const void* q, int Q, int k, int32_t* W, int found_rule, const void* oi, const void* od) {
   if (int rc = check_search_args(ix, KIND_IVF, q, Q, k, oi, od)) return rc;
-  if (*W <= 0) return fail(FREDDY_E_ARG, "W must be positive");
-  if (found_rule < 0 || found_rule > 2 || (found_rule == FREDDY_FOUND_BATCH_UDF && *W != 1))
-    return fail(FREDDY_E_ARG, "bad found_rule (FREDDY_FOUND_BATCH_UDF needs W == 1)");
+  if (int rc = check_probe_args(*W, found_rule)) return rc;
   if (*W > ix->C) *W = ix->C;
   return 0;
 }

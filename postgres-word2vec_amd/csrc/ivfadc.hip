@@ -18,6 +18,7 @@
 #include "io_kernels.h"
 #include "bigk.h"
 #include "ivf_host.h"
+#include "query_ids.h"
 
 // ---------------------------------------------------------------------------------------
 // kernel dispatch helpers.  A chooser maps the run-time facts to the instantiation (NULL: there is none); the launch site launches
@@ -712,7 +713,8 @@ extern "C" int freddy_gpu_ivfadc_search_dev(freddy_gpu_index_t* ix, const float*
 // rounds run and its lists are copied out: the transfers and the latency-bound ends of one sub-batch hide under the
 // scans of its neighbours, and ONE stream synchronisation per lane ends the call.
 // ---------------------------------------------------------------------------------------
-static int lane_open(freddy_gpu_index* ix, Lane& l, LaneSlot& c, size_t in_bytes, size_t n, size_t n_out) {
+// stage_bytes: what the sub-batch stages in pinned memory (its queries, or their row numbers: query_ids.h); in_bytes: its query block
+static int lane_open(freddy_gpu_index* ix, Lane& l, LaneSlot& c, size_t stage_bytes, size_t in_bytes, size_t n, size_t n_out) {
   // lane 0 is the handle's own stream: a call of one sub-batch (<= pipeline_batch queries: what a PostgreSQL backend makes) uses
   // ONE stream per process, and only larger calls create further streams -- every stream a process creates takes a hardware
   // queue, and the queues of several backends on one GPU are what decides their aggregate rate (profiles/r06_backends.txt)
@@ -720,7 +722,7 @@ static int lane_open(freddy_gpu_index* ix, Lane& l, LaneSlot& c, size_t in_bytes
   if (!l.stream) HIP_TRY(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
   if (!c.done) HIP_TRY(hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
   const size_t out_bytes = (n_out * 2 + 1 + n + 1) * 4;   // (+ the completion word)
-  if (c.h_in.ensure(in_bytes) || c.h_out.ensure(out_bytes)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+  if (c.h_in.ensure(stage_bytes) || c.h_out.ensure(out_bytes)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
   if (c.d_q.ensure(in_bytes + 16) || c.d_ids.ensure(n_out * 4) || c.d_dist.ensure(n_out * 4))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   return 0;
@@ -728,14 +730,16 @@ static int lane_open(freddy_gpu_index* ix, Lane& l, LaneSlot& c, size_t in_bytes
 
 // The old shape of the call, kept for what the pipeline hands back: a (small) batch searched to the end on the library's
 // own stream -- round one, then the extra rounds of the reference's "while (foundInstances < k)" loop with a host sync each.
-static int ivfadc_sync_search(freddy_gpu_index* ix, const float* queries, int Q, int k, int W, float sentinel, int found_rule,
+// A device-resident source (query_ids.h) brings its row numbers in MAPPED host memory (qs.rows): the block is gathered, not copied.
+static int ivfadc_sync_search(freddy_gpu_index* ix, const QuerySrc& qs, int Q, int k, int W, float sentinel, int found_rule,
                               int32_t* out_ids, float* out_dist) {
   Workspace* ws = workspace_for(ix, ix->stream);
   hipStream_t s = ix->stream;
   if (ws->w_q.ensure(sizeof(float) * (size_t)Q * ix->d) || ws->w_out_ids.ensure(sizeof(int32_t) * (size_t)Q * k) ||
       ws->w_out_dist.ensure(sizeof(float) * (size_t)Q * k))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  HIP_TRY(hipMemcpyAsync(ws->w_q.p, queries, sizeof(float) * (size_t)Q * ix->d, hipMemcpyHostToDevice, s));
+  if (qs.host) HIP_TRY(hipMemcpyAsync(ws->w_q.p, qs.host, sizeof(float) * (size_t)Q * ix->d, hipMemcpyHostToDevice, s));
+  else if (int rc = launch_query_gather(ix, s, qs, qs.rows, ws->w_q.as<float>(), Q, ix->d)) return rc;
   if (int rc = for_chunks(Q, max_queries_per_chunk(ix, W, k), [&](int q0, int n) {
         IvfRun r;
         if (int rc = ivfadc_begin(ix, s, scan_share_now(ix->tune.scan_share, true, ix->device), ws->w_q.as<float>() + (size_t)q0 * ix->d, n, k, W, sentinel, found_rule,
@@ -752,7 +756,7 @@ static int ivfadc_sync_search(freddy_gpu_index* ix, const float* queries, int Q,
 
 struct PipeCall {   // the arguments of one host-buffer call, for the lanes' retire step
   freddy_gpu_index* ix;
-  const float* queries;
+  QuerySrc src;
   int k, W, found_rule;
   float sentinel;
   int32_t* out_ids;
@@ -763,6 +767,7 @@ struct PipeCall {   // the arguments of one host-buffer call, for the lanes' ret
 // cells hold fewer than k rows -- rare) are searched again from the start, synchronously, with all their rounds: the
 // search is deterministic, so that is the list the round-by-round continuation would have produced, and no lane has to
 // keep per-round state while its stream already runs the next sub-batch.
+// (a device-resident source: the stragglers' row numbers go into the slot's staging block, free by now, and the re-search gathers them)
 static int lane_retire(LaneSlot& c, const PipeCall& pc) {
   if (!c.busy) return 0;
   c.busy = false;
@@ -785,11 +790,19 @@ static int lane_retire(LaneSlot& c, const PipeCall& pc) {
   // error has not surfaced yet -- must never become a host read or write out of bounds)
   for (int i = 0; i < n_next; ++i)
     if (who[(size_t)i] < 0 || who[(size_t)i] >= c.n) return fail(FREDDY_E_HIP, "sub-batch returned a straggler index %d outside [0, %d)", who[(size_t)i], c.n);
-  std::vector<float> q((size_t)n_next * d);
+  std::vector<float> q(pc.src.host ? (size_t)n_next * d : 0);
   std::vector<int32_t> ri((size_t)n_next * k);
   std::vector<float> rd((size_t)n_next * k);
-  for (int i = 0; i < n_next; ++i) memcpy(&q[(size_t)i * d], pc.queries + ((size_t)c.q0 + who[(size_t)i]) * d, sizeof(float) * d);
-  if (int rc = ivfadc_sync_search(pc.ix, q.data(), n_next, k, pc.W, pc.sentinel, pc.found_rule, ri.data(), rd.data())) return rc;
+  QuerySrc again = pc.src;
+  if (pc.src.host) {
+    for (int i = 0; i < n_next; ++i) memcpy(&q[(size_t)i * d], pc.src.host + ((size_t)c.q0 + who[(size_t)i]) * d, sizeof(float) * d);
+    again.host = q.data();
+  } else {
+    if (c.h_in.ensure(sizeof(int32_t) * (size_t)n_next)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+    for (int i = 0; i < n_next; ++i) c.h_in.as<int32_t>()[i] = pc.src.rows[(size_t)c.q0 + who[(size_t)i]];
+    again.rows = c.h_in.as<const int32_t>();
+  }
+  if (int rc = ivfadc_sync_search(pc.ix, again, n_next, k, pc.W, pc.sentinel, pc.found_rule, ri.data(), rd.data())) return rc;
   for (int i = 0; i < n_next; ++i) {
     memcpy(pc.out_ids + ((size_t)c.q0 + who[(size_t)i]) * k, &ri[(size_t)i * k], sizeof(int32_t) * k);
     memcpy(pc.out_dist + ((size_t)c.q0 + who[(size_t)i]) * k, &rd[(size_t)i * k], sizeof(float) * k);
@@ -901,21 +914,25 @@ static int ivf_one(freddy_gpu_index* ix, const float* queries, int k, int W, flo
 }
 
 // the batch [0, Q) of one device's handle
-static int ivfadc_host_search(freddy_gpu_index* ix, const float* queries, int Q, int k, int W, float sentinel, int found_rule,
+static int ivfadc_host_search(freddy_gpu_index* ix, const QuerySrc& qs, int Q, int k, int W, float sentinel, int found_rule,
                               int32_t* out_ids, float* out_dist) {
   HIP_TRY(hipSetDevice(ix->device));
+  const float* const queries = qs.host;   // (NULL: the queries are rows of a device table, query_ids.h)
   if (ivf_one_shape(ix, Q, k, W, found_rule)) {
     int verdict = 0;
-    if (int rc = ivf_one(ix, queries, k, W, sentinel, found_rule, out_ids, out_dist, &verdict)) return rc;
+    float* const row_q = queries ? nullptr : (ix->hio_in.ensure(sizeof(float) * (size_t)ix->d) ? nullptr : ix->hio_in.as<float>());   // the kernel takes the query by value
+    if (!queries && !row_q) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+    if (!queries) if (int rc = fetch_query_row(ix->stream, qs, ix->d, row_q)) return rc;
+    if (int rc = ivf_one(ix, queries ? queries : row_q, k, W, sentinel, found_rule, out_ids, out_dist, &verdict)) return rc;
     if (verdict == 2) return FREDDY_OK;
   }
   const int cap = std::max(1, std::min(max_queries_per_chunk(ix, W, k), ix->tune.pipeline_batch));
   const int n_sub = (Q + cap - 1) / cap;
   const int per = (Q + n_sub - 1) / n_sub;               // equal sub-batches rather than full ones and a remainder
   const int n_lanes = std::min(n_sub, std::min(ix->tune.pipeline_lanes, FREDDY_LANES));
-  const float* pinned_in = static_cast<const float*>(pinned_device_pointer(queries));
+  const float* pinned_in = queries ? static_cast<const float*>(pinned_device_pointer(queries)) : nullptr;
   const size_t row = sizeof(float) * (size_t)ix->d;
-  const PipeCall pc{ix, queries, k, W, found_rule, sentinel, out_ids, out_dist};
+  const PipeCall pc{ix, qs, k, W, found_rule, sentinel, out_ids, out_dist};
   const BackendBusy busy;   // (the registry of backends on this GPU: core.hip)
   const int share_call = scan_share_now(ix->tune.scan_share, true, ix->device);
   int rc = 0;
@@ -934,21 +951,29 @@ static int ivfadc_host_search(freddy_gpu_index* ix, const float* queries, int Q,
     if ((rc = lane_retire(c, pc))) break;
     if (trace) t1 = now_us();
     const int q0 = j * per, n = std::min(per, Q - q0);
-    if ((rc = lane_open(ix, l, c, row * n, (size_t)n, (size_t)n * k))) break;
+    if ((rc = lane_open(ix, l, c, queries ? row * n : sizeof(int32_t) * (size_t)n, row * n, (size_t)n, (size_t)n * k))) break;
     c.q0 = q0; c.n = n;
     const float* src = pinned_in ? pinned_in + (size_t)q0 * ix->d : nullptr;
-    const bool stage = !src || reinterpret_cast<uintptr_t>(src) % 16 || (row * n) % 16;   // (the copy kernel moves whole 16-byte words)
+    const bool stage = queries && (!src || reinterpret_cast<uintptr_t>(src) % 16 || (row * n) % 16);   // (the copy kernel moves whole 16-byte words)
     const float* d_queries = c.d_q.as<float>();
-    if (n <= 8) {
+    // read in place, without a launch in front: a handful of host queries where they are staged; ONE query of a device table where its row lies
+    const bool in_place = queries ? n <= 8 : n == 1;
+    if (in_place && queries) {
       // a handful of queries: the kernels read them where they are staged (pinned, mapped) -- one launch less
       if (stage) { memcpy(c.h_in.p, queries + (size_t)q0 * ix->d, row * n); src = c.h_in.as<const float>(); }
       d_queries = src;
+    } else if (in_place) {
+      d_queries = qs.row_ptr((size_t)q0, ix->d);
+    } else if (!queries) {
+      memcpy(c.h_in.p, qs.rows + q0, sizeof(int32_t) * (size_t)n);   // 4 bytes per query where the floats are staged
     }
     // pageable queries cross in pieces: the copy kernel of a piece reads it over PCIe while the host stages the next one (1.2 MB per
     // 1024 queries: 28 us of memcpy + 25 us of PCIe, back to back until round 4) -- and, since round 6, the piece's cell-selection /
     // table launch runs behind its copy while the next piece is staged (ivfadc_begin calls this once per piece)
     const std::function<int(int, int)> stage_piece = [&](int q_lo, int q_hi) -> int {
-      if (n <= 8) return 0;
+      if (in_place) return 0;
+      if (!queries)   // the piece's rows of the table -> the query block, by the row numbers staged above (one launch, as the copy)
+        return launch_query_gather(ix, l.stream, qs, c.h_in.as<const int32_t>() + q_lo, c.d_q.as<float>() + (size_t)q_lo * ix->d, q_hi - q_lo, ix->d);
       const size_t b_lo = row * (size_t)q_lo, b_hi = row * (size_t)q_hi;
       // (a range of whole queries; whole 16-byte words except at the end of the sub-batch, whose buffers are padded)
       const size_t w0 = b_lo / 16, w1 = (b_hi + 15) / 16;
@@ -1000,6 +1025,25 @@ static int ivfadc_host_search(freddy_gpu_index* ix, const float* queries, int Q,
   return rc;
 }
 
+// the host-buffer search of a handle without replicas, for either query source (query_ids.h); the arguments are checked
+int ivfadc_search_src(freddy_gpu_index* ix, const QuerySrc& qs, int Q, int k, int W, float sentinel, int found_rule, int32_t* out_ids, float* out_dist) {
+  if (Q == 0) return FREDDY_OK;
+  return ivfadc_host_search(ix, qs, Q, k, W, sentinel, found_rule, out_ids, out_dist);
+}
+
+extern "C" int freddy_gpu_ivfadc_search_ids(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule,
+                                            int32_t k, int32_t W, float sentinel, int32_t found_rule, int32_t* out_query_ids, int32_t* n_queries,
+                                            int32_t* out_ids, float* out_dist) {
+  if (int rc = check_query_ids_front(ivf, vecs, query_ids, n_ids, id_rule, out_query_ids, n_queries, out_ids, out_dist)) return rc;
+  if (int rc = check_list_count(n_ids, k)) return rc;
+  if (int rc = check_list_limit(k)) return rc;
+  if (int rc = check_probe_args(W, found_rule)) return rc;
+  if (int rc = check_ann_vecs(ivf, KIND_IVF, vecs, "a search by row id")) return rc;
+  if (W > ivf->C) W = ivf->C;
+  return search_selected_ids(vecs, query_ids, n_ids, id_rule, k, sentinel, out_query_ids, n_queries, out_ids, out_dist,
+                             [&](const QuerySrc& qs, int n, int32_t* oi, float* od) { return ivfadc_search_src(ivf, qs, n, k, W, sentinel, found_rule, oi, od); });
+}
+
 // Q queries split contiguously over a handle and its replicas (freddy_gpu_pin_ivf_multi): part g of G gets
 // [lo, hi) with sizes differing by at most one.  fn(part, index of that part, lo, hi) runs on its own host thread
 // for every part but the first; the first failure's code and message are returned on the caller's thread.
@@ -1008,7 +1052,7 @@ extern "C" int freddy_gpu_ivfadc_search(freddy_gpu_index_t* ix, const float* que
   if (int rc = check_ivfadc_args(ix, queries, Q, k, &W, found_rule, out_ids, out_dist)) return rc;
   if (Q == 0) return FREDDY_OK;
   return over_replicas(ix, Q, [&](freddy_gpu_index* part, int lo, int hi) {
-    return ivfadc_host_search(part, queries + (size_t)lo * ix->d, hi - lo, k, W, sentinel, found_rule, out_ids + (size_t)lo * k,
+    return ivfadc_host_search(part, QuerySrc::of_host(queries + (size_t)lo * ix->d), hi - lo, k, W, sentinel, found_rule, out_ids + (size_t)lo * k,
                               out_dist + (size_t)lo * k);
   });
 }

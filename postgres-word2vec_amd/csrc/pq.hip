@@ -9,6 +9,7 @@
 #include "io_kernels.h"
 #include "assign.h"
 #include "ivf_host.h"
+#include "query_ids.h"
 
 // kernel choosers (ivfadc.hip).  M2: dwords of codes per row with an instantiation of its own, else 0 = any m
 static decltype(&grouping_kernel<0>) grouping_kernel_for(int M2) {
@@ -390,10 +391,12 @@ static int pq_subset(freddy_gpu_index* ix, hipStream_t s, const int32_t* subset_
   return 0;
 }
 
-extern "C" int freddy_gpu_pq_search(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k, float sentinel,
-                                    const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_dist) {
-  if (int rc = check_search_args(ix, KIND_PQ, queries, Q, k, out_ids, out_dist)) return rc;
-  if (n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad subset");
+// The host-buffer search for either query source (query_ids.h; the arguments are checked).  queries == NULL: the queries are rows of a
+// device table -- their row numbers are staged where the floats would be and a gather fills the query block; ONE query is read where
+// its row lies, and for the one-launch kernel (which takes it by value) read back first.
+int pq_search_src(freddy_gpu_index* ix, const QuerySrc& qs, int Q, int k, float sentinel, const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids,
+                  float* out_dist) {
+  const float* queries = qs.host;
   if (Q == 0) return FREDDY_OK;
   HIP_TRY(hipSetDevice(ix->device));
   Workspace* ws = workspace_for(ix, ix->stream);
@@ -402,19 +405,33 @@ extern "C" int freddy_gpu_pq_search(freddy_gpu_index_t* ix, const float* queries
   // handful of queries are read where they are staged and their lists written straight back; larger batches cross PCIe
   // once, by a copy kernel each way.  No hipMemcpyAsync in the stream (each one is an SDMA hop with its own latency).
   const size_t q_bytes = sizeof(float) * (size_t)Q * ix->d, n_out = (size_t)Q * k;
-  if (ix->hio_in.ensure(q_bytes + 16) || ix->hio_out.ensure(n_out * 8 + 16)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
-  memcpy(ix->hio_in.p, queries, q_bytes);
+  // (a source of table rows stages their numbers; ONE such query: room for its floats behind the number, for the one-launch kernel)
+  if (ix->hio_in.ensure(queries ? q_bytes + 16 : Q == 1 ? 16 + q_bytes : sizeof(int32_t) * (size_t)Q) || ix->hio_out.ensure(n_out * 8 + 16)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+  if (queries) memcpy(ix->hio_in.p, queries, q_bytes);
+  else memcpy(ix->hio_in.p, qs.rows, sizeof(int32_t) * (size_t)Q);
   const bool direct = Q <= 8;
   if (!direct && (ws->w_q.ensure(q_bytes + 16) || ws->w_out_ids.ensure(sizeof(int32_t) * n_out) || ws->w_out_dist.ensure(sizeof(float) * n_out)))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   const float* d_q = ix->hio_in.as<const float>();
   int32_t* d_oi = ix->hio_out.as<int32_t>();
   float* d_od = reinterpret_cast<float*>(d_oi + n_out);
+  float* const row_q = ix->hio_in.as<float>() + 4;   // (Q == 1 of a device source: the row read back for pq_one)
+  if (!queries) {
+    if (Q == 1) {
+      d_q = qs.row_ptr(0, ix->d);
+    } else {
+      if (direct && ws->w_q.ensure(q_bytes + 16)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+      if (int rc = launch_query_gather(ix, s, qs, ix->hio_in.as<const int32_t>(), ws->w_q.as<float>(), Q, ix->d)) return rc;
+      d_q = ws->w_q.as<float>();
+    }
+  }
   if (!direct) {
-    const size_t n16 = (q_bytes + 15) / 16;
-    hipLaunchKernelGGL(lane_copy_in_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, s,
-                       ix->hio_in.as<const uint4>(), ws->w_q.as<uint4>(), n16);
-    HIP_TRY(hipGetLastError());
+    if (queries) {
+      const size_t n16 = (q_bytes + 15) / 16;
+      hipLaunchKernelGGL(lane_copy_in_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, s,
+                         ix->hio_in.as<const uint4>(), ws->w_q.as<uint4>(), n16);
+      HIP_TRY(hipGetLastError());
+    }
     d_q = ws->w_q.as<float>(); d_oi = ws->w_out_ids.as<int32_t>(); d_od = ws->w_out_dist.as<float>();
   }
 
@@ -432,6 +449,10 @@ extern "C" int freddy_gpu_pq_search(freddy_gpu_index_t* ix, const float* queries
   if (!fused_path && direct && pq_one_shape(ix, Q, k, n_blocks)) {
     int32_t* err = reinterpret_cast<int32_t*>(ix->hio_out.as<char>() + n_out * 8);   // (the staging block's spare 16 bytes)
     *err = 0;
+    if (!queries) {
+      if (int rc = fetch_query_row(s, qs, ix->d, row_q)) return rc;
+      queries = row_q;
+    }
     if (int rc = pq_one(ix, s, queries, k, sentinel, blk_off, packed, pos, n_blocks, d_oi, d_od, err)) return rc;
     int verdict = 0;
     if (int rc = one_finish(ix, ws, s, err, [](const unsigned long long* st) {
@@ -458,6 +479,27 @@ extern "C" int freddy_gpu_pq_search(freddy_gpu_index_t* ix, const float* queries
   return FREDDY_OK;
 }
 
+static int check_subset(const int32_t* subset_ids, int64_t n_subset) { return (n_subset < 0 || (n_subset > 0 && !subset_ids)) ? fail(FREDDY_E_ARG, "bad subset") : 0; }
+
+extern "C" int freddy_gpu_pq_search(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k, float sentinel,
+                                    const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_dist) {
+  if (int rc = check_search_args(ix, KIND_PQ, queries, Q, k, out_ids, out_dist)) return rc;
+  if (int rc = check_subset(subset_ids, n_subset)) return rc;
+  return pq_search_src(ix, QuerySrc::of_host(queries), Q, k, sentinel, subset_ids, n_subset, out_ids, out_dist);
+}
+
+extern "C" int freddy_gpu_pq_search_ids(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k,
+                                        float sentinel, const int32_t* subset_ids, int64_t n_subset, int32_t* out_query_ids, int32_t* n_queries,
+                                        int32_t* out_ids, float* out_dist) {
+  if (int rc = check_query_ids_front(pq, vecs, query_ids, n_ids, id_rule, out_query_ids, n_queries, out_ids, out_dist)) return rc;
+  if (int rc = check_list_count(n_ids, k)) return rc;
+  if (int rc = check_list_limit(k)) return rc;
+  if (int rc = check_subset(subset_ids, n_subset)) return rc;
+  if (int rc = check_ann_vecs(pq, KIND_PQ, vecs, "a search by row id")) return rc;
+  return search_selected_ids(vecs, query_ids, n_ids, id_rule, k, sentinel, out_query_ids, n_queries, out_ids, out_dist,
+                             [&](const QuerySrc& qs, int n, int32_t* oi, float* od) { return pq_search_src(pq, qs, n, k, sentinel, subset_ids, n_subset, oi, od); });
+}
+
 // ---------------------------------------------------------------------------------------
 // grouping_pq
 // ---------------------------------------------------------------------------------------
@@ -467,7 +509,7 @@ extern "C" int freddy_gpu_grouping_pq(freddy_gpu_index_t* ix, const float* group
   if (ix->kind != KIND_PQ) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
   if (int rc = refuse_poisoned(ix)) return rc;
   if (G <= 0 || !group_vectors || !out_ids || !out_group || !n_out) return fail(FREDDY_E_ARG, "bad argument");
-  if (n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad subset");
+  if (int rc = check_subset(subset_ids, n_subset)) return rc;
   *n_out = 0;
   HIP_TRY(hipSetDevice(ix->device));
   Workspace* ws = workspace_for(ix, ix->stream);

@@ -16,6 +16,8 @@ FOUND_ROWS = 0
 FOUND_ACCEPTED = 1
 FOUND_BATCH_UDF = 2   # ivfadc_batch_search itself (W == 1): accepted-rows rule + its argmin cell limit of 1000
 METHOD_PQ, METHOD_EXACT, METHOD_PQ_PV = 0, 1, 2
+QIDS_TABLE_ORDER = 0   # search_ids: "WHERE id IN (...)" -- ascending ids, duplicates collapse, ids without a row vanish
+QIDS_POSITIONAL = 1    # slot j answers ids[j]; an id without a row keeps its slot and gets fillers
 ANALOGY_METHODS = {"3cosadd": 0, "3cosmul": 1, "pair_direction": 2}   # include/freddy_gpu.h FREDDY_ANALOGY_*
 
 EXPORTS = [
@@ -35,6 +37,7 @@ EXPORTS = [
     "freddy_gpu_set_statistics", "freddy_gpu_get_statistics", "freddy_gpu_create_statistics",
     "freddy_gpu_debug_alloc_fail_nth", "freddy_gpu_debug_alloc_track", "freddy_gpu_debug_alloc_stats",
     "freddy_gpu_scan_elastic_stats",
+    "freddy_gpu_ivfadc_search_ids", "freddy_gpu_pq_search_ids", "freddy_gpu_ivfadc_search_pv_ids", "freddy_gpu_pq_search_pv_ids",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together): ids per pass of freddy_gpu_create_statistics
@@ -140,6 +143,18 @@ def load(path=None, optional=()):
         if name in optional and not hasattr(lib, name):
             continue
         getattr(lib, name).argtypes = types
+    # searches by row id.  (A library built from an earlier commit, which the A/B helpers load through FREDDY_GPU_SO, lacks them:
+    # every other call works, search_ids fails with the loader's "undefined symbol".)
+    for name, types in (("freddy_gpu_ivfadc_search_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_pq_search_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_ivfadc_search_pv_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                             C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_pq_search_pv_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
+        if hasattr(lib, name):
+            getattr(lib, name).argtypes = types
     lib.freddy_gpu_pq_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.freddy_gpu_ivfadc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -338,6 +353,21 @@ class _Index:
         return {"searched": v[0].value, "candidates": v[1].value, "scored": v[2].value}
 
 
+def _search_ids(ids, k, call):
+    """The buffers of a search by row id: call(query_ids, n_ids, out_query_ids, n_queries, out_ids, out_values) -> the outputs cut to
+    n_queries."""
+    q = _i32(ids).reshape(-1)
+    n = q.size
+    rows = max(n, 1) * max(int(k), 1)
+    out_q = np.empty(max(n, 1), np.int32)
+    out_i = np.empty(rows, np.int32)
+    out_v = np.empty(rows, np.float32)
+    nq = C.c_int32(-1)
+    _check(call(q, n, out_q, nq, out_i, out_v))
+    Q = nq.value
+    return out_q[:Q], out_i[:Q * k].reshape(Q, k), out_v[:Q * k].reshape(Q, k)
+
+
 class PQIndex(_Index):
     """pq_codebook + pq_quantization pinned in HBM."""
     kind = "pq"
@@ -373,6 +403,19 @@ class PQIndex(_Index):
         _check(self.lib.freddy_gpu_pq_search_pv(self.h, vecs.h, _p(qs), Q, k, pvf, C.c_float(sentinel), _p(sub),
                                                 0 if sub is None else sub.size, _p(out_i), _p(out_s)))
         return out_i, out_s
+
+    def search_ids(self, vecs, ids, k, sentinel=100.0, subset_ids=None, rule=QIDS_TABLE_ORDER):
+        """pq_search for the rows of the VectorIndex `vecs` with these ids, gathered on the device (freddy_gpu_pq_search_ids):
+        (query_ids[Q], ids[Q,k], dist[Q,k]) with Q = the queries `rule` selects; per query bit for bit search(<its row of vecs>, k, ...)."""
+        sub = None if subset_ids is None else _i32(subset_ids)
+        return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_pq_search_ids(
+            self.h, vecs.h, _p(q), n, rule, k, C.c_float(sentinel), _p(sub), 0 if sub is None else sub.size, _p(oq), C.byref(nq), _p(oi), _p(od)))
+
+    def search_pv_ids(self, vecs, ids, k, pvf, sentinel=100.0, subset_ids=None, rule=QIDS_TABLE_ORDER):
+        """search_pv for the rows of `vecs` with these ids (freddy_gpu_pq_search_pv_ids): (query_ids[Q], ids[Q,k], similarity[Q,k])."""
+        sub = None if subset_ids is None else _i32(subset_ids)
+        return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_pq_search_pv_ids(
+            self.h, vecs.h, _p(q), n, rule, k, pvf, C.c_float(sentinel), _p(sub), 0 if sub is None else sub.size, _p(oq), C.byref(nq), _p(oi), _p(od)))
 
     def analogy(self, vecs, triples, k=1, n_cand=23, sentinel=100.0, subset_ids=None):
         """Approximate 3CosAdd analogies (freddy_gpu_pq_analogy): triples [Q][3] of row ids (w1, w2, w3) -> (ids[Q,k], similarity[Q,k]);
@@ -550,6 +593,17 @@ class IVFIndex(_Index):
         _check(self.lib.freddy_gpu_ivfadc_search_pv(self.h, vecs.h, _p(qs), Q, k, pvf, W, C.c_float(sentinel), found_rule,
                                                     _p(out_i), _p(out_s)))
         return out_i, out_s
+
+    def search_ids(self, vecs, ids, k, W, sentinel=1000.0, found_rule=FOUND_ROWS, rule=QIDS_TABLE_ORDER):
+        """ivfadc_search for the rows of the VectorIndex `vecs` with these ids, gathered on the device (freddy_gpu_ivfadc_search_ids):
+        (query_ids[Q], ids[Q,k], dist[Q,k]) with Q = the queries `rule` selects; per query bit for bit search(<its row of vecs>, k, W, ...)."""
+        return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_ivfadc_search_ids(
+            self.h, vecs.h, _p(q), n, rule, k, W, C.c_float(sentinel), found_rule, _p(oq), C.byref(nq), _p(oi), _p(od)))
+
+    def search_pv_ids(self, vecs, ids, k, pvf, W, sentinel=1000.0, found_rule=FOUND_ROWS, rule=QIDS_TABLE_ORDER):
+        """search_pv for the rows of `vecs` with these ids (freddy_gpu_ivfadc_search_pv_ids): (query_ids[Q], ids[Q,k], similarity[Q,k])."""
+        return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_ivfadc_search_pv_ids(
+            self.h, vecs.h, _p(q), n, rule, k, pvf, W, C.c_float(sentinel), found_rule, _p(oq), C.byref(nq), _p(oi), _p(od)))
 
     def analogy(self, vecs, triples, k=1, n_cand=23, W=3, sentinel=1000.0, found_rule=FOUND_ROWS):
         """Approximate 3CosAdd analogies (freddy_gpu_ivfadc_analogy): triples [Q][3] of row ids (w1, w2, w3) -> (ids[Q,k],
