@@ -258,6 +258,43 @@ int freddy_gpu_pq_assign(freddy_gpu_index_t* pq, const float* queries /*[Q][d]*/
                          const int32_t* target_ids, int64_t n_targets, int32_t* out_query /*[n_targets]*/,
                          float* out_sim /*[n_targets]*/);
 
+/* ---- similarities by row id: pairs, matrices, joins (similarity.h) --------------------------------------------------------
+ * cosine_similarity(token1, token2) (freddy--0.0.1.sql:946-959) finds two rows of google_vecs_norm and runs
+ * cosine_similarity_bytea (core_functions.c:67-81) on them; cosine_similarity_bytea(vector, token) (:961-974) takes the first
+ * operand from the caller.  The usual query calls them once per row of a join, often under "WHERE cosine_similarity(..) > t".
+ * These calls are the batched forms on the pinned vector handle: they return the VALUES, with no ranking around them.
+ *   A similarity is the binary32 chain "scalar = 0; scalar += v1[i] * v2[i]", i ascending, every product and sum rounded on
+ *   its own -- bit for bit cosine_similarity_bytea of the two rows (so the matrix cores cannot be used: the order is fixed).
+ *   Ids are resolved on the device against the handle's ascending ids: a table with gaps needs no lookup by the caller, and a
+ *   call sees every append_rows / update_rows / remove_rows made before it.
+ * freddy_gpu_similarity_pairs: out_sim[i] = the chain over the rows of ids_a[i] (v1) and ids_b[i] (v2); out_known[i] = 1 when
+ *   both ids have a row, else 0 and out_sim[i] = 0.0f (the SQL's NULL).  Any n >= 0 (passes of 2^22 pairs).
+ * freddy_gpu_similarity_matrix: exactly one of a_ids / a_vectors is non-NULL -- the A side is na rows named by id, or [na][d]
+ *   floats of the caller's (the vector overload).  out[i][j] = the chain with v1 = A row i, v2 = the row of b_ids[j]; entries of
+ *   an id without a row are 0.0f, known_a[na] / known_b[nb] say which (known_a is all 1 for vectors).  Either side may repeat
+ *   an id.  nb <= 2^22 (FREDDY_E_LIMIT above, the message names the value), any na: A is walked in passes whose device result
+ *   block stays within 256 MiB (option "similarity_pass_bytes"; a multiple of 16 rows of A, 16 at least), one D2H copy per pass.
+ * freddy_gpu_similarity_join: "WHERE cosine_similarity(a, b) > threshold": every (i, j) with both rows known and
+ *   sim > threshold in PostgreSQL's float4 order (float4gt: a NaN similarity is greater than every non-NaN threshold, nothing is
+ *   greater than a NaN threshold, -0.0 is not greater than +0.0).  out_a / out_b are 0-based POSITIONS in the A / B arguments
+ *   (not ids), out_sim the value; the order is i ascending, then j ascending -- always.  *n_pairs = the number of matches
+ *   whatever max_pairs is; the first min(*n_pairs, max_pairs) in that order are written.  max_pairs = 0 (the outputs may be
+ *   NULL) only counts.  Every chain is computed once, and only the matches that are written leave the device.
+ * Errors, all before any device work and the scalars before the handle: FREDDY_E_ARG for a negative size, for both or neither
+ * of a_ids / a_vectors, for a NULL buffer that would be read or written (n > 0; na > 0 and nb > 0; the join's outputs when
+ * max_pairs > 0; n_pairs always), max_pairs < 0; FREDDY_E_LIMIT for nb > 2^22; FREDDY_E_ARG for a NULL handle, FREDDY_E_KIND
+ * for one of the wrong kind.  A refused call writes nothing, *n_pairs included.  A zero size succeeds with no device work
+ * (*n_pairs = 0), and so does a call in which no id has a row (zeros, known = 0, *n_pairs = 0: nothing is launched). */
+int freddy_gpu_similarity_pairs(freddy_gpu_index_t* vecs, const int32_t* ids_a /*[n]*/, const int32_t* ids_b /*[n]*/, int64_t n,
+                                float* out_sim /*[n]*/, uint8_t* out_known /*[n]*/);
+int freddy_gpu_similarity_matrix(freddy_gpu_index_t* vecs, const int32_t* a_ids /*[na] or NULL*/, const float* a_vectors /*[na][d] or NULL*/,
+                                 int32_t na, const int32_t* b_ids /*[nb]*/, int64_t nb, float* out /*[na][nb]*/,
+                                 uint8_t* known_a /*[na]*/, uint8_t* known_b /*[nb]*/);
+int freddy_gpu_similarity_join(freddy_gpu_index_t* vecs, const int32_t* a_ids /*[na] or NULL*/, const float* a_vectors /*[na][d] or NULL*/,
+                               int32_t na, const int32_t* b_ids /*[nb]*/, int64_t nb, float threshold, int64_t max_pairs,
+                               int32_t* out_a /*[max_pairs]*/, int32_t* out_b /*[max_pairs]*/, float* out_sim /*[max_pairs]*/,
+                               int64_t* n_pairs);
+
 /* ---- batched post verification: the ANN handles and the raw-vector handle in one call (pv.h) ----------------------------
  * k_nearest_neighbour_ivfadc_pv / k_nearest_neighbour_pq_pv (freddy--0.0.1.sql:556-662) for Q queries: fetch k * pvf candidates
  * with the approximate search, re-rank them by cosine_similarity_bytea against the raw vectors, keep the first k.
@@ -644,7 +681,8 @@ int freddy_gpu_abi_version(void);
  *                refine: -1 = tables of >= 8192 rows and k <= 32, 0 never -- and no fragment copy of a table pinned with it --,
  *                1 always), "exact_join_tile" (queries per workgroup of the exact join's filter: 0 = 128 when Q > 64 and
  *                d <= 320, else 64; 64 = never 128), "analogy_pass" (triples per pass of the approximate analogies: 0 = as many as
- *                keep a pass's lists within 8 M entries)
+ *                keep a pass's lists within 8 M entries), "similarity_pass_bytes" (the device result block of one pass of A rows of
+ *                freddy_gpu_similarity_matrix / _join: 0 = 256 MiB, at most 4 GiB; always 16 rows of A at least)
  *   self-checks (tests):  "check_brackets" (bit 0: the scan keeps and the merge refines EVERY probed row, bit 1: the cell
  *                selection refines every cell, bit 2: exact kNN and the exact join refine every row -- each with its proven bracket compared with
  *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines

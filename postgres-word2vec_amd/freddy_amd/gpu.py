@@ -38,6 +38,7 @@ EXPORTS = [
     "freddy_gpu_debug_alloc_fail_nth", "freddy_gpu_debug_alloc_track", "freddy_gpu_debug_alloc_stats",
     "freddy_gpu_scan_elastic_stats",
     "freddy_gpu_ivfadc_search_ids", "freddy_gpu_pq_search_ids", "freddy_gpu_ivfadc_search_pv_ids", "freddy_gpu_pq_search_pv_ids",
+    "freddy_gpu_similarity_pairs", "freddy_gpu_similarity_matrix", "freddy_gpu_similarity_join",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together): ids per pass of freddy_gpu_create_statistics
@@ -152,7 +153,13 @@ def load(path=None, optional=()):
                         ("freddy_gpu_ivfadc_search_pv_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                              C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
                         ("freddy_gpu_pq_search_pv_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
+                                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                        # similarities by row id (the same holds for them)
+                        ("freddy_gpu_similarity_pairs", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_similarity_matrix", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p]),
+                        ("freddy_gpu_similarity_join", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_float, C.c_int64,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = types
     lib.freddy_gpu_pq_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
@@ -539,6 +546,64 @@ class VectorIndex(_Index):
         target_ids[i] -- the first query under "cosine_similarity_bytea DESC (PostgreSQL's float4 order), query index ASC", the
         similarity bits of join(); (-1, -inf) where the id has no row."""
         return _assign(self, self.lib.freddy_gpu_exact_assign, queries, target_ids, ())
+
+    def similarity_pairs(self, ids_a, ids_b):
+        """cosine_similarity(token1, token2) for n pairs of row ids (freddy_gpu_similarity_pairs): (sim[n] float32, known[n] bool);
+        a pair with an id that has no row is (0.0, False)."""
+        a, b = _i32(ids_a).reshape(-1), _i32(ids_b).reshape(-1)
+        if a.size != b.size:
+            raise FreddyGpuError(f"ids_a has {a.size} ids, ids_b {b.size}")
+        sim = np.empty(a.size, np.float32)
+        known = np.empty(a.size, np.uint8)
+        _check(self.lib.freddy_gpu_similarity_pairs(self.h, _p(a), _p(b), a.size, _p(sim), _p(known)))
+        return sim, known.astype(bool)
+
+    def _sim_a(self, a):
+        """The A side of similarity_matrix / similarity_join: an integer array is row ids, a 2-d float array is vectors -> (ids, vectors, na)"""
+        a = np.asarray(a)
+        if np.issubdtype(a.dtype, np.integer):
+            if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise FreddyGpuError("row ids are 32-bit integers")
+            ids = _i32(a).reshape(-1)
+            return ids, None, ids.size
+        if a.ndim != 2 or a.shape[1] != self.d or not np.issubdtype(a.dtype, np.floating):
+            raise FreddyGpuError(f"the A side is an integer array of row ids or a float array [na][{self.d}]")
+        v = _f32(a)
+        return None, v, v.shape[0]
+
+    def similarity_matrix(self, a, b_ids):
+        """All similarities of A (row ids, or [na][d] float vectors: cosine_similarity_bytea(vector, token)) against the rows of b_ids
+        (freddy_gpu_similarity_matrix): (out[na, nb] float32, known_a[na] bool, known_b[nb] bool); entries of an id without a row are 0.0."""
+        ids, v, na = self._sim_a(a)
+        b = _i32(b_ids).reshape(-1)
+        out = np.empty((na, b.size), np.float32)
+        ka, kb = np.empty(na, np.uint8), np.empty(b.size, np.uint8)
+        # (a side without elements still names itself: the library refuses "both or neither")
+        _check(self.lib.freddy_gpu_similarity_matrix(self.h, _p(ids) if ids is not None else None, _p(v) if v is not None else None, na,
+                                                     _p(b), b.size, _p(out), _p(ka), _p(kb)))
+        return out, ka.astype(bool), kb.astype(bool)
+
+    def similarity_join(self, a, b_ids, threshold, max_pairs=None):
+        """WHERE cosine_similarity(a, b) > threshold (freddy_gpu_similarity_join; PostgreSQL's float4 order): (ia, ib, sim, total) --
+        0-based positions in a and b_ids and the value of the first min(total, max_pairs) matches, i ascending then j ascending; total
+        counts every match.  max_pairs=None: a count call first, then all of them."""
+        ids, v, na = self._sim_a(a)
+        b = _i32(b_ids).reshape(-1)
+        total = C.c_int64(0)
+
+        def call(cap, ia, ib, sim):
+            _check(self.lib.freddy_gpu_similarity_join(self.h, _p(ids) if ids is not None else None, _p(v) if v is not None else None, na,
+                                                       _p(b), b.size, C.c_float(threshold), cap, _p(ia), _p(ib), _p(sim), C.byref(total)))
+        counted = max_pairs is None
+        if counted:
+            call(0, None, None, None)
+            max_pairs = total.value
+        max_pairs = int(max_pairs)
+        ia, ib, sim = np.empty(max_pairs, np.int32), np.empty(max_pairs, np.int32), np.empty(max_pairs, np.float32)
+        if max_pairs > 0 or not counted:
+            call(max_pairs, ia, ib, sim)
+        n = min(int(total.value), int(max_pairs))
+        return ia[:n], ib[:n], sim[:n], int(total.value)
 
     def last_join_stats(self):
         """The last join() call (freddy_gpu_last_exact_join_stats): queries the filter ran for, candidates refined, queries redone all-exact."""
