@@ -258,6 +258,39 @@ int freddy_gpu_pq_assign(freddy_gpu_index_t* pq, const float* queries /*[Q][d]*/
                          const int32_t* target_ids, int64_t n_targets, int32_t* out_query /*[n_targets]*/,
                          float* out_sim /*[n_targets]*/);
 
+/* ---- the whole k-means of cluster_exact / cluster_pq in one call (cluster.h) ----------------------------------------------
+ * generic_cluster (freddy--0.0.1.sql:1086-1209) with the draws of random() supplied by the caller; pq == NULL: cluster_exact,
+ * else cluster_pq.  The semantics, bit for bit those of the host mirror's loop around the two assign calls above:
+ *   pick(u, r) = min(max(rint(r * u + 0.5), 1), u)  in binary64, the product rounded before the sum, rint half to even
+ *                (include/freddy_pick.h).
+ *   Start.   clusters[n] = 0, lens[kc] = 0; centroid[I] = the row in `vecs` of token_ids[pick(n, draws[I]) - 1], I = 0 .. kc - 1.
+ *   Round J = 1 .. rounds.   (best, sim) = what freddy_gpu_exact_assign(vecs, centroids, kc, token_ids, n) returns, resp.
+ *            freddy_gpu_pq_assign(pq, centroids, kc, sentinel, token_ids, n) -- the same kernels, the same bits.  Every position i
+ *            with best[i] >= 0: clusters[i] = best[i] + 1 and lens[best[i]] += 1.  A position no centroid claims keeps its cluster:
+ *            it then counts as a member but not in lens.
+ *   If J < rounds, for every I, with base = kc + ((J - 1) * kc + I) * 10:
+ *            lens[I] == 0: the centroid stays (its ten draws are not used, but they are counted).
+ *            Otherwise members = the positions i with clusters[i] == I + 1, ascending; for t = 0 .. 9: x = pick(lens[I], draws[base + t]),
+ *            and if x <= |members| the row of token members[x - 1] is a sample (repeats allowed).  With ns > 0 samples in draw
+ *            order: c = 0, then c[j] = c[j] + (row[j] / (float)ns) -- every operation binary32, the division the correctly rounded
+ *            one, never a reciprocal multiply (centroid_bytea, core_functions.c:371-379).  lens[I] = 0.
+ *   Outputs. out_cluster[i] = 1 .. kc, or 0 for a position no round claimed; out_sim[i] (may be NULL) = the last round's similarity,
+ *            -inf where the last round claimed nothing; out_centroids (may be NULL) = the centroids the last assignment used.
+ * Outputs are positional: a repeated id is a token per position.  Ids are resolved on the device against the handle's current
+ * ids, so a call sees every append_rows / update_rows / remove_rows made before it.
+ * Errors, all before any device work and the scalars before the handles: FREDDY_E_ARG for n <= 0, kc <= 0, rounds <= 0, a NULL
+ * token_ids / draws / out_cluster, n_draws < kc + 10 * kc * (rounds - 1) (the message names both numbers), a NaN among the draws
+ * the call would use, the sentinel rule of freddy_gpu_pq_assign (pq != NULL only); FREDDY_E_LIMIT for kc > 65536 and n > 2^31 - 1;
+ * FREDDY_E_ARG for a NULL vecs, FREDDY_E_KIND for handles of the wrong kind, FREDDY_E_ARG for handles on different devices or of
+ * different d.  A token id without a row in `vecs` is the reference's "token id %d has no vector": FREDDY_E_ARG naming the first
+ * such id by position (found on the device: a flag word, no host search); a refused call writes none of the outputs.  A failed
+ * allocation gives FREDDY_E_NOMEM, leaves the handles as they were, and the call may be repeated.
+ * One call enqueues everything on the vector handle's stream: ids and draws go up, the outputs come down, and the host does not
+ * wait for the device between the rounds.  The assignment takes 2^22 targets per pass (option "cluster_pass", 64 at least). */
+int freddy_gpu_cluster(freddy_gpu_index_t* vecs, freddy_gpu_index_t* pq /* NULL: cluster_exact */, float sentinel /* pq only */,
+                       const int32_t* token_ids, int64_t n, int32_t kc, int32_t rounds, const double* draws, int64_t n_draws,
+                       int32_t* out_cluster /*[n]*/, float* out_sim /*[n] or NULL*/, float* out_centroids /*[kc][d] or NULL*/);
+
 /* ---- similarities by row id: pairs, matrices, joins (similarity.h) --------------------------------------------------------
  * cosine_similarity(token1, token2) (freddy--0.0.1.sql:946-959) finds two rows of google_vecs_norm and runs
  * cosine_similarity_bytea (core_functions.c:67-81) on them; cosine_similarity_bytea(vector, token) (:961-974) takes the first
@@ -682,7 +715,10 @@ int freddy_gpu_abi_version(void);
  *                1 always), "exact_join_tile" (queries per workgroup of the exact join's filter: 0 = 128 when Q > 64 and
  *                d <= 320, else 64; 64 = never 128), "analogy_pass" (triples per pass of the approximate analogies: 0 = as many as
  *                keep a pass's lists within 8 M entries), "similarity_pass_bytes" (the device result block of one pass of A rows of
- *                freddy_gpu_similarity_matrix / _join: 0 = 256 MiB, at most 4 GiB; always 16 rows of A at least)
+ *                freddy_gpu_similarity_matrix / _join: 0 = 256 MiB, at most 4 GiB; always 16 rows of A at least), "cluster_pass" (targets
+ *                per assignment pass of freddy_gpu_cluster: 0 = 2^22; 64 at least), "cluster_walk" (how freddy_gpu_cluster finds a
+ *                cluster's sampled members: 1 = by walking all positions, as it does beyond 1024 clusters; 2 = from per-block counts;
+ *                0 = auto: 2 from n > 32768 tokens on)
  *   self-checks (tests):  "check_brackets" (bit 0: the scan keeps and the merge refines EVERY probed row, bit 1: the cell
  *                selection refines every cell, bit 2: exact kNN and the exact join refine every row -- each with its proven bracket compared with
  *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines

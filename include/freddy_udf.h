@@ -192,9 +192,11 @@ int knn_batch(freddy_session_t* s, const int32_t* query_ids, int32_t n_query_ids
  *   centroid, as the reference does.  `draws` are the values random() returns, in call order (k, then 10 per
  *   cluster and round): a caller-supplied sequence makes a run reproducible; once it is used up (or NULL) an
  *   internal generator continues.  cluster_out[i] = 1..k for token i (0: no centroid listed it).
- *   cluster_exact and cluster_pq take any number of tokens: the assignment is one device call per round that returns the first
- *   centroid of every token (exact_assign / pq_assign below; freddy_gpu_exact_assign / freddy_gpu_pq_assign), not lists of all
- *   tokens per centroid.  cluster_ivpq needs the kNN-join's lists themselves and keeps freddy_gpu_knn_join's limits on k = n. */
+ *   cluster_exact and cluster_pq take any number of tokens and are ONE device call (freddy_gpu_cluster): the draw sequence is filled
+ *   first -- the caller's draws, then the internal generator, k + 90 k values -- and the ten rounds (the assignment of exact_assign /
+ *   pq_assign below, the member ranks, the ten samples and their mean) stay on the device; a run with or without supplied draws
+ *   returns what the loop around the assign calls returned.  (Loaded beside a libfreddy_gpu.so without that entry point, the mirror
+ *   runs that loop.)  cluster_ivpq needs the kNN-join's lists themselves and keeps freddy_gpu_knn_join's limits on k = n. */
 int analogy_3cosadd_in_pq(freddy_session_t* s, int32_t id1, int32_t id2, int32_t id3, const int32_t* input_ids, int32_t n_ids, int32_t* result);
 /* The batch forms of the approximate analogies: results[i] = what the single-triple function returns for triples[i] (-1 where the SQL
  * returns NULL), all n triples in ONE device call (freddy_gpu_ivfadc_analogy / freddy_gpu_pq_analogy, approx_analogy.h) with

@@ -272,6 +272,8 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   else if (n == "exact_filter") t.exact_filter = (int)value;
   else if (n == "exact_join_tile") t.exact_join_tile = (int)value;
   else if (n == "analogy_pass") t.analogy_pass = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
+  else if (n == "cluster_pass") t.cluster_pass = value <= 0 ? 0 : (int)std::max<int64_t>(64, std::min<int64_t>(value, (int64_t)1 << 30));
+  else if (n == "cluster_walk") t.cluster_walk = value == 1 || value == 2 ? (int)value : 0;
   else if (n == "similarity_pass_bytes") t.similarity_pass_bytes = std::max<int64_t>(0, std::min<int64_t>(value, (int64_t)4 << 30));   // (a block's match count is a 32-bit number)
   else if (n == "codes_u8") t.codes_u8 = (int)value;
   else if (n == "running_bound") t.running_bound = (int)value;

@@ -10,7 +10,7 @@
 //   join.hip    pin_ivpq, knn_join (join.h: overview; join_kernels.h and join_traverse.h the kernels, join_host.h the host heap, join_run.h the run
 //               record of a call and its stages)
 //   exact.hip   pin_vectors, exact kNN, the exact join, analogies, post verification of pq / ivf lists (pv.h), approximate analogies (approx_analogy.h),
-//               exact_assign (assign.h), similarities by row id (similarity.h); exact_host.h the host sequences they share: the filter + refine chain, scan chunking, the re-rank stage, triple resolution
+//               exact_assign (assign.h), the whole k-means of cluster_exact / cluster_pq (cluster.h), similarities by row id (similarity.h); exact_host.h the host sequences they share: the filter + refine chain, scan chunking, the re-rank stage, triple resolution
 //   build.hip   encode, insert_quantize, k-means
 // Kernel headers are included by the unit that launches them (kernels shared by two units are static or templates).
 #pragma once
@@ -87,6 +87,8 @@ struct Tuning {
   int exact_filter = -1;       // FREDDY_GPU_EXACT_FILTER: exact kNN as MFMA filter + exact refine (exact2.h): -1 auto (tables of >= 8192 rows, k <= 32), 0 never, 1 always
   int exact_join_tile = 0;     // option exact_join_tile: queries per workgroup of the exact join's filter (exact_join.h): 0 auto (128 when Q > 64 and d <= 320), 64
   int analogy_pass = 0;        // option analogy_pass: triples per pass of the approximate analogies (approx_analogy.h): 0 = pv_search's bound (lists of at most 8 M entries)
+  int cluster_pass = 0;        // option cluster_pass: targets per assignment pass of freddy_gpu_cluster (cluster.h): 0 = 2^22; 64 at least
+  int cluster_walk = 0;        // option cluster_walk: how cluster_sample_kernel finds a cluster's ranked members: 1 = it walks them from position 0 (what it does for kc > 1024), 2 = over the apply kernel's per-block counts (kc <= 1024), 0 = auto: 2 from n > 32768 on
   int64_t similarity_pass_bytes = 0;   // option similarity_pass_bytes: the device result block of one pass of freddy_gpu_similarity_matrix / _join (similarity.h): 0 = 256 MiB, at most 4 GiB; 16 rows of A at least
   // -- self-checks (tests): bit 0 = the scan keeps every row and the merge refines every row (every probed row's bracket is checked),
   //    bit 1 = the cell selection refines every cell, bit 2 = exact kNN refines every row
@@ -432,6 +434,10 @@ int one_finish(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, volatile cons
 
 // ---- pq.hip ----
 int pq_shadow_build(freddy_gpu_index* ix);
+// the assignment step of cluster_pq on device pointers (freddy_gpu_pq_assign and freddy_gpu_cluster share it)
+int pq_assign_lut_queries(const freddy_gpu_index* ix, int Q);
+int pq_assign_pass(freddy_gpu_index* ix, hipStream_t s, float* d_lut, int Qc, int* lut_q0, const float* d_queries, int Q, float sentinel,
+                   const int32_t* d_targets, int n, int32_t* d_best, float* d_sim, float* d_best_dist);
 
 // ---- exact.hip ----
 int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n, const std::vector<int32_t>* changed_strips = nullptr);

@@ -555,6 +555,40 @@ extern "C" int freddy_gpu_grouping_pq(freddy_gpu_index_t* ix, const float* group
 static constexpr int64_t AS_PQ_PASS = (int64_t)1 << 22;
 static constexpr size_t AS_PQ_LUT_BYTES = (size_t)64 << 20;
 
+// LUTs built at a time for a call of Q queries (the size of the buffer pq_assign_pass is given)
+int pq_assign_lut_queries(const freddy_gpu_index* ix, int Q) {
+  const size_t lut_bytes = (size_t)ix->m * ix->K * sizeof(float);
+  return (int)std::min<size_t>((size_t)Q, std::max<size_t>(1, AS_PQ_LUT_BYTES / lut_bytes));
+}
+
+// One pass of n targets with everything on the device: the queries, the target ids, the three state arrays and the LUT buffer of Qc
+// LUTs (*lut_q0: the first query of the chunk whose LUTs it holds, -1 = none; kept between the passes of a call).  Enqueued on s;
+// best / sim hold the result behind the last launch.  freddy_gpu_pq_assign and freddy_gpu_cluster (exact.hip) both assign through it.
+int pq_assign_pass(freddy_gpu_index* ix, hipStream_t s, float* d_lut, int Qc, int* lut_q0, const float* d_queries, int Q, float sentinel,
+                   const int32_t* d_targets, int n, int32_t* d_best, float* d_sim, float* d_best_dist) {
+  const int m = ix->m, K = ix->K, d = ix->d;
+  const size_t lut_bytes = (size_t)m * K * sizeof(float);
+  const int LT = (int)std::min<size_t>(8, std::max<size_t>(1, ((size_t)64 << 10) / lut_bytes));   // LUTs staged in LDS at a time
+  // four targets per thread once that still gives every CU two workgroups: a staged LUT then serves 1024 targets
+  const int RPT = (int64_t)n >= (int64_t)ix->n_cus * 2 * 4 * AS_PQ_WG ? 4 : 1;
+  const dim3 grid((unsigned)((n + RPT * AS_PQ_WG - 1) / (RPT * AS_PQ_WG)));
+  for (int q0 = 0; q0 < Q; q0 += Qc) {
+    const int nq = std::min(Qc, Q - q0);
+    if (*lut_q0 != q0) {
+      if (int rc = launch_lut(ix, s, d_queries + (size_t)q0 * d, nullptr, d_lut, nq)) return rc;   // freddy.c:1288-1299
+      *lut_q0 = q0;
+    }
+    AssignPqArgs aa;
+    aa.lut = d_lut; aa.targets = d_targets; aa.ids = ix->ids; aa.packed = ix->packed;
+    aa.out_query = d_best; aa.out_sim = d_sim; aa.best_dist = d_best_dist;
+    aa.N = ix->N; aa.n_targets = n; aa.q_base = q0; aa.nq = nq; aa.m = m; aa.K = K; aa.LT = LT; aa.first = q0 == 0 ? 1 : 0; aa.sentinel = sentinel;
+    const size_t lds = (size_t)LT * lut_bytes;
+    timed_launch(ix, s, "assign_pq_kernel", [&] { hipLaunchKernelGGL(assign_pq_kernel_for(ix->M2, RPT), grid, dim3(AS_PQ_WG), lds, s, aa); });
+    HIP_TRY(hipGetLastError());
+  }
+  return FREDDY_OK;
+}
+
 extern "C" int freddy_gpu_pq_assign(freddy_gpu_index_t* ix, const float* queries, int32_t Q, float sentinel, const int32_t* target_ids,
                                     int64_t n_targets, int32_t* out_query, float* out_sim) {
   // (the scalar arguments first: they are checked before the handle is looked at, so no device is needed to see these errors)
@@ -570,10 +604,9 @@ extern "C" int freddy_gpu_pq_assign(freddy_gpu_index_t* ix, const float* queries
   HIP_TRY(hipSetDevice(ix->device));
   Workspace* ws = workspace_for(ix, ix->stream);
   hipStream_t s = ix->stream;
-  const int m = ix->m, K = ix->K, d = ix->d;
-  const size_t lutN = (size_t)m * K, lut_bytes = lutN * sizeof(float);
-  const int LT = (int)std::min<size_t>(8, std::max<size_t>(1, ((size_t)64 << 10) / lut_bytes));   // LUTs staged in LDS at a time
-  const int Qc = (int)std::min<size_t>((size_t)Q, std::max<size_t>(1, AS_PQ_LUT_BYTES / lut_bytes));   // LUTs built at a time
+  const int d = ix->d;
+  const size_t lut_bytes = (size_t)ix->m * ix->K * sizeof(float);
+  const int Qc = pq_assign_lut_queries(ix, Q);
   const int64_t pass = std::min(AS_PQ_PASS, n_targets);
   if (ws->w_q.ensure(sizeof(float) * (size_t)Q * d) || ws->w_lut.ensure(lut_bytes * (size_t)Qc) || ws->w_sub_rows.ensure(sizeof(int32_t) * (size_t)pass) ||
       ws->w_out_ids.ensure(sizeof(int32_t) * (size_t)pass) || ws->w_out_dist.ensure(sizeof(float) * (size_t)pass) ||
@@ -584,23 +617,9 @@ extern "C" int freddy_gpu_pq_assign(freddy_gpu_index_t* ix, const float* queries
   for (int64_t t0 = 0; t0 < n_targets; t0 += pass) {
     const int n = (int)std::min(pass, n_targets - t0);
     HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, target_ids + t0, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-    // four targets per thread once that still gives every CU two workgroups: a staged LUT then serves 1024 targets
-    const int RPT = (int64_t)n >= (int64_t)ix->n_cus * 2 * 4 * AS_PQ_WG ? 4 : 1;
-    const dim3 grid((unsigned)((n + RPT * AS_PQ_WG - 1) / (RPT * AS_PQ_WG)));
-    for (int q0 = 0; q0 < Q; q0 += Qc) {
-      const int nq = std::min(Qc, Q - q0);
-      if (lut_q0 != q0) {
-        if (int rc = launch_lut(ix, s, ws->w_q.as<float>() + (size_t)q0 * d, nullptr, ws->w_lut.as<float>(), nq)) return rc;   // freddy.c:1288-1299
-        lut_q0 = q0;
-      }
-      AssignPqArgs aa;
-      aa.lut = ws->w_lut.as<float>(); aa.targets = ws->w_sub_rows.as<int32_t>(); aa.ids = ix->ids; aa.packed = ix->packed;
-      aa.out_query = ws->w_out_ids.as<int32_t>(); aa.out_sim = ws->w_out_dist.as<float>(); aa.best_dist = ws->w_found.as<float>();
-      aa.N = ix->N; aa.n_targets = n; aa.q_base = q0; aa.nq = nq; aa.m = m; aa.K = K; aa.LT = LT; aa.first = q0 == 0 ? 1 : 0; aa.sentinel = sentinel;
-      const size_t lds = (size_t)LT * lut_bytes;
-      timed_launch(ix, s, "assign_pq_kernel", [&] { hipLaunchKernelGGL(assign_pq_kernel_for(ix->M2, RPT), grid, dim3(AS_PQ_WG), lds, s, aa); });
-      HIP_TRY(hipGetLastError());
-    }
+    if (int rc = pq_assign_pass(ix, s, ws->w_lut.as<float>(), Qc, &lut_q0, ws->w_q.as<float>(), Q, sentinel, ws->w_sub_rows.as<int32_t>(), n,
+                                ws->w_out_ids.as<int32_t>(), ws->w_out_dist.as<float>(), ws->w_found.as<float>()))
+      return rc;
     HIP_TRY(hipMemcpyAsync(out_query + t0, ws->w_out_ids.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(out_sim + t0, ws->w_out_dist.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));   // (the next pass overwrites the buffers)

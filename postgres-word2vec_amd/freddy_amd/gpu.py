@@ -39,6 +39,7 @@ EXPORTS = [
     "freddy_gpu_scan_elastic_stats",
     "freddy_gpu_ivfadc_search_ids", "freddy_gpu_pq_search_ids", "freddy_gpu_ivfadc_search_pv_ids", "freddy_gpu_pq_search_pv_ids",
     "freddy_gpu_similarity_pairs", "freddy_gpu_similarity_matrix", "freddy_gpu_similarity_join",
+    "freddy_gpu_cluster",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together): ids per pass of freddy_gpu_create_statistics
@@ -159,7 +160,10 @@ def load(path=None, optional=()):
                         ("freddy_gpu_similarity_matrix", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                           C.c_void_p]),
                         ("freddy_gpu_similarity_join", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_float, C.c_int64,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])):
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                        # the whole k-means of cluster_exact / cluster_pq (the same again)
+                        ("freddy_gpu_cluster", [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = types
     lib.freddy_gpu_pq_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
@@ -546,6 +550,20 @@ class VectorIndex(_Index):
         target_ids[i] -- the first query under "cosine_similarity_bytea DESC (PostgreSQL's float4 order), query index ASC", the
         similarity bits of join(); (-1, -inf) where the id has no row."""
         return _assign(self, self.lib.freddy_gpu_exact_assign, queries, target_ids, ())
+
+    def cluster(self, token_ids, kc, draws, rounds=10, pq=None, sentinel=1000.0):
+        """The whole k-means of cluster_exact (pq=None) / cluster_pq (pq: a PQIndex) in one call (freddy_gpu_cluster): (clusters[n] int32,
+        1 .. kc or 0 for a position no round claimed; similarity[n] of the last round, -inf where it claimed nothing; centroids[kc, d]
+        the last assignment used).  draws: the float64 values of random(), kc + 10 * kc * (rounds - 1) of them at least."""
+        t = _i32(token_ids).reshape(-1)
+        dr = np.ascontiguousarray(draws, np.float64).reshape(-1)
+        kc = int(kc)
+        out_c = np.empty(t.size, np.int32)
+        out_s = np.empty(t.size, np.float32)
+        out_m = np.empty((max(kc, 0), self.d), np.float32)
+        _check(self.lib.freddy_gpu_cluster(self.h, None if pq is None else pq.h, C.c_float(sentinel), _p(t) if t.size else None, t.size, kc, int(rounds),
+                                           _p(dr) if dr.size else None, dr.size, _p(out_c), _p(out_s), _p(out_m)))
+        return out_c, out_s, out_m
 
     def similarity_pairs(self, ids_a, ids_b):
         """cosine_similarity(token1, token2) for n pairs of row ids (freddy_gpu_similarity_pairs): (sim[n] float32, known[n] bool);

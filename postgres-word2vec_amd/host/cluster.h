@@ -1,5 +1,6 @@
 // cluster.h -- cluster_exact / cluster_pq / cluster_ivpq = generic_cluster (freddy--0.0.1.sql:1086-1209): the reference's plpgsql
-// k-means with its assignment step on the device.  Included by freddy_udf.cpp only, after similarity_of.
+// k-means.  cluster_exact and cluster_pq are ONE device call (freddy_gpu_cluster: the ten rounds stay in HBM); cluster_ivpq keeps the
+// loop below with its assignment from the kNN-join's lists.  Included by freddy_udf.cpp only, after similarity_of.
 #pragma once
 #include <cmath>
 
@@ -8,6 +9,11 @@
 namespace {
 struct SimRow { float sim; int qid; int tid; };
 }
+
+// The ABI version did not move with freddy_gpu_cluster (no struct grew, no entry point changed meaning), so this mirror may be loaded
+// beside a library that does not have it yet: the symbol is bound weakly, and without it the loop around the two assign calls runs.
+extern "C" int freddy_gpu_cluster(freddy_gpu_index_t*, freddy_gpu_index_t*, float, const int32_t*, int64_t, int32_t, int32_t, const double*, int64_t,
+                                  int32_t*, float*, float*) __attribute__((weak));
 
 // cluster_ivpq: (query, target, similarity) rows of knn_in_ivpq_batch (bytea[] overload: query = 1-based centroid index) for
 // k = all tokens; target as 1-based token index.  Its lists are the kNN-join's approximation, not "all tokens", so the rows
@@ -72,6 +78,16 @@ static int generic_cluster(freddy_session_t* s, int method, const int32_t* token
     const int v = (int)std::nearbyint(rnd() * upper + 0.5);   // float8 round() is rint()
     return v < 1 ? 1 : (v > upper ? upper : v);
   };
+  if (method != 2 && freddy_gpu_cluster) {   // the whole k-means on the device: the draw sequence in full, then one call
+    if (int rc = s->norm.pinned(s->device)) return rc;
+    if (method == 1 && !s->code[PQ].h) return fail(-1, "%s", kNotLoaded[PQ]);
+    std::vector<double> all((size_t)k + (size_t)90 * k);
+    for (double& r : all) r = rnd();
+    if (int rc = freddy_gpu_cluster(s->norm.h, method == 1 ? s->code[PQ].h : nullptr, 1000.0f, token_ids, n, k, 10, all.data(), (int64_t)all.size(),
+                                    cluster_out, nullptr, nullptr))
+      return gpu_fail(rc);
+    return 0;
+  }
   std::vector<const float*> tok((size_t)n);
   for (int i = 0; i < n; ++i) {
     tok[(size_t)i] = s->norm.find(token_ids[i]);
