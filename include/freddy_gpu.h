@@ -723,7 +723,13 @@ int freddy_gpu_abi_version(void);
  *                selection refines every cell, bit 2: exact kNN and the exact join refine every row -- each with its proven bracket compared with
  *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines
  *                every row for every analogy, counted the same way), "join_host_traversal",
- *                "join_libm_margin_ppm" */
+ *                "join_libm_margin_ppm", "grid_cus" (the CU count that every grid sized from the chip is planned with, and every
+ *                choice of a kernel made from it -- csrc/grid_plan.h: v <= 0 = the device's count, the default; otherwise
+ *                min(v, the device's count).  It can only shrink grids, never grow them: the workgroups of the one-launch kernels
+ *                wait for each other and must be co-resident.  With a small value every workgroup loops over many pieces of work
+ *                where at the device's count it takes one and leaves; also what a compute partition of the card would see.  It
+ *                reaches the replicas and a PQ handle's views, and holds across append_rows, remove_rows, update_rows and
+ *                update_codebook) */
 int freddy_gpu_set_option(freddy_gpu_index_t* index, const char* name, int64_t value);
 
 /* Thread-local message of the last failing call; valid until the next call. */

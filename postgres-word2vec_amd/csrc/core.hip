@@ -268,6 +268,11 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   else if (n == "one_launch") t.one_launch = (int)value;
   else if (n == "coarse_approx") t.coarse_approx = (int)value;
   else if (n == "check_brackets") t.check_brackets = (int)value;
+  else if (n == "grid_cus") {   // (never above the device's count: the one-launch kernels' workgroups must be co-resident)
+    ix->n_cus = grid_cus_value(value, ix->device_cus);
+    for (freddy_gpu_index* view : {ix->pq_shadow, ix->pq_sub_view})   // (a view built later copies it: pq_view_refresh)
+      if (view) view->n_cus = ix->n_cus;
+  }
   else if (n == "lut_budget_mb") t.lut_budget_mb = std::max<int64_t>(1, value);
   else if (n == "exact_filter") t.exact_filter = (int)value;
   else if (n == "exact_join_tile") t.exact_join_tile = (int)value;

@@ -28,7 +28,7 @@ int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n, const std::vect
   if (ix->exf_small.ensure(4096)) return fail(FREDDY_E_NOMEM, "device allocation failed");
   uint32_t* st = ix->exf_small.as<uint32_t>() + 512;   // (the upper part of the small buffer; the lower one is per-call state)
   HIP_TRY(hipMemsetAsync(st, 0, 16, ix->stream));
-  const unsigned grid = (unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)ix->n_cus * 8);
+  const unsigned grid = table_stats_grid(ix->n_cus, n);
   hipLaunchKernelGGL(exf_table_stats_kernel, dim3(grid), dim3(256), 0, ix->stream, ix->coarse + (size_t)r0 * ix->d, n, ix->d, st);
   HIP_TRY(hipGetLastError());
   uint32_t h[4] = {0, 0, 0, 0};
@@ -382,8 +382,7 @@ static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s,
     if (int rc = exf_chain(ix, s, p, nT, [&](auto sample, int64_t n_rows) {
       constexpr bool SAMPLE = decltype(sample)::value;
       filter_rows(fa, fp, SAMPLE, n_rows, ix->exf_sample.as<float>());
-      const int64_t wg_steps = (n_rows + 255) / 256;
-      const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(wg_steps, std::max<int64_t>((int64_t)ix->n_cus * 2 / qtiles, (wg_steps + 7) / 8)));
+      const int64_t gx = exact_join_gx(ix->n_cus, n_rows, qtiles);
       const dim3 grid((unsigned)gx, (unsigned)qtiles);
       switch (NT) {
         case 1: hipLaunchKernelGGL((exj_filter_kernel<1, SAMPLE>), grid, dim3(EXF_WG), tile_lds, s, fa); break;
@@ -1135,12 +1134,10 @@ static int sim_matrix_passes(freddy_gpu_index* ix, const int32_t* a_ids, const f
     }
     // workgroups: 64 B rows x a range of A tiles; A is split only until the chip has about sixteen waves per CU to place
     const int n_tiles = (n + SIM_AT - 1) / SIM_AT;
-    const int want = std::max(1, (16 * ix->n_cus + nblk - 1) / nblk);
-    const int split = std::min(n_tiles, want);
     SimMatrixArgs ma;
     ma.b_rows = ws->w_sub_pos.as<int32_t>(); ma.rows = ix->coarse; ma.a = ws->w_q.as<float>(); ma.known_a = a_ids ? ws->w_used.as<uint8_t>() : nullptr;
-    ma.out = ws->w_lut.as<float>(); ma.na = n; ma.nb = nb; ma.d = d; ma.tiles_per_wg = (n_tiles + split - 1) / split;
-    const dim3 grid((unsigned)nblk, (unsigned)((n_tiles + ma.tiles_per_wg - 1) / ma.tiles_per_wg));
+    ma.out = ws->w_lut.as<float>(); ma.na = n; ma.nb = nb; ma.d = d; ma.tiles_per_wg = sim_tiles_per_wg(ix->n_cus, n_tiles, nblk);
+    const dim3 grid((unsigned)nblk, sim_grid_y(ix->n_cus, n_tiles, nblk));
     timed_launch(ix, s, "sim_matrix_kernel", [&] { hipLaunchKernelGGL(sim_matrix_kernel, grid, dim3(64), 0, s, ma); });
     HIP_TRY(hipGetLastError());
     if (int rc = block((int32_t)a0, n, ma.out, ma.known_a, ws->w_found.as<const uint8_t>(), ws, s)) return rc;

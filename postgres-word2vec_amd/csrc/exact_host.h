@@ -20,7 +20,7 @@ static FilterPlan filter_plan(int64_t N, bool refine_all) {
 }
 // workgroups of a filter kernel over `rows` rows of the whole table: one per 256 rows, at most two per CU
 static unsigned filter_grid(const freddy_gpu_index* ix, int64_t rows) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, (int64_t)ix->n_cus * 2));
+  return freddy::filter_grid(ix->n_cus, rows);
 }
 // A filter kernel runs twice per pass: over the sample's strips (it writes the similarities the threshold kernel selects from),
 // then over all `n_rows` rows (it writes candidates).  What the two launches change in its arguments (ExfArgs, ExjArgs, AnFilterArgs).

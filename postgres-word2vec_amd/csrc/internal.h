@@ -37,6 +37,7 @@
 #include "hip_alloc.h"    // dev_malloc / dev_free / host_malloc / host_free: the only callers of the runtime's allocation functions
 #include "join_index.h"
 #include "pinned.h"
+#include "grid_plan.h"   // the grids and path choices made from n_cus
 
 using namespace freddy;
 
@@ -209,7 +210,8 @@ struct freddy_gpu_index {
   int max_list_blocks = 0;
   int64_t bytes = 0;
   int last_Q = 0;
-  int n_cus = 256;
+  int n_cus = 256;              // what every CU-sized grid is planned with (grid_plan.h): device_cus, or less under option grid_cus
+  int device_cus = 256;         // the device's count (open_device)
   // pinned tables
   float* coarse = nullptr;      // [C][d]
   float* coarseT = nullptr;     // [d][Cpad] for the coarse-distance kernel

@@ -292,7 +292,7 @@ int ivf_work_table(IvfRun& r, WorkTable& wt) {
   // (a negative option value forces the item-wise scan for cells of up to that many items whatever the batch: tests)
   const int sparse_max = r.scan_kernel != 5 ? 0
                          : ix->tune.sparse_items < 0 ? -ix->tune.sparse_items
-                         : ((size_t)n_items < 4 * (size_t)ix->C && n_items >= 16 * ix->n_cus) ? ix->tune.sparse_items : 0;
+                         : sparse_by_itself(ix->n_cus, n_items, ix->C) ? ix->tune.sparse_items : 0;
   wt.sp_cap = sparse_max > 0 ? (size_t)n_items * r.upi : 0;
   wt.sp_cell = base + 3 * wt.max_groups; wt.sp_first = wt.sp_cell + wt.sp_cap; wt.sp_chunk = wt.sp_first + wt.sp_cap;
   timed_launch(ix, s, "work_table", [&] {
@@ -371,8 +371,7 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   // chip: a persistent scan that took every CU would hold up the small kernels of the other batches until it drains, and
   // their scans behind them; with n_cus / share GUARANTEED workgroups each, the scans of `share` batches run side by side, the small
   // kernels fit in between, and a scan's workgroups pull more entries each (a shorter tail).
-  const int scan_cus = std::max(ix->n_cus / std::max(1, r.share), std::min(ix->n_cus, 32)) - ix->tune.reserve_cus;
-  const unsigned n_own = (unsigned)std::min<size_t>(wt.max_groups, (size_t)std::max(1, scan_cus));
+  const unsigned n_own = filter_scan_own(ix->n_cus, r.share, ix->tune.reserve_cus, wt.max_groups);   // (grid_plan.h)
   // K <= 256: one byte per code (packed8) unless option codes_u8 = 0 asks for the int16 layout
   const bool u8 = ix->packed8 && ix->tune.codes_u8 != 0 && ix->K <= 256;
   // ... and by default the kernel that keeps the WHOLE entry's slab in LDS (fused8.h; option codes_u8 = 2: fused5.h's one-byte instantiation)
@@ -386,8 +385,8 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
 #ifdef FREDDY_LAB
   if (ix->tune.scan_prof) elastic = false;   // (the profiling instantiations have no extras)
 #endif
-  const int cap = ix->n_cus - ix->tune.scan_elastic_reserve - ix->tune.reserve_cus * r.share;
-  const unsigned n_persist = elastic ? (unsigned)std::min<size_t>(wt.max_groups, (size_t)std::max((int)n_own, cap)) : n_own;
+  const int cap = filter_scan_cap(ix->n_cus, ix->tune.scan_elastic_reserve, ix->tune.reserve_cus, r.share);
+  const unsigned n_persist = filter_scan_persist(elastic, n_own, cap, wt.max_groups);
   if (!r.records_ready) {   // (a batch over the flat PQ table: pq_front_kernel has written them)
     if (ws->w_records.ensure(sizeof(int32_t) * REC_DW * wt.max_groups)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
     RecordArgs ra;
@@ -429,7 +428,7 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
     sp.item_dist = pa.item_dist; sp.sp_cell = wt.sp_cell; sp.sp_first = wt.sp_first; sp.sp_chunk = wt.sp_chunk;
     sp.n_units = wt.n_sparse; sp.work_counter = wt.sp_counter; sp.surv = fl.surv; sp.surv_count = fl.surv_count; sp.packed8 = fl.packed8;
     sp.cand_count = fl.cand_count; sp.K = K; sp.L = r.L; sp.Lt = r.Lt; sp.upi = r.upi; sp.sentinel = r.sentinel; sp.keep_all = fl.keep_all; sp.tau_run = fl.tau_run;
-    const unsigned sp_grid = (unsigned)std::min<size_t>(wt.sp_cap, (size_t)std::max(1, scan_cus) * (wt.sp_pairs ? 3 : 6));
+    const unsigned sp_grid = sparse_grid(ix->n_cus, r.share, ix->tune.reserve_cus, wt.sp_cap, wt.sp_pairs);
     const auto sparse = sparse_kernel(wt.sp_pairs, u8, fl.cand_count != nullptr);
     timed_launch(ix, s, "sparse_items", [&] { hipLaunchKernelGGL(sparse, dim3(sp_grid), dim3(256), 0, s, sp); });
     HIP_TRY(hipGetLastError());
@@ -511,7 +510,7 @@ static int ivf_scan_exact(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   const size_t desc_off = ((size_t)2 * SPEC2_G * K * sizeof(float) + 15) & ~(size_t)15;
   const size_t flds = desc_off + 4096 + 64 + 512 + (size_t)SPEC2_G * 12 * 28 * sizeof(float);
   fa.desc_offset = (uint32_t)desc_off;
-  const unsigned n_persist = (unsigned)std::min<size_t>(wt.max_groups, (size_t)ix->n_cus);
+  const unsigned n_persist = spec2_grid(ix->n_cus, wt.max_groups);
   timed_launch(ix, s, "ivf_exact_scan", [&] { hipLaunchKernelGGL(spec2_kernel(K == 1024), dim3(n_persist), dim3(SPEC2_T), flds, s, fa); });
   HIP_TRY(hipGetLastError());
 #ifdef FREDDY_LAB
@@ -537,8 +536,7 @@ static int ivf_scan_multi(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   memcpy(&ma.sentinel_bits, &r.sentinel, 4);
   const size_t lds = multi_lds_bytes(ix->m, ix->K);
   // persistent workgroups: as many as fit (LDS, 8 waves of ~100 registers), never more than there is work
-  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (size_t)(150 * 1024) / lds));
-  const unsigned grid = (unsigned)std::min<size_t>(wt.max_groups, (size_t)ix->n_cus * per_cu);
+  const unsigned grid = multi_grid(ix->n_cus, wt.max_groups, lds);
   timed_launch(ix, s, "ivf_multi_scan", [&] { hipLaunchKernelGGL(ivf_multi_kernel, dim3(grid), dim3(MULTI_T), lds, s, ma); });
   HIP_TRY(hipGetLastError());
   return launch_merge_surv(r, pa, ma.surv, ma.surv_count, ma.cand_count);
@@ -870,7 +868,7 @@ static int ivf_one(freddy_gpu_index* ix, const float* queries, int k, int W, flo
   Workspace* ws = workspace_for(ix, s);
   const int K = ix->K, C = ix->C, L = 2 * k;
   const size_t n_out = (size_t)k;
-  const int G = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)ix->n_cus, (int64_t)256, (int64_t)(56 * 1024) / (8 * L)}));
+  const int G = ivf_one_groups(ix->n_cus, L);
   if (G < W) return 0;   // (an item per workgroup at least)
   const size_t need_out = n_out * 8 + 16;
   if (ix->hio_out.ensure(need_out)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");

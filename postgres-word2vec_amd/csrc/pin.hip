@@ -366,7 +366,7 @@ int open_device(freddy_gpu_index* ix, int device) {
   if (int rc = raise_lds_limits(device)) return rc;
   HIP_TRY(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ix->n_cus = prop.multiProcessorCount;
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ix->n_cus = ix->device_cus = prop.multiProcessorCount;
   return 0;
 }
 

@@ -280,7 +280,7 @@ static int pq_one(freddy_gpu_index* ix, hipStream_t s, const float* h_q, int k, 
   Workspace* ws = workspace_for(ix, s);
   const int K = ix->K, L = 2 * k;
   // (one workgroup per CU at most: all co-resident; the last arriver stages every list in LDS: G * L keys within 56 KB)
-  const int G = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)ix->n_cus, (int64_t)256, (n_blocks + ONE_WAVES - 1) / ONE_WAVES, (int64_t)(56 * 1024) / (8 * L)}));
+  const int G = pq_one_groups(ix->n_cus, L, n_blocks, ONE_WAVES);
   const int chunk_blocks = (int)((n_blocks + G - 1) / G);
   const OneLayout lay{K, 0, 1, L, G};   // (the table | the workgroups' lists; the kernel's LDS: one_layout.h)
   uint32_t epoch = 0;
@@ -570,7 +570,7 @@ int pq_assign_pass(freddy_gpu_index* ix, hipStream_t s, float* d_lut, int Qc, in
   const size_t lut_bytes = (size_t)m * K * sizeof(float);
   const int LT = (int)std::min<size_t>(8, std::max<size_t>(1, ((size_t)64 << 10) / lut_bytes));   // LUTs staged in LDS at a time
   // four targets per thread once that still gives every CU two workgroups: a staged LUT then serves 1024 targets
-  const int RPT = (int64_t)n >= (int64_t)ix->n_cus * 2 * 4 * AS_PQ_WG ? 4 : 1;
+  const int RPT = assign_pq_rpt(ix->n_cus, n, AS_PQ_WG);
   const dim3 grid((unsigned)((n + RPT * AS_PQ_WG - 1) / (RPT * AS_PQ_WG)));
   for (int q0 = 0; q0 < Q; q0 += Qc) {
     const int nq = std::min(Qc, Q - q0);
