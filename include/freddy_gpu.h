@@ -394,6 +394,35 @@ int freddy_gpu_pq_search_pv_ids(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs
                                 int32_t id_rule, int32_t k, int32_t pvf, float sentinel, const int32_t* subset_ids,
                                 int64_t n_subset, int32_t* out_query_ids, int32_t* n_queries, int32_t* out_ids, float* out_sim);
 
+/* ---- exact kNN and the exact kNN-join by row id; id sets resolved on the device (resolve.h) --------------------------------
+ * The exact defaults of the SQL surface start from words, i.e. from row ids of the vector table: k_nearest_neighbour(token)
+ * (freddy--0.0.1.sql:426-454), knn_in_exact, knn_search_in_batch (:480-501) and grouping_func.  These two calls take the ids on
+ * both sides: the queries are rows of `vecs` (id_rule, out_query_ids, n_queries, the fillers (-1, -inf) and the compaction of
+ * slots without a row exactly as for the four calls above), and the id set -- subset_ids / target_ids -- is turned into ascending,
+ * distinct table rows by three kernels over a bitmap of the table's rows instead of one binary search per id, a sort and a copy on
+ * the host: N / 8 bytes cleared and read, 4 n bytes of ids read, 4 nT bytes of rows written, one synchronisation to learn nT.
+ * Contract: for every selected id with a row v, list j is bit for bit (ids, ranks, similarity bits) what freddy_gpu_exact_search /
+ * freddy_gpu_exact_join returns for the query v with the same k and the same set -- on every path: filter + refine, all-exact, the
+ * passes of k > 1024, the redo of overflowed queries, the fall-back for a non-finite query, more queries than one pass.
+ * subset_ids == NULL: the whole table (no bitmap); n_targets == 0: the empty set (every list is fillers).
+ * freddy_gpu_last_exact_join_stats reports for freddy_gpu_exact_join_ids as for freddy_gpu_exact_join.
+ * Errors, all before any device work and in this order: the front checks of the calls above (NULL handle, n_ids < 0, a bad id_rule,
+ * a NULL n_queries, a NULL buffer with n_ids > 0); what the entry point underneath refuses (FREDDY_E_ARG for k < 1, a negative set
+ * size or a NULL set of positive size; FREDDY_E_LIMIT for k > 4096); FREDDY_E_KIND; a poisoned handle.  Concurrency and mutations
+ * as above: a mutation before the call is seen, none may run beside it.
+ * Option "exact_resolve" = 1 makes freddy_gpu_exact_search (subset), freddy_gpu_exact_join and freddy_gpu_exact_analogy (subset)
+ * resolve their sets the same way (default 0: on the host, as before; no result changes); these two calls always do. */
+int freddy_gpu_exact_search_ids(freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k,
+                                const int32_t* subset_ids, int64_t n_subset, int32_t* out_query_ids /*[n_ids]*/,
+                                int32_t* n_queries, int32_t* out_ids /*[n_ids][k]*/, float* out_sim /*[n_ids][k]*/);
+int freddy_gpu_exact_join_ids(freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k,
+                              const int32_t* target_ids, int64_t n_targets, int32_t* out_query_ids /*[n_ids]*/,
+                              int32_t* n_queries, int32_t* out_ids /*[n_ids][k]*/, float* out_sim /*[n_ids][k]*/);
+/* Test hook: the device resolve alone.  out_rows[0..*n_rows) = the table rows of ids[0..n) that have one, ascending and distinct
+ * (unknown ids vanish, duplicates collapse); out_rows holds min(n, N) entries. */
+int freddy_gpu_debug_resolve_ids(freddy_gpu_index_t* vecs, const int32_t* ids, int64_t n, int32_t* out_rows /*[min(n, N)]*/,
+                                 int64_t* n_rows);
+
 /* ---- batched approximate analogies: 3CosAdd over the candidates of an approximate search (approx_analogy.h) ----------------
  * analogy_3cosadd_ivfadc (freddy--0.0.1.sql:1428-1460), analogy_3cosadd_pq (:1317-1346) and, with subset_ids, analogy_3cosadd_in_pq
  * (:1348-1384) for Q triples of row ids (w1, w2, w3) at once; the reference calls them with n_cand = get_pvf() + 3 and k = 1.
@@ -718,7 +747,10 @@ int freddy_gpu_abi_version(void);
  *                freddy_gpu_similarity_matrix / _join: 0 = 256 MiB, at most 4 GiB; always 16 rows of A at least), "cluster_pass" (targets
  *                per assignment pass of freddy_gpu_cluster: 0 = 2^22; 64 at least), "cluster_walk" (how freddy_gpu_cluster finds a
  *                cluster's sampled members: 1 = by walking all positions, as it does beyond 1024 clusters; 2 = from per-block counts;
- *                0 = auto: 2 from n > 32768 tokens on)
+ *                0 = auto: 2 from n > 32768 tokens on), "exact_resolve" (where freddy_gpu_exact_search / _exact_join /
+ *                _exact_analogy turn their id set into table rows: 0 = on the host, the default; 1 = on the device, as the
+ *                *_exact_*_ids calls always do), "resolve_block" (bitmap words per block of the device resolve: 0 = 256, at most
+ *                2^20; tests make a small table span many blocks)
  *   self-checks (tests):  "check_brackets" (bit 0: the scan keeps and the merge refines EVERY probed row, bit 1: the cell
  *                selection refines every cell, bit 2: exact kNN and the exact join refine every row -- each with its proven bracket compared with
  *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines

@@ -276,6 +276,8 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   else if (n == "lut_budget_mb") t.lut_budget_mb = std::max<int64_t>(1, value);
   else if (n == "exact_filter") t.exact_filter = (int)value;
   else if (n == "exact_join_tile") t.exact_join_tile = (int)value;
+  else if (n == "exact_resolve") t.exact_resolve = value != 0 ? 1 : 0;
+  else if (n == "resolve_block") t.resolve_block = (int)std::max<int64_t>(0, std::min<int64_t>(value, (int64_t)1 << 20));
   else if (n == "analogy_pass") t.analogy_pass = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
   else if (n == "cluster_pass") t.cluster_pass = value <= 0 ? 0 : (int)std::max<int64_t>(64, std::min<int64_t>(value, (int64_t)1 << 30));
   else if (n == "cluster_walk") t.cluster_walk = value == 1 || value == 2 ? (int)value : 0;

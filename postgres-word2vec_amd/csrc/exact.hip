@@ -1,6 +1,7 @@
 // exact.hip -- pin_vectors, exact brute-force kNN (core_functions.c:67-81, freddy--0.0.1.sql:426-454), the
 // exact analogies on the same handle (freddy--0.0.1.sql:1231-1315; analogy.h), the post verification of pq / ivf lists against it (pv.h)
 // the approximate analogies over such lists (approx_analogy.h) and the assignment step of cluster_exact (assign.h), the whole k-means of cluster_exact / cluster_pq (cluster.h); exact_host.h: what they share.
+// Exact kNN and the exact join by row id (freddy_gpu_exact_search_ids / _exact_join_ids): queries through a QuerySrc (query_ids.h), id sets resolved on the device (resolve.h).
 #include "internal.h"
 
 #include "kernels.h"
@@ -14,6 +15,7 @@
 #include "cluster.h"
 #include "similarity.h"
 #include "query_ids.h"
+#include "resolve.h"
 #include "exact_host.h"
 
 // ---- exact brute-force kNN as filter + refine (exact2.h) ----------------------------------------------------------------------
@@ -181,18 +183,92 @@ extern "C" int freddy_gpu_pin_vectors(const freddy_vec_desc* t, int device, fred
   return FREDDY_OK;
 }
 
-// "id = ANY(subset)" on a vector handle: the subset's rows (rows_of_ids) re-blocked into w_resid, their positions in w_sub_pos,
-// for the all-exact kernels.  An empty subset launches nothing (its buffers still exist).  Synchronises the stream.
-static int vec_subset(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const std::vector<int32_t>& rows, const float** xb,
+// ---- the rows of an id set (resolve.h) and the queries of a call, for either source ---------------------------------------------
+// Where the table rows of "id = ANY(set)" are: the host vector rows_of_ids made (every function then does exactly what it did
+// before), or already in ws->w_sub_rows, `resident` of them, put there by resolve_ids_device -- the copy to the device is skipped.
+// The buffer was sized for min(n_ids, N) >= resident rows before the resolve was launched, and DevBuf::ensure leaves a buffer
+// that is large enough where it is: the consumers' own ensure() calls for `resident` rows do not move it.
+struct RowSet {
+  const std::vector<int32_t>* host = nullptr;
+  int64_t resident = 0;
+  static RowSet of_host(const std::vector<int32_t>& rows) { RowSet r; r.host = &rows; return r; }
+  static RowSet on_device(int64_t n) { RowSet r; r.resident = n; return r; }
+  int64_t size() const { return host ? (int64_t)host->size() : resident; }
+};
+
+// ids[n] -> *n_rows ascending, distinct table rows in ws->w_sub_rows (resolve.h): a memset and four launches, recorded as
+// resolve_mark / resolve_scan / resolve_place, ONE synchronisation (the host reads the count from mapped memory behind it) and no
+// host work per id.  The other buffers (ids: w_item_cell, bitmap + chunk sums: w_used, counts: w_cnt, offsets: w_part) are free
+// again when this returns.  n == 0 or an empty table: no rows, nothing launched.
+static int resolve_ids_device(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const int32_t* ids, int64_t n, int64_t* n_rows) {
+  *n_rows = 0;
+  const int64_t N = ix->N;
+  if (n <= 0 || N <= 0) return 0;
+  const int B = ix->tune.resolve_block > 0 ? ix->tune.resolve_block : RESOLVE_BLOCK;
+  const int64_t n_words = (N + 31) / 32, n_blocks = (n_words + B - 1) / B, chunks = (n_blocks + SIM_CHUNK - 1) / SIM_CHUNK;
+  if (ws->w_sub_rows.ensure(sizeof(int32_t) * (size_t)std::min(n, N)) || ws->w_item_cell.ensure(sizeof(int32_t) * (size_t)n) ||
+      ws->w_used.ensure(sizeof(uint32_t) * (size_t)(n_words + chunks)) || ws->w_cnt.ensure(sizeof(int32_t) * (size_t)n_blocks) ||
+      ws->w_part.ensure(sizeof(int32_t) * (size_t)(n_blocks + 1)))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  if (ix->hio_in.ensure(sizeof(int32_t))) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+  volatile int32_t* const h_total = ix->hio_in.as<int32_t>();
+  *h_total = -1;
+  uint32_t* const bitmap = ws->w_used.as<uint32_t>();
+  int32_t* const part = reinterpret_cast<int32_t*>(bitmap + n_words);
+  HIP_TRY(hipMemcpyAsync(ws->w_item_cell.p, ids, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+  timed_launch(ix, s, "resolve_mark", [&] {
+    (void)hipMemsetAsync(bitmap, 0, sizeof(uint32_t) * (size_t)(n_words + chunks), s);
+    hipLaunchKernelGGL(resolve_mark_kernel, dim3(resolve_grid(ix->n_cus, (n + 255) / 256)), dim3(256), 0, s,
+                       ws->w_item_cell.as<const int32_t>(), n, (const int32_t*)ix->ids, N, bitmap);
+  });
+  HIP_TRY(hipGetLastError());
+  const dim3 bgrid(resolve_grid(ix->n_cus, (n_blocks + 3) / 4));   // (grid_plan.h: the kernels walk what a smaller grid leaves)
+  timed_launch(ix, s, "resolve_scan", [&] {
+    hipLaunchKernelGGL(resolve_count_kernel, bgrid, dim3(256), 0, s, (const uint32_t*)bitmap, n_words, B, n_blocks, ws->w_cnt.as<int32_t>(), part);
+    hipLaunchKernelGGL(sim_scan_kernel, dim3((unsigned)chunks), dim3(256), 0, s, ws->w_cnt.as<const int32_t>(), (const int32_t*)part, n_blocks,
+                       ws->w_part.as<int32_t>());
+  });
+  HIP_TRY(hipGetLastError());
+  timed_launch(ix, s, "resolve_place", [&] {
+    hipLaunchKernelGGL(resolve_place_kernel, bgrid, dim3(256), 0, s, (const uint32_t*)bitmap, n_words, B, n_blocks, ws->w_part.as<const int32_t>(),
+                       ws->w_sub_rows.as<int32_t>(), ix->hio_in.as<int32_t>());
+  });
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
+  const int64_t total = *h_total;
+  if (total < 0 || total > std::min(n, N)) return fail(FREDDY_E_HIP, "the device resolve reported %lld rows of %lld ids", (long long)total, (long long)n);
+  *n_rows = total;
+  return 0;
+}
+
+// The queries of a call where the kernels read them: the caller's floats copied into ws->w_q, or rows of the table (query_ids.h) --
+// one is read where it lies, more are gathered into ws->w_q by row numbers staged in the handle's pinned block (4 bytes per query).
+// Enqueued only; w_q holds Q d floats already.
+static int stage_queries(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const QuerySrc& qs, int Q, const float** d_q) {
+  const int d = ix->d;
+  *d_q = ws->w_q.as<float>();
+  if (qs.host) {
+    HIP_TRY(hipMemcpyAsync(ws->w_q.p, qs.host, sizeof(float) * (size_t)Q * d, hipMemcpyHostToDevice, s));
+    return 0;
+  }
+  if (Q == 1) { *d_q = qs.row_ptr(0, d); return 0; }
+  if (ix->hio_in.ensure(sizeof(int32_t) * (size_t)Q)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+  memcpy(ix->hio_in.p, qs.rows, sizeof(int32_t) * (size_t)Q);   // (every earlier reader of the block has been synchronised)
+  return launch_query_gather(ix, s, qs, ix->hio_in.as<const int32_t>(), ws->w_q.as<float>(), Q, d);
+}
+
+// "id = ANY(subset)" on a vector handle: the subset's rows (rows_of_ids, or the device resolve's) re-blocked into w_resid, their
+// positions in w_sub_pos, for the all-exact kernels.  An empty subset launches nothing (its buffers still exist).  Synchronises the stream.
+static int vec_subset(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const RowSet& rows, const float** xb,
                       const int32_t** pos, int64_t* n_rows, int64_t* n_blocks) {
-  *n_rows = (int64_t)rows.size();
+  *n_rows = rows.size();
   *n_blocks = (*n_rows + 63) / 64;
-  if (ws->w_sub_rows.ensure(sizeof(int32_t) * std::max<size_t>(rows.size(), 1)) ||
+  if (ws->w_sub_rows.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(rows.size(), 1)) ||
       ws->w_sub_pos.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(*n_blocks, 1) * 64) ||
       ws->w_resid.ensure(sizeof(float) * (size_t)std::max<int64_t>(*n_blocks, 1) * ix->d * 64))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   if (*n_rows) {
-    HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, s));
+    if (rows.host) HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, rows.host->data(), sizeof(int32_t) * rows.host->size(), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(block_rows_kernel, dim3((unsigned)*n_blocks), dim3(256), 0, s, ix->coarse, ws->w_sub_rows.as<int32_t>(), *n_rows,
                        ws->w_resid.as<float>(), ws->w_sub_pos.as<int32_t>(), ix->d);
     HIP_TRY(hipGetLastError());
@@ -205,7 +281,7 @@ static int vec_subset(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const 
 
 // Exact kNN of checked arguments (Q > 0) over all rows (sub_rows == NULL) or over the table rows *sub_rows (rows_of_ids' result;
 // the exact join hands over the rows it has resolved).
-static int exact_search_rows(freddy_gpu_index* ix, const float* queries, int32_t Q, int32_t k, const std::vector<int32_t>* sub_rows,
+static int exact_search_rows(freddy_gpu_index* ix, const QuerySrc& queries, int32_t Q, int32_t k, const RowSet* sub_rows,
                              int32_t* out_ids, float* out_sim) {
   HIP_TRY(hipSetDevice(ix->device));
   Workspace* ws = workspace_for(ix, ix->stream);
@@ -223,7 +299,7 @@ static int exact_search_rows(freddy_gpu_index* ix, const float* queries, int32_t
     // one block of mapped host memory: [lists][verdict words][the queries, when they are few]: the kernels read a handful of
     // queries where the host put them (1.2 KB each over PCIe) and write the lists where the host reads them
     const size_t n_out = (size_t)Q * k, q_bytes = sizeof(float) * (size_t)Q * d;
-    const bool q_pinned = q_bytes <= (256u << 10);
+    const bool q_pinned = queries.host && q_bytes <= (256u << 10);   // (queries that are rows of the table are on the device already)
     const size_t out_bytes = (n_out * 8 + 8 + 255) & ~(size_t)255, need = out_bytes + (q_pinned ? q_bytes : 0);
     if (ix->hio_out.ensure(need)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
     void* dp = nullptr;
@@ -232,12 +308,9 @@ static int exact_search_rows(freddy_gpu_index* ix, const float* queries, int32_t
     const float* d_q = nullptr;
     if (ws->w_q.ensure(q_bytes)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
     if (q_pinned) {
-      memcpy(ix->hio_out.as<char>() + out_bytes, queries, q_bytes);
+      memcpy(ix->hio_out.as<char>() + out_bytes, queries.host, q_bytes);
       d_q = reinterpret_cast<const float*>(static_cast<char*>(dp) + out_bytes);
-    } else {
-      HIP_TRY(hipMemcpyAsync(ws->w_q.p, queries, q_bytes, hipMemcpyHostToDevice, s));
-      d_q = ws->w_q.as<float>();
-    }
+    } else if (int rc = stage_queries(ix, ws, s, queries, Q, &d_q)) return rc;
     int fell_back = 0;
     if (int rc = exact_filter_search(ix, s, d_q, Q, k, &fell_back, h_out, static_cast<int32_t*>(dp), q_pinned ? ws->w_q.as<float>() : nullptr)) return rc;
     if (!fell_back) {
@@ -255,9 +328,10 @@ static int exact_search_rows(freddy_gpu_index* ix, const float* queries, int32_t
       ws->w_out_dist.ensure(sizeof(float) * (size_t)Q * k) ||
       ws->w_part.ensure(sizeof(u64) * (size_t)Q * nchunk * EX_WAVES * L))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  HIP_TRY(hipMemcpyAsync(ws->w_q.p, queries, sizeof(float) * (size_t)Q * d, hipMemcpyHostToDevice, s));
+  const float* d_q = nullptr;
+  if (int rc = stage_queries(ix, ws, s, queries, Q, &d_q)) return rc;
   ExactArgs ea;
-  ea.xb = xb; ea.pos = pos; ea.queries = ws->w_q.as<float>(); ea.part = ws->w_part.as<u64>();
+  ea.xb = xb; ea.pos = pos; ea.queries = d_q; ea.part = ws->w_part.as<u64>();
   ea.n_rows = n_rows; ea.n_blocks = (int)n_blocks; ea.chunk_blocks = chunk_blocks; ea.nchunk = nchunk; ea.Q = Q; ea.d = d; ea.L = L; ea.floor = nullptr;
   const size_t lds = exact_scan_lds(d, EX_QT);
   dim3 grid((unsigned)nchunk, (unsigned)qgroups);
@@ -305,6 +379,30 @@ static int exact_search_rows(freddy_gpu_index* ix, const float* queries, int32_t
   return FREDDY_OK;
 }
 
+// The id set of a call as a RowSet: on the device (resolve.h) into the workspace of the handle's stream, or on the host into *h_rows.
+static int resolve_row_set(freddy_gpu_index* ix, bool on_device, const int32_t* ids, int64_t n, std::vector<int32_t>* h_rows, RowSet* out) {
+  if (!on_device) {
+    *h_rows = rows_of_ids(ix->h_ids, ids, n);
+    *out = RowSet::of_host(*h_rows);
+    return 0;
+  }
+  HIP_TRY(hipSetDevice(ix->device));
+  int64_t n_rows = 0;
+  if (int rc = resolve_ids_device(ix, workspace_for(ix, ix->stream), ix->stream, ids, n, &n_rows)) return rc;
+  *out = RowSet::on_device(n_rows);
+  return 0;
+}
+
+// freddy_gpu_exact_search of checked arguments (Q > 0) for either source of the queries
+static int exact_search_src(freddy_gpu_index* ix, const QuerySrc& queries, int32_t Q, int32_t k, const int32_t* subset_ids, int64_t n_subset,
+                            bool resolve_on_device, int32_t* out_ids, float* out_sim) {
+  if (!subset_ids) return exact_search_rows(ix, queries, Q, k, nullptr, out_ids, out_sim);
+  std::vector<int32_t> h_rows;
+  RowSet rows;
+  if (int rc = resolve_row_set(ix, resolve_on_device, subset_ids, n_subset, &h_rows, &rows)) return rc;
+  return exact_search_rows(ix, queries, Q, k, &rows, out_ids, out_sim);
+}
+
 extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k,
                                        const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids, float* out_sim) {
   if (!ix) return fail(FREDDY_E_ARG, "NULL index");
@@ -314,9 +412,22 @@ extern "C" int freddy_gpu_exact_search(freddy_gpu_index_t* ix, const float* quer
   if (Q > 0 && (!queries || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
   if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
   if (Q == 0) return FREDDY_OK;
-  if (!subset_ids) return exact_search_rows(ix, queries, Q, k, nullptr, out_ids, out_sim);
-  const std::vector<int32_t> rows = rows_of_ids(ix->h_ids, subset_ids, n_subset);
-  return exact_search_rows(ix, queries, Q, k, &rows, out_ids, out_sim);
+  return exact_search_src(ix, QuerySrc::of_host(queries), Q, k, subset_ids, n_subset, ix->tune.exact_resolve != 0, out_ids, out_sim);
+}
+
+// Exact kNN of rows named by id (query_ids.h) over the whole table (subset_ids == NULL) or over an id set, which is resolved on the device.
+extern "C" int freddy_gpu_exact_search_ids(freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k,
+                                           const int32_t* subset_ids, int64_t n_subset, int32_t* out_query_ids, int32_t* n_queries,
+                                           int32_t* out_ids, float* out_sim) {
+  if (int rc = check_query_ids_front(vecs, vecs, query_ids, n_ids, id_rule, out_query_ids, n_queries, out_ids, out_sim)) return rc;
+  if (k <= 0 || n_subset < 0 || (n_subset > 0 && !subset_ids)) return fail(FREDDY_E_ARG, "bad sizes");
+  if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
+  if (vecs->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(vecs)) return rc;
+  return search_selected_ids(vecs, query_ids, n_ids, id_rule, k, -HUGE_VALF, out_query_ids, n_queries, out_ids, out_sim,
+                             [&](const QuerySrc& qs, int n, int32_t* oi, float* os) {
+    return exact_search_src(vecs, qs, n, k, subset_ids, n_subset, true, oi, os);
+  });
 }
 
 // ---- the exact kNN-join (exact_join.h) ---------------------------------------------------------------------------------
@@ -334,10 +445,10 @@ static constexpr size_t EXJ_PASS_BYTES = (size_t)2 << 30;
 // Filter + refine over the target rows `rows` (table order, distinct) for all Q queries: one gather, then five launches per pass
 // of queries.  cnt_out[q] = candidates the filter found for query q (> cap: its list is not valid, the caller redoes it);
 // *qbad_out: a query was not finite (no list is valid, the passes stop).
-static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const std::vector<int32_t>& rows, const float* queries, int Q, int k,
+static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const RowSet& rows, const QuerySrc& queries, int Q, int k,
                              int32_t* out_ids, float* out_sim, std::vector<int32_t>& cnt_out, int* cap_out, bool* qbad_out) {
   const int d = ix->d, T = (d + 15) / 16;
-  const int64_t nT = (int64_t)rows.size(), strips = (nT + 31) / 32;
+  const int64_t nT = rows.size(), strips = (nT + 31) / 32;
   const FilterPlan fp = filter_plan(nT, (ix->tune.check_brackets & 4) != 0);
   const int n_sample = fp.n_sample, cap = fp.cap;
   *cap_out = cap; *qbad_out = false;
@@ -362,8 +473,9 @@ static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s,
   p.copy_out = nullptr; p.k = k; p.out_ids = ws->w_out_ids.as<int32_t>(); p.out_sim = ws->w_out_dist.as<float>(); p.sample_when_empty = false;
   const int32_t* map = ws->w_sub_rows.as<int32_t>();
   h8v* xf = ws->w_resid.as<h8v>();
-  HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, rows.data(), sizeof(int32_t) * (size_t)nT, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(ws->w_q.p, queries, sizeof(float) * (size_t)Q * d, hipMemcpyHostToDevice, s));
+  if (rows.host) HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, rows.host->data(), sizeof(int32_t) * (size_t)nT, hipMemcpyHostToDevice, s));
+  const float* d_q = nullptr;
+  if (int rc = stage_queries(ix, ws, s, queries, Q, &d_q)) return rc;
   const int64_t gthreads = strips * T * 64;
   timed_launch(ix, s, "exact_join_gather", [&] {
     hipLaunchKernelGGL(exj_gather_kernel, dim3((unsigned)((gthreads + 255) / 256)), dim3(256), 0, s, ix->coarse, map, nT, d, T, ix->exf_ex, xf);
@@ -375,7 +487,7 @@ static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s,
   fa.cand = ix->exf_cand.as<uint2>(); fa.cap = cap;
   for (int q0 = 0; q0 < Q; q0 += Qc) {
     const int nq = std::min(Qc, Q - q0), qtiles = (nq + QT - 1) / QT;
-    p.nq = fa.nq = nq; p.grid_q = (unsigned)(qtiles * QT); p.total_wgs = nq; p.queries = ws->w_q.as<float>() + (size_t)q0 * d;
+    p.nq = fa.nq = nq; p.grid_q = (unsigned)(qtiles * QT); p.total_wgs = nq; p.queries = d_q + (size_t)q0 * d;
     HIP_TRY(hipMemsetAsync(p.flags, 0xFF, 8, s));   // (-1, -1: the pass's last refine workgroup overwrites both)
     // strip chunks: a workgroup's 8 waves take 8 strips per step; with many query tiles every workgroup stays long enough (>= 64
     // strips) to pay for its LDS image of the tile
@@ -404,21 +516,16 @@ static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s,
   return 0;
 }
 
-extern "C" int freddy_gpu_exact_join(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k, const int32_t* target_ids,
-                                     int64_t n_targets, int32_t* out_ids, float* out_sim) {
-  // (the scalar arguments first: they are checked before the handle is looked at, so no device is needed to see these errors)
-  if (Q < 0 || k <= 0 || n_targets < 0) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, k=%d, n_targets=%lld)", Q, k, (long long)n_targets);
-  if (n_targets > 0 && !target_ids) return fail(FREDDY_E_ARG, "NULL target_ids with n_targets=%lld", (long long)n_targets);
-  if (Q > 0 && (!queries || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
-  if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
-  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
-  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
-  if (int rc = refuse_poisoned(ix)) return rc;
-  ix->exj_stats[0] = ix->exj_stats[1] = ix->exj_stats[2] = 0;
-  if (Q == 0) return FREDDY_OK;
-  // the target ids resolved once: the filter and every all-exact answer (fall-back, redo) share the rows
-  const std::vector<int32_t> rows = rows_of_ids(ix->h_ids, target_ids, n_targets);
-  const int64_t nT = (int64_t)rows.size();
+// freddy_gpu_exact_join of checked arguments (Q > 0, the stats cleared) for either source of the queries and either place of the resolve
+static int exact_join_src(freddy_gpu_index* ix, const QuerySrc& queries, int32_t Q, int32_t k, const int32_t* target_ids, int64_t n_targets,
+                          bool resolve_on_device, int32_t* out_ids, float* out_sim) {
+  // the target ids resolved once: the filter and every all-exact answer (fall-back, redo) share the rows -- a resident set stays in
+  // w_sub_rows through all of them (nothing below writes that buffer but the copy of a host set), while w_q is written again by
+  // every stage: the redo and the fall-back take their queries from the source again, never from the filter's copy
+  std::vector<int32_t> h_rows;
+  RowSet rows;
+  if (int rc = resolve_row_set(ix, resolve_on_device, target_ids, n_targets, &h_rows, &rows)) return rc;
+  const int64_t nT = rows.size();
   const bool want_filter = ix->exf_ok && k <= 32 && ix->tune.exact_filter != 0 && (ix->tune.exact_filter == 1 || nT >= EXJ_MIN_TARGETS) && nT >= 1;
   if (!want_filter) return exact_search_rows(ix, queries, Q, k, &rows, out_ids, out_sim);
   HIP_TRY(hipSetDevice(ix->device));
@@ -440,15 +547,76 @@ extern "C" int freddy_gpu_exact_join(freddy_gpu_index_t* ix, const float* querie
   ix->exj_stats[0] = Q; ix->exj_stats[1] = cands; ix->exj_stats[2] = (int64_t)redo.size();
   if (!redo.empty()) {
     const int d = ix->d, nr = (int)redo.size();
-    std::vector<float> rq((size_t)nr * d), rs((size_t)nr * k);
-    std::vector<int32_t> ri((size_t)nr * k);
-    for (int i = 0; i < nr; ++i) memcpy(&rq[(size_t)i * d], queries + (size_t)redo[(size_t)i] * d, sizeof(float) * d);
-    if (int rc = exact_search_rows(ix, rq.data(), nr, k, &rows, ri.data(), rs.data())) return rc;
+    std::vector<float> rq, rs((size_t)nr * k);
+    std::vector<int32_t> ri((size_t)nr * k), rrows;
+    QuerySrc rsrc = queries;
+    if (queries.host) {
+      rq.resize((size_t)nr * d);
+      for (int i = 0; i < nr; ++i) memcpy(&rq[(size_t)i * d], queries.host + (size_t)redo[(size_t)i] * d, sizeof(float) * d);
+      rsrc.host = rq.data();
+    } else {   // (their row numbers: the rows are gathered again from the table)
+      rrows.resize((size_t)nr);
+      for (int i = 0; i < nr; ++i) rrows[(size_t)i] = queries.rows[redo[(size_t)i]];
+      rsrc.rows = rrows.data();
+    }
+    if (int rc = exact_search_rows(ix, rsrc, nr, k, &rows, ri.data(), rs.data())) return rc;
     for (int i = 0; i < nr; ++i) {
       memcpy(out_ids + (size_t)redo[(size_t)i] * k, &ri[(size_t)i * k], sizeof(int32_t) * k);
       memcpy(out_sim + (size_t)redo[(size_t)i] * k, &rs[(size_t)i * k], sizeof(float) * k);
     }
   }
+  return FREDDY_OK;
+}
+
+extern "C" int freddy_gpu_exact_join(freddy_gpu_index_t* ix, const float* queries, int32_t Q, int32_t k, const int32_t* target_ids,
+                                     int64_t n_targets, int32_t* out_ids, float* out_sim) {
+  // (the scalar arguments first: they are checked before the handle is looked at, so no device is needed to see these errors)
+  if (Q < 0 || k <= 0 || n_targets < 0) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, k=%d, n_targets=%lld)", Q, k, (long long)n_targets);
+  if (n_targets > 0 && !target_ids) return fail(FREDDY_E_ARG, "NULL target_ids with n_targets=%lld", (long long)n_targets);
+  if (Q > 0 && (!queries || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
+  if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(ix)) return rc;
+  ix->exj_stats[0] = ix->exj_stats[1] = ix->exj_stats[2] = 0;
+  if (Q == 0) return FREDDY_OK;
+  return exact_join_src(ix, QuerySrc::of_host(queries), Q, k, target_ids, n_targets, ix->tune.exact_resolve != 0, out_ids, out_sim);
+}
+
+// The exact kNN-join of rows named by id (query_ids.h): the queries are gathered from the table, the target set is resolved on the
+// device (resolve.h); no vector and no row number of the set crosses PCIe.
+extern "C" int freddy_gpu_exact_join_ids(freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k,
+                                         const int32_t* target_ids, int64_t n_targets, int32_t* out_query_ids, int32_t* n_queries,
+                                         int32_t* out_ids, float* out_sim) {
+  if (int rc = check_query_ids_front(vecs, vecs, query_ids, n_ids, id_rule, out_query_ids, n_queries, out_ids, out_sim)) return rc;
+  if (k <= 0 || n_targets < 0) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, k=%d, n_targets=%lld)", n_ids, k, (long long)n_targets);
+  if (n_targets > 0 && !target_ids) return fail(FREDDY_E_ARG, "NULL target_ids with n_targets=%lld", (long long)n_targets);
+  if (k > 4096) return fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k);
+  if (vecs->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(vecs)) return rc;
+  vecs->exj_stats[0] = vecs->exj_stats[1] = vecs->exj_stats[2] = 0;
+  return search_selected_ids(vecs, query_ids, n_ids, id_rule, k, -HUGE_VALF, out_query_ids, n_queries, out_ids, out_sim,
+                             [&](const QuerySrc& qs, int n, int32_t* oi, float* os) {
+    return exact_join_src(vecs, qs, n, k, target_ids, n_targets, true, oi, os);
+  });
+}
+
+// Test hook: the device resolve alone -- the rows of ids[n] in table order, distinct (what rows_of_ids gives), copied back.
+extern "C" int freddy_gpu_debug_resolve_ids(freddy_gpu_index_t* vecs, const int32_t* ids, int64_t n, int32_t* out_rows, int64_t* n_rows) {
+  if (!vecs) return fail(FREDDY_E_ARG, "NULL index");
+  if (n < 0 || !n_rows || (n > 0 && (!ids || !out_rows))) return fail(FREDDY_E_ARG, "bad argument (n=%lld)", (long long)n);
+  if (vecs->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (int rc = refuse_poisoned(vecs)) return rc;
+  *n_rows = 0;
+  HIP_TRY(hipSetDevice(vecs->device));
+  Workspace* ws = workspace_for(vecs, vecs->stream);
+  int64_t nT = 0;
+  if (int rc = resolve_ids_device(vecs, ws, vecs->stream, ids, n, &nT)) return rc;
+  if (nT) {
+    HIP_TRY(hipMemcpyAsync(out_rows, ws->w_sub_rows.p, sizeof(int32_t) * (size_t)nT, hipMemcpyDeviceToHost, vecs->stream));
+    HIP_TRY(hipStreamSynchronize(vecs->stream));
+  }
+  *n_rows = nT;
   return FREDDY_OK;
 }
 
@@ -603,8 +771,10 @@ extern "C" int freddy_gpu_exact_analogy(freddy_gpu_index_t* ix, int32_t method, 
   const int32_t* pos = nullptr;
   int64_t n_rows = ix->N, n_blocks = ix->n_blocks;
   if (subset_ids) {
-    const std::vector<int32_t> rows = rows_of_ids(ix->h_ids, subset_ids, n_subset);
-    if (rows.empty()) return FREDDY_OK;   // (before any launch: the lists stay empty)
+    std::vector<int32_t> h_rows;
+    RowSet rows;
+    if (int rc = resolve_row_set(ix, ix->tune.exact_resolve != 0, subset_ids, n_subset, &h_rows, &rows)) return rc;
+    if (rows.size() == 0) return FREDDY_OK;   // (a host set: before any launch; the lists stay empty)
     if (int rc = vec_subset(ix, ws, s, rows, &xb, &pos, &n_rows, &n_blocks)) return rc;
   }
   const int passes = (na + AN_PASS - 1) / AN_PASS;

@@ -71,4 +71,8 @@ inline int sim_split(int n_cus, int n_tiles, int nblk) { return std::min(n_tiles
 inline int sim_tiles_per_wg(int n_cus, int n_tiles, int nblk) { const int split = sim_split(n_cus, n_tiles, nblk); return (n_tiles + split - 1) / split; }
 inline unsigned sim_grid_y(int n_cus, int n_tiles, int nblk) { const int t = sim_tiles_per_wg(n_cus, n_tiles, nblk); return (unsigned)((n_tiles + t - 1) / t); }
 
+// ---- the device resolve of an id set (resolve.h): eight workgroups per CU at most; `wgs` = workgroups that would take the work in
+// one go (256 ids each in the mark kernel, four blocks -- one per wave -- in the count and place kernels) ----
+inline unsigned resolve_grid(int n_cus, int64_t wgs) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(wgs, (int64_t)n_cus * 8)); }
+
 }  // namespace freddy

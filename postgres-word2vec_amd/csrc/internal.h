@@ -90,6 +90,8 @@ struct Tuning {
   int analogy_pass = 0;        // option analogy_pass: triples per pass of the approximate analogies (approx_analogy.h): 0 = pv_search's bound (lists of at most 8 M entries)
   int cluster_pass = 0;        // option cluster_pass: targets per assignment pass of freddy_gpu_cluster (cluster.h): 0 = 2^22; 64 at least
   int cluster_walk = 0;        // option cluster_walk: how cluster_sample_kernel finds a cluster's ranked members: 1 = it walks them from position 0 (what it does for kc > 1024), 2 = over the apply kernel's per-block counts (kc <= 1024), 0 = auto: 2 from n > 32768 on
+  int exact_resolve = 0;       // option exact_resolve: how freddy_gpu_exact_search / _exact_join / _exact_analogy turn their id set into table rows: 0 = on the host (rows_of_ids), 1 = on the device (resolve.h); the *_ids forms always take the device
+  int resolve_block = 0;       // option resolve_block: bitmap words per block of the device resolve (resolve.h): 0 = 256; tests make small tables span many blocks
   int64_t similarity_pass_bytes = 0;   // option similarity_pass_bytes: the device result block of one pass of freddy_gpu_similarity_matrix / _join (similarity.h): 0 = 256 MiB, at most 4 GiB; 16 rows of A at least
   // -- self-checks (tests): bit 0 = the scan keeps every row and the merge refines every row (every probed row's bracket is checked),
   //    bit 1 = the cell selection refines every cell, bit 2 = exact kNN refines every row

@@ -40,6 +40,7 @@ EXPORTS = [
     "freddy_gpu_ivfadc_search_ids", "freddy_gpu_pq_search_ids", "freddy_gpu_ivfadc_search_pv_ids", "freddy_gpu_pq_search_pv_ids",
     "freddy_gpu_similarity_pairs", "freddy_gpu_similarity_matrix", "freddy_gpu_similarity_join",
     "freddy_gpu_cluster",
+    "freddy_gpu_exact_search_ids", "freddy_gpu_exact_join_ids", "freddy_gpu_debug_resolve_ids",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together): ids per pass of freddy_gpu_create_statistics
@@ -163,7 +164,13 @@ def load(path=None, optional=()):
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
                         # the whole k-means of cluster_exact / cluster_pq (the same again)
                         ("freddy_gpu_cluster", [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                                C.c_void_p, C.c_void_p, C.c_void_p])):
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+                        # exact kNN / the exact join by row id, and the device resolve's test hook (the same again)
+                        ("freddy_gpu_exact_search_ids", [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_exact_join_ids", [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_debug_resolve_ids", [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = types
     lib.freddy_gpu_pq_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
@@ -544,6 +551,28 @@ class VectorIndex(_Index):
         t = _i32(target_ids).reshape(-1)
         _check(self.lib.freddy_gpu_exact_join(self.h, _p(qs), Q, k, _p(t) if t.size else None, t.size, _p(out_i), _p(out_s)))
         return out_i, out_s
+
+    def exact_search_ids(self, ids, k, subset_ids=None, rule=QIDS_TABLE_ORDER):
+        """search() for the rows of this table with these ids (freddy_gpu_exact_search_ids): (query_ids[Q], ids[Q,k], similarity[Q,k])
+        with Q = the queries `rule` selects; per query bit for bit search(<its row>, k, subset_ids).  The subset is resolved on the device."""
+        sub = None if subset_ids is None else _i32(subset_ids).reshape(-1)
+        return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_exact_search_ids(
+            self.h, _p(q), n, rule, k, _p(sub), 0 if sub is None else sub.size, _p(oq), C.byref(nq), _p(oi), _p(od)))
+
+    def exact_join_ids(self, ids, k, target_ids, rule=QIDS_TABLE_ORDER):
+        """join() for the rows of this table with these ids (freddy_gpu_exact_join_ids): (query_ids[Q], ids[Q,k], similarity[Q,k]); per
+        query bit for bit join(<its row>, k, target_ids).  The target set is resolved on the device; an empty one is the empty set."""
+        t = _i32(target_ids).reshape(-1)
+        return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_exact_join_ids(
+            self.h, _p(q), n, rule, k, _p(t) if t.size else None, t.size, _p(oq), C.byref(nq), _p(oi), _p(od)))
+
+    def debug_resolve_ids(self, ids):
+        """The device resolve alone (freddy_gpu_debug_resolve_ids): the table rows of `ids`, ascending and distinct."""
+        t = _i32(ids).reshape(-1)
+        out = np.empty(max(t.size, 1), np.int32)   # (min(n, N) entries are written at most)
+        n = C.c_int64(-1)
+        _check(self.lib.freddy_gpu_debug_resolve_ids(self.h, _p(t) if t.size else None, t.size, _p(out), C.byref(n)))
+        return out[:n.value].copy()
 
     def assign(self, queries, target_ids):
         """The assignment step of cluster_exact (freddy_gpu_exact_assign): (query index[n], similarity[n]), slot i for
