@@ -441,16 +441,53 @@ int freddy_gpu_debug_resolve_ids(freddy_gpu_index_t* vecs, const int32_t* ids, i
  * buffers with Q > 0; FREDDY_E_LIMIT for n_cand > 4096 (the message names the value); FREDDY_E_KIND for handles of the wrong kinds;
  * FREDDY_E_ARG for vecs on another device or of another d, and for an ivf handle with replicas.  Q == 0 succeeds and does nothing.
  * Any Q (passes of triples whose lists hold at most 8 M entries; option "analogy_pass" sets the triples per pass).
- * analogy_3cosadd_in_ivpq goes through the kNN-join (freddy_gpu_knn_join with the literal k = 4) and has no entry point here. */
+ * analogy_3cosadd_in_ivpq goes through the kNN-join (the literal k = 4): freddy_gpu_ivpq_analogy below. */
 int freddy_gpu_ivfadc_analogy(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const int32_t* triples /*[Q][3] ids w1,w2,w3*/,
                               int32_t Q, int32_t k, int32_t n_cand, int32_t W, float sentinel, int32_t found_rule,
                               int32_t* out_ids /*[Q][k]*/, float* out_sim /*[Q][k]*/);
 int freddy_gpu_pq_analogy(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const int32_t* triples, int32_t Q, int32_t k,
                           int32_t n_cand, float sentinel, const int32_t* subset_ids, int64_t n_subset,
                           int32_t* out_ids, float* out_sim);
-/* The last approximate-analogy call on this pq / ivf handle: triples that reached stage one, their list entries with id >= 0, and
- * how many of those had a vector row and were not an input of their triple (were scored).  NULL pointers are skipped. */
+/* analogy_3cosadd_in_ivpq (freddy--0.0.1.sql:1383-1425) for Q triples at once: the contract above word for word, with another
+ * stage one.  Per pass of triples (the same pass rule and option "analogy_pass", set on the ivpq handle) the lists L are the list
+ * block of ONE freddy_gpu_knn_join(ivpq, <the unit rows of the pass's live triples>, nq, n_cand, target_ids, n_targets, alpha, pvf,
+ * method, use_target_lists, confidence, double_threshold, ...); the reference passes the literal n_cand = 4.  The join's fillers
+ * (-1, 1000.0) are no candidates.  `vecs` is required: it supplies v1 .. v3 and the candidates' rows, as google_vecs_norm does in the
+ * SQL.  The unit rows are written by aa_query straight into the join's query block and the join starts behind it on the same stream
+ * with no host synchronisation in between: they never reach the host.  "aa_query" and "aa_rerank" are recorded in the ivpq handle's
+ * profile, once per pass; freddy_gpu_last_approx_analogy_stats reports for this call on the ivpq handle.
+ * Errors, all before any device work: the scalars above (Q, k, n_cand, NULL buffers, FREDDY_E_LIMIT for n_cand > 4096), then what
+ * freddy_gpu_knn_join refuses at k = n_cand (with its messages), then the handles as above. */
+int freddy_gpu_ivpq_analogy(freddy_gpu_index_t* ivpq, freddy_gpu_index_t* vecs, const int32_t* triples /*[Q][3]*/, int32_t Q,
+                            int32_t k, int32_t n_cand, const int32_t* target_ids, int64_t n_targets, int32_t alpha, int32_t pvf,
+                            int32_t method, int32_t use_target_lists, float confidence, int32_t double_threshold,
+                            int32_t* out_ids /*[Q][k]*/, float* out_sim /*[Q][k]*/);
+/* The last approximate-analogy call on this pq / ivf / ivpq handle: triples that reached stage one, their list entries with id >= 0,
+ * and how many of those had a vector row and were not an input of their triple (were scored).  NULL pointers are skipped. */
 int freddy_gpu_last_approx_analogy_stats(const freddy_gpu_index_t* ann, int64_t* searched, int64_t* candidates, int64_t* scored);
+
+/* ---- the kNN-join by row id (join_run.h JoinQueries, join_kernels.h sub_dist_rows_kernel) -----------------------------------
+ * The kNN-join's SQL callers start from ids: knn_in_ivpq_batch(query_set varchar[], ...) selects "word, vector, id FROM
+ * google_vecs_norm WHERE word = ANY(...)" and hands the vectors over (freddy--0.0.1.sql:720-761, 797-814).  This call takes the ids:
+ * the queries are the rows of `vecs` -- or, with vecs == NULL, of the ivpq handle's own pinned vectors -- with these ids.  id_rule,
+ * out_query_ids and n_queries exactly as for the calls above; the ids are looked up in the id column of the table the rows come from.
+ * Contract: let R be the selected ids that have a row, in order, and V their rows.  The lists of R and *iterations_out are bit for
+ * bit (ids, ranks, distance bits) what ONE call freddy_gpu_knn_join(ivpq, V, |R|, k, <the same remaining arguments>) returns.  A
+ * positional slot whose id has no row holds k fillers (-1, 1000.0f) and is compacted away before anything is launched; |R| == 0
+ * launches nothing and gives *iterations_out = 0; TABLE_ORDER leaves the slots >= Q unwritten.  freddy_gpu_last_track reports as
+ * for freddy_gpu_knn_join, and the cache of the previous call's target array is shared with it.
+ * 4 bytes per query go up; ONE kernel ("join_front_rows" in the ivpq handle's profile) gathers the rows into the join's query block
+ * and computes their sub-distances, where freddy_gpu_knn_join's front pulls the caller's floats over PCIe.  Option
+ * "join_front_gather" = 0 (default 1), and d / 2 > 512, take two launches instead: "query_gather", then the sub-distance kernel.
+ * Errors, all before any device work and in this order: the front checks of the calls above; what freddy_gpu_knn_join refuses
+ * (k <= 0, n_targets < 0, NULL target ids, the method, the limits of k and k * pvf, pair codes), with its messages; FREDDY_E_KIND
+ * and a poisoned handle; vecs on another device or of another d; vecs == NULL on a handle pinned without vectors (FREDDY_E_ARG, the
+ * message says so).  A mutation of either handle BEFORE the call is seen; none may run beside it. */
+int freddy_gpu_knn_join_ids(freddy_gpu_index_t* ivpq, freddy_gpu_index_t* vecs /* NULL: the ivpq handle's own vectors */,
+                            const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k, const int32_t* target_ids,
+                            int64_t n_targets, int32_t alpha, int32_t pvf, int32_t method, int32_t use_target_lists,
+                            float confidence, int32_t double_threshold, int32_t* out_query_ids /*[n_ids]*/, int32_t* n_queries,
+                            int32_t* out_ids /*[n_ids][k]*/, float* out_dist /*[n_ids][k]*/, int32_t* iterations_out);
 
 /* ---- next row: grouping_pq ---------------------------------------------------------
  * Body of grouping_pq (freddy.c:1176-1401): for every row of the PQ table (subset_ids == NULL) or of
@@ -754,7 +791,9 @@ int freddy_gpu_abi_version(void);
  *   self-checks (tests):  "check_brackets" (bit 0: the scan keeps and the merge refines EVERY probed row, bit 1: the cell
  *                selection refines every cell, bit 2: exact kNN and the exact join refine every row -- each with its proven bracket compared with
  *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines
- *                every row for every analogy, counted the same way), "join_host_traversal",
+ *                every row for every analogy, counted the same way), "join_host_traversal", "join_front_gather" (1, the
+ *                default: freddy_gpu_knn_join_ids gathers its queries in the sub-distance launch; 0: a gather launch, then the
+ *                sub-distance kernel -- the same lists either way),
  *                "join_libm_margin_ppm", "grid_cus" (the CU count that every grid sized from the chip is planned with, and every
  *                choice of a kernel made from it -- csrc/grid_plan.h: v <= 0 = the device's count, the default; otherwise
  *                min(v, the device's count).  It can only shrink grids, never grow them: the workgroups of the one-launch kernels

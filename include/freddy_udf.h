@@ -120,6 +120,7 @@ int ivpq_search_in(freddy_session_t* s, const float* queries, int32_t n_queries,
  * alpha/pvf/method/use_targetlist/confidence/long_codes_threshold taken from the getters. */
 int knn_join(freddy_session_t* s, const float* queries, int32_t n_queries, int32_t dim, const int32_t* query_ids,
              int32_t k, const int32_t* input_ids, int32_t n_ids, freddy_row3* out, int32_t* n_rows);
+/* (the same by query id, and analogy_3cosadd_in_ivpq for a batch of triples: include/freddy_udf_ivpq.h) */
 
 /* Next row: the exact brute-force functions, by row id instead of word.
  * k_nearest_neighbour(bytea, int)             freddy--0.0.1.sql:426-439
@@ -201,7 +202,8 @@ int analogy_3cosadd_in_pq(freddy_session_t* s, int32_t id1, int32_t id2, int32_t
 /* The batch forms of the approximate analogies: results[i] = what the single-triple function returns for triples[i] (-1 where the SQL
  * returns NULL), all n triples in ONE device call (freddy_gpu_ivfadc_analogy / freddy_gpu_pq_analogy, approx_analogy.h) with
  * n_cand = get_pvf() + 3, k = 1 and the sentinels and W of the single-triple functions -- instead of a search and a host loop over
- * the candidates per triple.  analogy_3cosadd_in_ivpq goes through the kNN-join with the literal k = 4 and has no batch form. */
+ * the candidates per triple.  analogy_3cosadd_in_ivpq goes through the kNN-join with the literal k = 4; its batch form is declared in
+ * include/freddy_udf_ivpq.h. */
 int analogy_3cosadd_pq_batch(freddy_session_t* s, const int32_t* triples /*[n][3]*/, int32_t n, int32_t* results /*[n]*/);
 int analogy_3cosadd_ivfadc_batch(freddy_session_t* s, const int32_t* triples /*[n][3]*/, int32_t n, int32_t* results /*[n]*/);
 int analogy_3cosadd_in_pq_batch(freddy_session_t* s, const int32_t* triples /*[n][3]*/, int32_t n, const int32_t* input_ids, int32_t n_ids,

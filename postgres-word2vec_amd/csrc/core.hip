@@ -260,6 +260,7 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
     }
   }
   else if (n == "join_host_traversal") ix->join.host_traversal = value != 0;
+  else if (n == "join_front_gather") ix->join.front_gather = value != 0;
   else if (n == "join_libm_margin_ppm") ix->join.libm_margin = (float)value * 1e-6f;
   else if (n == "sparse_items") t.sparse_items = std::max(-16, std::min(16, (int)value));
   else if (n == "pipeline_batch") t.pipeline_batch = (int)std::max<int64_t>(16, value);

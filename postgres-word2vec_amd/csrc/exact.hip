@@ -964,11 +964,15 @@ extern "C" int freddy_gpu_last_pv_stats(const freddy_gpu_index_t* ann, int64_t* 
 
 // ---- approximate analogies: 3CosAdd over the candidates of pq / ivf lists (approx_analogy.h) ---------------------------------------
 // Everything both entry points refuse, scalars before handles; nothing here touches a device.
-static int aa_check(const freddy_gpu_index* ann, int kind, const freddy_gpu_index* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand,
-                    const int32_t* out_ids, const float* out_sim) {
+static int aa_check_scalars(const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand, const int32_t* out_ids, const float* out_sim) {
   if (Q < 0 || k < 1 || n_cand < k) return fail(FREDDY_E_ARG, "bad sizes (Q=%d, k=%d, n_cand=%d)", Q, k, n_cand);
   if (Q > 0 && (!triples || !out_ids || !out_sim)) return fail(FREDDY_E_ARG, "NULL buffer");
   if (n_cand > PV_MAX_CAND) return fail(FREDDY_E_LIMIT, "n_cand = %d exceeds this build's limit of %d candidates", n_cand, PV_MAX_CAND);
+  return 0;
+}
+static int aa_check(const freddy_gpu_index* ann, int kind, const freddy_gpu_index* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand,
+                    const int32_t* out_ids, const float* out_sim) {
+  if (int rc = aa_check_scalars(triples, Q, k, n_cand, out_ids, out_sim)) return rc;
   return pv_check_handles(ann, kind, vecs, "the approximate analogy");
 }
 
@@ -976,9 +980,12 @@ static int aa_check(const freddy_gpu_index* ann, int kind, const freddy_gpu_inde
 // pass's raw rows to device memory and its unit rows into the pinned block, stage one (`search`: the public entry point at n_cand,
 // reading its queries from that block and writing its lists into it) runs once the kernel has finished, and the re-rank scores the
 // lists against the raw rows without the inputs; the result rows are scattered back to their triples.
-template <class F>
+// unit_block (the ivpq form): `block(Qc, &p)` names device memory for a pass's unit rows instead of the pinned block -- the kNN-join's
+// query block, which stage one reads in stream order: aa_query is not waited for, and the unit rows never reach the host.
+static int aa_pinned_units(int, float** block) { *block = nullptr; return 0; }   // (the pq / ivf forms: the pinned block's unit rows)
+template <class F, class B>
 static int aa_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand, int32_t* out_ids,
-                     float* out_sim, F&& search) {
+                     float* out_sim, F&& search, B&& unit_block) {
   ann->aa_stats[0] = ann->aa_stats[1] = ann->aa_stats[2] = 0;
   for (size_t i = 0; i < (size_t)Q * k; ++i) { out_ids[i] = -1; out_sim[i] = -HUGE_VALF; }
   std::vector<int32_t> live, rows3, ids3;
@@ -991,17 +998,19 @@ static int aa_search(freddy_gpu_index* ann, freddy_gpu_index* vecs, const int32_
   HIP_TRY(hipSetDevice(ann->device));
   RerankBlock b;
   if (int rc = rerank_block(ann, Qc, n_cand, k, true, "approximate analogy", &b)) return rc;
+  float* d_unit = nullptr;
+  if (int rc = unit_block(Qc, &d_unit)) return rc;
   hipStream_t s = ann->stream;
   for (int q0 = 0; q0 < na; q0 += Qc) {
     const int nq = std::min(Qc, na - q0);
     memcpy(b.p_rows, rows3.data() + (size_t)q0 * 3, sizeof(int32_t) * 3 * (size_t)nq);
     memcpy(b.p_excl, ids3.data() + (size_t)q0 * 3, sizeof(int32_t) * 3 * (size_t)nq);
     AaQueryArgs qa;
-    qa.rows = vecs->coarse; qa.in_rows = b.p_rows; qa.raw = ann->pv_q.as<float>(); qa.unit = b.unit; qa.d = d;
+    qa.rows = vecs->coarse; qa.in_rows = b.p_rows; qa.raw = ann->pv_q.as<float>(); qa.unit = d_unit ? d_unit : b.unit; qa.d = d;
     timed_launch(ann, s, "aa_query", [&] { hipLaunchKernelGGL(aa_query_kernel, dim3((unsigned)nq), dim3(64), aa_query_lds(d), s, qa); });
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));   // (stage one reads the unit rows on streams of its own)
-    if (int rc = search(b.unit, nq, b.l_ids, b.l_dist)) return rc;
+    if (!d_unit) HIP_TRY(hipStreamSynchronize(s));   // (stage one reads the unit rows on streams of its own)
+    if (int rc = search(qa.unit, nq, b.l_ids, b.l_dist)) return rc;
     HIP_TRY(hipSetDevice(ann->device));
     if (int rc = launch_rerank(ann, vecs, s, "aa_rerank", aa_rerank_kernel<1>, aa_rerank_kernel<4>, b, b.p_excl, nq, n_cand, k)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
@@ -1021,7 +1030,7 @@ extern "C" int freddy_gpu_ivfadc_analogy(freddy_gpu_index_t* ivf, freddy_gpu_ind
   if (int rc = aa_check(ivf, KIND_IVF, vecs, triples, Q, k, n_cand, out_ids, out_sim)) return rc;
   return aa_search(ivf, vecs, triples, Q, k, n_cand, out_ids, out_sim, [&](const float* qp, int nq, int32_t* l_ids, float* l_dist) {
     return freddy_gpu_ivfadc_search(ivf, qp, nq, n_cand, W, sentinel, found_rule, l_ids, l_dist);
-  });
+  }, aa_pinned_units);
 }
 
 extern "C" int freddy_gpu_pq_analogy(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand,
@@ -1030,12 +1039,27 @@ extern "C" int freddy_gpu_pq_analogy(freddy_gpu_index_t* pq, freddy_gpu_index_t*
   if (int rc = aa_check(pq, KIND_PQ, vecs, triples, Q, k, n_cand, out_ids, out_sim)) return rc;
   return aa_search(pq, vecs, triples, Q, k, n_cand, out_ids, out_sim, [&](const float* qp, int nq, int32_t* l_ids, float* l_dist) {
     return freddy_gpu_pq_search(pq, qp, nq, n_cand, sentinel, subset_ids, n_subset, l_ids, l_dist);
-  });
+  }, aa_pinned_units);
+}
+
+// analogy_3cosadd_in_ivpq (freddy--0.0.1.sql:1383-1425) for a batch of triples: stage one is ONE kNN-join per pass at k = n_cand (the
+// reference's literal 4) over the unit rows of the pass's live triples, which aa_query writes straight into the join's query block; the
+// join's fillers (-1, 1000.0) are no candidates.
+extern "C" int freddy_gpu_ivpq_analogy(freddy_gpu_index_t* ivpq, freddy_gpu_index_t* vecs, const int32_t* triples, int32_t Q, int32_t k, int32_t n_cand,
+                                       const int32_t* target_ids, int64_t n_targets, int32_t alpha, int32_t pvf, int32_t method, int32_t use_target_lists,
+                                       float confidence, int32_t double_threshold, int32_t* out_ids, float* out_sim) {
+  if (int rc = aa_check_scalars(triples, Q, k, n_cand, out_ids, out_sim)) return rc;
+  if (!ivpq || !vecs) return fail(FREDDY_E_ARG, "NULL index");
+  if (int rc = knn_join_check(ivpq, n_cand, target_ids, n_targets, alpha, pvf, method, double_threshold)) return rc;
+  if (int rc = check_ann_vecs(ivpq, KIND_IVPQ, vecs, "the approximate analogy")) return rc;
+  return aa_search(ivpq, vecs, triples, Q, k, n_cand, out_ids, out_sim, [&](const float*, int nq, int32_t* l_ids, float* l_dist) {
+    return knn_join_block(ivpq, nq, n_cand, target_ids, n_targets, alpha, pvf, method, use_target_lists, confidence, double_threshold, l_ids, l_dist, nullptr);
+  }, [&](int Qc, float** block) { return join_query_block_for(ivpq, Qc, block); });
 }
 
 extern "C" int freddy_gpu_last_approx_analogy_stats(const freddy_gpu_index_t* ann, int64_t* searched, int64_t* candidates, int64_t* scored) {
   if (!ann) return fail(FREDDY_E_ARG, "NULL index");
-  if (ann->kind != KIND_PQ && ann->kind != KIND_IVF) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  if (ann->kind != KIND_PQ && ann->kind != KIND_IVF && ann->kind != KIND_IVPQ) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
   if (searched) *searched = ann->aa_stats[0];
   if (candidates) *candidates = ann->aa_stats[1];
   if (scored) *scored = ann->aa_stats[2];

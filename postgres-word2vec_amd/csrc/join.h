@@ -11,6 +11,8 @@
 // Split of work
 //   GPU  sub_dist_kernel : the 2 x coarse_codes sub-distances of every query to the
 //                          multi-index centroids (index_utils.c:297-305), fp32 sequential.
+//        sub_dist_rows_kernel : the same for queries that are rows of a device table (freddy_gpu_knn_join_ids): it gathers
+//                          the row while it computes (join_run.h JoinQueries has the three sources of a call's queries).
 //   GPU  join_traverse_kernel : multi-index cell selection with statistics (index_utils.c:252-443)
 //        for up to 1024 cells, one wave per query.  The reference's heap pops the cells in ascending
 //        d0[c0] + d1[c1]; with no two equal keys among the cells a query takes (and the first it leaves)

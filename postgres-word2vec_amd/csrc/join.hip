@@ -80,10 +80,65 @@ extern "C" int freddy_gpu_knn_join(freddy_gpu_index_t* ix, const float* queries,
   if (Q > 0 && (!queries || !out_ids || !out_dist)) return fail(FREDDY_E_ARG, "NULL buffer");
   if (n_targets > 0 && !target_ids) return fail(FREDDY_E_ARG, "NULL target ids");
   HIP_TRY(hipSetDevice(ix->device));
-  int rc = join_run(&ix->join, ix->stream, queries, Q, k, target_ids, n_targets, alpha, pvf, method,
+  int rc = join_run(&ix->join, ix->stream, JoinQueries::of_host(queries), Q, k, target_ids, n_targets, alpha, pvf, method,
                     use_target_lists, confidence, double_threshold, out_ids, out_dist, iterations_out);
   if (rc) return fail(rc, "%s", join_error());
   return FREDDY_OK;
+}
+
+// ---- the kNN-join whose queries are on the device already (join_run.h JoinQueries) ---------------------------------------------------
+// What freddy_gpu_knn_join refuses about its scalars, then what JoinRun::begin refuses about the shape of the call, with their messages.
+int knn_join_check(const freddy_gpu_index* ivpq, int32_t k, const int32_t* target_ids, int64_t n_targets, int32_t alpha, int32_t pvf, int32_t method,
+                   int32_t double_threshold) {
+  if (k <= 0 || n_targets < 0) return fail(FREDDY_E_ARG, "bad sizes");
+  if (n_targets > 0 && !target_ids) return fail(FREDDY_E_ARG, "NULL target ids");
+  if (int rc = join_refusals(&ivpq->join, k, n_targets, alpha, pvf, method, double_threshold)) return fail(rc, "%s", join_error());
+  return 0;
+}
+
+int join_query_block_for(freddy_gpu_index* ivpq, int Q, float** block) {
+  if (join_query_block(&ivpq->join, Q, block)) return fail(FREDDY_E_NOMEM, "%s", join_error());
+  return 0;
+}
+
+int knn_join_block(freddy_gpu_index* ivpq, int Q, int k, const int32_t* target_ids, int64_t n_targets, int alpha, int pvf, int method, int use_target_lists,
+                   float confidence, int double_threshold, int32_t* out_ids, float* out_dist, int32_t* iterations_out) {
+  HIP_TRY(hipSetDevice(ivpq->device));
+  if (int rc = join_run(&ivpq->join, ivpq->stream, JoinQueries::of_block(), Q, k, target_ids, n_targets, alpha, pvf, method, use_target_lists, confidence,
+                        double_threshold, out_ids, out_dist, iterations_out))
+    return fail(rc, "%s", join_error());
+  return FREDDY_OK;
+}
+
+// The queries are the rows of `vecs` (NULL: of the ivpq handle's own vectors) with these ids: the id rule on the host, the rows that
+// have one compacted, their numbers to the device (4 bytes per query) and ONE join over them -- sub_dist_rows_kernel gathers the rows
+// where freddy_gpu_knn_join's front pulls the caller's floats over PCIe.
+extern "C" int freddy_gpu_knn_join_ids(freddy_gpu_index_t* ivpq, freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k,
+                                       const int32_t* target_ids, int64_t n_targets, int32_t alpha, int32_t pvf, int32_t method,
+                                       int32_t use_target_lists, float confidence, int32_t double_threshold, int32_t* out_query_ids,
+                                       int32_t* n_queries, int32_t* out_ids, float* out_dist, int32_t* iterations_out) {
+  if (int rc = check_query_ids_front(ivpq, ivpq, query_ids, n_ids, id_rule, out_query_ids, n_queries, out_ids, out_dist)) return rc;
+  if (int rc = knn_join_check(ivpq, k, target_ids, n_targets, alpha, pvf, method, double_threshold)) return rc;
+  if (vecs) {
+    if (int rc = check_ann_vecs(ivpq, KIND_IVPQ, vecs, "a kNN-join by row id")) return rc;
+  } else {
+    if (ivpq->kind != KIND_IVPQ) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+    if (int rc = refuse_poisoned(ivpq)) return rc;
+    if (!ivpq->join.has_vectors)
+      return fail(FREDDY_E_ARG, "this ivpq handle was pinned without vectors: a kNN-join by row id needs a vector handle to take its queries from");
+  }
+  JoinIndex& j = ivpq->join;
+  const float* table = vecs ? vecs->coarse : j.vectors;
+  const int64_t n_table = vecs ? vecs->N : j.N;
+  if (iterations_out) *iterations_out = 0;
+  return search_selected_rows(vecs ? vecs->h_ids : j.h_ids, query_ids, n_ids, id_rule, k, JOIN_MAX_DIST, out_query_ids, n_queries, out_ids, out_dist,
+                              [&](const int32_t* rows, int n, int32_t* oi, float* od) {
+    HIP_TRY(hipSetDevice(ivpq->device));
+    if (int rc = join_run(&j, ivpq->stream, JoinQueries::of_rows(ivpq, table, n_table, rows), n, k, target_ids, n_targets, alpha, pvf, method,
+                          use_target_lists, confidence, double_threshold, oi, od, iterations_out))
+      return fail(rc, "%s", join_error());
+    return (int)FREDDY_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------------------

@@ -103,6 +103,7 @@ struct JoinIndex {
   void* w[JW_SLOTS] = {nullptr};
   size_t wcap[JW_SLOTS] = {0};
   float libm_margin = 1e-5f;     // option join_libm_margin_ppm: device confidences this close to the threshold are re-evaluated by the host's libm
+  bool front_gather = true;      // option join_front_gather: a join by row id gathers its queries in the sub-distance launch (sub_dist_rows_kernel); 0 = query_gather_kernel, then sub_dist_kernel
   bool host_traversal = false;   // option join_host_traversal / FREDDY_GPU_JOIN_HOST_TRAVERSAL: every traversal on the host heap
   // stage timers of the last call under the reference's TRACK names (ivpq_search_in.c:234-697)
   freddy_track track;

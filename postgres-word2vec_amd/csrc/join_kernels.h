@@ -78,6 +78,58 @@ __global__ __launch_bounds__(64) void sub_dist_kernel(const float* __restrict__ 
   }
 }
 
+// The front of a join whose queries are rows of a device table (freddy_gpu_knn_join_ids; JoinRun::front_rows): grid (nq, 2), 64
+// lanes, as sub_dist_kernel.  rows: [nq] row numbers in mapped host memory -- the workgroup reads its own once (the index is
+// wave-uniform: one scalar load over PCIe, 4 bytes instead of sub_dist_kernel's half vector); a row outside [0, n_table) gives
+// zeros, as query_gather_kernel does.  The half row goes from table + row * d + pos * half into LDS and into copy_out[q] (the
+// block the join kernel reads), with 16-byte loads where half and the offset allow them; then sub_dist_kernel's loop, statement for
+// statement, over the LDS copy: the bits of `out` are sub_dist_kernel's over the same vectors.  half <= 512 (the launcher's part).
+__global__ __launch_bounds__(64) void sub_dist_rows_kernel(const float* __restrict__ table, const int32_t* __restrict__ rows, int64_t n_table,
+                                                          const float* __restrict__ coarseT, float* __restrict__ out, int d, int Kc,
+                                                          float* __restrict__ copy_out) {
+  __shared__ __attribute__((aligned(16))) float qh[512];
+  const int q = blockIdx.x, pos = blockIdx.y;
+  const int half = d / 2;
+  const int64_t row = rows[q];
+  const bool known = row >= 0 && row < n_table;
+  const size_t src = (size_t)(known ? row : 0) * d + (size_t)pos * half;
+  float* dst = copy_out + (size_t)q * d + (size_t)pos * half;
+  if ((half & 3) == 0 && (src & 3) == 0) {   // (half % 4 == 0 makes d a multiple of 8: dst is 16-byte aligned as well)
+    const int n4 = half >> 2;
+    for (int i = threadIdx.x; i < n4; i += 64) {
+      float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (known) v = reinterpret_cast<const float4*>(table + src)[i];
+      reinterpret_cast<float4*>(qh)[i] = v;
+      reinterpret_cast<float4*>(dst)[i] = v;
+    }
+  } else {
+    for (int i = threadIdx.x; i < half; i += 64) { const float v = known ? table[src + i] : 0.0f; qh[i] = v; dst[i] = v; }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < Kc; c += 64) {
+    float acc = 0.0f;
+    constexpr int NB = 15;   // (loads in flight per batch: sub_dist_kernel)
+    int i = 0;
+    for (; i + NB <= half; i += NB) {
+      float cv[NB], qq[NB];
+#pragma unroll
+      for (int u = 0; u < NB; ++u) { cv[u] = coarseT[((size_t)pos * half + i + u) * Kc + c]; qq[u] = qh[i + u]; }
+#pragma unroll
+      for (int u = 0; u < NB; ++u) {
+        const float t = qq[u] - cv[u];
+        const float p = t * t;
+        acc = acc + p;
+      }
+    }
+    for (; i < half; ++i) {
+      const float t = qh[i] - coarseT[((size_t)pos * half + i) * Kc + c];
+      const float p = t * t;
+      acc = acc + p;
+    }
+    out[((size_t)q * 2 + pos) * Kc + c] = acc;
+  }
+}
+
 // Stable ascending order of one side's Kc sub-distances (index_utils.c:306-320 sorts each position's
 // distances; equal distances keep their code order): key = (distance bits << 32 | code), one wave per
 // (query, position).  Kc <= 64 * V.

@@ -7,8 +7,29 @@
 #include "internal.h"
 #include "bigk.h"
 #include "join.h"
+#include "query_ids.h"
 
 namespace freddy {
+
+// Where the queries of a call come from.  After front() the host never reads them again: everything later comes from
+// JW_QUERIES / JW_SUB.
+//   host      [Q][d] floats in the caller's memory (freddy_gpu_knn_join): staged, or read where they lie when they are pinned
+//   rows      rows of a device table, row numbers in host memory (freddy_gpu_knn_join_ids): 4 bytes per query go into the pinned block
+//             and sub_dist_rows_kernel gathers while it computes the sub-distances
+//   in_block  the caller has filled JW_QUERIES on the join's stream (freddy_gpu_ivpq_analogy: aa_query_kernel writes the unit rows
+//             there), sized through join_query_block() -- workspaces() finds the block large enough and leaves it where it is
+struct JoinQueries {
+  QuerySrc src;
+  bool in_block = false;
+  freddy_gpu_index* ix = nullptr;   // the handle whose profile records the front's launches (rows)
+  static JoinQueries of_host(const float* q) { JoinQueries s; s.src = QuerySrc::of_host(q); return s; }
+  static JoinQueries of_rows(freddy_gpu_index* ix, const float* table, int64_t n_table, const int32_t* rows) {
+    JoinQueries s; s.src.table = table; s.src.n_table = n_table; s.src.rows = rows; s.ix = ix; return s;
+  }
+  static JoinQueries of_block() { JoinQueries s; s.in_block = true; return s; }
+};
+// The block an in_block caller fills: JW_QUERIES with room for Q queries.
+static inline int join_query_block(JoinIndex* j, int Q, float** out) { return join_buf(j, JW_QUERIES, (size_t)Q * j->d, out); }
 
 // The pinned landing zone of a call (JoinIndex::h_sum), described once as byte offsets and applied to the host's and to the
 // device's address of the block.  The kernels read the lists and write summaries / results in it DIRECTLY (it is mapped into
@@ -47,7 +68,8 @@ struct JoinRun {
   // ---- the call
   JoinIndex* j;
   hipStream_t s;
-  const float* queries;
+  const float* queries;   // host floats, or NULL with
+  JoinQueries qsrc;       // the source of the call
   int Q, k;
   const int32_t* target_ids;
   int64_t n_targets;
@@ -121,12 +143,13 @@ struct JoinRun {
   int enqueue_fb_rows();
   int enqueue_join();
 
-  int begin(JoinIndex* j, hipStream_t s, const float* queries, int Q, int k, const int32_t* target_ids, int64_t n_targets, int alpha,
+  int begin(JoinIndex* j, hipStream_t s, const JoinQueries& queries, int Q, int k, const int32_t* target_ids, int64_t n_targets, int alpha,
             int pvf, int method, int use_tl, float confidence, int double_threshold, int32_t* out_ids, float* out_dist,
             int32_t* iterations_out);
   int workspaces();
   int targets();
   int front();
+  int front_rows();
   int prepare_rounds();
   int traverse_round();
   void check_stops();
@@ -137,20 +160,14 @@ struct JoinRun {
   void end();
 };
 
-// ---- argument checks, the shape of the call, initTopKs
-inline int JoinRun::begin(JoinIndex* j_, hipStream_t s_, const float* queries_, int Q_, int k_, const int32_t* target_ids_,
-                          int64_t n_targets_, int alpha_, int pvf_, int method_, int use_tl_, float confidence_,
-                          int double_threshold, int32_t* out_ids_, float* out_dist_, int32_t* iterations_out_) {
-  j = j_; s = s_; queries = queries_; Q = Q_; k = k_; target_ids = target_ids_; n_targets = n_targets_;
-  alpha = alpha_original = alpha_; pvf = pvf_; method = method_; use_tl = use_tl_; confidence = confidence_;
-  out_ids = out_ids_; out_dist = out_dist_; iterations_out = iterations_out_;
+// What a call is refused for besides its pointers and counts, in begin()'s order; nothing here touches a device or the handle (the
+// entry points that check their arguments before they resolve ids ask it first, begin() asks it again).
+static inline int join_refusals(const JoinIndex* j, int k, int64_t n_targets, int alpha, int pvf, int method, int double_threshold) {
   if (method < 0 || method > 2) return join_fail(FREDDY_E_ARG, "Unknown computation method!");   // ivpq_search_in.c:374-376
   if (method != FREDDY_METHOD_PQ && !j->has_vectors) return join_fail(FREDDY_E_ARG, "methods 1 and 2 need the vectors to be pinned");
   if (n_targets > INT32_MAX) return join_fail(FREDDY_E_LIMIT, "too many targets");
-  j->track = freddy_track();
-  t_start = t_last = Clock::now();
   if (pvf < 1) pvf = 1;                                                                       // :207-209
-  double_codes = method != FREDDY_METHOD_EXACT && (int64_t)alpha * k > double_threshold;      // :262-266
+  const bool double_codes = method != FREDDY_METHOD_EXACT && (int64_t)alpha * k > double_threshold;      // :262-266
   if (double_codes && (int64_t)j->K * j->K > 32768) return join_fail(FREDDY_E_LIMIT, "pair codes of K=%d overflow the reference's int16", j->K);
   const bool pv = method == FREDDY_METHOD_PQ_PV;
   const int64_t Lw = pv ? (int64_t)k * pvf : 2 * (int64_t)k;
@@ -159,6 +176,23 @@ inline int JoinRun::begin(JoinIndex* j_, hipStream_t s_, const float* queries_, 
   // registers, and beyond that bigk_replay_kernel computes the list the replay would leave -- bigk.h)
   if (!pv && k > BIGK_KMAX) return join_fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of %d", k, BIGK_KMAX);
   if (pv && Lw > 8192) return join_fail(FREDDY_E_LIMIT, "k*pvf=%lld exceeds this build's limit of 8192", (long long)Lw);
+  return 0;
+}
+
+// ---- argument checks, the shape of the call, initTopKs
+inline int JoinRun::begin(JoinIndex* j_, hipStream_t s_, const JoinQueries& queries_, int Q_, int k_, const int32_t* target_ids_,
+                          int64_t n_targets_, int alpha_, int pvf_, int method_, int use_tl_, float confidence_,
+                          int double_threshold, int32_t* out_ids_, float* out_dist_, int32_t* iterations_out_) {
+  j = j_; s = s_; qsrc = queries_; queries = qsrc.src.host; Q = Q_; k = k_; target_ids = target_ids_; n_targets = n_targets_;
+  alpha = alpha_original = alpha_; pvf = pvf_; method = method_; use_tl = use_tl_; confidence = confidence_;
+  out_ids = out_ids_; out_dist = out_dist_; iterations_out = iterations_out_;
+  if (int rc = join_refusals(j, k, n_targets, alpha, pvf, method, double_threshold)) return rc;
+  j->track = freddy_track();
+  t_start = t_last = Clock::now();
+  if (pvf < 1) pvf = 1;                                                                       // :207-209
+  double_codes = method != FREDDY_METHOD_EXACT && (int64_t)alpha * k > double_threshold;      // :262-266
+  const bool pv = method == FREDDY_METHOD_PQ_PV;
+  const int64_t Lw = pv ? (int64_t)k * pvf : 2 * (int64_t)k;
   big = Lw > 1024;
   replay = big && !pv;
   L = (int)Lw;
@@ -227,6 +261,13 @@ inline int JoinRun::targets() {
 // ---- the queries to the device, and their sub-distances to the multi-index centroids
 inline int JoinRun::front() {
   const int d = j->d, Kc = j->Kc;
+  if (qsrc.in_block) {   // the caller's kernel wrote JW_QUERIES on this stream: nothing to copy
+    hipLaunchKernelGGL(sub_dist_kernel, dim3((unsigned)Q, 2), dim3(64), 0, s, (const float*)d_q, j->coarseT, d_sub, d, Kc, (float*)nullptr, 0);
+    JOIN_HIP(hipGetLastError());
+    mark("queries in place, sub-distances enqueued");
+    return 0;
+  }
+  if (qsrc.src.table) return front_rows();
   // a query buffer that is pinned already (freddy_gpu_host_alloc: what pg/freddy_gpu_glue.c's query_buffer() hands over) is read
   // where it is -- the 6 MB staging copy of 5 000 queries is the longest host step of a call
   const float* p_queries = static_cast<const float*>(pinned_device_pointer(queries));
@@ -256,6 +297,31 @@ inline int JoinRun::front() {
     JOIN_HIP(hipGetLastError());
   }
   mark("queries staged, sub-distances enqueued");
+  return 0;
+}
+
+// Queries that are rows of a device table: their numbers (4 bytes per query) into the pinned block, and ONE launch that gathers the
+// rows into JW_QUERIES and computes their sub-distances (sub_dist_rows_kernel).  Half vectors beyond the kernel's staging buffer, and
+// option join_front_gather = 0, take two launches: query_gather_kernel into JW_QUERIES, then sub_dist_kernel over it.
+inline int JoinRun::front_rows() {
+  const int d = j->d, Kc = j->Kc;
+  if (j->h_q.ensure(sizeof(int32_t) * (size_t)Q)) return join_fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+  memcpy(j->h_q.p, qsrc.src.rows, sizeof(int32_t) * (size_t)Q);
+  void* p_rows = nullptr;
+  JOIN_HIP(hipHostGetDevicePointer(&p_rows, j->h_q.p, 0));
+  const int32_t* rows = static_cast<const int32_t*>(p_rows);
+  if (d / 2 <= 512 && j->front_gather) {
+    timed_launch(qsrc.ix, s, "join_front_rows", [&] {
+      hipLaunchKernelGGL(sub_dist_rows_kernel, dim3((unsigned)Q, 2), dim3(64), 0, s, qsrc.src.table, rows, qsrc.src.n_table, (const float*)j->coarseT,
+                         d_sub, d, Kc, d_q);
+    });
+    JOIN_HIP(hipGetLastError());
+  } else {
+    if (launch_query_gather(qsrc.ix, s, qsrc.src, rows, d_q, Q, d)) return join_fail(FREDDY_E_HIP, "launch of the query gather failed");
+    hipLaunchKernelGGL(sub_dist_kernel, dim3((unsigned)Q, 2), dim3(64), 0, s, (const float*)d_q, j->coarseT, d_sub, d, Kc, (float*)nullptr, 0);
+    JOIN_HIP(hipGetLastError());
+  }
+  mark("row numbers staged, gather + sub-distances enqueued");
   return 0;
 }
 
@@ -617,7 +683,7 @@ inline void JoinRun::end() {
   if (iterations_out) *iterations_out = iterations;
 }
 
-static inline int join_run(JoinIndex* j, hipStream_t s, const float* queries, int Q, int k, const int32_t* target_ids,
+static inline int join_run(JoinIndex* j, hipStream_t s, const JoinQueries& queries, int Q, int k, const int32_t* target_ids,
                            int64_t n_targets, int alpha, int pvf, int method, int use_tl, float confidence,
                            int double_threshold, int32_t* out_ids, float* out_dist, int32_t* iterations_out) {
   JoinRun r;

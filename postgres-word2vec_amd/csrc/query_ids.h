@@ -131,21 +131,23 @@ static inline int check_query_ids_front(const void* ann, const void* vecs, const
 // The frame of the four entry points once nothing is refused: select, search the compacted rows with `search(QuerySrc, n, ids, val)`,
 // put every list in its slot and fillers (-1, filler) in the slots without a row.  No device work before all ids are resolved; none at
 // all when no id has a row.
+// (search_selected_rows: the same over any ascending id column -- the kNN-join by row id reads the ivpq handle's own when it is given
+// no vector handle -- with `search(rows, n, ids, val)`)
 template <class F>
-static int search_selected_ids(const freddy_gpu_index* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k, float filler,
-                               int32_t* out_query_ids, int32_t* n_queries, int32_t* out_ids, float* out_val, F&& search) {
+static int search_selected_rows(const std::vector<int32_t>& h_ids, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k, float filler,
+                                int32_t* out_query_ids, int32_t* n_queries, int32_t* out_ids, float* out_val, F&& search) {
   *n_queries = 0;
   if (n_ids == 0) return FREDDY_OK;
-  const QidSelection s = select_query_ids(vecs->h_ids, query_ids, n_ids, id_rule);
+  const QidSelection s = select_query_ids(h_ids, query_ids, n_ids, id_rule);
   const int Q = (int)s.sel.size(), n = (int)s.rows.size();
   int rc = 0;
   if (s.dense()) {
-    if (n) rc = search(QuerySrc::of_rows(vecs, s.rows.data()), n, out_ids, out_val);
+    if (n) rc = search(s.rows.data(), n, out_ids, out_val);
   } else {
     for (size_t i = 0; i < (size_t)Q * k; ++i) { out_ids[i] = -1; out_val[i] = filler; }
     std::vector<int32_t> ti((size_t)n * k);
     std::vector<float> tv((size_t)n * k);
-    if (n) rc = search(QuerySrc::of_rows(vecs, s.rows.data()), n, ti.data(), tv.data());
+    if (n) rc = search(s.rows.data(), n, ti.data(), tv.data());
     for (int i = 0; i < n && !rc; ++i) {
       memcpy(out_ids + (size_t)s.slot[(size_t)i] * k, &ti[(size_t)i * k], sizeof(int32_t) * (size_t)k);
       memcpy(out_val + (size_t)s.slot[(size_t)i] * k, &tv[(size_t)i * k], sizeof(float) * (size_t)k);
@@ -156,6 +158,22 @@ static int search_selected_ids(const freddy_gpu_index* vecs, const int32_t* quer
   *n_queries = Q;
   return FREDDY_OK;
 }
+template <class F>
+static int search_selected_ids(const freddy_gpu_index* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k, float filler,
+                               int32_t* out_query_ids, int32_t* n_queries, int32_t* out_ids, float* out_val, F&& search) {
+  return search_selected_rows(vecs->h_ids, query_ids, n_ids, id_rule, k, filler, out_query_ids, n_queries, out_ids, out_val,
+                              [&](const int32_t* rows, int n, int32_t* oi, float* ov) { return search(QuerySrc::of_rows(vecs, rows), n, oi, ov); });
+}
+
+// ---- join.hip: the kNN-join for the approximate analogy over an ivpq handle (exact.hip freddy_gpu_ivpq_analogy) ---------------------
+// knn_join_check: what freddy_gpu_knn_join refuses about its scalars and its shape (nothing touches a device).  join_query_block_for: the
+// join's query block with room for Q queries, for a kernel of the caller's to fill on the handle's stream; knn_join_block: the join over
+// the first Q queries of that block (arguments already checked), enqueued behind whatever filled it -- no host synchronisation before.
+int knn_join_check(const freddy_gpu_index* ivpq, int32_t k, const int32_t* target_ids, int64_t n_targets, int32_t alpha, int32_t pvf, int32_t method,
+                   int32_t double_threshold);
+int join_query_block_for(freddy_gpu_index* ivpq, int Q, float** block);
+int knn_join_block(freddy_gpu_index* ivpq, int Q, int k, const int32_t* target_ids, int64_t n_targets, int alpha, int pvf, int method, int use_target_lists,
+                   float confidence, int double_threshold, int32_t* out_ids, float* out_dist, int32_t* iterations_out);
 
 // ---- ivfadc.hip / pq.hip: the host-buffer searches behind the public entry points, for either source (arguments already checked) ----
 int ivfadc_search_src(freddy_gpu_index* ix, const QuerySrc& qs, int Q, int k, int W, float sentinel, int found_rule, int32_t* out_ids, float* out_dist);

@@ -41,6 +41,7 @@ EXPORTS = [
     "freddy_gpu_similarity_pairs", "freddy_gpu_similarity_matrix", "freddy_gpu_similarity_join",
     "freddy_gpu_cluster",
     "freddy_gpu_exact_search_ids", "freddy_gpu_exact_join_ids", "freddy_gpu_debug_resolve_ids",
+    "freddy_gpu_knn_join_ids", "freddy_gpu_ivpq_analogy",
 ]
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together): ids per pass of freddy_gpu_create_statistics
@@ -170,7 +171,13 @@ def load(path=None, optional=()):
                                                          C.c_void_p, C.c_void_p, C.c_void_p]),
                         ("freddy_gpu_exact_join_ids", [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_debug_resolve_ids", [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])):
+                        ("freddy_gpu_debug_resolve_ids", [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+                        # the kNN-join by row id and the batched analogy over it (the same again)
+                        ("freddy_gpu_knn_join_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_ivpq_analogy", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = types
     lib.freddy_gpu_pq_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
@@ -364,7 +371,7 @@ class _Index:
         return {"candidates": v[0].value, "scored": v[1].value}
 
     def last_approx_analogy_stats(self):
-        """The last analogy() call on this pq / ivf handle (freddy_gpu_last_approx_analogy_stats): triples that reached stage one,
+        """The last analogy() call on this pq / ivf / ivpq handle (freddy_gpu_last_approx_analogy_stats): triples that reached stage one,
         their list entries with id >= 0, and how many of those had a vector row and were not an input of their triple."""
         v = [C.c_int64(0) for _ in range(3)]
         _check(self.lib.freddy_gpu_last_approx_analogy_stats(self.h, *(C.byref(x) for x in v)))
@@ -797,6 +804,34 @@ class IVPQIndex(_Index):
                                             1 if use_target_lists else 0, C.c_float(confidence),
                                             double_threshold, _p(out_i), _p(out_d), C.byref(iters)))
         return out_i, out_d, iters.value
+
+    def knn_join_ids(self, vecs, query_ids, k, target_ids, alpha, pvf, method, id_rule=QIDS_POSITIONAL, use_target_lists=True,
+                     confidence=0.8, double_threshold=10000000):
+        """knn_join() for the rows of the VectorIndex `vecs` -- None: of this handle's own pinned vectors -- with these ids, gathered
+        on the device (freddy_gpu_knn_join_ids): (query_ids[Q], ids[Q,k], dist[Q,k], iterations) with Q = the queries `id_rule`
+        selects; the lists of the ids that have a row and the iteration count are bit for bit ONE knn_join() over their vectors, a
+        positional slot without a row holds (-1, 1000.0)."""
+        tid = _i32(target_ids)
+        iters = C.c_int32(0)
+        oq, oi, od = _search_ids(query_ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_knn_join_ids(
+            self.h, None if vecs is None else vecs.h, _p(q), n, id_rule, k, _p(tid), tid.size, alpha, pvf, method, 1 if use_target_lists else 0,
+            C.c_float(confidence), double_threshold, _p(oq), C.byref(nq), _p(oi), _p(od), C.byref(iters)))
+        return oq, oi, od, iters.value
+
+    def analogy(self, vecs, triples, k=1, n_cand=4, target_ids=(), alpha=1, pvf=1, method=METHOD_PQ, use_target_lists=True, confidence=0.8,
+                double_threshold=10000000):
+        """Approximate 3CosAdd analogies over the kNN-join (freddy_gpu_ivpq_analogy; analogy_3cosadd_in_ivpq with its literal
+        n_cand = 4): triples [Q][3] of row ids -> (ids[Q,k], similarity[Q,k]); per triple bit for bit vecs.search(v3 - v1 + v2, k,
+        subset_ids=<the ids of the join's list for the normalised sum, without the inputs>); (-1, -inf) where there is no row or an
+        input id has no vector."""
+        t = _i32(triples).reshape(-1, 3)
+        Q = t.shape[0]
+        out_i = np.empty((Q, k), np.int32)
+        out_s = np.empty((Q, k), np.float32)
+        tid = _i32(target_ids)
+        _check(self.lib.freddy_gpu_ivpq_analogy(self.h, None if vecs is None else vecs.h, _p(t), Q, k, n_cand, _p(tid), tid.size, alpha, pvf, method,
+                                                1 if use_target_lists else 0, C.c_float(confidence), double_threshold, _p(out_i), _p(out_s)))
+        return out_i, out_s
 
     def set_statistics(self, stats):
         """set_statistics_table for the pinned handle (freddy_gpu_set_statistics): `stats` ([cells + 1] floats) becomes the row the

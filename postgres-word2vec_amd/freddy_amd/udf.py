@@ -254,6 +254,15 @@ class Session:
         self._check(self.lib.knn_search_in_batch_ids(self.h, _p(qid), qid.size, k, _p(ids), ids.size, _p(out), C.byref(n)))
         return out[:n.value]
 
+    def knn_in_ivpq_batch_ids(self, query_ids, k, input_ids):
+        """freddy--0.0.1.sql:720-761, the kNN-join whose queries are rows of google_vecs_norm: rows (query id, id, distance), k per
+        query id that has a row, in argument order."""
+        qid, ids = _i32(query_ids), _i32(input_ids)
+        out = np.empty(max(qid.size, 1) * k, ROW3)
+        n = C.c_int32(0)
+        self._check(self.lib.knn_in_ivpq_batch_ids(self.h, _p(qid), qid.size, k, _p(ids), ids.size, _p(out), C.byref(n)))
+        return out[:n.value]
+
     def _groups(self, fn, token_ids, group_ids):
         toks, groups = _i32(token_ids), _i32(group_ids)
         out = np.empty(max(toks.size, 1), GROUP_ROW)
@@ -305,6 +314,10 @@ class Session:
     def analogy_3cosadd_in_pq_batch(self, triples, input_ids):
         ids = _i32(input_ids)
         return self._analogy_batch(self.lib.analogy_3cosadd_in_pq_batch, triples, _p(ids), ids.size)
+
+    def analogy_3cosadd_in_ivpq_batch(self, triples, input_ids):
+        ids = _i32(input_ids)
+        return self._analogy_batch(self.lib.analogy_3cosadd_in_ivpq_batch, triples, _p(ids), ids.size)
 
     def gpu_index(self, table):
         """The pinned handle behind "pq", "ivfadc", "ivpq" or "vecs" as a borrowed gpu index object (profile_enable / profile_read /

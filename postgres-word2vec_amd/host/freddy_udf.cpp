@@ -668,6 +668,31 @@ int analogy_3cosadd_ivfadc_batch(freddy_session_t* s, const int32_t* triples, in
 int analogy_3cosadd_in_pq_batch(freddy_session_t* s, const int32_t* triples, int32_t n, const int32_t* input_ids, int32_t n_ids, int32_t* results) {
   return analogy_batch_common(s, PQ, true, triples, n, input_ids, n_ids, results);
 }
+// The two entry points by row id over the kNN-join came without a new ABI version (no struct grew, no entry point changed meaning), so --
+// as freddy_gpu_cluster in cluster.h -- they are bound weakly: beside a library that does not have them yet the functions below run
+// what their callers ran before, the single-triple loop and the join over vectors gathered from the host copy; the rows are the same.
+extern "C" int freddy_gpu_ivpq_analogy(freddy_gpu_index_t*, freddy_gpu_index_t*, const int32_t*, int32_t, int32_t, int32_t, const int32_t*, int64_t, int32_t,
+                                       int32_t, int32_t, int32_t, float, int32_t, int32_t*, float*) __attribute__((weak));
+extern "C" int freddy_gpu_knn_join_ids(freddy_gpu_index_t*, freddy_gpu_index_t*, const int32_t*, int32_t, int32_t, int32_t, const int32_t*, int64_t, int32_t,
+                                       int32_t, int32_t, int32_t, float, int32_t, int32_t*, int32_t*, int32_t*, float*, int32_t*) __attribute__((weak));
+
+// ... and of analogy_3cosadd_in_ivpq: ONE kNN-join per pass of triples at the SQL's literal k = 4 (freddy_gpu_ivpq_analogy), the join's
+// settings from the getters as session_knn_join passes them
+int analogy_3cosadd_in_ivpq_batch(freddy_session_t* s, const int32_t* triples, int32_t n, const int32_t* input_ids, int32_t n_ids, int32_t* results) {
+  if (!s || n < 0 || (n > 0 && (!triples || !results)) || n_ids < 0 || (n_ids > 0 && !input_ids)) return fail(-1, "bad argument");
+  REQUIRE(need_table_and_norm(s, IVPQ));
+  if (n == 0) return 0;
+  if (!freddy_gpu_ivpq_analogy) {
+    for (int32_t i = 0; i < n; ++i)
+      REQUIRE(analogy_common(s, IVPQ, true, triples[3 * i], triples[3 * i + 1], triples[3 * i + 2], input_ids, n_ids, results + i));
+    return 0;
+  }
+  REQUIRE(s->norm.pinned(s->device));
+  std::vector<float> sim((size_t)n);
+  const int rc = freddy_gpu_ivpq_analogy(s->code[IVPQ].h, s->norm.h, triples, n, 1, 4, input_ids, n_ids, s->alpha, s->pvf, s->method_flag, s->use_targetlist,
+                                         s->confidence, s->long_codes_threshold, results, sim.data());
+  return rc ? gpu_fail(rc) : 0;
+}
 
 // ---- exact analogies and the dispatchers      freddy--0.0.1.sql:1231-1315, 269-297 --------------------------------
 // one triple on a vector table's handle
@@ -762,6 +787,35 @@ int knn_search_in_batch_ids(freddy_session_t* s, const int32_t* query_ids, int32
   std::vector<float> qv;
   known_rows(s, query_ids, (size_t)n_queries, qids, qv);
   return exact_join_rows(s, qv.data(), qids.data(), (int32_t)qids.size(), k, input_ids, n_ids, out, n_rows);
+}
+
+// knn_in_ivpq_batch(query_set varchar[], ...) (freddy--0.0.1.sql:720-761): the queries are rows of google_vecs_norm.  knn_search_in_batch_ids'
+// rule -- argument order, an unknown id yields nothing, a duplicate is answered again, rows carry the query's id -- and knn_join's
+// lists; the vectors stay on the device (freddy_gpu_knn_join_ids over the pinned vector table).
+int knn_in_ivpq_batch_ids(freddy_session_t* s, const int32_t* query_ids, int32_t n_queries, int32_t k, const int32_t* input_ids, int32_t n_ids,
+                          freddy_row3* out, int32_t* n_rows) {
+  REQUIRE(need_table_and_norm(s, IVPQ));
+  if (k <= 0 || n_queries < 0 || n_ids < 0 || !out || (n_queries > 0 && !query_ids) || (n_ids > 0 && !input_ids)) return fail(-1, "bad argument");
+  if (n_rows) *n_rows = 0;
+  std::vector<int32_t> qids;
+  for (int32_t i = 0; i < n_queries; ++i) if (s->norm.find(query_ids[i])) qids.push_back(query_ids[i]);
+  const int32_t Q = (int32_t)qids.size();
+  if (Q == 0) return 0;
+  std::vector<int32_t> ids((size_t)Q * k), sel((size_t)Q);
+  std::vector<float> dist((size_t)Q * k);
+  if (!freddy_gpu_knn_join_ids) {
+    std::vector<float> qv;
+    for (int32_t id : qids) { const float* v = s->norm.find(id); qv.insert(qv.end(), v, v + s->norm.d); }
+    REQUIRE(session_knn_join(s, qv.data(), Q, k, input_ids, n_ids, ids.data(), dist.data()));
+    return emit3(qids.data(), Q, k, ids, dist, out, n_rows);
+  }
+  REQUIRE(s->norm.pinned(s->device));
+  int32_t nq = 0;
+  if (int rc = freddy_gpu_knn_join_ids(s->code[IVPQ].h, s->norm.h, qids.data(), Q, FREDDY_QIDS_POSITIONAL, k, input_ids, n_ids, s->alpha, s->pvf,
+                                       s->method_flag, s->use_targetlist, s->confidence, s->long_codes_threshold, sel.data(), &nq, ids.data(), dist.data(),
+                                       nullptr))
+    return gpu_fail(rc);
+  return emit3(qids.data(), Q, k, ids, dist, out, n_rows);
 }
 
 int grouping_func(freddy_session_t* s, const int32_t* token_ids, int32_t n_tokens, const int32_t* group_ids, int32_t n_groups,

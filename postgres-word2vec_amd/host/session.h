@@ -2,6 +2,7 @@
 // and who drops them, and the freddy_load_* entry points.  Included by freddy_udf.cpp only (one translation unit, as csrc/).
 #pragma once
 #include "../../include/freddy_udf.h"
+#include "../../include/freddy_udf_ivpq.h"
 
 #include <algorithm>
 #include <cstdarg>
