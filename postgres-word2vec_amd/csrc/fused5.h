@@ -25,16 +25,27 @@
 // The bound (u = 2^-24, B and the reference's error as for the fp32 slabs; D exact, d the reference's binary32 value):
 //   reference                                   |d - D|        <= 39 u B
 //   rterm (fp64, rounded once)                                  <=  1 u B
-//   per position: dot product (25 terms; since round 4 on the matrix cores, seven v_mfma_f32_16x16x4_f32 steps -- any
-//                 order of binary32 products and sums of 25 terms stays below 56 u, the fmaf chain of rounds 2-3 below 26 u)
-//                 and quotient                                <= 58 u 2|q_p||c| ; rint: <= 0.5 scale
+//   per position: the dot product on f16-split operands (query_codebook5_body: three v_mfma_f32_16x16x32_f16 per tile), against
+//                 T = |q_p| max|c_p| (Cauchy-Schwarz: sum_j |q_j c_j| <= |q_p||c| <= T).  In scaled units (x 2^eq, x 2^ecb: exact)
+//                 every element is v = hi + lo + r, |lo| <= 2^-11 |v|, |r| <= 2^-22 |v| + 2^-25 (the 2^-25: f16 subnormals);
+//                 the slice's and the position's largest elements are >= 2^9, so |q_p| >= 2^9 and max|c_p| >= 2^9.
+//                   representation  sum |r_q c| + |q r_c|  <= (4 + 4) u T + 2 . 2^-25 . 5 . 2^-9 T   (sum_j |v_j| <= 5 |v|)
+//                   dropped lo . lo                         <= 2^-22 T = 4 u T                              together <= 12.1 u T
+//                   accumulation: binary32, the order inside an instruction unknown and round-to-nearest not assumed -- every
+//                     nonzero addend (a product, exact: 22 bits; or the accumulator that comes in) costs one rounding of at most
+//                     2 u times the sum of the magnitudes, and so does the result: lo . hi and hi . lo (magnitudes <= 2^-11 T
+//                     each, 26 + 27 roundings) < 0.1 u T; hi . hi LAST, 25 products + the accumulator + the result = 27 roundings
+//                     of <= (1 + 2^-9) T                  <= 54.2 u T
+//                   the zero dimensions 25..31 add nothing; the rescaling by 2^-(eq + ecb) is exact
+//                 dot product <= 66.4 u T, and quotient (two roundings) <= 68.4 u 2 T: <= 69 u 2|q_p| max|c_p| ; rint: <= 0.5 scale
+//                 (the seven v_mfma_f32_16x16x4_f32 steps of rounds 4-6 were given 58 u; tests/test_table_split_cpu.py has the model)
 //                 no clamping: 2 |q_p| max|c_p| <= 2730 scale by construction
-//       summed over 12 positions                                <= 58 u B + 6 scale
+//       summed over 12 positions                                <= 69 u B + 6 scale
 //   the sum V itself: exact (integers below 2^15)
 //   s' = fma(scale, V, rterm), s = s' + OFF: two roundings of values <= 3 B + E      <=  7 u B
 //   residual's own rounding (as for the fp32 slabs)                         <=  2 u B
-//   =>  |(s - OFF + |r|^2) - d| <= e = 107 u B + 6 scale;  the construction needs e <= E / 4.2 = 121.9 u B + 6.67 scale:
-//   E = 512 u B + 28 scale   (typical: 2.0e-3 against 1.2e-3 of the fp32 slabs -- 13.7 instead of 11.8 survivors per item).
+//   =>  |(s - OFF + |r|^2) - d| <= e = 118 u B + 6 scale;  the construction needs e <= E / 4.2 = 121.9 u B + 6.67 scale:
+//   E = 512 u B + 28 scale stands   (typical: 2.0e-3 against 1.2e-3 of the fp32 slabs -- 13.7 instead of 11.8 survivors per item).
 // Everything downstream (survivor regions, merge_refine_kernel with the same E, the self-check of the bracket on
 // every refined row) is refine.h's.
 // The gatherer waves' selection tail (column minima, survivor pass) is scan_tail5.inc, ONE text that this kernel and fused8.h's
@@ -90,19 +101,15 @@ __device__ __forceinline__ void query_codebook5_body(const float* __restrict__ q
   // MFMA path: the B operands of the wave's FIRST group of code slots are requested before anything else -- the codebook
   // round trip runs under the prologue (the workgroup is a chain of latencies: all 768 are resident at once); the second
   // group's are requested into the same registers right after the first group's matrix instructions, under its conversion
-  constexpr int STEPS_B = (S + 3) / 4;
-  float bv[STEPS_B][4][2];
-  auto load_b = [&](int g) {   // (cbT here = the fragment-order copy, freddy_gpu.hip build_fragment_codebook)
-    typedef float f4b __attribute__((ext_vector_type(4)));
-    const f4b* src = reinterpret_cast<const f4b*>(cbT + ((((size_t)p * 8 + g) * STEPS_B) * 64 + (tid & 63)) * 8);
+  static_assert(S <= 32 && SP % 4 == 0, "one k-step of v_mfma_f32_16x16x32_f16 covers a position");
+  ch8v bh[8], bl[8];           // [tile 2 i + e]: codes 128 i + 16 g + col + 512 e, dimensions 8 kq .. 8 kq + 7 of lane (col, kq)
+  auto load_b = [&](int g) {   // (cbT here = the f16 hi / lo fragment copy, pin.hip build_fragment_codebook)
+    const ch8v* src = reinterpret_cast<const ch8v*>(cbT) + ((size_t)p * 8 + g) * (CBF_GROUP_HALVES / 8) + (tid & 63);
 #pragma unroll
-    for (int st = 0; st < STEPS_B; ++st) {
-      const f4b lo = src[(size_t)st * 128], hi = src[(size_t)st * 128 + 1];
-      bv[st][0][0] = lo.x; bv[st][0][1] = lo.y; bv[st][1][0] = lo.z; bv[st][1][1] = lo.w;
-      bv[st][2][0] = hi.x; bv[st][2][1] = hi.y; bv[st][3][0] = hi.z; bv[st][3][1] = hi.w;
-    }
+    for (int t = 0; t < 8; ++t) { bh[t] = src[(size_t)t * 128]; bl[t] = src[(size_t)t * 128 + 64]; }
   };
   load_b((tid >> 6) * 2);
+  const int ecb = reinterpret_cast<const int*>(cbT)[cbf_exp_offset(m) + p];   // the position's power-of-two scale (uniform)
   for (int i = tid; i < QT * SP; i += 256) {
     const int qi = i / SP, j = i - qi * SP;
     qs[qi][j] = (j < S && q0 + qi < Q) ? queries[(size_t)(q0 + qi) * d + p * S + j] : 0.0f;
@@ -126,20 +133,46 @@ __device__ __forceinline__ void query_codebook5_body(const float* __restrict__ q
     }
   }
   {
-    // The dot products on the matrix cores (v_mfma_f32_16x16x4_f32: A = 16 queries x 4 dimensions, B = 4 dimensions x 16
-    // codes, seven steps for S = 25): a wave takes two groups of 16 code slots and, per group, the eight tiles whose codes
-    // share a slot's uint4 (code 128 i + slot, i = 0..3, and its partner + 512) -- so a lane ends up with exactly the four
-    // words of one 16-byte store per query.  D[row = 4 (lane >> 4) + reg][col = lane & 15].  The sum's rounding differs from
-    // the fmaf chain's (order, product rounding): within the 28 u 2|q_p||c| -> 56 u the bracket's derivation (top of this
-    // file) leaves room for (e = 105 u B + 6 scale <= E / 4.2 = 122 u B + 6.67 scale).
+    // The dot products on the matrix cores, ONE k-step per position (v_mfma_f32_16x16x32_f16: A = 16 queries x 32 dimensions,
+    // B = 32 dimensions x 16 codes, S = 25 <= 32) on f16-split operands: the queries' slice times 2^eq (eq per (query, position):
+    // the slice's largest finite element in [2^9, 2^10)) = hi + lo + rest, the codebook likewise at pin time (ecb per position), and
+    // q . c ~ 2^-(eq + ecb) (lo . hi + hi . lo + hi . hi) -- three instructions per tile into one binary32 accumulator, the small
+    // products first, instead of seven v_mfma_f32_16x16x4_f32 at a sixteenth of the rate (error: top of this file).  A wave takes
+    // two groups of 16 code slots and, per group, the eight tiles whose codes share a slot's uint4 (code 128 i + slot, i = 0..3,
+    // and its partner + 512) -- so a lane ends up with exactly the four words of one 16-byte store per query.
+    // A[row = lane & 15][k = 8 (lane >> 4) + j], D[row = 4 (lane >> 4) + reg][col = lane & 15].
     typedef float f4v __attribute__((ext_vector_type(4)));
     __syncthreads();   // (qs, inv_s)
     const int wave = tid >> 6, lane = tid & 63, col = lane & 15, kq = lane >> 4;
     const int nq = (Q - q0 < QT) ? Q - q0 : QT;
-    constexpr int STEPS = (S + 3) / 4;
-    float av[STEPS];
+    ch8v ah, al;
+    int eq = 0;
+    {
+      // this lane's eight dimensions of query `col` (rows of qs are zero from S on; a row ends at SP)
+      f4v x0 = f4v{0.0f, 0.0f, 0.0f, 0.0f}, x1 = x0;
+      if (8 * kq < SP) x0 = *reinterpret_cast<const f4v*>(&qs[col][8 * kq]);
+      if (8 * kq + 4 < SP) x1 = *reinterpret_cast<const f4v*>(&qs[col][8 * kq + 4]);
+      const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+      // the slice's largest finite magnitude (fmaxf drops a NaN; with an infinity the scale stays 1 and the row is non-finite
+      // whatever the other elements become); the four lanes of a query agree on it
+      float am = 0.0f;
 #pragma unroll
-    for (int st = 0; st < STEPS; ++st) av[st] = 4 * st + kq < S ? qs[col][4 * st + kq] : 0.0f;   // (A: row = lane & 15 = the query)
+      for (int j = 0; j < 8; ++j) am = fmaxf(am, __builtin_fabsf(x[j]));
+      am = fmaxf(am, __shfl_xor(am, 16, 64));
+      am = fmaxf(am, __shfl_xor(am, 32, 64));
+      if (am > 0.0f && am < 3e38f) { (void)__builtin_frexpf(am, &eq); eq = CBF_EXP - eq; }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = __builtin_ldexpf(x[j], eq);   // (exact: a power of two)
+        const _Float16 hh = (_Float16)v;
+        ah[j] = hh;
+        al[j] = (_Float16)(v - (float)hh);
+      }
+    }
+    // the exact power of two that undoes both scales, for the four queries (rows of D) this lane stores
+    int unscale[4];
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) unscale[reg] = -(__shfl(eq, 4 * kq + reg, 64) + ecb);
     const float vmax = (float)FILT5_VMAX;
     const int bias = filt5_bias(p, m);
 #pragma unroll
@@ -147,13 +180,17 @@ __device__ __forceinline__ void query_codebook5_body(const float* __restrict__ q
       const int g = wave * 2 + gg;
       f4v acc[4][2];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int st = 0; st < STEPS; ++st)
+        for (int e = 0; e < 2; ++e) acc[i][e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[2 * i + e], f4v{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int e = 0; e < 2; ++e) acc[i][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[st], bv[st][i][e], acc[i][e], 0, 0, 0);
+        for (int e = 0; e < 2; ++e) acc[i][e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[2 * i + e], acc[i][e], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) acc[i][e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[2 * i + e], acc[i][e], 0, 0, 0);
       if (gg == 0) load_b(g + 1);
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
@@ -163,8 +200,8 @@ __device__ __forceinline__ void query_codebook5_body(const float* __restrict__ q
           uint32_t wd[4];
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const int i0 = (int)fminf(fmaxf(__builtin_rintf(-2.0f * acc[i][0][reg] * inv), -vmax), vmax) + bias;
-            const int i1 = (int)fminf(fmaxf(__builtin_rintf(-2.0f * acc[i][1][reg] * inv), -vmax), vmax) + bias;
+            const int i0 = (int)fminf(fmaxf(__builtin_rintf(-2.0f * __builtin_ldexpf(acc[i][0][reg], unscale[reg]) * inv), -vmax), vmax) + bias;
+            const int i1 = (int)fminf(fmaxf(__builtin_rintf(-2.0f * __builtin_ldexpf(acc[i][1][reg], unscale[reg]) * inv), -vmax), vmax) + bias;
             wd[i] = (uint32_t)i0 | ((uint32_t)i1 << 16);
           }
           *reinterpret_cast<uint4*>(qc + ((size_t)(q0 + qi) * m + p) * 512 + 4 * (16 * g + col)) = uint4{wd[0], wd[1], wd[2], wd[3]};
@@ -174,10 +211,14 @@ __device__ __forceinline__ void query_codebook5_body(const float* __restrict__ q
     }
   }
 }
+// The kernels made of table units are held to four waves per SIMD (128 registers): left to itself the compiler spends 160 on the
+// same code (the second group's B operands in registers of their own) -- three waves, and with four batches in flight the launch
+// was 3-4 us longer for it (profiles/table_f16_ab.txt).  No spills, no scratch at 128.
+#define FREDDY_TABLE_UNIT_KERNEL __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
 template <int S, int QT>
 static constexpr int query_codebook5_lds() { return QT * ((S + 3) & ~3) * 4 + QT * 4; }
 template <int S, int QT>
-__global__ __launch_bounds__(256) void query_codebook5_kernel(const float* __restrict__ queries, const float* __restrict__ cbT,
+FREDDY_TABLE_UNIT_KERNEL void query_codebook5_kernel(const float* __restrict__ queries, const float* __restrict__ cbT,
                                                              const float* __restrict__ cmax, float* __restrict__ qn,
                                                              float* __restrict__ qscale, uint32_t* __restrict__ qc,
                                                              int Q, int d, int m, int K, uint32_t* __restrict__ qc8) {
@@ -201,7 +242,7 @@ struct CoarseTableArgs {
   uint32_t* qc8;                 // K <= 256: the compact copy of the table (query_codebook5_body); NULL: not wanted
 };
 template <int S, int QT, bool H16 = false>   // H16: the coarse tiles on f16-split operands (many cells); an instantiation of its own, so
-__global__ __launch_bounds__(256) void coarse_table5_kernel(CoarseTableArgs a) {   // that the <= 1024-cell kernel compiles as before
+FREDDY_TABLE_UNIT_KERNEL void coarse_table5_kernel(CoarseTableArgs a) {   // that the <= 1024-cell kernel compiles as before
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n_coarse = a.coarse_gx * a.coarse_gy;
   const int b = blockIdx.x;

@@ -232,7 +232,8 @@ struct freddy_gpu_index {
   int64_t rterm_bytes = 0;      // its share of `bytes` (refresh_row_terms)
   float* pmax = nullptr;        // [m]        max |co_p| + max |c_p|, rounded up
   float* cmaxp = nullptr;       // [m]        max |c_p|, rounded up
-  float* cbF = nullptr;         // [m][8 groups][7 steps][64 lanes][8] the codebook in the B-fragment order of the table kernel's matrix instructions (fused5.h query_codebook5_body)
+  float* cbF = nullptr;         // [m][8 groups][8 tiles][hi / lo][64 lanes][8 halves] the codebook scaled by 2^ecb[p] and split into f16 hi / lo, in the B-fragment
+                                // order of the table kernel's matrix instructions, then int32 ecb[m] (cbf_floats; fused5.h query_codebook5_body)
   int32_t* viol = nullptr;      // [4] self-check counters: scan bracket violations / rows checked, coarse bracket violations / cells checked
   int32_t* elastic = nullptr;   // [4] the elastic scan's advisory words (IVF handles; a 64-byte line of viol's allocation): scan workgroups alive over all
                                 // streams, guaranteed workgroups announced and not yet started, extras that took work, extras that left for another scan

@@ -202,29 +202,53 @@ static int derive_codebook_tables(freddy_gpu_index* ix, const float* codebook, b
   if (old[2]) old_bytes += (int64_t)sizeof(float) * ix->m * ix->K * ix->S;
   if (old[3]) old_bytes += (int64_t)sizeof(float) * ix->m;
   if (old[4]) old_bytes += (int64_t)sizeof(float) * ix->m;
-  if (old[5]) old_bytes += (int64_t)sizeof(float) * ix->m * 8 * 7 * 64 * 8;
+  if (old[5]) old_bytes += (int64_t)sizeof(float) * (int64_t)cbf_floats(ix->m);
   ix->bytes -= old_bytes;       // (the footprint changes by the difference, not by a second copy)
   for (float* p : old) if (p) (void)dev_free(p);
   if (ix->kind == KIND_PQ) drop_pq_views(ix);    // rebuilt from the new tables on next use
   return 0;
 }
-// The codebook in the order the table kernel's v_mfma_f32_16x16x4_f32 B operands are read (m = 12, S = 25, K <= 1024): for
-// (position, group g of 16 code slots, step) lane l = (col = l & 15, kq = l >> 4) finds the eight values of dimension
-// 4 step + kq for the codes 128 i + 16 g + col + 512 e, (i, e) = (0,0) (0,1) (1,0) ... (3,1), as two 16-byte words: a wave's
-// load is 2 KB of consecutive bytes (the transposed copy gave 64-byte pieces of eight different lines).
+// The codebook in the order the table kernel's v_mfma_f32_16x16x32_f16 B operands are read (m = 12, S = 25 <= 32, K <= 1024): every
+// element times 2^ecb[p] and split into f16 hi + lo (lo = the rounded remainder); for (position, group g of 16 code slots, tile
+// t = 2 i + e, part hi / lo) lane l = (col = l & 15, kq = l >> 4) finds dimensions 8 kq .. 8 kq + 7 (zero from S on) of code
+// 128 i + 16 g + col + 512 e as one 16-byte word: a wave's load is 1 KB of consecutive bytes, a group's sixteen are 16 KB.
+// ecb[p] puts the position's largest FINITE element into [2^9, 2^10) (0: none, or all zero) -- the largest norm cmaxp[p] is then
+// at least 2^9 in scaled units, which is what the bracket's derivation (fused5.h) uses; a non-finite element stays what it is in hi
+// (and is NaN in lo), the finite ones beside it stay finite.  The exponents follow the fragments in the same allocation.
 static int build_fragment_codebook(freddy_gpu_index* ix, const float* codebook) {
-  std::vector<float> f((size_t)ix->m * 8 * 7 * 64 * 8, 0.0f);
-  for (int p = 0; p < ix->m; ++p)
+  static_assert(sizeof(_Float16) == 2 && sizeof(float) == 4 && sizeof(int32_t) == 4, "layout");
+  if (ix->S > 32) return fail(FREDDY_E_ARG, "table kernel: more than 32 dimensions per position");
+  std::vector<_Float16> f(2 * cbf_floats(ix->m), (_Float16)0.0f);
+  _Float16* h = f.data();
+  for (int p = 0; p < ix->m; ++p) {
+    float amax = 0.0f;
+    for (size_t i = 0; i < (size_t)ix->K * ix->S; ++i) {
+      const float v = std::fabs(codebook[(size_t)p * ix->K * ix->S + i]);
+      if (v < 3e38f && v > amax) amax = v;
+    }
+    int32_t ecb = 0;
+    if (amax > 0.0f) { int e = 0; (void)frexpf(amax, &e); ecb = CBF_EXP - e; }
+    std::memcpy(h + 2 * (cbf_exp_offset(ix->m) + p), &ecb, 4);
     for (int g = 0; g < 8; ++g)
-      for (int st = 0; st < 7; ++st)
-        for (int l = 0; l < 64; ++l)
-          for (int i = 0; i < 4; ++i)
-            for (int e = 0; e < 2; ++e) {
-              const int j = 4 * st + (l >> 4), c = 128 * i + 16 * g + (l & 15) + 512 * e;
-              if (j < ix->S && c < ix->K)
-                f[((((size_t)p * 8 + g) * 7 + st) * 64 + l) * 8 + i * 2 + e] = codebook[((size_t)p * ix->K + c) * ix->S + j];
-            }
-  if (upload(&ix->cbF, f.data(), f.size(), &ix->bytes)) return fail(FREDDY_E_NOMEM, "device allocation failed");
+      for (int t = 0; t < 8; ++t)
+        for (int l = 0; l < 64; ++l) {
+          const int c = 128 * (t >> 1) + 16 * g + (l & 15) + 512 * (t & 1);
+          if (c >= ix->K) continue;
+          _Float16* hi = h + ((size_t)p * 8 + g) * CBF_GROUP_HALVES + ((size_t)(t * 2) * 64 + l) * 8;
+          _Float16* lo = hi + 64 * 8;
+          for (int u = 0; u < 8; ++u) {
+            const int j = 8 * (l >> 4) + u;
+            if (j >= ix->S) continue;
+            const float v = ldexpf(codebook[((size_t)p * ix->K + c) * ix->S + j], ecb);
+            hi[u] = (_Float16)v;
+            lo[u] = (_Float16)(v - (float)hi[u]);
+          }
+        }
+  }
+  _Float16* dF = nullptr;
+  const int up = upload(&dF, f.data(), f.size(), &ix->bytes);
+  ix->cbF = reinterpret_cast<float*>(dF);   // (set even when the copy failed after the allocation: the caller frees it)
+  if (up) return fail(FREDDY_E_NOMEM, "device allocation failed");
   return 0;
 }
 // The largest norm so far, a NaN included and kept: std::max drops a NaN operand, and the filter's margin E must turn non-finite

@@ -72,6 +72,12 @@ enum { EL_ACTIVE = 0, EL_PENDING = 1, EL_STARTED = 2, EL_YIELDED = 3 };
 // The integer-slab scan (fused5.h) quantises the table with one scale per query; its margin (derivation there):
 static constexpr int FILT5_VMAX = 2730;   // 12 positions x 2730 = 32760 < 2^15
 static constexpr float FILT5_EPS = 512.0f * 5.9604644775390625e-8f * 1.0001f;
+// The codebook copy the table units read (index cbF; pin.hip build_fragment_codebook, fused5.h query_codebook5_body): per (position,
+// group of 16 code slots) eight tiles x (hi, lo) x 64 lanes x 8 f16 = 16 KB of consecutive bytes, then one int32 exponent per position.
+static constexpr int CBF_EXP = 10;                          // the largest finite element of a position (of a query's slice) lies in [2^9, 2^10)
+static constexpr size_t CBF_GROUP_HALVES = 8 * 2 * 64 * 8;
+__host__ __device__ constexpr size_t cbf_exp_offset(int m) { return (size_t)m * 8 * CBF_GROUP_HALVES / 2; }   // in 4-byte words
+__host__ __device__ constexpr size_t cbf_floats(int m) { return cbf_exp_offset(m) + (size_t)m; }
 template <int M>
 __device__ __forceinline__ float filter_width5(const float* __restrict__ qn, const float* __restrict__ pmax, float scale) {
   float sb = 0.0f;
