@@ -90,6 +90,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dot_chain.h"
 #include "exact.h"
 #include "exact2.h"
 #include "wave_topk.h"
@@ -275,6 +276,7 @@ __global__ __launch_bounds__(AN_WG) void an_scan_kernel(AnScanArgs a) {
     float acc[QC];
 #pragma unroll
     for (int c = 0; c < QC; ++c) acc[c] = 0.0f;
+    // (dot_chain.h's stream_row, kept in place for registers: profiles/HISTORY.md, the dot_chain.h entry)
     constexpr int DB = 8;
     float xn[DB];
 #pragma unroll
@@ -316,26 +318,6 @@ __global__ __launch_bounds__(AN_WG) void an_scan_kernel(AnScanArgs a) {
 }
 
 // ---- pair direction ------------------------------------------------------------------------------------------------------
-// A row's d values (lane = row of a 64-row block, xrow = the block's base + lane) handed to f(i, x) in ascending i, eight loads
-// in flight ahead of their use.
-template <class F>
-__device__ __forceinline__ void an_stream_row(const float* __restrict__ xrow, int d, F&& f) {
-  constexpr int DB = 8;
-  float xn[DB];
-#pragma unroll
-  for (int u = 0; u < DB; ++u) xn[u] = (u < d) ? xrow[(size_t)u * 64] : 0.0f;
-  for (int i0 = 0; i0 < d; i0 += DB) {
-    float xc[DB];
-#pragma unroll
-    for (int u = 0; u < DB; ++u) xc[u] = xn[u];
-#pragma unroll
-    for (int u = 0; u < DB; ++u) xn[u] = (i0 + DB + u < d) ? xrow[(size_t)(i0 + DB + u) * 64] : 0.0f;
-#pragma unroll
-    for (int u = 0; u < DB; ++u)
-      if (i0 + u < d) f(i0 + u, xc[u]);
-  }
-}
-
 // The columns of the pair-direction scan, one workgroup (one wave) per analogy: out[a][0][d] = A = vec_normalize(v1 - v2),
 // out[a][1][d] = v3.  The sum of squares is the reference's sequential chain: one lane walks it.
 __global__ __launch_bounds__(64) void an_pair_columns_kernel(const float* __restrict__ rows, int d, const int32_t* __restrict__ in_rows,
@@ -391,14 +373,14 @@ __global__ __launch_bounds__(AN_WG) void an_pair_scan_kernel(AnScanArgs a) {
     float sq[AT], len[AT], acc[AT];
 #pragma unroll
     for (int t = 0; t < AT; ++t) { sq[t] = 0.0f; acc[t] = 0.0f; }
-    an_stream_row(xrow, d, [&](int i, float x) {            // sweep 1: vec_normalize_bytea's sum of squares of v3 - v4
+    stream_row(xrow, d, [&](int i, float x) {            // sweep 1: vec_normalize_bytea's sum of squares of v3 - v4
       const float* q = qs + i * QC + AT;
 #pragma unroll
       for (int t = 0; t < AT; ++t) { const float df = q[t] - x; const float p = df * df; sq[t] = sq[t] + p; }
     });
 #pragma unroll
     for (int t = 0; t < AT; ++t) len[t] = (float)sqrt((double)sq[t]);                            // core_functions.c:259
-    an_stream_row(xrow, d, [&](int i, float x) {            // sweep 2: the cosine chain over A and (v3 - v4) / length
+    stream_row(xrow, d, [&](int i, float x) {            // sweep 2: the cosine chain over A and (v3 - v4) / length
       const float* q = qs + i * QC;
 #pragma unroll
       for (int t = 0; t < AT; ++t) {

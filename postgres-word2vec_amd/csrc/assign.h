@@ -12,15 +12,8 @@
 //       trip, then 1 - y / 2), first under "key DESC, query index ASC".
 //
 // assign_exact_kernel: one lane per target, one wave per workgroup (64 targets; the waves share nothing, so nothing is gained by
-// larger workgroups and a small set still spreads over n / 64 CUs).  Ids are resolved by binary search over the handle's ascending
-// device ids (as pv.h does).  The rows are a gather of 4 d-byte rows; pv_rerank's staging: per step 64 targets x AS_DCH = 32
-// dimensions are read with 16-byte loads (8 consecutive lanes = 128 contiguous bytes of one row; a scalar path for d % 4 != 0)
-// and stored transposed into the tile [32][65] (dimension-major: stores hit banks 4 * piece + target (mod 32), reads are
-// lane-consecutive -- both conflict free).  Beside it a tile of AS_QT = 16 queries x 32 dimensions, [32][16], loaded as 16-byte
-// pieces too (16 consecutive lanes = one piece of each of the 16 queries) and stored with its rows permuted (as_qrow) so that a
-// store's 64 lanes write 64 consecutive floats -- conflict free as well.  Every lane reads the same 16 consecutive floats of a
-// dimension (four broadcast ds_read_b128), multiplies them by its own row element and adds into 16 accumulators in registers -- a row piece is loaded once per 16 queries, and each chain stays sequential in its lane.  (The bit
-// contract fixes the summation order, so the matrix cores cannot produce these values.)
+// larger workgroups and a small set still spreads over n / 64 CUs).  Ids are resolved by row_of_id.  The rows are a gather of 4 d-byte
+// rows: dot_chain.h's gather tile with its tile of 16 queries beside it, all ten loads of a step issued before the first store.
 // LDS: 8 320 B + 2 048 B = 10 368 B static per workgroup of one wave (15 waves per CU by LDS); registers: 16 accumulators + 8
 // float4 of row pieces + 2 of query pieces in flight.  No workgroup reads what another wrote.
 //
@@ -37,38 +30,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dot_chain.h"
 #include "freddy_similarity.h"
 
 namespace freddy {
 
 static constexpr int AS_MAX_Q = 65536;     // queries per assign call
-static constexpr int AS_QT = 16;           // queries per tile of assign_exact_kernel
-static constexpr int AS_DCH = 32;          // dimensions per step
-static constexpr int AS_STRIDE = 65;       // floats per dimension of the row tile: 64 targets + 1
-static constexpr int AS_TILE = AS_DCH * AS_STRIDE;
-static constexpr int AS_QTILE = AS_DCH * AS_QT;
 static constexpr int AS_PQ_WG = 256;
-
-// the row of `id` in a table of N ascending ids, -1 if it has none
-__device__ __forceinline__ int32_t assign_row_of(const int32_t* __restrict__ ids, int64_t N, int32_t id) {
-  int64_t lo = 0, hi = N;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ids[mid] < id) lo = mid + 1; else hi = mid;
-  }
-  return (lo < N && ids[lo] == id) ? (int32_t)lo : -1;
-}
-
-// writes of the wave's lanes to its tiles become visible to its other lanes (pv.h pv_wave_sync)
-__device__ __forceinline__ void assign_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// The row of dimension j (of a step's 32) in the query tile: element c of the 16-byte piece p = j / 4 goes to row 8 c + p, so that
-// the lanes of one store -- 16 queries x 4 pieces, c fixed -- write rows p, p + 1, p + 2, p + 3: 64 consecutive floats.
-__device__ __forceinline__ constexpr int as_qrow(int j) { return (j & 3) * 8 + (j >> 2); }
 
 // PostgreSQL's float4 order as an unsigned number: ascending with the float, every NaN the one largest value; never 0
 __device__ __forceinline__ uint32_t assign_ord(float sim) {
@@ -90,75 +58,41 @@ struct AssignExactArgs {
 
 // (static: the header is included by two units, exact.hip launches it)
 static __global__ __launch_bounds__(64) void assign_exact_kernel(AssignExactArgs a) {
-  __shared__ __attribute__((aligned(16))) float tile[AS_TILE];     // [AS_DCH][AS_STRIDE]
-  __shared__ __attribute__((aligned(16))) float qs[AS_QTILE];      // [AS_DCH][AS_QT]
+  __shared__ __attribute__((aligned(16))) float tile[TILE_FLOATS];     // [TILE_DCH][TILE_STRIDE]
+  __shared__ __attribute__((aligned(16))) float qs[TILE_QFLOATS];      // [TILE_DCH][TILE_QT]
   const int lane = threadIdx.x, d = a.d;
   const int i = blockIdx.x * 64 + lane;
   int32_t row = -1;
-  if (i < a.n_targets) row = assign_row_of(a.vec_ids, a.N, a.targets[i]);
+  if (i < a.n_targets) row = row_of_id(a.vec_ids, a.N, a.targets[i]);
   uint32_t best_ord = 0;   // (no similarity's image)
   int32_t best_q = -1;
   float best_sim = -__builtin_huge_valf();
   if (__ballot(row >= 0) != 0ull) {
-    const bool vec4 = (d & 3) == 0;   // every row and query 16-byte aligned and no piece crosses its end
-    for (int q0 = 0; q0 < a.Q; q0 += AS_QT) {
-      float acc[AS_QT];
+    const bool vec4 = (d & 3) == 0;
+    for (int q0 = 0; q0 < a.Q; q0 += TILE_QT) {
+      float acc[TILE_QT];
 #pragma unroll
-      for (int t = 0; t < AS_QT; ++t) acc[t] = 0.0f;
-      for (int c0 = 0; c0 < d; c0 += AS_DCH) {
-        const int nd = (d - c0 < AS_DCH) ? d - c0 : AS_DCH;
+      for (int t = 0; t < TILE_QT; ++t) acc[t] = 0.0f;
+      for (int c0 = 0; c0 < d; c0 += TILE_DCH) {
+        const int nd = (d - c0 < TILE_DCH) ? d - c0 : TILE_DCH;
         float4 v[8], qv[2];
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {   // piece (it * 64 + lane): target (it * 8 + lane / 8), dimensions c0 + 4 (lane % 8) ..
-          const int cl = it * 8 + (lane >> 3), dim0 = (lane & 7) * 4;
-          const int32_t r = __shfl(row, cl, 64);
-          v[it] = float4{0.0f, 0.0f, 0.0f, 0.0f};
-          if (r >= 0 && dim0 < nd) {
-            const float* src = a.rows + (size_t)r * d + c0 + dim0;
-            if (vec4) v[it] = *reinterpret_cast<const float4*>(src);
-            else {
-              v[it].x = src[0];
-              if (dim0 + 1 < nd) v[it].y = src[1];
-              if (dim0 + 2 < nd) v[it].z = src[2];
-              if (dim0 + 3 < nd) v[it].w = src[3];
-            }
-          }
-        }
+        for (int it = 0; it < 8; ++it) v[it] = tile_row_piece(a.rows, row, it, lane, d, c0, nd, vec4);
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {   // query (q0 + lane % 16), dimensions c0 + 4 (it * 4 + lane / 16) ..
-          const int t = lane & 15, dim0 = (it * 4 + (lane >> 4)) * 4;
-          qv[it] = float4{0.0f, 0.0f, 0.0f, 0.0f};
-          if (q0 + t < a.Q && dim0 < nd) {
-            const float* src = a.queries + (size_t)(q0 + t) * d + c0 + dim0;
-            if (vec4) qv[it] = *reinterpret_cast<const float4*>(src);
-            else {
-              qv[it].x = src[0];
-              if (dim0 + 1 < nd) qv[it].y = src[1];
-              if (dim0 + 2 < nd) qv[it].z = src[2];
-              if (dim0 + 3 < nd) qv[it].w = src[3];
-            }
-          }
-        }
+        for (int it = 0; it < 2; ++it) qv[it] = tile_query_piece(a.queries, a.Q, q0, it, lane, d, c0, nd, vec4);
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int cl = it * 8 + (lane >> 3), dim0 = (lane & 7) * 4;
-          float* dst = tile + dim0 * AS_STRIDE + cl;
-          dst[0] = v[it].x; dst[AS_STRIDE] = v[it].y; dst[2 * AS_STRIDE] = v[it].z; dst[3 * AS_STRIDE] = v[it].w;
-        }
+        for (int it = 0; it < 8; ++it) tile_store_row_piece(tile, v[it], it, lane);
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {   // piece p, element c (dimension 4 p + c) -> row as_qrow(4 p + c) = 8 c + p
-          float* dst = qs + (it * 4 + (lane >> 4)) * AS_QT + (lane & 15);
-          dst[0] = qv[it].x; dst[8 * AS_QT] = qv[it].y; dst[16 * AS_QT] = qv[it].z; dst[24 * AS_QT] = qv[it].w;
-        }
-        assign_wave_sync();
-        const float* col = tile + lane;
-        if (nd == AS_DCH) {
+        for (int it = 0; it < 2; ++it) tile_store_query_piece(qs, qv[it], it, lane);
+        wave_lds_sync();
+        const float* col = tile + lane;   // (the 16-accumulator walk, kept in place for registers: dot_chain.h)
+        if (nd == TILE_DCH) {
 #pragma unroll
-          for (int j = 0; j < AS_DCH; ++j) {
-            const float x = col[j * AS_STRIDE];
+          for (int j = 0; j < TILE_DCH; ++j) {
+            const float x = col[j * TILE_STRIDE];
 #pragma unroll
-            for (int t4 = 0; t4 < AS_QT / 4; ++t4) {
-              const float4 qq = *reinterpret_cast<const float4*>(qs + as_qrow(j) * AS_QT + t4 * 4);
+            for (int t4 = 0; t4 < TILE_QT / 4; ++t4) {
+              const float4 qq = *reinterpret_cast<const float4*>(qs + tile_qrow(j) * TILE_QT + t4 * 4);
               float p;
               p = qq.x * x; acc[t4 * 4 + 0] = acc[t4 * 4 + 0] + p;   // core_functions.c:77: scalar += v1[i] * v2[i]
               p = qq.y * x; acc[t4 * 4 + 1] = acc[t4 * 4 + 1] + p;
@@ -168,10 +102,10 @@ static __global__ __launch_bounds__(64) void assign_exact_kernel(AssignExactArgs
           }
         } else {
           for (int j = 0; j < nd; ++j) {
-            const float x = col[j * AS_STRIDE];
+            const float x = col[j * TILE_STRIDE];
 #pragma unroll
-            for (int t4 = 0; t4 < AS_QT / 4; ++t4) {
-              const float4 qq = *reinterpret_cast<const float4*>(qs + as_qrow(j) * AS_QT + t4 * 4);
+            for (int t4 = 0; t4 < TILE_QT / 4; ++t4) {
+              const float4 qq = *reinterpret_cast<const float4*>(qs + tile_qrow(j) * TILE_QT + t4 * 4);
               float p;
               p = qq.x * x; acc[t4 * 4 + 0] = acc[t4 * 4 + 0] + p;
               p = qq.y * x; acc[t4 * 4 + 1] = acc[t4 * 4 + 1] + p;
@@ -180,10 +114,10 @@ static __global__ __launch_bounds__(64) void assign_exact_kernel(AssignExactArgs
             }
           }
         }
-        assign_wave_sync();
+        wave_lds_sync();
       }
 #pragma unroll
-      for (int t = 0; t < AS_QT; ++t) {   // ascending query index: only a strictly larger similarity replaces the best
+      for (int t = 0; t < TILE_QT; ++t) {   // ascending query index: only a strictly larger similarity replaces the best
         const uint32_t o = assign_ord(acc[t]);
         if (q0 + t < a.Q && o > best_ord) { best_ord = o; best_q = q0 + t; best_sim = acc[t]; }
       }
@@ -222,7 +156,7 @@ __global__ __launch_bounds__(AS_PQ_WG) void assign_pq_kernel(AssignPqArgs a) {
     const int i = (blockIdx.x * RPT + r) * AS_PQ_WG + tid;
     row[r] = -1; bq[r] = -1; bkey[r] = -__builtin_huge_valf(); bdist[r] = a.sentinel;
     if (i < a.n_targets) {
-      row[r] = assign_row_of(a.ids, a.N, a.targets[i]);
+      row[r] = row_of_id(a.ids, a.N, a.targets[i]);
       if (!a.first) { bq[r] = a.out_query[i]; bkey[r] = a.out_sim[i]; bdist[r] = a.best_dist[i]; }
     }
 #pragma unroll

@@ -2,7 +2,7 @@
 // whole k-means of cluster_exact / cluster_pq is one call (freddy_gpu_cluster, exact.hip; the contract: include/freddy_gpu.h):
 //
 //   cluster_init_kernel    once per call.  One lane per position: the row of its token id in the vector handle (binary search over
-//       the handle's ascending device ids, assign_row_of), clusters[i] = 0, and the smallest position whose id has no row into the
+//       the handle's ascending device ids, row_of_id), clusters[i] = 0, and the smallest position whose id has no row into the
 //       flag word (an unsigned atomic minimum; the word starts at 0xffffffff).  kc further workgroups, one per centroid: the row of
 //       token pick(n, draws[I]) copied into centroid I, lens[I] = 0.  (That workgroup resolves its own id: nothing in this kernel
 //       reads what another workgroup wrote.)
@@ -63,7 +63,7 @@ static __global__ __launch_bounds__(CL_WG) void cluster_init_kernel(ClusterInitA
   if (blockIdx.x < a.pos_blocks) {
     const int64_t i = (int64_t)blockIdx.x * CL_WG + tid;
     if (i < a.n) {
-      const int32_t r = assign_row_of(a.vec_ids, a.N, a.token_ids[i]);
+      const int32_t r = row_of_id(a.vec_ids, a.N, a.token_ids[i]);
       a.row_of[i] = r;
       a.clusters[i] = 0;
       if (r < 0) atomicMin(a.flag, (uint32_t)i);
@@ -72,7 +72,7 @@ static __global__ __launch_bounds__(CL_WG) void cluster_init_kernel(ClusterInitA
   }
   const int I = (int)(blockIdx.x - a.pos_blocks);
   const int32_t pos = freddy_pick(a.n, a.draws[I]) - 1;
-  const int32_t r = assign_row_of(a.vec_ids, a.N, a.token_ids[pos]);   // (the same in every lane)
+  const int32_t r = row_of_id(a.vec_ids, a.N, a.token_ids[pos]);   // (the same in every lane)
   if (tid == 0) a.lens[I] = 0;
   for (int j = tid; j < a.d; j += CL_WG) a.centroids[(size_t)I * a.d + j] = r >= 0 ? a.rows[(size_t)r * a.d + j] : 0.0f;
 }

@@ -96,6 +96,7 @@ __global__ __launch_bounds__(EX_WG) void exact_scan_kernel(ExactArgs a) {
     v2f acc[QT / 2];
 #pragma unroll
     for (int t = 0; t < QT / 2; ++t) acc[t] = v2f{0.0f, 0.0f};
+    // (dot_chain.h's stream_row, kept in place for registers: profiles/HISTORY.md, the dot_chain.h entry)
     constexpr int DB = 8;   // row values fetched DB dimensions ahead
     float xn[DB];
 #pragma unroll

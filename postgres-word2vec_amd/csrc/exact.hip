@@ -1289,8 +1289,8 @@ static int sim_matrix_passes(freddy_gpu_index* ix, const int32_t* a_ids, const f
   hipStream_t s = ix->stream;
   // rows of A per pass: the block within the budget, a multiple of 16 rows (16 at least, whatever the budget)
   const size_t budget = ix->tune.similarity_pass_bytes > 0 ? (size_t)ix->tune.similarity_pass_bytes : SIM_PASS_BYTES;
-  int64_t rows = (int64_t)(budget / (sizeof(float) * (size_t)nb)) / SIM_AT * SIM_AT;
-  rows = std::max<int64_t>(SIM_AT, std::min<int64_t>(rows, SIM_PASS_ROWS));
+  int64_t rows = (int64_t)(budget / (sizeof(float) * (size_t)nb)) / TILE_QT * TILE_QT;
+  rows = std::max<int64_t>(TILE_QT, std::min<int64_t>(rows, SIM_PASS_ROWS));
   if (rows > na) rows = na;
   if (ws->w_sub_rows.ensure(sizeof(int32_t) * (size_t)nb) || ws->w_sub_pos.ensure(sizeof(int32_t) * (size_t)nb) || ws->w_found.ensure((size_t)nb) ||
       ws->w_q.ensure(sizeof(float) * (size_t)rows * d) || ws->w_lut.ensure(sizeof(float) * (size_t)rows * nb))
@@ -1327,7 +1327,7 @@ static int sim_matrix_passes(freddy_gpu_index* ix, const int32_t* a_ids, const f
       HIP_TRY(hipMemcpyAsync(ws->w_q.p, a_vectors + (size_t)a0 * d, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, s));
     }
     // workgroups: 64 B rows x a range of A tiles; A is split only until the chip has about sixteen waves per CU to place
-    const int n_tiles = (n + SIM_AT - 1) / SIM_AT;
+    const int n_tiles = (n + TILE_QT - 1) / TILE_QT;
     SimMatrixArgs ma;
     ma.b_rows = ws->w_sub_pos.as<int32_t>(); ma.rows = ix->coarse; ma.a = ws->w_q.as<float>(); ma.known_a = a_ids ? ws->w_used.as<uint8_t>() : nullptr;
     ma.out = ws->w_lut.as<float>(); ma.na = n; ma.nb = nb; ma.d = d; ma.tiles_per_wg = sim_tiles_per_wg(ix->n_cus, n_tiles, nblk);

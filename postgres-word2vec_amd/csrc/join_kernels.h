@@ -2,6 +2,7 @@
 // front kernels, the target-list kernels, and join_query_kernel with its arguments (JoinArgs) and LDS layout (JOIN_LDS_ARRAYS).
 #pragma once
 
+#include "dot_chain.h"   // row_of_id
 #include "join_index.h"
 
 namespace freddy {
@@ -169,9 +170,7 @@ __global__ __launch_bounds__(256) void join_mark_kernel(const int32_t* __restric
     const int64_t c = (int64_t)id - ids[0];
     if (c >= 0 && c < N) r = c;
   } else {
-    int64_t lo = 0, hi = N;
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (ids[mid] < id) lo = mid + 1; else hi = mid; }
-    if (lo < N && ids[lo] == id) r = lo;
+    r = row_of_id(ids, N, id);
   }
   int32_t w = -1;
   if (r >= 0) {

@@ -2,36 +2,29 @@
 // k * pvf candidates an approximate search returned per query are re-ranked by cosine_similarity_bytea against the raw vectors
 // and the first k kept.  Stage one is the public search itself (freddy_gpu_ivfadc_search / freddy_gpu_pq_search at k * pvf, every
 // path of it); this header is stage two: one workgroup per query
-//   1. resolves the query's candidate ids to rows of the vector handle (binary search over its ascending device ids; the
+//   1. resolves the query's candidate ids to rows of the vector handle (row_of_id over its ascending device ids; the
 //      (-1, sentinel) fillers and ids without a row drop out -- and, for the approximate analogies of approx_analogy.h, the three
 //      ids of PvArgs::exclude),
 //   2. scores the rows: similarity = the binary32 chain "scalar += v1[i] * v2[i]", i ascending (core_functions.c:67-81), one lane
-//      per candidate.  A wave takes 64 candidates at a time and PV_DCH dimensions of them per step: the 64 row pieces are read
-//      from the row-major copy with 16-byte loads (8 consecutive lanes = 128 contiguous bytes of one row), stored transposed into
-//      the wave's LDS tile [PV_DCH][PV_STRIDE] (dimension-major), and every lane then walks its own column with the
-//      accumulator carried in a register across the steps,
+//      per candidate.  A wave takes 64 candidates at a time through dot_chain.h's gather tile, one tile per wave, and every lane
+//      walks its own column against the query in LDS with the accumulator carried in a register across the steps (chain1),
 //   3. sorts the keys (ordered similarity, row) -- exact.h's sim_key, the order of freddy_gpu_exact_search: similarity DESC,
 //      id ASC -- and writes the first k as (id, similarity), (-1, -inf) beyond the rows.
 // So a row of the result is bit for bit freddy_gpu_exact_search(vecs, q, 1, k, candidate ids of q).
 //
-// LDS: ds_write_b32 / ds_read_b32 bank = (address / 4) mod 32 within each half of the wave.  A store instruction writes, per
-// half, 4 candidates x 8 row pieces at tile[(4 * piece + j) * 65 + candidate]: banks 4 * piece + candidate (mod 32), all
-// different; a read is lane-consecutive.  Both are conflict free, which a stride of 64 would not be for the stores (8-way).
-// Budget per workgroup: P keys of 8 bytes (P = candidates padded to a power of two, <= 4096: 32 KiB) + waves x 8 320 B of tiles
+// LDS budget per workgroup: P keys of 8 bytes (P = candidates padded to a power of two, <= 4096: 32 KiB) + waves x 8 320 B of tiles
 // (4 waves: 32.5 KiB) + the query (d floats) -- 66 KiB at d = 300 with 4096 candidates, 2.2 KiB with up to 64 (one wave).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dot_chain.h"
 #include "exact.h"
 #include "wave_topk.h"
 
 namespace freddy {
 
 static constexpr int PV_MAX_CAND = 4096;   // k * pvf
-static constexpr int PV_DCH = 32;          // dimensions per step
-static constexpr int PV_STRIDE = 65;       // floats per dimension of a wave's tile: 64 candidates + 1 (see above)
-static constexpr int PV_TILE = PV_DCH * PV_STRIDE;
 
 struct PvArgs {
   const int32_t* cand;       // [Q][n_cand] stage one's ids (-1: filler)
@@ -51,15 +44,7 @@ static inline int pv_pad(int n) {
   while (p < n) p <<= 1;
   return p;
 }
-static inline size_t pv_lds_bytes(int NW, int P, int d) { return (size_t)P * sizeof(u64) + (size_t)NW * PV_TILE * sizeof(float) + (size_t)d * sizeof(float); }
-
-// writes of this wave's lanes to its tile become visible to its other lanes (the LDS executes a wave's accesses in order; the
-// fences keep the compiler from moving them across)
-__device__ __forceinline__ void pv_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+static inline size_t pv_lds_bytes(int NW, int P, int d) { return (size_t)P * sizeof(u64) + (size_t)NW * TILE_FLOATS * sizeof(float) + (size_t)d * sizeof(float); }
 
 // NW = 1: up to 64 candidates, the sort is wave_sort64; NW = 4: up to 4096, a bitonic sort in LDS.  EX: PvArgs::exclude is read
 // (a compile-time switch, so that the post-verification kernels below stay instruction for instruction what they were before the
@@ -69,8 +54,8 @@ __device__ __forceinline__ void pv_rerank_body(const PvArgs& a) {
   constexpr int T = NW * 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char pv_smem[];
   u64* keys = reinterpret_cast<u64*>(pv_smem);                              // [P]: the row of every candidate, then its key
-  float* tiles = reinterpret_cast<float*>(keys + a.P);                      // [NW][PV_DCH][PV_STRIDE]
-  float* qs = tiles + NW * PV_TILE;                                         // [d]
+  float* tiles = reinterpret_cast<float*>(keys + a.P);                      // [NW][TILE_DCH][TILE_STRIDE]
+  float* qs = tiles + NW * TILE_FLOATS;                                     // [d]
   __shared__ int sh_cnt[2];
   __shared__ int32_t sh_ex[3];
   const int q = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -90,12 +75,8 @@ __device__ __forceinline__ void pv_rerank_body(const PvArgs& a) {
       const int32_t id = a.cand[(size_t)q * a.n_cand + i];
       if (id >= 0) ++n_ids;
       if (id >= 0 && id != ex0 && id != ex1 && id != ex2) {
-        int64_t lo = 0, hi = a.N;
-        while (lo < hi) {
-          const int64_t mid = (lo + hi) >> 1;
-          if (a.vec_ids[mid] < id) lo = mid + 1; else hi = mid;
-        }
-        if (lo < a.N && a.vec_ids[lo] == id) { row = (int32_t)lo; ++n_rows; }
+        const int32_t r = row_of_id(a.vec_ids, a.N, id);
+        if (r >= 0) { row = r; ++n_rows; }
       }
     }
     keys[i] = (u64)(uint32_t)row;
@@ -105,54 +86,23 @@ __device__ __forceinline__ void pv_rerank_body(const PvArgs& a) {
   for (int i = tid; i < d; i += T) qs[i] = a.queries[(size_t)q * d + i];
   __syncthreads();
   // 2. similarities: wave `wave` takes the candidates [64 g, 64 g + 64), g = wave, wave + NW, ...
-  float* tile = tiles + wave * PV_TILE;
-  const bool vec4 = (d & 3) == 0;   // every row 16-byte aligned and no piece crosses the row's end
+  float* tile = tiles + wave * TILE_FLOATS;
+  const bool vec4 = (d & 3) == 0;
   for (int g = wave; g < P / 64; g += NW) {
     const int c = g * 64 + lane;
     const int32_t row = (int32_t)(uint32_t)keys[c];
     if (__ballot(row >= 0) == 0ull) { keys[c] = KEY_INF; continue; }
     float acc = 0.0f;
-    for (int c0 = 0; c0 < d; c0 += PV_DCH) {
-      const int nd = (d - c0 < PV_DCH) ? d - c0 : PV_DCH;
+    for (int c0 = 0; c0 < d; c0 += TILE_DCH) {
+      const int nd = (d - c0 < TILE_DCH) ? d - c0 : TILE_DCH;
       float4 v[8];
 #pragma unroll
-      for (int it = 0; it < 8; ++it) {   // piece (it * 64 + lane): candidate (it * 8 + lane / 8), dimensions c0 + 4 (lane % 8) ..
-        const int cl = it * 8 + (lane >> 3), dim0 = (lane & 7) * 4;
-        const int32_t r = __shfl(row, cl, 64);
-        v[it] = float4{0.0f, 0.0f, 0.0f, 0.0f};
-        if (r >= 0 && dim0 < nd) {
-          const float* src = a.rows + (size_t)r * d + c0 + dim0;
-          if (vec4) v[it] = *reinterpret_cast<const float4*>(src);
-          else {
-            v[it].x = src[0];
-            if (dim0 + 1 < nd) v[it].y = src[1];
-            if (dim0 + 2 < nd) v[it].z = src[2];
-            if (dim0 + 3 < nd) v[it].w = src[3];
-          }
-        }
-      }
+      for (int it = 0; it < 8; ++it) v[it] = tile_row_piece(a.rows, row, it, lane, d, c0, nd, vec4);
 #pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int cl = it * 8 + (lane >> 3), dim0 = (lane & 7) * 4;
-        float* dst = tile + dim0 * PV_STRIDE + cl;
-        dst[0] = v[it].x; dst[PV_STRIDE] = v[it].y; dst[2 * PV_STRIDE] = v[it].z; dst[3 * PV_STRIDE] = v[it].w;
-      }
-      pv_wave_sync();
-      const float* col = tile + lane;
-      const float* qc = qs + c0;
-      if (nd == PV_DCH) {
-#pragma unroll
-        for (int j = 0; j < PV_DCH; ++j) {
-          const float p = qc[j] * col[j * PV_STRIDE];   // core_functions.c:77: v1[i] * v2[i]
-          acc = acc + p;                                //                     scalar += ...
-        }
-      } else {
-        for (int j = 0; j < nd; ++j) {
-          const float p = qc[j] * col[j * PV_STRIDE];
-          acc = acc + p;
-        }
-      }
-      pv_wave_sync();
+      for (int it = 0; it < 8; ++it) tile_store_row_piece(tile, v[it], it, lane);
+      wave_lds_sync();
+      chain1<1, TILE_STRIDE>(acc, qs + c0, tile + lane, nd);   // v1: the query
+      wave_lds_sync();
     }
     keys[c] = row >= 0 ? sim_key(acc, (uint32_t)row) : KEY_INF;
   }

@@ -2,7 +2,7 @@
 // the ids that have one, in device memory.  The result equals rows_of_ids (internal.h): unknown ids vanish, duplicates collapse,
 // the order is table order -- but nothing is sorted: the set is a bitmap over the table's rows (bit r & 31 of word r >> 5), which is
 // ordered and duplicate-free by construction.
-//   resolve_mark_kernel    one lane per id: its row (the serial-id probe of row_of_near first, then assign_row_of's binary search --
+//   resolve_mark_kernel    one lane per id: its row (the serial-id probe of row_of_near first, then row_of_id's binary search --
 //                          the same row either way), and an atomicOr of the row's bit.  The bitmap was cleared by a memset.
 //   resolve_count_kernel   one wave per block of `B` bitmap words (option resolve_block): the block's popcount -> cnt[b], and added
 //                          to part[b / SIM_CHUNK], the sums sim_scan_kernel takes per chunk of 1024 counts (integer atomicAdd: the
@@ -34,7 +34,7 @@ __device__ __forceinline__ int32_t resolve_row_of(const int32_t* __restrict__ ve
   const int64_t g = (int64_t)id - (int64_t)vec_ids[0];   // serial ids: the row itself (strictly ascending ids: never less than the row)
   if (g < 0) return -1;
   if (g < N && vec_ids[g] == id) return (int32_t)g;
-  return assign_row_of(vec_ids, N, id);
+  return row_of_id(vec_ids, N, id);
 }
 
 static __global__ __launch_bounds__(256) void resolve_mark_kernel(const int32_t* __restrict__ ids, int64_t n, const int32_t* __restrict__ vec_ids,

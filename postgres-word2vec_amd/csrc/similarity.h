@@ -3,22 +3,16 @@
 // ranking around them (include/freddy_gpu.h: freddy_gpu_similarity_pairs / _matrix / _join).  A similarity is always the binary32
 // chain "scalar = 0; scalar += v1[i] * v2[i]", i ascending, every product and sum rounded on its own (-ffp-contract=off) -- one
 // sequential chain per lane.  (The bit contract fixes the summation order, so the matrix cores cannot produce these values.)
-// Ids are resolved on the device by binary search over the handle's ascending ids (assign_row_of).
+// Ids are resolved on the device by binary search over the handle's ascending ids (row_of_id).  The tiles are dot_chain.h's.
 //
-//   sim_pairs_kernel   one lane per pair, 64 pairs per wave, one wave per workgroup.  Both rows of a pair are a gather of 4 d bytes;
-//       pv_rerank's staging, twice: per step 64 pairs x SIM_DCH = 32 dimensions of the A rows and of the B rows are read with 16-byte
-//       loads (8 consecutive lanes = 128 contiguous bytes of one row; a scalar path for d % 4 != 0) and stored transposed into two
-//       tiles [32][65]; every lane then walks its own column of either tile with the accumulator in a register.
-//       LDS banks (ds_write_b32 / ds_read_b32: bank = (address / 4) mod 32 within each half of the wave): a store instruction writes,
-//       per half, 4 pairs x 8 row pieces at tile[(4 * piece + j) * 65 + pair]: banks 4 * piece + pair (mod 32), all different; a read
-//       is lane-consecutive.  The second tile begins 32 * 65 = 2080 floats after the first, a multiple of 32 banks, and no instruction
-//       touches both tiles: the argument of pv.h holds for each tile by itself.  LDS 2 x 8 320 B = 16 640 B per wave (9 waves per CU
-//       by LDS); registers: 16 float4 of row pieces in flight + one accumulator.
+//   sim_pairs_kernel   one lane per pair, 64 pairs per wave, one wave per workgroup.  Both rows of a pair are a gather of 4 d bytes:
+//       the gather tile twice, one of the A rows and one of the B rows, all 16 loads of a step issued before the first store; every
+//       lane then walks its own column of either tile with the accumulator in a register (chain1).  No instruction touches both
+//       tiles.  LDS 2 x 8 320 B = 16 640 B per wave (9 waves per CU by LDS); registers: 16 float4 of row pieces in flight + one
+//       accumulator.
 //   sim_rows_kernel    ids -> rows (-1: none) and the `known` bytes of the B side of a matrix, once per call.
-//   sim_matrix_kernel  assign_exact_kernel's tile with the values kept: lanes are B rows (row tile [32][65], the banks as above), a
-//       tile of SIM_AT = 16 A rows x 32 dimensions [32][16] is loaded as 16-byte pieces and stored with its rows permuted (as_qrow:
-//       a store's 64 lanes write 64 consecutive floats), every lane reads the same 16 consecutive floats of a dimension (four
-//       broadcast ds_read_b128) into 16 accumulators; a B row piece is loaded once per 16 A rows.  For a fixed A row the 64 lanes
+//   sim_matrix_kernel  assign_exact_kernel's tiles with the values kept: lanes are B rows (the gather tile), the query tile holds 16
+//       A rows, 16 accumulators per lane; a B row piece is loaded once per 16 A rows.  For a fixed A row the 64 lanes
 //       write 64 consecutive floats of out[a][.]: 16 stores of 256 contiguous bytes per A tile.  A workgroup (x: 64 B rows, y: a
 //       range of A tiles -- the host splits A only as far as the chip needs workgroups) is still ONE wave: the waves share nothing
 //       but the A tile (2 KiB per step beside 8 KiB of B pieces, and L2-resident), the 4 KiB of results per A tile leave through
@@ -39,11 +33,6 @@
 namespace freddy {
 
 static constexpr int64_t SIM_MAX_NB = (int64_t)1 << 22;   // B ids per matrix / join call
-static constexpr int SIM_AT = AS_QT;                       // A rows per tile of sim_matrix_kernel
-static constexpr int SIM_DCH = AS_DCH;                     // dimensions per step
-static constexpr int SIM_STRIDE = AS_STRIDE;               // floats per dimension of a row tile: 64 rows + 1
-static constexpr int SIM_TILE = SIM_DCH * SIM_STRIDE;
-static constexpr int SIM_ATILE = SIM_DCH * SIM_AT;
 static constexpr int SIM_CHUNK = 1024;                     // units per workgroup of sim_count_kernel / sim_scan_kernel
 static constexpr int SIM_COUNT_WAVES = 16;                 // waves per workgroup of sim_count_kernel
 
@@ -54,22 +43,6 @@ __host__ __device__ __forceinline__ bool sim_float4gt(float a, float b) {
   if (an) return !bn;
   if (bn) return false;
   return a > b;
-}
-
-// the piece (dimensions c0 + dim0 .. + 3) of row r of a row-major table, zeros where the row (r < 0) or the dimension is missing
-__device__ __forceinline__ float4 sim_piece(const float* __restrict__ rows, int32_t r, int d, int c0, int dim0, int nd, bool vec4) {
-  float4 v = float4{0.0f, 0.0f, 0.0f, 0.0f};
-  if (r >= 0 && dim0 < nd) {
-    const float* src = rows + (size_t)r * d + c0 + dim0;
-    if (vec4) v = *reinterpret_cast<const float4*>(src);
-    else {
-      v.x = src[0];
-      if (dim0 + 1 < nd) v.y = src[1];
-      if (dim0 + 2 < nd) v.z = src[2];
-      if (dim0 + 3 < nd) v.w = src[3];
-    }
-  }
-  return v;
 }
 
 struct SimPairsArgs {
@@ -84,52 +57,35 @@ struct SimPairsArgs {
 };
 
 static __global__ __launch_bounds__(64) void sim_pairs_kernel(SimPairsArgs a) {
-  __shared__ __attribute__((aligned(16))) float ta[SIM_TILE];   // [SIM_DCH][SIM_STRIDE] rows of ids_a
-  __shared__ __attribute__((aligned(16))) float tb[SIM_TILE];   // the same of ids_b
+  __shared__ __attribute__((aligned(16))) float ta[TILE_FLOATS];   // [TILE_DCH][TILE_STRIDE] rows of ids_a
+  __shared__ __attribute__((aligned(16))) float tb[TILE_FLOATS];   // the same of ids_b
   const int lane = threadIdx.x, d = a.d;
   const int i = blockIdx.x * 64 + lane;
   int32_t ra = -1, rb = -1;
   if (i < a.n) {
-    ra = assign_row_of(a.vec_ids, a.N, a.ids_a[i]);
-    if (ra >= 0) rb = assign_row_of(a.vec_ids, a.N, a.ids_b[i]);
+    ra = row_of_id(a.vec_ids, a.N, a.ids_a[i]);
+    if (ra >= 0) rb = row_of_id(a.vec_ids, a.N, a.ids_b[i]);
     if (rb < 0) ra = -1;   // (a pair is known with both rows; none of an unknown pair's rows is read)
   }
   float acc = 0.0f;
   if (__ballot(ra >= 0) != 0ull) {
-    const bool vec4 = (d & 3) == 0;   // every row 16-byte aligned and no piece crosses the row's end
-    for (int c0 = 0; c0 < d; c0 += SIM_DCH) {
-      const int nd = (d - c0 < SIM_DCH) ? d - c0 : SIM_DCH;
+    const bool vec4 = (d & 3) == 0;
+    for (int c0 = 0; c0 < d; c0 += TILE_DCH) {
+      const int nd = (d - c0 < TILE_DCH) ? d - c0 : TILE_DCH;
       float4 va[8], vb[8];
 #pragma unroll
-      for (int it = 0; it < 8; ++it) {   // piece (it * 64 + lane): pair (it * 8 + lane / 8), dimensions c0 + 4 (lane % 8) ..
-        const int cl = it * 8 + (lane >> 3), dim0 = (lane & 7) * 4;
-        va[it] = sim_piece(a.rows, __shfl(ra, cl, 64), d, c0, dim0, nd, vec4);
-        vb[it] = sim_piece(a.rows, __shfl(rb, cl, 64), d, c0, dim0, nd, vec4);
+      for (int it = 0; it < 8; ++it) {
+        va[it] = tile_row_piece(a.rows, ra, it, lane, d, c0, nd, vec4);
+        vb[it] = tile_row_piece(a.rows, rb, it, lane, d, c0, nd, vec4);
       }
 #pragma unroll
       for (int it = 0; it < 8; ++it) {
-        const int cl = it * 8 + (lane >> 3), dim0 = (lane & 7) * 4;
-        float* da = ta + dim0 * SIM_STRIDE + cl;
-        da[0] = va[it].x; da[SIM_STRIDE] = va[it].y; da[2 * SIM_STRIDE] = va[it].z; da[3 * SIM_STRIDE] = va[it].w;
-        float* db = tb + dim0 * SIM_STRIDE + cl;
-        db[0] = vb[it].x; db[SIM_STRIDE] = vb[it].y; db[2 * SIM_STRIDE] = vb[it].z; db[3 * SIM_STRIDE] = vb[it].w;
+        tile_store_row_piece(ta, va[it], it, lane);
+        tile_store_row_piece(tb, vb[it], it, lane);
       }
-      assign_wave_sync();
-      const float* ca = ta + lane;
-      const float* cb = tb + lane;
-      if (nd == SIM_DCH) {
-#pragma unroll
-        for (int j = 0; j < SIM_DCH; ++j) {
-          const float p = ca[j * SIM_STRIDE] * cb[j * SIM_STRIDE];   // core_functions.c:77: v1[i] * v2[i]
-          acc = acc + p;                                             //                     scalar += ...
-        }
-      } else {
-        for (int j = 0; j < nd; ++j) {
-          const float p = ca[j * SIM_STRIDE] * cb[j * SIM_STRIDE];
-          acc = acc + p;
-        }
-      }
-      assign_wave_sync();
+      wave_lds_sync();
+      chain1<TILE_STRIDE, TILE_STRIDE>(acc, ta + lane, tb + lane, nd);   // v1: the row of ids_a
+      wave_lds_sync();
     }
   }
   if (i < a.n) {
@@ -143,7 +99,7 @@ static __global__ __launch_bounds__(256) void sim_rows_kernel(const int32_t* __r
                                                               int32_t* __restrict__ rows, uint8_t* __restrict__ known) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const int32_t r = assign_row_of(vec_ids, N, ids[i]);
+  const int32_t r = row_of_id(vec_ids, N, ids[i]);
   rows[i] = r;
   known[i] = r >= 0 ? 1 : 0;
 }
@@ -159,55 +115,42 @@ struct SimMatrixArgs {
 };
 
 static __global__ __launch_bounds__(64) void sim_matrix_kernel(SimMatrixArgs a) {
-  __shared__ __attribute__((aligned(16))) float tile[SIM_TILE];    // [SIM_DCH][SIM_STRIDE]
-  __shared__ __attribute__((aligned(16))) float qs[SIM_ATILE];     // [SIM_DCH][SIM_AT]
+  __shared__ __attribute__((aligned(16))) float tile[TILE_FLOATS];    // [TILE_DCH][TILE_STRIDE]
+  __shared__ __attribute__((aligned(16))) float qs[TILE_QFLOATS];     // [TILE_DCH][TILE_QT] A rows
   const int lane = threadIdx.x, d = a.d;
   const int j = blockIdx.x * 64 + lane;
   const int32_t row = j < a.nb ? a.b_rows[j] : -1;
   const bool any = __ballot(row >= 0) != 0ull;
-  const bool vec4 = (d & 3) == 0;   // every row of the table and of A 16-byte aligned and no piece crosses its end
-  const int n_tiles = (a.na + SIM_AT - 1) / SIM_AT;
+  const bool vec4 = (d & 3) == 0;
+  const int n_tiles = (a.na + TILE_QT - 1) / TILE_QT;
   const int t_begin = blockIdx.y * a.tiles_per_wg;
   const int t_end = (t_begin + a.tiles_per_wg < n_tiles) ? t_begin + a.tiles_per_wg : n_tiles;
   for (int tl = t_begin; tl < t_end; ++tl) {
-    const int q0 = tl * SIM_AT;
-    float acc[SIM_AT];
+    const int q0 = tl * TILE_QT;
+    float acc[TILE_QT];
 #pragma unroll
-    for (int t = 0; t < SIM_AT; ++t) acc[t] = 0.0f;
+    for (int t = 0; t < TILE_QT; ++t) acc[t] = 0.0f;
     if (any) {
-      for (int c0 = 0; c0 < d; c0 += SIM_DCH) {
-        const int nd = (d - c0 < SIM_DCH) ? d - c0 : SIM_DCH;
+      for (int c0 = 0; c0 < d; c0 += TILE_DCH) {
+        const int nd = (d - c0 < TILE_DCH) ? d - c0 : TILE_DCH;
         float4 v[8], qv[2];
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {   // piece (it * 64 + lane): B row (it * 8 + lane / 8), dimensions c0 + 4 (lane % 8) ..
-          const int cl = it * 8 + (lane >> 3), dim0 = (lane & 7) * 4;
-          v[it] = sim_piece(a.rows, __shfl(row, cl, 64), d, c0, dim0, nd, vec4);
-        }
+        for (int it = 0; it < 8; ++it) v[it] = tile_row_piece(a.rows, row, it, lane, d, c0, nd, vec4);
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {   // A row (q0 + lane % 16), dimensions c0 + 4 (it * 4 + lane / 16) ..
-          const int t = lane & 15, dim0 = (it * 4 + (lane >> 4)) * 4;
-          qv[it] = sim_piece(a.a, q0 + t < a.na ? q0 + t : -1, d, c0, dim0, nd, vec4);
-        }
+        for (int it = 0; it < 2; ++it) qv[it] = tile_query_piece(a.a, a.na, q0, it, lane, d, c0, nd, vec4);
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int cl = it * 8 + (lane >> 3), dim0 = (lane & 7) * 4;
-          float* dst = tile + dim0 * SIM_STRIDE + cl;
-          dst[0] = v[it].x; dst[SIM_STRIDE] = v[it].y; dst[2 * SIM_STRIDE] = v[it].z; dst[3 * SIM_STRIDE] = v[it].w;
-        }
+        for (int it = 0; it < 8; ++it) tile_store_row_piece(tile, v[it], it, lane);
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {   // piece p, element c (dimension 4 p + c) -> row as_qrow(4 p + c) = 8 c + p
-          float* dst = qs + (it * 4 + (lane >> 4)) * SIM_AT + (lane & 15);
-          dst[0] = qv[it].x; dst[8 * SIM_AT] = qv[it].y; dst[16 * SIM_AT] = qv[it].z; dst[24 * SIM_AT] = qv[it].w;
-        }
-        assign_wave_sync();
-        const float* col = tile + lane;
-        if (nd == SIM_DCH) {
+        for (int it = 0; it < 2; ++it) tile_store_query_piece(qs, qv[it], it, lane);
+        wave_lds_sync();
+        const float* col = tile + lane;   // (the 16-accumulator walk, kept in place for registers: dot_chain.h)
+        if (nd == TILE_DCH) {
 #pragma unroll
-          for (int jj = 0; jj < SIM_DCH; ++jj) {
-            const float x = col[jj * SIM_STRIDE];
+          for (int jj = 0; jj < TILE_DCH; ++jj) {
+            const float x = col[jj * TILE_STRIDE];
 #pragma unroll
-            for (int t4 = 0; t4 < SIM_AT / 4; ++t4) {
-              const float4 qq = *reinterpret_cast<const float4*>(qs + as_qrow(jj) * SIM_AT + t4 * 4);
+            for (int t4 = 0; t4 < TILE_QT / 4; ++t4) {
+              const float4 qq = *reinterpret_cast<const float4*>(qs + tile_qrow(jj) * TILE_QT + t4 * 4);
               float p;
               p = qq.x * x; acc[t4 * 4 + 0] = acc[t4 * 4 + 0] + p;   // core_functions.c:77: scalar += v1[i] * v2[i] (v1: the A row)
               p = qq.y * x; acc[t4 * 4 + 1] = acc[t4 * 4 + 1] + p;
@@ -217,10 +160,10 @@ static __global__ __launch_bounds__(64) void sim_matrix_kernel(SimMatrixArgs a) 
           }
         } else {
           for (int jj = 0; jj < nd; ++jj) {
-            const float x = col[jj * SIM_STRIDE];
+            const float x = col[jj * TILE_STRIDE];
 #pragma unroll
-            for (int t4 = 0; t4 < SIM_AT / 4; ++t4) {
-              const float4 qq = *reinterpret_cast<const float4*>(qs + as_qrow(jj) * SIM_AT + t4 * 4);
+            for (int t4 = 0; t4 < TILE_QT / 4; ++t4) {
+              const float4 qq = *reinterpret_cast<const float4*>(qs + tile_qrow(jj) * TILE_QT + t4 * 4);
               float p;
               p = qq.x * x; acc[t4 * 4 + 0] = acc[t4 * 4 + 0] + p;
               p = qq.y * x; acc[t4 * 4 + 1] = acc[t4 * 4 + 1] + p;
@@ -229,12 +172,12 @@ static __global__ __launch_bounds__(64) void sim_matrix_kernel(SimMatrixArgs a) 
             }
           }
         }
-        assign_wave_sync();
+        wave_lds_sync();
       }
     }
     if (j < a.nb) {
 #pragma unroll
-      for (int t = 0; t < SIM_AT; ++t) {   // per A row: the wave's 64 lanes write 64 consecutive floats
+      for (int t = 0; t < TILE_QT; ++t) {   // per A row: the wave's 64 lanes write 64 consecutive floats
         if (q0 + t < a.na) {
           const bool known = row >= 0 && (a.known_a == nullptr || a.known_a[q0 + t] != 0);
           a.out[(size_t)(q0 + t) * a.nb + j] = known ? acc[t] : 0.0f;

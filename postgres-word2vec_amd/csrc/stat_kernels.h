@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dot_chain.h"   // row_of_id
+
 namespace freddy {
 
 static constexpr int STAT_WG = 256;
@@ -45,10 +47,7 @@ __global__ __launch_bounds__(STAT_WG) void stat_count_kernel(const int32_t* __re
       const int64_t c = (int64_t)tids[i] - ids[0];
       if (c >= 0 && c < N) r = c;
     } else {
-      const int32_t id = tids[i];
-      int64_t lo = 0, hi = N;
-      while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (ids[mid] < id) lo = mid + 1; else hi = mid; }
-      if (lo < N && ids[lo] == id) r = lo;
+      r = row_of_id(ids, N, tids[i]);
     }
     if (r < 0) continue;
     const int c = cell[r];

@@ -15,7 +15,7 @@ SWEEP_CUS = (1, 2, 3, 7, 32, 256, 304)
 # csrc constants the formulas are called with
 SCAN5_G, SPEC2_G, MULTI_G = 16, 12, 8      # items per work entry: fused5.h / fused8.h, fused3.h, multi.h
 ONE_WAVES, ONE_M = 8, 12                    # one_layout.h
-AS_PQ_WG, SIM_AT = 256, 16                  # assign.h, similarity.h
+AS_PQ_WG, SIM_AT = 256, 16                  # assign.h: AS_PQ_WG; dot_chain.h: TILE_QT, the A rows per tile of sim_matrix_kernel
 EXF_WAVES = 8                               # exact2.h: EXF_WG / 64
 
 

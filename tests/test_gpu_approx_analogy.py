@@ -201,6 +201,27 @@ def test_other_shapes(gpu, oracle, d, m, K):
         h.close()
 
 
+@pytest.mark.parametrize("d,m,K", [(7, 1, 16), (32, 4, 16), (33, 3, 16)])
+def test_small_tables_at_the_edges_of_a_step(gpu, oracle, d, m, K):
+    """The re-rank's tile takes 32 dimensions per step: d = 7 (less than one step, odd: the scalar loads), 32 (one full step and no
+    tail) and 33 (a tail of one dimension), over 300 rows and 40 triples, every fifth row without a vector; 1 and 63 candidates
+    (one wave), 65 (four waves)."""
+    N = 300
+    x = util.shape_corpus(N, d).numpy()
+    ids = np.arange(1, N + 1, dtype=np.int32)
+    t = np.random.default_rng(d).choice(ids, (40, 3)).astype(np.int32)
+    pt = util.shape_pq_tables(d, m, K, N)
+    keep = ids % 5 != 0
+    pq, vec = gpu.PQIndex(pt["codebook"], pt["ids"], pt["codes"]), gpu.VectorIndex(ids[keep], x[keep])
+    pq_t = oracle.pq_table(pt["codebook"], pt["ids"], pt["codes"])
+    for k, n_cand in ((1, 1), (5, 63), (5, 65)):
+        res = am.pq_expected(oracle, pq_t, x[keep], ids[keep], t, k, n_cand)
+        gi, gs = pq.analogy(vec, t, k, n_cand)
+        pm.same(gi, gs, res[0], k, f"pq d={d} k={k} n_cand={n_cand}")
+        assert pq.last_approx_analogy_stats() == res[1]
+    pq.close(); vec.close()
+
+
 def test_pass_boundary(main, oracle):
     """analogy_pass = 64 with 130 triples and an unknown one at position 64: three passes, the rows and the stats of the default."""
     x, ids, ivf, vec = main["x"], main["ids"], main["ivf"], main["vec"]

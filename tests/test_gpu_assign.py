@@ -12,7 +12,7 @@ import util
 pytestmark = pytest.mark.gpu
 
 N = 20000
-AS_QT, AS_MAX_Q = 16, 65536           # csrc/assign.h: the exact kernel's query tile, the calls' query limit
+AS_QT, AS_MAX_Q = 16, 65536           # csrc/dot_chain.h TILE_QT: the exact kernel's query tile; csrc/assign.h AS_MAX_Q: the calls' query limit
 SHAPES = {"300d_m12": (300, 12, 256), "25d_m5": (25, 5, 256)}
 
 
@@ -65,6 +65,26 @@ def test_assign_equals_the_model(tabs, oracle, n):
         assert q[3] == q[1] and q[64] == q[63] and np.array_equal(q[10:20], q[20:30])
         assert not np.isin(q, [4, 16, 40]).any(), "the later of two identical queries won a target"
         assert (np.delete(q, [5, 62, 700]) >= 0).all()
+
+
+@pytest.mark.parametrize("d", [7, 30, 32, 33])
+def test_exact_assign_at_the_edges_of_a_step(d):
+    """The exact kernel's tiles take 32 dimensions per step: d = 7 (less than one step, odd: the scalar loads), 30 (rows aligned to 8
+    bytes, not 16: the scalar loads again), 32 (one full step and no tail) and 33 (a tail of one dimension); 300 rows, 17 queries (a
+    tile of 16 and one of one), 65 targets (two waves), some without a row."""
+    from freddy_amd import gpu
+    n0 = 300
+    x = util.shape_corpus(n0, d).numpy()
+    ids = np.arange(1, n0 + 1, dtype=np.int32)
+    vec = gpu.VectorIndex(ids, x)
+    rng = np.random.default_rng(31 + d)
+    qs = np.stack([x[rng.choice(n0, 5)].mean(axis=0) for _ in range(AS_QT + 1)]).astype(np.float32)
+    tg = rng.choice(ids, 65).astype(np.int32)
+    tg[4] = n0 + 9; tg[63] = -2; tg[64] = tg[0]
+    for n in (1, 65):
+        got, exp = vec.assign(qs, tg[:n]), am.exact_assign(ids, x, qs, tg[:n])
+        assert am.same(got, exp), f"d={d} n={n}: {np.flatnonzero(got[0] != exp[0])[:8]}"
+    vec.close()
 
 
 def test_assign_at_the_query_limit(oracle):

@@ -175,6 +175,28 @@ def test_other_shapes(gpu, oracle, d, m, K):
         h.close()
 
 
+@pytest.mark.parametrize("d,m,K", [(7, 1, 16), (32, 4, 16), (33, 3, 16)])
+def test_small_tables_at_the_edges_of_a_step(gpu, oracle, d, m, K):
+    """The re-rank's tile takes 32 dimensions per step: d = 7 (less than one step, odd: the scalar loads), 32 (one full step and no
+    tail) and 33 (a tail of one dimension), over 300 rows and 40 queries, every third row without a vector; 1, 63, 64 candidates
+    (one wave) and 65 (four waves)."""
+    N = 300
+    x = util.shape_corpus(N, d).numpy()
+    ids = np.arange(1, N + 1, dtype=np.int32)
+    qs = util.shape_queries(N, d, 40)
+    pt = util.shape_pq_tables(d, m, K, N)
+    keep = np.arange(N) % 3 != 0
+    pq, vec = gpu.PQIndex(pt["codebook"], pt["ids"], pt["codes"]), gpu.VectorIndex(ids[keep], x[keep])
+    pq_t = oracle.pq_table(pt["codebook"], pt["ids"], pt["codes"])
+    for k, pvf in ((1, 1), (9, 7), (8, 8), (13, 5)):
+        lists = pm.pq_lists(oracle, pq_t, qs, k * pvf)
+        exp, n_cand, n_scored = pm.expected(oracle, lists, x[keep], ids[keep], qs, k)
+        (gi, gs), names = _profiled(pq, lambda: pq.search_pv(vec, qs, k, pvf))
+        pm.same(gi, gs, exp, k, f"pq d={d} k={k} pvf={pvf}")
+        assert "pv_rerank" in names and pq.last_pv_stats()["scored"] == int(n_scored.sum())
+    pq.close(); vec.close()
+
+
 def test_after_append_rows(gpu, oracle):
     """Rows appended to the IVFADC handle AND to the vector handle: they must be found, resolved and able to win."""
     d, m, K, C, N, n0 = 30, 5, 16, 16, 6000, 5000

@@ -88,6 +88,23 @@ def test_matrix_and_join_equal_the_model(handles, d):
                 assert names["sim_matrix_kernel"][0] == 1, "the join computes every chain once"
 
 
+@pytest.mark.parametrize("d", [30, 33])
+def test_rows_of_120_bytes_and_a_tail_of_one_dimension(d):
+    """The two widths si.DIMS leaves out: d = 30 (rows aligned to 8 bytes, not 16: the scalar loads with every piece but the last
+    whole) and d = 33 (one full step of 32 dimensions and a tail of one); 300 rows, 65 pairs, a matrix of 17 x 65."""
+    from freddy_amd import gpu
+    ids, x = si.table(d, 300)
+    vec = gpu.VectorIndex(ids, x)
+    rng = np.random.default_rng(d)
+    a, b = si.draw_ids(ids, 65, rng), si.draw_ids(ids, 65, rng)
+    sim, known = vec.similarity_pairs(a, b)
+    esim, eknown = sm.pairs(ids, x, a, b)
+    assert np.array_equal(known, eknown) and eknown.any() and not eknown.all()
+    assert sm.same_floats(sim, esim), (d, np.flatnonzero(sim.view(np.uint32) != esim.view(np.uint32))[:8])
+    _same_matrix(vec.similarity_matrix(a[:17], b), sm.matrix(ids, x, a[:17], b), f"d={d} na=17 nb=65")
+    vec.close()
+
+
 @pytest.mark.parametrize("d", [12, 7])
 def test_the_constructed_join(d):
     """similarities equal to the threshold and one ulp above, NaNs, +0.0 against -0.0, blocks of 0 / 1 / 64 matches, the last lane of a
