@@ -466,6 +466,49 @@ int freddy_gpu_ivpq_analogy(freddy_gpu_index_t* ivpq, freddy_gpu_index_t* vecs, 
  * and how many of those had a vector row and were not an input of their triple (were scored).  NULL pointers are skipped. */
 int freddy_gpu_last_approx_analogy_stats(const freddy_gpu_index_t* ann, int64_t* searched, int64_t* candidates, int64_t* scored);
 
+/* ---- text vectors from token ids, and searches over them (tokenize.h) ---------------------------------------------------------
+ * tokenize(text) = vec_normalize_bytea(centroid_bytea(ARRAY(SELECT vector FROM google_vecs_norm WHERE word = ANY(tokens)))) and
+ * tokenize_raw (the same over google_vecs, without the normalisation; freddy--0.0.1.sql:1512-1536) for n_texts texts at once, each a
+ * list of row ids of `vecs`: token_ids[offsets[n_texts]] and offsets[n_texts + 1] (non-decreasing, offsets[0] == 0).  At most
+ * FREDDY_TOK_MAX_LEN ids per text.  The rows never leave the device; bit for bit, no tolerance anywhere:
+ *   row list     FREDDY_QIDS_TABLE_ORDER (the SQL above): the DISTINCT table rows of the ids that have one, in ascending row order --
+ *                unknown ids vanish, duplicates collapse, as for every id set of this library (PostgreSQL leaves the order of "= ANY"
+ *                unspecified).  FREDDY_QIDS_POSITIONAL (centroid_bytea(ARRAY[...]) of an explicit array): the rows of the ids that have
+ *                one in the given order, duplicates kept.
+ *   centroid     n = the length of the row list; core_functions.c:371-379: out[j] = 0, then for i ascending
+ *                out[j] = out[j] + row_i[j] / (float)n -- every division (correctly rounded, never a reciprocal) and every addition
+ *                rounded to binary32, no FMA.
+ *   normalize    != 0: vec_normalize_bytea -- sq = sq + out[j] * out[j] for j ascending (one chain), len = (float)sqrt((double)sq),
+ *                out[j] / len.  Nothing is special-cased: a zero centroid gives a row of NaN.
+ *   n == 0       (an empty text, or no id with a row; the reference returns a zero-length bytea that no search accepts):
+ *                out_count[t] = 0 and the vector is all zeros; in the search forms the text's list holds the entry point's fillers,
+ *                (-1, sentinel) or (-1, -inf) for the exact form, costs no search work and disturbs no neighbour.
+ * The three *_search_texts forms: for every text with out_count > 0 the list is bit for bit (ids, ranks, distance or similarity
+ * bits) what freddy_gpu_ivfadc_search / freddy_gpu_pq_search / freddy_gpu_exact_search returns for the vector freddy_gpu_tokenize
+ * returns for that text, with the same remaining arguments.  The approximate forms always normalise (tokenize is the only producer
+ * of their queries); the exact form takes the flag (tokenize_raw).  The texts with a row list are compacted and searched in passes
+ * (option "tokenize_pass", set on `vecs`: texts per pass); the vectors of a pass are written by the kernels into a pinned block
+ * that the public search reads, and never reach the caller's memory.
+ * Errors, all before any device work and in this order: FREDDY_E_ARG for the scalars (k < 1, W, found_rule, the subset, n_texts < 0,
+ * a bad id_rule), for a NULL buffer with work to do, offsets[0] != 0 and decreasing offsets; FREDDY_E_LIMIT for a text of more than
+ * FREDDY_TOK_MAX_LEN ids (the message names the text and its length) and for k > 4096; then the handles as for the searches by id
+ * (NULL, kinds, devices, d, replicas) and a poisoned handle.  n_texts == 0 succeeds and launches nothing.  A failed allocation is
+ * FREDDY_E_NOMEM and leaves the handles' tables as they were.  Concurrency and mutations as for the searches by id: a mutation of
+ * `vecs` before the call is seen (the ids are resolved against the handle's device id column), none may run beside it.  The
+ * launches are recorded as "tok_resolve", "tok_rows", "tok_centroid" and "tok_unit" in the profile of `vecs`. */
+#define FREDDY_TOK_MAX_LEN 4096
+int freddy_gpu_tokenize(freddy_gpu_index_t* vecs, const int32_t* token_ids, const int64_t* offsets /*[n_texts + 1]*/, int32_t n_texts,
+                        int32_t id_rule, int32_t normalize, float* out_vectors /*[n_texts][d]*/, int32_t* out_count /*[n_texts]*/);
+int freddy_gpu_ivfadc_search_texts(freddy_gpu_index_t* ivf, freddy_gpu_index_t* vecs, const int32_t* token_ids, const int64_t* offsets,
+                                   int32_t n_texts, int32_t id_rule, int32_t k, int32_t W, float sentinel, int32_t found_rule,
+                                   int32_t* out_count /*[n_texts]*/, int32_t* out_ids /*[n_texts][k]*/, float* out_dist /*[n_texts][k]*/);
+int freddy_gpu_pq_search_texts(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs, const int32_t* token_ids, const int64_t* offsets,
+                               int32_t n_texts, int32_t id_rule, int32_t k, float sentinel, const int32_t* subset_ids, int64_t n_subset,
+                               int32_t* out_count, int32_t* out_ids, float* out_dist);
+int freddy_gpu_exact_search_texts(freddy_gpu_index_t* vecs, const int32_t* token_ids, const int64_t* offsets, int32_t n_texts,
+                                  int32_t id_rule, int32_t normalize, int32_t k, const int32_t* subset_ids, int64_t n_subset,
+                                  int32_t* out_count, int32_t* out_ids, float* out_sim);
+
 /* ---- the kNN-join by row id (join_run.h JoinQueries, join_kernels.h sub_dist_rows_kernel) -----------------------------------
  * The kNN-join's SQL callers start from ids: knn_in_ivpq_batch(query_set varchar[], ...) selects "word, vector, id FROM
  * google_vecs_norm WHERE word = ANY(...)" and hands the vectors over (freddy--0.0.1.sql:720-761, 797-814).  This call takes the ids:
@@ -787,7 +830,10 @@ int freddy_gpu_abi_version(void);
  *                0 = auto: 2 from n > 32768 tokens on), "exact_resolve" (where freddy_gpu_exact_search / _exact_join /
  *                _exact_analogy turn their id set into table rows: 0 = on the host, the default; 1 = on the device, as the
  *                *_exact_*_ids calls always do), "resolve_block" (bitmap words per block of the device resolve: 0 = 256, at most
- *                2^20; tests make a small table span many blocks)
+ *                2^20; tests make a small table span many blocks), "tokenize_pass" (on a vector handle: texts per pass of the
+ *                *_search_texts calls: 0 = as many as a pinned block of 256 MiB holds), "tokenize_unit" (the normalisation of
+ *                text vectors: 1 = a wave per text, lane 0 walking the chain of squares; 2 = one chain per lane over 64 texts;
+ *                0 = auto, the default: 1 below 16384 texts, 2 from there on)
  *   self-checks (tests):  "check_brackets" (bit 0: the scan keeps and the merge refines EVERY probed row, bit 1: the cell
  *                selection refines every cell, bit 2: exact kNN and the exact join refine every row -- each with its proven bracket compared with
  *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines

@@ -275,9 +275,22 @@ const char* freddy_get_groups_function(const freddy_session_t* s);
 int groups(freddy_session_t* s, const int32_t* token_ids, int32_t n_tokens, const int32_t* group_ids, int32_t n_groups,
            freddy_group_row* out, int32_t* n_rows);
 
+/* tokenize(text) / tokenize_raw(text) for a batch of texts, by row id        freddy--0.0.1.sql:1512-1536
+ *   A text is the list of the row ids of its tokens: token_ids[offsets[n_texts]], offsets[n_texts + 1] (non-decreasing, from 0; at
+ *   most FREDDY_TOK_MAX_LEN ids per text).  out_vectors[t] = centroid_bytea of "SELECT vector FROM <table> WHERE word = ANY(tokens)"
+ *   -- the DISTINCT rows, in table order; unknown ids vanish -- through vec_normalize_bytea for tokenize_batch (google_vecs_norm) and
+ *   as it is for tokenize_raw_batch (google_vecs: freddy_load_vecs_original; "google_vecs is not loaded" before that).  The rows are
+ *   read where they are pinned (freddy_gpu_tokenize), bit for bit the reference's arithmetic.  out_count[t] = the rows that went into
+ *   text t; 0 (no token is a row: the reference returns a zero-length bytea) leaves a vector of zeros. */
+int tokenize_batch(freddy_session_t* s, const int32_t* token_ids, const int64_t* offsets, int32_t n_texts,
+                   float* out_vectors /*[n_texts][d]*/, int32_t* out_count /*[n_texts]*/);
+int tokenize_raw_batch(freddy_session_t* s, const int32_t* token_ids, const int64_t* offsets, int32_t n_texts,
+                       float* out_vectors /*[n_texts][d]*/, int32_t* out_count /*[n_texts]*/);
+
 /* Next row: insert_batch(varchar[]) -> int4                  freddy.c:1403-1658
- * The tokenisation sub-query (:1503-1519: tokenize(term) for the terms NOT yet in the vocabulary) stays with SQL;
- * the caller passes its result, the normalised vectors of the new terms.  Per vector: PQ code, coarse cell +
+ * The tokenisation sub-query (:1503-1519: tokenize(term) for the terms NOT yet in the vocabulary) has a device form for terms
+ * whose tokens are rows, tokenize_batch above; splitting a term into words and looking the words up stays with SQL, and
+ * the caller passes the result, the normalised vectors of the new terms.  Per vector: PQ code, coarse cell +
  * residual code, ivpq code + multi-index cell (device); the three codebooks' running update exactly as
  * updateCodebook / updateCodebookRelation compute and store it (index_utils.c:908-991, "%f" text included);
  * one row per table with id = max(id) + 1 of THAT table (index_utils.c:993-1074); every pinned index is extended in

@@ -98,6 +98,7 @@ void free_index(freddy_gpu_index* ix) {
   for (DevBuf* b : {&ix->exf_qfrag, &ix->exf_small, &ix->exf_sample, &ix->exf_cand, &ix->exf_xf}) b->release();
   ix->hio_in.release(); ix->hio_out.release();
   ix->pv_io.release(); ix->pv_q.release();
+  ix->tok_dev.release(); ix->tok_raw.release(); ix->tok_vec.release(); ix->tok_io.release();
   for (Lane& l : ix->lanes) {
     if (l.stream && l.stream != ix->stream) (void)hipStreamDestroy(l.stream);
     for (LaneSlot& c : l.slot) {
@@ -280,6 +281,8 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   else if (n == "exact_resolve") t.exact_resolve = value != 0 ? 1 : 0;
   else if (n == "resolve_block") t.resolve_block = (int)std::max<int64_t>(0, std::min<int64_t>(value, (int64_t)1 << 20));
   else if (n == "analogy_pass") t.analogy_pass = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
+  else if (n == "tokenize_pass") t.tokenize_pass = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
+  else if (n == "tokenize_unit") t.tokenize_unit = value == 1 || value == 2 ? (int)value : 0;
   else if (n == "cluster_pass") t.cluster_pass = value <= 0 ? 0 : (int)std::max<int64_t>(64, std::min<int64_t>(value, (int64_t)1 << 30));
   else if (n == "cluster_walk") t.cluster_walk = value == 1 || value == 2 ? (int)value : 0;
   else if (n == "similarity_pass_bytes") t.similarity_pass_bytes = std::max<int64_t>(0, std::min<int64_t>(value, (int64_t)4 << 30));   // (a block's match count is a 32-bit number)

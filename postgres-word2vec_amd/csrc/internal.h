@@ -10,7 +10,7 @@
 //   join.hip    pin_ivpq, knn_join (join.h: overview; join_kernels.h and join_traverse.h the kernels, join_host.h the host heap, join_run.h the run
 //               record of a call and its stages)
 //   exact.hip   pin_vectors, exact kNN, the exact join, analogies, post verification of pq / ivf lists (pv.h), approximate analogies (approx_analogy.h),
-//               exact_assign (assign.h), the whole k-means of cluster_exact / cluster_pq (cluster.h), similarities by row id (similarity.h); exact_host.h the host sequences they share: the filter + refine chain, scan chunking, the re-rank stage, triple resolution
+//               exact_assign (assign.h), the whole k-means of cluster_exact / cluster_pq (cluster.h), similarities by row id (similarity.h), text vectors from token ids and the searches over them (tokenize.h); exact_host.h the host sequences they share: the filter + refine chain, scan chunking, the re-rank stage, triple resolution
 //   build.hip   encode, insert_quantize, k-means
 // Kernel headers are included by the unit that launches them (kernels shared by two units are static or templates).
 #pragma once
@@ -92,6 +92,8 @@ struct Tuning {
   int cluster_walk = 0;        // option cluster_walk: how cluster_sample_kernel finds a cluster's ranked members: 1 = it walks them from position 0 (what it does for kc > 1024), 2 = over the apply kernel's per-block counts (kc <= 1024), 0 = auto: 2 from n > 32768 on
   int exact_resolve = 0;       // option exact_resolve: how freddy_gpu_exact_search / _exact_join / _exact_analogy turn their id set into table rows: 0 = on the host (rows_of_ids), 1 = on the device (resolve.h); the *_ids forms always take the device
   int resolve_block = 0;       // option resolve_block: bitmap words per block of the device resolve (resolve.h): 0 = 256; tests make small tables span many blocks
+  int tokenize_pass = 0;       // option tokenize_pass (set on the vector handle): texts per pass of the *_search_texts calls (tokenize.h): 0 = as many as a pinned block of 256 MiB holds
+  int tokenize_unit = 0;       // option tokenize_unit: the sum of squares of freddy_gpu_tokenize's normalisation: 1 = a wave per text with lane 0 walking the chain (tok_unit_wave_kernel), 2 = a chain per lane over 64 texts (tok_unit_kernel), 0 = auto: 1 below 16384 texts, 2 from there on (tokenize.h)
   int64_t similarity_pass_bytes = 0;   // option similarity_pass_bytes: the device result block of one pass of freddy_gpu_similarity_matrix / _join (similarity.h): 0 = 256 MiB, at most 4 GiB; 16 rows of A at least
   // -- self-checks (tests): bit 0 = the scan keeps every row and the merge refines every row (every probed row's bracket is checked),
   //    bit 1 = the cell selection refines every cell, bit 2 = exact kNN refines every row
@@ -302,6 +304,11 @@ struct freddy_gpu_index {
   // the last approximate-analogy call on a pq / ivf handle (freddy_gpu_last_approx_analogy_stats; it shares pv_io / pv_q): triples
   // searched, their candidates, candidates scored
   int64_t aa_stats[3] = {0, 0, 0};
+  // text vectors on a vector handle (tokenize.h): the texts of a call on the device ([offsets][ids][rows][counts]), the centroids in
+  // front of the normalisation, the vectors of freddy_gpu_tokenize, and the pinned block of one pass of the *_search_texts calls
+  // ([the pass's vectors][their texts]) -- buffers of their own, because the searches of a pass run on this handle's workspace
+  DevBuf tok_dev, tok_raw, tok_vec;
+  PinnedBuf tok_io;
 };
 
 template <class F>

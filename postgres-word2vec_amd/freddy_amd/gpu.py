@@ -42,7 +42,9 @@ EXPORTS = [
     "freddy_gpu_cluster",
     "freddy_gpu_exact_search_ids", "freddy_gpu_exact_join_ids", "freddy_gpu_debug_resolve_ids",
     "freddy_gpu_knn_join_ids", "freddy_gpu_ivpq_analogy",
+    "freddy_gpu_tokenize", "freddy_gpu_ivfadc_search_texts", "freddy_gpu_pq_search_texts", "freddy_gpu_exact_search_texts",
 ]
+TOK_MAX_LEN = 4096   # include/freddy_gpu.h FREDDY_TOK_MAX_LEN: ids per text
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
 STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together): ids per pass of freddy_gpu_create_statistics
 
@@ -177,7 +179,15 @@ def load(path=None, optional=()):
                                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
                         ("freddy_gpu_ivpq_analogy", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p])):
+                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
+                        # text vectors from token ids and the searches over them (the same again)
+                        ("freddy_gpu_tokenize", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_ivfadc_search_texts", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                            C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_pq_search_texts", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_exact_search_texts", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = types
     lib.freddy_gpu_pq_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
@@ -393,6 +403,33 @@ def _search_ids(ids, k, call):
     return out_q[:Q], out_i[:Q * k].reshape(Q, k), out_v[:Q * k].reshape(Q, k)
 
 
+def _texts(texts):
+    """The texts of a tokenize / search_texts call as (token_ids int32, offsets int64[n + 1]): a sequence of id sequences, or an
+    (ids, offsets) pair -- a TUPLE whose second member is a numpy array, the offsets."""
+    if isinstance(texts, tuple) and len(texts) == 2 and isinstance(texts[1], np.ndarray):
+        ids, off = _i32(texts[0]).reshape(-1), np.ascontiguousarray(texts[1], dtype=np.int64).reshape(-1)
+        if off.size < 1:
+            raise FreddyGpuError("offsets needs n_texts + 1 entries")
+        return ids, off
+    lens = [len(t) for t in texts]
+    off = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    ids = np.concatenate([_i32(t).reshape(-1) for t in texts]) if lens else np.empty(0, np.int32)
+    return _i32(ids), off
+
+
+def _search_texts(texts, k, call):
+    """The buffers of a search over texts: call(token_ids, offsets, n_texts, out_count, out_ids, out_values) -> (counts[n], ids[n,k],
+    values[n,k])."""
+    ids, off = _texts(texts)
+    n = off.size - 1
+    cnt = np.empty(max(n, 1), np.int32)
+    out_i = np.empty((max(n, 1), k), np.int32)
+    out_v = np.empty((max(n, 1), k), np.float32)
+    _check(call(ids, off, n, cnt, out_i, out_v))
+    return cnt[:n], out_i[:n], out_v[:n]
+
+
 class PQIndex(_Index):
     """pq_codebook + pq_quantization pinned in HBM."""
     kind = "pq"
@@ -435,6 +472,13 @@ class PQIndex(_Index):
         sub = None if subset_ids is None else _i32(subset_ids)
         return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_pq_search_ids(
             self.h, vecs.h, _p(q), n, rule, k, C.c_float(sentinel), _p(sub), 0 if sub is None else sub.size, _p(oq), C.byref(nq), _p(oi), _p(od)))
+
+    def search_texts(self, vecs, texts, k, sentinel=100.0, subset_ids=None, rule=QIDS_TABLE_ORDER):
+        """pq_search for the text vectors vecs.tokenize(texts) computes, which stay on the device (freddy_gpu_pq_search_texts):
+        (counts[n], ids[n,k], dist[n,k]); per text with a row list bit for bit search(<its vector>, k, ...), fillers for the others."""
+        sub = None if subset_ids is None else _i32(subset_ids)
+        return _search_texts(texts, k, lambda t, o, n, oc, oi, od: self.lib.freddy_gpu_pq_search_texts(
+            self.h, vecs.h, _p(t), _p(o), n, rule, k, C.c_float(sentinel), _p(sub), 0 if sub is None else sub.size, _p(oc), _p(oi), _p(od)))
 
     def search_pv_ids(self, vecs, ids, k, pvf, sentinel=100.0, subset_ids=None, rule=QIDS_TABLE_ORDER):
         """search_pv for the rows of `vecs` with these ids (freddy_gpu_pq_search_pv_ids): (query_ids[Q], ids[Q,k], similarity[Q,k])."""
@@ -565,6 +609,25 @@ class VectorIndex(_Index):
         sub = None if subset_ids is None else _i32(subset_ids).reshape(-1)
         return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_exact_search_ids(
             self.h, _p(q), n, rule, k, _p(sub), 0 if sub is None else sub.size, _p(oq), C.byref(nq), _p(oi), _p(od)))
+
+    def tokenize(self, texts, normalize=True, rule=QIDS_TABLE_ORDER):
+        """Text vectors from token ids (freddy_gpu_tokenize; tokenize() / tokenize_raw() of the SQL surface): texts is a sequence of
+        sequences of row ids of this table, or an (ids, offsets) pair -> (vectors[n,d], counts[n]).  The vector of a text is the
+        reference's centroid of its rows (rule: the distinct rows in table order, or the given rows in the given order), normalised
+        unless normalize is false; a text without a row has count 0 and a vector of zeros."""
+        ids, off = _texts(texts)
+        n = off.size - 1
+        out = np.empty((max(n, 1), self.d), np.float32)
+        cnt = np.empty(max(n, 1), np.int32)
+        _check(self.lib.freddy_gpu_tokenize(self.h, _p(ids), _p(off), n, rule, 1 if normalize else 0, _p(out), _p(cnt)))
+        return out[:n], cnt[:n]
+
+    def search_texts(self, texts, k, normalize=True, subset_ids=None, rule=QIDS_TABLE_ORDER):
+        """search() for the text vectors tokenize(texts, normalize, rule) computes, which stay on the device
+        (freddy_gpu_exact_search_texts): (counts[n], ids[n,k], similarity[n,k]); (-1, -inf) for a text without a row."""
+        sub = None if subset_ids is None else _i32(subset_ids).reshape(-1)
+        return _search_texts(texts, k, lambda t, o, n, oc, oi, od: self.lib.freddy_gpu_exact_search_texts(
+            self.h, _p(t), _p(o), n, rule, 1 if normalize else 0, k, _p(sub), 0 if sub is None else sub.size, _p(oc), _p(oi), _p(od)))
 
     def exact_join_ids(self, ids, k, target_ids, rule=QIDS_TABLE_ORDER):
         """join() for the rows of this table with these ids (freddy_gpu_exact_join_ids): (query_ids[Q], ids[Q,k], similarity[Q,k]); per
@@ -712,6 +775,12 @@ class IVFIndex(_Index):
         _check(self.lib.freddy_gpu_ivfadc_search_pv(self.h, vecs.h, _p(qs), Q, k, pvf, W, C.c_float(sentinel), found_rule,
                                                     _p(out_i), _p(out_s)))
         return out_i, out_s
+
+    def search_texts(self, vecs, texts, k, W, sentinel=1000.0, found_rule=FOUND_ROWS, rule=QIDS_TABLE_ORDER):
+        """ivfadc_search for the text vectors vecs.tokenize(texts) computes, which stay on the device (freddy_gpu_ivfadc_search_texts):
+        (counts[n], ids[n,k], dist[n,k]); per text with a row list bit for bit search(<its vector>, k, W, ...), fillers for the others."""
+        return _search_texts(texts, k, lambda t, o, n, oc, oi, od: self.lib.freddy_gpu_ivfadc_search_texts(
+            self.h, vecs.h, _p(t), _p(o), n, rule, k, W, C.c_float(sentinel), found_rule, _p(oc), _p(oi), _p(od)))
 
     def search_ids(self, vecs, ids, k, W, sentinel=1000.0, found_rule=FOUND_ROWS, rule=QIDS_TABLE_ORDER):
         """ivfadc_search for the rows of the VectorIndex `vecs` with these ids, gathered on the device (freddy_gpu_ivfadc_search_ids):

@@ -104,6 +104,23 @@ class Session:
         ids, v = _i32(ids), _f32(vectors)
         self._check(self.lib.freddy_load_vecs_original(self.h, _p(ids), _p(v), C.c_int64(ids.size), v.shape[1]))
 
+    def _tokenize(self, fn, texts, dim):
+        ids, off = _gpu._texts(texts)
+        n = off.size - 1
+        out = np.zeros((max(n, 1), int(dim)), np.float32)
+        cnt = np.zeros(max(n, 1), np.int32)
+        self._check(fn(self.h, _p(ids), _p(off), n, _p(out), _p(cnt)))
+        return out[:n], cnt[:n]
+
+    def tokenize_batch(self, texts, dim):
+        """tokenize(text) for a batch of texts, each a sequence of row ids of google_vecs_norm (or an (ids, offsets) pair):
+        (vectors[n, dim], counts[n]); dim = the table's dimension."""
+        return self._tokenize(self.lib.tokenize_batch, texts, dim)
+
+    def tokenize_raw_batch(self, texts, dim):
+        """tokenize_raw(text) the same way over google_vecs (load_vecs_original): centroids, not normalised."""
+        return self._tokenize(self.lib.tokenize_raw_batch, texts, dim)
+
     def load_pq(self, codebook, ids, codes):
         pos, code, vec, n, s = _entries(codebook)
         ids, codes = _i32(ids), _i16(codes)

@@ -730,6 +730,29 @@ int analogy_pair_direction(freddy_session_t* s, int32_t id1, int32_t id2, int32_
   return one_exact_analogy(s, s->orig, FREDDY_ANALOGY_PAIR_DIRECTION, id1, id2, id3, nullptr, 0, result);
 }
 
+// ---- tokenize / tokenize_raw for a batch of texts             freddy--0.0.1.sql:1512-1536 ----------------------------------
+// "SELECT vector FROM <table> WHERE word = ANY(tokens)": the distinct rows in table order (FREDDY_QIDS_TABLE_ORDER), their centroid,
+// normalised for tokenize(); the table is pinned on first use and the rows are read on the device (freddy_gpu_tokenize).  The entry
+// point came without a new ABI version and is bound weakly, as freddy_gpu_knn_join_ids above; it has no earlier path to fall back to,
+// so beside a library without it the two functions fail and say so.
+extern "C" int freddy_gpu_tokenize(freddy_gpu_index_t*, const int32_t*, const int64_t*, int32_t, int32_t, int32_t, float*, int32_t*) __attribute__((weak));
+static int tokenize_table(freddy_session_t* s, VecTable freddy_session::*table, const char* missing, int normalize, const int32_t* token_ids,
+                          const int64_t* offsets, int32_t n_texts, float* out_vectors, int32_t* out_count) {
+  if (!s) return fail(-1, "bad argument");
+  VecTable& t = s->*table;
+  if (t.empty()) return fail(-1, "%s is not loaded", missing);
+  if (!freddy_gpu_tokenize) return fail(-1, "the device library has no freddy_gpu_tokenize");
+  REQUIRE(t.pinned(s->device));
+  if (int rc = freddy_gpu_tokenize(t.h, token_ids, offsets, n_texts, FREDDY_QIDS_TABLE_ORDER, normalize, out_vectors, out_count)) return gpu_fail(rc);
+  return 0;
+}
+int tokenize_batch(freddy_session_t* s, const int32_t* token_ids, const int64_t* offsets, int32_t n_texts, float* out_vectors, int32_t* out_count) {
+  return tokenize_table(s, &freddy_session::norm, "google_vecs_norm", 1, token_ids, offsets, n_texts, out_vectors, out_count);
+}
+int tokenize_raw_batch(freddy_session_t* s, const int32_t* token_ids, const int64_t* offsets, int32_t n_texts, float* out_vectors, int32_t* out_count) {
+  return tokenize_table(s, &freddy_session::orig, "google_vecs", 0, token_ids, offsets, n_texts, out_vectors, out_count);
+}
+
 // EXECUTE format('SELECT * FROM %s(''%s'', ''%s'',''%s'')', get_analogy_function_name(), ...)
 int analogy(freddy_session_t* s, int32_t a, int32_t b, int32_t c, int32_t* result) {
   if (!s || !result) return fail(-1, "bad argument");
