@@ -22,6 +22,12 @@
 //   final add/fma  2 u (|q| + |c|)^2
 //   sum < 3.7e-5 (|q| + |c|)^2;   eps(q) = COARSE_EPS (|q| + max_j |c_j|)^2 with COARSE_EPS = 1.2e-4 (3x margin,
 //   and it would still hold if the matrix core TRUNCATED every accumulation step instead of rounding it).
+// Small magnitudes.  The f16-split tile (coarse_approx16_body) unscales its dot product by 2^-(eq + ec), a binary32 power of two
+// that is 0 once eq + ec >= 150: the largest |element| of the query times that of the centroids is then <= 2^-122, the dot
+// product the tile drops is |q.c| <= d 2^-122, and a is off by 2 |q.c| <= 1.9e-34 (d <= 512) -- nothing the relative terms
+// above know of, at distances (scale 2^-57 .. 2^-62) that are still normal numbers.  eps(q) therefore carries the absolute term
+// COARSE_EPS_ABS = 2e-34, which also covers every operation whose result is subnormal (absolute error 2^-149 each, a few
+// thousand of them).  At ordinary magnitudes it is rounded away: eps, the candidates and the lists are bit for bit what they were.
 // Every refined cell has both numbers in hand: the kernel counts the cells whose d left [a - eps, a + eps]
 // (freddy_gpu_filter_bound_violations; the tests also run with EVERY cell refined).
 #pragma once
@@ -35,6 +41,7 @@
 namespace freddy {
 
 static constexpr float COARSE_EPS = 1.2e-4f;
+static constexpr float COARSE_EPS_ABS = 2e-34f;   // the dot product lost to an underflowed unscale factor (above)
 static constexpr int COARSE_DP_ALIGN = 64;    // padded dimension count: whole blocks of 8 iterations x 8 dimensions (zeros)
 static constexpr int COARSE_TQ = 32;          // queries per MFMA tile (a workgroup = 32 queries x 128 cells)
 static constexpr int COARSE_MAX_CPAD = 1024;  // the plan keeps a query's approximate distances in registers: 16 per lane
@@ -485,7 +492,7 @@ __global__ __launch_bounds__(64 * NWP, NWP == 1 ? 4 : 4) void probe_plan2_kernel
   bool finite = true;
   if (wave == 0) {
     const float s = __builtin_sqrtf(g.qn2[q]) * (1.0f + 1e-6f) + g.cmax;
-    eps = s * s * COARSE_EPS;
+    eps = s * s * COARSE_EPS + COARSE_EPS_ABS;
     finite = eps < 1e30f;   // (false for NaN too)
     float thr = INF;
     if (finite && !g.refine_all) {

@@ -43,7 +43,9 @@ int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n, const std::vect
   const bool was_ok = ix->exf_ok;
   const int ex_before = ix->exf_ex;
   if (h[2] || !(n2 < 1e30f)) { ix->exf_ok = false; return 0; }
-  const float xn = std::sqrt(n2) * (1.0f + 1e-5f);
+  float tiny_norm;   // rows whose sum of squares is below EXF_N2_FLOOR: their bound comes from their largest |element| (exact2.h)
+  memcpy(&tiny_norm, &h[3], 4);
+  const float xn = std::max(std::sqrt(n2) * (1.0f + 1e-5f), tiny_norm);
   int64_t relayout_from = r0;
   if (first) { ix->exf_ok = true; ix->exf_xnorm = xn; ix->exf_ex = exf_scale_exp(amax); }
   else if (ix->exf_ok) {

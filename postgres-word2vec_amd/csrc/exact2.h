@@ -29,6 +29,18 @@
 //   MFMA accumulation    fp32, <= 64 roundings (19 steps x 3 products + in-step adds), doubled in case the matrix core
 //                        TRUNCATES instead of rounding: 128 u sum|terms|            <= 0.77e-5 |x||q|
 //   sum < 2.7e-5 |x||q|;   eps(q) = EXF_EPS X |q| with EXF_EPS = 4e-5 (d <= 512: the chain term grows to 3.1e-5 -> 6e-5).
+// Small magnitudes.  The similarity is bilinear, the norms are not: a table at 2^-80 searched with unit-scale queries has
+// similarities near 2^-80 (normal numbers the reference orders strictly) while every square of its elements is 0 in binary32.
+// A norm taken from a binary32 sum of squares alone would be 0 there and eps(q) would shrink to its floor, orders of magnitude
+// below the rounding of the reference's chain.  So X and |q| come from the sum of squares only where that sum is at least
+// EXF_N2_FLOOR = 2^-100 (the squares the chain lost to underflow, <= d 2^-150, are then within the 1e-5 the root is raised by);
+// below it the norm is bounded by sqrt(d) * (largest |element|), rounded up (exf_norm_from_amax) -- an upper bound for every
+// finite input, at most sqrt(d) wider than needed, in a range where only the number of candidates depends on it.
+// The floor of 1e-37 in eps(q) covers ONE thing: the product EXF_EPS X |q| itself rounding to 0 or to a subnormal with few bits
+// (both factors are sound upper bounds by then; every error term of the bracket is below 2.7e-5 |x||q| <= that product, so it
+// lies below 1e-37 too).  It does not stand in for a norm that underflowed.  One more absolute term: the scaled products are
+// unscaled by qunscale = 2^-(eq + ex), which is 0 from eq + ex = 150 on.  The largest |element| of the query times the table's
+// is then <= 2^-122, so |s| <= d 2^-122 < 1e-34 (d <= 512) for every row while a = 0: the floor is 1e-34 for such a query.
 // Every refined row has both numbers in hand: the refine kernel counts rows whose similarity left [a - eps, a + eps]
 // (freddy_gpu_filter_bound_violations on the vector handle; the tests refine EVERY row, option exact_refine_all).
 //
@@ -66,30 +78,59 @@ __host__ __device__ __forceinline__ int exf_scale_exp(float vmax) {
   return EXF_TARGET_EXP - e;   // vmax = f * 2^e, f in [0.5, 1)
 }
 
+// ---- norms where the squares underflow ------------------------------------------------------------------------------------
+static constexpr float EXF_N2_FLOOR = 7.8886090522101181e-31f;   // 2^-100: below it a binary32 sum of squares is no bound of the norm^2
+// sqrt(d) * amax, rounded up: |v| <= sqrt(d) max|v_i| for every v.  (sqrtf and the two products are within 3 ulps; where the
+// result is subnormal its rounding is absolute, half the smallest subnormal: one more ulp covers that.)
+__host__ __device__ __forceinline__ float exf_norm_from_amax(float amax, int d) {
+  if (!(amax > 0.0f)) return 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float r = __builtin_sqrtf((float)d);
+#else
+  const float r = sqrtf((float)d);
+#endif
+  const float b = (r * (1.0f + 1e-6f)) * amax;
+  uint32_t u;
+  __builtin_memcpy(&u, &b, 4);
+  if (u < 0x00800000u) ++u;          // (subnormal, positive: the next value up)
+  float out;
+  __builtin_memcpy(&out, &u, 4);
+  return out;
+}
+
 // ---- pin time: the table's largest |element| and largest row norm (both rounded up) ------------------------
-// out[0] = max |x_i| (bits, atomicMax on non-negative floats), out[1] = max row norm^2 (fp32 fma chain, bits); out[2] |= 1 if non-finite
+// out[0] = max |x_i| (bits, atomicMax on non-negative floats), out[1] = max row norm^2 (fp32 fma chain, bits) over the rows whose
+// sum reaches EXF_N2_FLOOR, out[3] = max exf_norm_from_amax(row) (bits) over the other rows; out[2] |= 1 if non-finite.  Both
+// maxima fold over slices of the table in any order (append_rows): the host takes the larger bound.
 __global__ __launch_bounds__(256) void exf_table_stats_kernel(const float* __restrict__ rows, int64_t n_rows, int d, uint32_t* __restrict__ out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float amax = 0.0f, nmax = 0.0f;
+  float amax = 0.0f, nmax = 0.0f, tiny_max = 0.0f;
   bool bad = false;
   for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n_rows; r += (int64_t)gridDim.x * 4) {
     const float* x = rows + (size_t)r * d;
-    float n2 = 0.0f;
+    float n2 = 0.0f, rmax = 0.0f;
     for (int i = lane; i < d; i += 64) {
       const float v = x[i];
       if (!(__builtin_fabsf(v) < 3e38f)) bad = true;
-      amax = fmaxf(amax, __builtin_fabsf(v));
+      rmax = fmaxf(rmax, __builtin_fabsf(v));
       n2 = __builtin_fmaf(v, v, n2);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n2 += __shfl_xor(n2, o, 64);
-    nmax = fmaxf(nmax, n2);
+    amax = fmaxf(amax, rmax);
+    if (n2 >= EXF_N2_FLOOR) nmax = fmaxf(nmax, n2);
+    else if (!(n2 != n2)) {            // (wave-uniform; a NaN sum is a non-finite row: `bad` answers for it)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) rmax = fmaxf(rmax, __shfl_xor(rmax, o, 64));
+      tiny_max = fmaxf(tiny_max, exf_norm_from_amax(rmax, d));
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
   if (lane == 0) {
     atomicMax(out + 0, __float_as_uint(amax));
     atomicMax(out + 1, __float_as_uint(nmax));
+    atomicMax(out + 3, __float_as_uint(tiny_max));
   }
   if (__ballot(bad) != 0ull && lane == 0) atomicOr(out + 2, 1u);
 }
@@ -166,8 +207,10 @@ __global__ __launch_bounds__(256) void exf_prep_kernel(ExfPrepArgs a) {
     const float nn = (red[4] + red[5]) + (red[6] + red[7]);
     const int eq = exf_scale_exp(am);
     eq_s = eq;
-    const float qn = __builtin_sqrtf(nn) * (1.0f + 1e-5f);
-    a.qeps[q] = live ? a.eps_factor * a.xmax_norm * qn * (1.0f + 1e-6f) + 1e-37f : 0.0f;
+    const float qn = nn >= EXF_N2_FLOOR ? __builtin_sqrtf(nn) * (1.0f + 1e-5f) : exf_norm_from_amax(am, a.d);   // (a NaN sum: a non-finite query, qbad)
+    // (eq + ex >= 150: qunscale is 0, every a of this query is 0 and cannot rank -- its error is |s| itself, <= d 2^-122 < 1e-34)
+    const float eps_floor = eq + a.ex >= 150 ? 1e-34f : 1e-37f;
+    a.qeps[q] = live ? a.eps_factor * a.xmax_norm * qn * (1.0f + 1e-6f) + eps_floor : 0.0f;
     a.qunscale[q] = __builtin_ldexpf(1.0f, -(eq + a.ex));
   }
   __syncthreads();

@@ -17,7 +17,9 @@ pytestmark = pytest.mark.gpu
 
 N, C, M, S, K_LIST, W, QMAX = 6000, 8, 12, 25, 5, 3, 48
 ZERO_POS, SPIKE_POS, SPIKE_CODE = 3, 7, 5
-SCALES = {"2^-20": 2.0 ** -20, "1": 1.0, "2^12": 2.0 ** 12}
+# 2^-64, 2^-80, 2^-140: the small end of binary32.  The distances are quadratic: at 2^-64 they are around 2^-128, subnormal, from
+# 2^-80 on most of them are 0 -- a list is decided by the scan order under massive ties, and the brackets have to hold all the same.
+SCALES = {"2^-20": 2.0 ** -20, "1": 1.0, "2^12": 2.0 ** 12, "2^-64": 2.0 ** -64, "2^-80": 2.0 ** -80, "2^-140": 2.0 ** -140}
 
 
 @pytest.fixture(scope="module")
@@ -68,6 +70,8 @@ def _variant(base, oracle, K, scale):
         ivf, pq = base[K]["ivf"], base[K]["pq"]
         qs = base["qs"] * s
         sent = float(1000.0 * s * s)
+        if 1000.0 * SCALES[scale] ** 2 < 2.0 ** -126:     # below binary32's normal range: the plain sentinel, or every list is fillers
+            sent = 1000.0
         v = dict(qs=qs, sentinel=sent, coarse=ivf["coarse"] * s, codebook=ivf["codebook"] * s, plain=ivf["plain"] * s,
                  pq_codebook=pq["codebook"] * s)
         ot = oracle.ivf_table(v["coarse"], v["codebook"], ivf["list_off"], ivf["ids"], ivf["codes"])
