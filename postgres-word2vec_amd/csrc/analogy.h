@@ -19,7 +19,7 @@
 //            finite normalised table; here such a row simply scores inf / NaN.  An unknown input id: the INNER JOIN is empty,
 //            every slot of that analogy is (-1, -inf) (the host resolves ids, no device work).
 //
-// Two paths (exact.hip: freddy_gpu_exact_analogy -> analogy_scan / analogy_filter; what the filter shares with exact kNN: exact_host.h):
+// Two paths (analogy.hip: freddy_gpu_exact_analogy -> analogy_scan / analogy_filter; what the filter shares with exact kNN: exact_host.h):
 //
 // ALL-EXACT (an_scan_kernel + an_merge_kernel): every eligible row's score from the reference's chains -- one query column
 //   per analogy for 3CosAdd, three for 3CosMul -- in exact_scan_kernel's style (64-row blocks, lane = row, columns in LDS).

@@ -56,7 +56,7 @@ struct AssignExactArgs {
   int n_targets, Q, d;
 };
 
-// (static: the header is included by two units, exact.hip launches it)
+// (static: the header is included by several units, cluster.hip launches it)
 static __global__ __launch_bounds__(64) void assign_exact_kernel(AssignExactArgs a) {
   __shared__ __attribute__((aligned(16))) float tile[TILE_FLOATS];     // [TILE_DCH][TILE_STRIDE]
   __shared__ __attribute__((aligned(16))) float qs[TILE_QFLOATS];      // [TILE_DCH][TILE_QT]

@@ -1,5 +1,5 @@
 // cluster.h -- what generic_cluster (freddy--0.0.1.sql:1086-1209) does between two assignment steps, on the device, so that the
-// whole k-means of cluster_exact / cluster_pq is one call (freddy_gpu_cluster, exact.hip; the contract: include/freddy_gpu.h):
+// whole k-means of cluster_exact / cluster_pq is one call (freddy_gpu_cluster, cluster.hip; the contract: include/freddy_gpu.h):
 //
 //   cluster_init_kernel    once per call.  One lane per position: the row of its token id in the vector handle (binary search over
 //       the handle's ascending device ids, row_of_id), clusters[i] = 0, and the smallest position whose id has no row into the

@@ -45,9 +45,10 @@ __device__ __forceinline__ float key_sim(u64 key) {
 }
 
 // rows [N][d] -> xb[block][d][64] (zero padded); pos_out[i] = source row or -1
-__global__ __launch_bounds__(256) void block_rows_kernel(const float* __restrict__ src, const int32_t* __restrict__ rows,
-                                                        int64_t n_rows, float* __restrict__ xb, int32_t* __restrict__ pos_out,
-                                                        int d) {
+// (static: the header is included by three units, exact.hip launches it)
+static __global__ __launch_bounds__(256) void block_rows_kernel(const float* __restrict__ src, const int32_t* __restrict__ rows,
+                                                               int64_t n_rows, float* __restrict__ xb, int32_t* __restrict__ pos_out,
+                                                               int d) {
   const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);   // output row
   const int part = threadIdx.x >> 6;                                   // 4 dimension slices
   const int64_t r = (i < n_rows) ? (rows ? rows[i] : i) : -1;

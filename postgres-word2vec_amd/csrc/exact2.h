@@ -102,7 +102,8 @@ __host__ __device__ __forceinline__ float exf_norm_from_amax(float amax, int d) 
 // out[0] = max |x_i| (bits, atomicMax on non-negative floats), out[1] = max row norm^2 (fp32 fma chain, bits) over the rows whose
 // sum reaches EXF_N2_FLOOR, out[3] = max exf_norm_from_amax(row) (bits) over the other rows; out[2] |= 1 if non-finite.  Both
 // maxima fold over slices of the table in any order (append_rows): the host takes the larger bound.
-__global__ __launch_bounds__(256) void exf_table_stats_kernel(const float* __restrict__ rows, int64_t n_rows, int d, uint32_t* __restrict__ out) {
+// (static, as the other plain kernels of this header: two units include it -- exact.hip launches this one)
+static __global__ __launch_bounds__(256) void exf_table_stats_kernel(const float* __restrict__ rows, int64_t n_rows, int d, uint32_t* __restrict__ out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float amax = 0.0f, nmax = 0.0f, tiny_max = 0.0f;
   bool bad = false;
@@ -141,8 +142,8 @@ __global__ __launch_bounds__(256) void exf_table_stats_kernel(const float* __res
 // row.  A wave's operand load for one k-step is two fully coalesced 1 KB reads (row-major rows, 1200 bytes apart, cost
 // 64 cache-line lookups per load instruction: 4.7 instead of 6.0 TB/s -- measured with lane-linear addresses), and the
 // conversion leaves the kernel.  Same bytes as the fp32 rows.
-__global__ __launch_bounds__(256) void exf_layout_kernel(const float* __restrict__ rows, int64_t n_rows, int d, int T, int ex,
-                                                        int64_t strip0, int64_t n_strips, const int32_t* __restrict__ strip_list, h8v* __restrict__ xf) {
+static __global__ __launch_bounds__(256) void exf_layout_kernel(const float* __restrict__ rows, int64_t n_rows, int d, int T, int ex,
+                                                               int64_t strip0, int64_t n_strips, const int32_t* __restrict__ strip_list, h8v* __restrict__ xf) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;      // (strip - strip0, t, lane); strip_list: its n_strips entries instead of the range
   if (i >= n_strips * T * 64) return;
   const int lane = (int)(i & 63);
@@ -180,7 +181,8 @@ struct ExfPrepArgs {
   int32_t* qbad;          // [1] |= 1 if a query is not finite
   float* copy_out;        // NULL, or [nq][d]: `queries` is mapped host memory -- read once here, the refine kernel reads this copy
 };
-__global__ __launch_bounds__(256) void exf_prep_kernel(ExfPrepArgs a) {
+// (static: exact.hip and analogy.hip both launch it, each its own copy)
+static __global__ __launch_bounds__(256) void exf_prep_kernel(ExfPrepArgs a) {
   const int q = blockIdx.x;        // 0 .. EXF_QT-1
   const int tid = threadIdx.x;
   __shared__ float red[8];
@@ -375,7 +377,7 @@ struct ExfThrArgs {
   int32_t* cand_cnt;       // [EXF_QT] <- 0 (the filter pass behind this launch counts from there)
 };
 static constexpr int EXF_TW = 16;   // waves per query of the threshold and refine kernels (one query: the launch is one workgroup)
-__global__ __launch_bounds__(64 * EXF_TW) void exf_threshold_kernel(ExfThrArgs a) {
+static __global__ __launch_bounds__(64 * EXF_TW) void exf_threshold_kernel(ExfThrArgs a) {
   __shared__ u64 stage[EXF_TW][64];
   __shared__ u64 lists[EXF_TW][64];
   __shared__ int nan_s[EXF_TW];

@@ -1,14 +1,21 @@
-// exact_host.h -- the host-side sequences that the entry points of exact.hip share (included by exact.hip alone, after the kernel
-// headers): the filter + refine chain of exact kNN and the exact join with the handle's state it runs on, the chunking of the
-// all-exact scans, the re-rank stage of post verification and the approximate analogies, and the INNER JOIN of analogy triples.
+// exact_host.h -- the host-side sequences that exact.hip and analogy.hip share (included after their kernel headers): the filter +
+// refine chain of exact kNN and the exact join with the handle's state it runs on, when a call takes it, and the chunking of the
+// all-exact scans.
 #pragma once
 
 #include "internal.h"
 #include "exact2.h"
-#include "pv.h"
-#include "approx_analogy.h"
 
 // ---- filter + refine (exact2.h, exact_join.h, analogy.h) -----------------------------------------------------------------
+// Under option exact_filter = -1 (auto) a whole table takes filter + refine from this many rows on.
+static constexpr int64_t EXF_AUTO_ROWS = 8192;
+// What exact kNN, the exact join and the exact analogies all ask before they take filter + refine: the handle has the filter's copy
+// of its rows, the option does not forbid it, and it is forced or the set has `auto_rows` rows.  What else a call asks (k, no
+// subset, the LDS its tiles take) stands at the call.
+static bool exf_wanted(const freddy_gpu_index* ix, int64_t n_rows, int64_t auto_rows = EXF_AUTO_ROWS) {
+  return ix->exf_ok && ix->tune.exact_filter != 0 && (ix->tune.exact_filter == 1 || n_rows >= auto_rows);
+}
+
 // What the filter passes over a set of rows share.  The threshold's sample: whole 32-row strips of REAL rows (a zero-padded row
 // would be a similarity of 0 that no row has), spread evenly over the set; the candidate buffer: 8192 rows per query (every row
 // under the self-check that refines every row).
@@ -123,68 +130,4 @@ static int scan_chunks(int64_t n_blocks, int groups, int* chunk_blocks) {
   while ((n_blocks + cb - 1) / cb * (int64_t)groups > 8192 && cb < 1024) cb *= 2;
   *chunk_blocks = cb;
   return (int)std::max<int64_t>(1, (n_blocks + cb - 1) / cb);
-}
-
-// ---- the re-rank stage of post verification and the approximate analogies (pv.h, approx_analogy.h) ----------------------------
-// Queries (triples) per pass: stage one's lists of `n_cand` entries hold at most 8 M entries
-static int rerank_pass(int64_t n, int n_cand) { return (int)std::min<int64_t>(n, std::max<int64_t>(1, ((int64_t)8 << 20) / n_cand)); }
-
-// The pinned block of one pass of Qc queries: [stage one's lists][the result lists][per-query counts]; the approximate analogies put
-// their unit rows (padded to 16 bytes) in front and the input rows and ids behind.
-struct RerankBlock {
-  float *unit, *l_dist, *o_sim;
-  int32_t *l_ids, *o_ids, *o_cnt, *p_rows, *p_excl;
-};
-static int rerank_block(freddy_gpu_index* ann, int Qc, int n_cand, int k, bool analogy, const char* call, RerankBlock* b) {
-  const int d = ann->d;
-  const size_t n_unit = analogy ? ((size_t)Qc * d + 3) / 4 * 4 : 0, n_list = (size_t)Qc * n_cand, n_out = (size_t)Qc * k;
-  if (ann->pv_io.ensure(4 * (n_unit + 2 * n_list + 2 * n_out + 2 * (size_t)Qc + (analogy ? 6 * (size_t)Qc : 0))) || ann->pv_q.ensure(sizeof(float) * (size_t)Qc * d))
-    return fail(FREDDY_E_NOMEM, "%s: staging allocation failed", call);
-  b->unit = ann->pv_io.as<float>();
-  b->l_ids = reinterpret_cast<int32_t*>(b->unit + n_unit); b->l_dist = reinterpret_cast<float*>(b->l_ids + n_list);
-  b->o_ids = b->l_ids + 2 * n_list; b->o_sim = reinterpret_cast<float*>(b->o_ids + n_out);
-  b->o_cnt = b->o_ids + 2 * n_out;
-  b->p_rows = b->o_cnt + 2 * (size_t)Qc; b->p_excl = b->p_rows + 3 * (size_t)Qc;
-  return 0;
-}
-// The re-rank of `nq` lists of the block against the raw queries in pv_q, by pv_rerank_kernel<NW> or aa_rerank_kernel<NW> (which
-// leaves out the ids at `exclude`): k1 = <1>, one wave per query, for lists of up to 64 entries, k4 = <4> beyond.
-using RerankKernel = void (*)(PvArgs);
-static int launch_rerank(freddy_gpu_index* ann, const freddy_gpu_index* vecs, hipStream_t s, const char* label, RerankKernel k1, RerankKernel k4,
-                         const RerankBlock& b, const int32_t* exclude, int nq, int n_cand, int k) {
-  const int d = ann->d, P = pv_pad(n_cand);
-  PvArgs pa;
-  pa.cand = b.l_ids; pa.vec_ids = vecs->ids; pa.rows = vecs->coarse; pa.queries = ann->pv_q.as<float>(); pa.exclude = exclude; pa.out_ids = b.o_ids;
-  pa.out_sim = b.o_sim; pa.counts = b.o_cnt; pa.N = vecs->N; pa.n_cand = n_cand; pa.k = k; pa.d = d; pa.P = P;
-  timed_launch(ann, s, label, [&] {
-    if (P == 64) hipLaunchKernelGGL(k1, dim3((unsigned)nq), dim3(64), pv_lds_bytes(1, P, d), s, pa);
-    else hipLaunchKernelGGL(k4, dim3((unsigned)nq), dim3(256), pv_lds_bytes(4, P, d), s, pa);
-  });
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-// ---- analogy triples -> table rows -----------------------------------------------------------------------------------------------
-// The INNER JOINs of the analogy entry points: a triple with an unknown id has no rows at all; the others, compacted -- live: their
-// positions in the call, rows3 / ids3 (optional): their three table rows / ids.  h_ids is strictly ascending (pin_vectors); serial ids
-// (last - first + 1 of them) make the row a subtraction: 3 Q binary searches over millions of ids cost more than a batch's device work.
-static void resolve_triples(const std::vector<int32_t>& h_ids, const int32_t* triples, int32_t Q, std::vector<int32_t>& live, std::vector<int32_t>& rows3,
-                            std::vector<int32_t>* ids3 = nullptr) {
-  const bool serial = !h_ids.empty() && (int64_t)h_ids.back() - h_ids.front() + 1 == (int64_t)h_ids.size();
-  auto row = [&](int32_t id) -> int32_t {
-    if (serial) return id >= h_ids.front() && id <= h_ids.back() ? id - h_ids.front() : -1;
-    return row_of(h_ids, id);
-  };
-  live.reserve((size_t)Q); rows3.reserve((size_t)Q * 3);
-  if (ids3) ids3->reserve((size_t)Q * 3);
-  for (int32_t q = 0; q < Q; ++q) {
-    const int32_t* t = triples + (size_t)q * 3;
-    int32_t r[3];
-    bool ok = true;
-    for (int m = 0; m < 3 && ok; ++m) ok = (r[m] = row(t[m])) >= 0;
-    if (!ok) continue;
-    live.push_back(q);
-    rows3.insert(rows3.end(), r, r + 3);
-    if (ids3) ids3->insert(ids3->end(), t, t + 3);
-  }
 }

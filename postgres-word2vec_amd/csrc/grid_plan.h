@@ -1,6 +1,6 @@
 // grid_plan.h -- every launch whose grid, or whose choice of kernel, comes from the handle's CU count (freddy_gpu_index::n_cus:
 // the device's count, or less under option grid_cus): the formulas as pure functions of (n_cus, work sizes, options), one
-// statement of each.  ivfadc.hip, pq.hip, exact.hip and exact_host.h call them; the kernels behind them loop over the work a
+// statement of each.  ivfadc.hip, pq.hip, exact.hip and its sibling units and exact_host.h call them; the kernels behind them loop over the work a
 // smaller grid leaves (grid-stride loops, work counters, units dealt round G workgroups), so no value of n_cus >= 1 changes a
 // result -- tests/test_gpu_grid_cus.py runs them at 1, 2, 3 and 7.
 // Plain C++17, no HIP, so that tests/test_grid_inputs_cpu.py compiles this file on its own with g++ (as block_plan.h is).

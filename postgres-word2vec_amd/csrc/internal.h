@@ -9,10 +9,16 @@
 //               ivf_host.h what these two share on the host: shape predicates and sizes, the query table's layout, the run state of a chain, merge arguments
 //   join.hip    pin_ivpq, knn_join (join.h: overview; join_kernels.h and join_traverse.h the kernels, join_host.h the host heap, join_run.h the run
 //               record of a call and its stages)
-//   exact.hip   pin_vectors, exact kNN, the exact join, analogies, post verification of pq / ivf lists (pv.h), approximate analogies (approx_analogy.h),
-//               exact_assign (assign.h), the whole k-means of cluster_exact / cluster_pq (cluster.h), similarities by row id (similarity.h), text vectors from token ids and the searches over them (tokenize.h); exact_host.h the host sequences they share: the filter + refine chain, scan chunking, the re-rank stage, triple resolution
+//   exact.hip   pin_vectors, exact kNN and the exact join (also by row id: query_ids.h, resolve.h), the rows of an id set
+//   analogy.hip the exact analogies (analogy.h), the INNER JOIN of analogy triples
+//               exact_host.h what these two share on the host: the filter + refine chain and when a call takes it, scan chunking
+//   rerank.hip  post verification of pq / ivf lists (pv.h), the approximate analogies over pq / ivf / ivpq (approx_analogy.h), the re-rank stage they share
+//   cluster.hip exact_assign (assign.h), the whole k-means of cluster_exact / cluster_pq (cluster.h)
+//   similarity.hip  similarities by row id: pairs, matrices, joins (similarity.h)
+//   tokenize.hip    text vectors from token ids and the searches over them (tokenize.h)
 //   build.hip   encode, insert_quantize, k-means
-// Kernel headers are included by the unit that launches them (kernels shared by two units are static or templates).
+// Kernel headers are included by the unit that launches them (kernels shared by two units are static or templates).  A kernel with
+// an LDS limit is compiled into ONE unit, whose lds_limits_*() names it: the limit belongs to that unit's copy of the function.
 #pragma once
 #include "../../include/freddy_gpu.h"
 
@@ -351,6 +357,16 @@ int check_search_args(const freddy_gpu_index* ix, int kind, const void* q, int Q
 // analogies, the searches by row id).
 static inline int check_list_count(int Q, int k) { return (Q < 0 || k <= 0) ? fail(FREDDY_E_ARG, "Q must be >= 0 and k > 0") : 0; }
 static inline int check_list_limit(int k) { return k > 4096 ? fail(FREDDY_E_LIMIT, "k=%d exceeds this build's limit of 4096", k) : 0; }
+// a raw-vector handle that a call reads: there, of that kind, not poisoned
+static inline int check_vec_handle(const freddy_gpu_index* ix) {
+  if (!ix) return fail(FREDDY_E_ARG, "NULL index");
+  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  return refuse_poisoned(ix);
+}
+// the id set of the calls that pass one on to a search of their own (post verification, the approximate analogies, the searches by texts)
+static inline int pv_check_subset(const int32_t* subset_ids, int64_t n_subset) {
+  return (n_subset < 0 || (n_subset > 0 && !subset_ids)) ? fail(FREDDY_E_ARG, "bad subset (n_subset=%lld)", (long long)n_subset) : 0;
+}
 static inline int check_probe_args(int W, int found_rule) {
   if (W <= 0) return fail(FREDDY_E_ARG, "W must be positive");
   if (found_rule < 0 || found_rule > 2 || (found_rule == FREDDY_FOUND_BATCH_UDF && W != 1))
@@ -405,6 +421,8 @@ std::vector<LdsLimit> lds_limits_ivfadc();
 std::vector<LdsLimit> lds_limits_pq();
 std::vector<LdsLimit> lds_limits_join();
 std::vector<LdsLimit> lds_limits_exact();
+std::vector<LdsLimit> lds_limits_analogy();
+std::vector<LdsLimit> lds_limits_rerank();
 
 // ---- ivfadc.hip ----
 namespace freddy { struct PlanArgs; struct ScanArgs; struct MergeArgs; }
@@ -453,6 +471,26 @@ int pq_assign_pass(freddy_gpu_index* ix, hipStream_t s, float* d_lut, int Qc, in
 
 // ---- exact.hip ----
 int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n, const std::vector<int32_t>* changed_strips = nullptr);
+// Where the table rows of "id = ANY(set)" are: the host vector rows_of_ids made (every function then does exactly what it did
+// before), or already in ws->w_sub_rows, `resident` of them, put there by resolve_ids_device -- the copy to the device is skipped.
+// The buffer was sized for min(n_ids, N) >= resident rows before the resolve was launched, and DevBuf::ensure leaves a buffer
+// that is large enough where it is: the consumers' own ensure() calls for `resident` rows do not move it.
+struct RowSet {
+  const std::vector<int32_t>* host = nullptr;
+  int64_t resident = 0;
+  static RowSet of_host(const std::vector<int32_t>& rows) { RowSet r; r.host = &rows; return r; }
+  static RowSet on_device(int64_t n) { RowSet r; r.resident = n; return r; }
+  int64_t size() const { return host ? (int64_t)host->size() : resident; }
+};
+// what exact kNN, the exact join and the exact analogies (analogy.hip) do with an id set
+int resolve_row_set(freddy_gpu_index* ix, bool on_device, const int32_t* ids, int64_t n, std::vector<int32_t>* h_rows, RowSet* out);
+int vec_subset(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const RowSet& rows, const float** xb, const int32_t** pos, int64_t* n_rows,
+               int64_t* n_blocks);
+
+// ---- analogy.hip ----
+// the triples of an analogy call that have rows (the exact analogies, and the approximate ones of rerank.hip)
+void resolve_triples(const std::vector<int32_t>& h_ids, const int32_t* triples, int32_t Q, std::vector<int32_t>& live, std::vector<int32_t>& rows3,
+                     std::vector<int32_t>* ids3 = nullptr);
 
 template <class F>
 static int over_replicas(freddy_gpu_index* ix, int Q, F&& fn) {

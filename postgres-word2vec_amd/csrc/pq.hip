@@ -563,7 +563,7 @@ int pq_assign_lut_queries(const freddy_gpu_index* ix, int Q) {
 
 // One pass of n targets with everything on the device: the queries, the target ids, the three state arrays and the LUT buffer of Qc
 // LUTs (*lut_q0: the first query of the chunk whose LUTs it holds, -1 = none; kept between the passes of a call).  Enqueued on s;
-// best / sim hold the result behind the last launch.  freddy_gpu_pq_assign and freddy_gpu_cluster (exact.hip) both assign through it.
+// best / sim hold the result behind the last launch.  freddy_gpu_pq_assign and freddy_gpu_cluster (cluster.hip) both assign through it.
 int pq_assign_pass(freddy_gpu_index* ix, hipStream_t s, float* d_lut, int Qc, int* lut_q0, const float* d_queries, int Q, float sentinel,
                    const int32_t* d_targets, int n, int32_t* d_best, float* d_sim, float* d_best_dist) {
   const int m = ix->m, K = ix->K, d = ix->d;

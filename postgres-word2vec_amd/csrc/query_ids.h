@@ -1,5 +1,5 @@
 // query_ids.h -- searches whose queries are rows of a pinned vector table, named by id (freddy_gpu_*_search_ids, include/freddy_gpu.h):
-// what ivfadc.hip, pq.hip and exact.hip share for them.
+// what ivfadc.hip, pq.hip, exact.hip and rerank.hip share for them (similarity.hip: the gather).
 //   QuerySrc             where the queries of a host-buffer search come from: the caller's floats, or (device table, row numbers).  Every place
 //                        that read the caller's host pointer takes one; with `host` set it does exactly what it did before.
 //   query_gather_kernel  rows[0..n) of the row-major table [N][d] -> a contiguous query block [n][d].  The row numbers arrive in the
@@ -165,7 +165,7 @@ static int search_selected_ids(const freddy_gpu_index* vecs, const int32_t* quer
                               [&](const int32_t* rows, int n, int32_t* oi, float* ov) { return search(QuerySrc::of_rows(vecs, rows), n, oi, ov); });
 }
 
-// ---- join.hip: the kNN-join for the approximate analogy over an ivpq handle (exact.hip freddy_gpu_ivpq_analogy) ---------------------
+// ---- join.hip: the kNN-join for the approximate analogy over an ivpq handle (rerank.hip freddy_gpu_ivpq_analogy) ---------------------
 // knn_join_check: what freddy_gpu_knn_join refuses about its scalars and its shape (nothing touches a device).  join_query_block_for: the
 // join's query block with room for Q queries, for a kernel of the caller's to fill on the handle's stream; knn_join_block: the join over
 // the first Q queries of that block (arguments already checked), enqueued behind whatever filled it -- no host synchronisation before.

@@ -87,7 +87,7 @@ def pv_max_cand():
     return constant("pv.h", "PV_MAX_CAND")
 
 
-EXF_AUTO_ROWS = 8192   # exact.hip: "exact_filter == 1 || n_rows >= 8192" (a literal there, in the three entry points)
+EXF_AUTO_ROWS = constant("exact_host.h", "EXF_AUTO_ROWS")   # exf_wanted: "exact_filter == 1 || n_rows >= auto_rows" of the three entry points
 
 
 def filter_eligible(d):

@@ -248,10 +248,10 @@ def test_knn_join(gpu, oracle, tabs, method):
 # =======================================================================================
 # raw vectors
 # =======================================================================================
-# floors (exact.hip, exact_host.h): the filter chain: exf_qfrag, exf_sample, exf_cand (:103) + viol (ensure_viol) + hio_out (:222) = 5;
-# all-exact: w_q, w_out_ids, w_out_dist, w_part (:248) = 4; analogy: w_rows, w_out_ids, w_out_dist, w_cnt (:606) = 4; exact join: the
-# smaller of its two paths -- vec_subset's w_sub_rows, w_sub_pos, w_resid (:184) + the four of the all-exact scan = 7 (the filter's
-# path, :347-350, has nine); exact_assign: w_q, w_sub_rows, w_out_ids, w_out_dist (:850) = 4
+# floors (exact.hip, exact_host.h): the filter chain: exf_qfrag, exf_sample, exf_cand (exact_filter_search) + viol (ensure_viol) + hio_out (exact_search_rows) = 5;
+# all-exact: w_q, w_out_ids, w_out_dist, w_part (exact_search_rows) = 4; analogy: w_rows, w_out_ids, w_out_dist, w_cnt (analogy.hip) = 4;
+# exact join: the smaller of its two paths -- vec_subset's w_sub_rows, w_sub_pos, w_resid + the four of the all-exact scan = 7 (the
+# filter's path, exact_join_filter, has nine); exact_assign: w_q, w_sub_rows, w_out_ids, w_out_dist (cluster.hip) = 4
 @pytest.mark.parametrize("form", ["filter_on", "filter_off", "analogy", "join", "assign"])
 def test_exact_calls(gpu, oracle, tabs, form):
     ids, xv = tabs["vec64"]
@@ -289,7 +289,7 @@ def test_exact_calls(gpu, oracle, tabs, form):
 
 
 # =======================================================================================
-# two handles: post verification and the approximate analogies (exact_host.h:141: pv_io + pv_q = 2, and the search's own buffers)
+# two handles: post verification and the approximate analogies (rerank.hip rerank_block: pv_io + pv_q = 2, and the search's own buffers)
 # =======================================================================================
 @pytest.mark.parametrize("ann", ["ivf", "pq"])
 @pytest.mark.parametrize("what", ["search_pv", "analogy"])

@@ -250,7 +250,7 @@ def test_refusals_leave_the_outputs_alone(tabs):
 # ---- allocation failures -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("method", ["exact", "pq"])
 def test_every_allocation_fails_once(tabs, oracle, method):
-    """FLOORS (exact.hip freddy_gpu_cluster): ids, rows, clusters, best, sim, centroids, lens + flag, draws, per-block members = 9; pq: +
+    """FLOORS (cluster.hip freddy_gpu_cluster): ids, rows, clusters, best, sim, centroids, lens + flag, draws, per-block members = 9; pq: +
     the smallest distances and the LUTs = 11 (and what launch_lut needs)."""
     from freddy_amd import gpu
     t = tabs

@@ -1,6 +1,6 @@
 """-m gpu: every allocation of freddy_gpu_similarity_pairs / _matrix / _join fails once (the allocation seam, csrc/alloc_hook.h),
 test_gpu_alloc_failures.py's frame for calls that change no table: the call runs once on a cold handle with the seam's counter read
-around it (A allocations, at least the FLOOR counted in csrc/exact.hip); then for every n in 1 .. A a fresh handle is pinned, the n-th
+around it (A allocations, at least the FLOOR counted in csrc/similarity.hip); then for every n in 1 .. A a fresh handle is pinned, the n-th
 allocation from now fails, the call must return FREDDY_E_NOMEM with a message and exactly one failed allocation, the handle must not
 be poisoned, and the same call made again must answer as the model does."""
 import ctypes as C
@@ -40,7 +40,7 @@ def _same(got, exp):
     return len(got) == len(exp) and all(sm.same_floats(g, e) if np.asarray(e).dtype == np.float32 else np.array_equal(g, e) for g, e in zip(got, exp))
 
 
-# FLOORS (exact.hip): pairs -- the two id arrays, the values, the known bytes = 4;  matrix -- B ids, B rows, known_b, the A block, the
+# FLOORS (similarity.hip): pairs -- the two id arrays, the values, the known bytes = 4;  matrix -- B ids, B rows, known_b, the A block, the
 # result block = 5, + A's known bytes and the pinned row numbers when A is named by ids = 7;  join -- the matrix's, + counts and offsets,
 # + the three arrays of matches when any are written
 def _scenarios():

@@ -22,7 +22,7 @@ def gpu():
 
 
 def filter_serves(d, call):
-    """Whether filter + refine answers the call (exact.hip: want_filter of the three entry points; analogy.h: an_filter_lds): the
+    """Whether filter + refine answers the call (exf_wanted, exact_host.h, and want_filter of the three entry points in exact.hip / analogy.hip; analogy.h: an_filter_lds): the
     condition under which a refine-all run must have compared rows with their brackets."""
     if not si.filter_eligible(d["d"]):
         return False
