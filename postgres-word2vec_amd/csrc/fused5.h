@@ -62,6 +62,7 @@ namespace freddy {
 
 // (FILT5_VMAX, filter_width5: refine.h, next to the merge that shares them)
 static constexpr int SCAN5_G = 16;   // items per work entry
+static constexpr int SCAN5_PROF_WGS = 1024;   // lab builds: workgroups the counters' buffer holds (two tables of 8 counters each)
 
 // The table stores v + bias(p) >= 0 with sum_p bias(p) = 2^15 (m = 12: 2731 for the first eight positions, 2730 for the
 // others): a (row, item) sum is then an UNSIGNED 16-bit field in [8, 65528] at every step, so two fields per register are
@@ -528,40 +529,32 @@ __device__ __forceinline__ void ivf_filter5_body(const FilterArgs& a) {
         lds_barrier();
         tick(1);
       }
-      // S1: thresholds tau + E (builder wave w: items w and w + 8), while the gatherers are in their tail
-      if (!(a.fence & 4)) {
-        const int32_t* rec = dsc + cur * REC_DW;
-        const int cnt = __builtin_amdgcn_readfirstlane(rec[1]);
-        const int i0 = wave, i1 = wave + NG;
-        if (i0 < cnt) {
-          uint32_t c0 = colmin[i0 * 64 + lane], c1 = colmin[i1 * 64 + lane];
-          wave_sort32_x2(c0, c1);   // (order-preserving keys of the float column minima)
-          uint32_t t0 = __shfl(c0, a.Lt - 1, 64), t1 = __shfl(c1, a.Lt - 1, 64);
-          if (lane == 0) {
-            if (a.tau_run) {
-              // The query's running bound (FilterArgs::tau_run).  tau' + A_up of this (item, chunk) is reported (no answer is
-              // waited for); the bound read at the start of the last phase -- whatever other workgroups had reported by
-              // then -- lowers this item's cut to bound - A_lo.  Why any such value is valid: tau' is at least the k-th smallest s'
-              // of the chunk (k = a.Lt, the threshold rank), s' + A is the cheap distance up to the item-independent part of its
-              // error, and the k-th smallest over MORE rows is never larger -- so every reported value is an upper bound of the
-              // query's k-th smallest cheap distance D_k, and the rows that can matter have s' + A <= D_k + 2 e.  (The three float roundings here are
-              // below 10 u B of the 2.2 e = 230 u B + 13 T that E leaves over 2 e.)
-              auto lower = [&](uint32_t t, int i, uint32_t inv) -> uint32_t {
-                // (only a value that improves on what was read goes out: see running_bound5)
-                return running_bound5(a.tau_run, (uint32_t)rec[24 + i], t, __int_as_float(rec[144 + i]), __int_as_float(rec[160 + i]), inv);
-              };
-              t0 = lower(t0, i0, run0);
-              if (i1 < cnt) t1 = lower(t1, i1, run1);
-            }
-            thr_s[i0] = a.keep_all ? 0x7f800000u : widen_threshold5(t0, __int_as_float(rec[56 + i0]));
-            thr_s[i1] = a.keep_all ? 0x7f800000u : widen_threshold5(t1, __int_as_float(rec[56 + i1]));
-          }
-          colmin[i0 * 64 + lane] = 0xffffffffu;
-          colmin[i1 * 64 + lane] = 0xffffffffu;
+      // S1: thresholds tau + E, one item segment at a time while the gatherers are in their tail on the OTHER segment (builder wave w:
+      // item w between the gatherers' barriers T1 and T2, item w + 8 -- entries of more than 8 items -- between T2 and T3).
+      // The query's running bound (FilterArgs::tau_run; running_bound5, filter_threshold5).  tau' + A_up of this (item, chunk) is
+      // reported (no answer is waited for); the bound read at the start of the last phase -- whatever other workgroups had
+      // reported by then -- lowers this item's cut to bound - A_lo.  Why any such value is valid: tau' is at least the k-th smallest
+      // s' of the chunk (k = a.Lt, the threshold rank), s' + A is the cheap distance up to the item-independent part of its error,
+      // and the k-th smallest over MORE rows is never larger -- so every reported value is an upper bound of the query's k-th
+      // smallest cheap distance D_k, and the rows that can matter have s' + A <= D_k + 2 e.  (The three float roundings here are
+      // below 10 u B of the 2.2 e = 230 u B + 13 T that E leaves over 2 e.)  Item w reports before item w + 8, as it always did.
+      const int32_t* rec_t = dsc + cur * REC_DW;
+      const int cnt_t = __builtin_amdgcn_readfirstlane(rec_t[1]);
+      auto threshold = [&](int i, uint32_t run) {
+        if (i < cnt_t && !(a.fence & 4)) {
+          const uint32_t c = wave_sort32(colmin[i * 64 + lane]);   // (order-preserving keys of the float column minima)
+          const uint32_t t = __shfl(c, a.Lt - 1, 64);
+          if (lane == 0) thr_s[i] = filter_threshold5(a, rec_t, i, t, run);
+          colmin[i * 64 + lane] = 0xffffffffu;
         }
+      };
+      threshold(wave, run0);
+      lds_barrier();   // T2
+      if (cnt_t > 8) {
+        threshold(wave + NG, run1);
+        lds_barrier();   // T3
       }
-      lds_barrier();   // S1
-      stash_row_terms();   // (the gatherers took the current entry's into registers before their S1 barrier)
+      stash_row_terms();   // (the gatherers took the current entry's into registers before T1)
       lds_barrier();   // S2
       tick(3);
       if constexpr (PROF) pt[7] += 1;
@@ -602,7 +595,9 @@ __device__ __forceinline__ void ivf_filter5_body(const FilterArgs& a) {
     };
     prefetch_first_codes(dsc);
     lds_barrier();   // (pairs with the builders' barrier after the first slab)
-    long long gt[3] = {0, 0, 0}, gc = 0;
+    // (PROF slots: 0 main loop, 1 column minima, 2 survivor pass; 3, 4, 5 the waits at the tail's barriers T1, T2, T3; 6 the wait at
+    // the entry's last barrier; 7 entries of more than 8 items)
+    long long gt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gc = 0;
     auto gtick = [&](int slot) { if constexpr (PROF) { const long long t = clock64(); if (slot >= 0) gt[slot] += t - gc; gc = t; } };
     for (;;) {
       gtick(-1);
@@ -695,20 +690,48 @@ __device__ __forceinline__ void ivf_filter5_body(const FilterArgs& a) {
 #define SCAN_TAIL5_PART 1
 #include "scan_tail5.inc"
       gtick(0);
+      // The tail in two item segments, 0-7 and 8-15: the builders sort a segment's thresholds (S1) while the gatherers work on
+      // the other one -- column minima of 8.. under S1 of 0-7, survivors of 0-7 under S1 of 8.. -- instead of waiting for all sixteen.
+      // cnt is uniform and both roles read it from the same record: an entry of more than 8 items takes one barrier more, on both
+      // sides; one of up to 8 items has no second segment and keeps the sequence it had.
 #define SCAN_TAIL5_PART 2
+#define SCAN_TAIL5_G0 0
+#define SCAN_TAIL5_G1 8
 #include "scan_tail5.inc"
       gtick(1);
-      lds_barrier();
-      // (S1, the thresholds tau' + E, is computed by the builder waves between these two barriers)
-      lds_barrier();
-      gtick(-1);
+      lds_barrier();   // T1: the column minima of items 0-7 are in
+      gtick(3);
+      if (cnt > 8) {
+#define SCAN_TAIL5_PART 2
+#define SCAN_TAIL5_G0 8
+#define SCAN_TAIL5_G1 16
+#include "scan_tail5.inc"
+      }
+      gtick(1);
+      lds_barrier();   // T2: thr_s[0..7]; the column minima of items 8.. are in
+      gtick(4);
 #define SCAN_TAIL5_PART 3
+#define SCAN_TAIL5_G0 0
+#define SCAN_TAIL5_G1 8
+#include "scan_tail5.inc"
+      gtick(2);
+      if (cnt > 8) {
+        lds_barrier();   // T3: thr_s[8..15]
+        gtick(5);
+#define SCAN_TAIL5_PART 3
+#define SCAN_TAIL5_G0 8
+#define SCAN_TAIL5_G1 16
+#include "scan_tail5.inc"
+      }
+#define SCAN_TAIL5_PART 4
 #include "scan_tail5.inc"
 #undef SCAN_TAIL5_FENCE
       gtick(2);
       const int next_ok = __builtin_amdgcn_readfirstlane(dsc[nb * REC_DW + 6]);
       if (next_ok > 0) prefetch_first_codes(dsc + nb * REC_DW);
       lds_barrier();
+      gtick(6);
+      if constexpr (PROF) gt[7] += cnt > 8 ? 1 : 0;
       if (next_ok < 0) break;
       cur = nb;
     }
@@ -716,6 +739,10 @@ __device__ __forceinline__ void ivf_filter5_body(const FilterArgs& a) {
       a.prof[(size_t)blockIdx.x * 8 + 2] = gt[0];
       a.prof[(size_t)blockIdx.x * 8 + 4] = gt[1];
       a.prof[(size_t)blockIdx.x * 8 + 5] = gt[2];
+      // (a second table behind the first, at a fixed offset: the tail's barrier waits; the host hands out no buffer to a grid
+      // of more than SCAN5_PROF_WGS workgroups, scan_prof_buffer)
+      long long* p2 = a.prof + ((size_t)SCAN5_PROF_WGS + blockIdx.x) * 8;
+      for (int i = 0; i < 5; ++i) p2[i] = gt[3 + i];
     }
   }
 }

@@ -312,7 +312,8 @@ static int scan_prof_buffer(freddy_gpu_index* ix, Workspace* ws, long long** pro
 #ifdef FREDDY_LAB
   if (fence) *fence = (uint32_t)ix->tune.scan_fence;
   if (!ix->tune.scan_prof) return 0;
-  if (ws->w_prof.ensure(sizeof(long long) * 8 * 1024)) return fail(FREDDY_E_NOMEM, "profile buffer");
+  if (ws->w_prof.ensure(sizeof(long long) * 16 * SCAN5_PROF_WGS))   // (two tables of 8 counters per workgroup: ivf_filter5_kernel)
+    return fail(FREDDY_E_NOMEM, "profile buffer");
   *prof = ws->w_prof.as<long long>();
 #endif
   (void)ix; (void)ws; (void)fence;
@@ -321,8 +322,10 @@ static int scan_prof_buffer(freddy_gpu_index* ix, Workspace* ws, long long** pro
 
 #ifdef FREDDY_LAB
 // debugging aid (option fused_prof): per-phase shader-clock sums of every persistent workgroup's builder wave 0
-static int scan_prof_print(freddy_gpu_index* ix, hipStream_t s, const long long* prof, unsigned n_persist) {
-  std::vector<long long> h(8 * (size_t)n_persist);
+// tail_waits (ivf_filter5_kernel): a second table behind the first -- gatherer wave 0's waits at the tail's barriers T1, T2, T3 and at the
+// entry's last barrier, and the number of entries of more than 8 items (the ones with a second item segment and T3)
+static int scan_prof_print(freddy_gpu_index* ix, hipStream_t s, const long long* prof, unsigned n_persist, bool tail_waits = false) {
+  std::vector<long long> h(tail_waits ? 8 * ((size_t)SCAN5_PROF_WGS + n_persist) : 8 * (size_t)n_persist);
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipMemcpy(h.data(), prof, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
   double sum[8] = {0}; long long mx_end = 0, mn_end = -1; double ent = 0;
@@ -334,6 +337,13 @@ static int scan_prof_print(freddy_gpu_index* ix, hipStream_t s, const long long*
   }
   fprintf(stderr, "[scan prof] wgs=%u entries=%.0f  builder cycles/entry: builds=%.0f barrier-wait=%.0f tail=%.0f | gatherer wave 0 (fused5.h): main=%.0f colmin=%.0f S2=%.0f | workgroups ran dry over %.1f us\n",
           n_persist, ent, sum[0] / ent, sum[1] / ent, sum[3] / ent, sum[2] / ent, sum[4] / ent, sum[5] / ent, (mx_end - mn_end) / 100.0);
+  if (tail_waits) {
+    double w[5] = {0};
+    for (unsigned b = 0; b < n_persist; ++b)
+      for (int i = 0; i < 5; ++i) w[i] += (double)h[((size_t)SCAN5_PROF_WGS + b) * 8 + i];
+    fprintf(stderr, "[scan prof] gatherer wave 0 waits, cycles/entry: T1=%.0f T2=%.0f T3=%.0f last=%.0f | entry total=%.0f | entries of more than 8 items: %.0f\n",
+            w[0] / ent, w[1] / ent, w[2] / ent, w[3] / ent, (sum[2] + sum[4] + sum[5] + w[0] + w[1] + w[2] + w[3]) / ent, w[4]);
+  }
   (void)ix;
   return 0;
 }
@@ -341,7 +351,7 @@ static int scan_prof_print(freddy_gpu_index* ix, hipStream_t s, const long long*
 // as above, ivf_filter8_kernel's (fused8.h) are gatherer wave 0's stages
 static int filter_prof_print(freddy_gpu_index* ix, hipStream_t s, const FilterArgs& fl, bool whole, unsigned n_persist) {
   if (!fl.prof || fl.cand_count || !(whole || fl.K == 1024)) return 0;
-  if (!whole) return scan_prof_print(ix, s, fl.prof, n_persist);
+  if (!whole) return scan_prof_print(ix, s, fl.prof, n_persist, true);
   std::vector<long long> h(8 * (size_t)n_persist);
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipMemcpy(h.data(), fl.prof, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
@@ -409,6 +419,7 @@ int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt) {
   // 96 -> 128 us -- and its merge gains nothing; an IVFADC batch: +2.6 % queries/s with four batches in flight)
   fl.tau_run = r.running_bound ? ws->w_cand.as<uint32_t>() + r.Q : nullptr;
   if (int rc = scan_prof_buffer(ix, ws, &fl.prof, &fl.fence)) return rc;
+  if (n_persist > (unsigned)SCAN5_PROF_WGS) fl.prof = nullptr;   // (a grid the counters' buffer does not hold: no counters)
   fl.elastic = elastic ? ix->elastic : nullptr; fl.n_own = (int)n_own; fl.cap = cap; fl.elastic_yield = ix->tune.scan_elastic;
   // LDS: slabs [2 buffers][2 positions][K][16 items] int16 (whole: [12 positions][2 halves][256][8 items]), then column minima /
   // thresholds, two entry records, row terms

@@ -47,8 +47,8 @@ __device__ __forceinline__ uint32_t running_bound5(uint32_t* __restrict__ tau_ru
 
 // S1, lane 0's part for item i of a cell-grouped entry (rec: its record, entry_record5_kernel): t = the key of tau', the Lt-th
 // smallest of the item's sorted column minima; returns the bits of the float the item cuts at, tau' + E (+inf: keep_all).
-// inv = the query's running bound as read earlier.  (ivf_filter5_kernel's S1 takes two items per wave and keeps its own text: one
-// test of tau_run around both -- with two calls of this function that kernel compiled to other code.)
+// inv = the query's running bound as read earlier.  (ivf_filter5_kernel's builder waves call it once per item segment, item w
+// and then item w + 8, each after a sort of its own.)
 __device__ __forceinline__ uint32_t filter_threshold5(const FilterArgs& a, const int32_t* rec, int i, uint32_t t, uint32_t inv) {
   if (a.tau_run) t = running_bound5(a.tau_run, (uint32_t)rec[24 + i], t, __int_as_float(rec[144 + i]), __int_as_float(rec[160 + i]), inv);
   return a.keep_all ? 0x7f800000u : widen_threshold5(t, __int_as_float(rec[56 + i]));

@@ -8,6 +8,16 @@
 //   #define SCAN_TAIL5_PART 3   S2: rows with s' <= tau' + E (thr_s[item], from the kernel's S1 step) -> this wave's
 //                               region of each item's survivor buffer
 //
+// Parts 2 and 3 handle the items one after the other, so an including kernel may cut them into item SEGMENTS and put a barrier of
+// its own between two of them (ivf_filter5_kernel: the thresholds of one segment are sorted while the gatherers work on the other):
+//
+//   #define SCAN_TAIL5_G0 / SCAN_TAIL5_G1   items [G0, G1) of part 2 or 3, integer literals, in ascending segments from 0.  The
+//                               segment that starts at 0 declares what the later ones and the later parts use; part 3 of a
+//                               segment reads ITS items' thresholds when it starts.
+//   #define SCAN_TAIL5_PART 4   after the last segment of part 3: the one store of the entry's survivor counts
+//
+// Without the two names a part covers all G items and part 3 ends with the store itself (fused8.h).
+//
 // Why text and not functions: both kernels sit at 128 VGPRs, and the same statements moved into __forceinline__ functions (arrays
 // by reference, sval as a free function) came back from the compiler with other code -- the optimiser simplifies a callee before
 // it is inlined, later passes then hoist and order the same instructions differently, and the register allocator spills
@@ -17,7 +27,9 @@
 // thr_s (LDS); acc[G / 2][RMAX]; cnt, chunk, blk0, nrows, rl_wave, gw, lane; and the macro SCAN_TAIL5_FENCE: FilterArgs::fence in
 // ivf_filter5_kernel (always 0 at run time, opaque to the compiler: its conditions keep that kernel's register allocation where
 // it is, profiles/HISTORY.md), the literal 0u in ivf_filter8_kernel, where the conditions fold away.
-// Names it leaves behind for the later parts: base[], sval, p_sc, live8, best[], sec16[], apack[].
+// Names it leaves behind for the later parts: base[] (part 1); sval, gi, p_sc, live8, best[], sec16[], apack[] (part 2, its segment
+// from 0); with segments also part 3's per-lane record words and counts -- p_shift, p_off, p_lo, p_hi, p_q, p_reg, cntv -- which its
+// later segments and part 4 use.
 //
 // The contract with merge_refine_kernel (refine.h) -- written down here and in sparse5.h's two survivor passes, nowhere else:
 //   key     surv_key5(d_lo, location): d_lo = max(0, (s' + OFF) - shift); location = the row's global slot, bit 31 = `amb` (CAND
@@ -28,7 +40,7 @@
 // ---- tail.  The selection works on s' = fma(scale[item], V, rterm[row]) -- the stored sum WITHOUT the item's
 // constant OFF -- compared as floats: a constant shift changes neither the order nor tau' + E.  OFF (which keeps
 // the stored bits positive for the merge) is added for the survivors only: s = s' + OFF.
-// base[r] = the row's own term (staged by the builders in the previous entry's tail, replaced in this one's after the S1 barrier); +inf for the slots of this wave beyond its last block and for the lanes
+// base[r] = the row's own term (staged by the builders in the previous entry's tail, replaced in this one's once the last threshold barrier is behind the builders: every gatherer passed this point before the first); +inf for the slots of this wave beyond its last block and for the lanes
 // past the end of the list (s = +inf: above every finite threshold; S2 skips the former and masks the latter)
 float base[RMAX];
 const int last_blk = nrows > 0 ? (nrows - 1) >> 6 : -1;     // chunk-relative block holding the last row
@@ -46,6 +58,11 @@ for (int h = 0; h < G / 2; ++h)
 #pragma unroll
   for (int r = 0; r < RMAX; ++r) acc[h][r] ^= 0x80008000u;   // biased unsigned fields -> signed sums
 #elif SCAN_TAIL5_PART == 2
+#ifndef SCAN_TAIL5_G0
+#define SCAN_TAIL5_G0 0
+#define SCAN_TAIL5_G1 G
+#endif
+#if SCAN_TAIL5_G0 == 0
 auto sval = [&](int g, int r, float sc) -> float {
   const uint32_t w = acc[g >> 1][r];
   const int v = (g & 1) ? ((int32_t)w >> 16) : ((int32_t)(w << 16) >> 16);
@@ -67,9 +84,10 @@ uint32_t apack[2] = {0u, 0u};
 for (int g = 0; g < G; ++g) best[g] = __uint_as_float(0x7f800000u);
 #pragma unroll
 for (int i = 0; i < G / 2; ++i) sec16[i] = 0x7f807f80u;
+#endif
 if (!(SCAN_TAIL5_FENCE & 4)) {
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
+  for (int g = SCAN_TAIL5_G0; g < SCAN_TAIL5_G1; ++g) {
     if (g < cnt) {
       // the lane's smallest and second smallest s' of this item and the row of the smallest: a lane hardly ever
       // holds two survivors, so S2 can emit (best, its row) without looking at the sums again
@@ -97,9 +115,17 @@ if (!(SCAN_TAIL5_FENCE & 4)) {
     }
   }
 }
+#undef SCAN_TAIL5_G0
+#undef SCAN_TAIL5_G1
 #elif SCAN_TAIL5_PART == 3
+#ifndef SCAN_TAIL5_G0
+#define SCAN_TAIL5_G0 0
+#define SCAN_TAIL5_G1 G
+#define SCAN_TAIL5_WHOLE
+#endif
 // S2: survivors -> this wave's region of each item's buffer.  Normally every lane has at most one (its smallest
 // sum, kept from the pass above); otherwise the pass bits of the lane's 8 rows, branch free, then per-row ballots.
+#ifdef SCAN_TAIL5_WHOLE
 if (!(SCAN_TAIL5_FENCE & 4)) {
   const float p_thr = __uint_as_float(thr_s[gi]);
   const int p_it = rec[8 + gi];
@@ -110,8 +136,33 @@ if (!(SCAN_TAIL5_FENCE & 4)) {
   // lane g: item g's survivor region of this wave, and (collected below) its count -- ONE store of the counts per entry
   const int p_reg = (p_it * a.upi + chunk) * NG + gw;
   int cntv = 0;
+#else
+// (segments: the record words outlive this segment's block; the thresholds are read per segment -- a later segment's are
+// published after an earlier segment's pass has begun)
+#if SCAN_TAIL5_G0 == 0
+// (initialised: left undefined on the fence's path they were live -- as undefined values -- around the whole entry loop, three
+// registers the main loop does not have)
+float p_shift = 0.0f, p_off = 0.0f;
+uint32_t p_lo = 0u, p_hi = 0u;
+int p_q = 0, p_reg = 0;
+int cntv = 0;
+#endif
+if (!(SCAN_TAIL5_FENCE & 4)) {
+  // (the address recomputed per segment from an opaque lane id: as one value of the entry loop it was hoisted over the main loop
+  // and spilled there.  Every lane reads the word of item lane & 15, this segment's or not: the builders may be writing a LATER
+  // segment's thresholds at this moment, and what such a lane gets is never used -- the readlanes below take lanes G0 .. G1 - 1,
+  // whose words were published before the barrier in front of this segment, and the later segment reads again behind its own)
+  const float p_thr = __uint_as_float(*reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(thr_s) + (lane_byte4() & 60u)));
+#if SCAN_TAIL5_G0 == 0
+  p_shift = __int_as_float(rec[72 + gi]);
+  p_off = __int_as_float(rec[40 + gi]);
+  p_lo = (uint32_t)rec[88 + gi]; p_hi = (uint32_t)rec[104 + gi];
+  p_q = rec[24 + gi];
+  p_reg = (rec[8 + gi] * a.upi + chunk) * NG + gw;
+#endif
+#endif
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
+  for (int g = SCAN_TAIL5_G0; g < SCAN_TAIL5_G1; ++g) {
     if (g < cnt) {
       const float thr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_thr), g));
       const float off = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p_off), g));
@@ -185,9 +236,18 @@ if (!(SCAN_TAIL5_FENCE & 4)) {
       asm("v_writelane_b32 %0, %1, %2" : "+v"(cntv) : "s"(run), "i"(g));
     }
   }
+#ifdef SCAN_TAIL5_WHOLE
+  if (lane < cnt) a.surv_count[(uint32_t)p_reg] = cntv;
+#endif
+}
+#undef SCAN_TAIL5_G0
+#undef SCAN_TAIL5_G1
+#undef SCAN_TAIL5_WHOLE
+#elif SCAN_TAIL5_PART == 4
+if (!(SCAN_TAIL5_FENCE & 4)) {
   if (lane < cnt) a.surv_count[(uint32_t)p_reg] = cntv;
 }
 #else
-#error "SCAN_TAIL5_PART: 1, 2 or 3"
+#error "SCAN_TAIL5_PART: 1 .. 4"
 #endif
 #undef SCAN_TAIL5_PART
