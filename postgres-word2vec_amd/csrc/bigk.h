@@ -25,13 +25,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ivf_sizes.h"   // BIGK_KMAX (largest k), BIGK_PASS (keys a selection pass adds)
 #include "kernels.h"
 #include "wave_topk.h"
 
 namespace freddy {
 
-static constexpr int BIGK_KMAX = 4096;   // largest k
-static constexpr int BIGK_PASS = 1024;   // keys a selection pass adds
 static constexpr int BIGK_T = 1024;      // threads of the replay workgroup
 
 struct SelectArgs {

@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ivf_sizes.h"
 #include "kernels.h"
 #include "wave_topk.h"
 #include "refine.h"
@@ -44,8 +45,7 @@ static constexpr float COARSE_EPS = 1.2e-4f;
 static constexpr float COARSE_EPS_ABS = 2e-34f;   // the dot product lost to an underflowed unscale factor (above)
 static constexpr int COARSE_DP_ALIGN = 64;    // padded dimension count: whole blocks of 8 iterations x 8 dimensions (zeros)
 static constexpr int COARSE_TQ = 32;          // queries per MFMA tile (a workgroup = 32 queries x 128 cells)
-static constexpr int COARSE_MAX_CPAD = 1024;  // the plan keeps a query's approximate distances in registers: 16 per lane
-static constexpr int COARSE_STREAM_MAX_CPAD = 16384;   // beyond 1024 cells the plan streams them twice (minima, then candidates as a bitmap)
+// (COARSE_MAX_CPAD, COARSE_STREAM_MAX_CPAD: ivf_sizes.h)
 
 // ---------------------------------------------------------------------------------------
 // a[q][j] for a 32-query x 128-cell tile per workgroup; wave w owns the 32 x 32 block of cells [32 w, 32 w + 32).

@@ -1,6 +1,6 @@
 // grid_plan.h -- every launch whose grid, or whose choice of kernel, comes from the handle's CU count (freddy_gpu_index::n_cus:
 // the device's count, or less under option grid_cus): the formulas as pure functions of (n_cus, work sizes, options), one
-// statement of each.  ivfadc.hip, pq.hip, exact.hip and its sibling units and exact_host.h call them; the kernels behind them loop over the work a
+// statement of each.  ivf_scan.hip, one.hip, pq.hip, exact.hip and its sibling units and exact_host.h call them; the kernels behind them loop over the work a
 // smaller grid leaves (grid-stride loops, work counters, units dealt round G workgroups), so no value of n_cus >= 1 changes a
 // result -- tests/test_gpu_grid_cus.py runs them at 1, 2, 3 and 7.
 // Plain C++17, no HIP, so that tests/test_grid_inputs_cpu.py compiles this file on its own with g++ (as block_plan.h is).
@@ -16,7 +16,7 @@ namespace freddy {
 // and must be co-resident: the option may only shrink grids).
 inline int grid_cus_value(int64_t v, int device_cus) { return v <= 0 ? device_cus : (int)std::min<int64_t>(v, device_cus); }
 
-// ---- the persistent scans of an IVFADC batch (ivfadc.hip) ----
+// ---- the persistent scans of an IVFADC batch (ivf_scan.hip) ----
 // CUs a batch's filter scan may take: its share of the chip (32 at least, where the chip has them), less the reserved ones.
 // May be <= 0: the callers take max(1, .).
 inline int scan_cus(int n_cus, int share, int reserve_cus) { return std::max(n_cus / std::max(1, share), std::min(n_cus, 32)) - reserve_cus; }

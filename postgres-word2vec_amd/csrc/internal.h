@@ -4,9 +4,16 @@
 //   pin.hip     pin_pq / pin_ivf(_multi): table layouts, the codebook's tables, update_codebook; append_rows / remove_rows / update_rows (HBM index mutation:
 //               mutate.h the entry points and one function per handle kind, mutate_host.h the staging owner and what else they share, block_plan.h lists ->
 //               blocks in plain C++, mutate_kernels.h / remove_kernels.h / update_kernels.h the kernels)
-//   ivfadc.hip  the IVFADC search: cell selection, work table, scans, merge; *_dev entry, host-buffer pipeline, one-query launch
-//   pq.hip      pq_search (+ subsets, pseudo-list batches, one-query launch), grouping_pq
-//               ivf_host.h what these two share on the host: shape predicates and sizes, the query table's layout, the run state of a chain, merge arguments
+//   ivfadc.hip  the IVFADC search chunk by chunk: the path a chunk takes, its probing rounds, the *_dev entry (launches nothing itself)
+//   ivf_select.hip  cell selection: coarse distances (+ the query x codebook table), the probe plan
+//   ivf_scan.hip    the cell-grouped scans and their merges: work table, filter + refine, the exact scan, the scan of other shapes
+//   generic.hip     LUTs -> adc_scan -> merge_replay and the selection passes of k > 512: every shape's path, and what pq.hip launches of it
+//   one.hip     ONE query of a host-buffer call as one launch (one.h): the hand-off buffer and the end of such a call, ivf_one (pq_one: pq.hip)
+//   pipeline.hip    the host-buffer IVFADC calls: sub-batches on lanes over ivfadc.hip's chunk driver (stage_plan.h: the staging decisions in plain C++)
+//   pq.hip      pq_search (+ subsets, pseudo-list batches, one-query launch), grouping_pq, the assignment step of cluster_pq
+//               ivf_run.h what these share on the host: shape predicates and sizes, the query table's layout, the run state of a chain (no kernel
+//               header: ivf_sizes.h has the constants); ivf_host.h adds the merge arguments for the units that launch
+//               host_io.h the copy-in launch and the layout of the pinned result block, for pipeline.hip, one.hip and pq.hip
 //   join.hip    pin_ivpq, knn_join (join.h: overview; join_kernels.h and join_traverse.h the kernels, join_host.h the host heap, join_run.h the run
 //               record of a call and its stages)
 //   exact.hip   pin_vectors, exact kNN and the exact join (also by row id: query_ids.h, resolve.h), the rows of an id set
@@ -32,6 +39,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <chrono>
 #include <map>
@@ -73,7 +81,7 @@ struct Tuning {
                                // An explicit contract -- the library does not guess it; the host-buffer calls multiply it by their lane count
   int reserve_cus = 0;         // FREDDY_GPU_RESERVE_CUS: CUs the persistent scan leaves to the kernels of other streams (RCCL beside the scans)
   int scan_elastic = 0;        // FREDDY_GPU_SCAN_ELASTIC: a scan with scan_share > 1 brings EXTRA workgroups beyond its n_cus / share, which take work only while
-                               // no other batch's scan is announced and fewer than the cap of scan workgroups are alive (ivfadc.hip ivf_scan_filter, fused5.h):
+                               // no other batch's scan is announced and fewer than the cap of scan workgroups are alive (ivf_scan.hip ivf_scan_filter, fused5.h):
                                // 0 off, 1 on, 2 = every extra leaves after its first entry (tests)
   int scan_elastic_reserve = 64;   // FREDDY_GPU_SCAN_ELASTIC_RESERVE: CUs the elastic scans together leave to the small kernels of the batches in flight
   int pipeline_batch = 2048;   // FREDDY_GPU_PIPELINE_BATCH: queries per sub-batch of the host-buffer pipeline (freddy_gpu_ivfadc_search)
@@ -417,15 +425,18 @@ struct LdsLimit {
   int bytes;
   template <class K> LdsLimit(K* k, int b = 160 * 1024) : kernel(reinterpret_cast<const void*>(k)), bytes(b) {}
 };
-std::vector<LdsLimit> lds_limits_ivfadc();
+std::vector<LdsLimit> lds_limits_ivf_select();
+std::vector<LdsLimit> lds_limits_ivf_scan();
+std::vector<LdsLimit> lds_limits_generic();
 std::vector<LdsLimit> lds_limits_pq();
 std::vector<LdsLimit> lds_limits_join();
 std::vector<LdsLimit> lds_limits_exact();
 std::vector<LdsLimit> lds_limits_analogy();
 std::vector<LdsLimit> lds_limits_rerank();
 
-// ---- ivfadc.hip ----
 namespace freddy { struct PlanArgs; struct ScanArgs; struct MergeArgs; }
+
+// ---- ivf_scan.hip ----
 // The work table shared by both cell-grouped scans: per-cell item counts -> (<= 12 items of a cell, 4096-row
 // chunk) entries, largest first.
 struct WorkTable {
@@ -436,7 +447,6 @@ struct WorkTable {
   int32_t *sp_cell, *sp_first, *sp_chunk, *n_sparse, *sp_counter;
   bool sp_pairs = false;   // units of up to two items (sparse5.h NI = 2)
 };
-int pick_V(int L);
 // f(std::integral_constant<int, V>()) for a selection width of pick_V (1, 2, 4, 8, 16); false for any other V
 template <class F>
 static inline bool with_V(int V, F&& f) {
@@ -449,18 +459,41 @@ static inline bool with_V(int V, F&& f) {
   }
   return false;
 }
+
+// ---- generic.hip ----
+int pick_V(int L);
 int launch_scan(freddy_gpu_index* ix, hipStream_t s, const ScanArgs& a, int n_items);
 int launch_merge(freddy_gpu_index* ix, hipStream_t s, const MergeArgs& a);
 int bigk_select_replay(freddy_gpu_index* ix, hipStream_t s, Workspace* ws, ScanArgs sa, int n_items, const MergeArgs& ma, int Q);
 int launch_lut(freddy_gpu_index* ix, hipStream_t s, const float* vecs, const int32_t* item_cell, float* lut, int n_items,
                const float* coarse = nullptr, const int32_t* item_query = nullptr);
+int ivf_scan_generic(IvfRun& r, const PlanArgs& pa);
+
+// ---- ivf_scan.hip (the work table's record: above) ----
 int ivf_work_table(IvfRun& r, WorkTable& wt);
 int ivf_scan_filter(IvfRun& r, const PlanArgs& pa, const WorkTable& wt);
+int ivf_scan_exact(IvfRun& r, const PlanArgs& pa, const WorkTable& wt);
+int ivf_scan_multi(IvfRun& r, const PlanArgs& pa, const WorkTable& wt);
+
+// ---- ivf_select.hip ----
+bool ivf_coarse_by_pieces(const IvfRun& r);
+int ivf_coarse(IvfRun& r, int q_lo = 0, int q_n = -1);
+int ivf_plan(IvfRun& r, PlanArgs& pa);
+
+// ---- ivfadc.hip ----
+int ivfadc_begin(freddy_gpu_index* ix, hipStream_t s, int share, const float* d_q, int Q, int k, int W, float sentinel, int found_rule,
+                 int32_t* d_out_ids, float* d_out_dist, int32_t* d_status, IvfRun& r, const std::function<int(int, int)>* stage = nullptr,
+                 bool by_pieces = false);
+int ivfadc_finish(IvfRun& r, int n_next);
 int max_queries_per_chunk(const freddy_gpu_index* ix, int W, int k);
+
+// ---- one.hip ----
 int one_buffer(Workspace* ws, hipStream_t s, uint64_t shape, size_t bytes, uint32_t* epoch);
 bool one_prof();   // FREDDY_GPU_ONE_PROF (read once per process): the one-launch kernels' stamps on stderr
 int one_finish(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, volatile const int32_t* err,
                void (*print_stamps)(const unsigned long long* st), int* verdict);
+bool ivf_one_shape(const freddy_gpu_index* ix, int Q, int k, int W, int found_rule);
+int ivf_one(freddy_gpu_index* ix, const float* queries, int k, int W, float sentinel, int found_rule, int32_t* out_ids, float* out_dist, int* verdict);
 
 // ---- pq.hip ----
 int pq_shadow_build(freddy_gpu_index* ix);

@@ -1,8 +1,10 @@
-// io_kernels.h -- the copy kernels of the host-buffer calls (ivfadc.hip, pq.hip): pinned host memory is read and written by
+// io_kernels.h -- the copy kernels of the host-buffer calls (pipeline.hip, pq.hip): pinned host memory is read and written by
 // kernels in the search's own stream, not by SDMA copies.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 // The lanes move their data with KERNELS, not with hipMemcpyAsync: pinned host memory is mapped into the device's address
 // space, so a grid-stride copy reads the staged queries over PCIe (1.2 MB per 1024 queries: ~25 us) and a second one
@@ -12,6 +14,11 @@
 // device-resident batches of bench.py: 0.68 ms.
 static __global__ __launch_bounds__(256) void lane_copy_in_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n16) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = src[i];
+}
+// the 16-byte words [w0, w1) of `from` -> the same words of `to`: one launch in s (the caller asks hipGetLastError)
+static inline void launch_copy_in(hipStream_t s, const void* from, void* to, size_t w0, size_t w1) {
+  hipLaunchKernelGGL(lane_copy_in_kernel, dim3((unsigned)std::min<size_t>((w1 - w0 + 255) / 256, 512)), dim3(256), 0, s,
+                     reinterpret_cast<const uint4*>(from) + w0, reinterpret_cast<uint4*>(to) + w0, w1 - w0);
 }
 
 // The lists, the straggler count and the stragglers' numbers out by ONE workgroup, followed by a completion word the host

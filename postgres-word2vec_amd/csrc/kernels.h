@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ivf_sizes.h"
 #include "wave_topk.h"
 
 namespace freddy {
@@ -255,22 +256,7 @@ __global__ __launch_bounds__(256) void coarse_tile_kernel(const float* __restric
 //   ordered by cell id and replayed by lane 0 -- same argument as merge_replay below.
 //   Emits W work items per query (cell -1 = no cell left) and marks the cells used.
 // ---------------------------------------------------------------------------------------
-struct PlanArgs {
-  const float* dist;        // [Q][Cpad]
-  const int32_t* active;    // [n_active] query indices (NULL = identity)
-  const int32_t* list_off;  // [C+1]
-  uint32_t* used;           // [Q][used_words] bitmap of cells already probed
-  int32_t* item_cell;       // [n_active*W]
-  int32_t* item_query;      // [n_active*W]
-  float* item_dist;         // [n_active*W] or NULL: the item's coarse distance (the scan's bound on |r|^2)
-  int32_t* round_rows;      // [n_active] rows retrieved this round, -1 = no cell was left
-  int32_t* cell_count;      // [C] fused path only (NULL otherwise): += items probing each cell
-  int32_t* cell_items;      // [C][cell_cap] fused path: the items of each cell, in arrival order (any order is fine)
-  int cell_cap;             // >= number of active queries (a query probes a cell at most once)
-  int n_active, Cpad, C, W, used_words;
-  float cell_limit;         // a cell at this distance or beyond is never probed: 100.0 (ivfadc_search, the cell list's
-                            // sentinel, freddy.c:266-283), 1000.0 (ivfadc_batch_search, minDist of its argmin, freddy.c:855)
-};
+// (struct PlanArgs: ivf_sizes.h)
 
 template <int V>
 __global__ __launch_bounds__(64) void probe_plan_kernel(PlanArgs a) {

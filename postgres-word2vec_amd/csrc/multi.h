@@ -19,11 +19,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ivf_sizes.h"   // MULTI_G (items per work entry), multi_lds_bytes
 #include "scan_common.h"
 
 namespace freddy {
 
-static constexpr int MULTI_G = 8;       // items per work entry
 static constexpr int MULTI_T = 512;     // eight waves: wave w <-> row blocks w, w + 8, ... of the chunk
 
 struct MultiArgs {
@@ -44,8 +44,6 @@ struct MultiArgs {
   int m, M2, K, L, upi;
   uint32_t sentinel_bits;
 };
-
-static inline size_t multi_lds_bytes(int m, int K) { return (size_t)m * K * MULTI_G * sizeof(float) + MULTI_G * 64 * 4 + MULTI_G * 4 + 64; }
 
 __global__ __launch_bounds__(MULTI_T) void ivf_multi_kernel(MultiArgs a) {
   constexpr int G = MULTI_G, RMAX = FUSED_RMAX, NW = FUSED_NW;

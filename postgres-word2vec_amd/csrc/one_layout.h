@@ -1,5 +1,5 @@
 // one_layout.h -- where the one-launch kernels (one.h) keep what: the regions of the hand-off buffer in global memory and of the
-// dynamic LDS, from the call's shape (K, C, W, L, G).  The host (pq_one in pq.hip, ivf_one in ivfadc.hip) sizes the buffer and the
+// dynamic LDS, from the call's shape (K, C, W, L, G).  The host (pq_one in pq.hip, ivf_one in one.hip) sizes the buffer and the
 // launch with it, the kernels carve `smem` and nothing else with it: one statement of every offset.
 // Plain C++17, no HIP, so that tests/test_one_layout_cpu.py compiles this file on its own with g++ (as block_plan.h is); the
 // functions are constexpr, which is what lets device code call them.

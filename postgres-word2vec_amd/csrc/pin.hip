@@ -365,7 +365,7 @@ static int raise_lds_limits(int device) {
   static std::vector<char> done;
   std::lock_guard<std::mutex> g(mu);
   if ((size_t)device < done.size() && done[(size_t)device]) return 0;
-  for (const std::vector<LdsLimit>& unit : {lds_limits_ivfadc(), lds_limits_pq(), lds_limits_join(), lds_limits_exact(), lds_limits_analogy(), lds_limits_rerank()})
+  for (const std::vector<LdsLimit>& unit : {lds_limits_ivf_select(), lds_limits_ivf_scan(), lds_limits_generic(), lds_limits_pq(), lds_limits_join(), lds_limits_exact(), lds_limits_analogy(), lds_limits_rerank()})
     for (const LdsLimit& l : unit) HIP_TRY(hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l.bytes));
   if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
   done[(size_t)device] = 1;

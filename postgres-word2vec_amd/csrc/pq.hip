@@ -10,8 +10,9 @@
 #include "assign.h"
 #include "ivf_host.h"
 #include "query_ids.h"
+#include "stage_plan.h"
 
-// kernel choosers (ivfadc.hip).  M2: dwords of codes per row with an instantiation of its own, else 0 = any m
+// kernel choosers (generic.hip says what one is).  M2: dwords of codes per row with an instantiation of its own, else 0 = any m
 static decltype(&grouping_kernel<0>) grouping_kernel_for(int M2) {
   return M2 == 6 ? &grouping_kernel<6> : M2 == 15 ? &grouping_kernel<15> : &grouping_kernel<0>;
 }
@@ -268,6 +269,7 @@ static int pq_fused_chunk(freddy_gpu_index* ix, freddy_gpu_index* fx, hipStream_
   return ivf_scan_filter(r, pa, wt);
 }
 
+
 // ONE query over the flat table as one launch (one.h): table slices, grid barrier, scan, last-arriver merge.  `err` is a
 // word of mapped host memory the kernel sets when one of its bounded polls ran out (the grid was not co-resident): the
 // caller then re-arms the counters and takes the three-launch path.
@@ -391,92 +393,129 @@ static int pq_subset(freddy_gpu_index* ix, hipStream_t s, const int32_t* subset_
   return 0;
 }
 
-// The host-buffer search for either query source (query_ids.h; the arguments are checked).  queries == NULL: the queries are rows of a
-// device table -- their row numbers are staged where the floats would be and a gather fills the query block; ONE query is read where
-// its row lies, and for the one-launch kernel (which takes it by value) read back first.
+// ---- the host-buffer call, stage by stage: pq_stage_in -> pq_call_rows -> pq_one_try, or pq_batch -> pq_stage_out ------------------
+// Queries in, lists out through pinned staging that the kernels read and write themselves (mapped host memory): a handful of
+// queries (in_place, stage_plan.h) are read where they are staged and their lists written straight back; larger batches cross PCIe
+// once, by a copy kernel each way.  No hipMemcpyAsync in the stream (each one is an SDMA hop with its own latency).
+struct PqCall {
+  bool in_place;
+  size_t n_out;
+  const float* d_q;   // where the search reads the queries, and where it writes the lists
+  int32_t* d_oi;
+  float* d_od;
+};
+// the rows the call scans: the table's, or the gathered rows of an "id IN (...)" subset; view: their IVF-shaped view if the batch takes the cell-grouped scan
+struct PqRows {
+  const int32_t* blk_off;
+  const uint32_t* packed;
+  const int32_t* pos;
+  int64_t n_blocks, n_rows;
+  freddy_gpu_index* view;
+};
+
+// queries == NULL (a source of table rows): their row numbers are staged where the floats would be and a gather fills the query block;
+// ONE such query is read where its row lies, with room for its floats behind the number, for the one-launch kernel
+static int pq_stage_in(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const QuerySrc& qs, int Q, int k, PqCall& c) {
+  const float* const queries = qs.host;
+  const size_t q_bytes = sizeof(float) * (size_t)Q * ix->d;
+  c.n_out = (size_t)Q * k;
+  if (ix->hio_in.ensure(queries ? q_bytes + 16 : Q == 1 ? 16 + q_bytes : sizeof(int32_t) * (size_t)Q) || ix->hio_out.ensure(HioOut::bytes(c.n_out))) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
+  if (queries) memcpy(ix->hio_in.p, queries, q_bytes);
+  else memcpy(ix->hio_in.p, qs.rows, sizeof(int32_t) * (size_t)Q);
+  c.in_place = Q <= IN_PLACE_QUERIES;
+  if (!c.in_place && (ws->w_q.ensure(q_bytes + 16) || ws->w_out_ids.ensure(sizeof(int32_t) * c.n_out) || ws->w_out_dist.ensure(sizeof(float) * c.n_out)))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  const HioOut out(ix->hio_out.p, c.n_out);
+  c.d_q = ix->hio_in.as<const float>(); c.d_oi = out.ids; c.d_od = out.dist;
+  if (!queries) {
+    if (Q == 1) {
+      c.d_q = qs.row_ptr(0, ix->d);
+    } else {
+      if (c.in_place && ws->w_q.ensure(q_bytes + 16)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+      if (int rc = launch_query_gather(ix, s, qs, ix->hio_in.as<const int32_t>(), ws->w_q.as<float>(), Q, ix->d)) return rc;
+      c.d_q = ws->w_q.as<float>();
+    }
+  }
+  if (!c.in_place) {
+    if (queries) {
+      launch_copy_in(s, ix->hio_in.p, ws->w_q.p, 0, (q_bytes + 15) / 16);
+      HIP_TRY(hipGetLastError());
+    }
+    c.d_q = ws->w_q.as<float>(); c.d_oi = ws->w_out_ids.as<int32_t>(); c.d_od = ws->w_out_dist.as<float>();
+  }
+  return 0;
+}
+
+static int pq_call_rows(freddy_gpu_index* ix, hipStream_t s, int Q, int k, const int32_t* subset_ids, int64_t n_subset, PqRows& t) {
+  t = PqRows{ix->blk_off, ix->packed, ix->pos, ix->n_blocks, ix->N, nullptr};
+  if (subset_ids)
+    if (int rc = pq_subset(ix, s, subset_ids, n_subset, &t.blk_off, &t.packed, &t.pos, &t.n_blocks, &t.n_rows)) return rc;
+  // (a subset of at least one full pseudo-list: its gathered rows get a view of their own, refreshed on this stream)
+  const bool fused_path = pq_use_fused(ix, Q, k) && (!subset_ids || t.n_blocks >= FUSED_UNIT_BLOCKS);
+  if (fused_path && !subset_ids) if (int rc = pq_shadow_build(ix)) return rc;
+  if (fused_path && subset_ids) if (int rc = pq_view_refresh(ix, &ix->pq_sub_view, s, t.packed, t.pos, t.n_blocks, t.n_rows)) return rc;
+  t.view = !fused_path ? nullptr : subset_ids ? ix->pq_sub_view : ix->pq_shadow;
+  return 0;
+}
+
+// ONE query as one launch (pq_one; the caller has asked pq_one_shape): the kernel takes the query by value, so a device source's
+// row is read back first, behind its staged number.  *answered: the lists are in the caller's buffers.
+static int pq_one_try(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, const QuerySrc& qs, int k, float sentinel, const PqRows& t, const PqCall& c,
+                      int32_t* out_ids, float* out_dist, bool* answered) {
+  const HioOut out(ix->hio_out.p, c.n_out);
+  *out.verdict = 0;
+  const float* queries = qs.host;
+  if (!queries) {
+    float* const row_q = ix->hio_in.as<float>() + 4;
+    if (int rc = fetch_query_row(s, qs, ix->d, row_q)) return rc;
+    queries = row_q;
+  }
+  if (int rc = pq_one(ix, s, queries, k, sentinel, t.blk_off, t.packed, t.pos, t.n_blocks, c.d_oi, c.d_od, out.verdict)) return rc;
+  int verdict = 0;
+  if (int rc = one_finish(ix, ws, s, out.verdict, [](const unsigned long long* st) {
+        fprintf(stderr, "[pq_one] wg0: slice %.2f barrier %.2f stage %.2f scan %.2f publish %.2f | last: since wg0 start %.2f merge %.2f replay %.2f us\n",
+                (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01, (st[3] - st[2]) * 0.01, (st[4] - st[3]) * 0.01, (st[5] - st[4]) * 0.01,
+                (st[8] - st[0]) * 0.01, (st[9] - st[8]) * 0.01, (st[10] - st[9]) * 0.01);
+      }, &verdict))
+    return rc;
+  *answered = verdict == 2;
+  if (*answered) {   // (positions out: mapped through the host copy of the ids)
+    for (size_t i = 0; i < c.n_out; ++i) out_ids[i] = out.ids[i] >= 0 ? ix->h_ids[(size_t)out.ids[i]] : -1;
+    memcpy(out_dist, out.dist, c.n_out * 4);
+  }
+  return 0;
+}
+
+static int pq_stage_out(freddy_gpu_index* ix, hipStream_t s, const PqCall& c, int32_t* out_ids, float* out_dist) {
+  const HioOut out(ix->hio_out.p, c.n_out);
+  if (!c.in_place) {
+    hipLaunchKernelGGL(host_io_out_kernel, dim3((unsigned)((c.n_out + 255) / 256)), dim3(256), 0, s, c.d_oi, c.d_od, out.ids, (int)c.n_out);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  memcpy(out_ids, out.ids, c.n_out * 4);
+  memcpy(out_dist, out.dist, c.n_out * 4);
+  return 0;
+}
+
+// The host-buffer search for either query source (query_ids.h; the arguments are checked).
 int pq_search_src(freddy_gpu_index* ix, const QuerySrc& qs, int Q, int k, float sentinel, const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids,
                   float* out_dist) {
-  const float* queries = qs.host;
   if (Q == 0) return FREDDY_OK;
   HIP_TRY(hipSetDevice(ix->device));
   Workspace* ws = workspace_for(ix, ix->stream);
   hipStream_t s = ix->stream;
-  // queries in, lists out through pinned staging that the kernels read and write themselves (mapped host memory): a
-  // handful of queries are read where they are staged and their lists written straight back; larger batches cross PCIe
-  // once, by a copy kernel each way.  No hipMemcpyAsync in the stream (each one is an SDMA hop with its own latency).
-  const size_t q_bytes = sizeof(float) * (size_t)Q * ix->d, n_out = (size_t)Q * k;
-  // (a source of table rows stages their numbers; ONE such query: room for its floats behind the number, for the one-launch kernel)
-  if (ix->hio_in.ensure(queries ? q_bytes + 16 : Q == 1 ? 16 + q_bytes : sizeof(int32_t) * (size_t)Q) || ix->hio_out.ensure(n_out * 8 + 16)) return fail(FREDDY_E_NOMEM, "pinned staging allocation failed");
-  if (queries) memcpy(ix->hio_in.p, queries, q_bytes);
-  else memcpy(ix->hio_in.p, qs.rows, sizeof(int32_t) * (size_t)Q);
-  const bool direct = Q <= 8;
-  if (!direct && (ws->w_q.ensure(q_bytes + 16) || ws->w_out_ids.ensure(sizeof(int32_t) * n_out) || ws->w_out_dist.ensure(sizeof(float) * n_out)))
-    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-  const float* d_q = ix->hio_in.as<const float>();
-  int32_t* d_oi = ix->hio_out.as<int32_t>();
-  float* d_od = reinterpret_cast<float*>(d_oi + n_out);
-  float* const row_q = ix->hio_in.as<float>() + 4;   // (Q == 1 of a device source: the row read back for pq_one)
-  if (!queries) {
-    if (Q == 1) {
-      d_q = qs.row_ptr(0, ix->d);
-    } else {
-      if (direct && ws->w_q.ensure(q_bytes + 16)) return fail(FREDDY_E_NOMEM, "workspace allocation failed");
-      if (int rc = launch_query_gather(ix, s, qs, ix->hio_in.as<const int32_t>(), ws->w_q.as<float>(), Q, ix->d)) return rc;
-      d_q = ws->w_q.as<float>();
-    }
+  PqCall c;
+  PqRows t;
+  if (int rc = pq_stage_in(ix, ws, s, qs, Q, k, c)) return rc;
+  if (int rc = pq_call_rows(ix, s, Q, k, subset_ids, n_subset, t)) return rc;
+  if (!t.view && c.in_place && pq_one_shape(ix, Q, k, t.n_blocks)) {
+    bool answered = false;
+    if (int rc = pq_one_try(ix, ws, s, qs, k, sentinel, t, c, out_ids, out_dist, &answered)) return rc;
+    if (answered) return FREDDY_OK;
   }
-  if (!direct) {
-    if (queries) {
-      const size_t n16 = (q_bytes + 15) / 16;
-      hipLaunchKernelGGL(lane_copy_in_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 512)), dim3(256), 0, s,
-                         ix->hio_in.as<const uint4>(), ws->w_q.as<uint4>(), n16);
-      HIP_TRY(hipGetLastError());
-    }
-    d_q = ws->w_q.as<float>(); d_oi = ws->w_out_ids.as<int32_t>(); d_od = ws->w_out_dist.as<float>();
-  }
-
-  const int32_t* blk_off = ix->blk_off;
-  const uint32_t* packed = ix->packed;
-  const int32_t* pos = ix->pos;
-  int64_t n_blocks = ix->n_blocks, n_rows = ix->N;
-  if (subset_ids)
-    if (int rc = pq_subset(ix, s, subset_ids, n_subset, &blk_off, &packed, &pos, &n_blocks, &n_rows)) return rc;
-  // (a subset of at least one full pseudo-list: its gathered rows get a view of their own, refreshed on this stream)
-  const bool fused_path = pq_use_fused(ix, Q, k) && (!subset_ids || n_blocks >= FUSED_UNIT_BLOCKS);
-  if (fused_path && !subset_ids) if (int rc = pq_shadow_build(ix)) return rc;
-  if (fused_path && subset_ids) if (int rc = pq_view_refresh(ix, &ix->pq_sub_view, s, packed, pos, n_blocks, n_rows)) return rc;
-  freddy_gpu_index* const view = !fused_path ? nullptr : subset_ids ? ix->pq_sub_view : ix->pq_shadow;
-  if (!fused_path && direct && pq_one_shape(ix, Q, k, n_blocks)) {
-    int32_t* err = reinterpret_cast<int32_t*>(ix->hio_out.as<char>() + n_out * 8);   // (the staging block's spare 16 bytes)
-    *err = 0;
-    if (!queries) {
-      if (int rc = fetch_query_row(s, qs, ix->d, row_q)) return rc;
-      queries = row_q;
-    }
-    if (int rc = pq_one(ix, s, queries, k, sentinel, blk_off, packed, pos, n_blocks, d_oi, d_od, err)) return rc;
-    int verdict = 0;
-    if (int rc = one_finish(ix, ws, s, err, [](const unsigned long long* st) {
-          fprintf(stderr, "[pq_one] wg0: slice %.2f barrier %.2f stage %.2f scan %.2f publish %.2f | last: since wg0 start %.2f merge %.2f replay %.2f us\n",
-                  (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01, (st[3] - st[2]) * 0.01, (st[4] - st[3]) * 0.01, (st[5] - st[4]) * 0.01,
-                  (st[8] - st[0]) * 0.01, (st[9] - st[8]) * 0.01, (st[10] - st[9]) * 0.01);
-        }, &verdict))
-      return rc;
-    if (verdict == 2) {
-      const int32_t* h_pos = ix->hio_out.as<const int32_t>();
-      for (size_t i = 0; i < n_out; ++i) out_ids[i] = h_pos[i] >= 0 ? ix->h_ids[(size_t)h_pos[i]] : -1;
-      memcpy(out_dist, h_pos + n_out, n_out * 4);
-      return FREDDY_OK;
-    }
-  }
-  if (int rc = pq_batch(ix, view, s, d_q, Q, k, sentinel, blk_off, packed, pos, n_blocks, d_oi, d_od)) return rc;
-  if (!direct) {
-    hipLaunchKernelGGL(host_io_out_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, d_oi, d_od, ix->hio_out.as<int32_t>(), (int)n_out);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  memcpy(out_ids, ix->hio_out.p, n_out * 4);
-  memcpy(out_dist, ix->hio_out.as<const int32_t>() + n_out, n_out * 4);
-  return FREDDY_OK;
+  if (int rc = pq_batch(ix, t.view, s, c.d_q, Q, k, sentinel, t.blk_off, t.packed, t.pos, t.n_blocks, c.d_oi, c.d_od)) return rc;
+  return pq_stage_out(ix, s, c, out_ids, out_dist);
 }
 
 static int check_subset(const int32_t* subset_ids, int64_t n_subset) { return (n_subset < 0 || (n_subset > 0 && !subset_ids)) ? fail(FREDDY_E_ARG, "bad subset") : 0; }

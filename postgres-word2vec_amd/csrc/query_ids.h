@@ -1,5 +1,5 @@
 // query_ids.h -- searches whose queries are rows of a pinned vector table, named by id (freddy_gpu_*_search_ids, include/freddy_gpu.h):
-// what ivfadc.hip, pq.hip, exact.hip and rerank.hip share for them (similarity.hip: the gather).
+// what pipeline.hip, pq.hip, exact.hip and rerank.hip share for them (similarity.hip: the gather).
 //   QuerySrc             where the queries of a host-buffer search come from: the caller's floats, or (device table, row numbers).  Every place
 //                        that read the caller's host pointer takes one; with `host` set it does exactly what it did before.
 //   query_gather_kernel  rows[0..n) of the row-major table [N][d] -> a contiguous query block [n][d].  The row numbers arrive in the
@@ -175,7 +175,7 @@ int join_query_block_for(freddy_gpu_index* ivpq, int Q, float** block);
 int knn_join_block(freddy_gpu_index* ivpq, int Q, int k, const int32_t* target_ids, int64_t n_targets, int alpha, int pvf, int method, int use_target_lists,
                    float confidence, int double_threshold, int32_t* out_ids, float* out_dist, int32_t* iterations_out);
 
-// ---- ivfadc.hip / pq.hip: the host-buffer searches behind the public entry points, for either source (arguments already checked) ----
+// ---- pipeline.hip / pq.hip: the host-buffer searches behind the public entry points, for either source (arguments already checked) ----
 int ivfadc_search_src(freddy_gpu_index* ix, const QuerySrc& qs, int Q, int k, int W, float sentinel, int found_rule, int32_t* out_ids, float* out_dist);
 int pq_search_src(freddy_gpu_index* ix, const QuerySrc& qs, int Q, int k, float sentinel, const int32_t* subset_ids, int64_t n_subset, int32_t* out_ids,
                   float* out_dist);

@@ -57,7 +57,7 @@ struct FilterArgs {
   // selection-then-replay keeps of EXACT keys: DESIGN.md 3); a cut on a cheap bound only has to let every row at or below the
   // query's k-th smallest exact distance through.  (Appended: the fields above keep their offsets.)
   int Lt;
-  // The ELASTIC scan (ivf_filter5_kernel; ivfadc.hip ivf_scan_filter; appended likewise).  elastic = the handle's four advisory words
+  // The ELASTIC scan (ivf_filter5_kernel; ivf_scan.hip ivf_scan_filter; appended likewise).  elastic = the handle's four advisory words
   // {active, pending, started, yielded}, NULL: off -- the whole grid is guaranteed, as before.  Workgroups below n_own are the scan's
   // GUARANTEED ones (own entry by number); those from n_own on are EXTRAS: one takes work only while no scan but its own is announced
   // (pending) and fewer than `cap` scan workgroups are alive, and stops claiming entries once one is announced (elastic_yield = 2:

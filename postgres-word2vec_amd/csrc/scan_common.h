@@ -13,16 +13,10 @@
 
 #include <type_traits>
 
+#include "ivf_sizes.h"   // FUSED_T, FUSED_NW, FUSED_G, FUSED_RMAX, FUSED_E, FUSED_UNIT_BLOCKS: the chunk geometry
 #include "wave_topk.h"
 
 namespace freddy {
-
-static constexpr int FUSED_T = 512;
-static constexpr int FUSED_NW = FUSED_T / 64;
-static constexpr int FUSED_G = 16;                                 // (query, cell) items per workgroup
-static constexpr int FUSED_RMAX = 8;
-static constexpr int FUSED_E = 2;                                  // codes per lane: K <= 1024
-static constexpr int FUSED_UNIT_BLOCKS = FUSED_RMAX * FUSED_NW;   // 64 row blocks = 4096 rows per chunk
 
 // ---------------------------------------------------------------------------------------
 // Cell-major grouping of the round's (query, cell) items: the probe plan appends every item to its

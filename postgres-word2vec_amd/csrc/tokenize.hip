@@ -1,5 +1,5 @@
 // tokenize.hip -- text vectors from token ids on a raw-vector handle (tokenize.h): freddy_gpu_tokenize, and the three *_search_texts
-// calls, which search over such vectors through the public float entry points of ivfadc.hip, pq.hip and exact.hip.
+// calls, which search over such vectors through the public float entry points of pipeline.hip, pq.hip and exact.hip.
 #include "internal.h"
 
 #include "tokenize.h"

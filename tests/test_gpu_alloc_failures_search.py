@@ -182,10 +182,11 @@ def test_grouping_pq_and_pq_assign(gpu, oracle, tabs):
 # =======================================================================================
 # ivfadc
 # =======================================================================================
-# floors (ivfadc.hip, ivf_host.h): one query: hio_out (:846) + the one-launch buffer w_oneb (one_buffer) = 2; a batch: the staging of
-# either host path (the pipeline's lane_open: h_in, h_out, d_q, d_ids, d_dist; ivfadc_sync_search: w_q, w_out_ids, w_out_dist) = 3 at
-# least, and the run's nine buffers (ivf_host.h:64-68) = 12; fused = 0 adds w_resid, w_lut, w_part (:609) = 15; k = 600 adds bigk.h's
-# w_bigsel + w_floor (:101) = 14; the device-pointer entry: the nine + w_distT, w_used, w_qn2 (:599) = 12
+# floors: one query: hio_out (one.hip ivf_one) + the one-launch buffer w_oneb (one_buffer) = 2; a batch: the staging of either host
+# path (pipeline.hip: lane_open's h_in, h_out, d_q, d_ids, d_dist; ivfadc_sync_search's w_q, w_out_ids, w_out_dist) = 3 at least, and
+# the run's nine buffers (ivf_run.h ivf_run_ensure) = 12; fused = 0 adds w_resid, w_lut, w_part (ivfadc.hip ivfadc_begin) = 15; k = 600
+# adds bigk.h's w_bigsel + w_floor (generic.hip bigk_select_replay) = 14; the device-pointer entry: the nine + w_distT, w_used, w_qn2
+# (ivfadc_begin) = 12
 @pytest.mark.parametrize("form", ["one", "batch64", "fused0", "k600", "dev"])
 def test_ivfadc_search(gpu, oracle, tabs, form):
     x = tabs["x"]

@@ -1,4 +1,4 @@
-"""-m gpu: every path of ivfadc.hip and pq.hip taking turns on handles that are pinned ONCE.  The paths size and overwrite the same
+"""-m gpu: every path of the IVFADC units (ivfadc.hip and the units it calls) and pq.hip taking turns on handles that are pinned ONCE.  The paths size and overwrite the same
 workspace of their handle (items, counters, survivor regions, the query table and its compact copy, the partial lists, the
 one-launch buffer), and a flat-PQ batch runs the IVFADC filter + refine chain on a run state of its own making; a fixed sequence
 of calls is run forward and then backward, so every path follows every kind of neighbour.  Every call's lists must be bit for bit

@@ -296,13 +296,13 @@ def test_ivf_sequence_equals_oracle_and_a_fresh_pin(gpu, oracle, shape, n0, step
 
 def test_ivf_one_list_grows_past_a_scan_unit_and_past_256_blocks(gpu, oracle):
     """More rows than the table holds go into ONE cell, twice.  The boundaries are the source's: a cell-grouped work entry scans
-    at most FUSED_UNIT_BLOCKS row blocks (scan_common.h: FUSED_RMAX * FUSED_NW = 64 blocks = 4096 rows; ivfadc.hip sizes the
+    at most FUSED_UNIT_BLOCKS row blocks (ivf_sizes.h: FUSED_RMAX * FUSED_NW = 64 blocks = 4096 rows; ivfadc.hip sizes the
     survivor regions by upi = ceil(max_list_blocks / FUSED_UNIT_BLOCKS)), and the generic scan cuts a list into chunks of 256
-    blocks (ivf_host.h generic_chunks: 256 blocks per chunk of a round of more than 64 items, n = ceil(max_list_blocks / blocks)).
+    blocks (ivf_run.h generic_chunks: 256 blocks per chunk of a round of more than 64 items, n = ceil(max_list_blocks / blocks)).
       step 1: 4200 rows into cell X -- its list crosses 4096 rows: upi 1 -> 2
       step 3: 12200 rows into cell X -- its list crosses 16384 rows = 256 blocks: nchunk 1 -> 2, upi -> 5"""
-    unit_blocks = _source_constant("scan_common.h", "FUSED_UNIT_BLOCKS")
-    host = open(os.path.join(CSRC, "ivf_host.h")).read()
+    unit_blocks = _source_constant("ivf_sizes.h", "FUSED_UNIT_BLOCKS")
+    host = open(os.path.join(CSRC, "ivf_run.h")).read()
     assert re.search(r"blocks = n_items <= \(size_t\)GENERIC_FEW_ITEMS \? 32 : 256;", host) and re.search(r"max_list_blocks \+ blocks - 1\) / blocks", host), \
         "the generic scan's chunk is no longer 256 blocks"
     unit_rows, big_rows = unit_blocks * 64, 256 * 64

@@ -19,8 +19,8 @@ def _bits(a):
 
 # ---- the ladder and the case lists ------------------------------------------------------------------------------------------
 def test_ladder_is_the_sources():
-    """pick_V of csrc/ivfadc.hip, read from the source: the restatement in width_inputs.py has the same rungs."""
-    src = open(os.path.join(CSRC, "ivfadc.hip")).read()
+    """pick_V of csrc/generic.hip, read from the source: the restatement in width_inputs.py has the same rungs."""
+    src = open(os.path.join(CSRC, "generic.hip")).read()
     body = src[src.index("int pick_V(int L) {"):]
     body = body[:body.index("\n}")]
     rungs = [(int(a), int(b)) for a, b in re.findall(r"if \(L <= (\d+)\) return (\d+);", body)]

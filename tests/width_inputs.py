@@ -2,7 +2,7 @@
 sides of its bounds, and of tests/test_width_inputs_cpu.py, which proves with the oracle alone that these cases reach what they
 claim.  Tables, queries and case lists only: nothing here touches a device.
 
-Every search path keeps its candidates in a WaveSelect<V> of 64 V keys and picks V from one ladder (csrc/ivfadc.hip pick_V,
+Every search path keeps its candidates in a WaveSelect<V> of 64 V keys and picks V from one ladder (csrc/generic.hip pick_V,
 restated below): L <= 64 -> 1, <= 128 -> 2, <= 256 -> 4, <= 512 -> 8, <= 1024 -> 16.  What L is depends on the family:
   ivfadc12 / ivfadc0   adc_scan_kernel<12 | 0, V> + merge_replay_kernel<V> of the IVFADC generic path      L = 2k
   pq12 / pq0           the same kernels from the flat PQ scan                                               L = min(2k, 1024)
@@ -26,7 +26,7 @@ WIDTHS = (1, 2, 4, 8, 16)
 
 
 def pick_V(L):
-    """csrc/ivfadc.hip pick_V: the selection width of a list of L keys; 0 = no instantiation."""
+    """csrc/generic.hip pick_V: the selection width of a list of L keys; 0 = no instantiation."""
     for v, r in zip(WIDTHS, RUNGS):
         if L <= r:
             return v
