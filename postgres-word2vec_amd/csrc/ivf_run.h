@@ -4,6 +4,7 @@
 #pragma once
 
 #include "internal.h"
+#include "chunk_plan.h"
 #include "ivf_sizes.h"
 
 // ---- shapes and sizes ----------------------------------------------------------------------------------------------------
@@ -18,6 +19,7 @@ static int units_per_item(const freddy_gpu_index* ix) { return std::max(1, (ix->
 static constexpr int GENERIC_FEW_ITEMS = 64;
 struct Chunks { int blocks, n; };
 static Chunks generic_chunks(const freddy_gpu_index* ix, size_t n_items) {
+  static_assert(GENERIC_MANY_BLOCKS == 256, "chunk_plan.h counts the chunks of a round of many items");
   const int blocks = n_items <= (size_t)GENERIC_FEW_ITEMS ? 32 : 256;
   return {blocks, std::max(1, (ix->max_list_blocks + blocks - 1) / blocks)};
 }
@@ -95,7 +97,7 @@ static int check_ivfadc_args(const freddy_gpu_index* ix, const void* q, int Q, i
   if (*W > ix->C) *W = ix->C;
   return 0;
 }
-// fn(q0, n) for the chunks [q0, q0 + n) of at most `per` queries, until one fails
+// fn(q0, n) for the chunks [q0, q0 + n) of at most `per` queries (chunk_plan.h), until one fails
 template <class F>
 static int for_chunks(int Q, int per, F&& fn) {
   for (int q0 = 0; q0 < Q; q0 += per)

@@ -108,26 +108,9 @@ int ivfadc_finish(IvfRun& r, int n_next) {
   return 0;
 }
 
+// the queries of a chunk within option lut_budget_mb (chunk_plan.h), for this handle
 int max_queries_per_chunk(const freddy_gpu_index* ix, int W, int k) {
-  // workspace per query: the LUTs of its W items (generic path) or their survivor regions (fused path)
-  const size_t upi = (size_t)units_per_item(ix);
-  size_t lut_bytes = sizeof(float) * (size_t)ix->m * ix->K * (size_t)W;
-  if (2 * k > 64) {
-    // lists beyond the cell-grouped scans' selection width take the generic kernels: one list of L keys per (item, chunk) beside
-    // the LUTs, and from k = 513 on the passes' selected keys (bigk.h: ceil(2k / 1024) x 1024 per query)
-    const size_t L = (size_t)std::min(2 * k, 1024), nchunk = (size_t)generic_chunks(ix, SIZE_MAX).n;   // (a chunk of many items: the coarse chunks)
-    lut_bytes += sizeof(u64) * (size_t)W * nchunk * L;
-    if (2 * k > 1024) lut_bytes += sizeof(u64) * (size_t)((2 * k + BIGK_PASS - 1) / BIGK_PASS) * BIGK_PASS;
-  }
-  const bool special = fused_shape(ix);
-  const size_t surv_bytes = upi <= (special ? 8u : 32u) ? sizeof(u64) * (size_t)W * upi * FUSED_NW * FUSED_RMAX * 64 : 0;
-  const size_t per_query = special ? std::max(lut_bytes, surv_bytes) : lut_bytes + surv_bytes;   // (multi.h: the LUTs of all items AND their survivor regions)
-  size_t n = ((size_t)ix->tune.lut_budget_mb << 20) / std::max<size_t>(per_query, 1);
-  // the fused path's per-cell item buckets are [C][queries of the chunk]: keep them within 256 MiB
-  if (surv_bytes) n = std::min<size_t>(n, ((size_t)256 << 20) / (sizeof(int32_t) * (size_t)std::max(ix->C, 1)));
-  if (n < 1) n = 1;
-  if (n > (1u << 20)) n = 1u << 20;
-  return (int)n;
+  return freddy::max_queries_per_chunk(ix->tune.lut_budget_mb, ix->m, ix->K, W, k, units_per_item(ix), fused_shape(ix), ix->C, ix->max_list_blocks);
 }
 
 extern "C" int freddy_gpu_ivfadc_search_dev(freddy_gpu_index_t* ix, const float* d_queries, int32_t Q, int32_t k,

@@ -47,6 +47,9 @@ static int ivfadc_sync_search(freddy_gpu_index* ix, const QuerySrc& qs, int Q, i
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   if (qs.host) HIP_TRY(hipMemcpyAsync(ws->w_q.p, qs.host, sizeof(float) * (size_t)Q * ix->d, hipMemcpyHostToDevice, s));
   else if (int rc = launch_query_gather(ix, s, qs, qs.rows, ws->w_q.as<float>(), Q, ix->d)) return rc;
+  // (lane_retire, the only caller, brings the stragglers of ONE sub-batch, and pipe_plan caps a sub-batch at this very chunk size for
+  // the same handle, W and k: Q <= max_queries_per_chunk, so the loop runs once.  It stays a loop so that a caller with more queries
+  // would still respect the budget; no test can make it run twice -- tests/chunk_inputs.py STRAGGLERS)
   if (int rc = for_chunks(Q, max_queries_per_chunk(ix, W, k), [&](int q0, int n) {
         IvfRun r;
         if (int rc = ivfadc_begin(ix, s, scan_share_now(ix->tune.scan_share, true, ix->device), ws->w_q.as<float>() + (size_t)q0 * ix->d, n, k, W, sentinel, found_rule,

@@ -169,14 +169,6 @@ __global__ __launch_bounds__(256) void pq_front_kernel(PqFrontArgs a) {
   else pq_records_body(a, b - n_table, smem);
 }
 
-// survivor regions: 32 KiB per (query, pseudo-list) within the workspace budget; the buckets [lists][queries] within 256 MiB
-static int pq_fused_queries_per_chunk(const freddy_gpu_index* ix, int64_t n_blocks) {
-  const size_t lists = (size_t)((n_blocks + FUSED_UNIT_BLOCKS - 1) / FUSED_UNIT_BLOCKS);
-  size_t n = ((size_t)ix->tune.lut_budget_mb << 20) / (sizeof(u64) * lists * FUSED_NW * FUSED_RMAX * 64);
-  n = std::min<size_t>(n, ((size_t)256 << 20) / (sizeof(int32_t) * lists));
-  return (int)std::max<size_t>(16, std::min<size_t>(n, 1u << 16));
-}
-
 // An IVF-shaped view (*view; created on first use) of `n_rows` rows in `n_blocks` packed blocks: pseudo-lists, zero centroids,
 // row terms, ids.  Everything is enqueued on s; nothing is synchronised.
 static int pq_view_refresh(freddy_gpu_index* ix, freddy_gpu_index** view, hipStream_t s, const uint32_t* packed, const int32_t* pos,
@@ -302,16 +294,6 @@ static int pq_one(freddy_gpu_index* ix, hipStream_t s, const float* h_q, int k, 
   return 0;
 }
 
-// Queries per chunk of the generic scan over `n_blocks` row blocks: a LUT per query, one list of L keys per (query, 4096-row
-// chunk) -- the finest chunks pq_chunk may choose -- and, from k = 513 on, the keys the selection passes keep (bigk.h).
-static int pq_queries_per_chunk(const freddy_gpu_index* ix, int64_t n_blocks, int k) {
-  const size_t L = (size_t)std::min(2 * k, 1024), nchunk = (size_t)std::max<int64_t>(1, (n_blocks + 63) / 64);
-  size_t per_query = sizeof(float) * (size_t)ix->m * ix->K + sizeof(u64) * nchunk * L;
-  if (2 * k > 1024) per_query += sizeof(u64) * (size_t)((2 * k + 1024 - 1) / 1024) * 1024;
-  const size_t n = ((size_t)ix->tune.lut_budget_mb << 20) / per_query;
-  return (int)std::min<size_t>(std::max<size_t>(n, 1), (size_t)1 << 20);
-}
-
 static int pq_chunk(freddy_gpu_index* ix, hipStream_t s, const float* d_q, int Q, int k, float sentinel,
                     const int32_t* blk_off, const uint32_t* packed, const int32_t* pos, int64_t n_blocks,
                     int32_t* d_out_ids, float* d_out_dist) {
@@ -343,7 +325,8 @@ static int pq_chunk(freddy_gpu_index* ix, hipStream_t s, const float* d_q, int Q
 // The chunks of a batch: through the cell-grouped scan of `view` (an IVF-shaped view of the rows), or view == NULL: the generic scan.
 static int pq_batch(freddy_gpu_index* ix, freddy_gpu_index* view, hipStream_t s, const float* d_q, int Q, int k, float sentinel, const int32_t* blk_off,
                     const uint32_t* packed, const int32_t* pos, int64_t n_blocks, int32_t* d_oi, float* d_od) {
-  return for_chunks(Q, view ? pq_fused_queries_per_chunk(ix, n_blocks) : pq_queries_per_chunk(ix, n_blocks, k), [&](int q0, int n) {
+  const int64_t mb = ix->tune.lut_budget_mb;   // (the chunk sizes of either path: chunk_plan.h)
+  return for_chunks(Q, view ? pq_fused_queries_per_chunk(mb, n_blocks) : pq_queries_per_chunk(mb, ix->m, ix->K, n_blocks, k), [&](int q0, int n) {
     const float* q = d_q + (size_t)q0 * ix->d;
     if (view) return pq_fused_chunk(ix, view, s, q, n, k, sentinel, d_oi + (size_t)q0 * k, d_od + (size_t)q0 * k);
     return pq_chunk(ix, s, q, n, k, sentinel, blk_off, packed, pos, n_blocks, d_oi + (size_t)q0 * k, d_od + (size_t)q0 * k);

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import chunk_inputs
 import dev_contract_inputs as dci
 import util
 
@@ -217,11 +218,10 @@ def test_default_stream_then_host_buffer_call(gpu, pins):
 
 
 def _max_queries_per_chunk(mb, m, K, W, upi, C_):
-    """csrc/ivfadc.hip max_queries_per_chunk for a 300-d / m = 12 table and 2k <= 64: the LUTs of a query's W items or their
-    survivor regions (8 waves x 8 x 64 keys of 8 bytes per 4096-row unit), whichever is larger, within lut_budget_mb."""
-    per_query = max(4 * m * K * W, 8 * W * upi * 8 * 8 * 64)
-    n = min((mb << 20) // per_query, (256 << 20) // (4 * C_))
-    return max(1, min(n, 1 << 20))
+    """csrc/chunk_plan.h max_queries_per_chunk (restated in tests/chunk_inputs.py) for a 300-d / m = 12 table and 2k <= 64: the LUTs
+    of a query's W items or their survivor regions (8 waves x 8 x 64 keys of 8 bytes per 4096-row unit), whichever is larger,
+    within lut_budget_mb.  Holds for upi <= 8 only: longer lists have no survivor term and no bucket cap."""
+    return chunk_inputs.ivf_per(mb, m, K, W, 5, upi, True, C_, 64 * upi)
 
 
 @pytest.mark.parametrize("where", ["first", "last"])
