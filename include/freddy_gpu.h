@@ -411,7 +411,16 @@ int freddy_gpu_pq_search_pv_ids(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs
  * size or a NULL set of positive size; FREDDY_E_LIMIT for k > 4096); FREDDY_E_KIND; a poisoned handle.  Concurrency and mutations
  * as above: a mutation before the call is seen, none may run beside it.
  * Option "exact_resolve" = 1 makes freddy_gpu_exact_search (subset), freddy_gpu_exact_join and freddy_gpu_exact_analogy (subset)
- * resolve their sets the same way (default 0: on the host, as before; no result changes); these two calls always do. */
+ * resolve their sets the same way (default 0: on the host, as before; no result changes); these two calls always do.
+ * Option "exact_wide" (vector handles, default 0): 1 lets exact kNN (freddy_gpu_exact_search, _exact_search_ids, the *_search_texts
+ * forms; whole table, k <= 32, as for narrow tables) take filter + refine on tables of 512 < d <= 2048, d % 4 == 0; the lists are the
+ * same bits.  Setting it takes the table's statistics and builds the fragment-order copy of the rows, a THIRD copy of the table:
+ * freddy_gpu_index_bytes grows by N d 4 bytes (rounded up to strips of 32 rows and 16 dimensions) and returns when the option goes
+ * back to 0.  While it is 1, append_rows / remove_rows / update_rows keep the copy current (their contract is unchanged).  d <= 512:
+ * accepted, no effect.  FREDDY_E_LIMIT (the message names d) for d > 2048 or d % 4 != 0, FREDDY_E_NOMEM when the copy cannot be
+ * allocated: the handle and the option stay as they were.  A table with a non-finite element or a row norm^2 >= 1e30 accepts the
+ * option and keeps the all-exact kernels.  The exact join, the exact analogies, exact_assign and the similarity calls run the
+ * kernels they run without it.  "exact_wide_shape" (0, 1, 2) chooses among the measured shapes of the kernel (csrc/exact_wide.h). */
 int freddy_gpu_exact_search_ids(freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k,
                                 const int32_t* subset_ids, int64_t n_subset, int32_t* out_query_ids /*[n_ids]*/,
                                 int32_t* n_queries, int32_t* out_ids /*[n_ids][k]*/, float* out_sim /*[n_ids][k]*/);

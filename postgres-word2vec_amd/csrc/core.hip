@@ -279,6 +279,8 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   else if (n == "exact_filter") t.exact_filter = (int)value;
   else if (n == "exact_join_tile") t.exact_join_tile = (int)value;
   else if (n == "exact_resolve") t.exact_resolve = value != 0 ? 1 : 0;
+  else if (n == "exact_wide") return exf_wide_set(ix, value);
+  else if (n == "exact_wide_shape") t.exact_wide_shape = value == 1 || value == 2 ? (int)value : 0;
   else if (n == "resolve_block") t.resolve_block = (int)std::max<int64_t>(0, std::min<int64_t>(value, (int64_t)1 << 20));
   else if (n == "analogy_pass") t.analogy_pass = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
   else if (n == "tokenize_pass") t.tokenize_pass = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));

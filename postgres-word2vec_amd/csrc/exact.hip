@@ -16,7 +16,7 @@
 // changed_strips (update_rows, r0 = 0): the 32-row strips that hold a rewritten row -- all that is laid out again when the state
 // the statistics lead to is the one the fragment copy was built for.
 int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n, const std::vector<int32_t>* changed_strips) {
-  const bool shape_ok = ix->d % 4 == 0 && ix->d <= 512 && ix->d >= 16;
+  const bool shape_ok = ix->d % 4 == 0 && ix->d <= (ix->tune.exact_wide ? EXW_MAX_D : EXF_NARROW_D) && ix->d >= 16;   // (option exact_wide admits the wide tables: exact_wide.hip)
   if (!shape_ok) { ix->exf_ok = false; return 0; }
   if (ix->tune.exact_filter == 0 || ix->exf_never) { ix->exf_never = true; ix->exf_ok = false; return 0; }   // (option exact_filter = 0 when the table is pinned: no third copy of it -- nor later, when remove_rows takes the statistics again from row 0)
   if (n <= 0) return 0;
@@ -112,7 +112,8 @@ static int exact_filter_search(freddy_gpu_index* ix, hipStream_t s, const float*
   // small per-call state: [0..63] thr, [64..127] qeps, [128..191] qunscale, [192..255] cand_cnt, [256] qbad, [257] arrived
   float* sm = ix->exf_small.as<float>();
   ExfPass p;
-  p.labels = &EXF_KNN_LABELS; p.fp = fp; p.thr = sm; p.qeps = sm + 64; p.qunscale = sm + 128; p.cand_cnt = reinterpret_cast<int32_t*>(sm + 192);
+  const bool wide = d > EXF_NARROW_D;   // (option exact_wide: the query image streams through LDS, exact_wide.h)
+  p.labels = wide ? &EXF_KNN_WIDE_LABELS : &EXF_KNN_LABELS; p.fp = fp; p.thr = sm; p.qeps = sm + 64; p.qunscale = sm + 128; p.cand_cnt = reinterpret_cast<int32_t*>(sm + 192);
   p.flags = p_out + 2 * (size_t)Q * k; p.k = k; p.grid_q = EXF_QT; p.total_wgs = Q; p.sample_when_empty = true;
   ExfArgs fa;
   fa.xf = ix->exf_xf.as<h8v>(); fa.T = T; fa.qfrag = ix->exf_qfrag.as<h8v>(); fa.qunscale = p.qunscale; fa.thr = p.thr; fa.cand_cnt = p.cand_cnt;
@@ -124,6 +125,7 @@ static int exact_filter_search(freddy_gpu_index* ix, hipStream_t s, const float*
     if (int rc = exf_chain(ix, s, p, N, [&](auto sample, int64_t n_rows) {
       constexpr bool SAMPLE = decltype(sample)::value;
       filter_rows(fa, fp, SAMPLE, n_rows, ix->exf_sample.as<float>());
+      if (wide) { exf_wide_launch(ix, s, fa, p.nq, SAMPLE); return; }
       const dim3 grid(filter_grid(ix, n_rows));
       if (p.nq <= 32) hipLaunchKernelGGL((exf_filter_kernel<1, SAMPLE>), grid, dim3(EXF_WG), tile_lds, s, fa);
       else hipLaunchKernelGGL((exf_filter_kernel<2, SAMPLE>), grid, dim3(EXF_WG), 2 * tile_lds, s, fa);
@@ -276,7 +278,7 @@ static int exact_search_rows(freddy_gpu_index* ix, const QuerySrc& queries, int3
   if (sub_rows)   // (an empty subset: the scan below finds nothing)
     if (int rc = vec_subset(ix, ws, s, *sub_rows, &xb, &pos, &n_rows, &n_blocks)) return rc;
   // Filter + refine (exact2.h): the whole table, k <= 32, finite rows of a supported shape; identical lists.
-  const bool want_filter = !sub_rows && exf_wanted(ix, n_rows) && k <= 32 && n_rows >= 1;
+  const bool want_filter = !sub_rows && exf_knn_wanted(ix, n_rows) && k <= 32 && n_rows >= 1;
   if (want_filter) {
     // one block of mapped host memory: [lists][verdict words][the queries, when they are few]: the kernels read a handful of
     // queries where the host put them (1.2 KB each over PCIe) and write the lists where the host reads them

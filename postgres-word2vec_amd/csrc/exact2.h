@@ -29,6 +29,20 @@
 //   MFMA accumulation    fp32, <= 64 roundings (19 steps x 3 products + in-step adds), doubled in case the matrix core
 //                        TRUNCATES instead of rounding: 128 u sum|terms|            <= 0.77e-5 |x||q|
 //   sum < 2.7e-5 |x||q|;   eps(q) = EXF_EPS X |q| with EXF_EPS = 4e-5 (d <= 512: the chain term grows to 3.1e-5 -> 6e-5).
+// Wide rows, 512 < d <= 2048 (option exact_wide, exact_wide.h: same operands, same products), the same lines, T = ceil(d / 16):
+//   reference chain      (1+u)^(d+1) - 1 = (d+1) u + ((d+1) u)^2 / 2 + ..        d = 768: 4.59e-5   1024: 6.11e-5   1536: 9.17e-5   2048: 1.222e-4
+//                        (this term is REACHED: x = q = (1, t, .., t) with t^2 next to half an ulp of 1 rounds all d - 1 additions one way)
+//   dropped lo.lo        <= 2^-22 sum|x_i q_i|, whatever d                                 0.03e-5
+//   lo rounded to f16    <= 2 * 2^-22 sum|x_i q_i|, whatever d.  A subnormal lo is off by <= 2^-25 against a largest scaled element
+//                        >= 2^13: summed over the row <= sqrt(d) 2^-38 |x||q| < 2e-10       0.05e-5
+//   MFMA accumulation    a product passes <= 16 in-step adds of its own instruction and then the 3 T - 1 accumulations behind it:
+//                        <= 3 T + 16 roundings, doubled for a truncating matrix core, on sum|terms| <= (1 + 2^-10) sum|x_i q_i|:
+//                        2 (3 T + 16) u                  T = 48: 1.91e-5   64: 2.48e-5   96: 3.63e-5   128: 4.77e-5
+//   sum                                                  d <= 768: 6.58e-5   1024: 8.67e-5   1536: 1.288e-4   2048: 1.707e-4
+//   EXF_EPS, the sum raised by a fifth or more (what the narrow factors leave: the products of the bound are binary32 themselves)
+//                                                        d <= 768: 8e-5      1024: 1.1e-4    1536: 1.6e-4     2048: 2.1e-4
+// Steps, not one worst case: the candidates of a 768-d table should not pay for the chain of a 2048-d one.  The products that
+// underflow inside the reference's chain cost <= d 2^-150 < 3e-42 in all, far below the floors that follow.
 // Small magnitudes.  The similarity is bilinear, the norms are not: a table at 2^-80 searched with unit-scale queries has
 // similarities near 2^-80 (normal numbers the reference orders strictly) while every square of its elements is 0 in binary32.
 // A norm taken from a binary32 sum of squares alone would be 0 there and eps(q) would shrink to its floor, orders of magnitude
@@ -41,6 +55,7 @@
 // lies below 1e-37 too).  It does not stand in for a norm that underflowed.  One more absolute term: the scaled products are
 // unscaled by qunscale = 2^-(eq + ex), which is 0 from eq + ex = 150 on.  The largest |element| of the query times the table's
 // is then <= 2^-122, so |s| <= d 2^-122 < 1e-34 (d <= 512) for every row while a = 0: the floor is 1e-34 for such a query.
+// (The bound grows with d: 2048 * 2^-122 = 3.86e-34, so the floor is 4e-34 for 512 < d <= 2048 -- exf_zero_scale_floor.)
 // Every refined row has both numbers in hand: the refine kernel counts rows whose similarity left [a - eps, a + eps]
 // (freddy_gpu_filter_bound_violations on the vector handle; the tests refine EVERY row, option exact_refine_all).
 //
@@ -64,7 +79,14 @@ static constexpr int EXF_TARGET_EXP = 14;  // scaled maxima land in [2^13, 2^14]
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 typedef float f16acc __attribute__((ext_vector_type(16)));
 
-__host__ __device__ __forceinline__ float exf_eps_factor(int d) { return d <= 300 ? 4e-5f : 6e-5f; }
+static constexpr int EXW_MAX_D = 2048;     // the widest row the bracket covers (option exact_wide)
+__host__ __device__ __forceinline__ float exf_eps_factor(int d) {
+  if (d <= 512) return d <= 300 ? 4e-5f : 6e-5f;
+  return d <= 768 ? 8e-5f : d <= 1024 ? 1.1e-4f : d <= 1536 ? 1.6e-4f : 2.1e-4f;   // (d <= EXW_MAX_D; the table above)
+}
+// the floor of eps(q) for a query whose scaled products unscale to 0 (eq + ex >= 150): every |s| <= d 2^-122 (1 + 2e-4), which is
+// < 1e-34 for d <= 512 and 3.86e-34 for d = 2048
+__host__ __device__ __forceinline__ float exf_zero_scale_floor(int d) { return d <= 512 ? 1e-34f : 4e-34f; }
 
 // power-of-two exponent e with |v| * 2^e in [2^(T-1), 2^T] (v > 0, finite); 0 for v == 0
 __host__ __device__ __forceinline__ int exf_scale_exp(float vmax) {
@@ -210,8 +232,8 @@ static __global__ __launch_bounds__(256) void exf_prep_kernel(ExfPrepArgs a) {
     const int eq = exf_scale_exp(am);
     eq_s = eq;
     const float qn = nn >= EXF_N2_FLOOR ? __builtin_sqrtf(nn) * (1.0f + 1e-5f) : exf_norm_from_amax(am, a.d);   // (a NaN sum: a non-finite query, qbad)
-    // (eq + ex >= 150: qunscale is 0, every a of this query is 0 and cannot rank -- its error is |s| itself, <= d 2^-122 < 1e-34)
-    const float eps_floor = eq + a.ex >= 150 ? 1e-34f : 1e-37f;
+    // (eq + ex >= 150: qunscale is 0, every a of this query is 0 and cannot rank -- its error is |s| itself, <= d 2^-122 < 1e-34; wider rows: exf_zero_scale_floor)
+    const float eps_floor = eq + a.ex >= 150 ? exf_zero_scale_floor(a.d) : 1e-37f;
     a.qeps[q] = live ? a.eps_factor * a.xmax_norm * qn * (1.0f + 1e-6f) + eps_floor : 0.0f;
     a.qunscale[q] = __builtin_ldexpf(1.0f, -(eq + a.ex));
   }

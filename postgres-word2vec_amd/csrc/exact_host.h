@@ -12,8 +12,14 @@ static constexpr int64_t EXF_AUTO_ROWS = 8192;
 // What exact kNN, the exact join and the exact analogies all ask before they take filter + refine: the handle has the filter's copy
 // of its rows, the option does not forbid it, and it is forced or the set has `auto_rows` rows.  What else a call asks (k, no
 // subset, the LDS its tiles take) stands at the call.
-static bool exf_wanted(const freddy_gpu_index* ix, int64_t n_rows, int64_t auto_rows = EXF_AUTO_ROWS) {
+// Under option exact_wide the handle has that copy for 512 < d <= 2048 too, and exact kNN alone takes it (exf_knn_wanted): the
+// tiles and bounds of the join's and the analogies' filters were derived for d <= 512 (EXF_NARROW_D), so they keep their kernels.
+static constexpr int EXF_NARROW_D = 512;
+static bool exf_knn_wanted(const freddy_gpu_index* ix, int64_t n_rows, int64_t auto_rows = EXF_AUTO_ROWS) {
   return ix->exf_ok && ix->tune.exact_filter != 0 && (ix->tune.exact_filter == 1 || n_rows >= auto_rows);
+}
+static bool exf_wanted(const freddy_gpu_index* ix, int64_t n_rows, int64_t auto_rows = EXF_AUTO_ROWS) {
+  return ix->d <= EXF_NARROW_D && exf_knn_wanted(ix, n_rows, auto_rows);
 }
 
 // What the filter passes over a set of rows share.  The threshold's sample: whole 32-row strips of REAL rows (a zero-padded row
@@ -71,6 +77,7 @@ static int exf_verdict_arrived(const int32_t* flags, const char* call) {
 
 struct ExfLabels { const char *prep, *sample, *threshold, *filter, *refine; };   // the chain's launches in a profile
 static constexpr ExfLabels EXF_KNN_LABELS = {"exact_prep", "exact_sample", "exact_threshold", "exact_filter", "exact_refine"};
+static constexpr ExfLabels EXF_KNN_WIDE_LABELS = {"exact_prep", "exact_sample_wide", "exact_threshold", "exact_filter_wide", "exact_refine"};   // d > 512: exf_wide_filter_kernel
 static constexpr ExfLabels EXF_JOIN_LABELS = {"exact_join_prep", "exact_join_sample", "exact_join_threshold", "exact_join_filter", "exact_join_refine"};
 
 // One pass of the chain: `nq` queries against one set of rows.  Exact kNN keeps the small arrays in exf_small (a pass is one tile of

@@ -19,6 +19,7 @@
 //   exact.hip   pin_vectors, exact kNN and the exact join (also by row id: query_ids.h, resolve.h), the rows of an id set
 //   analogy.hip the exact analogies (analogy.h), the INNER JOIN of analogy triples
 //               exact_host.h what these two share on the host: the filter + refine chain and when a call takes it, scan chunking
+//   exact_wide.hip  option exact_wide: the filter pass of exact kNN for 512 < d <= 2048 (exact_wide.h), its state on the handle
 //   rerank.hip  post verification of pq / ivf lists (pv.h), the approximate analogies over pq / ivf / ivpq (approx_analogy.h), the re-rank stage they share
 //   cluster.hip exact_assign (assign.h), the whole k-means of cluster_exact / cluster_pq (cluster.h)
 //   similarity.hip  similarities by row id: pairs, matrices, joins (similarity.h)
@@ -105,6 +106,8 @@ struct Tuning {
   int cluster_pass = 0;        // option cluster_pass: targets per assignment pass of freddy_gpu_cluster (cluster.h): 0 = 2^22; 64 at least
   int cluster_walk = 0;        // option cluster_walk: how cluster_sample_kernel finds a cluster's ranked members: 1 = it walks them from position 0 (what it does for kc > 1024), 2 = over the apply kernel's per-block counts (kc <= 1024), 0 = auto: 2 from n > 32768 on
   int exact_resolve = 0;       // option exact_resolve: how freddy_gpu_exact_search / _exact_join / _exact_analogy turn their id set into table rows: 0 = on the host (rows_of_ids), 1 = on the device (resolve.h); the *_ids forms always take the device
+  int exact_wide = 0;          // option exact_wide (vector handles): 1 = tables of 512 < d <= 2048 get the fragment-order copy and exact kNN takes filter + refine with exf_wide_filter_kernel (exact_wide.h); 0 = such tables take the all-exact scan
+  int exact_wide_shape = 0;    // option exact_wide_shape: how exf_wide_filter_kernel streams the query image: 0 = segments of 8 k-steps, one strip per wave (two workgroups per CU), 1 = segments of 16, 2 = segments of 8 and two strips per wave (profiles/exact_wide_timing.txt)
   int resolve_block = 0;       // option resolve_block: bitmap words per block of the device resolve (resolve.h): 0 = 256; tests make small tables span many blocks
   int tokenize_pass = 0;       // option tokenize_pass (set on the vector handle): texts per pass of the *_search_texts calls (tokenize.h): 0 = as many as a pinned block of 256 MiB holds
   int tokenize_unit = 0;       // option tokenize_unit: the sum of squares of freddy_gpu_tokenize's normalisation: 1 = a wave per text with lane 0 walking the chain (tok_unit_wave_kernel), 2 = a chain per lane over 64 texts (tok_unit_kernel), 0 = auto: 1 below 16384 texts, 2 from there on (tokenize.h)
@@ -269,7 +272,7 @@ struct freddy_gpu_index {
   // raw vectors (exact kNN): 64-row blocks [block][d][64]
   float* xb = nullptr;
   // exact kNN as filter + refine (exact2.h): the table's statistics (pin time / append) and the per-call buffers
-  bool exf_ok = false;          // every element finite, d % 4 == 0, d <= 512
+  bool exf_ok = false;          // every element finite, d % 4 == 0, d <= 512 (d <= 2048 under option exact_wide: only exact kNN takes the filter there, exf_wanted / exf_wide_wanted)
   bool exf_never = false;       // the statistics were once taken with option exact_filter = 0: rows are missing from them, the filter stays off for good
   bool exf_dirty = true;        // no filter + refine call has completed yet, or the last one failed part-way: its device-side words are cleared before the next
   float exf_xnorm = 0.0f;       // largest row norm, rounded up
@@ -431,10 +434,11 @@ std::vector<LdsLimit> lds_limits_generic();
 std::vector<LdsLimit> lds_limits_pq();
 std::vector<LdsLimit> lds_limits_join();
 std::vector<LdsLimit> lds_limits_exact();
+std::vector<LdsLimit> lds_limits_exact_wide();
 std::vector<LdsLimit> lds_limits_analogy();
 std::vector<LdsLimit> lds_limits_rerank();
 
-namespace freddy { struct PlanArgs; struct ScanArgs; struct MergeArgs; }
+namespace freddy { struct PlanArgs; struct ScanArgs; struct MergeArgs; struct ExfArgs; }
 
 // ---- ivf_scan.hip ----
 // The work table shared by both cell-grouped scans: per-cell item counts -> (<= 12 items of a cell, 4096-row
@@ -504,6 +508,13 @@ int pq_assign_pass(freddy_gpu_index* ix, hipStream_t s, float* d_lut, int Qc, in
 
 // ---- exact.hip ----
 int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n, const std::vector<int32_t>* changed_strips = nullptr);
+// ---- exact_wide.hip ----
+// option exact_wide on a vector handle (the handle is left as it was when this fails)
+int exf_wide_set(freddy_gpu_index* ix, int64_t value);
+// exf_wide_filter_kernel over fa.n_rows rows for nq <= 64 queries (sample: the SAMPLE instantiation), enqueued on s
+void exf_wide_launch(const freddy_gpu_index* ix, hipStream_t s, const freddy::ExfArgs& fa, int nq, bool sample);
+
+// ---- exact.hip (continued) ----
 // Where the table rows of "id = ANY(set)" are: the host vector rows_of_ids made (every function then does exactly what it did
 // before), or already in ws->w_sub_rows, `resident` of them, put there by resolve_ids_device -- the copy to the device is skipped.
 // The buffer was sized for min(n_ids, N) >= resident rows before the resolve was launched, and DevBuf::ensure leaves a buffer
