@@ -420,7 +420,14 @@ int freddy_gpu_pq_search_pv_ids(freddy_gpu_index_t* pq, freddy_gpu_index_t* vecs
  * accepted, no effect.  FREDDY_E_LIMIT (the message names d) for d > 2048 or d % 4 != 0, FREDDY_E_NOMEM when the copy cannot be
  * allocated: the handle and the option stay as they were.  A table with a non-finite element or a row norm^2 >= 1e30 accepts the
  * option and keeps the all-exact kernels.  The exact join, the exact analogies, exact_assign and the similarity calls run the
- * kernels they run without it.  "exact_wide_shape" (0, 1, 2) chooses among the measured shapes of the kernel (csrc/exact_wide.h). */
+ * kernels they run without it.  "exact_wide_shape" (0, 1, 2) chooses among the measured shapes of the kernel (csrc/exact_wide.h).
+ * Option "exact_filter_k" (vector handles, default 32): the largest k for which exact kNN (the same calls) takes filter + refine,
+ * 32 .. 1024; any other value is FREDDY_E_LIMIT and the message names it.  With the default every call launches what it launched
+ * before.  Above 32 the chain takes its threshold by rank selection over a sample that grows with k and refines with a selection as
+ * wide as the list (csrc/exact_rank.h); the threshold sample and the candidate buffer grow with k (at 3 M rows and k = 1024: 64 MiB
+ * and 25 MiB, allocated by the first such call); the lists are the same bits.  A candidate buffer that overflows is the redo path it
+ * was: the all-exact scan answers the call.  The exact join and the exact analogies keep k <= 32.  "exact_rank_hist" (0, 1) chooses
+ * between the measured histogram layouts of the threshold kernel. */
 int freddy_gpu_exact_search_ids(freddy_gpu_index_t* vecs, const int32_t* query_ids, int32_t n_ids, int32_t id_rule, int32_t k,
                                 const int32_t* subset_ids, int64_t n_subset, int32_t* out_query_ids /*[n_ids]*/,
                                 int32_t* n_queries, int32_t* out_ids /*[n_ids][k]*/, float* out_sim /*[n_ids][k]*/);

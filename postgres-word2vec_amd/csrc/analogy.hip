@@ -86,6 +86,8 @@ static int analogy_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s, in
                           int32_t* d_ids, double* d_score, int32_t* flags) {
   const int d = ix->d, T = (d + 15) / 16;
   const int64_t N = ix->N;
+  // (filter_plan, not exact kNN's filter_plan_k: option exact_filter_k does not reach the analogies -- k <= AN_MAXK = 32 here, and the
+  // threshold and refine kernels of this chain are an_threshold_kernel / an_refine_kernel, whose selections hold one wave's 64 keys)
   const FilterPlan fp = filter_plan(N, (ix->tune.check_brackets & 8) != 0);
   const int n_sample = fp.n_sample, cap = fp.cap, all = fp.refine_all ? 1 : 0;
   const int passes = (na + AN_PASS - 1) / AN_PASS;

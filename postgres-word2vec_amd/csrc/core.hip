@@ -277,6 +277,12 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   }
   else if (n == "lut_budget_mb") t.lut_budget_mb = std::max<int64_t>(1, value);
   else if (n == "exact_filter") t.exact_filter = (int)value;
+  else if (n == "exact_filter_k") {
+    if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "option exact_filter_k belongs to a vector handle");
+    if (value < 32 || value > 1024) return fail(FREDDY_E_LIMIT, "option exact_filter_k: %lld is not served (32 .. 1024: above 1024 rows the all-exact scan itself works in passes)", (long long)value);
+    t.exact_filter_k = (int)value;
+  }
+  else if (n == "exact_rank_hist") t.exact_rank_hist = value == 1 ? 1 : 0;
   else if (n == "exact_join_tile") t.exact_join_tile = (int)value;
   else if (n == "exact_resolve") t.exact_resolve = value != 0 ? 1 : 0;
   else if (n == "exact_wide") return exf_wide_set(ix, value);

@@ -101,7 +101,7 @@ static int exact_filter_search(freddy_gpu_index* ix, hipStream_t s, const float*
   *fell_back = 0;
   const int d = ix->d, T = (d + 15) / 16;
   const int64_t N = ix->N;
-  const FilterPlan fp = filter_plan(N, (ix->tune.check_brackets & 4) != 0);
+  const FilterPlan fp = filter_plan_k(N, (ix->tune.check_brackets & 4) != 0, k);   // (k > 32, option exact_filter_k: a longer sample, a larger buffer)
   const size_t tile_lds = (size_t)T * 2 * 64 * 16;
   if (ix->exf_qfrag.ensure(2 * tile_lds) || ix->exf_sample.ensure(sizeof(float) * (size_t)EXF_QT * fp.n_sample) ||
       ix->exf_cand.ensure(sizeof(uint2) * (size_t)EXF_QT * fp.cap))
@@ -277,8 +277,8 @@ static int exact_search_rows(freddy_gpu_index* ix, const QuerySrc& queries, int3
   int64_t n_rows = ix->N, n_blocks = ix->n_blocks;
   if (sub_rows)   // (an empty subset: the scan below finds nothing)
     if (int rc = vec_subset(ix, ws, s, *sub_rows, &xb, &pos, &n_rows, &n_blocks)) return rc;
-  // Filter + refine (exact2.h): the whole table, k <= 32, finite rows of a supported shape; identical lists.
-  const bool want_filter = !sub_rows && exf_knn_wanted(ix, n_rows) && k <= 32 && n_rows >= 1;
+  // Filter + refine (exact2.h): the whole table, k <= 32 (option exact_filter_k: up to 1024), finite rows of a supported shape; identical lists.
+  const bool want_filter = !sub_rows && exf_knn_wanted(ix, n_rows) && k <= ix->tune.exact_filter_k && n_rows >= 1;
   if (want_filter) {
     // one block of mapped host memory: [lists][verdict words][the queries, when they are few]: the kernels read a handful of
     // queries where the host put them (1.2 KB each over PCIe) and write the lists where the host reads them
@@ -431,7 +431,7 @@ static int exact_join_filter(freddy_gpu_index* ix, Workspace* ws, hipStream_t s,
                              int32_t* out_ids, float* out_sim, std::vector<int32_t>& cnt_out, int* cap_out, bool* qbad_out) {
   const int d = ix->d, T = (d + 15) / 16;
   const int64_t nT = rows.size(), strips = (nT + 31) / 32;
-  const FilterPlan fp = filter_plan(nT, (ix->tune.check_brackets & 4) != 0);
+  const FilterPlan fp = filter_plan(nT, (ix->tune.check_brackets & 4) != 0);   // (k <= 32 here, whatever option exact_filter_k says: exact_join_src)
   const int n_sample = fp.n_sample, cap = fp.cap;
   *cap_out = cap; *qbad_out = false;
   // the query tile: 128 queries (NT = 4) when more than one 64-tile is needed and four tiles' fragments fit the LDS
@@ -508,6 +508,8 @@ static int exact_join_src(freddy_gpu_index* ix, const QuerySrc& queries, int32_t
   RowSet rows;
   if (int rc = resolve_row_set(ix, resolve_on_device, target_ids, n_targets, &h_rows, &rows)) return rc;
   const int64_t nT = rows.size();
+  // (k <= 32 and not option exact_filter_k, though exf_chain is shared: the join holds a sample and a candidate buffer per query for
+  // thousands of queries a pass -- EXJ_PASS_BYTES was sized for filter_plan's 8192 -- and its redo is per query; neither was measured for wider lists)
   const bool want_filter = exf_wanted(ix, nT, EXJ_MIN_TARGETS) && k <= 32 && nT >= 1;
   if (!want_filter) return exact_search_rows(ix, queries, Q, k, &rows, out_ids, out_sim);
   HIP_TRY(hipSetDevice(ix->device));

@@ -31,6 +31,21 @@ static FilterPlan filter_plan(int64_t N, bool refine_all) {
   const int n_sample = (int)(std::min<int64_t>(full_strips, EXF_SAMPLE / 32) * 32);
   return {n_sample, n_sample > 0 ? std::max<int64_t>(1, full_strips / (n_sample / 32)) : 1, (int)(refine_all ? N : std::min<int64_t>(N, 8192)), refine_all};
 }
+// The plan of exact kNN for a list of k rows (option exact_filter_k; the exact join and the analogies keep filter_plan: their k <= 32).
+// k <= 32: filter_plan, field for field.  Above, the expected number of candidates is k N / n_sample (the rows above the sample's
+// k-th best), so both the sample and the buffer grow with k: EXF_SAMPLE rows per 32 rows of the list, eight times at most (262 144
+// rows: EXF_RANK_MAX_SAMPLE, 1 MiB per query for the rank selection), and four times the candidates a uniformly ordered table would
+// give (the 2 eps margin and an unevenly ordered table take the rest; more than that is the overflow redo, as before).
+static constexpr int EXF_K_SAMPLE_MAX = 8, EXF_K_CAP_FACTOR = 4;
+static FilterPlan filter_plan_k(int64_t N, bool refine_all, int k) {
+  if (k <= 32) return filter_plan(N, refine_all);
+  const int64_t full_strips = N / 32;
+  const int64_t want = (int64_t)EXF_SAMPLE * std::min(EXF_K_SAMPLE_MAX, (k + 31) / 32);
+  const int n_sample = (int)(std::min<int64_t>(full_strips, want / 32) * 32);
+  const int64_t per_sample_row = n_sample > 0 ? (N + n_sample - 1) / n_sample : N;
+  const int64_t cap = refine_all ? N : std::min<int64_t>(N, std::max<int64_t>(8192, (int64_t)EXF_K_CAP_FACTOR * k * per_sample_row));
+  return {n_sample, n_sample > 0 ? std::max<int64_t>(1, full_strips / (n_sample / 32)) : 1, (int)cap, refine_all};
+}
 // workgroups of a filter kernel over `rows` rows of the whole table: one per 256 rows, at most two per CU
 static unsigned filter_grid(const freddy_gpu_index* ix, int64_t rows) {
   return freddy::filter_grid(ix->n_cus, rows);
@@ -76,6 +91,7 @@ static int exf_verdict_arrived(const int32_t* flags, const char* call) {
 }
 
 struct ExfLabels { const char *prep, *sample, *threshold, *filter, *refine; };   // the chain's launches in a profile
+// (p.k > 32 -- exact kNN under option exact_filter_k alone -- names its threshold launch "exact_threshold_rank" whatever the set says)
 static constexpr ExfLabels EXF_KNN_LABELS = {"exact_prep", "exact_sample", "exact_threshold", "exact_filter", "exact_refine"};
 static constexpr ExfLabels EXF_KNN_WIDE_LABELS = {"exact_prep", "exact_sample_wide", "exact_threshold", "exact_filter_wide", "exact_refine"};   // d > 512: exf_wide_filter_kernel
 static constexpr ExfLabels EXF_JOIN_LABELS = {"exact_join_prep", "exact_join_sample", "exact_join_threshold", "exact_join_filter", "exact_join_refine"};
@@ -112,7 +128,9 @@ static int exf_chain(freddy_gpu_index* ix, hipStream_t s, const ExfPass& p, int6
   ExfThrArgs ta;
   ta.sample = ix->exf_sample.as<float>(); ta.n_sample = p.fp.n_sample; ta.nq = p.nq; ta.k = p.k; ta.qeps = p.qeps; ta.qunscale = p.qunscale; ta.thr = p.thr;
   ta.refine_all = p.fp.refine_all ? 1 : 0; ta.cand_cnt = p.cand_cnt;
-  timed_launch(ix, s, p.labels->threshold, [&] { hipLaunchKernelGGL(exf_threshold_kernel, dim3(p.grid_q), dim3(64 * EXF_TW), 0, s, ta); });
+  // k > 32: the k-th best of the lanes' bests is no threshold beyond a wave's 64 keys and a loose one before: the exact k-th largest of the sample (exact_rank.h)
+  if (p.k > 32) timed_launch(ix, s, "exact_threshold_rank", [&] { exf_rank_threshold_launch(ix, s, p.grid_q, ta); });
+  else timed_launch(ix, s, p.labels->threshold, [&] { hipLaunchKernelGGL(exf_threshold_kernel, dim3(p.grid_q), dim3(64 * EXF_TW), 0, s, ta); });
   HIP_TRY(hipGetLastError());
   timed_launch(ix, s, p.labels->filter, [&] { filter(std::false_type(), n_rows); });
   HIP_TRY(hipGetLastError());
@@ -121,11 +139,13 @@ static int exf_chain(freddy_gpu_index* ix, hipStream_t s, const ExfPass& p, int6
   ra.viol = ix->viol; ra.cap = p.fp.cap; ra.d = d; ra.L = p.k; ra.count_checked = p.fp.refine_all ? 1 : 0;
   ra.ids = ix->ids; ra.out_ids = p.out_ids; ra.out_sim = p.out_sim; ra.k = p.k; ra.arrived = qbad + 1; ra.total_wgs = p.total_wgs;
   ra.qbad = qbad; ra.flags_out = p.flags;
-  const size_t rlds = exf_refine_lds(d, V == 1 ? 1 : 2);
+  // lists of up to 64 rows: one register of keys per lane, wave 0 absorbs the others' lists; wider ones: exf_refine_tree_kernel<V> (exact_rank.h)
+  bool known = true;
   timed_launch(ix, s, p.labels->refine, [&] {
-    if (V == 1) hipLaunchKernelGGL((exf_refine_kernel<1>), dim3((unsigned)p.nq), dim3(64 * EXF_TW), rlds, s, ra);
-    else hipLaunchKernelGGL((exf_refine_kernel<2>), dim3((unsigned)p.nq), dim3(64 * EXF_TW), rlds, s, ra);
+    if (V == 1) hipLaunchKernelGGL((exf_refine_kernel<1>), dim3((unsigned)p.nq), dim3(64 * EXF_TW), exf_refine_lds(d, 1), s, ra);
+    else known = exf_refine_tree_launch(s, V, (unsigned)p.nq, ra);
   });
+  if (!known) return fail(FREDDY_E_LIMIT, "no refine kernel for lists of %d rows", p.k);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -20,6 +20,7 @@
 //   analogy.hip the exact analogies (analogy.h), the INNER JOIN of analogy triples
 //               exact_host.h what these two share on the host: the filter + refine chain and when a call takes it, scan chunking
 //   exact_wide.hip  option exact_wide: the filter pass of exact kNN for 512 < d <= 2048 (exact_wide.h), its state on the handle
+//   exact_rank.hip  option exact_filter_k: the rank-selection threshold and the tree-merge refine of exact kNN's lists of 33 .. 1024 rows (exact_rank.h)
 //   rerank.hip  post verification of pq / ivf lists (pv.h), the approximate analogies over pq / ivf / ivpq (approx_analogy.h), the re-rank stage they share
 //   cluster.hip exact_assign (assign.h), the whole k-means of cluster_exact / cluster_pq (cluster.h)
 //   similarity.hip  similarities by row id: pairs, matrices, joins (similarity.h)
@@ -101,6 +102,8 @@ struct Tuning {
                                // (FilterArgs::tau_run): fewer survivors for the merge; 0 = every (item, chunk) cuts at its own threshold
   int codes_u8 = 1;            // FREDDY_GPU_CODES_U8: K <= 256: the integer-slab scans read one byte per code (packed8, 16 instead of 28 B per row) -- 1: the scan with the whole entry's slab in LDS (fused8.h), 2: the six-phase scan (fused5.h); 0 = the int16 layout
   int exact_filter = -1;       // FREDDY_GPU_EXACT_FILTER: exact kNN as MFMA filter + exact refine (exact2.h): -1 auto (tables of >= 8192 rows, k <= 32), 0 never, 1 always
+  int exact_filter_k = 32;     // option exact_filter_k (vector handles): the largest k for which exact kNN takes filter + refine, 32 .. 1024; above 32 the chain launches exact_rank.h's threshold and refine kernels.  The exact join and the analogies keep k <= 32
+  int exact_rank_hist = 0;     // option exact_rank_hist: histogram copies of exf_rank_threshold_kernel: 0 = one, 1 = four (waves w, w + 4, ..: the measured alternative, profiles/exact_filter_k_timing.txt)
   int exact_join_tile = 0;     // option exact_join_tile: queries per workgroup of the exact join's filter (exact_join.h): 0 auto (128 when Q > 64 and d <= 320), 64
   int analogy_pass = 0;        // option analogy_pass: triples per pass of the approximate analogies (approx_analogy.h): 0 = pv_search's bound (lists of at most 8 M entries)
   int cluster_pass = 0;        // option cluster_pass: targets per assignment pass of freddy_gpu_cluster (cluster.h): 0 = 2^22; 64 at least
@@ -435,10 +438,11 @@ std::vector<LdsLimit> lds_limits_pq();
 std::vector<LdsLimit> lds_limits_join();
 std::vector<LdsLimit> lds_limits_exact();
 std::vector<LdsLimit> lds_limits_exact_wide();
+std::vector<LdsLimit> lds_limits_exact_rank();
 std::vector<LdsLimit> lds_limits_analogy();
 std::vector<LdsLimit> lds_limits_rerank();
 
-namespace freddy { struct PlanArgs; struct ScanArgs; struct MergeArgs; struct ExfArgs; }
+namespace freddy { struct PlanArgs; struct ScanArgs; struct MergeArgs; struct ExfArgs; struct ExfThrArgs; struct ExfRefineArgs; }
 
 // ---- ivf_scan.hip ----
 // The work table shared by both cell-grouped scans: per-cell item counts -> (<= 12 items of a cell, 4096-row
@@ -513,6 +517,11 @@ int exf_table_stats(freddy_gpu_index* ix, int64_t r0, int64_t n, const std::vect
 int exf_wide_set(freddy_gpu_index* ix, int64_t value);
 // exf_wide_filter_kernel over fa.n_rows rows for nq <= 64 queries (sample: the SAMPLE instantiation), enqueued on s
 void exf_wide_launch(const freddy_gpu_index* ix, hipStream_t s, const freddy::ExfArgs& fa, int nq, bool sample);
+// ---- exact_rank.hip ----
+// exf_rank_threshold_kernel for grid_q queries (exf_threshold_kernel's arguments), enqueued on s
+void exf_rank_threshold_launch(const freddy_gpu_index* ix, hipStream_t s, unsigned grid_q, const freddy::ExfThrArgs& ta);
+// exf_refine_tree_kernel<V> for n_queries queries, V = 2, 4, 8, 16 (exf_refine_kernel's arguments); false: no kernel of that width
+bool exf_refine_tree_launch(hipStream_t s, int V, unsigned n_queries, const freddy::ExfRefineArgs& ra);
 
 // ---- exact.hip (continued) ----
 // Where the table rows of "id = ANY(set)" are: the host vector rows_of_ids made (every function then does exactly what it did
