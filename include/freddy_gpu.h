@@ -574,6 +574,25 @@ typedef struct freddy_encode_desc {
 } freddy_encode_desc;
 int freddy_gpu_encode(const freddy_encode_desc* desc, int device, const float* vectors, int64_t N, int32_t* out_cell,
                       int16_t* out_codes);
+/* Index build, encoding step, for rows that are already pinned: the coarse cell and the PQ code of rows
+ * [row0, row0 + n_rows) of a vector handle, in table order.  Bit for bit what freddy_gpu_encode returns for
+ * the same float rows and the same desc (desc->d must equal the handle's d).  The nearest centroids are found as filter +
+ * refine (csrc/encode_filter.h): squared distances on the matrix cores inside a proven bracket, then the reference's chain for
+ * the few centroids that can be the nearest; the approximate value never reaches an output.  Shapes the bracket does not cover
+ * (more than 512 dimensions per search: d / m, or d with a coarse quantizer), rows with a non-finite element or norm, crowded
+ * items (more than 16 centroids inside the bracket) and positions with a non-finite centroid take freddy_gpu_encode's kernels
+ * inside the same call.  Refused before any launch: NULL pointers, d % m != 0, C and coarse not
+ * given together, out_cell == NULL with C > 0, desc->d != the handle's d, a row range outside [0, N] (FREDDY_E_ARG); K > 32767
+ * (FREDDY_E_LIMIT); a handle of another kind (FREDDY_E_KIND); a poisoned handle (FREDDY_E_HIP).  n_rows == 0 writes nothing.
+ * The call sees every append / remove / update made to the handle before it; none may run beside it.
+ * Option "encode_refine_all" (vector handles, 0 / 1, default 0): every centroid of every item is refined, so the bracket of every
+ * (row, centroid) pair is checked -- the self-check the tests run; the outputs are the same bits. */
+int freddy_gpu_encode_rows(freddy_gpu_index_t* vecs, const freddy_encode_desc* desc, int64_t row0, int64_t n_rows,
+                           int32_t* out_cell /*[n_rows] or NULL when desc->C == 0*/, int16_t* out_codes /*[n_rows][m]*/);
+/* The last encode_rows call on this handle: items = (row, position) searches incl. the coarse one; candidates = centroids
+ * refined with the exact chain; redone = items sent to the all-exact kernels; checked / violations = refined
+ * centroids whose exact distance was compared with / left its bracket. */
+int freddy_gpu_last_encode_stats(const freddy_gpu_index_t* vecs, int64_t out[5]);
 
 /* Quantizer training (index_creation/quantizer_creation.py:13-52: scipy k-means for the coarse quantizer, per
  * sub-vector position for the PQ codebooks): Lloyd's algorithm on the device.  Initial centroids =

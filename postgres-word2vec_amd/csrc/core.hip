@@ -99,6 +99,7 @@ void free_index(freddy_gpu_index* ix) {
   ix->hio_in.release(); ix->hio_out.release();
   ix->pv_io.release(); ix->pv_q.release();
   ix->tok_dev.release(); ix->tok_raw.release(); ix->tok_vec.release(); ix->tok_io.release();
+  ix->enc_img.release(); ix->enc_work.release(); ix->enc_redo.release(); ix->enc_all.release(); ix->enc_io.release();
   for (Lane& l : ix->lanes) {
     if (l.stream && l.stream != ix->stream) (void)hipStreamDestroy(l.stream);
     for (LaneSlot& c : l.slot) {
@@ -286,6 +287,10 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   else if (n == "exact_join_tile") t.exact_join_tile = (int)value;
   else if (n == "exact_resolve") t.exact_resolve = value != 0 ? 1 : 0;
   else if (n == "exact_wide") return exf_wide_set(ix, value);
+  else if (n == "encode_refine_all") {
+    if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "option encode_refine_all belongs to a vector handle");
+    t.encode_refine_all = value != 0 ? 1 : 0;
+  }
   else if (n == "exact_wide_shape") t.exact_wide_shape = value == 1 || value == 2 ? (int)value : 0;
   else if (n == "resolve_block") t.resolve_block = (int)std::max<int64_t>(0, std::min<int64_t>(value, (int64_t)1 << 20));
   else if (n == "analogy_pass") t.analogy_pass = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));

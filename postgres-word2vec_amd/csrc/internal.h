@@ -26,6 +26,7 @@
 //   similarity.hip  similarities by row id: pairs, matrices, joins (similarity.h)
 //   tokenize.hip    text vectors from token ids and the searches over them (tokenize.h)
 //   build.hip   encode, insert_quantize, k-means
+//   encode_rows.hip  encode_rows: the encoding step for rows of a vector handle as MFMA filter + exact refine (encode_filter.h)
 // Kernel headers are included by the unit that launches them (kernels shared by two units are static or templates).  A kernel with
 // an LDS limit is compiled into ONE unit, whose lds_limits_*() names it: the limit belongs to that unit's copy of the function.
 #pragma once
@@ -114,6 +115,7 @@ struct Tuning {
   int resolve_block = 0;       // option resolve_block: bitmap words per block of the device resolve (resolve.h): 0 = 256; tests make small tables span many blocks
   int tokenize_pass = 0;       // option tokenize_pass (set on the vector handle): texts per pass of the *_search_texts calls (tokenize.h): 0 = as many as a pinned block of 256 MiB holds
   int tokenize_unit = 0;       // option tokenize_unit: the sum of squares of freddy_gpu_tokenize's normalisation: 1 = a wave per text with lane 0 walking the chain (tok_unit_wave_kernel), 2 = a chain per lane over 64 texts (tok_unit_kernel), 0 = auto: 1 below 16384 texts, 2 from there on (tokenize.h)
+  int encode_refine_all = 0;   // option encode_refine_all (vector handles): freddy_gpu_encode_rows refines EVERY centroid of every item, so every (row, centroid) bracket is checked (encode_filter.h); 0 / 1
   int64_t similarity_pass_bytes = 0;   // option similarity_pass_bytes: the device result block of one pass of freddy_gpu_similarity_matrix / _join (similarity.h): 0 = 256 MiB, at most 4 GiB; 16 rows of A at least
   // -- self-checks (tests): bit 0 = the scan keeps every row and the merge refines every row (every probed row's bracket is checked),
   //    bit 1 = the cell selection refines every cell, bit 2 = exact kNN refines every row
@@ -329,6 +331,12 @@ struct freddy_gpu_index {
   // ([the pass's vectors][their texts]) -- buffers of their own, because the searches of a pass run on this handle's workspace
   DevBuf tok_dev, tok_raw, tok_vec;
   PinnedBuf tok_io;
+  // freddy_gpu_encode_rows on a vector handle (encode_filter.h): the centroid image of the call, the chunk's workspace (candidate lists, redo
+  // lists, cells, codes, redo staging), the pinned block the chunk's counters come back in, and the last call's counts
+  // (freddy_gpu_last_encode_stats): items, candidates, redone, checked, violations
+  DevBuf enc_img, enc_work, enc_redo, enc_all;
+  PinnedBuf enc_io;
+  int64_t enc_stats[5] = {0, 0, 0, 0, 0};
 };
 
 template <class F>

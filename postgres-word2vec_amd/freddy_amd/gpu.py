@@ -43,6 +43,7 @@ EXPORTS = [
     "freddy_gpu_exact_search_ids", "freddy_gpu_exact_join_ids", "freddy_gpu_debug_resolve_ids",
     "freddy_gpu_knn_join_ids", "freddy_gpu_ivpq_analogy",
     "freddy_gpu_tokenize", "freddy_gpu_ivfadc_search_texts", "freddy_gpu_pq_search_texts", "freddy_gpu_exact_search_texts",
+    "freddy_gpu_encode_rows", "freddy_gpu_last_encode_stats",
 ]
 TOK_MAX_LEN = 4096   # include/freddy_gpu.h FREDDY_TOK_MAX_LEN: ids per text
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
@@ -217,6 +218,10 @@ def load(path=None, optional=()):
         if name not in optional:
             getattr(lib, name).argtypes = types
     lib.freddy_gpu_kmeans.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name, types in (("freddy_gpu_encode_rows", [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+                        ("freddy_gpu_last_encode_stats", [C.c_void_p, C.c_void_p])):
+        if name not in optional:
+            getattr(lib, name).argtypes = types
     lib.freddy_gpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     lib.freddy_gpu_last_track.argtypes = [C.c_void_p, C.c_void_p]
     lib.freddy_gpu_profile_enable.argtypes = [C.c_void_p, C.c_int32]
@@ -585,6 +590,27 @@ class VectorIndex(_Index):
         _check(self.lib.freddy_gpu_exact_analogy(self.h, ANALOGY_METHODS[method], _p(t), Q, k, _p(sub), 0 if sub is None else sub.size,
                                                  _p(out_i), _p(out_s)))
         return out_i, out_s
+
+    def encode_rows(self, codebook, coarse=None, row0=0, n_rows=None):
+        """Index build, encoding step, for the pinned rows [row0, row0 + n_rows) in table order (freddy_gpu_encode_rows):
+        (cell[n] or None, codes[n, m]) for a codebook [m][K][s] and an optional coarse quantizer [C][d] -- bit for bit what
+        encode() returns for the same rows, found as filter + refine on the matrix cores."""
+        cb = _f32(codebook)
+        m, K, s_ = cb.shape
+        co = None if coarse is None else _f32(coarse)
+        n = self.N - row0 if n_rows is None else int(n_rows)
+        desc = EncodeDesc(m * s_, m, K, _p(cb), 0 if co is None else co.shape[0], _p(co))
+        codes = np.empty((max(n, 0), m), np.int16)
+        cell = None if co is None else np.empty(max(n, 0), np.int32)
+        _check(self.lib.freddy_gpu_encode_rows(self.h, C.byref(desc), int(row0), n, _p(cell), _p(codes)))
+        return cell, codes
+
+    def last_encode_stats(self):
+        """The last encode_rows() call (freddy_gpu_last_encode_stats): (row, position) items, centroids refined with the exact chain,
+        items sent to the all-exact kernels, brackets checked and brackets violated."""
+        v = (C.c_int64 * 5)()
+        _check(self.lib.freddy_gpu_last_encode_stats(self.h, v))
+        return dict(zip(("items", "candidates", "redone", "checked", "violations"), (int(x) for x in v)))
 
     def last_analogy_stats(self):
         """The last analogy() call (freddy_gpu_last_analogy_stats): filter passes, candidates they refined, passes redone all-exact."""

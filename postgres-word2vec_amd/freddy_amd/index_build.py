@@ -192,3 +192,24 @@ def build_ivf_index_native(x, C=1000, m=12, K=256, train_size=100000, iters=10, 
     list_off[1:] = np.cumsum(np.bincount(cid, minlength=C))
     return dict(coarse=coarse, codebook=cb, list_off=list_off, ids=(order + 1).astype(np.int32),
                 codes=np.ascontiguousarray(codes[order]), coarse_id=cid.astype(np.int32))
+
+
+def build_tables_from_pinned(vecs, pq_codebook, coarse=None, ivf_codebook=None):
+    """The pq and ivf tables of rows that are already pinned (a gpu.VectorIndex, e.g. google_vecs_norm), for trained quantizers:
+    VectorIndex.encode_rows finds the cells and the codes on the matrix cores from the rows in HBM -- no upload of the vectors.
+    -> dict(pq=dict(codebook, ids, codes)[, ivf=dict(coarse, codebook, list_off, ids, codes, coarse_id)]); ids = table row + 1,
+    as the other builders number them.  ivf needs both coarse [C][d] and ivf_codebook (the residuals' codebook)."""
+    if (coarse is None) != (ivf_codebook is None):
+        raise ValueError("coarse and ivf_codebook are given together")
+    pq_cb = np.ascontiguousarray(pq_codebook, dtype=np.float32)
+    _, codes = vecs.encode_rows(pq_cb)
+    out = dict(pq=dict(codebook=pq_cb, ids=np.arange(1, vecs.N + 1, dtype=np.int32), codes=codes))
+    if coarse is not None:
+        co, cb = np.ascontiguousarray(coarse, dtype=np.float32), np.ascontiguousarray(ivf_codebook, dtype=np.float32)
+        cid, codes = vecs.encode_rows(cb, coarse=co)
+        order = np.argsort(cid, kind="stable")            # ids stay ascending inside each list
+        list_off = np.zeros(co.shape[0] + 1, np.int32)
+        list_off[1:] = np.cumsum(np.bincount(cid, minlength=co.shape[0]))
+        out["ivf"] = dict(coarse=co, codebook=cb, list_off=list_off, ids=(order + 1).astype(np.int32),
+                          codes=np.ascontiguousarray(codes[order]), coarse_id=cid.astype(np.int32))
+    return out
