@@ -20,34 +20,90 @@ QIDS_TABLE_ORDER = 0   # search_ids: "WHERE id IN (...)" -- ascending ids, dupli
 QIDS_POSITIONAL = 1    # slot j answers ids[j]; an id without a row keeps its slot and gets fillers
 ANALOGY_METHODS = {"3cosadd": 0, "3cosmul": 1, "pair_direction": 2}   # include/freddy_gpu.h FREDDY_ANALOGY_*
 
-EXPORTS = [
-    "freddy_gpu_pin_pq", "freddy_gpu_pin_ivf", "freddy_gpu_pin_ivpq", "freddy_gpu_unpin",
-    "freddy_gpu_pq_search", "freddy_gpu_ivfadc_search", "freddy_gpu_knn_join",
-    "freddy_gpu_ivfadc_search_dev", "freddy_gpu_pq_search_dev", "freddy_gpu_last_error",
-    "freddy_gpu_profile_enable", "freddy_gpu_profile_read", "freddy_gpu_index_bytes",
-    "freddy_gpu_last_scanned_rows", "freddy_gpu_filter_bound_violations", "freddy_gpu_filter_bound_checked", "freddy_gpu_pin_vectors", "freddy_gpu_exact_search", "freddy_gpu_grouping_pq",
-    "freddy_gpu_encode", "freddy_gpu_set_option", "freddy_gpu_last_track", "freddy_gpu_last_probed_cells", "freddy_gpu_coarse_bound_checked",
-    "freddy_gpu_insert_quantize", "freddy_gpu_append_rows", "freddy_gpu_update_codebook", "freddy_gpu_kmeans",
-    "freddy_gpu_host_alloc", "freddy_gpu_host_free", "freddy_gpu_pin_ivf_multi", "freddy_gpu_replica_count",
-    "freddy_gpu_last_track_sized", "freddy_gpu_abi_version", "freddy_gpu_exact_analogy",
-    "freddy_gpu_last_analogy_stats", "freddy_gpu_exact_join", "freddy_gpu_last_exact_join_stats",
-    "freddy_gpu_ivfadc_search_pv", "freddy_gpu_pq_search_pv", "freddy_gpu_last_pv_stats",
-    "freddy_gpu_ivfadc_analogy", "freddy_gpu_pq_analogy", "freddy_gpu_last_approx_analogy_stats",
-    "freddy_gpu_exact_assign", "freddy_gpu_pq_assign", "freddy_gpu_remove_rows", "freddy_gpu_update_rows",
-    "freddy_gpu_set_statistics", "freddy_gpu_get_statistics", "freddy_gpu_create_statistics",
-    "freddy_gpu_debug_alloc_fail_nth", "freddy_gpu_debug_alloc_track", "freddy_gpu_debug_alloc_stats",
-    "freddy_gpu_scan_elastic_stats",
-    "freddy_gpu_ivfadc_search_ids", "freddy_gpu_pq_search_ids", "freddy_gpu_ivfadc_search_pv_ids", "freddy_gpu_pq_search_pv_ids",
-    "freddy_gpu_similarity_pairs", "freddy_gpu_similarity_matrix", "freddy_gpu_similarity_join",
-    "freddy_gpu_cluster",
-    "freddy_gpu_exact_search_ids", "freddy_gpu_exact_join_ids", "freddy_gpu_debug_resolve_ids",
-    "freddy_gpu_knn_join_ids", "freddy_gpu_ivpq_analogy",
-    "freddy_gpu_tokenize", "freddy_gpu_ivfadc_search_texts", "freddy_gpu_pq_search_texts", "freddy_gpu_exact_search_texts",
-    "freddy_gpu_encode_rows", "freddy_gpu_last_encode_stats",
-]
+_INT, _I32, _I64, _SIZE, _F32, _F64, _PTR, _STR = C.c_int, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_double, C.c_void_p, C.c_char_p
+# name -> (restype, [argtypes]) of every function include/freddy_gpu.h declares, in the header's order; load() binds from it and
+# tests/test_gpu_binding_cpu.py compares it with the header.  A pointer or array of any type is _PTR, a const char* argument _STR.
+PROTOTYPES = {
+    "freddy_gpu_pin_pq": (_INT, [_PTR, _INT, _PTR]),
+    "freddy_gpu_pin_ivf": (_INT, [_PTR, _INT, _PTR]),
+    "freddy_gpu_pin_ivpq": (_INT, [_PTR, _INT, _PTR]),
+    "freddy_gpu_unpin": (_INT, [_PTR]),
+    "freddy_gpu_pq_search": (_INT, [_PTR, _PTR, _I32, _I32, _F32, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_ivfadc_search": (_INT, [_PTR, _PTR, _I32, _I32, _I32, _F32, _I32, _PTR, _PTR]),
+    "freddy_gpu_host_alloc": (_INT, [_PTR, _SIZE]),
+    "freddy_gpu_host_free": (_INT, [_PTR]),
+    "freddy_gpu_pin_ivf_multi": (_INT, [_PTR, _PTR, _INT, _PTR]),
+    "freddy_gpu_replica_count": (_INT, [_PTR]),
+    "freddy_gpu_knn_join": (_INT, [_PTR, _PTR, _I32, _I32, _PTR, _I64, _I32, _I32, _I32, _I32, _F32, _I32, _PTR, _PTR, _PTR]),
+    "freddy_gpu_pin_vectors": (_INT, [_PTR, _INT, _PTR]),
+    "freddy_gpu_exact_search": (_INT, [_PTR, _PTR, _I32, _I32, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_exact_analogy": (_INT, [_PTR, _I32, _PTR, _I32, _I32, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_last_analogy_stats": (_INT, [_PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_exact_join": (_INT, [_PTR, _PTR, _I32, _I32, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_last_exact_join_stats": (_INT, [_PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_exact_assign": (_INT, [_PTR, _PTR, _I32, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_pq_assign": (_INT, [_PTR, _PTR, _I32, _F32, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_cluster": (_INT, [_PTR, _PTR, _F32, _PTR, _I64, _I32, _I32, _PTR, _I64, _PTR, _PTR, _PTR]),
+    "freddy_gpu_similarity_pairs": (_INT, [_PTR, _PTR, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_similarity_matrix": (_INT, [_PTR, _PTR, _PTR, _I32, _PTR, _I64, _PTR, _PTR, _PTR]),
+    "freddy_gpu_similarity_join": (_INT, [_PTR, _PTR, _PTR, _I32, _PTR, _I64, _F32, _I64, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_ivfadc_search_pv": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _I32, _F32, _I32, _PTR, _PTR]),
+    "freddy_gpu_pq_search_pv": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _F32, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_last_pv_stats": (_INT, [_PTR, _PTR, _PTR]),
+    "freddy_gpu_ivfadc_search_ids": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _I32, _F32, _I32, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_pq_search_ids": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _F32, _PTR, _I64, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_ivfadc_search_pv_ids": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _I32, _I32, _F32, _I32, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_pq_search_pv_ids": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _I32, _F32, _PTR, _I64, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_exact_search_ids": (_INT, [_PTR, _PTR, _I32, _I32, _I32, _PTR, _I64, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_exact_join_ids": (_INT, [_PTR, _PTR, _I32, _I32, _I32, _PTR, _I64, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_debug_resolve_ids": (_INT, [_PTR, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_ivfadc_analogy": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _I32, _F32, _I32, _PTR, _PTR]),
+    "freddy_gpu_pq_analogy": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _F32, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_ivpq_analogy": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _PTR, _I64, _I32, _I32, _I32, _I32, _F32, _I32, _PTR, _PTR]),
+    "freddy_gpu_last_approx_analogy_stats": (_INT, [_PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_tokenize": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _PTR, _PTR]),
+    "freddy_gpu_ivfadc_search_texts": (_INT, [_PTR, _PTR, _PTR, _PTR, _I32, _I32, _I32, _I32, _F32, _I32, _PTR, _PTR, _PTR]),
+    "freddy_gpu_pq_search_texts": (_INT, [_PTR, _PTR, _PTR, _PTR, _I32, _I32, _I32, _F32, _PTR, _I64, _PTR, _PTR, _PTR]),
+    "freddy_gpu_exact_search_texts": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _I32, _PTR, _I64, _PTR, _PTR, _PTR]),
+    "freddy_gpu_knn_join_ids": (_INT, [_PTR, _PTR, _PTR, _I32, _I32, _I32, _PTR, _I64, _I32, _I32, _I32, _I32, _F32, _I32, _PTR, _PTR, _PTR, _PTR,
+                                       _PTR]),
+    "freddy_gpu_grouping_pq": (_INT, [_PTR, _PTR, _I32, _PTR, _I64, _PTR, _PTR, _PTR]),
+    "freddy_gpu_encode": (_INT, [_PTR, _INT, _PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_encode_rows": (_INT, [_PTR, _PTR, _I64, _I64, _PTR, _PTR]),
+    "freddy_gpu_last_encode_stats": (_INT, [_PTR, _PTR]),
+    "freddy_gpu_kmeans": (_INT, [_INT, _PTR, _I64, _I32, _I32, _I32, _PTR, _PTR, _PTR]),
+    "freddy_gpu_insert_quantize": (_INT, [_PTR, _INT, _PTR, _I64, _PTR, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_append_rows": (_INT, [_PTR, _I64, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_remove_rows": (_INT, [_PTR, _I64, _PTR, _PTR]),
+    "freddy_gpu_update_rows": (_INT, [_PTR, _I64, _PTR, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_update_codebook": (_INT, [_PTR, _PTR]),
+    "freddy_gpu_set_statistics": (_INT, [_PTR, _PTR, _I32]),
+    "freddy_gpu_get_statistics": (_INT, [_PTR, _PTR, _I32]),
+    "freddy_gpu_create_statistics": (_INT, [_PTR, _PTR, _I64, _I32, _PTR, _PTR]),
+    "freddy_gpu_ivfadc_search_dev": (_INT, [_PTR, _PTR, _I32, _I32, _I32, _F32, _I32, _PTR, _PTR, _PTR, _PTR]),
+    "freddy_gpu_pq_search_dev": (_INT, [_PTR, _PTR, _I32, _I32, _F32, _PTR, _PTR, _PTR]),
+    "freddy_gpu_last_track": (_INT, [_PTR, _PTR]),
+    "freddy_gpu_last_track_sized": (_INT, [_PTR, _PTR, _SIZE]),
+    "freddy_gpu_debug_alloc_fail_nth": (_INT, [_I64, _I32]),
+    "freddy_gpu_debug_alloc_track": (_INT, [_I32]),
+    "freddy_gpu_debug_alloc_stats": (_INT, [_PTR, _SIZE]),
+    "freddy_gpu_abi_version": (_INT, []),
+    "freddy_gpu_set_option": (_INT, [_PTR, _STR, _I64]),
+    "freddy_gpu_last_error": (_STR, []),
+    "freddy_gpu_profile_enable": (_INT, [_PTR, _I32]),
+    "freddy_gpu_profile_read": (_INT, [_PTR, _I32, _PTR, _PTR, _PTR]),
+    "freddy_gpu_index_bytes": (_I64, [_PTR]),
+    "freddy_gpu_last_scanned_rows": (_I64, [_PTR]),
+    "freddy_gpu_last_probed_cells": (_INT, [_PTR, _PTR, _PTR]),
+    "freddy_gpu_filter_bound_violations": (_I64, [_PTR]),
+    "freddy_gpu_filter_bound_checked": (_I64, [_PTR]),
+    "freddy_gpu_coarse_bound_checked": (_I64, [_PTR]),
+    "freddy_gpu_scan_elastic_stats": (_INT, [_PTR, _PTR]),
+}
+EXPORTS = list(PROTOTYPES)
 TOK_MAX_LEN = 4096   # include/freddy_gpu.h FREDDY_TOK_MAX_LEN: ids per text
 ABI_VERSION = 4   # include/freddy_gpu.h FREDDY_GPU_ABI_VERSION this binding was written against
-STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together): ids per pass of freddy_gpu_create_statistics
+STAT_PASS = 1 << 22   # a copy of csrc/join.hip STAT_PASS (change both together; tests/test_gpu_binding_cpu.py compares them): ids per pass of freddy_gpu_create_statistics
 
 
 class FreddyGpuError(RuntimeError):
@@ -81,8 +137,10 @@ _lib = None
 
 
 def load(path=None, optional=()):
-    """dlopen the library (once).  Raises if it has not been built.  path / optional: a tool that times a build of an earlier
-    commit beside this one loads that library instead, which may lack the entry points named in `optional` (calling one fails)."""
+    """dlopen the library (once) and bind every function of PROTOTYPES that it exports.  Raises if it has not been built.  path: a
+    tool that times a build of an earlier commit beside this one loads that library instead.  A function the loaded library lacks
+    is left unbound: every other call works, calling the missing one fails with ctypes' own "undefined symbol".  optional: the
+    names such a tool expects to be missing; kept for those callers, it decides nothing."""
     global _lib, LIB_PATH
     if _lib is not None:
         if path and os.path.abspath(path) != os.path.abspath(LIB_PATH):
@@ -105,131 +163,10 @@ def load(path=None, optional=()):
     lib = C.CDLL(LIB_PATH)
     if lib.freddy_gpu_abi_version() != ABI_VERSION:
         raise FreddyGpuError(f"{LIB_PATH} has ABI version {lib.freddy_gpu_abi_version()}, this binding expects {ABI_VERSION}: rebuild")
-    lib.freddy_gpu_last_track_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.freddy_gpu_last_error.restype = C.c_char_p
-    lib.freddy_gpu_index_bytes.restype = C.c_int64
-    lib.freddy_gpu_index_bytes.argtypes = [C.c_void_p]
-    lib.freddy_gpu_last_scanned_rows.restype = C.c_int64
-    lib.freddy_gpu_last_scanned_rows.argtypes = [C.c_void_p]
-    lib.freddy_gpu_filter_bound_violations.restype = C.c_int64
-    lib.freddy_gpu_filter_bound_violations.argtypes = [C.c_void_p]
-    lib.freddy_gpu_filter_bound_checked.restype = C.c_int64
-    lib.freddy_gpu_filter_bound_checked.argtypes = [C.c_void_p]
-    lib.freddy_gpu_coarse_bound_checked.restype = C.c_int64
-    lib.freddy_gpu_coarse_bound_checked.argtypes = [C.c_void_p]
-    if "freddy_gpu_scan_elastic_stats" not in optional:
-        lib.freddy_gpu_scan_elastic_stats.argtypes = [C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_pin_pq.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.freddy_gpu_pin_ivf.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.freddy_gpu_pin_ivpq.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.freddy_gpu_pin_ivf_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.freddy_gpu_replica_count.argtypes = [C.c_void_p]
-    lib.freddy_gpu_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
-    lib.freddy_gpu_host_free.argtypes = [C.c_void_p]
-    lib.freddy_gpu_unpin.argtypes = [C.c_void_p]
-    lib.freddy_gpu_pin_vectors.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.freddy_gpu_exact_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                            C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_exact_analogy.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                             C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_last_analogy_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    for name, types in (("freddy_gpu_exact_join", [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_last_exact_join_stats", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_ivfadc_search_pv", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                                         C.c_int32, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_pq_search_pv", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
-                                                     C.c_int64, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_last_pv_stats", [C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_ivfadc_analogy", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                                       C.c_int32, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_pq_analogy", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
-                                                   C.c_int64, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_last_approx_analogy_stats", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_exact_assign", [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_pq_assign", [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])):
-        if name in optional and not hasattr(lib, name):
-            continue
-        getattr(lib, name).argtypes = types
-    # searches by row id.  (A library built from an earlier commit, which the A/B helpers load through FREDDY_GPU_SO, lacks them:
-    # every other call works, search_ids fails with the loader's "undefined symbol".)
-    for name, types in (("freddy_gpu_ivfadc_search_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_pq_search_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
-                                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_ivfadc_search_pv_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                                             C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_pq_search_pv_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-                        # similarities by row id (the same holds for them)
-                        ("freddy_gpu_similarity_pairs", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_similarity_matrix", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                                          C.c_void_p]),
-                        ("freddy_gpu_similarity_join", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_float, C.c_int64,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-                        # the whole k-means of cluster_exact / cluster_pq (the same again)
-                        ("freddy_gpu_cluster", [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                                C.c_void_p, C.c_void_p, C.c_void_p]),
-                        # exact kNN / the exact join by row id, and the device resolve's test hook (the same again)
-                        ("freddy_gpu_exact_search_ids", [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
-                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_exact_join_ids", [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
-                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_debug_resolve_ids", [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-                        # the kNN-join by row id and the batched analogy over it (the same again)
-                        ("freddy_gpu_knn_join_ids", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_ivpq_analogy", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
-                        # text vectors from token ids and the searches over them (the same again)
-                        ("freddy_gpu_tokenize", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_ivfadc_search_texts", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                                            C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_pq_search_texts", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_exact_search_texts", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p])):
-        if hasattr(lib, name):
-            getattr(lib, name).argtypes = types
-    lib.freddy_gpu_pq_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
-                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_ivfadc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                             C.c_float, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_knn_join.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_ivfadc_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                                 C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p]
-    lib.freddy_gpu_pq_search_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
-                                             C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_last_probed_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_insert_quantize.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_append_rows.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_update_codebook.argtypes = [C.c_void_p, C.c_void_p]
-    if "freddy_gpu_remove_rows" not in optional:
-        lib.freddy_gpu_remove_rows.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    if "freddy_gpu_update_rows" not in optional:
-        lib.freddy_gpu_update_rows.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    for name, types in (("freddy_gpu_set_statistics", [C.c_void_p, C.c_void_p, C.c_int32]),
-                        ("freddy_gpu_get_statistics", [C.c_void_p, C.c_void_p, C.c_int32]),
-                        ("freddy_gpu_create_statistics", [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p])):
-        if name not in optional:
-            getattr(lib, name).argtypes = types
-    lib.freddy_gpu_kmeans.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    for name, types in (("freddy_gpu_encode_rows", [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
-                        ("freddy_gpu_last_encode_stats", [C.c_void_p, C.c_void_p])):
-        if name not in optional:
-            getattr(lib, name).argtypes = types
-    lib.freddy_gpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-    lib.freddy_gpu_last_track.argtypes = [C.c_void_p, C.c_void_p]
-    lib.freddy_gpu_profile_enable.argtypes = [C.c_void_p, C.c_int32]
-    lib.freddy_gpu_profile_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    for name, types in (("freddy_gpu_debug_alloc_fail_nth", [C.c_int64, C.c_int32]), ("freddy_gpu_debug_alloc_track", [C.c_int32]),
-                        ("freddy_gpu_debug_alloc_stats", [C.c_void_p, C.c_size_t])):
-        if name not in optional:
-            getattr(lib, name).argtypes = types
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name, None)   # (None: this library lacks the symbol)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = lib
     return lib
 
@@ -284,6 +221,40 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _subset(ids):
+    """An optional id set as (array, pointer, count); None, the whole table, is (None, NULL, 0).  The array keeps the pointer alive."""
+    if ids is None:
+        return None, None, 0
+    a = _i32(ids)
+    return a, _p(a), a.size
+
+
+def _lists(Q, k, value_dtype=np.float32):
+    """The output arrays of Q result lists: ids[Q, k] int32 and values[Q, k]."""
+    return np.empty((Q, k), np.int32), np.empty((Q, k), value_dtype)
+
+
+def _row_ids(ids):
+    """Row ids as a flat int32 array; a value outside 32 bits is refused instead of wrapped."""
+    ids = np.asarray(ids)
+    if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
+        raise FreddyGpuError("row ids are 32-bit integers")
+    return _i32(ids).reshape(-1)
+
+
+def _payload(coarse_id, codes, vectors):
+    """The row payload of append_rows / update_rows as (int32, int16, float32) arrays, None for a part that was not given."""
+    return (None if coarse_id is None else _i32(coarse_id), None if codes is None else _i16(codes),
+            None if vectors is None else _f32(vectors))
+
+
+def _stats(fn, handle, names):
+    """A last_*_stats call, which writes one int64 per name through a pointer -> {name: value}."""
+    v = [C.c_int64(0) for _ in names]
+    _check(fn(handle, *(C.byref(x) for x in v)))
+    return {n: x.value for n, x in zip(names, v)}
+
+
 class _Index:
     kind = "?"
 
@@ -309,19 +280,14 @@ class _Index:
     def append_rows(self, ids, coarse_id=None, codes=None, vectors=None):
         """INSERT of new rows into the pinned tables (freddy_gpu_append_rows): ids ascending beyond the pinned ones."""
         ids = _i32(ids)
-        cid = None if coarse_id is None else _i32(coarse_id)
-        cd = None if codes is None else _i16(codes)
-        v = None if vectors is None else _f32(vectors)
+        cid, cd, v = _payload(coarse_id, codes, vectors)
         _check(self.lib.freddy_gpu_append_rows(self.h, ids.size, _p(ids), _p(cid), _p(cd), _p(v)))
         self.N += ids.size   # (grouping() sizes its output arrays by it)
 
     def remove_rows(self, ids):
         """DELETE of rows from the pinned tables (freddy_gpu_remove_rows): ids in any order, unknown ids are skipped, an id listed
         twice counts once.  -> the number of rows that left."""
-        ids = np.asarray(ids)
-        if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
-            raise FreddyGpuError("row ids are 32-bit integers")
-        ids = _i32(ids).reshape(-1)
+        ids = _row_ids(ids)
         gone = C.c_int64(0)
         _check(self.lib.freddy_gpu_remove_rows(self.h, ids.size, _p(ids), C.byref(gone)))
         self.N -= gone.value   # (grouping() sizes its output arrays by it)
@@ -331,13 +297,8 @@ class _Index:
         """UPDATE of rows of the pinned tables (freddy_gpu_update_rows): every pinned row whose id is ids[i] gets the i-th payload
         (the arrays append_rows takes for the handle's kind) and keeps its id.  ids in any order, unknown ids are skipped, an id
         listed twice is refused.  -> the number of rows that changed."""
-        ids = np.asarray(ids)
-        if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
-            raise FreddyGpuError("row ids are 32-bit integers")
-        ids = _i32(ids).reshape(-1)
-        cid = None if coarse_id is None else _i32(coarse_id)
-        cd = None if codes is None else _i16(codes)
-        v = None if vectors is None else _f32(vectors)
+        ids = _row_ids(ids)
+        cid, cd, v = _payload(coarse_id, codes, vectors)
         # the library reads ids.size rows of each array it is given: m codes, d floats (a borrowed handle knows neither: the caller's part)
         for name, a, per_row in (("coarse_id", cid, 1), ("codes", cd, getattr(self, "m", None)), ("vectors", v, getattr(self, "d", None))):
             if a is not None and per_row is not None and a.size != ids.size * per_row:
@@ -381,16 +342,12 @@ class _Index:
     def last_pv_stats(self):
         """The last search_pv() call on this pq / ivf handle (freddy_gpu_last_pv_stats): list entries with id >= 0 summed over the
         queries, and how many of them had a vector row."""
-        v = [C.c_int64(0) for _ in range(2)]
-        _check(self.lib.freddy_gpu_last_pv_stats(self.h, *(C.byref(x) for x in v)))
-        return {"candidates": v[0].value, "scored": v[1].value}
+        return _stats(self.lib.freddy_gpu_last_pv_stats, self.h, ("candidates", "scored"))
 
     def last_approx_analogy_stats(self):
         """The last analogy() call on this pq / ivf / ivpq handle (freddy_gpu_last_approx_analogy_stats): triples that reached stage one,
         their list entries with id >= 0, and how many of those had a vector row and were not an input of their triple."""
-        v = [C.c_int64(0) for _ in range(3)]
-        _check(self.lib.freddy_gpu_last_approx_analogy_stats(self.h, *(C.byref(x) for x in v)))
-        return {"searched": v[0].value, "candidates": v[1].value, "scored": v[2].value}
+        return _stats(self.lib.freddy_gpu_last_approx_analogy_stats, self.h, ("searched", "candidates", "scored"))
 
 
 def _search_ids(ids, k, call):
@@ -429,8 +386,7 @@ def _search_texts(texts, k, call):
     ids, off = _texts(texts)
     n = off.size - 1
     cnt = np.empty(max(n, 1), np.int32)
-    out_i = np.empty((max(n, 1), k), np.int32)
-    out_v = np.empty((max(n, 1), k), np.float32)
+    out_i, out_v = _lists(max(n, 1), k)
     _check(call(ids, off, n, cnt, out_i, out_v))
     return cnt[:n], out_i[:n], out_v[:n]
 
@@ -452,11 +408,9 @@ class PQIndex(_Index):
         """(ids[Q,k], dist[Q,k]); subset_ids=None -> pq_search, else pq_search_in[_batch]."""
         qs = _f32(queries).reshape(-1, self.d)
         Q = qs.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_d = np.empty((Q, k), np.float32)
-        sub = None if subset_ids is None else _i32(subset_ids)
-        _check(self.lib.freddy_gpu_pq_search(self.h, _p(qs), Q, k, C.c_float(sentinel), _p(sub),
-                                             0 if sub is None else sub.size, _p(out_i), _p(out_d)))
+        out_i, out_d = _lists(Q, k)
+        _keep, sub, n_sub = _subset(subset_ids)
+        _check(self.lib.freddy_gpu_pq_search(self.h, _p(qs), Q, k, C.c_float(sentinel), sub, n_sub, _p(out_i), _p(out_d)))
         return out_i, out_d
 
     def search_pv(self, vecs, queries, k, pvf, sentinel=100.0, subset_ids=None):
@@ -464,32 +418,30 @@ class PQIndex(_Index):
         (ids[Q,k], similarity[Q,k]), bit for bit vecs.search(q, k, subset_ids=<the candidates of q>) per query."""
         qs = _f32(queries).reshape(-1, self.d)
         Q = qs.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_s = np.empty((Q, k), np.float32)
-        sub = None if subset_ids is None else _i32(subset_ids)
-        _check(self.lib.freddy_gpu_pq_search_pv(self.h, vecs.h, _p(qs), Q, k, pvf, C.c_float(sentinel), _p(sub),
-                                                0 if sub is None else sub.size, _p(out_i), _p(out_s)))
+        out_i, out_s = _lists(Q, k)
+        _keep, sub, n_sub = _subset(subset_ids)
+        _check(self.lib.freddy_gpu_pq_search_pv(self.h, vecs.h, _p(qs), Q, k, pvf, C.c_float(sentinel), sub, n_sub, _p(out_i), _p(out_s)))
         return out_i, out_s
 
     def search_ids(self, vecs, ids, k, sentinel=100.0, subset_ids=None, rule=QIDS_TABLE_ORDER):
         """pq_search for the rows of the VectorIndex `vecs` with these ids, gathered on the device (freddy_gpu_pq_search_ids):
         (query_ids[Q], ids[Q,k], dist[Q,k]) with Q = the queries `rule` selects; per query bit for bit search(<its row of vecs>, k, ...)."""
-        sub = None if subset_ids is None else _i32(subset_ids)
+        _keep, sub, n_sub = _subset(subset_ids)
         return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_pq_search_ids(
-            self.h, vecs.h, _p(q), n, rule, k, C.c_float(sentinel), _p(sub), 0 if sub is None else sub.size, _p(oq), C.byref(nq), _p(oi), _p(od)))
+            self.h, vecs.h, _p(q), n, rule, k, C.c_float(sentinel), sub, n_sub, _p(oq), C.byref(nq), _p(oi), _p(od)))
 
     def search_texts(self, vecs, texts, k, sentinel=100.0, subset_ids=None, rule=QIDS_TABLE_ORDER):
         """pq_search for the text vectors vecs.tokenize(texts) computes, which stay on the device (freddy_gpu_pq_search_texts):
         (counts[n], ids[n,k], dist[n,k]); per text with a row list bit for bit search(<its vector>, k, ...), fillers for the others."""
-        sub = None if subset_ids is None else _i32(subset_ids)
+        _keep, sub, n_sub = _subset(subset_ids)
         return _search_texts(texts, k, lambda t, o, n, oc, oi, od: self.lib.freddy_gpu_pq_search_texts(
-            self.h, vecs.h, _p(t), _p(o), n, rule, k, C.c_float(sentinel), _p(sub), 0 if sub is None else sub.size, _p(oc), _p(oi), _p(od)))
+            self.h, vecs.h, _p(t), _p(o), n, rule, k, C.c_float(sentinel), sub, n_sub, _p(oc), _p(oi), _p(od)))
 
     def search_pv_ids(self, vecs, ids, k, pvf, sentinel=100.0, subset_ids=None, rule=QIDS_TABLE_ORDER):
         """search_pv for the rows of `vecs` with these ids (freddy_gpu_pq_search_pv_ids): (query_ids[Q], ids[Q,k], similarity[Q,k])."""
-        sub = None if subset_ids is None else _i32(subset_ids)
+        _keep, sub, n_sub = _subset(subset_ids)
         return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_pq_search_pv_ids(
-            self.h, vecs.h, _p(q), n, rule, k, pvf, C.c_float(sentinel), _p(sub), 0 if sub is None else sub.size, _p(oq), C.byref(nq), _p(oi), _p(od)))
+            self.h, vecs.h, _p(q), n, rule, k, pvf, C.c_float(sentinel), sub, n_sub, _p(oq), C.byref(nq), _p(oi), _p(od)))
 
     def analogy(self, vecs, triples, k=1, n_cand=23, sentinel=100.0, subset_ids=None):
         """Approximate 3CosAdd analogies (freddy_gpu_pq_analogy): triples [Q][3] of row ids (w1, w2, w3) -> (ids[Q,k], similarity[Q,k]);
@@ -497,11 +449,9 @@ class PQIndex(_Index):
         without the inputs>); (-1, -inf) where there is no row or an input id has no vector.  subset_ids: analogy_3cosadd_in_pq."""
         t = _i32(triples).reshape(-1, 3)
         Q = t.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_s = np.empty((Q, k), np.float32)
-        sub = None if subset_ids is None else _i32(subset_ids)
-        _check(self.lib.freddy_gpu_pq_analogy(self.h, vecs.h, _p(t), Q, k, n_cand, C.c_float(sentinel), _p(sub),
-                                              0 if sub is None else sub.size, _p(out_i), _p(out_s)))
+        out_i, out_s = _lists(Q, k)
+        _keep, sub, n_sub = _subset(subset_ids)
+        _check(self.lib.freddy_gpu_pq_analogy(self.h, vecs.h, _p(t), Q, k, n_cand, C.c_float(sentinel), sub, n_sub, _p(out_i), _p(out_s)))
         return out_i, out_s
 
     def bind_search(self, queries, k, sentinel=100.0):
@@ -509,8 +459,7 @@ class PQIndex(_Index):
         caller's costs): returns (call, out_ids, out_dist); call() fills the two arrays."""
         qs = _f32(queries).reshape(-1, self.d)
         Q = qs.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_d = np.empty((Q, k), np.float32)
+        out_i, out_d = _lists(Q, k)
         fn = self.lib.freddy_gpu_pq_search
         args = (self.h, _p(qs), C.c_int32(Q), C.c_int32(k), C.c_float(sentinel), None, C.c_int64(0), _p(out_i), _p(out_d))
 
@@ -523,12 +472,11 @@ class PQIndex(_Index):
     def grouping(self, group_vectors, subset_ids=None):
         """grouping_pq: (ids, group index) of every (requested) row; groups tried in the given order."""
         gv = _f32(group_vectors).reshape(-1, self.d)
-        sub = None if subset_ids is None else _i32(subset_ids)
-        cap = self.N if sub is None else max(sub.size, 1)
+        _keep, sub, n_sub = _subset(subset_ids)
+        cap = self.N if subset_ids is None else max(n_sub, 1)
         oi = np.empty(cap, np.int32); og = np.empty(cap, np.int32)
         n = C.c_int64(0)
-        _check(self.lib.freddy_gpu_grouping_pq(self.h, _p(gv), gv.shape[0], _p(sub), 0 if sub is None else sub.size,
-                                               _p(oi), _p(og), C.byref(n)))
+        _check(self.lib.freddy_gpu_grouping_pq(self.h, _p(gv), gv.shape[0], sub, n_sub, _p(oi), _p(og), C.byref(n)))
         return oi[:n.value], og[:n.value]
 
     def assign(self, queries, target_ids, sentinel=1000.0):
@@ -568,11 +516,9 @@ class VectorIndex(_Index):
         """(ids[Q,k], similarity[Q,k]) ORDER BY cosine_similarity_bytea DESC, id ASC."""
         qs = _f32(queries).reshape(-1, self.d)
         Q = qs.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_s = np.empty((Q, k), np.float32)
-        sub = None if subset_ids is None else _i32(subset_ids)
-        _check(self.lib.freddy_gpu_exact_search(self.h, _p(qs), Q, k, _p(sub), 0 if sub is None else sub.size,
-                                                _p(out_i), _p(out_s)))
+        out_i, out_s = _lists(Q, k)
+        _keep, sub, n_sub = _subset(subset_ids)
+        _check(self.lib.freddy_gpu_exact_search(self.h, _p(qs), Q, k, sub, n_sub, _p(out_i), _p(out_s)))
         return out_i, out_s
 
     def analogy(self, triples, k=1, method="3cosmul", subset_ids=None):
@@ -584,11 +530,9 @@ class VectorIndex(_Index):
             raise ValueError(f"method must be one of {sorted(ANALOGY_METHODS)}")
         t = _i32(triples).reshape(-1, 3)
         Q = t.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_s = np.empty((Q, k), np.float64)
-        sub = None if subset_ids is None else _i32(subset_ids)
-        _check(self.lib.freddy_gpu_exact_analogy(self.h, ANALOGY_METHODS[method], _p(t), Q, k, _p(sub), 0 if sub is None else sub.size,
-                                                 _p(out_i), _p(out_s)))
+        out_i, out_s = _lists(Q, k, np.float64)
+        _keep, sub, n_sub = _subset(subset_ids)
+        _check(self.lib.freddy_gpu_exact_analogy(self.h, ANALOGY_METHODS[method], _p(t), Q, k, sub, n_sub, _p(out_i), _p(out_s)))
         return out_i, out_s
 
     def encode_rows(self, codebook, coarse=None, row0=0, n_rows=None):
@@ -614,17 +558,14 @@ class VectorIndex(_Index):
 
     def last_analogy_stats(self):
         """The last analogy() call (freddy_gpu_last_analogy_stats): filter passes, candidates they refined, passes redone all-exact."""
-        v = [C.c_int64(0) for _ in range(3)]
-        _check(self.lib.freddy_gpu_last_analogy_stats(self.h, *(C.byref(x) for x in v)))
-        return {"filter_passes": v[0].value, "candidates": v[1].value, "redone_passes": v[2].value}
+        return _stats(self.lib.freddy_gpu_last_analogy_stats, self.h, ("filter_passes", "candidates", "redone_passes"))
 
     def join(self, queries, k, target_ids):
         """The exact kNN-join (freddy_gpu_exact_join): (ids[Q,k], similarity[Q,k]) of every query over the rows whose id is in
         target_ids -- bit for bit search(queries, k, subset_ids=target_ids); an empty target_ids is the empty set."""
         qs = _f32(queries).reshape(-1, self.d)
         Q = qs.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_s = np.empty((Q, k), np.float32)
+        out_i, out_s = _lists(Q, k)
         t = _i32(target_ids).reshape(-1)
         _check(self.lib.freddy_gpu_exact_join(self.h, _p(qs), Q, k, _p(t) if t.size else None, t.size, _p(out_i), _p(out_s)))
         return out_i, out_s
@@ -632,9 +573,9 @@ class VectorIndex(_Index):
     def exact_search_ids(self, ids, k, subset_ids=None, rule=QIDS_TABLE_ORDER):
         """search() for the rows of this table with these ids (freddy_gpu_exact_search_ids): (query_ids[Q], ids[Q,k], similarity[Q,k])
         with Q = the queries `rule` selects; per query bit for bit search(<its row>, k, subset_ids).  The subset is resolved on the device."""
-        sub = None if subset_ids is None else _i32(subset_ids).reshape(-1)
+        _keep, sub, n_sub = _subset(subset_ids)
         return _search_ids(ids, k, lambda q, n, oq, nq, oi, od: self.lib.freddy_gpu_exact_search_ids(
-            self.h, _p(q), n, rule, k, _p(sub), 0 if sub is None else sub.size, _p(oq), C.byref(nq), _p(oi), _p(od)))
+            self.h, _p(q), n, rule, k, sub, n_sub, _p(oq), C.byref(nq), _p(oi), _p(od)))
 
     def tokenize(self, texts, normalize=True, rule=QIDS_TABLE_ORDER):
         """Text vectors from token ids (freddy_gpu_tokenize; tokenize() / tokenize_raw() of the SQL surface): texts is a sequence of
@@ -651,9 +592,9 @@ class VectorIndex(_Index):
     def search_texts(self, texts, k, normalize=True, subset_ids=None, rule=QIDS_TABLE_ORDER):
         """search() for the text vectors tokenize(texts, normalize, rule) computes, which stay on the device
         (freddy_gpu_exact_search_texts): (counts[n], ids[n,k], similarity[n,k]); (-1, -inf) for a text without a row."""
-        sub = None if subset_ids is None else _i32(subset_ids).reshape(-1)
+        _keep, sub, n_sub = _subset(subset_ids)
         return _search_texts(texts, k, lambda t, o, n, oc, oi, od: self.lib.freddy_gpu_exact_search_texts(
-            self.h, _p(t), _p(o), n, rule, 1 if normalize else 0, k, _p(sub), 0 if sub is None else sub.size, _p(oc), _p(oi), _p(od)))
+            self.h, _p(t), _p(o), n, rule, 1 if normalize else 0, k, sub, n_sub, _p(oc), _p(oi), _p(od)))
 
     def exact_join_ids(self, ids, k, target_ids, rule=QIDS_TABLE_ORDER):
         """join() for the rows of this table with these ids (freddy_gpu_exact_join_ids): (query_ids[Q], ids[Q,k], similarity[Q,k]); per
@@ -705,9 +646,7 @@ class VectorIndex(_Index):
         """The A side of similarity_matrix / similarity_join: an integer array is row ids, a 2-d float array is vectors -> (ids, vectors, na)"""
         a = np.asarray(a)
         if np.issubdtype(a.dtype, np.integer):
-            if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-                raise FreddyGpuError("row ids are 32-bit integers")
-            ids = _i32(a).reshape(-1)
+            ids = _row_ids(a)
             return ids, None, ids.size
         if a.ndim != 2 or a.shape[1] != self.d or not np.issubdtype(a.dtype, np.floating):
             raise FreddyGpuError(f"the A side is an integer array of row ids or a float array [na][{self.d}]")
@@ -750,9 +689,7 @@ class VectorIndex(_Index):
 
     def last_join_stats(self):
         """The last join() call (freddy_gpu_last_exact_join_stats): queries the filter ran for, candidates refined, queries redone all-exact."""
-        v = [C.c_int64(0) for _ in range(3)]
-        _check(self.lib.freddy_gpu_last_exact_join_stats(self.h, *(C.byref(x) for x in v)))
-        return {"filter_queries": v[0].value, "candidates": v[1].value, "redone_queries": v[2].value}
+        return _stats(self.lib.freddy_gpu_last_exact_join_stats, self.h, ("filter_queries", "candidates", "redone_queries"))
 
     def bound_checked(self):
         """Rows the self-check has compared with their bracket (option check_brackets bits 2 / 3 refine every row)."""
@@ -785,8 +722,7 @@ class IVFIndex(_Index):
     def search(self, queries, k, W, sentinel=1000.0, found_rule=FOUND_ROWS):
         qs = _f32(queries).reshape(-1, self.d)
         Q = qs.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_d = np.empty((Q, k), np.float32)
+        out_i, out_d = _lists(Q, k)
         _check(self.lib.freddy_gpu_ivfadc_search(self.h, _p(qs), Q, k, W, C.c_float(sentinel), found_rule,
                                                  _p(out_i), _p(out_d)))
         return out_i, out_d
@@ -796,8 +732,7 @@ class IVFIndex(_Index):
         (ids[Q,k], similarity[Q,k]), bit for bit vecs.search(q, k, subset_ids=<the candidates of q>) per query."""
         qs = _f32(queries).reshape(-1, self.d)
         Q = qs.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_s = np.empty((Q, k), np.float32)
+        out_i, out_s = _lists(Q, k)
         _check(self.lib.freddy_gpu_ivfadc_search_pv(self.h, vecs.h, _p(qs), Q, k, pvf, W, C.c_float(sentinel), found_rule,
                                                     _p(out_i), _p(out_s)))
         return out_i, out_s
@@ -825,8 +760,7 @@ class IVFIndex(_Index):
         the normalised sum, without the inputs>); (-1, -inf) where there is no row or an input id has no vector."""
         t = _i32(triples).reshape(-1, 3)
         Q = t.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_s = np.empty((Q, k), np.float32)
+        out_i, out_s = _lists(Q, k)
         _check(self.lib.freddy_gpu_ivfadc_analogy(self.h, vecs.h, _p(t), Q, k, n_cand, W, C.c_float(sentinel), found_rule,
                                                   _p(out_i), _p(out_s)))
         return out_i, out_s
@@ -892,8 +826,7 @@ class IVPQIndex(_Index):
         qs = _f32(queries).reshape(-1, self.d)
         tid = _i32(target_ids)
         Q = qs.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_d = np.empty((Q, k), np.float32)
+        out_i, out_d = _lists(Q, k)
         iters = C.c_int32(0)
         _check(self.lib.freddy_gpu_knn_join(self.h, _p(qs), Q, k, _p(tid), tid.size, alpha, pvf, method,
                                             1 if use_target_lists else 0, C.c_float(confidence),
@@ -921,8 +854,7 @@ class IVPQIndex(_Index):
         input id has no vector."""
         t = _i32(triples).reshape(-1, 3)
         Q = t.shape[0]
-        out_i = np.empty((Q, k), np.int32)
-        out_s = np.empty((Q, k), np.float32)
+        out_i, out_s = _lists(Q, k)
         tid = _i32(target_ids)
         _check(self.lib.freddy_gpu_ivpq_analogy(self.h, None if vecs is None else vecs.h, _p(t), Q, k, n_cand, _p(tid), tid.size, alpha, pvf, method,
                                                 1 if use_target_lists else 0, C.c_float(confidence), double_threshold, _p(out_i), _p(out_s)))
@@ -945,10 +877,7 @@ class IVPQIndex(_Index):
         their multiplicity (unknown ids are skipped); None = every pinned row once.  install=True makes the row the handle's row.
         -> (stats [cells + 1], matched = the entries that have a row)."""
         if ids is not None:
-            ids = np.asarray(ids)
-            if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
-                raise FreddyGpuError("row ids are 32-bit integers")
-            ids = _i32(ids).reshape(-1)
+            ids = _row_ids(ids)
         n = 0 if ids is None else ids.size
         # (an empty LIST is not "every row": the library gets a pointer that is not NULL with n = 0 and refuses it)
         ptr = None if ids is None else _p(ids if n else np.zeros(1, np.int32))
@@ -994,7 +923,7 @@ def encode(codebook, vectors, coarse=None, device=0):
     desc = EncodeDesc(d, m, K, _p(cb), 0 if co is None else co.shape[0], _p(co))
     codes = np.empty((v.shape[0], m), np.int16)
     cell = None if co is None else np.empty(v.shape[0], np.int32)
-    _check(lib.freddy_gpu_encode(C.byref(desc), device, _p(v), C.c_int64(v.shape[0]), _p(cell), _p(codes)))
+    _check(lib.freddy_gpu_encode(C.byref(desc), device, _p(v), v.shape[0], _p(cell), _p(codes)))
     return cell, codes
 
 
