@@ -289,6 +289,114 @@ def test_exact_calls(gpu, oracle, tabs, form):
         _sweep(gpu, "exact_assign", make, lambda h: h[0].assign(qs, sub), check, 4)
 
 
+# floors of the filter chain behind options exact_filter_k and exact_wide (exact.hip): the mapped block hio_out and w_q
+# (exact_search_rows), exf_qfrag, exf_sample -- EXF_QT * n_sample floats, n_sample from filter_plan_k -- and exf_cand
+# (exact_filter_search), viol (ensure_viol) = 6; exf_small exists since the statistics were taken (pin time; exf_wide_set for a wide
+# table).  The buffers are the same six for k = 100 and for d = 516: what grows is their size.
+@pytest.mark.parametrize("form", ["k100", "wide"])
+def test_exact_search_on_the_newer_routes(gpu, oracle, tabs, form):
+    if form == "k100":
+        ids, xv = tabs["vec64"]
+        k, options, kernels = 100, (("exact_filter_k", 1024),), {"exact_filter", "exact_threshold_rank", "exact_refine"}
+    else:
+        xv, ids = _vec_table(516, 8300)
+        k, options, kernels = 5, (("exact_wide", 1),), {"exact_filter_wide", "exact_threshold", "exact_refine"}
+    rng = np.random.default_rng(14)
+    qs = np.ascontiguousarray(xv[rng.choice(8000, 12, replace=False)]); qs[1] = -qs[1]
+    full = Lazy(lambda: [oracle.exact_knn(xv, ids, q, k) for q in qs])
+
+    def make():
+        idx = gpu.VectorIndex(ids, xv)
+        for name, value in options:                       # (outside the armed window: exact_wide = 1 allocates the copy)
+            idx.set_option(name, value)
+        return [idx]
+
+    def call(h):
+        h[0].profile_enable(True)
+        try:
+            return h[0].search(qs, k), set(h[0].profile_read())
+        finally:
+            h[0].profile_enable(False)
+
+    def check(r):
+        (gi, gs), names = r
+        assert kernels <= names and "exact_scan" not in names, sorted(names)
+        _exact_same(gi, gs, full(), k, form)
+    _sweep(gpu, f"exact_search, {form}", make, call, check, 6)
+
+
+def test_set_option_exact_wide(gpu, oracle):
+    """exf_wide_set -> exf_table_stats on a wide table that was pinned without the option: exf_small (the statistics' words: a wide
+    pin returns before it) and the fragment-order copy = 2.  A failed set leaves "the handle ... the one it was" (exact_wide.hip):
+    index_bytes as before (the sweep), the option off -- a search takes the all-exact scan and gives the oracle's lists; the same
+    set_option then succeeds and the search is the wide filter's."""
+    xv, ids = _vec_table(516, 8300)
+    qs = np.ascontiguousarray(xv[np.random.default_rng(15).choice(8000, 6, replace=False)])
+    full = Lazy(lambda: [oracle.exact_knn(xv, ids, q, 5) for q in qs])
+
+    def search(idx):
+        idx.profile_enable(True)
+        try:
+            return idx.search(qs, 5), set(idx.profile_read())
+        finally:
+            idx.profile_enable(False)
+
+    def call(h):
+        nbytes = h[0].nbytes
+        try:
+            h[0].set_option("exact_wide", 1)
+        except gpu.FreddyGpuError:
+            gpu.alloc_fail_nth(0)
+            assert h[0].nbytes == nbytes
+            (gi, gs), names = search(h[0])
+            assert "exact_scan" in names and "exact_filter_wide" not in names, sorted(names)
+            _exact_same(gi, gs, full(), 5, "after the failed set_option")
+            raise
+        assert h[0].nbytes - nbytes >= 8300 * 516 * 4
+        return h[0]
+
+    def check(idx):
+        (gi, gs), names = search(idx)
+        assert "exact_filter_wide" in names and "exact_scan" not in names, sorted(names)
+        _exact_same(gi, gs, full(), 5, "after set_option exact_wide = 1")
+    _sweep(gpu, "set_option exact_wide = 1", lambda: [gpu.VectorIndex(ids, xv)], call, check, 2)
+
+
+@pytest.mark.parametrize("form", ["plain", "refine_all", "crowded"])
+def test_encode_rows(gpu, form):
+    """encode_rows.hip: enc_img, enc_work, enc_io = 3 (enc_redo's ensure beside them is for the shapes the filter does not serve);
+    encode_refine_all adds enc_all = 4; a crowded input (tests/test_gpu_encode_rows.py test_redo_of_crowded_items' table) reaches
+    redo_position's enc_redo = 4.  The check is equality with freddy_gpu_encode."""
+    import test_gpu_encode_rows as er
+    if form == "crowded":
+        d, m, K, C, n = 24, 6, 100, 0, 96
+        x, cb, coarse = er._tables(d, m, K, C, n, seed=7)
+        cb[2, 10:74] = np.float32(6.0)
+        near = np.arange(0, n, 3)
+        x[near, 8:12] = cb[2, 10] + np.float32(1e-3) * x[near, 8:12]
+    else:
+        d, m, K, C, n = 24, 6, 31, 3, 70
+        x, cb, coarse = er._tables(d, m, K, C, n)
+    want = gpu.encode(cb, x, coarse=coarse)
+    ids = np.arange(1, n + 1, dtype=np.int32)
+
+    def make():
+        idx = gpu.VectorIndex(ids, x)
+        idx.set_option("encode_refine_all", int(form == "refine_all"))
+        return [idx]
+
+    def call(h):
+        got = h[0].encode_rows(cb, coarse=coarse)
+        return got, h[0].last_encode_stats()
+
+    def check(r):
+        got, st = r
+        assert er._same(got[0], want[0]) and er._same(got[1], want[1]), (form, st)
+        assert st["violations"] == 0 and (form != "crowded" or st["redone"] > 0), (form, st)
+        assert form != "refine_all" or st["checked"] == n * (m * K + C), st
+    _sweep(gpu, f"encode_rows {form}", make, call, check, {"plain": 3, "refine_all": 4, "crowded": 4}[form])
+
+
 # =======================================================================================
 # two handles: post verification and the approximate analogies (rerank.hip rerank_block: pv_io + pv_q = 2, and the search's own buffers)
 # =======================================================================================

@@ -121,6 +121,58 @@ def test_exact_knn_lists_and_brackets(gpu, oracle, name):
     plain.close()
 
 
+KS_RANK = (33, 100, 200, 201, 1024)      # (query 0: 100 and 200 cut inside its 201 near-ties, 201 ends at their edge: test_tiny_inputs_cpu.py)
+RANK_FILTER = {"exact_filter", "exact_threshold_rank", "exact_refine"}
+
+
+@functools.lru_cache(maxsize=None)
+def _expected_1024(oracle, name, wide=False):
+    ids, t, q = ti.wide_case(name) if wide else ti.case(name)
+    return [oracle.exact_knn(t, ids, v, 100 if wide else 1024) for v in q]
+
+
+def _rank_calls(idx, q, exp, ks, brackets_of, kernels, what0):
+    for brackets in brackets_of:
+        idx.set_option("check_brackets", brackets)
+        for k in ks:
+            what = f"{what0} check_brackets {brackets} k {k}"
+            v0, c0 = idx.bound_violations(), idx.bound_checked()
+            got, names = _profiled(idx, lambda: idx.search(q, k))
+            viol, checked = idx.bound_violations() - v0, idx.bound_checked() - c0
+            print(what, "violations", viol, "checked", checked, "lists equal", bool(np.array_equal(got[0], _lists(exp, k)[0])))
+            assert kernels(k) <= names and not (names & ALL_EXACT), (what, sorted(names))
+            assert viol == 0, (what, "rows outside their bracket", viol)
+            assert checked == (ti.Q * ti.N if brackets else 0), (what, checked)
+            _same(got, _lists(exp, k), what)
+
+
+@pytest.mark.parametrize("name,hist", [(n, 0) for n in sorted(ti.CASES)] + [("unscale_underflows", 1), ("elements_subnormal", 1)])
+def test_exact_knn_lists_and_brackets_at_k_above_32(gpu, oracle, name, hist):
+    """Option exact_filter_k = 1024: exf_rank_threshold_kernel orders the raw binary32 patterns of the approximate similarities,
+    which these cases make subnormal or all +-0 (unscale_underflows: the unscale factor is 0; elements_subnormal), so the bracket
+    rests on its floor; exf_refine_tree_kernel merges the lists.  k = 33 .. 1024 with every row refined and without: the oracle's
+    ids and similarity bits, the filter's kernels, no bracket left, Q N rows checked.  hist = 1: the four histogram copies."""
+    ids, t, q = ti.case(name)
+    idx = _pin(gpu, ids, t)
+    idx.set_option("exact_filter_k", 1024)
+    idx.set_option("exact_rank_hist", hist)
+    _rank_calls(idx, q, _expected_1024(oracle, name), KS_RANK, (4, 0), lambda k: RANK_FILTER, f"{name} exact_rank_hist {hist}")
+    idx.close()
+
+
+@pytest.mark.parametrize("name", ti.WIDE_CASES)
+def test_wide_exact_knn_lists_and_brackets(gpu, oracle, name):
+    """The same construction at d = 516 under options exact_wide = 1 and exact_filter = 1 (2 080 rows: forced), k = 5 and 100,
+    every row refined: exf_wide_filter_kernel's products where the norms vanish or the unscale factor is 0."""
+    ids, t, q = ti.wide_case(name)
+    idx = gpu.VectorIndex(ids, t)
+    for option, value in (("exact_wide", 1), ("exact_filter", 1), ("exact_filter_k", 1024)):
+        idx.set_option(option, value)
+    kernels = lambda k: {"exact_filter_wide", "exact_refine", "exact_threshold_rank" if k > 32 else "exact_threshold"}
+    _rank_calls(idx, q, _expected_1024(oracle, name, True), (5, 100), (4,), kernels, f"wide {name}")
+    idx.close()
+
+
 @pytest.mark.parametrize("name", sorted(ti.CASES))
 def test_join_by_id_and_by_text_lists_and_brackets(gpu, oracle, name):
     """The same cases once each through join, exact_search_ids, exact_join_ids and exact_search_texts (one token per text, not

@@ -60,6 +60,46 @@ def test_cluster_is_a_near_tie_the_reference_orders(oracle, name):
     assert np.all(np.abs(s64[ti.CLUSTER] - fifth) <= width), name
 
 
+def test_query_0_at_k_above_32(oracle):
+    """What tests/test_gpu_tiny_magnitudes.py's k = 33 .. 1024 rely on.  Query 0's 201 best rows are the cluster and ONE more row
+    of the corpus (a copy of the row the cluster was made from: util.corpus duplicates 1 % of its rows), 201 near-ties within
+    1e-5 of each other with the 202nd row 3 % below: k = 100 and k = 200 cut inside the near-ties, k = 201 ends at their edge."""
+    for name in sorted(ti.CASES):
+        ids, t, q = ti.case(name)
+        e = oracle.exact_knn(t, ids, q[0], 202)
+        near = set(ids[ti.CLUSTER].tolist()) | {int(ids[1542])}
+        assert set(e["id"][:201].tolist()) == near and e["id"][201] not in near, name
+        s = e["dist"].astype(np.float64)
+        assert s[200] >= s[0] * (1 - 1e-5) and s[201] <= s[0] * 0.98, (name, s[[0, 200, 201]])
+    assert ti.N >= 1024 and ti.N // 32 * 32 == ti.N     # the sample is the table: at least k rows of it for every k <= 1024
+
+
+@pytest.mark.parametrize("name", ti.WIDE_CASES)
+def test_wide_cases(oracle, name):
+    """base(516) under the exponents of three cases: the same construction at T = 33 (a short last segment of the wide filter)"""
+    ids, x, qs = ti.base(ti.WIDE_D)
+    assert x.shape == (ti.N, ti.WIDE_D) and qs.shape == (ti.Q, ti.WIDE_D) and (ti.WIDE_D + 15) // 16 == 33 and ti.WIDE_D % 4 == 0
+    assert np.array_equal(ids, ti.base()[0])
+    norms = np.linalg.norm(x.astype(np.float64), axis=1)
+    assert 0.5 < norms.min() and norms.max() < 2.0, "unit-scale rows"
+    _, t, q = ti.wide_case(name)
+    te, qe = ti.CASES[name][:2]
+    assert np.array_equal(t.astype(np.float64), x.astype(np.float64) * 2.0 ** te), name        # exact scalings
+    assert np.array_equal(q.astype(np.float64), qs.astype(np.float64) * 2.0 ** qe), name
+    longest = int(np.argmax(norms))
+    assert ti.classify(ti.fma_chain_of_squares(t[longest])) == ti.CASES[name][2], name
+    assert ti.classify(ti.fma_chain_of_squares(q[0])) == ti.CASES[name][3], name
+    if name == "unscale_underflows":     # exf_scale_exp: the largest |element| lands in [2^13, 2^14); 2^-(eq + ex) underflows from 150 on
+        ex = 14 - int(np.frexp(np.abs(t).max())[1])
+        assert all(14 - int(np.frexp(np.abs(v).max())[1]) + ex >= 150 for v in q), name
+    # query 0's 200 best rows are the cluster, all similarities normal numbers: k = 100 cuts inside it
+    e = oracle.exact_knn(t, ids, q[0], 201)
+    cluster_ids = set(ids[ti.CLUSTER].tolist())
+    assert set(e["id"][:200].tolist()) == cluster_ids and e["id"][200] not in cluster_ids, name
+    # (516 roundings of the chain leave the 200 rows a handful of distinct values: the rounding and the ids order them)
+    assert np.all(np.abs(e["dist"]) >= 2.0 ** -126) and 5 <= np.unique(e["dist"][:200].view(np.uint32)).size < 200, name
+
+
 @pytest.mark.parametrize("name", ti.NORM_VANISHES)
 def test_a_bracket_of_1e37_drops_a_true_member(oracle, name):
     """The model of a filter whose bracket is only the floor: a = the exact dot product rounded to binary32, candidates = rows

@@ -47,19 +47,35 @@ NORM_VANISHES = ("squares_rounded_away_74", "squares_vanish_80", "squares_vanish
 
 
 @functools.lru_cache(maxsize=None)
-def base():
-    """(ids int32[N] ascending with gaps, x float32[N][D] with the cluster in it, queries float32[Q][D] with query 0 parallel to it)"""
-    x = util.corpus(N, d=D).numpy().astype(np.float32).copy()
+def base(d=D):
+    """(ids int32[N] ascending with gaps, x float32[N][d] with the cluster in it, queries float32[Q][d] with query 0 parallel to it)"""
+    x = util.corpus(N, d=d).numpy().astype(np.float32).copy()
     ids = (np.arange(N) * 3 + 2).astype(np.int32)
     rng = np.random.default_rng(SEED)
     row = x[CLUSTER_ROW].copy()
     n = CLUSTER.stop - CLUSTER.start
-    nudge = rng.integers(-NUDGE_ULPS, NUDGE_ULPS + 1, size=(n, D)).astype(np.int32)
+    nudge = rng.integers(-NUDGE_ULPS, NUDGE_ULPS + 1, size=(n, d)).astype(np.int32)
     x[CLUSTER] = (row.view(np.int32)[None, :] + nudge).view(np.float32)     # (sign-magnitude: +j moves |v| by j ulps)
-    qs = rng.standard_normal((Q, D)).astype(np.float32)
+    qs = rng.standard_normal((Q, d)).astype(np.float32)
     qs[0] = row * np.float32(4.0)
     x.setflags(write=False); ids.setflags(write=False); qs.setflags(write=False)
     return ids, x, qs
+
+
+# the wide table (option exact_wide: T = 33 k-steps, a short last segment): base(WIDE_D) under the exponents of these cases
+WIDE_D = 516
+WIDE_CASES = ("squares_vanish_80", "unscale_underflows", "tiny_query")
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case(name):
+    """(ids, table, queries) of a case at d = WIDE_D; read-only arrays, computed once"""
+    ids, x, qs = base(WIDE_D)
+    te, qe = CASES[name][:2]
+    t = (x * np.float32(2.0 ** te)).astype(np.float32)
+    q = (qs * np.float32(2.0 ** qe)).astype(np.float32)
+    t.setflags(write=False); q.setflags(write=False)
+    return ids, t, q
 
 
 @functools.lru_cache(maxsize=None)
