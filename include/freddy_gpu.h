@@ -257,6 +257,16 @@ int freddy_gpu_exact_assign(freddy_gpu_index_t* vecs, const float* queries /*[Q]
 int freddy_gpu_pq_assign(freddy_gpu_index_t* pq, const float* queries /*[Q][d]*/, int32_t Q, float sentinel,
                          const int32_t* target_ids, int64_t n_targets, int32_t* out_query /*[n_targets]*/,
                          float* out_sim /*[n_targets]*/);
+/* Option "assign_filter" = 1 on the vector handle: freddy_gpu_exact_assign, and freddy_gpu_cluster without a pq handle, compute the
+ * same bits as filter + refine + redo (csrc/assign_filter.h): x.q for every (target, centroid) on the matrix cores inside a proven
+ * bracket, the chain above for the few centroids that can be the first, the all-exact walk for the targets the filter cannot
+ * answer (a non-finite row, norm or centroid, scales outside the bracket's range, more than 16 centroids inside the bracket); the
+ * approximate value never reaches an output.  Tables of more than 512 dimensions take the all-exact kernel with the option on.
+ * The last such call on this handle (both entry points; zeros after a call that did not take the filter): out[0] = targets with a
+ * row that entered the filter, [1] = candidates refined with the exact chain, [2] = targets redone all-exact, [3] / [4] = brackets
+ * compared with the chain / violated (option check_brackets bit 4), summed over the call's passes and rounds.  FREDDY_E_ARG for
+ * NULL, FREDDY_E_KIND for a handle of another kind. */
+int freddy_gpu_last_assign_stats(const freddy_gpu_index_t* vecs, int64_t out[5]);
 
 /* ---- the whole k-means of cluster_exact / cluster_pq in one call (cluster.h) ----------------------------------------------
  * generic_cluster (freddy--0.0.1.sql:1086-1209) with the draws of random() supplied by the caller; pq == NULL: cluster_exact,
@@ -868,11 +878,16 @@ int freddy_gpu_abi_version(void);
  *                2^20; tests make a small table span many blocks), "tokenize_pass" (on a vector handle: texts per pass of the
  *                *_search_texts calls: 0 = as many as a pinned block of 256 MiB holds), "tokenize_unit" (the normalisation of
  *                text vectors: 1 = a wave per text, lane 0 walking the chain of squares; 2 = one chain per lane over 64 texts;
- *                0 = auto, the default: 1 below 16384 texts, 2 from there on)
+ *                0 = auto, the default: 1 below 16384 texts, 2 from there on), "assign_filter" (vector handles; also
+ *                FREDDY_GPU_ASSIGN_FILTER at pin time: 1 = freddy_gpu_exact_assign and freddy_gpu_cluster without a pq handle assign
+ *                as matrix-core filter + exact refine + redo, d <= 512; 0 = the all-exact kernel, the default; FREDDY_E_KIND on
+ *                another kind of handle)
  *   self-checks (tests):  "check_brackets" (bit 0: the scan keeps and the merge refines EVERY probed row, bit 1: the cell
  *                selection refines every cell, bit 2: exact kNN and the exact join refine every row -- each with its proven bracket compared with
  *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines
- *                every row for every analogy, counted the same way), "join_host_traversal", "join_front_gather" (1, the
+ *                every row for every analogy, counted the same way; bit 4, value 16: with "assign_filter" the filter keeps every value and
+ *                the refine compares every (target, centroid) bracket with the chain, counted the same way and in
+ *                freddy_gpu_last_assign_stats), "join_host_traversal", "join_front_gather" (1, the
  *                default: freddy_gpu_knn_join_ids gathers its queries in the sub-distance launch; 0: a gather launch, then the
  *                sub-distance kernel -- the same lists either way),
  *                "join_libm_margin_ppm", "grid_cus" (the CU count that every grid sized from the chip is planned with, and every

@@ -56,7 +56,8 @@ struct AssignExactArgs {
   int n_targets, Q, d;
 };
 
-// (static: the header is included by several units, cluster.hip launches it)
+// (static: the header is included by several units, cluster.hip launches it; its walk over the queries is assign_exact_walk.inc,
+// which the redo of option assign_filter includes too)
 static __global__ __launch_bounds__(64) void assign_exact_kernel(AssignExactArgs a) {
   __shared__ __attribute__((aligned(16))) float tile[TILE_FLOATS];     // [TILE_DCH][TILE_STRIDE]
   __shared__ __attribute__((aligned(16))) float qs[TILE_QFLOATS];      // [TILE_DCH][TILE_QT]
@@ -64,65 +65,7 @@ static __global__ __launch_bounds__(64) void assign_exact_kernel(AssignExactArgs
   const int i = blockIdx.x * 64 + lane;
   int32_t row = -1;
   if (i < a.n_targets) row = row_of_id(a.vec_ids, a.N, a.targets[i]);
-  uint32_t best_ord = 0;   // (no similarity's image)
-  int32_t best_q = -1;
-  float best_sim = -__builtin_huge_valf();
-  if (__ballot(row >= 0) != 0ull) {
-    const bool vec4 = (d & 3) == 0;
-    for (int q0 = 0; q0 < a.Q; q0 += TILE_QT) {
-      float acc[TILE_QT];
-#pragma unroll
-      for (int t = 0; t < TILE_QT; ++t) acc[t] = 0.0f;
-      for (int c0 = 0; c0 < d; c0 += TILE_DCH) {
-        const int nd = (d - c0 < TILE_DCH) ? d - c0 : TILE_DCH;
-        float4 v[8], qv[2];
-#pragma unroll
-        for (int it = 0; it < 8; ++it) v[it] = tile_row_piece(a.rows, row, it, lane, d, c0, nd, vec4);
-#pragma unroll
-        for (int it = 0; it < 2; ++it) qv[it] = tile_query_piece(a.queries, a.Q, q0, it, lane, d, c0, nd, vec4);
-#pragma unroll
-        for (int it = 0; it < 8; ++it) tile_store_row_piece(tile, v[it], it, lane);
-#pragma unroll
-        for (int it = 0; it < 2; ++it) tile_store_query_piece(qs, qv[it], it, lane);
-        wave_lds_sync();
-        const float* col = tile + lane;   // (the 16-accumulator walk, kept in place for registers: dot_chain.h)
-        if (nd == TILE_DCH) {
-#pragma unroll
-          for (int j = 0; j < TILE_DCH; ++j) {
-            const float x = col[j * TILE_STRIDE];
-#pragma unroll
-            for (int t4 = 0; t4 < TILE_QT / 4; ++t4) {
-              const float4 qq = *reinterpret_cast<const float4*>(qs + tile_qrow(j) * TILE_QT + t4 * 4);
-              float p;
-              p = qq.x * x; acc[t4 * 4 + 0] = acc[t4 * 4 + 0] + p;   // core_functions.c:77: scalar += v1[i] * v2[i]
-              p = qq.y * x; acc[t4 * 4 + 1] = acc[t4 * 4 + 1] + p;
-              p = qq.z * x; acc[t4 * 4 + 2] = acc[t4 * 4 + 2] + p;
-              p = qq.w * x; acc[t4 * 4 + 3] = acc[t4 * 4 + 3] + p;
-            }
-          }
-        } else {
-          for (int j = 0; j < nd; ++j) {
-            const float x = col[j * TILE_STRIDE];
-#pragma unroll
-            for (int t4 = 0; t4 < TILE_QT / 4; ++t4) {
-              const float4 qq = *reinterpret_cast<const float4*>(qs + tile_qrow(j) * TILE_QT + t4 * 4);
-              float p;
-              p = qq.x * x; acc[t4 * 4 + 0] = acc[t4 * 4 + 0] + p;
-              p = qq.y * x; acc[t4 * 4 + 1] = acc[t4 * 4 + 1] + p;
-              p = qq.z * x; acc[t4 * 4 + 2] = acc[t4 * 4 + 2] + p;
-              p = qq.w * x; acc[t4 * 4 + 3] = acc[t4 * 4 + 3] + p;
-            }
-          }
-        }
-        wave_lds_sync();
-      }
-#pragma unroll
-      for (int t = 0; t < TILE_QT; ++t) {   // ascending query index: only a strictly larger similarity replaces the best
-        const uint32_t o = assign_ord(acc[t]);
-        if (q0 + t < a.Q && o > best_ord) { best_ord = o; best_q = q0 + t; best_sim = acc[t]; }
-      }
-    }
-  }
+#include "assign_exact_walk.inc"
   if (i < a.n_targets) {
     a.out_query[i] = row >= 0 ? best_q : -1;
     a.out_sim[i] = row >= 0 ? best_sim : -__builtin_huge_valf();

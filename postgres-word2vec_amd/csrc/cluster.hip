@@ -3,6 +3,7 @@
 #include "internal.h"
 
 #include "assign.h"
+#include "assign_filter.h"
 #include "cluster.h"
 
 // ---- the assignment step of cluster_exact (assign.h) ----------------------------------------------------------------------
@@ -20,6 +21,100 @@ static int exact_assign_pass(freddy_gpu_index* ix, hipStream_t s, const float* d
   return FREDDY_OK;
 }
 
+// ---- option assign_filter: the same assignment as filter + refine + redo (assign_filter.h) ------------------------------------
+// What a call with the option on keeps between its launches: the buffers of the handle, carved for passes of `cap` targets.
+struct AsfRun {
+  bool on = false, check = false;
+  int T = 0, Qpad = 0;
+  int64_t cap = 0;
+  AsfHead* head = nullptr;
+  ench8* img = nullptr;
+  int32_t *cand_cnt = nullptr, *rows = nullptr, *redo = nullptr, *cand_idx = nullptr;
+  float* eps = nullptr;
+};
+static inline size_t asf_up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// Whether the call takes the filter, the targets per pass it may then take (*pass shrinks under the self-check), and every buffer it
+// needs -- before the first launch, so that a failed allocation leaves nothing half done.
+static int asf_begin(freddy_gpu_index* ix, int Q, int64_t* pass, AsfRun& r) {
+  for (int64_t& v : ix->asf_stats) v = 0;
+  r.on = ix->tune.assign_filter != 0 && ix->d <= ENC_MAX_S;
+  if (!r.on) return FREDDY_OK;
+  r.check = (ix->tune.check_brackets & ASF_CHECK) != 0;
+  r.T = (ix->d + 15) / 16;
+  r.Qpad = (Q + 127) / 128 * 128;
+  if (r.check) *pass = std::min(*pass, asf_check_pass(r.Qpad));
+  r.cap = *pass;
+  const size_t n = (size_t)r.cap, img_bytes = (size_t)r.Qpad * r.T * 64;
+  if (ix->asf_img.ensure(ASF_HEAD_BYTES + img_bytes) || ix->asf_work.ensure(4 * asf_up256(4 * n) + asf_up256(4 * n * ENC_KEEP)) ||
+      (r.check && ix->asf_all.ensure(sizeof(float) * n * (size_t)r.Qpad)))
+    return fail(FREDDY_E_NOMEM, "workspace allocation failed");
+  if (r.check)
+    if (int rc = ensure_viol(ix)) return rc;
+  r.head = ix->asf_img.as<AsfHead>();
+  r.img = reinterpret_cast<ench8*>(ix->asf_img.as<unsigned char>() + ASF_HEAD_BYTES);
+  unsigned char* p = ix->asf_work.as<unsigned char>();
+  auto take = [&](size_t bytes) { unsigned char* at = p; p += asf_up256(bytes); return at; };
+  r.cand_cnt = (int32_t*)take(4 * n); r.rows = (int32_t*)take(4 * n); r.redo = (int32_t*)take(4 * n); r.eps = (float*)take(4 * n);
+  r.cand_idx = (int32_t*)take(4 * n * ENC_KEEP);
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&assign_filter_kernel<ENC_PF>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  return FREDDY_OK;
+}
+
+// The image of the Q centroids at d_queries (once per call, once per round of the k-means); first: the call's counters start at zero.
+static int asf_image(freddy_gpu_index* ix, hipStream_t s, const AsfRun& r, const float* d_queries, int Q, bool first) {
+  hipLaunchKernelGGL(assign_begin_kernel, dim3(1), dim3(64), 0, s, r.head, 1, first ? 1 : 0);
+  AsfImageArgs ia;
+  ia.queries = d_queries; ia.head = r.head; ia.img = r.img; ia.Q = Q; ia.Qpad = r.Qpad; ia.d = ix->d; ia.T = r.T;
+  const unsigned g0 = (unsigned)std::min<int64_t>(((int64_t)Q + 3) / 4, 4096);
+  const unsigned g1 = (unsigned)(((int64_t)(r.Qpad / 32) * r.T * 64 + 255) / 256);
+  timed_launch(ix, s, "assign_image_kernel", [&] {
+    ia.phase = 0; hipLaunchKernelGGL(assign_image_kernel, dim3(g0), dim3(256), 0, s, ia);
+    ia.phase = 1; hipLaunchKernelGGL(assign_image_kernel, dim3(g1), dim3(256), 0, s, ia);
+  });
+  HIP_TRY(hipGetLastError());
+  return FREDDY_OK;
+}
+
+// One pass of n <= r.cap targets: filter, refine, redo.  d_row_in: the targets' rows where the caller has them (cluster.h's row_of).
+static int asf_pass(freddy_gpu_index* ix, hipStream_t s, const AsfRun& r, bool first_pass, const float* d_queries, int Q, const int32_t* d_targets,
+                    const int32_t* d_row_in, int n, int32_t* d_best, float* d_sim) {
+  if (!first_pass) hipLaunchKernelGGL(assign_begin_kernel, dim3(1), dim3(64), 0, s, r.head, 0, 0);   // (the image's launch cleared the first pass's count)
+  const unsigned tiles = (unsigned)((n + ASF_TQ - 1) / ASF_TQ);
+  AsfFilterArgs fa;
+  fa.targets = d_targets; fa.row_in = d_row_in; fa.row_out = d_row_in ? nullptr : r.rows; fa.vec_ids = ix->ids; fa.rows = ix->coarse; fa.N = ix->N;
+  fa.n = n; fa.d = ix->d; fa.T = r.T; fa.Q = Q; fa.Qpad = r.Qpad; fa.head = r.head; fa.img = r.img; fa.eps_rel = asf_eps_rel(ix->d);
+  fa.cand_cnt = r.cand_cnt; fa.cand_idx = r.cand_idx; fa.tgt_eps = r.check ? r.eps : nullptr; fa.all_a = r.check ? ix->asf_all.as<float>() : nullptr;
+  fa.redo_list = r.redo; fa.out_query = d_best; fa.out_sim = d_sim;
+  timed_launch(ix, s, "assign_filter_kernel", [&] {
+    hipLaunchKernelGGL((assign_filter_kernel<ENC_PF>), dim3(tiles), dim3(256), asf_filter_lds(r.T), s, fa);
+  });
+  const int32_t* trow = d_row_in ? d_row_in : r.rows;
+  AsfRefineArgs ra;
+  ra.trow = trow; ra.rows = ix->coarse; ra.queries = d_queries; ra.n = n; ra.d = ix->d; ra.Q = Q; ra.Qpad = r.Qpad;
+  ra.cand_cnt = r.cand_cnt; ra.cand_idx = r.cand_idx; ra.tgt_eps = fa.tgt_eps; ra.all_a = fa.all_a; ra.out_query = d_best; ra.out_sim = d_sim;
+  ra.head = r.head; ra.viol = ix->viol;
+  timed_launch(ix, s, "assign_refine_kernel", [&] { hipLaunchKernelGGL(assign_refine_kernel, dim3(tiles), dim3(64), 0, s, ra); });
+  AsfRedoArgs da;
+  da.redo_list = r.redo; da.trow = trow; da.rows = ix->coarse; da.queries = d_queries; da.d = ix->d; da.Q = Q; da.out_query = d_best; da.out_sim = d_sim;
+  da.head = r.head;
+  timed_launch(ix, s, "assign_redo_kernel", [&] { hipLaunchKernelGGL(assign_redo_kernel, dim3(tiles), dim3(64), 0, s, da); });
+  HIP_TRY(hipGetLastError());
+  return FREDDY_OK;
+}
+// the call's counters from the head a copy on the stream brought down (freddy_gpu_last_assign_stats)
+static void asf_keep_stats(freddy_gpu_index* ix, const AsfHead& h) {
+  ix->asf_stats[0] = (int64_t)h.filtered; ix->asf_stats[1] = (int64_t)h.stats[0]; ix->asf_stats[2] = (int64_t)h.stats[3];
+  ix->asf_stats[3] = (int64_t)h.stats[1]; ix->asf_stats[4] = (int64_t)h.stats[2];
+}
+
+extern "C" int freddy_gpu_last_assign_stats(const freddy_gpu_index_t* ix, int64_t out[5]) {
+  if (!ix || !out) return fail(FREDDY_E_ARG, "NULL argument");
+  if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "index handle has the wrong kind for this call");
+  for (int i = 0; i < 5; ++i) out[i] = ix->asf_stats[i];
+  return FREDDY_OK;
+}
+
 extern "C" int freddy_gpu_exact_assign(freddy_gpu_index_t* ix, const float* queries, int32_t Q, const int32_t* target_ids, int64_t n_targets,
                                        int32_t* out_query, float* out_sim) {
   // (the scalar arguments first: they are checked before the handle is looked at, so no device is needed to see these errors)
@@ -32,18 +127,30 @@ extern "C" int freddy_gpu_exact_assign(freddy_gpu_index_t* ix, const float* quer
   Workspace* ws = workspace_for(ix, ix->stream);
   hipStream_t s = ix->stream;
   const int d = ix->d;
-  const int64_t pass = std::min(AS_PASS, n_targets);
+  int64_t pass = std::min(AS_PASS, n_targets);
+  AsfRun fr;
+  if (int rc = asf_begin(ix, Q, &pass, fr)) return rc;
   if (ws->w_q.ensure(sizeof(float) * (size_t)Q * d) || ws->w_sub_rows.ensure(sizeof(int32_t) * (size_t)pass) ||
       ws->w_out_ids.ensure(sizeof(int32_t) * (size_t)pass) || ws->w_out_dist.ensure(sizeof(float) * (size_t)pass))
     return fail(FREDDY_E_NOMEM, "workspace allocation failed");
   HIP_TRY(hipMemcpyAsync(ws->w_q.p, queries, sizeof(float) * (size_t)Q * d, hipMemcpyHostToDevice, s));
+  if (fr.on)
+    if (int rc = asf_image(ix, s, fr, ws->w_q.as<float>(), Q, true)) return rc;
   for (int64_t t0 = 0; t0 < n_targets; t0 += pass) {
     const int n = (int)std::min(pass, n_targets - t0);
     HIP_TRY(hipMemcpyAsync(ws->w_sub_rows.p, target_ids + t0, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-    if (int rc = exact_assign_pass(ix, s, ws->w_q.as<float>(), Q, ws->w_sub_rows.as<int32_t>(), n, ws->w_out_ids.as<int32_t>(), ws->w_out_dist.as<float>())) return rc;
+    if (fr.on) {
+      if (int rc = asf_pass(ix, s, fr, t0 == 0, ws->w_q.as<float>(), Q, ws->w_sub_rows.as<int32_t>(), nullptr, n, ws->w_out_ids.as<int32_t>(), ws->w_out_dist.as<float>())) return rc;
+    } else if (int rc = exact_assign_pass(ix, s, ws->w_q.as<float>(), Q, ws->w_sub_rows.as<int32_t>(), n, ws->w_out_ids.as<int32_t>(), ws->w_out_dist.as<float>())) return rc;
     HIP_TRY(hipMemcpyAsync(out_query + t0, ws->w_out_ids.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(out_sim + t0, ws->w_out_dist.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));   // (the next pass overwrites the three buffers)
+  }
+  if (fr.on) {
+    AsfHead h;
+    HIP_TRY(hipMemcpyAsync(&h, fr.head, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    asf_keep_stats(ix, h);
   }
   return FREDDY_OK;
 }
@@ -78,7 +185,11 @@ extern "C" int freddy_gpu_cluster(freddy_gpu_index_t* vecs, freddy_gpu_index_t* 
   Workspace* ws = workspace_for(vecs, s);
   Workspace* wpq = pq ? workspace_for(pq, s) : nullptr;
   const int d = vecs->d, nn = (int)n;
-  const int64_t pass = std::min<int64_t>(vecs->tune.cluster_pass > 0 ? vecs->tune.cluster_pass : CL_PASS, n);
+  int64_t pass = std::min<int64_t>(vecs->tune.cluster_pass > 0 ? vecs->tune.cluster_pass : CL_PASS, n);
+  AsfRun fr;
+  if (!pq) {
+    if (int rc = asf_begin(vecs, kc, &pass, fr)) return rc;
+  }
   const int Qc = pq ? pq_assign_lut_queries(pq, kc) : 0;
   const size_t head = 64;   // bytes in front of lens[]: the unknown-id word
   const int n_blk = (int)((n + CL_STEP - 1) / CL_STEP);
@@ -111,10 +222,14 @@ extern "C" int freddy_gpu_cluster(freddy_gpu_index_t* vecs, freddy_gpu_index_t* 
   }
   for (int J = 1; J <= rounds; ++J) {
     int lut_q0 = -1;   // (new centroids: no LUT of the round before is theirs)
+    if (fr.on)
+      if (int rc = asf_image(vecs, s, fr, d_cent, kc, J == 1)) return rc;
     for (int64_t t0 = 0; t0 < n; t0 += pass) {
       const int np = (int)std::min(pass, n - t0);
       if (pq) {
         if (int rc = pq_assign_pass(pq, s, wpq->w_lut.as<float>(), Qc, &lut_q0, d_cent, kc, sentinel, d_ids + t0, np, d_best + t0, d_sim + t0, ws->w_found.as<float>() + t0)) return rc;
+      } else if (fr.on) {
+        if (int rc = asf_pass(vecs, s, fr, t0 == 0, d_cent, kc, d_ids + t0, d_row + t0, np, d_best + t0, d_sim + t0)) return rc;
       } else {
         if (int rc = exact_assign_pass(vecs, s, d_cent, kc, d_ids + t0, np, d_best + t0, d_sim + t0)) return rc;
       }
@@ -132,8 +247,11 @@ extern "C" int freddy_gpu_cluster(freddy_gpu_index_t* vecs, freddy_gpu_index_t* 
     HIP_TRY(hipGetLastError());
   }
   uint32_t unknown = CL_NO_FLAG;
+  AsfHead h;
   HIP_TRY(hipMemcpyAsync(&unknown, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (fr.on) HIP_TRY(hipMemcpyAsync(&h, fr.head, sizeof(h), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  if (fr.on) asf_keep_stats(vecs, h);
   if (unknown != CL_NO_FLAG) return fail(FREDDY_E_ARG, "token id %d has no vector", token_ids[unknown]);   // (the first such position; nothing was written)
   HIP_TRY(hipMemcpyAsync(out_cluster, d_clusters, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
   if (out_sim) HIP_TRY(hipMemcpyAsync(out_sim, d_sim, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));

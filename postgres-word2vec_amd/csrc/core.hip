@@ -59,6 +59,7 @@ Tuning read_tuning() {
   t.lut_budget_mb = std::max<int64_t>(1, env_int("FREDDY_GPU_LUT_BUDGET_MB", t.lut_budget_mb));
   t.lane0_own = (int)env_int("FREDDY_GPU_LANE0_OWN", t.lane0_own);
   t.coarse_pieces = (int)env_int("FREDDY_GPU_COARSE_PIECES", t.coarse_pieces);
+  t.assign_filter = env_int("FREDDY_GPU_ASSIGN_FILTER", t.assign_filter) != 0 ? 1 : 0;
 #ifdef FREDDY_LAB
   t.scan_prof = getenv("FREDDY_GPU_FUSED_PROF") != nullptr;
 #endif
@@ -100,6 +101,7 @@ void free_index(freddy_gpu_index* ix) {
   ix->pv_io.release(); ix->pv_q.release();
   ix->tok_dev.release(); ix->tok_raw.release(); ix->tok_vec.release(); ix->tok_io.release();
   ix->enc_img.release(); ix->enc_work.release(); ix->enc_redo.release(); ix->enc_all.release(); ix->enc_io.release();
+  ix->asf_img.release(); ix->asf_work.release(); ix->asf_all.release();
   for (Lane& l : ix->lanes) {
     if (l.stream && l.stream != ix->stream) (void)hipStreamDestroy(l.stream);
     for (LaneSlot& c : l.slot) {
@@ -290,6 +292,10 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   else if (n == "encode_refine_all") {
     if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "option encode_refine_all belongs to a vector handle");
     t.encode_refine_all = value != 0 ? 1 : 0;
+  }
+  else if (n == "assign_filter") {
+    if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "option assign_filter belongs to a vector handle");
+    t.assign_filter = value != 0 ? 1 : 0;
   }
   else if (n == "exact_wide_shape") t.exact_wide_shape = value == 1 || value == 2 ? (int)value : 0;
   else if (n == "resolve_block") t.resolve_block = (int)std::max<int64_t>(0, std::min<int64_t>(value, (int64_t)1 << 20));

@@ -63,13 +63,6 @@ static ExfPrepArgs exf_prep_args(const freddy_gpu_index* ix, const float* querie
   pa.eps_factor = exf_eps_factor(ix->d); pa.qfrag = ix->exf_qfrag.as<h8v>(); pa.qeps = qeps; pa.qunscale = qunscale; pa.qbad = qbad; pa.copy_out = copy_out;
   return pa;
 }
-// the self-check counters the refine kernels write (allocated by the handle's first filter + refine call)
-static int ensure_viol(freddy_gpu_index* ix) {
-  if (ix->viol) return 0;
-  HIP_TRY(dev_malloc((void**)&ix->viol, 4 * sizeof(int32_t)));
-  HIP_TRY(hipMemset(ix->viol, 0, 4 * sizeof(int32_t)));
-  return 0;
-}
 
 // The words exf_refine_kernel keeps on the handle between the launches of a call -- exf_small [256] qbad, [257] arrived, viol[3] --
 // are zero when a call starts: its last workgroup leaves them so.  exf_begin before a call's first launch (the handle's first call, or

@@ -22,7 +22,7 @@
 //   exact_wide.hip  option exact_wide: the filter pass of exact kNN for 512 < d <= 2048 (exact_wide.h), its state on the handle
 //   exact_rank.hip  option exact_filter_k: the rank-selection threshold and the tree-merge refine of exact kNN's lists of 33 .. 1024 rows (exact_rank.h)
 //   rerank.hip  post verification of pq / ivf lists (pv.h), the approximate analogies over pq / ivf / ivpq (approx_analogy.h), the re-rank stage they share
-//   cluster.hip exact_assign (assign.h), the whole k-means of cluster_exact / cluster_pq (cluster.h)
+//   cluster.hip exact_assign (assign.h; option assign_filter: assign_filter.h), the whole k-means of cluster_exact / cluster_pq (cluster.h)
 //   similarity.hip  similarities by row id: pairs, matrices, joins (similarity.h)
 //   tokenize.hip    text vectors from token ids and the searches over them (tokenize.h)
 //   build.hip   encode, insert_quantize, k-means
@@ -115,10 +115,12 @@ struct Tuning {
   int resolve_block = 0;       // option resolve_block: bitmap words per block of the device resolve (resolve.h): 0 = 256; tests make small tables span many blocks
   int tokenize_pass = 0;       // option tokenize_pass (set on the vector handle): texts per pass of the *_search_texts calls (tokenize.h): 0 = as many as a pinned block of 256 MiB holds
   int tokenize_unit = 0;       // option tokenize_unit: the sum of squares of freddy_gpu_tokenize's normalisation: 1 = a wave per text with lane 0 walking the chain (tok_unit_wave_kernel), 2 = a chain per lane over 64 texts (tok_unit_kernel), 0 = auto: 1 below 16384 texts, 2 from there on (tokenize.h)
+  int assign_filter = 0;       // FREDDY_GPU_ASSIGN_FILTER / option assign_filter (vector handles): 1 = freddy_gpu_exact_assign and freddy_gpu_cluster without a pq handle assign as MFMA filter + exact refine + redo (assign_filter.h) for d <= 512; 0 = assign_exact_kernel for every pair
   int encode_refine_all = 0;   // option encode_refine_all (vector handles): freddy_gpu_encode_rows refines EVERY centroid of every item, so every (row, centroid) bracket is checked (encode_filter.h); 0 / 1
   int64_t similarity_pass_bytes = 0;   // option similarity_pass_bytes: the device result block of one pass of freddy_gpu_similarity_matrix / _join (similarity.h): 0 = 256 MiB, at most 4 GiB; 16 rows of A at least
   // -- self-checks (tests): bit 0 = the scan keeps every row and the merge refines every row (every probed row's bracket is checked),
-  //    bit 1 = the cell selection refines every cell, bit 2 = exact kNN refines every row
+  //    bit 1 = the cell selection refines every cell, bit 2 = exact kNN refines every row, bit 3 = the exact analogy refines every row,
+  //    bit 4 = the assignment filter keeps every value and its refine checks every (target, centroid) bracket
   int check_brackets = 0;
 #ifdef FREDDY_LAB
   int scan_prof = 0;           // FREDDY_GPU_FUSED_PROF (lab builds only): per-phase cycle sums of the scan kernel on stderr
@@ -337,6 +339,10 @@ struct freddy_gpu_index {
   DevBuf enc_img, enc_work, enc_redo, enc_all;
   PinnedBuf enc_io;
   int64_t enc_stats[5] = {0, 0, 0, 0, 0};
+  // option assign_filter (assign_filter.h): the head and the centroid image, a pass's candidate lists / rows / redo list, the self-check's
+  // values, and the last call's counts (freddy_gpu_last_assign_stats): filtered, candidates, redone, checked, violations
+  DevBuf asf_img, asf_work, asf_all;
+  int64_t asf_stats[5] = {0, 0, 0, 0, 0};
 };
 
 template <class F>
@@ -428,6 +434,14 @@ static inline int32_t row_of_near(const std::vector<int32_t>& h_ids, int32_t id)
   while (lo > 0 && h_ids[(size_t)lo] > id) { hi = lo; lo = std::max<int64_t>(0, lo - step); step *= 2; }   // h_ids[lo] <= id < h_ids[hi]
   auto it = std::lower_bound(h_ids.begin() + lo, h_ids.begin() + hi + 1, id);
   return *it == id ? (int32_t)(it - h_ids.begin()) : -1;
+}
+
+// the self-check counters the refine kernels write (allocated by the handle's first filter + refine call)
+static inline int ensure_viol(freddy_gpu_index* ix) {
+  if (ix->viol) return 0;
+  HIP_TRY(dev_malloc((void**)&ix->viol, 4 * sizeof(int32_t)));
+  HIP_TRY(hipMemset(ix->viol, 0, 4 * sizeof(int32_t)));
+  return 0;
 }
 
 // ---- pin.hip ----

@@ -71,6 +71,7 @@ PROTOTYPES = {
     "freddy_gpu_encode": (_INT, [_PTR, _INT, _PTR, _I64, _PTR, _PTR]),
     "freddy_gpu_encode_rows": (_INT, [_PTR, _PTR, _I64, _I64, _PTR, _PTR]),
     "freddy_gpu_last_encode_stats": (_INT, [_PTR, _PTR]),
+    "freddy_gpu_last_assign_stats": (_INT, [_PTR, _PTR]),
     "freddy_gpu_kmeans": (_INT, [_INT, _PTR, _I64, _I32, _I32, _I32, _PTR, _PTR, _PTR]),
     "freddy_gpu_insert_quantize": (_INT, [_PTR, _INT, _PTR, _I64, _PTR, _PTR, _PTR, _PTR, _PTR]),
     "freddy_gpu_append_rows": (_INT, [_PTR, _I64, _PTR, _PTR, _PTR, _PTR]),
@@ -616,6 +617,13 @@ class VectorIndex(_Index):
         target_ids[i] -- the first query under "cosine_similarity_bytea DESC (PostgreSQL's float4 order), query index ASC", the
         similarity bits of join(); (-1, -inf) where the id has no row."""
         return _assign(self, self.lib.freddy_gpu_exact_assign, queries, target_ids, ())
+
+    def last_assign_stats(self):
+        """The last assign() / cluster() call under option assign_filter (freddy_gpu_last_assign_stats): targets with a row that entered
+        the filter, centroids refined with the exact chain, targets redone all-exact, brackets checked and brackets violated."""
+        v = (C.c_int64 * 5)()
+        _check(self.lib.freddy_gpu_last_assign_stats(self.h, v))
+        return dict(zip(("filtered", "candidates", "redone", "checked", "violations"), (int(x) for x in v)))
 
     def cluster(self, token_ids, kc, draws, rounds=10, pq=None, sentinel=1000.0):
         """The whole k-means of cluster_exact (pq=None) / cluster_pq (pq: a PQIndex) in one call (freddy_gpu_cluster): (clusters[n] int32,

@@ -10,7 +10,12 @@ m = 12, K = 1024).
      the exact kernel's achieved bytes/s (n * d * 4 gathered per 16-query tile) and fp32 flop/s (2 * n * Q * d) against the HBM and
      VALU peaks of the MI355X (8 TB/s; 256 CUs x 128 lanes x 2.4 GHz x 1 separately rounded op = 78.6 Tflop/s without FMA).
 Writes profiles/assign_timing.txt (assign_timing_parent.txt in a tree without the entry points) anew and appends part 1 to the A/B
-log.  N / REPS from the environment for a smaller run."""
+log.  N / REPS from the environment for a smaller run.
+ASSIGN_FILTER_AB=1: instead of the above, option assign_filter 0 and 1 ALTERNATED on one vector handle in one process, ROUNDS (3)
+rounds: freddy_gpu_exact_assign at Q in {10, 100, 1000}, n in {4096, 100 000, 3 M}, and freddy_gpu_cluster (cluster_exact, ten rounds)
+at kc in {10, 100} and the same n; equal outputs are asserted before anything is timed; per setting the kernels' time (the handle's
+profile, all assign_ kernels) of every round, so the baseline's own spread stands beside the gain; candidates per target and the
+redo count from freddy_gpu_last_assign_stats.  Writes profiles/assign_filter_timing.txt."""
 import os
 import statistics
 import sys
@@ -26,8 +31,8 @@ from freddy_amd import gpu, index_build as ib, udf   # noqa: E402
 N, REPS = int(os.environ.get("N", 3000000)), int(os.environ.get("REPS", 5))
 D, HBM_PEAK, VALU_PEAK = 300, 8.0e12, 256 * 128 * 2.4e9
 HAVE = hasattr(gpu.load(), "freddy_gpu_exact_assign")
-out = open(os.path.join(ROOT, "profiles", "assign_timing.txt" if HAVE else "assign_timing_parent.txt"), "w")
-ab = open(os.environ.get("ASSIGN_AB", os.path.join(ROOT, "profiles", "assign_ab.txt")), "a")
+FILTER_AB = bool(os.environ.get("ASSIGN_FILTER_AB"))
+out = open(os.path.join(ROOT, "profiles", "assign_filter_timing.txt" if FILTER_AB else "assign_timing.txt" if HAVE else "assign_timing_parent.txt"), "w")
 SIDE = "this  " if HAVE else "parent"
 
 
@@ -40,6 +45,51 @@ def say(line, ab_too=False):
         ab.flush()
 
 
+def filter_ab():
+    rounds = int(os.environ.get("ROUNDS", 3))
+    xh = ib.make_corpus(N, seed=20260101, device=torch.device("cuda", 0)).cpu().numpy()
+    ids = np.arange(1, N + 1, dtype=np.int32)
+    vec = gpu.VectorIndex(ids, xh)
+    rng = np.random.default_rng(7)
+
+    def kernel_ms(call, option):
+        vec.set_option("assign_filter", option)
+        vec.profile_enable(True)
+        res = call()
+        ms = sum(t for nm, (_, t) in vec.profile_read().items() if nm.startswith("assign_"))
+        vec.profile_enable(False)
+        return res, ms
+
+    say(f"# option assign_filter 0 / 1 alternated on one handle, {N} x {D}, {rounds} rounds; kernel_ms = all assign_ kernels of one call")
+    say("# call            n   Q/kc   off_ms (rounds)            on_ms (rounds)             off/on  cand/target  redone")
+    for n in (4096, 100000, min(N, 3000000)):
+        tg = rng.choice(ids, n).astype(np.int32)
+        for what, sizes in (("exact_assign", (10, 100, 1000)), ("cluster_exact", (10, 100))):
+            for Q in sizes:
+                if what == "exact_assign":
+                    cent = np.stack([xh[rng.choice(N, 10)].mean(axis=0) for _ in range(Q)]).astype(np.float32)
+                    call = lambda: vec.assign(cent, tg)                                   # noqa: E731
+                else:
+                    draws = rng.random(Q + 9 * Q * 10)
+                    call = lambda: vec.cluster(tg, Q, draws)                              # noqa: E731
+                (a, _), (b, _) = kernel_ms(call, 0), kernel_ms(call, 1)                     # warm-up, and the outputs
+                assert all(np.array_equal(u.view(np.uint32), v.view(np.uint32)) for u, v in zip(a, b)), (what, n, Q)
+                off, on = [], []
+                for _ in range(rounds):
+                    off.append(kernel_ms(call, 0)[1])
+                    on.append(kernel_ms(call, 1)[1])
+                st = vec.last_assign_stats()
+                fmt = lambda ts: " ".join(f"{t:8.3f}" for t in ts)                          # noqa: E731
+                say(f"{what:14s} {n:8d} {Q:5d}   {fmt(off)}   {fmt(on)}   {statistics.median(off) / statistics.median(on):6.2f}"
+                    f"  {st['candidates'] / max(st['filtered'], 1):11.2f}  {st['redone']:6d}")
+    vec.close()
+
+
+if FILTER_AB:
+    filter_ab()
+    out.close()
+    sys.exit(0)
+ab = open(os.environ.get("ASSIGN_AB", os.path.join(ROOT, "profiles", "assign_ab.txt")), "a")
 t0 = time.time()
 x = ib.make_corpus(N, seed=20260101, device=torch.device("cuda", 0))
 pq = ib.build_pq_index(x, m=12, K=1024, train_size=100000, iters=10, seed=2)
