@@ -289,6 +289,51 @@ def test_exact_calls(gpu, oracle, tabs, form):
         _sweep(gpu, "exact_assign", make, lambda h: h[0].assign(qs, sub), check, 4)
 
 
+# floors with option assign_filter (cluster.hip): asf_begin's asf_img + asf_work, then exact_assign's w_q, w_sub_rows, w_out_ids,
+# w_out_dist = 6; check_brackets = 16 adds asf_all and viol (ensure_viol) = 8; a 17-copy plateau (the redo runs) allocates nothing
+# more: the redo list is carved from asf_work = 6; cluster without a pq handle: asf_img + asf_work and w_sub_rows, w_rows, w_cand,
+# w_out_ids, w_out_dist, w_q, w_cnt, w_qc = 10
+@pytest.mark.parametrize("form", ["plain", "check", "plateau", "cluster"])
+def test_assign_filter(gpu, form):
+    import assign_filter_inputs as fi
+    x, ids, qs, tg, pos, _, _ = fi.list_cases(257)["17_in_tile0" if form == "plateau" else "16_in_tile0"]
+    n_rows = int((asm.rows_of(ids, tg) >= 0).sum())
+
+    def make():
+        idx = gpu.VectorIndex(ids, x)
+        idx.set_option("assign_filter", 1)
+        idx.set_option("check_brackets", 16 if form == "check" else 0)
+        return [idx]
+    if form == "cluster":
+        tokens = np.ascontiguousarray(ids[:300])
+        draws = np.random.default_rng(16).random(7 + 10 * 7 * 9)
+        off = Lazy(lambda: _cluster_off(gpu, ids, x, tokens, draws))
+
+        def check(r):
+            got, st = r
+            for g, e in zip(got, off()):
+                assert np.array_equal(np.asarray(g).view(np.uint32), np.asarray(e).view(np.uint32))
+            assert st["filtered"] == 10 * tokens.size, st
+        _sweep(gpu, "cluster, assign_filter on", make, lambda h: (h[0].cluster(tokens, 7, draws), h[0].last_assign_stats()), check, 10)
+        return
+    exp = Lazy(lambda: asm.exact_assign(ids, x, qs, tg))
+
+    def check(r):
+        got, st = r
+        assert asm.same(got, exp()), form
+        assert st["filtered"] == n_rows and st["redone"] == (len(pos) if form == "plateau" else 0), (form, st)
+        assert form != "check" or (st["violations"] == 0 and st["checked"] == n_rows * 257), st
+    _sweep(gpu, f"exact_assign, assign_filter on, {form}", make, lambda h: (h[0].assign(qs, tg), h[0].last_assign_stats()), check, 8 if form == "check" else 6)
+
+
+def _cluster_off(gpu, ids, x, tokens, draws):
+    idx = gpu.VectorIndex(ids, x)
+    try:
+        return idx.cluster(tokens, 7, draws)
+    finally:
+        idx.close()
+
+
 # floors of the filter chain behind options exact_filter_k and exact_wide (exact.hip): the mapped block hio_out and w_q
 # (exact_search_rows), exf_qfrag, exf_sample -- EXF_QT * n_sample floats, n_sample from filter_plan_k -- and exf_cand
 # (exact_filter_search), viol (ensure_viol) = 6; exf_small exists since the statistics were taken (pin time; exf_wide_set for a wide

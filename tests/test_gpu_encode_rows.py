@@ -111,6 +111,33 @@ def test_redo_of_crowded_items(oracle):
     vi.close()
 
 
+@pytest.mark.parametrize("name", ["16_in_tile0", "17_in_tile0", "16_in_last_tile", "17_in_last_tile", "compaction_12_then_10", "33_in_one_tile"])
+def test_list_mechanics_over_three_tiles(name):
+    """Steps b and c of encode_filter_kernel (the append `a - eps <= U`, the compaction `if (av - eps <= Urow)` of a list above ENC_KEEP,
+    `have > ENC_CAP`) at m = 6, S = 4, K = 300: 16 copies of the nearest centroid are filtered and the lowest index wins, 17 are redone,
+    in tile 0 and in the last tile; 12 farther copies in tile 0 are compacted away by 10 nearer ones in tile 1; 33 arrivals in one
+    tile are redone.  `redone` is the count tests/assign_filter_inputs.py predicts with the header's bracket (proven separated in
+    tests/test_assign_filter_inputs_cpu.py)."""
+    import assign_filter_inputs as fi
+    from freddy_amd import gpu
+    x, cb, winner, redone = fi.encode_cases()[name]
+    S = fi.ENC_D // fi.ENC_M
+    want = gpu.encode(cb, x)
+    vi = gpu.VectorIndex(np.arange(1, len(x) + 1, dtype=np.int32), x)
+    got = vi.encode_rows(cb)
+    st = vi.last_encode_stats()
+    assert _same(got[0], want[0]) and _same(got[1], want[1]), (name, st)
+    assert (got[1][list(fi.ENC_NEAR), fi.ENC_POS] == winner).all(), name
+    predicted = sum(int(fi.enc_predicted_redo(x[:, p * S:(p + 1) * S], cb[p]).sum()) for p in range(fi.ENC_M))
+    assert predicted == (len(fi.ENC_NEAR) if redone else 0)
+    assert st["redone"] == predicted and st["violations"] == 0 and st["items"] == len(x) * fi.ENC_M, (name, st)
+    vi.set_option("encode_refine_all", 1)                    # every bracket of the same input checked
+    again = vi.encode_rows(cb)
+    st = vi.last_encode_stats()
+    assert _same(again[1], want[1]) and st["redone"] == predicted and st["violations"] == 0 and st["checked"] > 0, (name, st)
+    vi.close()
+
+
 @pytest.mark.parametrize("kind", ["bad_rows", "nan_centroid_0", "nan_centroid_5", "nan_coarse", "scale_-40", "scale_20"])
 def test_non_finite_values_and_magnitudes(kind):
     from freddy_amd import gpu
