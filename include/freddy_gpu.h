@@ -881,13 +881,20 @@ int freddy_gpu_abi_version(void);
  *                0 = auto, the default: 1 below 16384 texts, 2 from there on), "assign_filter" (vector handles; also
  *                FREDDY_GPU_ASSIGN_FILTER at pin time: 1 = freddy_gpu_exact_assign and freddy_gpu_cluster without a pq handle assign
  *                as matrix-core filter + exact refine + redo, d <= 512; 0 = the all-exact kernel, the default; FREDDY_E_KIND on
- *                another kind of handle)
+ *                another kind of handle), "similarity_filter" (vector handles; also FREDDY_GPU_SIMILARITY_FILTER at pin time:
+ *                freddy_gpu_similarity_join as matrix-core filter + exact refine (csrc/similarity_filter.h) -- the same triples, order
+ *                and total, bit for bit: 1 = a pass in which more than 1 / 20 of the known pairs are candidates takes today's
+ *                kernels, 2 = never (tests, tools/similarity_filter_timing.py), 0 = today's kernels, the default; tables of fewer
+ *                than 16 or more than 512 dimensions take today's kernels with the option on; FREDDY_E_KIND on another kind of
+ *                handle)
  *   self-checks (tests):  "check_brackets" (bit 0: the scan keeps and the merge refines EVERY probed row, bit 1: the cell
  *                selection refines every cell, bit 2: exact kNN and the exact join refine every row -- each with its proven bracket compared with
  *                the reference's value: freddy_gpu_filter_bound_violations / _checked; bit 3: the exact analogy refines
  *                every row for every analogy, counted the same way; bit 4, value 16: with "assign_filter" the filter keeps every value and
  *                the refine compares every (target, centroid) bracket with the chain, counted the same way and in
- *                freddy_gpu_last_assign_stats), "join_host_traversal", "join_front_gather" (1, the
+ *                freddy_gpu_last_assign_stats; bit 5, value 32: with "similarity_filter" the filter keeps every value and every known
+ *                fit pair's bracket is compared with the chain, counted in freddy_gpu_filter_bound_violations / _checked),
+ *                "join_host_traversal", "join_front_gather" (1, the
  *                default: freddy_gpu_knn_join_ids gathers its queries in the sub-distance launch; 0: a gather launch, then the
  *                sub-distance kernel -- the same lists either way),
  *                "join_libm_margin_ppm", "grid_cus" (the CU count that every grid sized from the chip is planned with, and every

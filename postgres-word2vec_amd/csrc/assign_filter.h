@@ -210,6 +210,17 @@ __device__ __forceinline__ void asf_load8(const float* __restrict__ x, int j, in
   }
 }
 
+// the f16 split of eight elements scaled by sc (a power of two: exact): hi = f16(f), lo = f16(f - hi)
+__device__ __forceinline__ void asf_split8(const float (&v)[8], float sc, ench8& hi, ench8& lo) {
+#pragma unroll
+  for (int w = 0; w < 8; ++w) {
+    const float f = v[w] * sc;
+    const _Float16 hh = (_Float16)f;
+    hi[w] = hh;
+    lo[w] = (_Float16)(f - (float)hh);
+  }
+}
+
 template <int PF>
 __global__ __launch_bounds__(256) void assign_filter_kernel(AsfFilterArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char asf_smem[];
@@ -312,13 +323,7 @@ __global__ __launch_bounds__(256) void assign_filter_kernel(AsfFilterArgs a) {
     }
     const float sc = rsc[row];
     ench8 hi, lo;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-      const float f = v[w] * sc;   // (a power of two: exact)
-      const _Float16 hh = (_Float16)f;
-      hi[w] = hh;
-      lo[w] = (_Float16)(f - (float)hh);
-    }
+    asf_split8(v, sc, hi, lo);
     const int t = g8 >> 1, g = g8 & 1, l = (row & 31) + 32 * g;
     frag[((size_t)((row >> 5) * T + t) * 2 + 0) * 64 + l] = hi;
     frag[((size_t)((row >> 5) * T + t) * 2 + 1) * 64 + l] = lo;

@@ -60,6 +60,7 @@ Tuning read_tuning() {
   t.lane0_own = (int)env_int("FREDDY_GPU_LANE0_OWN", t.lane0_own);
   t.coarse_pieces = (int)env_int("FREDDY_GPU_COARSE_PIECES", t.coarse_pieces);
   t.assign_filter = env_int("FREDDY_GPU_ASSIGN_FILTER", t.assign_filter) != 0 ? 1 : 0;
+  t.similarity_filter = (int)std::min<int64_t>(2, std::max<int64_t>(0, env_int("FREDDY_GPU_SIMILARITY_FILTER", t.similarity_filter)));
 #ifdef FREDDY_LAB
   t.scan_prof = getenv("FREDDY_GPU_FUSED_PROF") != nullptr;
 #endif
@@ -296,6 +297,10 @@ extern "C" int freddy_gpu_set_option(freddy_gpu_index_t* ix, const char* name, i
   else if (n == "assign_filter") {
     if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "option assign_filter belongs to a vector handle");
     t.assign_filter = value != 0 ? 1 : 0;
+  }
+  else if (n == "similarity_filter") {
+    if (ix->kind != KIND_VEC) return fail(FREDDY_E_KIND, "option similarity_filter belongs to a vector handle");
+    t.similarity_filter = (int)std::min<int64_t>(2, std::max<int64_t>(0, value));
   }
   else if (n == "exact_wide_shape") t.exact_wide_shape = value == 1 || value == 2 ? (int)value : 0;
   else if (n == "resolve_block") t.resolve_block = (int)std::max<int64_t>(0, std::min<int64_t>(value, (int64_t)1 << 20));

@@ -116,11 +116,13 @@ struct Tuning {
   int tokenize_pass = 0;       // option tokenize_pass (set on the vector handle): texts per pass of the *_search_texts calls (tokenize.h): 0 = as many as a pinned block of 256 MiB holds
   int tokenize_unit = 0;       // option tokenize_unit: the sum of squares of freddy_gpu_tokenize's normalisation: 1 = a wave per text with lane 0 walking the chain (tok_unit_wave_kernel), 2 = a chain per lane over 64 texts (tok_unit_kernel), 0 = auto: 1 below 16384 texts, 2 from there on (tokenize.h)
   int assign_filter = 0;       // FREDDY_GPU_ASSIGN_FILTER / option assign_filter (vector handles): 1 = freddy_gpu_exact_assign and freddy_gpu_cluster without a pq handle assign as MFMA filter + exact refine + redo (assign_filter.h) for d <= 512; 0 = assign_exact_kernel for every pair
+  int similarity_filter = 0;   // FREDDY_GPU_SIMILARITY_FILTER / option similarity_filter (vector handles): freddy_gpu_similarity_join as MFMA filter + exact refine (similarity_filter.h) for 16 <= d <= 512: 1 = with the density fallback (a pass with more than 1 / SIMF_DENSE_DIV of its known pairs as candidates takes sim_matrix_kernel), 2 = never falling back (tests, the timing tool); 0 = sim_matrix_kernel for every pair
   int encode_refine_all = 0;   // option encode_refine_all (vector handles): freddy_gpu_encode_rows refines EVERY centroid of every item, so every (row, centroid) bracket is checked (encode_filter.h); 0 / 1
   int64_t similarity_pass_bytes = 0;   // option similarity_pass_bytes: the device result block of one pass of freddy_gpu_similarity_matrix / _join (similarity.h): 0 = 256 MiB, at most 4 GiB; 16 rows of A at least
   // -- self-checks (tests): bit 0 = the scan keeps every row and the merge refines every row (every probed row's bracket is checked),
   //    bit 1 = the cell selection refines every cell, bit 2 = exact kNN refines every row, bit 3 = the exact analogy refines every row,
-  //    bit 4 = the assignment filter keeps every value and its refine checks every (target, centroid) bracket
+  //    bit 4 = the assignment filter keeps every value and its refine checks every (target, centroid) bracket,
+  //    bit 5 = the similarity filter keeps every value and every known fit pair's bracket is checked against sim_matrix_kernel's chain
   int check_brackets = 0;
 #ifdef FREDDY_LAB
   int scan_prof = 0;           // FREDDY_GPU_FUSED_PROF (lab builds only): per-phase cycle sums of the scan kernel on stderr
